@@ -3,6 +3,7 @@
 fixed minibatch, 1/2/4/8 MI355X).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5] [--scaling weak|strong]
+                    [--full] [--dump-outputs DIR]
 
 Default workload (BASELINE.json configs[1]): sparse variational GP
 regression, 1-D UnitRBF, N = 1e6 synthetic points, M = 512 inducing points,
@@ -18,17 +19,21 @@ launched plainly (`python bench.py --gpus N`) it starts the N ranks itself -- fr
 `python -m torch.distributed.run` on 127.0.0.1, BEFORE anything in this process touches the GPU -- and exits
 with their return code.  `--gpus` must equal the world size (anything else is an error, rc 2).  Every rank owns a 1/N
 shard of the data; `--scaling weak` (default) keeps the per-GPU minibatch, `--scaling strong` keeps the GLOBAL
-minibatch and gives every rank 1/N of it; with N > 1 the line always carries the OTHER mode too, measured right
+minibatch and gives every rank 1/N of it; with N > 1 and --full the line also carries the OTHER mode, measured right
 after (`"also": {...}`).  The flat gradient is all-reduced over RCCL once per step (hb_allreduce_sum behind the C ABI).
 `--dry-run` runs the launch plumbing only (gloo process group, shard arithmetic, one all-reduce on CPU tensors)
 and prints the JSON skeleton with `n_gpus` = world size: the CPU test of the N > 1 launch path.
 
-Rank 0 prints ONE JSON line: the contract fields plus
+A plain run sets up, runs W warm-up steps, times EXACTLY K steps (wall clock between two device synchronisations),
+writes the outputs of the last one if --dump-outputs is given (dump_outputs), and rank 0 prints ONE JSON line: the
+contract fields (`value` = global minibatch x steps/s, `ms_per_step` = timed wall time / K) plus
+  "roofline_step" -- algorithmic flops of the whole step / measured step time / fp32 MFMA peak.
+--full measures, after that, what the headline does not need:
   "roofline"      -- the plan step with the largest share of the step time, FOUND AT RUN TIME (every step of the
                      plan is timed with HIP events on the plan's stream, back to back), priced with the work
                      model of its op against the fp32 MFMA peak or the HBM peak;
-  "roofline_step" -- algorithmic flops of the whole step / measured step time / fp32 MFMA peak;
-  "step_time_us"  -- median / min / max of per-step HIP-event intervals over the timed steps' replay;
+  "step_time_us"  -- median / min / max of per-step HIP-event intervals over a further replay of the steps;
+  "elbo_after"    -- the minibatch ELBO after those steps;
   "cpu_baseline"  -- the CPU oracle's restatement of the reference graph (torch-CPU fp32 + autograd + TF-formula
                      Adam) on ALL usable host cores, bounded sample (kind "port": TensorFlow is not available).
 """
@@ -238,6 +243,57 @@ def time_steps_standalone(plan, torch, iters=40):
     return out
 
 
+def run_time_roofline(plan, torch, args, itemsize, peak):
+    """(roofline, breakdown) of the plan step that dominates, found at run time: every step of the plan timed
+    stand-alone (time_steps_standalone) and the largest priced with the work model of its op."""
+    roofline, breakdown = None, None
+    try:
+        timed = time_steps_standalone(plan, torch)
+        total = sum(t for _, _, t in timed)
+        breakdown = {}
+        for lab, _, t in timed:
+            breakdown[lab] = round(breakdown.get(lab, 0.0) + t, 1)
+        breakdown = dict(sorted(breakdown.items(), key=lambda kv: -kv[1])[:14])
+        lab, node, us = max(timed, key=lambda r: r[2])
+        f, b, bound = work_model(node, itemsize) if node is not None else (0.0, 0.0, "hbm")
+        if bound == "mfma":
+            achieved, pk, unit = f / (us * 1e-6) * 1e-12, peak, "TFLOP/s"
+        else:
+            achieved, pk, unit = b / (us * 1e-6) * 1e-9, PEAK_HBM_GBS, "GB/s"
+        shapes = "" if node is None else " ".join("x".join(str(d) for d in t.shape) or "scalar" for t in node.inputs[:4])
+        traffic, traffic_src = None, None
+        try:
+            # the newest per-round table (tools/pmc_traffic.sh -> tools/make_traffic_json.py): PMC counters of an earlier
+            # run of this same command, regenerated with the kernels -- the source file is named in the line
+            import glob
+
+            tfile = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_pmc_traffic.json")))[-1]
+            with open(tfile) as fh:
+                pmc = json.load(fh)
+            rec = pmc.get(args.config, {}).get(lab)
+            if rec:
+                traffic = rec["traffic_bytes"]
+                traffic_src = "profiles/%s (%s)" % (os.path.basename(tfile), rec.get("kernel", lab))
+        except (OSError, KeyError, ValueError, IndexError):
+            pass
+        peaks_16bit = None
+        if bound == "mfma" and args.contraction == "bf16x3" and lab in ("sgp", "sgp_grad"):
+            # the M^2 n contractions run on the bf16 matrix pipe: SIX bf16 MFMAs (hi*hi, hi*mid, mid*hi, mid*mid, hi*lo, lo*hi)
+            # per fp32-equivalent product, so their own ceiling is the dense bf16 peak / 6; both fractions are reported
+            pk = PEAK_BF16_MFMA_TFLOPS / 6.0
+            peaks_16bit = {"bf16_dense_peak": PEAK_BF16_MFMA_TFLOPS, "divisor": 6, "frac_of_bf16x3_effective_peak": achieved / pk,
+                           "frac_of_16bit_peak": achieved / PEAK_BF16_MFMA_TFLOPS, "frac_of_fp32_mfma_peak": achieved / peak}
+        roofline = {"kernel": "%s [%s]" % (lab, shapes), "bound": bound, "achieved": achieved, "peak": pk, "unit": unit,
+                    "frac": achieved / pk, "traffic": traffic, "traffic_source": traffic_src, "avg_kernel_us": us,
+                    "share_of_step": us / total if total else None, "flops_per_launch": f,
+                    "algorithmic_bytes_per_launch": b, "bf16x3": peaks_16bit,
+                    "how": "largest of all plan steps, each timed stand-alone with HIP events on the plan's stream "
+                           "(%d back-to-back calls); a step may be a short chain of launches" % 40}
+    except Exception as e:  # never lose the headline over the diagnostics
+        roofline = {"error": repr(e)}
+    return roofline, breakdown
+
+
 def _free_port():
     import socket
 
@@ -286,6 +342,27 @@ def dry_run(args, world, rank):
     return 0 if ok else 1
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, model, plan):
+    """--dump-outputs: what the timed path hands back after its last step, in the run's dtype -- `params`, the raw
+    parameter vector the last Adam update wrote (what a caller of Optimizer.optimize reads its model from), and what
+    that step computed on the way: `grad`, d ELBO / d params, and `objective`, the minibatch ELBO.  The inputs are
+    seeded (data, initialisation, device RNG streams), so the same arguments give the same inputs in every run."""
+    import numpy as np
+
+    theta = model._session.theta
+    arrays = {"params": theta, "grad": plan.gflat[:theta.numel()], "objective": plan.buf(plan.objective).reshape(1)}
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -301,10 +378,18 @@ def main():
     ap.add_argument("--tri-pack", action="store_true", help="cfg3: keep the full-rank q_sqrt as its packed lower triangle")
     ap.add_argument("--dry-run", action="store_true", help="launch plumbing only (gloo, no GPU): see the module docstring")
     ap.add_argument("--no-also", action="store_true", help="N > 1: skip the second measurement in the other scaling mode")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-step event times, the ELBO after the run, "
+                         "the run-time roofline and step breakdown, the CPU baseline, and (N > 1) the other scaling mode")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
         return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args.gpus)       # parent of the ranks: no torch import, no GPU call in this process
@@ -370,20 +455,8 @@ def main():
 
     elapsed = timed_steps(n_local)
     plan = opt.last_plan
-
-    # per-step HIP-event intervals (one event per step on the plan's stream; all ranks take part in the steps)
-    ksteps = max(min(args.steps, 400), 20)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(ksteps + 1)]
-    with torch.cuda.stream(plan.stream):
-        for i in range(ksteps):
-            evs[i].record(plan.stream)
-            opt._run_steps(plan, 1)
-        evs[ksteps].record(plan.stream)
-        plan.stream.synchronize()
-    opt._check_step_failure(plan)
-    per = sorted(evs[i].elapsed_time(evs[i + 1]) * 1e3 for i in range(ksteps))
-    elbo_after = opt.run(minibatch_size=n_local)
-    barrier()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m, plan)
 
     # the exchange really spans `world` ranks (an RCCL communicator of another size would be a silent 1-GPU run)
     dp_ranks = 1
@@ -395,16 +468,31 @@ def main():
         assert dp_ranks == world, "data-parallel exchange spans %d ranks, expected %d" % (dp_ranks, world)
         assert getattr(plan, "dp_mode", "none") != "none", "N > 1 but the compiled step has no gradient exchange"
 
-    # N > 1: the other scaling mode, same protocol, right after (strong: global minibatch fixed, n / N per rank;
-    # weak: per-GPU minibatch fixed) -- north_star quotes a strong-scaling target, the contract line is weak by default
-    also = None
-    if world > 1 and not args.no_also:
-        other = "strong" if args.scaling == "weak" else "weak"
-        ng2 = cfg["n"] if other == "strong" else cfg["n"] * world
-        nl2 = ng2 // world
-        el2 = timed_steps(nl2)
-        also = {"scaling": other, "global_batch": ng2, "per_gpu_batch": nl2, "ms_per_step": el2 / args.steps * 1e3,
-                "value": args.steps / el2 * ng2, "unit": "samples/s", "steps_per_sec": args.steps / el2}
+    per, elbo_after, also = None, None, None
+    if args.full:
+        # per-step HIP-event intervals (one event per step on the plan's stream; all ranks take part in the steps)
+        ksteps = max(min(args.steps, 400), 20)
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(ksteps + 1)]
+        with torch.cuda.stream(plan.stream):
+            for i in range(ksteps):
+                evs[i].record(plan.stream)
+                opt._run_steps(plan, 1)
+            evs[ksteps].record(plan.stream)
+            plan.stream.synchronize()
+        opt._check_step_failure(plan)
+        per = sorted(evs[i].elapsed_time(evs[i + 1]) * 1e3 for i in range(ksteps))
+        elbo_after = opt.run(minibatch_size=n_local)
+        barrier()
+
+        # N > 1: the other scaling mode, same protocol, right after (strong: global minibatch fixed, n / N per rank;
+        # weak: per-GPU minibatch fixed) -- the contract line is weak by default, the strong-scaling figure rides beside it
+        if world > 1 and not args.no_also:
+            other = "strong" if args.scaling == "weak" else "weak"
+            ng2 = cfg["n"] if other == "strong" else cfg["n"] * world
+            nl2 = ng2 // world
+            el2 = timed_steps(nl2)
+            also = {"scaling": other, "global_batch": ng2, "per_gpu_batch": nl2, "ms_per_step": el2 / args.steps * 1e3,
+                    "value": args.steps / el2 * ng2, "unit": "samples/s", "steps_per_sec": args.steps / el2}
 
     if rank != 0:
         if world > 1:
@@ -417,53 +505,6 @@ def main():
     peak = PEAK_F32_MFMA_TFLOPS if args.dtype == "float32" else PEAK_F64_MFMA_TFLOPS
     flops_step = flops_fn(n_global)          # whole job, algorithmic
     flops_rank = flops_fn(n_local)           # what this rank's step computes
-
-    # ---- roofline of the step that dominates, found at run time
-    roofline, breakdown = None, None
-    try:
-        timed = time_steps_standalone(plan, torch)
-        total = sum(t for _, _, t in timed)
-        breakdown = {}
-        for lab, _, t in timed:
-            breakdown[lab] = round(breakdown.get(lab, 0.0) + t, 1)
-        breakdown = dict(sorted(breakdown.items(), key=lambda kv: -kv[1])[:14])
-        lab, node, us = max(timed, key=lambda r: r[2])
-        f, b, bound = work_model(node, itemsize) if node is not None else (0.0, 0.0, "hbm")
-        if bound == "mfma":
-            achieved, pk, unit = f / (us * 1e-6) * 1e-12, peak, "TFLOP/s"
-        else:
-            achieved, pk, unit = b / (us * 1e-6) * 1e-9, PEAK_HBM_GBS, "GB/s"
-        shapes = "" if node is None else " ".join("x".join(str(d) for d in t.shape) or "scalar" for t in node.inputs[:4])
-        traffic, traffic_src = None, None
-        try:
-            # the newest per-round table (tools/pmc_traffic.sh -> tools/make_traffic_json.py): PMC counters of an earlier
-            # run of this same command, regenerated with the kernels -- the source file is named in the line
-            import glob
-
-            tfile = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_pmc_traffic.json")))[-1]
-            with open(tfile) as fh:
-                pmc = json.load(fh)
-            rec = pmc.get(args.config, {}).get(lab)
-            if rec:
-                traffic = rec["traffic_bytes"]
-                traffic_src = "profiles/%s (%s)" % (os.path.basename(tfile), rec.get("kernel", lab))
-        except (OSError, KeyError, ValueError, IndexError):
-            pass
-        peaks_16bit = None
-        if bound == "mfma" and args.contraction == "bf16x3" and lab in ("sgp", "sgp_grad"):
-            # the M^2 n contractions run on the bf16 matrix pipe: SIX bf16 MFMAs (hi*hi, hi*mid, mid*hi, mid*mid, hi*lo, lo*hi)
-            # per fp32-equivalent product, so their own ceiling is the dense bf16 peak / 6; both fractions are reported
-            pk = PEAK_BF16_MFMA_TFLOPS / 6.0
-            peaks_16bit = {"bf16_dense_peak": PEAK_BF16_MFMA_TFLOPS, "divisor": 6, "frac_of_bf16x3_effective_peak": achieved / pk,
-                           "frac_of_16bit_peak": achieved / PEAK_BF16_MFMA_TFLOPS, "frac_of_fp32_mfma_peak": achieved / peak}
-        roofline = {"kernel": "%s [%s]" % (lab, shapes), "bound": bound, "achieved": achieved, "peak": pk, "unit": unit,
-                    "frac": achieved / pk, "traffic": traffic, "traffic_source": traffic_src, "avg_kernel_us": us,
-                    "share_of_step": us / total if total else None, "flops_per_launch": f,
-                    "algorithmic_bytes_per_launch": b, "bf16x3": peaks_16bit,
-                    "how": "largest of all plan steps, each timed stand-alone with HIP events on the plan's stream "
-                           "(%d back-to-back calls); a step may be a short chain of launches" % 40}
-    except Exception as e:  # never lose the headline over the diagnostics
-        roofline = {"error": repr(e)}
 
     out = {
         "metric": "elbo_samples_per_sec", "value": steps_per_sec * n_global, "unit": "samples/s",
@@ -479,19 +520,23 @@ def main():
                    "tri_pack": bool(args.tri_pack)},
         "steps_per_sec": steps_per_sec,
         "flops_per_step_algorithmic": flops_step,
-        "elbo_after": elbo_after,
-        "step_time_us": {"median": per[len(per) // 2], "min": per[0], "max": per[-1], "steps": ksteps,
-                         "how": "HIP events between consecutive steps on the plan's stream"},
-        "roofline": roofline,
         "roofline_step": {"bound": "mfma", "achieved": flops_rank / (ms_per_step * 1e-3) * 1e-12, "peak": peak,
                           "unit": "TFLOP/s", "frac": flops_rank / (ms_per_step * 1e-3) * 1e-12 / peak,
                           "what": "algorithmic flops of one rank's step / ms_per_step"},
-        "step_breakdown_us_standalone": breakdown,
     }
-    if also is not None:
-        out["also"] = also
-    if world == 1 and not args.no_cpu_baseline and args.config == "cfg2":
-        out["cpu_baseline"] = cpu_baseline(cfg)
+    if args.full:
+        roofline, breakdown = run_time_roofline(plan, torch, args, itemsize, peak)
+        out.update({
+            "elbo_after": elbo_after,
+            "step_time_us": {"median": per[len(per) // 2], "min": per[0], "max": per[-1], "steps": len(per),
+                             "how": "HIP events between consecutive steps on the plan's stream"},
+            "roofline": roofline,
+            "step_breakdown_us_standalone": breakdown,
+        })
+        if also is not None:
+            out["also"] = also
+        if world == 1 and not args.no_cpu_baseline and args.config == "cfg2":
+            out["cpu_baseline"] = cpu_baseline(cfg)
     print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

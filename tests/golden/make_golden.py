@@ -27,8 +27,10 @@ Every executed value is cross-checked against an independent loop-style numpy
 re-derivation (`_rederive_*` below, the round-1 generator) to 1e-14.
 
 The archive is written with fixed zip timestamps, so regenerating gives a
-byte-identical file (tests/test_oracle.py::test_golden_regenerates_byte_identically
-checks that whenever /root/reference is present).
+byte-identical file (`--check` compares a regeneration with the committed file;
+tests/test_oracle.py::test_golden_provenance_and_byte_identical_regeneration
+re-serialises the committed arrays and runs cross_checks() on them, without the
+reference).
 
 Run:  python tests/golden/make_golden.py [--check]
 """
@@ -161,12 +163,49 @@ def _same(a, b, tol=1e-14):
     return a.shape == b.shape and np.max(np.abs(a - b) / (1.0 + np.abs(b)), initial=0.0) <= tol
 
 
+def cross_checks(g):
+    """(executed value, independent re-derivation) pairs for every reference-executed array of the fixture `g`,
+    computed from the inputs stored beside it: build() checks them before writing, tests/test_oracle.py on the
+    committed file."""
+    checks = []
+    l1, l2 = g["k_l1"], g["k_l2"]
+    X, Xb = g["k_X"], g["k_Xb"]
+    for tag, a, b in (("XX", X, X), ("XX2", X, g["k_X2"]), ("b", Xb, Xb), ("b2", Xb, g["k_X2b"])):
+        checks += [(g["k_rbf1_" + tag], _rederive_rbf(a, b, l1)), (g["k_rbf2_" + tag], _rederive_rbf(a, b, l2)),
+                   (g["k_csym_" + tag], _rederive_csym(a, b, l1)), (g["k_sqdist2_" + tag], _rederive_sqdist(a, b, l2))]
+    checks += [(g["k_csym_diag"], 1.0 + np.exp(-2.0 * np.sum((X / l1) ** 2, axis=-1))),
+               (g["k_csym_diag_b"], 1.0 + np.exp(-2.0 * np.sum((Xb / l1) ** 2, axis=-1)))]
+    vx, sq_full, sq_diag = g["v_mu"], g["v_sq_full"], g["v_sq_diag"]
+    kl_full = 0.0
+    kl_diag = 0.0
+    for i in range(3):
+        kl_full += 0.5 * (-np.sum(np.log(np.square(np.diagonal(sq_full[i])))) - 10 + np.sum(np.square(sq_full[i])) + vx[i] @ vx[i])
+        kl_diag += 0.5 * (-2.0 * np.sum(sq_diag[i]) - 10 + np.sum(np.exp(2.0 * sq_diag[i])) + vx[i] @ vx[i])
+    checks += [(g["v_kl_full"], kl_full), (g["v_kl_diag"], kl_diag)]
+    sx, smu, sscale, snu = g["s_x"], g["s_mu"], g["s_scale"], g["s_nu"]
+    checks += [(g["d_logp1"], _rederive_student_t(g["d_b"], 0.0, 2.0, 3.0)),
+               (g["s_logp_nu3"], _rederive_student_t(sx, smu, sscale, 3.0)),
+               (g["s_logp_nuT"], _rederive_student_t(sx, smu, sscale, snu))]
+    tx = g["t_x"]
+    checks += [(g["t_log1pe"], np.log(1.0 + np.exp(tx)) + 1e-6), (g["t_exp"], np.exp(tx) + 1e-6)]
+    if "lt_vec" in g:
+        lx = g["lt_vec"].reshape(-1)
+        ref_tri = np.zeros((3, 4, 4))
+        for b in range(3):
+            k = 0
+            for i in range(4):
+                for j in range(i + 1):
+                    ref_tri[b, i, j] = lx[b * 10 + k]
+                    k += 1
+        checks += [(g["lt_tri"], ref_tri), (g["lt_back"], g["lt_vec"])]
+    return checks
+
+
 def build():
     ns, prov = load_reference_definitions()
     RefRBF, RefCsymRBF = ns["RefRBF"], ns["RefCsymRBF"]
     gaussian_KL, student_t_ref = ns["gaussian_KL"], ns["student_t_ref"]
     g = {}
-    checks = []
 
     # ---- kernels: reference draws (test_kernels.py:66-88), reference classes executed ----
     rng = np.random.RandomState(0)
@@ -183,14 +222,10 @@ def build():
         g["k_rbf2_" + tag] = k2.K(a, b)
         g["k_csym_" + tag] = k3.K(a, b)
         g["k_sqdist2_" + tag] = k2.square_dist(a, b)
-        checks += [(g["k_rbf1_" + tag], _rederive_rbf(a, b, l1)), (g["k_rbf2_" + tag], _rederive_rbf(a, b, l2)),
-                   (g["k_csym_" + tag], _rederive_csym(a, b, l1)), (g["k_sqdist2_" + tag], _rederive_sqdist(a, b, l2))]
     g["k_rbf_diag"] = k1.Kdiag(X)
     g["k_rbf_diag_b"] = k1.Kdiag(Xb)
     g["k_csym_diag"] = k3.Kdiag(X)
     g["k_csym_diag_b"] = k3.Kdiag(Xb)
-    checks += [(g["k_csym_diag"], 1.0 + np.exp(-2.0 * np.sum((X / l1) ** 2, axis=-1))),
-               (g["k_csym_diag_b"], 1.0 + np.exp(-2.0 * np.sum((Xb / l1) ** 2, axis=-1)))]
 
     # ---- variationals: reference draws (test_variationals.py:30-52) ----
     rng = np.random.RandomState(0)
@@ -219,12 +254,6 @@ def build():
     # analytic KL: the reference's gaussian_KL executed (it selects the branch with `is 'diagonal'`)
     g["v_kl_full"] = np.array(gaussian_KL(vx, sq_full, q_shape=sys.intern("fullrank")))
     g["v_kl_diag"] = np.array(gaussian_KL(vx, sq_diag, q_shape=sys.intern("diagonal")))
-    kl_full = 0.0
-    kl_diag = 0.0
-    for i in range(3):
-        kl_full += 0.5 * (-np.sum(np.log(np.square(np.diagonal(sq_full[i])))) - 10 + np.sum(np.square(sq_full[i])) + vx[i] @ vx[i])
-        kl_diag += 0.5 * (-2.0 * np.sum(sq_diag[i]) - 10 + np.sum(np.exp(2.0 * sq_diag[i])) + vx[i] @ vx[i])
-    checks += [(g["v_kl_full"], kl_full), (g["v_kl_diag"], kl_diag)]
     # closed-form KL on a second, batch-free set (used by the closed-form KL mode's tests)
     rng2 = np.random.RandomState(3)
     cmu = rng2.randn(1, 24) * 0.7
@@ -250,7 +279,7 @@ def build():
     cov_full = kg.K(xg, xg) - LnT.T @ LnT
     cov_diag = kg.Kdiag(xg) - np.sum(LnT * LnT, axis=0)
     g.update(g_z=z, g_ell=ell, g_x=xg, g_cholT=Lz.T, g_LnT=LnT, g_cov_full=cov_full, g_cov_diag=cov_diag)
-    checks += [(Kzx, _rederive_rbf(z, xg, ell))]
+    checks = [(Kzx, _rederive_rbf(z, xg, ell))]     # an intermediate: not stored, so not in cross_checks()
 
     # ---- densities (test_densities.py:11-75): student_t_ref executed ----
     rng = np.random.RandomState(0)
@@ -269,8 +298,6 @@ def build():
     g.update(s_x=sx, s_mu=smu, s_scale=sscale, s_nu=snu)
     g["s_logp_nu3"] = np.real(student_t_ref(sx, smu, sscale, 3.0))
     g["s_logp_nuT"] = np.real(student_t_ref(sx, smu, sscale, snu))
-    checks += [(lp1, _rederive_student_t(b, 0.0, 2.0, 3.0)), (g["s_logp_nu3"], _rederive_student_t(sx, smu, sscale, 3.0)),
-               (g["s_logp_nuT"], _rederive_student_t(sx, smu, sscale, snu))]
 
     # ---- log_sum_exp (test_tf_wraps.py:45-59; inline numpy in a TF body) ----
     rng = np.random.RandomState(0)
@@ -287,7 +314,6 @@ def build():
         y = np.asarray(tr.forward(tx), dtype=np.float64)
         g["t_" + key] = y
         g["t_" + key + "_back"] = np.asarray(tr.backward(y), dtype=np.float64)
-    checks += [(g["t_log1pe"], np.log(1.0 + np.exp(tx)) + 1e-6), (g["t_exp"], np.exp(tx) + 1e-6)]
 
     # ---- tri-pack element order: the reference's LowerTriangular.forward / backward executed (numpy only) ----
     if "LowerTriangular" in ns:
@@ -298,14 +324,6 @@ def build():
         g["lt_vec"] = lx.reshape(3, 10)
         g["lt_tri"] = np.ascontiguousarray(np.transpose(ly, (2, 0, 1)))   # [3, 4, 4] = vec_to_tri(lt_vec)
         g["lt_back"] = np.asarray(lt.backward(ly), dtype=np.float64).reshape(3, 10)
-        ref_tri = np.zeros((3, 4, 4))
-        for b in range(3):
-            k = 0
-            for i in range(4):
-                for j in range(i + 1):
-                    ref_tri[b, i, j] = lx[b * 10 + k]
-                    k += 1
-        checks += [(g["lt_tri"], ref_tri), (g["lt_back"], g["lt_vec"])]
 
     # ---- MLP (test_nn.py:11-29 shape pattern; the reference compares TF with TF, weights drawn here) ----
     rng = np.random.RandomState(0)
@@ -318,6 +336,7 @@ def build():
     g.update(n_x=nx, n_w1=w1, n_b1=b1, n_w2=w2, n_b2=b2)
     g["n_y"] = np.einsum("lni,lio->lno", h, w2) + b2
 
+    checks += cross_checks(g)
     for i, (got, want) in enumerate(checks):
         if not _same(got, want):
             raise AssertionError("reference-executed value #%d disagrees with its independent re-derivation" % i)

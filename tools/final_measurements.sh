@@ -6,11 +6,11 @@ o=gpurun_out/r4final
 mkdir -p $o
 tools/_bin/stream_peak > $o/stream_peak.txt 2>&1 || true
 tools/prof_bench.sh r4final/cfg2 --steps 200 --warmup 20 > /dev/null
-python bench.py --steps 200 --warmup 20 > $o/bench_cfg2.json 2> $o/bench_cfg2.err
-python bench.py --no-cpu-baseline --contraction bf16x3 --steps 200 --warmup 20 > $o/bench_cfg2_bf16x3.json 2>/dev/null
-for c in cfg3 cfg4 cfg5; do python bench.py --no-cpu-baseline --config $c --steps 50 --warmup 5 > $o/bench_$c.json 2>/dev/null; done
-python bench.py --no-cpu-baseline --config cfg5 --contraction bf16x3 --steps 50 --warmup 5 > $o/bench_cfg5_bf16x3.json 2>/dev/null
-python bench.py --no-cpu-baseline --config cfg3 --tri-pack --steps 50 --warmup 5 > $o/bench_cfg3_tripack.json 2>/dev/null
+python bench.py --full --steps 200 --warmup 20 > $o/bench_cfg2.json 2> $o/bench_cfg2.err
+python bench.py --full --no-cpu-baseline --contraction bf16x3 --steps 200 --warmup 20 > $o/bench_cfg2_bf16x3.json 2>/dev/null
+for c in cfg3 cfg4 cfg5; do python bench.py --full --no-cpu-baseline --config $c --steps 50 --warmup 5 > $o/bench_$c.json 2>/dev/null; done
+python bench.py --full --no-cpu-baseline --config cfg5 --contraction bf16x3 --steps 50 --warmup 5 > $o/bench_cfg5_bf16x3.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --config cfg3 --tri-pack --steps 50 --warmup 5 > $o/bench_cfg3_tripack.json 2>/dev/null
 tools/prof_bench.sh r4final/cfg4 --config cfg4 --steps 100 --warmup 10 > /dev/null
 tools/prof_bench.sh r4final/cfg5 --config cfg5 --steps 20 --warmup 3 > /dev/null
 python tools/dump_plan.py cfg5 --explain > $o/plan_cfg5.txt 2>/dev/null

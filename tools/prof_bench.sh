@@ -7,7 +7,7 @@ root=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 out=$root/gpurun_out/$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o bench -- python3 "$root/bench.py" --no-cpu-baseline "$@" > "$out/bench.json" 2> "$out/bench.err"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o bench -- python3 "$root/bench.py" --full --no-cpu-baseline "$@" > "$out/bench.json" 2> "$out/bench.err"
 f=$(find "$out" -name 'bench_kernel_stats.csv' | head -1)
 cp "$f" "$out/kernel_stats.csv"
 steps=$(python3 -c "import json,sys; d=json.load(open('$out/bench.json')); print(d['steps']+d['warmup']+d['step_time_us']['steps']+1)")
