@@ -75,6 +75,64 @@ class SparseGP(GP):
         noise = G.random_normal([N, 1, n]) if eps is None else G.as_tensor(eps)
         return G.add(samples, G.squeeze(G.matmul(noise, chol, transpose_b=True), [1]))
 
+    def predict_f(self, x, q, q_shape="diagonal"):
+        """Closed-form (mean, var) of the draw `samples(x, u, q_shape)` makes, u being the sample of the Variational `q`:
+        with A = Lm^-1 K(z, x) and u ~ N(m, S S^T),
+            mean = m A,   var = ||S^T A_j||^2 + r_j,
+        r = |kdiag - colsum(A^2)| ('diagonal', the |v| samples() takes the root of), 0 ('neglected'),
+        kdiag - colsum(A^2) + jitter ('fullrank': the diagonal of the covariance samples() factorises).
+        Both are graph tensors with the shape of samples()' output.  Not in the reference (its only route to a
+        prediction is averaging draws); in the spirit of GPflow's predict_f.  Forward only: gradients through either
+        output raise NotImplementedError.  `q` is read through its parameters -- no noise is drawn and the
+        Variational's per-trace draw is left alone.  A 2-D x with the UnitRBF kernel lowers to hb_sgp_predict (fused
+        streaming kernel or column chunks, settings.runtime.fused_predict); every other case is composed from generic
+        graph ops with the same semantics."""
+        assert q_shape in ["diagonal", "neglected", "fullrank"]
+        m, s, s_kind = _posterior_of(q)
+        x = G.as_tensor(x)
+        kern = self._kern()
+        z = self._z()
+        jitter = settings.numerics.jitter_level
+        if len(x.shape) == 2:
+            lead = tuple(z.shape[:-2])
+            if len(m.shape) < 2 or tuple(m.shape[:-2]) != lead or m.shape[-1] != z.shape[-2]:
+                raise ValueError("predict_f: the variational's shape %s does not match [.., P, %d] for z %s"
+                                 % (tuple(m.shape), z.shape[-2], tuple(z.shape)))
+            if isinstance(kern, UnitRBF):
+                return G.sgp_predict(x, z, kern._ell(), kern.Cholesky(z), m, s, mode=q_shape, s_kind=s_kind, jitter=jitter)
+        return self._predict_generic(x, m, s, s_kind, q_shape, jitter)
+
+    def _predict_generic(self, x, m, s, s_kind, q_shape, jitter):
+        """predict_f composed from generic graph ops (non-RBF kernels, 3-D x), the way samples() composes its draw."""
+        LnT = self._effective_LT(x)                       # 2-D x: [.., M, n];  3-D x [N, n, d]: [N, M, n]
+        A2 = G.reduce_sum(G.square(LnT), -2)              # [.., n] / [N, n]
+        kd = self._kern().Kdiag(x)
+        if len(x.shape) == 2:
+            P, M = m.shape[-2], m.shape[-1]
+            lead = tuple(m.shape[:-2])
+            mean = G.matmul(m, LnT)
+            if s_kind == "diag":
+                var = G.matmul(G.square(s), G.square(LnT))
+            else:
+                R = s.shape[-1]
+                A4 = G.broadcast_to(G.expand_dims(LnT, -3), lead + (P, M, LnT.shape[-1]))
+                C = G.matmul(G.reshape(s, lead + (P, M, R)), A4, transpose_a=True)     # S_ep^T A_e  [.., P, R, n]
+                var = G.reduce_sum(G.square(C), -2)
+            kd, A2 = G.expand_dims(kd, -2), G.expand_dims(A2, -2)
+        else:
+            N, M = m.shape[0], m.shape[-1]
+            mean = G.squeeze(G.matmul(G.expand_dims(m, 1), LnT), [1])
+            if s_kind == "diag":
+                var = G.squeeze(G.matmul(G.expand_dims(G.square(s), 1), G.square(LnT)), [1])
+            else:
+                C = G.matmul(G.reshape(s, [N, M, s.shape[-1]]), LnT, transpose_a=True)  # [N, R, n]
+                var = G.reduce_sum(G.square(C), -2)
+        if q_shape == "diagonal":
+            var = G.add(var, G.unary("ABS", G.sub(kd, A2)))
+        elif q_shape == "fullrank":
+            var = G.add(var, G.affine(G.sub(kd, A2), 1.0, jitter))
+        return mean, var
+
     def _effective_LT(self, x):
         """Lm^{-1} K(z, x) (reference gp/gp.py:146-174)."""
         x = G.as_tensor(x)
@@ -94,3 +152,39 @@ class SparseGP(GP):
         if q_shape == "diagonal":
             return G.sub(kern.Kdiag(x), G.reduce_sum(G.square(LnT), -2))
         return G.sub(kern.K(x), G.matmul(LnT, LnT, transpose_a=True))
+
+
+def _posterior_of(q):
+    """(m, s, s_kind) of u ~ N(m, S S^T) for the Variational whose sample samples() consumes, as graph tensors read from
+    its parameters (never from its sample): m shaped like the sample; s = the standard deviations (s_kind 'diag') or the
+    dense lower-triangular factor [size, size] ('tril').  Gaussian: m = scale m, S = diag(scale) S."""
+    from .. import transforms
+    from ..variationals import Gaussian, Normal, Variational
+
+    if isinstance(q, (G.Tensor, np.ndarray)) or not isinstance(q, Variational):
+        raise TypeError("predict_f needs the Variational object itself, not a sample of it (got %s): call predict_f "
+                        "outside tf_mode, or pass object.__getattribute__(model, 'u')" % type(q).__name__)
+    if type(q) not in (Normal, Gaussian):
+        raise NotImplementedError("predict_f: closed-form moments for %s are not implemented (Normal and Gaussian only)"
+                                  % type(q).__name__)
+    if q.is_local:
+        raise NotImplementedError("predict_f: a LOCAL variational (fed by an encoder) has no closed-form prediction here")
+    if q.n_layers or q.n_batch is not None:
+        raise NotImplementedError("predict_f: variationals with n_layers / n_batch are not supported")
+    if not isinstance(q.transform, transforms.Identity):
+        raise NotImplementedError("predict_f: the moments are closed-form only for the Identity transform")
+    mu, sq = q._raw_params()
+    shape = list(q._shape)
+    m = G.reshape(mu, shape)
+    scale = object.__getattribute__(q, "scale").tensor() if type(q) is Gaussian else None
+    if q.q_shape == "diagonal":
+        s, kind = G.reshape(G.unary("EXP", sq), shape), "diag"
+        if scale is not None:
+            s = G.mul(scale, s)
+    else:
+        s, kind = (q._dense_sqrt(sq) if q.packed else G.band_part(sq, -1, 0)), "tril"
+        if scale is not None:
+            s = G.mul(G.reshape(G.broadcast_to(scale, shape), [q.size, 1]), s)
+    if scale is not None:
+        m = G.mul(scale, m)
+    return m, s, kind

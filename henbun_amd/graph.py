@@ -1160,12 +1160,15 @@ def _cholesky_emit(plan, node):
         users = list(plan._consumers.get(inv_node.outputs[0], ()))
         users += [c2 for c in users if c.op == "stop_gradient" for c2 in plan._consumers.get(c.outputs[0], ())]
         bf3 = False
-        if plan.dtype == plan.torch.float32 and M % 32 == 0 and M >= 32 and any(c.op in ("sgp", "sgp_grad") for c in users):
+        if plan.dtype == plan.torch.float32 and M % 32 == 0 and M >= 32 and any(c.op in ("sgp", "sgp_grad", "sgp_predict")
+                                                                                for c in users):
             from ._settings import settings as _st
 
             # settings.numerics.contraction = bf16x3: the M^2 n contractions take three-term bf16 operands
-            # (fp32-level accuracy at the bf16 MFMA rate, include/henbun_hip.h HB_PREC_BF16X3); M <= 512 only
-            bf3 = str(getattr(_st.numerics, "contraction", "native")) == "bf16x3" and M <= 512
+            # (fp32-level accuracy at the bf16 MFMA rate, include/henbun_hip.h HB_PREC_BF16X3); M <= 512 only.
+            # Not requested by sgp_predict: prediction runs in native precision only.
+            bf3 = (str(getattr(_st.numerics, "contraction", "native")) == "bf16x3" and M <= 512
+                   and any(c.op in ("sgp", "sgp_grad") for c in users))
             frag = plan.scratch(((5 if bf3 else 2) * max(int(np.prod(node.outputs[0].shape)), 1),))
             plan._wfrag[inv_node.outputs[0]] = (frag, bf3)
         # launch 0 of the 64-column chain hosts pending side jobs (minibatch gather, the sample of q(u))
@@ -1869,6 +1872,59 @@ def _sgp_grad_emit(plan, node):
 
 defop("sgp", _sgp_emit, _sgp_vjp)
 defop("sgp_grad", _sgp_grad_emit, None)
+
+SGP_PREDICT_MODES = {"neglected": 0, "diagonal": 1, "fullrank": 2}
+SGP_PREDICT_S = {"diag": 0, "tril": 1}
+
+
+def sgp_predict(x, z, ell, L, m, s, mode="diagonal", s_kind="diag", jitter=0.0) -> Tuple[Tensor, Tensor]:
+    """Closed-form first two moments of sgp_samples' draw (the fused SparseGP.predict_f for the UnitRBF kernel and a 2-D
+    x): with A = L^-1 K(z, x) and u ~ N(m, S S^T),
+        mean = m A                          [.., P, n]
+        var  = ||S_p^T A_j||^2 + r_j        [.., P, n],  r = |1 - colsum(A^2)| ('diagonal'), 0 ('neglected'),
+                                                        1 - colsum(A^2) + jitter ('fullrank')
+    m [.., P, M]; s: standard deviations [.., P, M] (s_kind 'diag') or one lower-triangular [R, R], R = E P M ('tril').
+    Forward only (include/henbun_hip.h hb_sgp_predict_*)."""
+    x, z, ell, L, m, s = (as_tensor(t) for t in (x, z, ell, L, m, s))
+    W = stop_gradient(trinv(L))
+    lead, P, n = z.shape[:-2], m.shape[-2], x.shape[-2]
+    if tuple(m.shape) != tuple(lead) + (P, z.shape[-2]):
+        raise ValueError("sgp_predict: m must be %s, got %s" % (tuple(lead) + (P, z.shape[-2]), tuple(m.shape)))
+    nd = make("sgp_predict", (x, z, ell, L, W, m, s), {"mode": mode, "s_kind": s_kind, "jitter": float(jitter)},
+              [lead + (P, n), lead + (P, n)])
+    return nd.outputs[0], nd.outputs[1]
+
+
+def _sgp_predict_emit(plan, node):
+    H = plan.H
+    x, z, ell, _, W, m, s = (plan.buf(t) for t in node.inputs)
+    mean, var = (plan.out(t) for t in node.outputs)
+    zsh, xsh = node.inputs[1].shape, node.inputs[0].shape
+    E, M, n, d, P = int(np.prod(zsh[:-2])) if len(zsh) > 2 else 1, zsh[-2], xsh[-2], xsh[-1], node.inputs[5].shape[-2]
+    s_kind = SGP_PREDICT_S[node.attrs["s_kind"]]
+    wfrag, bf3 = plan._wfrag.get(_through_stop_gradient(node.inputs[4]), (None, False))
+    from ._settings import settings as _st
+
+    want = bool(getattr(_st.runtime, "fused_predict", True))
+    fused = want and H.sgp_predict_fused(plan.dtype, E, n, M, d, P, s_kind, wfrag is not None)
+    plan.note("fused streaming prediction (hb_sgp_predict, one strip kernel)", node, fused,
+              "settings.runtime.fused_predict is off" if not want else
+              "needs fp32, the fragment-major W images, M % 32 == 0, 32 <= M <= 512, d <= 4, P <= 4 and a full-rank S "
+              "only for one latent function: column chunks (hb_sgp_A + hb_matmul + column statistics)")
+    wf = wfrag if fused else None
+    ws = plan.scratch((max(H.sgp_predict_ws_elems(plan.dtype, E, n, M, d, P, s_kind, wf is not None), 1),))
+    mode, jit = SGP_PREDICT_MODES[node.attrs["mode"]], node.attrs["jitter"]
+    plan.steps.append(lambda: H.sgp_predict(x, z, ell, W, m, s, s_kind=s_kind, mode=mode, jitter=jit, out=(mean, var),
+                                            wfrag=wf, ws=ws))
+
+
+def _sgp_predict_vjp(node, gs):
+    if any(g is not None for g in gs):
+        raise NotImplementedError("sgp_predict (SparseGP.predict_f) is forward-only: no gradient through its mean or variance")
+    return [None] * len(node.inputs)
+
+
+defop("sgp_predict", _sgp_predict_emit, _sgp_predict_vjp)
 
 
 # ------------------------------------------------------------------------------

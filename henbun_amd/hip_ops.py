@@ -37,7 +37,8 @@ MM_SYM_OUT = 8
 MM_SYMLOW_OUT = 32
 MM_ACTGRAD = 16
 ACT = dict(none=0, sigmoid=1, relu=2, tanh=3)
-SGP_NEGLECTED, SGP_DIAGONAL = 0, 1
+SGP_NEGLECTED, SGP_DIAGONAL, SGP_FULLRANK = 0, 1, 2
+SGP_S_DIAG, SGP_S_TRIL = 0, 1
 MATUTIL_BAND, MATUTIL_ADD_EYE, MATUTIL_PHI, MATUTIL_SYM = 0, 1, 2, 3
 
 WS_ELEMS = 1 << 16  # generic scratch (elements) for reductions / KL partials
@@ -1031,6 +1032,41 @@ def sgp_A(x, z, ell, W, out=None, wfrag=None, prec=PREC_NATIVE):
     _lib.lib().call("hb_sgp_A" + _suf(x), KERN_RBF, _p(x), sx, _p(z), _p(ell), ell.numel() // E, _p(W), _p(wfrag), int(prec),
                     _p(out), E, n, M, d, stream())
     return out
+
+
+def sgp_predict_fused(dtype, E, n, M, d, P, s_kind, has_wfrag):
+    """True when hb_sgp_predict runs its fused streaming kernel for these extents (the rule of csrc/sgp_predict.hip,
+    pred_is_fused): fp32 with the fragment-major W images, M % 32 == 0, 32 <= M <= 512, d <= 4, P <= 4, and a full-rank
+    S only for one latent function of one expert.  Everything else runs in column chunks."""
+    return (dtype == torch.float32 and bool(has_wfrag) and 32 <= M <= 512 and M % 32 == 0 and 1 <= d <= 4 and 1 <= P <= 4
+            and n > 0 and 1 <= E <= 65535 and (s_kind == SGP_S_DIAG or E * P == 1))
+
+
+def sgp_predict_ws_elems(dtype, E, n, M, d, P, s_kind, has_wfrag):
+    """Scratch elements hb_sgp_predict needs (bounded by one column chunk, not by n)."""
+    return int(_lib.lib().raw("hb_sgp_predict_ws_elems")(int(E), int(n), int(M), int(d), int(P), int(s_kind),
+                                                         int(bool(has_wfrag)), 4 if dtype == torch.float32 else 8))
+
+
+def sgp_predict(x, z, ell, W, m, s, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, jitter=0.0, out=None, wfrag=None, ws=None):
+    """Closed-form predictive moments (mean[E?,P,n], var[E?,P,n]) of sgp_fwd's draw for u ~ N(m, S S^T) (hb_sgp_predict).
+    m [E?, P, M]; s: standard deviations [E?, P, M] (SGP_S_DIAG) or ONE lower-triangular [R, R], R = E P M (SGP_S_TRIL).
+    `wfrag`: cholesky_inverse's fragment-major images of W (the fused form needs them; None: chunked form)."""
+    for t in (x, z, ell, W, m, s):
+        _chk(t)
+    E, n, M, d, P, sx = _sgp_dims(x, z, m)
+    lead = (E,) if z.dim() == 3 else ()
+    dev, dt = x.device, x.dtype
+    if out is None:
+        mean = _empty(lead + (P, n), dtype=dt, device=dev)
+        var = _empty(lead + (P, n), dtype=dt, device=dev)
+    else:
+        mean, var = out
+    if ws is None:
+        ws = workspace(dt, dev, max(sgp_predict_ws_elems(dt, E, n, M, d, P, s_kind, wfrag is not None), 1))
+    _lib.lib().call("hb_sgp_predict" + _suf(x), KERN_RBF, _p(x), sx, _p(z), _p(ell), ell.numel() // E, _p(W), _p(wfrag), _p(m),
+                    _p(s), int(s_kind), int(mode), float(jitter), _p(mean), _p(var), E, n, M, d, P, _p(ws), stream())
+    return mean, var
 
 
 def sgp_bwd(x, z, ell, W, u, eps, A, v, fbar, mode=SGP_DIAGONAL, need_xbar=False, out=None, wfrag=None,

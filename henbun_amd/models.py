@@ -33,6 +33,31 @@ class SVGP(hb.model.Model):
         ll = tf.reduce_sum(hb.densities.gaussian(tf.transpose(self.Y), f, self.var))
         return (self.N / n) * ll - self.KL()
 
+    def _predict(self, Xnew, noise):
+        """One plan with both outputs: (mean sqrt(k_var), var k_var [+ var of the likelihood]) at Xnew, as numpy."""
+        Xnew = np.asarray(Xnew)
+        q = object.__getattribute__(self, "u")
+        self.initialize()
+        with self.tf_mode():
+            mean, var = self.gp.predict_f(Xnew, q, q_shape=self.residual)
+            mean = mean * tf.sqrt(self.k_var)
+            var = var * self.k_var
+            if noise:
+                var = var + self.var
+        plan = self._session.make_plan([mean, var])
+        plan.run()
+        plan.check()
+        return plan.value(plan.outputs[0]), plan.value(plan.outputs[1])
+
+    def predict_f(self, Xnew):
+        """Closed-form posterior mean and variance of the latent f at Xnew [n, 1]: arrays [1, n] (SparseGP.predict_f
+        scaled by k_var, the model's ELBO convention f = samples * sqrt(k_var))."""
+        return self._predict(Xnew, False)
+
+    def predict_y(self, Xnew):
+        """predict_f plus the Gaussian likelihood's variance: the predictive of a new observation y at Xnew."""
+        return self._predict(Xnew, True)
+
 
 class Amortised(hb.model.Model):
     """cfg 4: NeuralNet encoder -> LOCAL Normal -> linear Gaussian decoder."""

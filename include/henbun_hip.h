@@ -42,7 +42,9 @@ extern "C" {
  * bumped it and did not); 2 = round 4: hb_debug_set / hb_debug_clear, hb_cholesky_inverse_ws_elems and the workspace
  * contract of hb_cholesky_inverse_f32 (exchange + sync area, zero-filled once by its owner); added without changing an
  * existing signature: hb_cholesky_persistent_shape, hb_gram_cholesky_inverse_f32, hb_mlp2_sample_*, hb_matmul_gauss_*,
- * hb_matmul_gram_vjp_*, hb_gram_ell_fold_*, hb_sgp_rider_*, hb_fullrank_sample_kl_fwd1_* / hb_fullrank_one_launch_shape. */
+ * hb_matmul_gram_vjp_*, hb_gram_ell_fold_*, hb_sgp_rider_*, hb_fullrank_sample_kl_fwd1_* / hb_fullrank_one_launch_shape.
+ * Still 2 after additions that change no existing signature: hb_sgp_predict_f32 / _f64, hb_sgp_predict_ws_elems and the
+ * enum values HB_SGP_FULLRANK, HB_SGP_S_DIAG, HB_SGP_S_TRIL (closed-form predictive moments). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -455,7 +457,8 @@ int hb_trinv_f64(const double* L, double* W, long B, long M, double* ws, void* s
 
 /* ---- K5/K6: fused sparse-GP conditional (reference gp/gp.py:99-143 samples,
  *      :146-162 _effective_LT, :177-189 _additional_cov 'diagonal') -------- */
-enum { HB_SGP_NEGLECTED = 0, HB_SGP_DIAGONAL = 1 };
+enum { HB_SGP_NEGLECTED = 0, HB_SGP_DIAGONAL = 1, HB_SGP_FULLRANK = 2 /* hb_sgp_predict_* only */ };
+enum { HB_SGP_S_DIAG = 0, HB_SGP_S_TRIL = 1 };   /* the posterior factor S of hb_sgp_predict_* */
 /* Operand precision of the M^2 n contraction.  NATIVE: the arithmetic type (fp32 / fp64 MFMA).  BF16X3 (fp32
  * only; BASELINE cfg 5's "fp16-with-fp32-accum" variant in a usable form): every fp32 operand is split into three
  * bf16 terms and the six significant cross products run on v_mfma_f32_32x32x16_bf16 with fp32 accumulation --
@@ -552,6 +555,30 @@ int hb_sgp_A_f32(int kind, const float* x, long sx, const float* z, const float*
 int hb_sgp_A_f64(int kind, const double* x, long sx, const double* z, const double* ell, long dl,
                  const double* W, const double* Wfrag, int prec, double* A, long E, long n, long M,
                  long d, void* stream);
+/* Closed-form predictive moments of the sparse-GP conditional (csrc/sgp_predict.hip; not in the reference, whose only
+ * route to a prediction is Monte-Carlo draws of gp/gp.py:99-143).  For the draw f = u^T A + residual of hb_sgp_fwd with
+ * u ~ N(m, S S^T), per expert e, latent function p and column j:
+ *   mean[e,p,j] = m_ep^T A_j
+ *   var [e,p,j] = || S_ep^T A_j ||^2 + r_j,   r_j = |1 - sum_m A_mj^2|       (mode HB_SGP_DIAGONAL)
+ *                                                  0                          (HB_SGP_NEGLECTED)
+ *                                                  1 - sum_m A_mj^2 + jitter  (HB_SGP_FULLRANK: the diagonal of the
+ *                                                  residual covariance whose Cholesky factor samples() draws with)
+ * computed from A itself (never as a quadratic form in Kmm^-1, which cancels in fp32).  m [E, P, M].  s_kind
+ * HB_SGP_S_DIAG: s [E, P, M] holds the standard deviations (diagonal S).  HB_SGP_S_TRIL: s is ONE lower-triangular
+ * [R, R] matrix, R = E P M, its strict upper triangle zero; row (e P + p) M + i is the coefficient row of u[e, p, i],
+ * so S_ep = s[(e P + p) M .. + M, 0 .. R].  x, sx, z, ell, dl, W, Wfrag as for hb_sgp_fwd.  Forward only.
+ * With Wfrag, fp32, M % 32 == 0, 32 <= M <= 512, d <= 4, P <= 4 (HB_SGP_S_TRIL: E P == 1) ONE kernel per call: one
+ * workgroup per 32-column strip forms A and (full rank) S^T A in registers / LDS and writes only mean and var.  Every other
+ * shape runs chunked: columns in chunks of at most 32768, per chunk hb_sgp_A_*, (full rank) hb_matmul_*, one column-
+ * statistics kernel.  ws >= hb_sgp_predict_ws_elems(E, n, M, d, P, s_kind, Wfrag != NULL, sizeof(T)) elements (16-byte
+ * aligned; independent of n beyond one chunk). */
+long hb_sgp_predict_ws_elems(long E, long n, long M, long d, long P, int s_kind, int has_wfrag, int dtype_bytes);
+int hb_sgp_predict_f32(int kind, const float* x, long sx, const float* z, const float* ell, long dl, const float* W,
+                       const float* Wfrag, const float* m, const float* s, int s_kind, int mode, double jitter, float* mean,
+                       float* var, long E, long n, long M, long d, long P, float* ws, void* stream);
+int hb_sgp_predict_f64(int kind, const double* x, long sx, const double* z, const double* ell, long dl, const double* W,
+                       const double* Wfrag, const double* m, const double* s, int s_kind, int mode, double jitter,
+                       double* mean, double* var, long E, long n, long M, long d, long P, double* ws, void* stream);
 /* VJP given fbar [E,P,n]:
  *   Abar = u^T fbar + A diag(c),  c = -eps sign(v)/sqrt|v| * sum_p fbar_p
  *   Kbar = W^T Abar            [E,M,n]  (scratch output, kept for Lbar)
