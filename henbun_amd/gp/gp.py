@@ -75,7 +75,7 @@ class SparseGP(GP):
         noise = G.random_normal([N, 1, n]) if eps is None else G.as_tensor(eps)
         return G.add(samples, G.squeeze(G.matmul(noise, chol, transpose_b=True), [1]))
 
-    def predict_f(self, x, q, q_shape="diagonal"):
+    def predict_f(self, x, q, q_shape="diagonal", full_cov=False):
         """Closed-form (mean, var) of the draw `samples(x, u, q_shape)` makes, u being the sample of the Variational `q`:
         with A = Lm^-1 K(z, x) and u ~ N(m, S S^T),
             mean = m A,   var = ||S^T A_j||^2 + r_j,
@@ -86,21 +86,59 @@ class SparseGP(GP):
         output raise NotImplementedError.  `q` is read through its parameters -- no noise is drawn and the
         Variational's per-trace draw is left alone.  A 2-D x with the UnitRBF kernel lowers to hb_sgp_predict (fused
         streaming kernel or column chunks, settings.runtime.fused_predict); every other case is composed from generic
-        graph ops with the same semantics."""
+        graph ops with the same semantics.
+
+        full_cov=True returns (mean, cov) instead: the same mean tensor and cov [.., P, n, n], the exact covariance of
+        that draw,
+            cov_p = A^T S_p S_p^T A + K(x, x) - A^T A + jitter I   ('fullrank': what samples() factorises, plus u)
+                  = A^T S_p S_p^T A + diag(|kdiag - colsum(A^2)|)  ('diagonal': independent residuals)
+                  = A^T S_p S_p^T A                                ('neglected'),
+        so diag(cov) == var.  A 2-D x with UnitRBF and a diagonal S, or a full-rank S for one latent function of one
+        expert, lowers to hb_sgp_predict_cov (bitwise symmetric) while settings.runtime.fused_predict is on; everything
+        else is composed from generic graph ops.  3-D x raises NotImplementedError."""
         assert q_shape in ["diagonal", "neglected", "fullrank"]
         m, s, s_kind = _posterior_of(q)
         x = G.as_tensor(x)
         kern = self._kern()
         z = self._z()
         jitter = settings.numerics.jitter_level
+        if full_cov and len(x.shape) != 2:
+            raise NotImplementedError("predict_f(full_cov=True) takes a 2-D x [n, d] only (got %s)" % (tuple(x.shape),))
         if len(x.shape) == 2:
             lead = tuple(z.shape[:-2])
             if len(m.shape) < 2 or tuple(m.shape[:-2]) != lead or m.shape[-1] != z.shape[-2]:
                 raise ValueError("predict_f: the variational's shape %s does not match [.., P, %d] for z %s"
                                  % (tuple(m.shape), z.shape[-2], tuple(z.shape)))
             if isinstance(kern, UnitRBF):
-                return G.sgp_predict(x, z, kern._ell(), kern.Cholesky(z), m, s, mode=q_shape, s_kind=s_kind, jitter=jitter)
-        return self._predict_generic(x, m, s, s_kind, q_shape, jitter)
+                mean, var = G.sgp_predict(x, z, kern._ell(), kern.Cholesky(z), m, s, mode=q_shape, s_kind=s_kind,
+                                          jitter=jitter)
+                if not full_cov:
+                    return mean, var
+                P = m.shape[-2]
+                E = int(np.prod(lead)) if lead else 1
+                if bool(getattr(settings.runtime, "fused_predict", True)) and (s_kind == "diag" or E * P == 1):
+                    return mean, G.sgp_predict_cov(x, z, kern._ell(), kern.Cholesky(z), s, P, mode=q_shape,
+                                                   s_kind=s_kind, jitter=jitter)
+                return mean, self._predict_cov_generic(x, m, s, s_kind, q_shape, jitter)
+        mean, var = self._predict_generic(x, m, s, s_kind, q_shape, jitter)
+        if not full_cov:
+            return mean, var
+        return mean, self._predict_cov_generic(x, m, s, s_kind, q_shape, jitter)
+
+    def predict_f_samples(self, x, q, num_samples, q_shape="fullrank"):
+        """num_samples joint posterior draws at x, [.., P, num_samples, n]: mean + eps L^T with (mean, cov) of
+        predict_f(x, q, q_shape, full_cov=True), L = cholesky(cov) and a fresh standard-normal eps every run.  'neglected'
+        raises ValueError (its cov has rank at most the number of inducing points).  A cov that is not positive definite
+        reports through plan.check() like every factorisation: fp32 draws on a grid much denser than the lengthscale
+        need a larger settings.numerics.jitter_level.  Forward only; no draw is taken from q."""
+        if q_shape == "neglected":
+            raise ValueError("predict_f_samples: the 'neglected' covariance A^T S S^T A has rank at most M and cannot be "
+                             "factorised; use 'fullrank' or 'diagonal'")
+        mean, cov = self.predict_f(x, q, q_shape=q_shape, full_cov=True)
+        chol = G.cholesky(cov)                                              # [.., P, n, n]
+        S, n = int(num_samples), cov.shape[-1]
+        eps = G.random_normal(tuple(cov.shape[:-2]) + (S, n))               # [.., P, S, n]
+        return G.add(G.expand_dims(mean, -2), G.matmul(eps, chol, transpose_b=True))
 
     def _predict_generic(self, x, m, s, s_kind, q_shape, jitter):
         """predict_f composed from generic graph ops (non-RBF kernels, 3-D x), the way samples() composes its draw."""
@@ -132,6 +170,25 @@ class SparseGP(GP):
         elif q_shape == "fullrank":
             var = G.add(var, G.affine(G.sub(kd, A2), 1.0, jitter))
         return mean, var
+
+    def _predict_cov_generic(self, x, m, s, s_kind, q_shape, jitter):
+        """predict_f(full_cov=True)'s covariance [.., P, n, n] composed from generic graph ops (2-D x): other kernels, a
+        full-rank S for several latent functions, settings.runtime.fused_predict = False."""
+        LnT = self._effective_LT(x)                       # [.., M, n]
+        P, M, n = m.shape[-2], m.shape[-1], LnT.shape[-1]
+        lead = tuple(m.shape[:-2])
+        A4 = G.broadcast_to(G.expand_dims(LnT, -3), lead + (P, M, n))
+        if s_kind == "diag":
+            C = G.mul(G.expand_dims(s, -1), A4)                                           # diag(s_p) A    [.., P, M, n]
+        else:
+            C = G.matmul(G.reshape(s, lead + (P, M, s.shape[-1])), A4, transpose_a=True)  # S_ep^T A_e     [.., P, R, n]
+        cov = G.matmul(C, C, transpose_a=True)
+        if q_shape == "fullrank":
+            cov = G.add(cov, G.expand_dims(G.add_eye(self._additional_cov(x, LnT, "fullrank"), jitter), -3))
+        elif q_shape == "diagonal":
+            r = G.unary("ABS", self._additional_cov(x, LnT, "diagonal"))                 # [.., n]
+            cov = G.add(cov, G.expand_dims(G.matrix_diag(r), -3))
+        return cov
 
     def _effective_LT(self, x):
         """Lm^{-1} K(z, x) (reference gp/gp.py:146-174)."""

@@ -1130,6 +1130,16 @@ def diag_part(x) -> Tensor:
     return strided_view(x, x.shape[:-2] + (n,), st[:-2] + [n + 1])
 
 
+def matrix_diag(v) -> Tensor:
+    """tf.matrix_diag: [.., n] -> [.., n, n] with v on the diagonal and zeros elsewhere (a strided scatter)."""
+    v = as_tensor(v)
+    n = v.shape[-1]
+    shape = tuple(v.shape[:-1]) + (n, n)
+    st = _contig_strides(shape)
+    return make("scatter_strided", (v,), {"xshape": shape, "shape": tuple(v.shape), "strides": tuple(st[:-2] + [n + 1]),
+                                          "offset": 0}, [shape]).outputs[0]
+
+
 def cholesky(a) -> Tensor:
     """Lower Cholesky factor, batched (tf.cholesky; reference gp/kernels.py:101)."""
     a = as_tensor(a)
@@ -1160,13 +1170,14 @@ def _cholesky_emit(plan, node):
         users = list(plan._consumers.get(inv_node.outputs[0], ()))
         users += [c2 for c in users if c.op == "stop_gradient" for c2 in plan._consumers.get(c.outputs[0], ())]
         bf3 = False
-        if plan.dtype == plan.torch.float32 and M % 32 == 0 and M >= 32 and any(c.op in ("sgp", "sgp_grad", "sgp_predict")
+        if plan.dtype == plan.torch.float32 and M % 32 == 0 and M >= 32 and any(c.op in ("sgp", "sgp_grad", "sgp_predict",
+                                                                                             "sgp_predict_cov")
                                                                                 for c in users):
             from ._settings import settings as _st
 
             # settings.numerics.contraction = bf16x3: the M^2 n contractions take three-term bf16 operands
             # (fp32-level accuracy at the bf16 MFMA rate, include/henbun_hip.h HB_PREC_BF16X3); M <= 512 only.
-            # Not requested by sgp_predict: prediction runs in native precision only.
+            # Not requested by sgp_predict / sgp_predict_cov: prediction runs in native precision only.
             bf3 = (str(getattr(_st.numerics, "contraction", "native")) == "bf16x3" and M <= 512
                    and any(c.op in ("sgp", "sgp_grad") for c in users))
             frag = plan.scratch(((5 if bf3 else 2) * max(int(np.prod(node.outputs[0].shape)), 1),))
@@ -1925,6 +1936,51 @@ def _sgp_predict_vjp(node, gs):
 
 
 defop("sgp_predict", _sgp_predict_emit, _sgp_predict_vjp)
+
+
+def sgp_predict_cov(x, z, ell, L, s, P, mode="diagonal", s_kind="diag", jitter=0.0) -> Tensor:
+    """Full covariance of sgp_samples' draw (the fused SparseGP.predict_f(full_cov=True) for the UnitRBF kernel and a 2-D
+    x): with A = L^-1 K(z, x) and u ~ N(m, S S^T),
+        cov_p = A^T S_p S_p^T A + R     [.., P, n, n],  R = K(x, x) - A^T A + jitter I ('fullrank'),
+                                                         diag(|1 - colsum(A^2)|) ('diagonal'), 0 ('neglected')
+    s: standard deviations [.., P, M] (s_kind 'diag') or one lower-triangular [M, M] for E P == 1 ('tril').  Bitwise
+    symmetric; its diagonal is sgp_predict's var.  Forward only (include/henbun_hip.h hb_sgp_predict_cov_*)."""
+    x, z, ell, L, s = (as_tensor(t) for t in (x, z, ell, L, s))
+    W = stop_gradient(trinv(L))
+    lead, n, M = tuple(z.shape[:-2]), x.shape[-2], z.shape[-2]
+    E = int(np.prod(lead)) if lead else 1
+    if s_kind == "diag" and tuple(s.shape) != lead + (P, M):
+        raise ValueError("sgp_predict_cov: s must be %s, got %s" % (lead + (P, M), tuple(s.shape)))
+    if s_kind == "tril" and (E * P != 1 or tuple(s.shape) != (M, M)):
+        raise ValueError("sgp_predict_cov: a full-rank S must be [%d, %d] for one latent function of one expert" % (M, M))
+    nd = make("sgp_predict_cov", (x, z, ell, L, W, s), {"mode": mode, "s_kind": s_kind, "jitter": float(jitter), "P": int(P)},
+              [lead + (P, n, n)])
+    return nd.outputs[0]
+
+
+def _sgp_predict_cov_emit(plan, node):
+    H = plan.H
+    x, z, ell, _, W, s = (plan.buf(t) for t in node.inputs)
+    cov = plan.out(node.outputs[0])
+    zsh, xsh = node.inputs[1].shape, node.inputs[0].shape
+    E, M, n, P = int(np.prod(zsh[:-2])) if len(zsh) > 2 else 1, zsh[-2], xsh[-2], node.attrs["P"]
+    s_kind = SGP_PREDICT_S[node.attrs["s_kind"]]
+    wfrag, _ = plan._wfrag.get(_through_stop_gradient(node.inputs[4]), (None, False))
+    plan.note("fused predictive covariance (hb_sgp_predict_cov: A, then one symmetric MFMA product)", node, True)
+    ws = plan.scratch((max(H.sgp_predict_cov_ws_elems(plan.dtype, E, n, M, P, s_kind), 1),))
+    mode, jit = SGP_PREDICT_MODES[node.attrs["mode"]], node.attrs["jitter"]
+    plan.steps.append(lambda: H.sgp_predict_cov(x, z, ell, W, s, P, s_kind=s_kind, mode=mode, jitter=jit, out=cov,
+                                                wfrag=wfrag, ws=ws))
+
+
+def _sgp_predict_cov_vjp(node, gs):
+    if any(g is not None for g in gs):
+        raise NotImplementedError("sgp_predict_cov (SparseGP.predict_f(full_cov=True)) is forward-only: no gradient through "
+                                  "the covariance or the draws built on it")
+    return [None] * len(node.inputs)
+
+
+defop("sgp_predict_cov", _sgp_predict_cov_emit, _sgp_predict_cov_vjp)
 
 
 # ------------------------------------------------------------------------------

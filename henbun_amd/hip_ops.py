@@ -1069,6 +1069,30 @@ def sgp_predict(x, z, ell, W, m, s, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, jitter
     return mean, var
 
 
+def sgp_predict_cov_ws_elems(dtype, E, n, M, P, s_kind):
+    """Scratch elements hb_sgp_predict_cov needs: A [E, M, n], C = S^T A [M, n] (full-rank S), a2 [E, n] -- linear in n."""
+    return int(_lib.lib().raw("hb_sgp_predict_cov_ws_elems")(int(E), int(n), int(M), int(P), int(s_kind),
+                                                             4 if dtype == torch.float32 else 8))
+
+
+def sgp_predict_cov(x, z, ell, W, s, P, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, jitter=0.0, out=None, wfrag=None, ws=None):
+    """Full predictive covariance cov[E?, P, n, n] of sgp_fwd's draw for u ~ N(m, S S^T) (hb_sgp_predict_cov): bitwise
+    symmetric, its diagonal the var of sgp_predict.  s: standard deviations [E?, P, M] (SGP_S_DIAG) or one lower-triangular
+    [M, M] for E P == 1 (SGP_S_TRIL).  `wfrag`: cholesky_inverse's fragment-major images of W (optional)."""
+    for t in (x, z, ell, W, s):
+        _chk(t)
+    E, n, M, d, _, sx = _sgp_dims(x, z, s if s_kind == SGP_S_DIAG else z)
+    lead = (E,) if z.dim() == 3 else ()
+    dev, dt = x.device, x.dtype
+    if out is None:
+        out = _empty(lead + (int(P), n, n), dtype=dt, device=dev)
+    if ws is None:
+        ws = workspace(dt, dev, max(sgp_predict_cov_ws_elems(dt, E, n, M, P, s_kind), 1))
+    _lib.lib().call("hb_sgp_predict_cov" + _suf(x), KERN_RBF, _p(x), sx, _p(z), _p(ell), ell.numel() // E, _p(W), _p(wfrag),
+                    _p(s), int(s_kind), int(mode), float(jitter), _p(out), E, n, M, d, int(P), _p(ws), stream())
+    return out
+
+
 def sgp_bwd(x, z, ell, W, u, eps, A, v, fbar, mode=SGP_DIAGONAL, need_xbar=False, out=None, wfrag=None,
             prec=PREC_NATIVE, a_frag=None, kbar_frag=None):
     """Returns (Lbar, ubar, zbar, ellbar, xbar|None)."""

@@ -33,26 +33,39 @@ class SVGP(hb.model.Model):
         ll = tf.reduce_sum(hb.densities.gaussian(tf.transpose(self.Y), f, self.var))
         return (self.N / n) * ll - self.KL()
 
-    def _predict(self, Xnew, noise):
-        """One plan with both outputs: (mean sqrt(k_var), var k_var [+ var of the likelihood]) at Xnew, as numpy."""
+    def _predict(self, Xnew, noise, full_cov=False, num_samples=None):
+        """One plan: (mean sqrt(k_var), var k_var [+ var of the likelihood]) at Xnew, as numpy -- with full_cov the
+        covariance [1, n, n] times k_var instead of var; with num_samples joint draws [num_samples, n] of f (the model's
+        ELBO convention f = samples * sqrt(k_var) for all three)."""
         Xnew = np.asarray(Xnew)
         q = object.__getattribute__(self, "u")
         self.initialize()
         with self.tf_mode():
-            mean, var = self.gp.predict_f(Xnew, q, q_shape=self.residual)
-            mean = mean * tf.sqrt(self.k_var)
-            var = var * self.k_var
-            if noise:
-                var = var + self.var
-        plan = self._session.make_plan([mean, var])
+            if num_samples is not None:
+                f = self.gp.predict_f_samples(Xnew, q, num_samples, q_shape=self.residual)
+                outs = [tf.reshape(f * tf.sqrt(self.k_var), [int(num_samples), Xnew.shape[0]])]
+            else:
+                mean, var = self.gp.predict_f(Xnew, q, q_shape=self.residual, full_cov=full_cov)
+                mean = mean * tf.sqrt(self.k_var)
+                var = var * self.k_var
+                if noise:
+                    var = var + self.var
+                outs = [mean, var]
+        plan = self._session.make_plan(outs)
         plan.run()
         plan.check()
-        return plan.value(plan.outputs[0]), plan.value(plan.outputs[1])
+        return tuple(plan.value(o) for o in plan.outputs) if num_samples is None else plan.value(plan.outputs[0])
 
-    def predict_f(self, Xnew):
+    def predict_f(self, Xnew, full_cov=False):
         """Closed-form posterior mean and variance of the latent f at Xnew [n, 1]: arrays [1, n] (SparseGP.predict_f
-        scaled by k_var, the model's ELBO convention f = samples * sqrt(k_var))."""
-        return self._predict(Xnew, False)
+        scaled by k_var, the model's ELBO convention f = samples * sqrt(k_var)); full_cov=True: the covariance [1, n, n]
+        in place of the variance."""
+        return self._predict(Xnew, False, full_cov=full_cov)
+
+    def predict_f_samples(self, Xnew, num_samples):
+        """num_samples joint posterior draws of the latent f at Xnew [n, 1]: array [num_samples, n]
+        (SparseGP.predict_f_samples with the model's residual, scaled by sqrt(k_var))."""
+        return self._predict(Xnew, False, num_samples=num_samples)
 
     def predict_y(self, Xnew):
         """predict_f plus the Gaussian likelihood's variance: the predictive of a new observation y at Xnew."""

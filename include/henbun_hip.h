@@ -44,7 +44,8 @@ extern "C" {
  * existing signature: hb_cholesky_persistent_shape, hb_gram_cholesky_inverse_f32, hb_mlp2_sample_*, hb_matmul_gauss_*,
  * hb_matmul_gram_vjp_*, hb_gram_ell_fold_*, hb_sgp_rider_*, hb_fullrank_sample_kl_fwd1_* / hb_fullrank_one_launch_shape.
  * Still 2 after additions that change no existing signature: hb_sgp_predict_f32 / _f64, hb_sgp_predict_ws_elems and the
- * enum values HB_SGP_FULLRANK, HB_SGP_S_DIAG, HB_SGP_S_TRIL (closed-form predictive moments). */
+ * enum values HB_SGP_FULLRANK, HB_SGP_S_DIAG, HB_SGP_S_TRIL (closed-form predictive moments); hb_sgp_predict_cov_f32 /
+ * _f64 and hb_sgp_predict_cov_ws_elems (full predictive covariance). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -579,6 +580,26 @@ int hb_sgp_predict_f32(int kind, const float* x, long sx, const float* z, const 
 int hb_sgp_predict_f64(int kind, const double* x, long sx, const double* z, const double* ell, long dl, const double* W,
                        const double* Wfrag, const double* m, const double* s, int s_kind, int mode, double jitter,
                        double* mean, double* var, long E, long n, long M, long d, long P, double* ws, void* stream);
+/* Full predictive covariance of the same draw (csrc/sgp_predict_cov.hip; not in the reference).  Per expert e and latent
+ * function p, with A_e = L_e^-1 K(z_e, x):
+ *   cov[e,p] = A^T S_ep S_ep^T A + K(x, x) - A^T A + jitter I   (mode HB_SGP_FULLRANK: what samples() factorises, plus u)
+ *            = A^T S_ep S_ep^T A + diag(|1 - sum_m A_m^2|)        (HB_SGP_DIAGONAL: independent residuals)
+ *            = A^T S_ep S_ep^T A                                  (HB_SGP_NEGLECTED)
+ * so diag(cov) is hb_sgp_predict's var.  cov [E, P, n, n], written in full and bitwise symmetric (one triangle is computed
+ * and mirrored).  x, sx, z, ell, dl, W, Wfrag, s, s_kind as for hb_sgp_predict_*; HB_SGP_S_TRIL needs E P == 1 (S is then
+ * [M, M]).  Forward only.  Two passes: hb_sgp_A_* writes A into ws (from Wfrag when given), a full-rank S adds
+ * C = S^T A (hb_matmul_*) and HB_SGP_DIAGONAL the column sums of A^2; then fp32 runs one MFMA launch, a workgroup per
+ * 128 x 128 lower-triangle tile, the K-loop over the rows of A weighted by s_pk^2 - [FULLRANK] (diagonal S) or
+ * -[FULLRANK] (full-rank S, then over the rows of C with weight 1), the RBF block and the diagonal term added in the
+ * epilogue; fp64 runs a plain loop in the same order.  ws >= hb_sgp_predict_cov_ws_elems(E, n, M, P, s_kind, sizeof(T))
+ * elements (16-byte aligned; O((E + 1) M n), linear in n). */
+long hb_sgp_predict_cov_ws_elems(long E, long n, long M, long P, int s_kind, int dtype_bytes);
+int hb_sgp_predict_cov_f32(int kind, const float* x, long sx, const float* z, const float* ell, long dl, const float* W,
+                           const float* Wfrag, const float* s, int s_kind, int mode, double jitter, float* cov, long E, long n,
+                           long M, long d, long P, float* ws, void* stream);
+int hb_sgp_predict_cov_f64(int kind, const double* x, long sx, const double* z, const double* ell, long dl, const double* W,
+                           const double* Wfrag, const double* s, int s_kind, int mode, double jitter, double* cov, long E,
+                           long n, long M, long d, long P, double* ws, void* stream);
 /* VJP given fbar [E,P,n]:
  *   Abar = u^T fbar + A diag(c),  c = -eps sign(v)/sqrt|v| * sum_p fbar_p
  *   Kbar = W^T Abar            [E,M,n]  (scratch output, kept for Lbar)
