@@ -140,6 +140,142 @@ class SparseGP(GP):
         eps = G.random_normal(tuple(cov.shape[:-2]) + (S, n))               # [.., P, S, n]
         return G.add(G.expand_dims(mean, -2), G.matmul(eps, chol, transpose_b=True))
 
+    # -- closed-form posterior (Titsias 2009; the whitened model of models.SVGP) ------------------------------------
+    def _stats_session(self):
+        root = self.highest_parent
+        sess = getattr(root, "_session", None)
+        if sess is None:
+            raise ValueError("statistics / optimal_q / collapsed_bound need the SparseGP to be part of a Model")
+        kern = self._kern()
+        if not isinstance(kern, UnitRBF):
+            raise NotImplementedError("statistics: the closed-form optimal q(u) is implemented for the UnitRBF kernel only "
+                                      "(got %s)" % type(kern).__name__)
+        zvar = object.__getattribute__(self, "z")
+        if len(zvar.shape) != 2:
+            raise NotImplementedError("statistics: one expert only (z must be [M, d], got %s)" % (tuple(zvar.shape),))
+        ls = object.__getattribute__(kern, "lengthscales")
+        if not isinstance(ls, Variable) or len(ls.shape) != 1:
+            raise NotImplementedError("statistics: the lengthscales must be one Variable [dl]")
+        root.initialize()
+        return sess, zvar, ls
+
+    def _device_data(self, sess, a, name):
+        """X / Y as a contiguous [N, k] device tensor of the session's dtype: a Data / MinibatchData of the model is read
+        from its device-resident buffer (all rows), a device tensor is taken as it is, anything else is uploaded."""
+        from ..param import Data
+
+        torch = sess.torch
+        if isinstance(a, Data):
+            t = sess.data_buffer(a)
+        elif isinstance(a, torch.Tensor):
+            t = a.to(device=sess.device, dtype=sess.torch_dtype)
+        else:
+            t = torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=sess.np_dtype))).to(sess.device)
+        if t.dim() != 2:
+            raise ValueError("%s must be 2-D [N, k], got %s" % (name, tuple(t.shape)))
+        return t.contiguous()
+
+    def statistics(self, X, Y):
+        """(Phi [M, M], b [P, M], yy [P], a2sum [1]) of the whole data set X [N, d], Y [N, P] for the current z,
+        lengthscales and settings.numerics.jitter_level, as float64 device tensors (hb_sgp_stats: one streaming pass):
+        Phi = A A^T, b = (A Y)^T, yy_p = sum_j Y_jp^2, a2sum = tr Phi, A = Lm^-1 K(z, X), Lm = chol(K(z, z) + jitter I)
+        from the fused factor + inverse the plans use.  A failed factorisation raises graph.CholeskyError."""
+        sess, zvar, ls = self._stats_session()
+        torch, H = sess.torch, sess.H
+        Xd, Yd = self._device_data(sess, X, "X"), self._device_data(sess, Y, "Y")
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=sess.np_dtype))).to(sess.device)
+        z, ell = up(sess.read_value(zvar)), up(np.reshape(sess.read_value(ls), [-1]))
+        if Xd.shape[0] != Yd.shape[0] or Xd.shape[1] != z.shape[1]:
+            raise ValueError("statistics: X %s, Y %s do not match z %s" % (tuple(Xd.shape), tuple(Yd.shape), tuple(z.shape)))
+        M = z.shape[0]
+        K = H.gram_fwd(z, z, ell, diag_add=float(settings.numerics.jitter_level))
+        frag = None
+        if sess.torch_dtype == torch.float32 and M % 32 == 0:
+            frag = torch.empty(2 * M * M, dtype=sess.torch_dtype, device=sess.device)
+        _, W, info = H.cholesky_inverse(K, frag=frag)
+        bad = int(info.cpu()[0])
+        if bad != 0:
+            raise G.CholeskyError("statistics: leading minor %d of K(z, z) + jitter I is not positive definite" % bad)
+        return H.sgp_stats(Xd, Yd, z, ell, W, wfrag=frag)
+
+    def _lambda_solve(self, stats, noise_var, k_var):
+        """(Lam, L, V, t, c): Lambda = I + (k_var / noise_var) Phi = L L^T, V = L^-1, c = sqrt(k_var) b / noise_var [P, M],
+        t = c V^T [P, M] (so |t_p|^2 = c_p^T Lambda^-1 c_p and t V = Lambda^-1 c), float64 on the device."""
+        root = self.highest_parent
+        H = root._session.H
+        Phi, b = stats[0], stats[1]
+        noise_var, k_var = float(noise_var), float(k_var)
+        if not (noise_var > 0.0 and k_var > 0.0):
+            raise ValueError("noise_var and k_var must be positive (got %r, %r)" % (noise_var, k_var))
+        Lam = H.matutil((Phi * (k_var / noise_var)).contiguous(), H.MATUTIL_ADD_EYE, alpha=1.0)
+        L, info = H.cholesky(Lam)
+        bad = int(info.cpu()[0])
+        if bad != 0:
+            raise G.CholeskyError("optimal_q: leading minor %d of Lambda = I + (k_var / noise_var) Phi is not positive "
+                                  "definite" % bad)
+        V = H.trinv(L)
+        c = (b * (np.sqrt(k_var) / noise_var)).contiguous()
+        t = H.matmul(c, V, transB=True)
+        return Lam, L, V, t, c
+
+    @staticmethod
+    def _check_residual(residual):
+        if residual == "fullrank":
+            raise NotImplementedError("the closed-form posterior is implemented for residual 'diagonal' and 'neglected' "
+                                      "(the 'fullrank' residual couples the data points)")
+        if residual not in ("diagonal", "neglected"):
+            raise ValueError("residual must be 'diagonal' or 'neglected', got %r" % (residual,))
+
+    def optimal_q(self, X, Y, noise_var, k_var=1.0, q_shape="fullrank", residual="diagonal", stats=None):
+        """The optimum of the ELBO over q(u_p) = N(m_p, S S^T) at fixed hyper-parameters, for the whitened model
+        u_p ~ N(0, I), f_p = sqrt(k_var) (u_p A + residual), Y_p ~ N(f_p, noise_var):
+            Lambda = I + (k_var / noise_var) Phi,  c_p = sqrt(k_var) b_p / noise_var,  m_p = Lambda^-1 c_p,
+        q_shape 'fullrank': S = chol(Lambda^-1), lower-triangular [M, M] with a positive diagonal, the same for every p;
+        'diagonal': s = diag(Lambda)^-1/2 [M], the optimum of the mean-field family (the mean is the same).
+        Returns (m [P, M], S or s) as float64 numpy.  `residual` ('diagonal' / 'neglected') does not change q*: that
+        term of the ELBO does not depend on q.  The M^3 tail runs on the device in float64 (hb_cholesky, hb_trinv,
+        hb_matmul).  `stats`: the tuple statistics(X, Y) returned, to share one pass between calls."""
+        self._check_residual(residual)
+        if q_shape not in ("fullrank", "diagonal"):
+            raise ValueError("q_shape must be 'fullrank' or 'diagonal', got %r" % (q_shape,))
+        if stats is None:
+            stats = self.statistics(X, Y)
+        H = self.highest_parent._session.H
+        Lam, L, V, t, _ = self._lambda_solve(stats, noise_var, k_var)
+        m = H.matmul(t, V).cpu().numpy()
+        if q_shape == "diagonal":
+            return m, 1.0 / np.sqrt(np.diagonal(Lam.cpu().numpy()).copy())
+        Sig = H.matmul(V, V, transA=True)              # Lambda^-1 = V^T V
+        S, info = H.cholesky(Sig)
+        bad = int(info.cpu()[0])
+        if bad != 0:
+            raise G.CholeskyError("optimal_q: leading minor %d of Lambda^-1 is not positive definite" % bad)
+        return m, np.tril(S.cpu().numpy())
+
+    def collapsed_bound(self, X, Y, noise_var, k_var=1.0, residual="diagonal", stats=None):
+        """The ELBO at the optimal q(u) of optimal_q (the collapsed bound), a float:
+            sum_p [ -N/2 log(2 pi noise_var) - yy_p / (2 noise_var) + 1/2 c_p^T Lambda^-1 c_p ] - P/2 log|Lambda|
+            - P k_var (N - a2sum) / (2 noise_var)          ('diagonal'; 'neglected' drops the last term).
+        N - a2sum is sum_j (kdiag_j - sum_m A_mj^2) for the unit-variance kernel.  samples() takes the absolute value of
+        that difference per point, so the two agree except where round-off makes a term negative."""
+        self._check_residual(residual)
+        if stats is None:
+            stats = self.statistics(X, Y)
+        _, L, _, t, _ = self._lambda_solve(stats, noise_var, k_var)
+        noise_var, k_var = float(noise_var), float(k_var)
+        yy, a2sum = stats[2].cpu().numpy(), float(stats[3].cpu()[0])
+        from ..param import Data
+
+        N = int(self.highest_parent._session.data_buffer(X).shape[0] if isinstance(X, Data) else np.shape(X)[0])
+        P = yy.shape[0]
+        quad = (t.cpu().numpy() ** 2).sum(-1)                                  # [P]
+        logdet = 2.0 * float(np.log(np.diagonal(L.cpu().numpy())).sum())
+        val = float(np.sum(-0.5 * N * np.log(2.0 * np.pi * noise_var) - yy / (2.0 * noise_var) + 0.5 * quad))
+        val -= 0.5 * P * logdet
+        if residual == "diagonal":
+            val -= P * k_var * (N - a2sum) / (2.0 * noise_var)
+        return val
+
     def _predict_generic(self, x, m, s, s_kind, q_shape, jitter):
         """predict_f composed from generic graph ops (non-RBF kernels, 3-D x), the way samples() composes its draw."""
         LnT = self._effective_LT(x)                       # 2-D x: [.., M, n];  3-D x [N, n, d]: [N, M, n]

@@ -1093,6 +1093,40 @@ def sgp_predict_cov(x, z, ell, W, s, P, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, ji
     return out
 
 
+def sgp_stats_ws_elems(dtype, N, M, d, P):
+    """Scratch elements hb_sgp_stats needs: one column chunk of A plus the K-split partial tiles -- the same for every
+    N above one chunk."""
+    return int(_lib.lib().raw("hb_sgp_stats_ws_elems")(int(N), int(M), int(d), int(P), 4 if dtype == torch.float32 else 8))
+
+
+def sgp_stats(X, Y, z, ell, W, wfrag=None, ws=None):
+    """Sufficient statistics of the whole data set for the closed-form optimal q(u) (hb_sgp_stats): with
+    A = W K(z, X) [M, N], (Phi = A A^T [M, M], b = (A Y)^T [P, M], yy = sum_j Y_jp^2 [P], a2sum = tr Phi [1]) as FLOAT64
+    device tensors whatever the input dtype.  X [N, d], Y [N, P], z [M, d], ell [dl], W [M, M]; one expert.  Phi is
+    bitwise symmetric; two calls on the same inputs return the same bits.  `wfrag`: cholesky_inverse's fragment-major
+    images of W (optional)."""
+    for t in (X, Y, z, ell, W):
+        _chk(t)
+    if X.dim() != 2 or Y.dim() != 2 or z.dim() != 2 or X.shape[0] != Y.shape[0] or X.shape[1] != z.shape[1]:
+        raise ValueError("sgp_stats: X [N, d], Y [N, P], z [M, d] expected, got %s %s %s"
+                         % (tuple(X.shape), tuple(Y.shape), tuple(z.shape)))
+    dt, dev = X.dtype, X.device
+    if any(t.dtype != dt for t in (Y, z, ell, W)):
+        raise TypeError("sgp_stats: all operands must share one dtype")
+    N, d = X.shape
+    M, P = z.shape[0], Y.shape[1]
+    Phi = _empty((M, M), dtype=torch.float64, device=dev)
+    b = _empty((P, M), dtype=torch.float64, device=dev)
+    yy = _empty((P,), dtype=torch.float64, device=dev)
+    a2sum = _empty((1,), dtype=torch.float64, device=dev)
+    if ws is None:
+        ws = workspace(dt, dev, max(sgp_stats_ws_elems(dt, N, M, d, P), 1))
+    assert ws.numel() >= sgp_stats_ws_elems(dt, N, M, d, P), "hb_sgp_stats: workspace too small (sgp_stats_ws_elems)"
+    _lib.lib().call("hb_sgp_stats" + _suf(X), KERN_RBF, _p(X), _p(Y), _p(z), _p(ell), ell.numel(), _p(W), _p(wfrag), _p(Phi),
+                    _p(b), _p(yy), _p(a2sum), N, M, d, P, _p(ws), stream())
+    return Phi, b, yy, a2sum
+
+
 def sgp_bwd(x, z, ell, W, u, eps, A, v, fbar, mode=SGP_DIAGONAL, need_xbar=False, out=None, wfrag=None,
             prec=PREC_NATIVE, a_frag=None, kbar_frag=None):
     """Returns (Lbar, ubar, zbar, ellbar, xbar|None)."""

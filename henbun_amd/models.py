@@ -71,6 +71,37 @@ class SVGP(hb.model.Model):
         """predict_f plus the Gaussian likelihood's variance: the predictive of a new observation y at Xnew."""
         return self._predict(Xnew, True)
 
+    def _closed_form_inputs(self):
+        """(X, Y, noise variance, k_var) of the whole data set at the current hyper-parameters."""
+        self.initialize()
+        g = lambda k: object.__getattribute__(self, k)
+        return g("X"), g("Y"), float(np.ravel(g("var").value)[0]), float(np.ravel(g("k_var").value)[0])
+
+    def fit_q(self):
+        """Set q(u) to its closed-form optimum at the current z, lengthscales, k_var and var, from ONE pass over the
+        model's full device-resident X, Y (SparseGP.optimal_q; not a minibatch, no Adam step).  u.q_mu / u.q_sqrt are
+        written in their own parametrisation -- log standard deviations for q_shape 'diagonal' (the mean-field optimum),
+        the lower-triangular factor (packed or dense) for 'fullrank'.  Returns (m [1, M], S or s) as optimal_q does."""
+        from henbun_amd.param import tri_pack
+
+        X, Y, var, k_var = self._closed_form_inputs()
+        q = object.__getattribute__(self, "u")
+        m, S = object.__getattribute__(self, "gp").optimal_q(X, Y, var, k_var, q_shape=q.q_shape, residual=self.residual)
+        sess = self._session
+        q_mu, q_sqrt = object.__getattribute__(q, "q_mu"), object.__getattribute__(q, "q_sqrt")
+        sess.write_raw(q_mu, m.reshape(-1))
+        if q.q_shape == "diagonal":
+            sess.write_raw(q_sqrt, np.log(S))
+        else:
+            sess.write_raw(q_sqrt, tri_pack(S) if q.packed else S)
+        return m, S
+
+    def collapsed_bound(self):
+        """The ELBO at the optimal q(u) for the current hyper-parameters (SparseGP.collapsed_bound on the full X, Y):
+        what fit_q() followed by an exact evaluation of ELBO over all rows would give."""
+        X, Y, var, k_var = self._closed_form_inputs()
+        return object.__getattribute__(self, "gp").collapsed_bound(X, Y, var, k_var, residual=self.residual)
+
 
 class Amortised(hb.model.Model):
     """cfg 4: NeuralNet encoder -> LOCAL Normal -> linear Gaussian decoder."""

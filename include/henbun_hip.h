@@ -45,7 +45,8 @@ extern "C" {
  * hb_matmul_gram_vjp_*, hb_gram_ell_fold_*, hb_sgp_rider_*, hb_fullrank_sample_kl_fwd1_* / hb_fullrank_one_launch_shape.
  * Still 2 after additions that change no existing signature: hb_sgp_predict_f32 / _f64, hb_sgp_predict_ws_elems and the
  * enum values HB_SGP_FULLRANK, HB_SGP_S_DIAG, HB_SGP_S_TRIL (closed-form predictive moments); hb_sgp_predict_cov_f32 /
- * _f64 and hb_sgp_predict_cov_ws_elems (full predictive covariance). */
+ * _f64 and hb_sgp_predict_cov_ws_elems (full predictive covariance); hb_sgp_stats_f32 / _f64 and hb_sgp_stats_ws_elems
+ * (sufficient statistics of the closed-form optimal q(u)). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -55,7 +56,8 @@ const char* hb_last_error_string(void);
  * key -> value table.  The library never reads the environment; without a call here every dispatch rule is the
  * shipped one.  Keys: chol_persist (0: the launch-chain Cholesky), chol_no64, mm_no_wgk, mm_no_rowsreg, mm_no_rows,
  * mm_force_bt, mm_force_s, sgp_no_strip, sgp_force_strip, sgp_tiled_crossover, sgp_strip_form2, sgp_no_fused_finish,
- * lbar_force_s, lbar_no_lds.  hb_debug_clear() drops every entry. */
+ * lbar_force_s, lbar_no_lds, sgp_stats_no_A, sgp_stats_no_syrk (hb_sgp_stats_* without its first / second pass: timing
+ * only, the outputs are then meaningless), sgp_stats_target_wg (tiles x K-splits aimed at; hb_sgp_stats_ws_elems follows).  hb_debug_clear() drops every entry. */
 int hb_debug_set(const char* key, long value);
 int hb_debug_clear(void);
 /* device name / arch of the current device into (host) buf; returns 0 or hipError */
@@ -600,6 +602,25 @@ int hb_sgp_predict_cov_f32(int kind, const float* x, long sx, const float* z, co
 int hb_sgp_predict_cov_f64(int kind, const double* x, long sx, const double* z, const double* ell, long dl, const double* W,
                            const double* Wfrag, const double* s, int s_kind, int mode, double jitter, double* cov, long E,
                            long n, long M, long d, long P, double* ws, void* stream);
+/* Sufficient statistics of the whole data set for the closed-form optimal q(u) and the collapsed bound of the whitened
+ * sparse GP regression model (csrc/sgp_stats.hip; not in the reference).  With A = W k(z, X) [M, N], W = Lm^-1:
+ *   Phi [M, M] = A A^T,   b [P, M] = (A Y)^T,   yy [P] = sum_j Y[j, p]^2,   a2sum [1] = tr Phi = sum_j sum_m A_mj^2
+ * ALWAYS double, whatever the input type.  Phi is written in full and bitwise symmetric (the lower triangle is computed
+ * and mirrored); a2sum is the fold of its diagonal.  X [N, d] and Y [N, P] row-major; z [M, d], ell [dl], W [M, M], Wfrag
+ * (nullable) as for hb_sgp_A_* with E = 1.  kind must be HB_KERN_RBF; N >= 1, d >= 1, P >= 1.  One streaming pass in
+ * column chunks of at most 32768: per chunk hb_sgp_A_* writes A_c into ws; fp32 with M % 32 == 0 and P <= 4 then runs a
+ * split-K symmetric rank update on MFMA (128 x 128 lower-triangle tiles x K-splits, fp32 accumulation inside one split
+ * only) whose partial tiles a second launch folds into Phi and b in double, in a fixed order (bitwise reproducible; no
+ * atomics); every other shape runs plain loops in double.  The fp32 entry forms A in float32
+ * (profiles/sgp_stats_errors.txt).  ws >= hb_sgp_stats_ws_elems(N, M, d, P, sizeof(T)) elements of T, 16-byte aligned;
+ * the same for every N above one chunk. */
+long hb_sgp_stats_ws_elems(long N, long M, long d, long P, int dtype_bytes);
+int hb_sgp_stats_f32(int kind, const float* X, const float* Y, const float* z, const float* ell, long dl, const float* W,
+                     const float* Wfrag, double* Phi, double* b, double* yy, double* a2sum, long N, long M, long d, long P,
+                     float* ws, void* stream);
+int hb_sgp_stats_f64(int kind, const double* X, const double* Y, const double* z, const double* ell, long dl, const double* W,
+                     const double* Wfrag, double* Phi, double* b, double* yy, double* a2sum, long N, long M, long d, long P,
+                     double* ws, void* stream);
 /* VJP given fbar [E,P,n]:
  *   Abar = u^T fbar + A diag(c),  c = -eps sign(v)/sqrt|v| * sum_p fbar_p
  *   Kbar = W^T Abar            [E,M,n]  (scratch output, kept for Lbar)
