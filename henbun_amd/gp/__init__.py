@@ -1,2 +1,2 @@
 from . import kernels
-from .gp import GP, SparseGP
+from .gp import GP, SparseGP, greedy_inducing

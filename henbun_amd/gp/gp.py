@@ -198,6 +198,34 @@ class SparseGP(GP):
             raise G.CholeskyError("statistics: leading minor %d of K(z, z) + jitter I is not positive definite" % bad)
         return H.sgp_stats(Xd, Yd, z, ell, W, wfrag=frag)
 
+    def select_inducing(self, X, threshold=None):
+        """Move z to the M = z.shape[0] rows of X [N, d] that greedy conditional-variance selection picks at the CURRENT
+        lengthscales (hb_sgp_select; see greedy_inducing), in selection order, and return their row indices as numpy
+        int64 [M].  X: a Data / MinibatchData of the model (read in full from its device buffer), a device tensor or an
+        array.  threshold=None: settings.numerics.jitter_level.  Same restrictions and exception types as statistics():
+        UnitRBF, one expert, the lengthscales one Variable.  If fewer than M points have a conditional variance above
+        the threshold, ValueError is raised and z is left untouched.  q(u) is not touched: the optimum for the new z is
+        one optimal_q / fit_q away."""
+        sess, zvar, ls = self._stats_session()
+        torch, H = sess.torch, sess.H
+        Xd = self._device_data(sess, X, "X")
+        M, d = int(zvar.shape[0]), int(zvar.shape[1])
+        if Xd.shape[1] != d:
+            raise ValueError("select_inducing: X %s does not match z %s" % (tuple(Xd.shape), tuple(zvar.shape)))
+        if M > Xd.shape[0]:
+            raise ValueError("select_inducing: z holds %d points, X only %d rows" % (M, Xd.shape[0]))
+        ell = torch.as_tensor(np.ascontiguousarray(np.reshape(sess.read_value(ls), [-1]).astype(sess.np_dtype))).to(sess.device)
+        thr = float(settings.numerics.jitter_level if threshold is None else threshold)
+        idx, _, count, _ = H.sgp_select(Xd, ell, M, thr)
+        count = int(count.cpu()[0])
+        if count < M:
+            raise ValueError("select_inducing: only %d of the %d points asked for have a conditional variance above the "
+                             "threshold %g; z is unchanged (use fewer inducing points or a lower threshold)"
+                             % (count, M, thr))
+        Z = Xd[idx].cpu().numpy()
+        sess.write_raw(zvar, zvar.transform.backward(Z.astype(np.float64)))
+        return idx.cpu().numpy()
+
     def _lambda_solve(self, stats, noise_var, k_var):
         """(Lam, L, V, t, c): Lambda = I + (k_var / noise_var) Phi = L L^T, V = L^-1, c = sqrt(k_var) b / noise_var [P, M],
         t = c V^T [P, M] (so |t_p|^2 = c_p^T Lambda^-1 c_p and t V = Lambda^-1 c), float64 on the device."""
@@ -381,3 +409,42 @@ def _posterior_of(q):
     if scale is not None:
         m = G.mul(scale, m)
     return m, s, kind
+
+
+def greedy_inducing(X, M, lengthscales=1.0, threshold=None, return_info=False, dtype=None):
+    """Z [M, d] (numpy, selection order): the M rows of X [N, d] that greedy conditional-variance selection picks for the
+    UnitRBF kernel with the given lengthscales (a scalar, [1] or [d]) -- a pivoted incomplete Cholesky of K(X, X) (Burt,
+    Rasmussen, van der Wilk 2020), each step taking the point whose variance given the points chosen so far is largest
+    (exact ties: the lowest row, so X[0] is always first).  Deterministic; needs no model, so it can make the Z a model
+    is built with.  X is uploaded in the configured float type (`dtype`: as for Model) to the device a Session would
+    pick; the work is M launches of hb_sgp_select with no read-back, and O(M N) device memory for the duration.
+    threshold=None: settings.numerics.jitter_level -- a point whose conditional variance is below the jitter adds
+    nothing that K(z, z) + jitter I can resolve.  If fewer than M points clear the threshold ValueError is raised, naming
+    the count reached.  return_info=True: (Z, dict(idx int64 [M], pivots [M], trace float, count int)); trace is the
+    residual tr(K_XX - K_XZ K_ZZ^-1 K_ZX), the N - a2sum term of collapsed_bound at zero jitter."""
+    from ..session import Session
+
+    sess = Session(None, dtype=dtype)
+    sess._ensure_device()
+    torch, H = sess.torch, sess.H
+    X = np.asarray(X, dtype=sess.np_dtype)
+    if X.ndim != 2:
+        raise ValueError("greedy_inducing: X must be 2-D [N, d], got %s" % (X.shape,))
+    ell = np.reshape(np.asarray(lengthscales, dtype=sess.np_dtype), [-1])
+    if ell.size not in (1, X.shape[1]) or not np.all(ell > 0):
+        raise ValueError("greedy_inducing: lengthscales must be positive, a scalar or one per column of X")
+    M = int(M)
+    if not 1 <= M <= X.shape[0]:
+        raise ValueError("greedy_inducing: 1 <= M <= N expected, got M=%d, N=%d" % (M, X.shape[0]))
+    thr = float(settings.numerics.jitter_level if threshold is None else threshold)
+    up = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(sess.device)
+    idx, pivots, count, trace = H.sgp_select(up(X), up(ell), M, thr)
+    count = int(count.cpu()[0])
+    if count < M:
+        raise ValueError("greedy_inducing: only %d of the %d points asked for have a conditional variance above the "
+                         "threshold %g (use fewer inducing points or a lower threshold)" % (count, M, thr))
+    idx = idx.cpu().numpy()
+    Z = X[idx].copy()
+    if not return_info:
+        return Z
+    return Z, dict(idx=idx, pivots=pivots.cpu().numpy(), trace=float(trace.cpu()[0]), count=count)

@@ -1127,6 +1127,47 @@ def sgp_stats(X, Y, z, ell, W, wfrag=None, ws=None):
     return Phi, b, yy, a2sum
 
 
+def sgp_select_ws_elems(dtype, N, M, d):
+    """Scratch elements hb_sgp_select needs: the history C [M, N], dvar [N] and the arg-max partials -- O(M N)."""
+    return int(_lib.lib().raw("hb_sgp_select_ws_elems")(int(N), int(M), int(d), 4 if dtype == torch.float32 else 8))
+
+
+def sgp_select(X, ell, M, threshold=0.0, ws=None):
+    """Greedy conditional-variance selection of M inducing points out of X [N, d] (hb_sgp_select: a pivoted incomplete
+    Cholesky of K(X, X), one launch per chosen point, no read-back).  Returns device tensors (idx int64 [M], pivots [M]
+    in the dtype of X, count int64 [1], trace float64 [1]): the chosen rows in selection order (exact ties of the
+    conditional variance go to the lowest index, so idx[0] == 0), the conditional variance each had when chosen, how many
+    were chosen before the largest conditional variance fell to `threshold` or below (idx / pivots from there on hold
+    -1 / 0), and the residual sum of conditional variances tr(K_XX - K_XZ K_ZZ^-1 K_ZX).  ell [1] or [d]; one expert.
+    Two calls on the same inputs return the same bits.  The workspace is O(M N) elements (sgp_select_ws_elems): when
+    `ws` is not given it is allocated for this call alone and released with it, not taken from the shared scratch."""
+    for t in (X, ell):
+        _chk(t)
+    if X.dim() != 2 or ell.dim() != 1 or ell.numel() not in (1, X.shape[1]):
+        raise ValueError("sgp_select: X [N, d] and ell [1] or [d] expected, got %s %s" % (tuple(X.shape), tuple(ell.shape)))
+    dt, dev = X.dtype, X.device
+    if ell.dtype != dt:
+        raise TypeError("sgp_select: all operands must share one dtype")
+    N, d = X.shape
+    M = int(M)
+    if not 1 <= M <= N:
+        raise ValueError("sgp_select: 1 <= M <= N expected, got M=%d, N=%d" % (M, N))
+    if not float(threshold) >= 0.0:
+        raise ValueError("sgp_select: threshold must be >= 0, got %r" % (threshold,))
+    idx = _empty((M,), dtype=torch.int64, device=dev)
+    pivots = _empty((M,), dtype=dt, device=dev)
+    count = _empty((1,), dtype=torch.int64, device=dev)
+    trace = _empty((1,), dtype=torch.float64, device=dev)
+    need = sgp_select_ws_elems(dt, N, M, d)
+    if ws is None:
+        ws = _empty((need,), dtype=dt, device=dev)
+    if ws.dtype != dt or ws.numel() < need:
+        raise ValueError("sgp_select: the workspace must hold %d elements of %s (sgp_select_ws_elems)" % (need, dt))
+    _lib.lib().call("hb_sgp_select" + _suf(X), KERN_RBF, _p(X), _p(ell), ell.numel(), N, M, d, float(threshold), _p(idx),
+                    _p(pivots), _p(count), _p(trace), _p(ws), stream())
+    return idx, pivots, count, trace
+
+
 def sgp_bwd(x, z, ell, W, u, eps, A, v, fbar, mode=SGP_DIAGONAL, need_xbar=False, out=None, wfrag=None,
             prec=PREC_NATIVE, a_frag=None, kbar_frag=None):
     """Returns (Lbar, ubar, zbar, ellbar, xbar|None)."""

@@ -96,6 +96,13 @@ class SVGP(hb.model.Model):
             sess.write_raw(q_sqrt, tri_pack(S) if q.packed else S)
         return m, S
 
+    def select_inducing(self, threshold=None):
+        """Move z to the M rows of the model's own full X that greedy conditional-variance selection picks at the current
+        lengthscales (SparseGP.select_inducing: one launch per point over the device-resident X); returns their row
+        indices.  q(u) is NOT touched and no longer fits the new z: call fit_q() afterwards."""
+        self.initialize()
+        return object.__getattribute__(self, "gp").select_inducing(object.__getattribute__(self, "X"), threshold=threshold)
+
     def collapsed_bound(self):
         """The ELBO at the optimal q(u) for the current hyper-parameters (SparseGP.collapsed_bound on the full X, Y):
         what fit_q() followed by an exact evaluation of ELBO over all rows would give."""

@@ -46,7 +46,8 @@ extern "C" {
  * Still 2 after additions that change no existing signature: hb_sgp_predict_f32 / _f64, hb_sgp_predict_ws_elems and the
  * enum values HB_SGP_FULLRANK, HB_SGP_S_DIAG, HB_SGP_S_TRIL (closed-form predictive moments); hb_sgp_predict_cov_f32 /
  * _f64 and hb_sgp_predict_cov_ws_elems (full predictive covariance); hb_sgp_stats_f32 / _f64 and hb_sgp_stats_ws_elems
- * (sufficient statistics of the closed-form optimal q(u)). */
+ * (sufficient statistics of the closed-form optimal q(u)); hb_sgp_select_f32 / _f64 and hb_sgp_select_ws_elems (greedy
+ * conditional-variance selection of inducing points). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -57,7 +58,8 @@ const char* hb_last_error_string(void);
  * shipped one.  Keys: chol_persist (0: the launch-chain Cholesky), chol_no64, mm_no_wgk, mm_no_rowsreg, mm_no_rows,
  * mm_force_bt, mm_force_s, sgp_no_strip, sgp_force_strip, sgp_tiled_crossover, sgp_strip_form2, sgp_no_fused_finish,
  * lbar_force_s, lbar_no_lds, sgp_stats_no_A, sgp_stats_no_syrk (hb_sgp_stats_* without its first / second pass: timing
- * only, the outputs are then meaningless), sgp_stats_target_wg (tiles x K-splits aimed at; hb_sgp_stats_ws_elems follows).  hb_debug_clear() drops every entry. */
+ * only, the outputs are then meaningless), sgp_stats_target_wg (tiles x K-splits aimed at; hb_sgp_stats_ws_elems follows), sgp_select_block (64 / 256: the workgroup
+ * size of hb_sgp_select_*; the results do not depend on it).  hb_debug_clear() drops every entry. */
 int hb_debug_set(const char* key, long value);
 int hb_debug_clear(void);
 /* device name / arch of the current device into (host) buf; returns 0 or hipError */
@@ -621,6 +623,26 @@ int hb_sgp_stats_f32(int kind, const float* X, const float* Y, const float* z, c
 int hb_sgp_stats_f64(int kind, const double* X, const double* Y, const double* z, const double* ell, long dl, const double* W,
                      const double* Wfrag, double* Phi, double* b, double* yy, double* a2sum, long N, long M, long d, long P,
                      double* ws, void* stream);
+/* Greedy conditional-variance selection of M inducing points out of X [N, d] (csrc/sgp_select.hip; not in the reference;
+ * Burt, Rasmussen, van der Wilk 2020): a pivoted incomplete Cholesky of K(X, X).  With dvar [N] = kdiag = 1 and the
+ * history C [M, N], for j = 0 .. M - 1:
+ *   i_j = argmax_i dvar_i, exact ties to the LOWEST index (i_0 = 0);  if dvar_{i_j} <= threshold: stop, count = j;
+ *   pivots[j] = dvar_{i_j};  idx[j] = i_j;
+ *   C[j, i] = (k(x_i, x_{i_j}) - sum_{t < j} C[t, i] C[t, i_j]) / sqrt(pivots[j])     (the sum in t order);
+ *   dvar_i <- max(dvar_i - C[j, i]^2, 0);  dvar_{i_j} <- 0.
+ * Outputs, all DEVICE memory: idx [M] and pivots [M] (entries from count on: -1 and 0), count [1] (M when the threshold
+ * never stopped it), trace [1] = sum_i dvar_i at the end = tr(K_XX - K_XZ K_ZZ^-1 K_ZX), summed in double in a fixed order.
+ * k is the library's one definition of the kernel value (csrc/gram_value.cuh); kind must be HB_KERN_RBF; ell [dl],
+ * dl in {1, d}; 1 <= M <= N, M <= 8192, d >= 1, threshold >= 0.  The _f32 entry keeps C and dvar in float, the _f64 entry
+ * runs the same code in double.  M + 1 launches, one per chosen point plus a fold, no host synchronisation, no atomics:
+ * two calls on the same inputs return the same bits.  ws >= hb_sgp_select_ws_elems(N, M, d, sizeof(T)) elements of T,
+ * 16-byte aligned: the history, dvar and the arg-max partials -- O(M N): (M + 1) x (N rounded up to 64) + 12288 (float) /
+ * 8192 (double).  Row j streams j rows of the history: N M^2 / 2 elements read in all. */
+long hb_sgp_select_ws_elems(long N, long M, long d, int dtype_bytes);
+int hb_sgp_select_f32(int kind, const float* X, const float* ell, long dl, long N, long M, long d, double threshold, long* idx,
+                      float* pivots, long* count, double* trace, float* ws, void* stream);
+int hb_sgp_select_f64(int kind, const double* X, const double* ell, long dl, long N, long M, long d, double threshold,
+                      long* idx, double* pivots, long* count, double* trace, double* ws, void* stream);
 /* VJP given fbar [E,P,n]:
  *   Abar = u^T fbar + A diag(c),  c = -eps sign(v)/sqrt|v| * sum_p fbar_p
  *   Kbar = W^T Abar            [E,M,n]  (scratch output, kept for Lbar)
