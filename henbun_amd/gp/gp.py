@@ -304,6 +304,102 @@ class SparseGP(GP):
             val -= P * k_var * (N - a2sum) / (2.0 * noise_var)
         return val
 
+    def collapsed_bound_and_grad(self, X, Y, noise_var, k_var=1.0, residual="diagonal"):
+        """(value, grad): the collapsed bound of collapsed_bound() and its exact gradient with respect to the CONSTRAINED
+        values, grad = dict(z=[M, d], lengthscales=[dl], noise_var=float, k_var=float), float64 numpy.  One pass over
+        the data for the statistics, the M^3 tail, one more pass for the part of the gradient that goes through
+        K(z, X) (hb_sgp_kgrad) and the Gram VJP of K(z, z) + jitter I.
+
+        Everything is FLOAT64 ARITHMETIC on the device whatever the session's dtype: the z gradient is the difference of
+        two terms about 1000 times its size whose weights carry Lm^-1 twice, and float32 anywhere in the chain --
+        reusing the float32-formed Phi, b of statistics() included -- returns noise ("Gradient of the
+        collapsed bound").  A float32 session's X, Y, z, lengthscales are read as they are stored and are exact in
+        double.  `value` is the bound of this same float64 evaluation, so value and gradient are consistent; in a
+        float32 session it can differ from collapsed_bound() by the float32 error of statistics().  Same restrictions
+        and exception types as statistics(): UnitRBF, one expert, the lengthscales one Variable; residual 'fullrank'
+        raises NotImplementedError; a K(z, z) + jitter I or Lambda that is not positive definite raises
+        graph.CholeskyError."""
+        self._check_residual(residual)
+        if not (float(noise_var) > 0.0 and float(k_var) > 0.0):
+            raise ValueError("noise_var and k_var must be positive (got %r, %r)" % (noise_var, k_var))
+        sess, Xd, Yd, z, ell, W = self._grad_inputs(X, Y)
+        stats = self._statistics_f64(sess, Xd, Yd, z, ell, W)
+        return self._grad_from_statistics(sess, Xd, Yd, z, ell, W, stats, noise_var, k_var, residual)
+
+    def _grad_inputs(self, X, Y):
+        """(sess, Xd, Yd, z, ell, W): the data as the session stores it, z and the lengthscales as the session stores
+        them carried in double, and W = chol(K(z, z) + jitter I)^-1 in double."""
+        sess, zvar, ls = self._stats_session()
+        torch, H = sess.torch, sess.H
+        Xd, Yd = self._device_data(sess, X, "X"), self._device_data(sess, Y, "Y")
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=sess.np_dtype).astype(np.float64))).to(sess.device)
+        z, ell = up(sess.read_value(zvar)), up(np.reshape(sess.read_value(ls), [-1]))
+        if Xd.shape[0] != Yd.shape[0] or Xd.shape[1] != z.shape[1]:
+            raise ValueError("collapsed_bound_and_grad: X %s, Y %s do not match z %s"
+                             % (tuple(Xd.shape), tuple(Yd.shape), tuple(z.shape)))
+        L, info = H.cholesky(H.gram_fwd(z, z, ell, diag_add=float(settings.numerics.jitter_level)))
+        bad = int(info.cpu()[0])
+        if bad != 0:
+            raise G.CholeskyError("collapsed_bound_and_grad: leading minor %d of K(z, z) + jitter I is not positive "
+                                  "definite" % bad)
+        return sess, Xd, Yd, z, ell, H.trinv(L)
+
+    def _statistics_f64(self, sess, Xd, Yd, z, ell, W):
+        """(Phi [M, M], b [P, M], yy [P]) with float64 ARITHMETIC whatever the storage type of Xd, Yd: column chunks are
+        up-converted, A_c = W K(z, X_c) by hb_sgp_A_f64, the three products by hb_matmul_f64, the chunks' results added in
+        chunk order.  (statistics() forms A in the session's dtype: its float32 rounding of Phi, b is harmless for
+        optimal_q and collapsed_bound and fatal for the gradient)"""
+        torch, H = sess.torch, sess.H
+        N, M = Xd.shape[0], z.shape[0]
+        chunk = int(min(32768, max(32, (1 << 24) // M)))
+        Phi = b = yy = None
+        for c0 in range(0, N, chunk):
+            Xc = Xd[c0:c0 + chunk].to(torch.float64).contiguous()
+            Yc = Yd[c0:c0 + chunk].to(torch.float64).contiguous()
+            A = H.sgp_A(Xc, z, ell, W)                                      # [M, nc]
+            parts = (H.matmul(A, A, transB=True), H.matmul(Yc, A, transA=True, transB=True), H.matmul(Yc, Yc, transA=True))
+            Phi, b, yy = parts if Phi is None else (Phi + parts[0], b + parts[1], yy + parts[2])
+        return H.matutil(Phi.contiguous(), H.MATUTIL_SYM), b.contiguous(), torch.diagonal(yy).contiguous()
+
+    def _grad_from_statistics(self, sess, Xd, Yd, z, ell, W, stats, noise_var, k_var, residual):
+        """The tail and the two gradient passes of collapsed_bound_and_grad for given float64 (Phi, b, yy)."""
+        torch, H = sess.torch, sess.H
+        Phi, b, yy = stats
+        s2, k = float(noise_var), float(k_var)
+        rho = 1.0 if residual == "diagonal" else 0.0
+        N, (M, d), P = int(Xd.shape[0]), z.shape, int(Yd.shape[1])
+        # tail: D = dF/dLambda, G = dF/dPhi, g = dF/db
+        _, LL, V, t, c = self._lambda_solve((Phi, b), s2, k)                  # t [P, M], |t_p|^2 = c_p^T Lambda^-1 c_p
+        m = H.matmul(t, V)                                                   # [P, M] = c Lambda^-1
+        D = (H.matmul(m, m, transA=True, alpha=-0.5) - (0.5 * P) * H.matmul(V, V, transA=True)).contiguous()
+        Gm = H.matutil((D * (k / s2)).contiguous(), H.MATUTIL_ADD_EYE, alpha=rho * P * k / (2.0 * s2))
+        g = (m * (np.sqrt(k) / s2)).contiguous()
+        # streamed part: Q = 2 W^T G W, R = W^T g^T
+        Q = H.matmul(W, H.matmul(Gm, W), transA=True, alpha=2.0)
+        R = H.matmul(W, g, transA=True, transB=True)
+        zbar, ellbar = H.sgp_kgrad(Xd, Yd, z, ell, Q, R)
+        # Kmm part: L^T Lbar = T = -(2 G Phi + g^T b); the Cholesky VJP; the Gram VJP of K(z, z)
+        T = (H.matmul(Gm, Phi, alpha=-2.0) - H.matmul(g, b, transA=True)).contiguous()
+        S = H.matmul(W, H.matmul(H.matutil(T, H.MATUTIL_PHI), W), transA=True)
+        Kmmbar = H.matutil(S, H.MATUTIL_SYM)
+        zk = torch.empty((M, d), dtype=torch.float64, device=sess.device)
+        ek = torch.empty((ell.numel(),), dtype=torch.float64, device=sess.device)
+        H.gram_bwd_raw(H.KERN_RBF | H.KERN_KBAR_SYMMETRIC, z, 0, z, 0, ell, 0, ell.numel(), Kmmbar, zk, zk, ek, 1, M, M, d,
+                       H.workspace(torch.float64, sess.device, max(M * d, 1)))
+        # scalars and the value, on the host
+        tau, mb, mc = float((D * Phi).sum().cpu()), float((m * b).sum().cpu()), float((m * c).sum().cpu())
+        a2sum, yys = float(torch.diagonal(Phi).sum().cpu()), float(yy.sum().cpu())
+        quad = float((t * t).sum().cpu())
+        logdet = 2.0 * float(np.log(np.diagonal(LL.cpu().numpy())).sum())
+        val = -0.5 * N * P * np.log(2.0 * np.pi * s2) - yys / (2.0 * s2) + 0.5 * quad - 0.5 * P * logdet
+        val -= rho * P * k * (N - a2sum) / (2.0 * s2)
+        dk = tau / s2 + mb / (2.0 * np.sqrt(k) * s2) - rho * P * (N - a2sum) / (2.0 * s2)
+        ds2 = (-N * P / (2.0 * s2) + yys / (2.0 * s2 ** 2) - (k / s2 ** 2) * tau - mc / s2
+               + rho * P * k * (N - a2sum) / (2.0 * s2 ** 2))
+        grad = dict(z=(zbar + zk).cpu().numpy(), lengthscales=(ellbar + ek).cpu().numpy(), noise_var=float(ds2),
+                    k_var=float(dk))
+        return float(val), grad
+
     def _predict_generic(self, x, m, s, s_kind, q_shape, jitter):
         """predict_f composed from generic graph ops (non-RBF kernels, 3-D x), the way samples() composes its draw."""
         LnT = self._effective_LT(x)                       # 2-D x: [.., M, n];  3-D x [N, n, d]: [N, M, n]

@@ -1127,6 +1127,41 @@ def sgp_stats(X, Y, z, ell, W, wfrag=None, ws=None):
     return Phi, b, yy, a2sum
 
 
+def sgp_kgrad_ws_elems(N, M, d, P):
+    """Scratch DOUBLES hb_sgp_kgrad needs: the repacked Q and one partial per strip -- independent of N."""
+    return int(_lib.lib().raw("hb_sgp_kgrad_ws_elems")(int(N), int(M), int(d), int(P)))
+
+
+def sgp_kgrad(X, Y, z, ell, Q, R, ws=None):
+    """Streamed part of the gradient of the collapsed bound (hb_sgp_kgrad): with K = K(z, X), Kbar = Q K + R Y^T and
+    E = Kbar o K, returns (zbar [M, d], ellbar [dl]) = (-sum_j E_ij (z_i - x_j) / ell^2, sum_ij E_ij (z_i - x_j)^2 / ell^3)
+    as float64 device tensors.  X [N, d] and Y [N, P] share one storage dtype (float32 or float64); z [M, d], ell [dl],
+    Q [M, M], R [M, P] are float64 and all arithmetic is float64.  Two calls on the same inputs return the same bits."""
+    for t in (X, Y, z, ell, Q, R):
+        _chk(t)
+    if X.dim() != 2 or Y.dim() != 2 or z.dim() != 2 or X.shape[0] != Y.shape[0] or X.shape[1] != z.shape[1]:
+        raise ValueError("sgp_kgrad: X [N, d], Y [N, P], z [M, d] expected, got %s %s %s"
+                         % (tuple(X.shape), tuple(Y.shape), tuple(z.shape)))
+    N, d = X.shape
+    M, P = z.shape[0], Y.shape[1]
+    if ell.dim() != 1 or ell.numel() not in (1, d) or tuple(Q.shape) != (M, M) or tuple(R.shape) != (M, P):
+        raise ValueError("sgp_kgrad: ell [1] or [d], Q [M, M], R [M, P] expected, got %s %s %s"
+                         % (tuple(ell.shape), tuple(Q.shape), tuple(R.shape)))
+    if Y.dtype != X.dtype or any(t.dtype != torch.float64 for t in (z, ell, Q, R)):
+        raise TypeError("sgp_kgrad: X and Y share one storage dtype; z, ell, Q, R must be float64")
+    dev = X.device
+    zbar = _empty((M, d), dtype=torch.float64, device=dev)
+    ellbar = _empty((ell.numel(),), dtype=torch.float64, device=dev)
+    need = sgp_kgrad_ws_elems(N, M, d, P)
+    if ws is None:
+        ws = workspace(torch.float64, dev, max(need, 1))
+    if ws.dtype != torch.float64 or ws.numel() < need:
+        raise ValueError("sgp_kgrad: the workspace must hold %d float64 elements (sgp_kgrad_ws_elems)" % need)
+    _lib.lib().call("hb_sgp_kgrad" + _suf(X), KERN_RBF, _p(X), _p(Y), _p(z), _p(ell), ell.numel(), _p(Q), _p(R), _p(zbar),
+                    _p(ellbar), N, M, d, P, _p(ws), stream())
+    return zbar, ellbar
+
+
 def sgp_select_ws_elems(dtype, N, M, d):
     """Scratch elements hb_sgp_select needs: the history C [M, N], dvar [N] and the arg-max partials -- O(M N)."""
     return int(_lib.lib().raw("hb_sgp_select_ws_elems")(int(N), int(M), int(d), 4 if dtype == torch.float32 else 8))

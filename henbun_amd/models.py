@@ -109,6 +109,69 @@ class SVGP(hb.model.Model):
         X, Y, var, k_var = self._closed_form_inputs()
         return object.__getattribute__(self, "gp").collapsed_bound(X, Y, var, k_var, residual=self.residual)
 
+    def _hyper_variables(self):
+        """The Variables collapsed_bound() depends on, by the names the gradient uses."""
+        g = object.__getattribute__
+        gp = g(self, "gp")
+        return dict(z=g(gp, "z"), lengthscales=g(g(gp, "kern"), "lengthscales"), k_var=g(self, "k_var"), var=g(self, "var"))
+
+    def collapsed_bound_and_grad(self):
+        """(value, grad): the collapsed bound and its exact gradient with respect to the RAW (free) parameters,
+        grad = dict(z, lengthscales, k_var, var) in the shapes of the raw arrays, float64 numpy.
+        SparseGP.collapsed_bound_and_grad on the full X, Y (float64 arithmetic whatever the session's dtype), chained
+        through the transforms' dforward."""
+        X, Y, var, k_var = self._closed_form_inputs()
+        value, gr = object.__getattribute__(self, "gp").collapsed_bound_and_grad(X, Y, var, k_var, residual=self.residual)
+        sess = self._session
+        cons = dict(z=gr["z"], lengthscales=gr["lengthscales"], k_var=gr["k_var"], var=gr["noise_var"])
+        grad = {}
+        for name, v in self._hyper_variables().items():
+            raw = sess.read_raw(v)
+            grad[name] = np.reshape(np.asarray(cons[name], dtype=np.float64), raw.shape) * v.transform.dforward(raw)
+        return value, grad
+
+    def fit_hyper(self, steps, lr=0.01, train_z=True):
+        """Full-batch fit of the hyper-parameters: `steps` Adam ASCENT steps on the collapsed bound in the raw
+        parameters of lengthscales, k_var, var and (train_z) z, on the host in float64 with the exact gradient of
+        collapsed_bound_and_grad -- M d + dl + 2 numbers, two passes over the data per step, no minibatch noise.  The
+        parameters are written back after every step and q(u) is set to its optimum (fit_q) at the end.  Returns the
+        trace of bound values, steps + 1 entries: before the first step .. at the final parameters.  A step after
+        which K(z, z) + jitter I or Lambda is no longer positive definite raises graph.CholeskyError with the last good
+        parameters restored."""
+        from henbun_amd.graph import CholeskyError
+
+        self.initialize()
+        sess = self._session
+        hv = self._hyper_variables()
+        names = [n for n in hv if train_z or n != "z"]
+        for v in hv.values():
+            sess.read_value(v)   # uploads a value that was assigned and not yet written
+        raw = {n: sess.read_raw(hv[n]).astype(np.float64) for n in names}
+        m1 = {n: np.zeros_like(raw[n]) for n in names}
+        m2 = {n: np.zeros_like(raw[n]) for n in names}
+        b1, b2, eps = 0.9, 0.999, 1e-8
+        good = {n: raw[n].copy() for n in names}
+        trace = []
+        for t in range(int(steps) + 1):
+            try:
+                value, grad = self.collapsed_bound_and_grad()
+            except CholeskyError:
+                for n in names:
+                    sess.write_raw(hv[n], good[n])
+                raise
+            trace.append(value)
+            good = {n: raw[n].copy() for n in names}
+            if t == int(steps):
+                break
+            for n in names:
+                m1[n] = b1 * m1[n] + (1.0 - b1) * grad[n]
+                m2[n] = b2 * m2[n] + (1.0 - b2) * grad[n] ** 2
+                step = lr * (m1[n] / (1.0 - b1 ** (t + 1))) / (np.sqrt(m2[n] / (1.0 - b2 ** (t + 1))) + eps)
+                sess.write_raw(hv[n], raw[n] + step)
+                raw[n] = sess.read_raw(hv[n]).astype(np.float64)   # what the session holds (rounded in a float32 session)
+        self.fit_q()
+        return np.asarray(trace)
+
 
 class Amortised(hb.model.Model):
     """cfg 4: NeuralNet encoder -> LOCAL Normal -> linear Gaussian decoder."""

@@ -15,6 +15,10 @@ class Transform:
     def backward(self, y):
         raise NotImplementedError
 
+    def dforward(self, x):
+        """d forward(x) / dx, elementwise (numpy float64): the chain rule of a gradient taken on the host."""
+        raise NotImplementedError
+
     def tf_forward(self, x):
         raise NotImplementedError
 
@@ -37,6 +41,9 @@ class Identity(Transform):
     def backward(self, y):
         return y
 
+    def dforward(self, x):
+        return np.ones_like(np.asarray(x, dtype=np.float64))
+
     def tf_forward(self, x):
         return G.as_tensor(x)
 
@@ -58,6 +65,9 @@ class Exp(Transform):
 
     def backward(self, y):
         return np.log(np.asarray(y, dtype=np.float64) - self._lower)
+
+    def dforward(self, x):
+        return np.exp(np.asarray(x, dtype=np.float64))
 
     def tf_forward(self, x):
         return G.affine(G.unary("EXP", x), 1.0, self._lower)
@@ -84,6 +94,10 @@ class Log1pe(Transform):
         # log(exp(y) - 1), stable for large y
         return y + np.log(-np.expm1(-y))
 
+    def dforward(self, x):
+        # the sigmoid, stable for both signs
+        return np.exp(-np.logaddexp(0.0, -np.asarray(x, dtype=np.float64)))
+
     def tf_forward(self, x):
         return G.affine(G.unary("SOFTPLUS", x), 1.0, self._lower)
 
@@ -108,6 +122,10 @@ class Logistic(Transform):
     def backward(self, y):
         y = np.asarray(y, dtype=np.float64)
         return -np.log((self.b - self.a) / (y - self.a) - 1.0)
+
+    def dforward(self, x):
+        s = np.exp(-np.logaddexp(0.0, -np.asarray(x, dtype=np.float64)))
+        return (self.b - self.a) * s * (1.0 - s)
 
     def tf_forward(self, x):
         return G.affine(G.unary("SIGMOID", x), self.b - self.a, self.a)

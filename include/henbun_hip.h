@@ -47,7 +47,8 @@ extern "C" {
  * enum values HB_SGP_FULLRANK, HB_SGP_S_DIAG, HB_SGP_S_TRIL (closed-form predictive moments); hb_sgp_predict_cov_f32 /
  * _f64 and hb_sgp_predict_cov_ws_elems (full predictive covariance); hb_sgp_stats_f32 / _f64 and hb_sgp_stats_ws_elems
  * (sufficient statistics of the closed-form optimal q(u)); hb_sgp_select_f32 / _f64 and hb_sgp_select_ws_elems (greedy
- * conditional-variance selection of inducing points). */
+ * conditional-variance selection of inducing points); hb_sgp_kgrad_f32 / _f64 and hb_sgp_kgrad_ws_elems (streamed part
+ * of the gradient of the collapsed bound). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -59,7 +60,8 @@ const char* hb_last_error_string(void);
  * mm_force_bt, mm_force_s, sgp_no_strip, sgp_force_strip, sgp_tiled_crossover, sgp_strip_form2, sgp_no_fused_finish,
  * lbar_force_s, lbar_no_lds, sgp_stats_no_A, sgp_stats_no_syrk (hb_sgp_stats_* without its first / second pass: timing
  * only, the outputs are then meaningless), sgp_stats_target_wg (tiles x K-splits aimed at; hb_sgp_stats_ws_elems follows), sgp_select_block (64 / 256: the workgroup
- * size of hb_sgp_select_*; the results do not depend on it).  hb_debug_clear() drops every entry. */
+ * size of hb_sgp_select_*; the results do not depend on it), sgp_kgrad_plain (hb_sgp_kgrad_* in its plain-loop form for
+ * every shape).  hb_debug_clear() drops every entry. */
 int hb_debug_set(const char* key, long value);
 int hb_debug_clear(void);
 /* device name / arch of the current device into (host) buf; returns 0 or hipError */
@@ -643,6 +645,22 @@ int hb_sgp_select_f32(int kind, const float* X, const float* ell, long dl, long 
                       float* pivots, long* count, double* trace, float* ws, void* stream);
 int hb_sgp_select_f64(int kind, const double* X, const double* ell, long dl, long N, long M, long d, double threshold,
                       long* idx, double* pivots, long* count, double* trace, double* ws, void* stream);
+/* Streamed part of the gradient of the collapsed bound (csrc/sgp_cbgrad.hip; not in the reference).  With K = k(z, X)
+ * [M, N] and the weights Q [M, M], R [M, P] of the M^3 tail (SparseGP.collapsed_bound_and_grad):
+ *   Kbar = Q K + R Y^T,  E = Kbar o K,
+ *   zbar[i, k] = -sum_j E_ij (z_ik - x_jk) / ell_k^2,   ellbar[k] = sum_ij E_ij (z_ik - x_jk)^2 / ell_k^3
+ * (dl == 1: ellbar [1], summed over k).  Kbar is never written.  The suffix is the STORAGE type of X [N, d] and Y [N, P]
+ * only: z, ell, Q, R, zbar [M, d], ellbar [dl], the workspace and all arithmetic are double (the z gradient of the bound
+ * is a difference of two terms about 1000 times its size).  kind must be HB_KERN_RBF; N, M, d, P >= 1,
+ * d <= 256, P <= 256, M + d + P <= 8000.  M % 16 == 0, M <= 512, d <= 4, P <= 4: column strips of 32 on
+ * v_mfma_f64_16x16x4_f64 with K synthesised in LDS, at most 256 strips; every other shape: plain double loops.  A second
+ * launch folds the strips' partials in strip order (no atomics, no flags): two calls on the same inputs return the same
+ * bits.  Outputs are overwritten.  ws >= hb_sgp_kgrad_ws_elems(N, M, d, P) doubles, 16-byte aligned; independent of N. */
+long hb_sgp_kgrad_ws_elems(long N, long M, long d, long P);
+int hb_sgp_kgrad_f32(int kind, const float* X, const float* Y, const double* z, const double* ell, long dl, const double* Q,
+                     const double* R, double* zbar, double* ellbar, long N, long M, long d, long P, double* ws, void* stream);
+int hb_sgp_kgrad_f64(int kind, const double* X, const double* Y, const double* z, const double* ell, long dl, const double* Q,
+                     const double* R, double* zbar, double* ellbar, long N, long M, long d, long P, double* ws, void* stream);
 /* VJP given fbar [E,P,n]:
  *   Abar = u^T fbar + A diag(c),  c = -eps sign(v)/sqrt|v| * sum_p fbar_p
  *   Kbar = W^T Abar            [E,M,n]  (scratch output, kept for Lbar)
