@@ -77,6 +77,7 @@ _SIGS = {
     "hb_chain_discard": [],
     "hb_chain_source": [P, L],
     "hb_chain_compile_dry": [],
+    "hb_chain_stamps": [P, L],
     "hb_comm_available": [],
     "hb_comm_unique_id": [P],
     "hb_comm_init": [P, I, I, P],

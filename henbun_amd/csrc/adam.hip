@@ -55,6 +55,10 @@ static int adam_launch(T* theta, const T* g, T* m, T* v, long n, double lr, doub
       j.p[0] = theta, j.p[1] = g, j.p[2] = m, j.p[3] = v, j.p[4] = t, j.p[5] = info, j.p[6] = dpflag, j.p[7] = fail;
       j.l[0] = n, j.l[1] = n_info, j.l[2] = tick;
       j.d[0] = lr, j.d[1] = b1, j.d[2] = b2, j.d[3] = eps, j.d[4] = gscale;
+      const long nb = n * (long)sizeof(T);
+      j.span(0, nb, HB_CHAIN_RW), j.span(1, nb, HB_CHAIN_READ), j.span(2, nb, HB_CHAIN_RW), j.span(3, nb, HB_CHAIN_RW);
+      j.span(4, sizeof(long), HB_CHAIN_RW), j.span(5, n_info * (long)sizeof(int), HB_CHAIN_READ);
+      j.span(6, sizeof(T), HB_CHAIN_READ), j.span(7, 2 * sizeof(long), HB_CHAIN_RW);
       return hb_chain_push(j, stream);
     }
     const int crc = hb_chain_flush(stream);

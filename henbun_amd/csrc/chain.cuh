@@ -10,6 +10,11 @@
 // Only entry points that know about chains may be called between begin and end (henbun_amd/graph.py wraps exactly those
 // steps): hb_ewise_jit_run, hb_gauss_ll, hb_adam_step, hb_sgp_fwd (its finishing pass), hb_gram_bwd (its lengthscale fold).
 // Where hiprtc is unavailable hb_chain_begin records nothing and every call launches as usual.
+//
+// The generated kernel does not load job by job: whatever a job reads that no earlier job of the chain writes is final
+// when the kernel starts, and is requested in ONE load phase in front of the first job; the few values one job hands to
+// the next travel through LDS (slots for one-element results, windows for arrays) next to their stores to memory.  The
+// spans below (HbChainJob::ext / role) are what that classification works from; csrc/jit.hip, chain_source_hoist.
 #ifndef HB_CHAIN_CUH
 #define HB_CHAIN_CUH
 #include "common.cuh"
@@ -27,6 +32,8 @@ enum { HB_CHAIN_PROG = 1, HB_CHAIN_ADAM = 2, HB_CHAIN_GLL = 3, HB_CHAIN_SGP_FINI
 #define HB_CHAIN_ELL_MAX_N 16384      // partials of a lengthscale fold
 #define HB_CHAIN_GLL_FOLD_MAX_N 4096  // units of a likelihood-head fold
 
+enum { HB_CHAIN_READ = 1, HB_CHAIN_WRITE = 2, HB_CHAIN_RW = 3 };
+
 struct HbChainJob {
   int kind = 0, is64 = 0;
   const void* p[HB_PROG_MAX_IN + HB_PROG_MAX_OUT] = {};   // pointers (programs: the nin inputs, then the nout outputs)
@@ -34,6 +41,15 @@ struct HbChainJob {
   double d[8] = {};
   ProgArgs prog;      // HB_CHAIN_PROG: the validated descriptor
   int reduces = 0;
+  // What the job reaches through p[k]: `ext[k]` bytes from p[k] on (0 for a NULL pointer), read, written or both.  Filled
+  // where the job is recorded (hb_chain_span); the generator classifies every input by range overlap with the outputs of
+  // the jobs in front of it (csrc/jit.hip, chain_source).
+  long ext[HB_PROG_MAX_IN + HB_PROG_MAX_OUT] = {};
+  unsigned char role[HB_PROG_MAX_IN + HB_PROG_MAX_OUT] = {};
+  void span(int k, long bytes, int r) {
+    ext[k] = p[k] != nullptr && bytes > 0 ? bytes : 0;
+    role[k] = (unsigned char)r;
+  }
 };
 
 bool hb_chain_recording();

@@ -887,6 +887,10 @@ static int gauss_ll(const T* x, const T* f, const T* scale, const T* var, long n
       j.p[8] = fbar;
       j.l[0] = n;
       j.d[0] = post;
+      const long nbytes = n * (long)sizeof(T), one = sizeof(T);
+      j.span(0, nbytes, HB_CHAIN_READ), j.span(1, nbytes, HB_CHAIN_READ), j.span(2, one, HB_CHAIN_READ), j.span(3, one, HB_CHAIN_READ);
+      j.span(4, nbytes, HB_CHAIN_WRITE), j.span(5, one, HB_CHAIN_WRITE), j.span(6, one, HB_CHAIN_WRITE), j.span(7, one, HB_CHAIN_WRITE);
+      j.span(8, nbytes, HB_CHAIN_WRITE);
       return hb_chain_push(j, stream);
     }
     const int crc = hb_chain_flush(stream);
@@ -933,6 +937,8 @@ static int gauss_fold(const T* partial, long nb, T* ll, T* dscale, T* dvar, hipS
       j.is64 = sizeof(T) == 8;
       j.p[0] = partial, j.p[1] = ll, j.p[2] = dscale, j.p[3] = dvar;
       j.l[0] = nb;
+      j.span(0, 3 * nb * (long)sizeof(T), HB_CHAIN_READ);
+      j.span(1, sizeof(T), HB_CHAIN_WRITE), j.span(2, sizeof(T), HB_CHAIN_WRITE), j.span(3, sizeof(T), HB_CHAIN_WRITE);
       return hb_chain_push(j, stream);
     }
     const int crc = hb_chain_flush(stream);

@@ -189,6 +189,7 @@ static int gram_bwd(int kind_flags, const T* X, long sX, const T* X2, long sX2, 
         j.is64 = sizeof(T) == 8;
         j.p[0] = ws, j.p[1] = ellbar;
         j.l[0] = rows_, j.l[1] = d, j.l[2] = dl, j.l[3] = groups_;
+        j.span(0, groups_ * rows_ * d * (long)sizeof(T), HB_CHAIN_READ), j.span(1, groups_ * dl * (long)sizeof(T), HB_CHAIN_WRITE);
         return hb_chain_push(j, stream);
       }
       if (sEll != 0)
@@ -216,6 +217,7 @@ static int gram_ell_fold(const T* partial, long rows, long d, long dl, long grou
     j.is64 = sizeof(T) == 8;
     j.p[0] = partial, j.p[1] = ellbar;
     j.l[0] = rows, j.l[1] = d, j.l[2] = dl, j.l[3] = groups;
+    j.span(0, groups * rows * d * (long)sizeof(T), HB_CHAIN_READ), j.span(1, groups * dl * (long)sizeof(T), HB_CHAIN_WRITE);
     return hb_chain_push(j, stream);
   }
   if (hb_chain_recording()) {

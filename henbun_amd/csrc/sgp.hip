@@ -2158,6 +2158,9 @@ static int sgp_fwd(int kind, int mode, const T* x, long sx, const T* z, const T*
       j.p[4] = f;
       j.p[5] = v;
       j.l[0] = gyp, j.l[1] = rng_lanes, j.l[2] = total, j.l[3] = n, j.l[4] = P, j.l[5] = mode == HB_SGP_DIAGONAL;
+      const long tb = total * (long)sizeof(T);
+      j.span(0, tb * gyp * 5, HB_CHAIN_READ), j.span(1, tb, HB_CHAIN_READ), j.span(2, 2 * rng_lanes * (long)sizeof(uint64_t), HB_CHAIN_RW);
+      j.span(3, tb, HB_CHAIN_WRITE), j.span(4, tb * P, HB_CHAIN_WRITE), j.span(5, tb, HB_CHAIN_WRITE);
       return hb_chain_push(j, stream);
     }
     const int fgrid = draw ? hb_cdiv(rng_lanes, 256) : hb_stream_grid((total + 1) / 2, 256);

@@ -747,6 +747,11 @@ int hb_chain_source(char* out, long cap);
 /* hb_chain_compile_dry: compile the kernel of the recorded jobs for gfx950 without loading or launching it (no device
  * needed), drop the jobs and stop recording: the build / CPU check of the generated chains. */
 int hb_chain_compile_dry(void);
+/* hb_chain_stamps: diagnostics of a chain generated under hb_debug_set("chain_stamps", 1): thread 0 of the chain kernel
+ * keeps clock stamps (kernel entry, end of the load phase, end of every job) and stores them when it ends; out[0] = their
+ * number, out[1..] the stamps of the chain that ran last.  Synchronises the device; the first call allocates the buffer
+ * (call it once before capturing a stream). */
+int hb_chain_stamps(unsigned long long* out, long cap);
 
 /* ---- data-parallel exchange step (no reference counterpart: the reference is one tf.Session on one
  *      device, model.py:57,255-269) --------------------------------------------------
