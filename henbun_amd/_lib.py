@@ -51,6 +51,8 @@ _SIGS = {
     "hb_sgp_stats_ws_elems": [L, L, L, L, I],
     "hb_sgp_select_ws_elems": [L, L, L, I],
     "hb_sgp_kgrad_ws_elems": [L, L, L, L],
+    "hb_sgp_wstats_ws_elems": [L, L, L, I],
+    "hb_lik_sites_ws_elems": [L],
     "hb_matmul_gauss_units": [L, L, L],
     "hb_matmul_gram_vjp_ok": [L, L, L, L],
     "hb_matmul_gram_vjp_ws_elems": [L, L, L],
@@ -87,7 +89,7 @@ _RESTYPES = {"hb_last_error_string": c_char_p, "hb_sgp_ws_elems": c_long, "hb_ew
              "hb_sgp_head_units": c_long, "hb_matmul_gauss_units": c_long, "hb_matmul_gram_vjp_ws_elems": c_long, "hb_cholesky_inverse_ws_elems": c_long, "hb_mlp2_sample_ws_elems": c_long,
              "hb_sgp_predict_ws_elems": c_long, "hb_sgp_predict_cov_ws_elems": c_long,
              "hb_sgp_stats_ws_elems": c_long, "hb_sgp_select_ws_elems": c_long,
-             "hb_sgp_kgrad_ws_elems": c_long}
+             "hb_sgp_kgrad_ws_elems": c_long, "hb_sgp_wstats_ws_elems": c_long, "hb_lik_sites_ws_elems": c_long}
 
 # entry points that exist as _f32 and _f64
 _TYPED = {
@@ -128,6 +130,9 @@ _TYPED = {
     "hb_sgp_predict": [I, P, L, P, P, L, P, P, P, P, I, I, D, P, P, L, L, L, L, L, P, P],
     "hb_sgp_predict_cov": [I, P, L, P, P, L, P, P, P, I, I, D, P, L, L, L, L, L, P, P],
     "hb_sgp_stats": [I, P, P, P, P, L, P, P, P, P, P, P, L, L, L, L, P, P],
+    "hb_sgp_wstats": [I, P, P, P, P, P, L, P, P, P, P, P, L, L, L, P, P],
+    "hb_lik_sites": [I, P, P, P, D, D, D, P, P, P, L, P, P],
+    "hb_lik_predict": [I, P, P, D, P, P, L, P],
     "hb_sgp_select": [I, P, P, L, L, L, L, D, P, P, P, P, P, P],
     "hb_sgp_kgrad": [I, P, P, P, P, L, P, P, P, P, L, L, L, L, P, P],
     "hb_adam_step": [P, P, P, P, L, D, D, D, D, D, P, I, P, L, P, P, P],

@@ -55,9 +55,13 @@ struct StatsArgs {
   long T, nt;       // lower-triangle tiles, tile rows
   float* part;      // [splits][T][128 x 128]
   float* bpart;     // [splits][nt][P][128]
+  const float* w;   // WGT: weights of the chunk's columns [nc], 16-byte aligned
 };
 
-template <bool VEC>
+// WGT (hb_sgp_wstats_*): Phi_w = A diag(w) A^T.  The column panel is staged as A_c diag(w) -- one 16-byte load of w per
+// thread and stage, the product taken on the way from the global load to LDS -- and the row panel as A_c itself, on the
+// diagonal tiles too, so weights of either sign and zeros need no root; b comes from the unweighted row panel.
+template <bool VEC, bool WGT>
 __global__ void __launch_bounds__(ST_THREADS) sgp_stats_syrk_kernel(StatsArgs a) {
   typedef Mma<float> MM;
   __shared__ __attribute__((aligned(16))) float smem[2 * ST_STAGE];
@@ -105,6 +109,27 @@ __global__ void __launch_bounds__(ST_THREADS) sgp_stats_syrk_kernel(StatsArgs a)
     for (int q = 0; q < 2; ++q) {
       ri[q] = load4(i0 + lr + 64 * q, k0 + lk);
       rj[q] = diag ? ri[q] : load4(j0 + lr + 64 * q, k0 + lk);
+    }
+    if (WGT) {
+      const long k = k0 + lk;
+      float4 wq = {0.f, 0.f, 0.f, 0.f};
+      if (k < kend) {
+        if (VEC) {
+          wq = *(const float4*)(a.w + k);
+        } else {
+          wq.x = a.w[k];
+          if (k + 1 < kend) wq.y = a.w[k + 1];
+          if (k + 2 < kend) wq.z = a.w[k + 2];
+          if (k + 3 < kend) wq.w = a.w[k + 3];
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        rj[q].x *= wq.x;
+        rj[q].y *= wq.y;
+        rj[q].z *= wq.z;
+        rj[q].w *= wq.w;
+      }
     }
     if (diag && tid < nY) yreg = k0 + tid / a.P < kend ? a.Y[k0 * a.P + tid] : 0.f;
   };
@@ -209,7 +234,7 @@ __device__ __forceinline__ void st_yy_block(const T* __restrict__ Y, long nc, lo
 
 // Phi (lower triangle) and b take the sum of the splits' partials in double, split order; `accumulate` = 0: first chunk.
 // blocks [0, 64 T): one element of one tile per thread; the blocks after them: one entry of b per thread; the last
-// block: yy of the chunk.
+// block: yy of the chunk (yy == NULL, the weighted form: nothing).
 __global__ void __launch_bounds__(256) sgp_stats_fold_kernel(const float* __restrict__ part, const float* __restrict__ bpart,
                                                              long T, long nt, long splits, long M, long P,
                                                              double* __restrict__ Phi, double* __restrict__ b,
@@ -218,7 +243,7 @@ __global__ void __launch_bounds__(256) sgp_stats_fold_kernel(const float* __rest
   __shared__ double red[16];
   const long blk = blockIdx.x;
   if (blk == (long)gridDim.x - 1) {
-    st_yy_block(Y, nc, P, yy, accumulate, red);
+    if (yy) st_yy_block(Y, nc, P, yy, accumulate, red);
   } else if (blk < 64 * T) {
     const long t = blk / 64, e = (blk % 64) * 256 + threadIdx.x;
     long ti = (long)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
@@ -241,9 +266,10 @@ __global__ void __launch_bounds__(256) sgp_stats_fold_kernel(const float* __rest
 }
 
 // plain forms (fp64; fp32 shapes the MFMA form does not take): the whole chunk per thread, in double
-template <typename T>
+template <typename T, bool WGT>
 __global__ void __launch_bounds__(ST_PLAIN_T * ST_PLAIN_T) sgp_stats_plain_phi_kernel(const T* __restrict__ A, long ld, long M,
-                                                                                     long nc, double* __restrict__ Phi,
+                                                                                     long nc, const T* __restrict__ w,
+                                                                                     double* __restrict__ Phi,
                                                                                      int accumulate) {
   if (blockIdx.x > blockIdx.y) return;   // the tile lies above the diagonal
   const long i = (long)blockIdx.y * ST_PLAIN_T + threadIdx.y, j = (long)blockIdx.x * ST_PLAIN_T + threadIdx.x;
@@ -251,7 +277,8 @@ __global__ void __launch_bounds__(ST_PLAIN_T * ST_PLAIN_T) sgp_stats_plain_phi_k
   const T* ai = A + i * ld;
   const T* aj = A + j * ld;
   double s = 0.0;
-  for (long k = 0; k < nc; ++k) s = __builtin_fma((double)ai[k], (double)aj[k], s);
+  for (long k = 0; k < nc; ++k)   // WGT: the weight on the column operand
+    s = __builtin_fma((double)ai[k], WGT ? (double)w[k] * (double)aj[k] : (double)aj[k], s);
   Phi[i * M + j] = accumulate ? Phi[i * M + j] + s : s;
 }
 template <typename T>
@@ -260,7 +287,7 @@ __global__ void __launch_bounds__(256) sgp_stats_plain_b_kernel(const T* __restr
                                                                 double* __restrict__ yy, int accumulate) {
   __shared__ double red[16];
   if (blockIdx.x == gridDim.x - 1) {   // the last block: yy of the chunk
-    st_yy_block(Y, nc, P, yy, accumulate, red);
+    if (yy) st_yy_block(Y, nc, P, yy, accumulate, red);
     return;
   }
   const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -337,18 +364,21 @@ static inline int st_sgp_A(int kind, const double* x, const double* z, const dou
   return hb_sgp_A_f64(kind, x, 0, z, ell, dl, W, Wf, HB_PREC_NATIVE, A, 1, n, M, d, st);
 }
 
-template <typename T>
-static int sgp_stats(int kind, const T* X, const T* Y, const T* z, const T* ell, long dl, const T* W, const T* Wf, double* Phi,
-                     double* b, double* yy, double* a2sum, long N, long M, long d, long P, T* ws, hipStream_t st) {
-  HB_REQUIRE(kind == HB_KERN_RBF, "hb_sgp_stats: only the UnitRBF kernel is supported (kind=%d)", kind);
-  HB_REQUIRE(N >= 1 && M >= 1 && d >= 1 && P >= 1, "hb_sgp_stats: bad extents (N=%ld M=%ld d=%ld P=%ld)", N, M, d, P);
-  HB_REQUIRE(dl == 1 || dl == d, "hb_sgp_stats: lengthscales must have 1 or d entries");
-  HB_REQUIRE(X && Y && z && ell && W, "hb_sgp_stats: NULL input pointer");
-  HB_REQUIRE(Phi && b && yy && a2sum, "hb_sgp_stats: NULL output pointer");
-  HB_REQUIRE(M * M < 2147483647L && M <= 16384, "hb_sgp_stats: M=%ld too large", M);
-  HB_REQUIRE(!Wf || ((uintptr_t)Wf % 16 == 0 && M % 32 == 0), "hb_sgp_stats: Wfrag needs 16-byte alignment and M %% 32 == 0");
+// hb_sgp_stats_* (WGT false: w NULL) and hb_sgp_wstats_* (WGT true: Y is r [N], P = 1, yy NULL) share every launch
+template <typename T, bool WGT>
+static int sgp_stats(const char* who, int kind, const T* X, const T* Y, const T* w, const T* z, const T* ell, long dl, const T* W,
+                     const T* Wf, double* Phi, double* b, double* yy, double* a2sum, long N, long M, long d, long P, T* ws,
+                     hipStream_t st) {
+  HB_REQUIRE(kind == HB_KERN_RBF, "%s: only the UnitRBF kernel is supported (kind=%d)", who, kind);
+  HB_REQUIRE(N >= 1 && M >= 1 && d >= 1 && P >= 1, "%s: bad extents (N=%ld M=%ld d=%ld P=%ld)", who, N, M, d, P);
+  HB_REQUIRE(dl == 1 || dl == d, "%s: lengthscales must have 1 or d entries", who);
+  HB_REQUIRE(X && Y && z && ell && W && (!WGT || w), "%s: NULL input pointer", who);
+  HB_REQUIRE(Phi && b && (WGT || yy) && a2sum, "%s: NULL output pointer", who);
+  HB_REQUIRE(M * M < 2147483647L && M <= 16384, "%s: M=%ld too large", who, M);
+  HB_REQUIRE(!Wf || ((uintptr_t)Wf % 16 == 0 && M % 32 == 0), "%s: Wfrag needs 16-byte alignment and M %% 32 == 0", who);
+  HB_REQUIRE(!WGT || (uintptr_t)w % 16 == 0, "%s: the weights need 16-byte alignment", who);
   const long need = hb_sgp_stats_ws_elems(N, M, d, P, (int)sizeof(T));
-  HB_REQUIRE(ws && (uintptr_t)ws % 16 == 0, "hb_sgp_stats: needs a 16-byte aligned workspace of %ld elements", need);
+  HB_REQUIRE(ws && (uintptr_t)ws % 16 == 0, "%s: needs a 16-byte aligned workspace of %ld elements", who, need);
   const long nc_max = st_chunk_cols(N, M);
   const bool mfma = st_is_mfma(M, P, (int)sizeof(T));
   T* Abuf = ws;
@@ -370,13 +400,14 @@ static int sgp_stats(int kind, const T* X, const T* Y, const T* z, const T* ell,
         st_split(M, nc, &Tn, &nt, &ks, &splits);   // splits <= st_max_splits(Tn): the workspace holds them
         StatsArgs a;
         a.A = Abuf; a.ld = nc; a.Y = Y + c0 * P; a.P = P; a.M = M; a.nc = nc; a.ks = ks; a.T = Tn; a.nt = nt;
+        a.w = WGT ? w + c0 : nullptr;   // c0 is a multiple of 32: the chunk's weights stay 16-byte aligned
         a.part = ws + st_round(M * nc_max);
         a.bpart = a.part + st_round(st_max_splits(Tn) * Tn * ST_TILE);
         const dim3 grid((unsigned)(Tn * splits), 1, 1);
         if (nc % 4 == 0)
-          hipLaunchKernelGGL((sgp_stats_syrk_kernel<true>), grid, dim3(ST_THREADS), 0, st, a);
+          hipLaunchKernelGGL((sgp_stats_syrk_kernel<true, WGT>), grid, dim3(ST_THREADS), 0, st, a);
         else
-          hipLaunchKernelGGL((sgp_stats_syrk_kernel<false>), grid, dim3(ST_THREADS), 0, st, a);
+          hipLaunchKernelGGL((sgp_stats_syrk_kernel<false, WGT>), grid, dim3(ST_THREADS), 0, st, a);
         HB_LAUNCH_CHECK();
         const long fb = 64 * Tn + (P * M + 255) / 256 + 1;
         hipLaunchKernelGGL(sgp_stats_fold_kernel, dim3((unsigned)fb), dim3(256), 0, st, a.part, a.bpart, Tn, nt, splits, M, P,
@@ -386,8 +417,8 @@ static int sgp_stats(int kind, const T* X, const T* Y, const T* z, const T* ell,
       }
     }
     const long nb = (M + ST_PLAIN_T - 1) / ST_PLAIN_T;
-    hipLaunchKernelGGL((sgp_stats_plain_phi_kernel<T>), dim3((unsigned)nb, (unsigned)nb, 1), dim3(ST_PLAIN_T, ST_PLAIN_T), 0, st,
-                       Abuf, nc, M, nc, Phi, accumulate);
+    hipLaunchKernelGGL((sgp_stats_plain_phi_kernel<T, WGT>), dim3((unsigned)nb, (unsigned)nb, 1), dim3(ST_PLAIN_T, ST_PLAIN_T), 0,
+                       st, Abuf, nc, M, nc, WGT ? w + c0 : nullptr, Phi, accumulate);
     HB_LAUNCH_CHECK();
     hipLaunchKernelGGL((sgp_stats_plain_b_kernel<T>), dim3((unsigned)((P * M + 255) / 256 + 1)), dim3(256), 0, st, Abuf, nc,
                        Y + c0 * P, M, P, nc, b, yy, accumulate);
@@ -401,10 +432,28 @@ static int sgp_stats(int kind, const T* X, const T* Y, const T* z, const T* ell,
 extern "C" int hb_sgp_stats_f32(int kind, const float* X, const float* Y, const float* z, const float* ell, long dl,
                                 const float* W, const float* Wfrag, double* Phi, double* b, double* yy, double* a2sum, long N,
                                 long M, long d, long P, float* ws, void* stream) {
-  return sgp_stats<float>(kind, X, Y, z, ell, dl, W, Wfrag, Phi, b, yy, a2sum, N, M, d, P, ws, (hipStream_t)stream);
+  return sgp_stats<float, false>("hb_sgp_stats", kind, X, Y, nullptr, z, ell, dl, W, Wfrag, Phi, b, yy, a2sum, N, M, d, P, ws, (hipStream_t)stream);
 }
 extern "C" int hb_sgp_stats_f64(int kind, const double* X, const double* Y, const double* z, const double* ell, long dl,
                                 const double* W, const double* Wfrag, double* Phi, double* b, double* yy, double* a2sum,
                                 long N, long M, long d, long P, double* ws, void* stream) {
-  return sgp_stats<double>(kind, X, Y, z, ell, dl, W, Wfrag, Phi, b, yy, a2sum, N, M, d, P, ws, (hipStream_t)stream);
+  return sgp_stats<double, false>("hb_sgp_stats", kind, X, Y, nullptr, z, ell, dl, W, Wfrag, Phi, b, yy, a2sum, N, M, d, P, ws, (hipStream_t)stream);
+}
+
+// Weighted statistics of the natural-gradient step on q(u) (SparseGP.natgrad_q): Phi_w = A diag(w) A^T, b = (A r)^T,
+// tr Phi_w -- hb_sgp_stats_* with the weight on the column operand and r in the place of Y (P = 1).
+extern "C" long hb_sgp_wstats_ws_elems(long N, long M, long d, int dtype_bytes) {
+  return hb_sgp_stats_ws_elems(N, M, d, 1, dtype_bytes);
+}
+extern "C" int hb_sgp_wstats_f32(int kind, const float* X, const float* w, const float* r, const float* z, const float* ell,
+                                 long dl, const float* W, const float* Wfrag, double* Phi, double* b, double* tr, long N, long M,
+                                 long d, float* ws, void* stream) {
+  return sgp_stats<float, true>("hb_sgp_wstats", kind, X, r, w, z, ell, dl, W, Wfrag, Phi, b, nullptr, tr, N, M, d, 1, ws,
+                                (hipStream_t)stream);
+}
+extern "C" int hb_sgp_wstats_f64(int kind, const double* X, const double* w, const double* r, const double* z, const double* ell,
+                                 long dl, const double* W, const double* Wfrag, double* Phi, double* b, double* tr, long N,
+                                 long M, long d, double* ws, void* stream) {
+  return sgp_stats<double, true>("hb_sgp_wstats", kind, X, r, w, z, ell, dl, W, Wfrag, Phi, b, nullptr, tr, N, M, d, 1, ws,
+                                 (hipStream_t)stream);
 }

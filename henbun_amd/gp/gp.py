@@ -181,12 +181,35 @@ class SparseGP(GP):
         Phi = A A^T, b = (A Y)^T, yy_p = sum_j Y_jp^2, a2sum = tr Phi, A = Lm^-1 K(z, X), Lm = chol(K(z, z) + jitter I)
         from the fused factor + inverse the plans use.  A failed factorisation raises graph.CholeskyError."""
         sess, zvar, ls = self._stats_session()
-        torch, H = sess.torch, sess.H
         Xd, Yd = self._device_data(sess, X, "X"), self._device_data(sess, Y, "Y")
+        z, ell, W, frag = self._whitening(sess, zvar, ls, Xd, Yd, "statistics")
+        return sess.H.sgp_stats(Xd, Yd, z, ell, W, wfrag=frag)
+
+    def _whitening(self, sess, zvar, ls, Xd, Yd, who, as_plans=False):
+        """(z, ell, W, frag) on the device in the session's dtype: W = chol(K(z, z) + jitter I)^-1 from the fused factor
+        + inverse the plans use, frag its fragment-major images (float32, M % 32 == 0; else None).
+        z and the lengthscales are their transforms of the raw parameters taken on the host in double and rounded;
+        as_plans=True takes them from a plan instead, i.e. as the session's dtype transforms them on the device -- the
+        values predict_f and the ELBO see.  In a float32 session the two can differ in the last bit of a lengthscale,
+        which moves W by cond(K(z, z)) times that; a q(u) that a plan reads must be fitted in the plan's whitening
+        ("Natural-gradient fit")."""
+        torch, H = sess.torch, sess.H
         up = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=sess.np_dtype))).to(sess.device)
-        z, ell = up(sess.read_value(zvar)), up(np.reshape(sess.read_value(ls), [-1]))
+        if as_plans:
+            sess.read_value(zvar), sess.read_value(ls)      # uploads a value that was assigned and not yet written
+            cache = object.__getattribute__(self, "__dict__").setdefault("_whitening_plans", {})
+            key = (id(sess), sess.layout_version, id(zvar), id(ls))
+            if key not in cache:
+                zt, et = zvar.tensor(), G.reshape(ls.tensor(), [-1])
+                cache.clear()
+                cache[key] = (sess.make_plan([zt, et]), zt, et)
+            plan, zt, et = cache[key]
+            plan.run()
+            z, ell = plan.buf(zt).clone().contiguous(), plan.buf(et).clone().contiguous()
+        else:
+            z, ell = up(sess.read_value(zvar)), up(np.reshape(sess.read_value(ls), [-1]))
         if Xd.shape[0] != Yd.shape[0] or Xd.shape[1] != z.shape[1]:
-            raise ValueError("statistics: X %s, Y %s do not match z %s" % (tuple(Xd.shape), tuple(Yd.shape), tuple(z.shape)))
+            raise ValueError("%s: X %s, Y %s do not match z %s" % (who, tuple(Xd.shape), tuple(Yd.shape), tuple(z.shape)))
         M = z.shape[0]
         K = H.gram_fwd(z, z, ell, diag_add=float(settings.numerics.jitter_level))
         frag = None
@@ -195,8 +218,8 @@ class SparseGP(GP):
         _, W, info = H.cholesky_inverse(K, frag=frag)
         bad = int(info.cpu()[0])
         if bad != 0:
-            raise G.CholeskyError("statistics: leading minor %d of K(z, z) + jitter I is not positive definite" % bad)
-        return H.sgp_stats(Xd, Yd, z, ell, W, wfrag=frag)
+            raise G.CholeskyError("%s: leading minor %d of K(z, z) + jitter I is not positive definite" % (who, bad))
+        return z, ell, W, frag
 
     def select_inducing(self, X, threshold=None):
         """Move z to the M = z.shape[0] rows of X [N, d] that greedy conditional-variance selection picks at the CURRENT
@@ -303,6 +326,91 @@ class SparseGP(GP):
         if residual == "diagonal":
             val -= P * k_var * (N - a2sum) / (2.0 * noise_var)
         return val
+
+    def natgrad_q(self, X, Y, likelihood, k_var=1.0, residual="diagonal", q0=None, steps=20, rho=1.0, tol=1e-8):
+        """Natural-gradient fit of q(u) = N(m, S S^T) for a factorising likelihood (henbun_amd.likelihoods: Gaussian,
+        Bernoulli, Poisson) at fixed hyper-parameters, for the whitened model u ~ N(0, I), f = sqrt(k_var) (u A +
+        residual), y_j ~ p(y_j | f_j).  q is kept as Lambda = (S S^T)^-1, eta = Lambda m; one step is the conjugate
+        update with per-point pseudo-observations (conjugate-computation VI, Khan & Lin 2017):
+            mu_j, v_j            the marginals of f_j under q                         (hb_sgp_predict, one pass over X)
+            lam_j, beta_j, l_j   E[-d2 log p], E[d log p] + lam_j mu_j, E[log p]      (hb_lik_sites)
+            Phi = A diag(lam) A^T,  b = A beta                                        (hb_sgp_wstats, one pass over X)
+            Lambda <- (1 - rho) Lambda + rho (I + k_var Phi),   eta <- (1 - rho) eta + rho sqrt(k_var) b
+        and m = Lambda^-1 eta, S = chol(Lambda^-1) from the float64 tail of optimal_q.  With the Gaussian likelihood one
+        step at rho = 1 is optimal_q.  K(z, z) is factorised once per call, from z and the lengthscales as the session's
+        plans transform them on the device, so the q(u) returned lives in the whitening predict_f and the ELBO use.
+        Returns (m [1, M], S [M, M] lower with a positive diagonal, info) as float64 numpy; info = dict(elbo, residual,
+        steps): the ELBO sum_j l_j - KL(q || N(0, I)) and the fixed-point residual max|Lambda - (I + k_var Phi)| /
+        max|I + k_var Phi| at every iterate, the starting one included (steps + 1 entries), and the steps taken.  m, S
+        are the last iterate evaluated.  q0=None starts at the prior; q0 = (m, S) at a given full-rank q.  Stops when
+        the relative change of the ELBO is <= tol, or after `steps`.  X, Y as for statistics(), Y [N, 1].  Same
+        restrictions and exception types as statistics(); residual 'fullrank' and a mean-field q0 raise
+        NotImplementedError; a Lambda that is not positive definite raises graph.CholeskyError.  A full step (rho = 1)
+        is not guaranteed to raise the ELBO from a q far from the optimum (info['elbo'] shows an overshoot): start at
+        the prior or damp with rho < 1."""
+        from ..likelihoods import Likelihood
+
+        self._check_residual(residual)
+        if not isinstance(likelihood, Likelihood):
+            raise TypeError("natgrad_q: likelihood must be a henbun_amd.likelihoods.Likelihood, got %s" % type(likelihood).__name__)
+        k_var, rho, steps = float(k_var), float(rho), int(steps)
+        if not (k_var > 0.0 and 0.0 < rho <= 1.0 and steps >= 0):
+            raise ValueError("natgrad_q: k_var > 0, 0 < rho <= 1 and steps >= 0 expected (got %r, %r, %r)" % (k_var, rho, steps))
+        sess, zvar, ls = self._stats_session()
+        torch, H = sess.torch, sess.H
+        Xd, Yd = self._device_data(sess, X, "X"), self._device_data(sess, Y, "Y")
+        if Yd.shape[1] != 1:
+            raise NotImplementedError("natgrad_q: one latent function only (Y must be [N, 1], got %s)" % (tuple(Yd.shape),))
+        z, ell, W, frag = self._whitening(sess, zvar, ls, Xd, Yd, "natgrad_q", as_plans=True)
+        N, d, M = Xd.shape[0], Xd.shape[1], z.shape[0]
+        f64 = dict(dtype=torch.float64, device=sess.device)
+        if q0 is None:
+            Lam, eta = torch.eye(M, **f64), torch.zeros((1, M), **f64)
+        else:
+            m0, S0 = (np.asarray(a, dtype=np.float64) for a in q0)
+            if S0.ndim != 2:
+                raise NotImplementedError("natgrad_q: q0 must be a full-rank q, (m [1, M], S [M, M]); a mean-field q "
+                                          "does not stay mean-field under the update")
+            if m0.size != M or S0.shape != (M, M):
+                raise ValueError("natgrad_q: q0 = (m [1, %d], S [%d, %d]) expected, got %s %s" % (M, M, M, m0.shape, S0.shape))
+            Sinv = H.trinv(torch.as_tensor(np.ascontiguousarray(np.tril(S0))).to(sess.device))
+            Lam = H.matmul(Sinv, Sinv, transA=True)
+            eta = H.matmul(torch.as_tensor(np.ascontiguousarray(m0.reshape(1, M))).to(sess.device), Lam)
+        mode = H.SGP_DIAGONAL if residual == "diagonal" else H.SGP_NEGLECTED
+        fused = bool(getattr(settings.runtime, "fused_predict", True)) and H.sgp_predict_fused(
+            sess.torch_dtype, 1, N, M, d, 1, H.SGP_S_TRIL, frag is not None)
+        mean = torch.empty((1, N), dtype=sess.torch_dtype, device=sess.device)
+        var, lam, beta = (torch.empty_like(mean) for _ in range(3))
+        eye = torch.eye(M, **f64)
+        elbo, resid = [], []
+        for it in range(steps + 1):
+            # the float64 tail of optimal_q: Lambda = L L^T, V = L^-1, m = eta V^T V, S = chol(V^T V)
+            L, info = H.cholesky(Lam.contiguous())
+            bad = int(info.cpu()[0])
+            if bad != 0:
+                raise G.CholeskyError("natgrad_q: leading minor %d of Lambda is not positive definite (step %d)" % (bad, it))
+            V = H.trinv(L)
+            m = H.matmul(H.matmul(eta.contiguous(), V, transB=True), V)
+            Sig = H.matmul(V, V, transA=True)
+            S, info = H.cholesky(Sig)
+            bad = int(info.cpu()[0])
+            if bad != 0:
+                raise G.CholeskyError("natgrad_q: leading minor %d of Lambda^-1 is not positive definite (step %d)" % (bad, it))
+            H.sgp_predict(Xd, z, ell, W, m.to(sess.torch_dtype), S.to(sess.torch_dtype), s_kind=H.SGP_S_TRIL, mode=mode,
+                          out=(mean, var), wfrag=frag if fused else None)
+            _, _, lsum = H.lik_sites(likelihood.lik_id, Yd, mean, var, param=likelihood.param, mscale=np.sqrt(k_var),
+                                     vscale=k_var, out=(lam, beta))
+            Phi, b, _ = H.sgp_wstats(Xd, lam, beta, z, ell, W, wfrag=frag)
+            Lt, et = Phi * k_var + eye, b * np.sqrt(k_var)
+            kl = 0.5 * (float(torch.diagonal(Sig).sum().cpu()) + float((m * m).sum().cpu()) - M
+                        + 2.0 * float(np.log(np.diagonal(L.cpu().numpy())).sum()))
+            elbo.append(float(lsum.cpu()[0]) - kl)
+            resid.append(float(((Lam - Lt).abs().max() / Lt.abs().max()).cpu()))
+            if it == steps or (it > 0 and abs(elbo[-1] - elbo[-2]) <= tol * abs(elbo[-1])):
+                break
+            Lam, eta = (1.0 - rho) * Lam + rho * Lt, (1.0 - rho) * eta + rho * et
+        return (m.cpu().numpy(), np.tril(S.cpu().numpy()),
+                dict(elbo=np.asarray(elbo), residual=np.asarray(resid), steps=it))
 
     def collapsed_bound_and_grad(self, X, Y, noise_var, k_var=1.0, residual="diagonal"):
         """(value, grad): the collapsed bound of collapsed_bound() and its exact gradient with respect to the CONSTRAINED

@@ -1127,6 +1127,69 @@ def sgp_stats(X, Y, z, ell, W, wfrag=None, ws=None):
     return Phi, b, yy, a2sum
 
 
+def sgp_wstats_ws_elems(dtype, N, M, d):
+    """Scratch elements hb_sgp_wstats needs (those of hb_sgp_stats with P = 1; the same for every N above one chunk)."""
+    return int(_lib.lib().raw("hb_sgp_wstats_ws_elems")(int(N), int(M), int(d), 4 if dtype == torch.float32 else 8))
+
+
+def sgp_wstats(X, w, r, z, ell, W, wfrag=None, ws=None):
+    """Weighted statistics (hb_sgp_wstats): with A = W K(z, X) [M, N], (Phi = A diag(w) A^T [M, M], b = (A r)^T [1, M],
+    tr Phi [1]) as FLOAT64 device tensors.  X [N, d], w [N] (any sign, zeros included), r [N], z [M, d], ell [dl],
+    W [M, M]; one expert.  Phi is bitwise symmetric; two calls return the same bits; w == 1 gives the bits of sgp_stats."""
+    for t in (X, w, r, z, ell, W):
+        _chk(t)
+    if X.dim() != 2 or z.dim() != 2 or X.shape[1] != z.shape[1] or w.numel() != X.shape[0] or r.numel() != X.shape[0]:
+        raise ValueError("sgp_wstats: X [N, d], w [N], r [N], z [M, d] expected, got %s %s %s %s"
+                         % (tuple(X.shape), tuple(w.shape), tuple(r.shape), tuple(z.shape)))
+    dt, dev = X.dtype, X.device
+    if any(t.dtype != dt for t in (w, r, z, ell, W)):
+        raise TypeError("sgp_wstats: all operands must share one dtype")
+    N, d = X.shape
+    M = z.shape[0]
+    Phi = _empty((M, M), dtype=torch.float64, device=dev)
+    b = _empty((1, M), dtype=torch.float64, device=dev)
+    tr = _empty((1,), dtype=torch.float64, device=dev)
+    if ws is None:
+        ws = workspace(dt, dev, max(sgp_wstats_ws_elems(dt, N, M, d), 1))
+    assert ws.numel() >= sgp_wstats_ws_elems(dt, N, M, d), "hb_sgp_wstats: workspace too small (sgp_wstats_ws_elems)"
+    _lib.lib().call("hb_sgp_wstats" + _suf(X), KERN_RBF, _p(X), _p(w), _p(r), _p(z), _p(ell), ell.numel(), _p(W), _p(wfrag),
+                    _p(Phi), _p(b), _p(tr), N, M, d, _p(ws), stream())
+    return Phi, b, tr
+
+
+LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON = 0, 1, 2
+
+
+def lik_sites(lik, y, mean, var, param=1.0, mscale=1.0, vscale=1.0, out=None):
+    """Sites of a factorising likelihood under f_j ~ N(mscale mean_j, vscale var_j) (hb_lik_sites): (lam [N], beta [N]) in
+    the dtype of the inputs and sum_j E[log p(y_j | f_j)] as a float64 device tensor [1].  lik: LIK_GAUSSIAN (param = the
+    variance), LIK_BERNOULLI (logit link), LIK_POISSON (exp link).  Double arithmetic; two calls return the same bits."""
+    for t in (y, mean, var):
+        _chk(t)
+    N = y.numel()
+    if mean.numel() != N or var.numel() != N or mean.dtype != y.dtype or var.dtype != y.dtype:
+        raise ValueError("lik_sites: y, mean, var must hold N elements of one dtype")
+    lam, beta = out if out is not None else (_empty((N,), dtype=y.dtype, device=y.device),
+                                             _empty((N,), dtype=y.dtype, device=y.device))
+    ell = _empty((1,), dtype=torch.float64, device=y.device)
+    ws = workspace(torch.float64, y.device, int(_lib.lib().raw("hb_lik_sites_ws_elems")(N)))
+    _lib.lib().call("hb_lik_sites" + _suf(y), int(lik), _p(y), _p(mean), _p(var), float(mscale), float(vscale), float(param),
+                    _p(lam), _p(beta), _p(ell), N, _p(ws), stream())
+    return lam, beta, ell
+
+
+def lik_predict(lik, mean, var, param=1.0):
+    """(mean, variance) of a new observation y given f ~ N(mean, var) elementwise (hb_lik_predict), shaped like `mean`."""
+    _chk(mean)
+    _chk(var)
+    if mean.shape != var.shape or mean.dtype != var.dtype:
+        raise ValueError("lik_predict: mean and var must share shape and dtype")
+    ym, yv = _empty_like(mean), _empty_like(mean)
+    _lib.lib().call("hb_lik_predict" + _suf(mean), int(lik), _p(mean), _p(var), float(param), _p(ym), _p(yv), mean.numel(),
+                    stream())
+    return ym, yv
+
+
 def sgp_kgrad_ws_elems(N, M, d, P):
     """Scratch DOUBLES hb_sgp_kgrad needs: the repacked Q and one partial per strip -- independent of N."""
     return int(_lib.lib().raw("hb_sgp_kgrad_ws_elems")(int(N), int(M), int(d), int(P)))

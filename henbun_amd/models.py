@@ -173,6 +173,68 @@ class SVGP(hb.model.Model):
         return np.asarray(trace)
 
 
+class SVGPLik(hb.model.Model):
+    """Sparse variational GP with a non-conjugate factorising likelihood (hb.likelihoods: Bernoulli, Poisson, Gaussian)
+    and a full-rank q(u): SVGP's latent model, the sampled ELBO with likelihood.logp, and a deterministic fit of q(u) by
+    natural-gradient steps (SparseGP.natgrad_q)."""
+
+    def setUp(self, X, Y, Z, likelihood, residual="diagonal", eps=None):
+        self.N = X.shape[0]
+        self.X = hb.param.MinibatchData(X)
+        self.Y = hb.param.MinibatchData(Y)
+        self.gp = hb.gp.SparseGP(kern=hb.gp.kernels.UnitRBF(np.ones(1)), z=Z)
+        self.u = hb.variationals.Normal(shape=[1, Z.shape[0]], q_shape="fullrank")
+        self.k_var = hb.param.Variable([1], transform=hb.transforms.positive)
+        self.likelihood = likelihood
+        self.residual = residual
+        self.eps = None if eps is None else hb.param.MinibatchData(eps)  # injected residual noise (parity runs)
+
+    @hb.model.AutoOptimize()
+    def ELBO(self):
+        f = self.gp.samples(self.X, self.u, q_shape=self.residual, eps=self.eps) * tf.sqrt(self.k_var)
+        n = tf.shape(self.X)[0]
+        ll = tf.reduce_sum(self.likelihood.logp(f, tf.transpose(self.Y)))
+        return (self.N / n) * ll - self.KL()
+
+    _predict = SVGP._predict                      # reads gp, u, k_var and residual only when no noise is asked for
+    predict_f = SVGP.predict_f
+    predict_f_samples = SVGP.predict_f_samples
+    select_inducing = SVGP.select_inducing
+
+    def predict_y(self, Xnew):
+        """Mean and variance [1, n] of a new observation y at Xnew [n, 1]: the likelihood's predictive under the
+        Gaussian marginals of predict_f (hb_lik_predict)."""
+        mean, var = self.predict_f(Xnew)
+        sess = self._session
+        torch, lik = sess.torch, object.__getattribute__(self, "likelihood")
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=sess.np_dtype)).to(sess.device)
+        ym, yv = sess.H.lik_predict(lik.lik_id, up(mean), up(var), param=lik.param)
+        return ym.cpu().numpy(), yv.cpu().numpy()
+
+    def fit_q(self, steps=20, rho=1.0, tol=1e-8):
+        """Fit q(u) at the current z, lengthscales and k_var by natural-gradient steps from the model's CURRENT q, over
+        the model's full device-resident X, Y (SparseGP.natgrad_q: per step one marginals pass, the sites, one weighted
+        statistics pass and the M^3 tail; no minibatch, no Adam step).  u.q_mu / u.q_sqrt are written as SVGP.fit_q
+        writes them for 'fullrank'.  Returns (m [1, M], S [M, M], info) as natgrad_q does.  A full step (rho = 1) from a q
+        far from the optimum, such as a freshly initialised one, can overshoot before it settles: info['elbo'] shows it,
+        and rho < 1 damps it."""
+        from henbun_amd.param import tri_pack, tri_unpack
+
+        self.initialize()
+        g = lambda k: object.__getattribute__(self, k)
+        q, sess = g("u"), self._session
+        q_mu, q_sqrt = object.__getattribute__(q, "q_mu"), object.__getattribute__(q, "q_sqrt")
+        M = q.size
+        S0 = np.asarray(sess.read_raw(q_sqrt), dtype=np.float64)
+        S0 = tri_unpack(S0.reshape(-1)) if q.packed else np.tril(S0.reshape(M, M))
+        m0 = np.asarray(sess.read_raw(q_mu), dtype=np.float64).reshape(1, M)
+        m, S, info = g("gp").natgrad_q(g("X"), g("Y"), g("likelihood"), k_var=float(np.ravel(g("k_var").value)[0]),
+                                       residual=self.residual, q0=(m0, S0), steps=steps, rho=rho, tol=tol)
+        sess.write_raw(q_mu, m.reshape(-1))
+        sess.write_raw(q_sqrt, tri_pack(S) if q.packed else S)
+        return m, S, info
+
+
 class Amortised(hb.model.Model):
     """cfg 4: NeuralNet encoder -> LOCAL Normal -> linear Gaussian decoder."""
 

@@ -48,7 +48,9 @@ extern "C" {
  * _f64 and hb_sgp_predict_cov_ws_elems (full predictive covariance); hb_sgp_stats_f32 / _f64 and hb_sgp_stats_ws_elems
  * (sufficient statistics of the closed-form optimal q(u)); hb_sgp_select_f32 / _f64 and hb_sgp_select_ws_elems (greedy
  * conditional-variance selection of inducing points); hb_sgp_kgrad_f32 / _f64 and hb_sgp_kgrad_ws_elems (streamed part
- * of the gradient of the collapsed bound). */
+ * of the gradient of the collapsed bound); hb_sgp_wstats_f32 / _f64, hb_sgp_wstats_ws_elems, hb_lik_sites_f32 / _f64,
+ * hb_lik_sites_ws_elems, hb_lik_predict_f32 / _f64 and the enum values HB_LIK_* (natural-gradient fit of q(u) for
+ * non-Gaussian likelihoods). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -625,6 +627,47 @@ int hb_sgp_stats_f32(int kind, const float* X, const float* Y, const float* z, c
 int hb_sgp_stats_f64(int kind, const double* X, const double* Y, const double* z, const double* ell, long dl, const double* W,
                      const double* Wfrag, double* Phi, double* b, double* yy, double* a2sum, long N, long M, long d, long P,
                      double* ws, void* stream);
+/* Weighted form of hb_sgp_stats_* (csrc/sgp_stats.hip; not in the reference), the data pass of a natural-gradient step
+ * on q(u) under any factorising likelihood (SparseGP.natgrad_q).  With A = W k(z, X) [M, N]:
+ *   Phi [M, M] = A diag(w) A^T,   b [1, M] = (A r)^T,   tr [1] = tr Phi
+ * ALWAYS double.  w [N] (16-byte aligned) and r [N] in the storage type; weights of either sign and zeros are taken as
+ * they are: the weight multiplies the column operand of the rank update as it is staged (fp32 MFMA form: A_c diag(w)
+ * rounded to float32 once; plain form: in double), A is never scaled by a root.  Chunking, K-splits, the fold in split
+ * order and the final mirror are those of hb_sgp_stats_*: Phi is bitwise symmetric, two calls return the same bits, and
+ * with w == 1, r = Y[:, 0] Phi and b have the bits of hb_sgp_stats_*.  Every other argument as for hb_sgp_stats_*;
+ * ws >= hb_sgp_wstats_ws_elems(N, M, d, sizeof(T)) elements of T (= hb_sgp_stats_ws_elems with P = 1). */
+long hb_sgp_wstats_ws_elems(long N, long M, long d, int dtype_bytes);
+int hb_sgp_wstats_f32(int kind, const float* X, const float* w, const float* r, const float* z, const float* ell, long dl,
+                      const float* W, const float* Wfrag, double* Phi, double* b, double* tr, long N, long M, long d, float* ws,
+                      void* stream);
+int hb_sgp_wstats_f64(int kind, const double* X, const double* w, const double* r, const double* z, const double* ell, long dl,
+                      const double* W, const double* Wfrag, double* Phi, double* b, double* tr, long N, long M, long d,
+                      double* ws, void* stream);
+/* Sites of a factorising likelihood under Gaussian marginals (csrc/lik_sites.hip; not in the reference).  For
+ * f_j ~ N(mu_j, v_j), mu_j = mscale mean[j], v_j = vscale var[j] (the scales take the unit-variance moments of
+ * hb_sgp_predict_* to those of f = sqrt(k_var) (..): mscale = sqrt(k_var), vscale = k_var):
+ *   l_j = E[log p(y_j | f)],  lam[j] = E[-d2 log p / df2],  beta[j] = E[d log p / df] + lam[j] mu_j,  ell_sum[0] = sum_j l_j.
+ *   HB_LIK_GAUSSIAN   y ~ N(f, param), param = the variance > 0: l = -log(2 pi param) / 2 - ((y - mu)^2 + v) / (2 param),
+ *                     lam = 1 / param, beta = y / param
+ *   HB_LIK_BERNOULLI  y in {0, 1}, log p = y f - softplus(f): 20-node Gauss-Hermite, f_i = mu + sqrt(2 v) x_i
+ *   HB_LIK_POISSON    log p = y f - exp(f) - lgamma(y + 1): with e = exp(mu + v / 2), l = y mu - e - lgamma(y + 1), lam = e,
+ *                     beta = y - e + e mu
+ * y, mean, var, lam, beta [N] in the storage type; all arithmetic is double, rounded once on output and saturated to the
+ * largest finite value of the storage type.  ell_sum: per-block partials (ws) folded in block order by a second launch,
+ * no atomics -- two calls return the same bits.  ws >= hb_lik_sites_ws_elems(N) doubles (at most 1024).  Validated before
+ * any launch: the id, N >= 0, param > 0 for HB_LIK_GAUSSIAN, vscale >= 0.
+ * hb_lik_predict_*: mean and variance of a new y given f ~ N(mean[j], var[j]): (mean, var + param); (p, p (1 - p)) with
+ * p = E sigmoid(f) by the same rule; (e, e + (exp(var) - 1) e^2). */
+enum { HB_LIK_GAUSSIAN = 0, HB_LIK_BERNOULLI = 1, HB_LIK_POISSON = 2 };
+long hb_lik_sites_ws_elems(long N);
+int hb_lik_sites_f32(int lik, const float* y, const float* mean, const float* var, double mscale, double vscale, double param,
+                     float* lam, float* beta, double* ell_sum, long N, double* ws, void* stream);
+int hb_lik_sites_f64(int lik, const double* y, const double* mean, const double* var, double mscale, double vscale,
+                     double param, double* lam, double* beta, double* ell_sum, long N, double* ws, void* stream);
+int hb_lik_predict_f32(int lik, const float* mean, const float* var, double param, float* ymean, float* yvar, long N,
+                       void* stream);
+int hb_lik_predict_f64(int lik, const double* mean, const double* var, double param, double* ymean, double* yvar, long N,
+                       void* stream);
 /* Greedy conditional-variance selection of M inducing points out of X [N, d] (csrc/sgp_select.hip; not in the reference;
  * Burt, Rasmussen, van der Wilk 2020): a pivoted incomplete Cholesky of K(X, X).  With dvar [N] = kdiag = 1 and the
  * history C [M, N], for j = 0 .. M - 1:
