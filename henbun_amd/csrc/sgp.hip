@@ -18,7 +18,7 @@
 // E * M^2 * n (Kbar = W^T Abar), E * M^2 * n (Lbar = -tril(Kbar A^T)).
 // The roofline that bounds them is the f32 MFMA peak (v_mfma_f32_32x32x2_f32).
 #include "common.cuh"
-#include "sgp_strip.cuh"  // strip constants, sgp_store_frag_tile
+#include "sgp_strip.cuh"  // strip constants, the strip prologue, sgp_store_frag_tile
 #include "chain.cuh"      // serial chains: the finishing pass may be recorded instead of launched
 #include "chol_persist.cuh"  // the early-start form runs inside the persistent factorisation's launch
 #include <type_traits>
@@ -28,7 +28,6 @@
 
 #define SGP_BM 64
 #define SGP_BN 128
-#define SGP_DREG 4  // input dims held in registers by the operand loaders
 
 // provided by linalg.hip / elementwise.hip (same shared object)
 extern "C" int hb_matmul_f32(const float*, const float*, float*, long, long, long, long, long, long, long, long, long,
@@ -381,73 +380,18 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS) sgp_A_strip_kernel(SgpArgs<
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 31, h = lane >> 5;
 
   HB_SSTAMP(0);
-  // ---- K(z, x[strip]) -> LDS, [column][k]: thread (c = tid % 32, kq = tid / 32) takes the 16-byte groups kq, kq+16, ...
-  // z is staged (pre-scaled) in LDS first: read straight from global, every group would be a dependent
-  // load round trip (measured: the prologue alone cost ~10 us).
-  {
-    const int c = tid & 31, kq = tid >> 5;
-    const int cc = col0 + c < n ? col0 + c : n - 1;  // columns past n compute garbage that is never stored
-    float sc[D], xs[D];
-#pragma unroll
-    for (int dd = 0; dd < D; ++dd) {
-      sc[dd] = float(SGP_EXP2_SCALE) / ell[a.dl == 1 ? 0 : dd];
-      xs[dd] = x[cc * D + dd];   // raw: the difference is taken first, then scaled (see hb_exp2_neg in sgp_strip.cuh)
-    }
-    // all staging loads are issued before any is consumed (a load -> LDS store loop would pay one dependent
-    // round trip per iteration: five of them, ~5 us, in the first version of this prologue)
-    constexpr int NTH = SGP_STRIP_THREADS;
-    constexpr int ZIT = (SGP_SM_MAX * D) / NTH, UIT = SGP_SM_MAX / NTH;
-    static_assert(ZIT >= 1 && UIT >= 1, "staging loops");
-    float zt[ZIT], ut[4][UIT];
-    const int npu = a.part ? ((int)a.P < 4 ? (int)a.P : 4) : 0;
-#pragma unroll
-    for (int it = 0; it < ZIT; ++it) {
-      const int i = tid + NTH * it;
-      zt[it] = z[i < M * D ? i : 0];
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-      for (int it = 0; it < UIT; ++it) {
-        const int i = tid + NTH * it;
-        ut[p][it] = p < npu ? a.u[e * a.P * a.M + (long)p * M + (i < M ? i : 0)] : 0.f;
-      }
-#pragma unroll
-    for (int it = 0; it < ZIT; ++it) {
-      const int i = tid + NTH * it;
-      if (i < M * D) zs[i] = zt[it];
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-      for (int it = 0; it < UIT; ++it) {
-        const int i = tid + NTH * it;
-        if (p < npu && i < M) us[p][i] = ut[p][it];
-      }
-    __syncthreads();
-#pragma unroll 4
-    for (int k4 = kq * 4; k4 < M; k4 += NTH / 8) {
-      float zq[4 * D];
-#pragma unroll
-      for (int q = 0; q < 4 * D; q += 4) {
-        const V4 zz = *reinterpret_cast<const V4*>(&zs[k4 * D + q]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) zq[q + s] = zz[s];
-      }
-      V4 v;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        float r2 = 0.f;
-#pragma unroll
-        for (int dd = 0; dd < D; ++dd) {
-          const float tt = (zq[q * D + dd] - xs[dd]) * sc[dd];
-          r2 += tt * tt;
-        }
-        v[q] = hb_exp2_neg<float>(r2);
-      }
-      *reinterpret_cast<V4*>(&Ks[c][k4]) = v;
-    }
-  }
+  // ---- K(z, x[strip]) -> LDS, [column][k] (the strip prologue of sgp_strip.cuh), and the u rows of the column statistics
+  SgpStripColumn<D> col;
+  SgpStageZ<D, SGP_STRIP_THREADS> zst;
+  SgpStageU<SGP_STRIP_THREADS> ust;
+  const int npu = a.part ? ((int)a.P < 4 ? (int)a.P : 4) : 0;
+  col.load(x, ell, a.dl, col0, n, tid);
+  zst.request(z, M, tid);
+  ust.request(a.u + e * a.P * a.M, npu, M, tid);
+  zst.store(zs, M, tid);
+  ust.store(us, npu, M, tid);
+  __syncthreads();
+  sgp_strip_fill<D, SGP_STRIP_THREADS>(Ks, zs, col, M, tid);
   __syncthreads();
 
   HB_SSTAMP(1);
@@ -676,68 +620,18 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS) sgp_A_strip2_kernel(SgpArgs
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 31, h = lane >> 5;
 
   HB_SSTAMP(0);
-  // ---- K(z, x[strip]) -> LDS (as in the first form)
-  {
-    const int c = tid & 31, kq = tid >> 5;
-    const int cc = col0 + c < n ? col0 + c : n - 1;
-    float sc[D], xs[D];
-#pragma unroll
-    for (int dd = 0; dd < D; ++dd) {
-      sc[dd] = float(SGP_EXP2_SCALE) / ell[a.dl == 1 ? 0 : dd];
-      xs[dd] = x[cc * D + dd];   // raw: the difference is taken first, then scaled (see hb_exp2_neg in sgp_strip.cuh)
-    }
-    constexpr int NTH = SGP_STRIP_THREADS;
-    constexpr int ZIT = (SGP_SM_MAX * D) / NTH, UIT = SGP_SM_MAX / NTH;
-    float zt[ZIT], ut[4][UIT];
-    const int npu = a.part ? ((int)a.P < 4 ? (int)a.P : 4) : 0;
-#pragma unroll
-    for (int it = 0; it < ZIT; ++it) {
-      const int i = tid + NTH * it;
-      zt[it] = z[i < M * D ? i : 0];
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-      for (int it = 0; it < UIT; ++it) {
-        const int i = tid + NTH * it;
-        ut[p][it] = p < npu ? a.u[e * a.P * a.M + (long)p * M + (i < M ? i : 0)] : 0.f;
-      }
-#pragma unroll
-    for (int it = 0; it < ZIT; ++it) {
-      const int i = tid + NTH * it;
-      if (i < M * D) zs[i] = zt[it];
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-      for (int it = 0; it < UIT; ++it) {
-        const int i = tid + NTH * it;
-        if (p < npu && i < M) us[p][i] = ut[p][it];
-      }
-    __syncthreads();
-#pragma unroll 4
-    for (int k4 = kq * 4; k4 < M; k4 += NTH / 8) {
-      float zq[4 * D];
-#pragma unroll
-      for (int q = 0; q < 4 * D; q += 4) {
-        const V4 zz = *reinterpret_cast<const V4*>(&zs[k4 * D + q]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) zq[q + s] = zz[s];
-      }
-      V4 v;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        float r2 = 0.f;
-#pragma unroll
-        for (int dd = 0; dd < D; ++dd) {
-          const float tt = (zq[q * D + dd] - xs[dd]) * sc[dd];
-          r2 += tt * tt;
-        }
-        v[q] = hb_exp2_neg<float>(r2);
-      }
-      *reinterpret_cast<V4*>(&Ks[c][k4]) = v;
-    }
-  }
+  // ---- K(z, x[strip]) -> LDS, and the u rows of the column statistics
+  SgpStripColumn<D> col;
+  SgpStageZ<D, SGP_STRIP_THREADS> zst;
+  SgpStageU<SGP_STRIP_THREADS> ust;
+  const int npu = a.part ? ((int)a.P < 4 ? (int)a.P : 4) : 0;
+  col.load(x, ell, a.dl, col0, n, tid);
+  zst.request(z, M, tid);
+  ust.request(a.u + e * a.P * a.M, npu, M, tid);
+  zst.store(zs, M, tid);
+  ust.store(us, npu, M, tid);
+  __syncthreads();
+  sgp_strip_fill<D, SGP_STRIP_THREADS>(Ks, zs, col, M, tid);
   __syncthreads();
   HB_SSTAMP(1);
 
@@ -995,53 +889,14 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, 4) sgp_A_strip2t_kernel(Sgp
     if (d0) u0 = up[32 * t0 + li];
     if (d1) u1 = up[32 * t1 + li];
   }
-  // ---- K(z, x[strip]) -> LDS (as in the other forms: difference first, then the exp2 scale)
-  {
-    const int c = tid & 31, kq = tid >> 5;
-    const int cc = col0 + c < n ? col0 + c : n - 1;
-    float sc[D], xs[D];
-#pragma unroll
-    for (int dd = 0; dd < D; ++dd) {
-      sc[dd] = float(SGP_EXP2_SCALE) / ell[a.dl == 1 ? 0 : dd];
-      xs[dd] = x[cc * D + dd];
-    }
-    constexpr int NTH = SGP_STRIP_THREADS;
-    constexpr int ZIT = (SGP_SM_MAX * D) / NTH;
-    float zt[ZIT];
-#pragma unroll
-    for (int it = 0; it < ZIT; ++it) {
-      const int i = tid + NTH * it;
-      zt[it] = z[i < M * D ? i : 0];
-    }
-#pragma unroll
-    for (int it = 0; it < ZIT; ++it) {
-      const int i = tid + NTH * it;
-      if (i < M * D) zs[i] = zt[it];
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int k4 = kq * 4; k4 < M; k4 += NTH / 8) {
-      float zq[4 * D];
-#pragma unroll
-      for (int q = 0; q < 4 * D; q += 4) {
-        const V4 zz = *reinterpret_cast<const V4*>(&zs[k4 * D + q]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) zq[q + s] = zz[s];
-      }
-      V4 v;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        float r2 = 0.f;
-#pragma unroll
-        for (int dd = 0; dd < D; ++dd) {
-          const float tt = (zq[q * D + dd] - xs[dd]) * sc[dd];
-          r2 += tt * tt;
-        }
-        v[q] = hb_exp2_neg<float>(r2);
-      }
-      *reinterpret_cast<V4*>(&Ks[c][k4]) = v;
-    }
-  }
+  // ---- K(z, x[strip]) -> LDS
+  SgpStripColumn<D> col;
+  SgpStageZ<D, SGP_STRIP_THREADS> zst;
+  col.load(x, ell, a.dl, col0, n, tid);
+  zst.request(z, M, tid);
+  zst.store(zs, M, tid);
+  __syncthreads();
+  sgp_strip_fill<D, SGP_STRIP_THREADS>(Ks, zs, col, M, tid);
   __syncthreads();
   HB_SSTAMP(1);
 
@@ -1171,42 +1026,12 @@ __global__ void __launch_bounds__(SGP_S16_THREADS, 4) sgp_A_strip16_kernel(SgpAr
   const bool means = a.part && a.P > 0;
   const int nS = (n + SGP_SN - 1) / SGP_SN;
 
-  // ---- K(z, x[strip]) -> LDS (as in the other forms: difference first, then the exp2 scale)
-  {
-    const int c = tid & 31, kq = tid >> 5;
-    const int cc = col0 + c < n ? col0 + c : n - 1;
-    float sc[D], xs[D];
-#pragma unroll
-    for (int dd = 0; dd < D; ++dd) {
-      sc[dd] = float(SGP_EXP2_SCALE) / ell[a.dl == 1 ? 0 : dd];
-      xs[dd] = x[cc * D + dd];
-    }
-    constexpr int NTH = SGP_S16_THREADS;
-    for (int i = tid; i < M * D; i += NTH) zs[i] = z[i];
-    __syncthreads();
-#pragma unroll 4
-    for (int k4 = kq * 4; k4 < M; k4 += NTH / 8) {
-      float zq[4 * D];
-#pragma unroll
-      for (int q = 0; q < 4 * D; q += 4) {
-        const V4 zz = *reinterpret_cast<const V4*>(&zs[k4 * D + q]);
-#pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2) zq[q + s2] = zz[s2];
-      }
-      V4 v;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        float r2 = 0.f;
-#pragma unroll
-        for (int dd = 0; dd < D; ++dd) {
-          const float tt = (zq[q * D + dd] - xs[dd]) * sc[dd];
-          r2 += tt * tt;
-        }
-        v[q] = hb_exp2_neg<float>(r2);
-      }
-      *reinterpret_cast<V4*>(&Ks[c][k4]) = v;
-    }
-  }
+  // ---- K(z, x[strip]) -> LDS (z by a plain loop: 1024 threads leave no whole register round at D = 1)
+  SgpStripColumn<D> col;
+  col.load(x, ell, a.dl, col0, n, tid);
+  for (int i = tid; i < M * D; i += SGP_S16_THREADS) zs[i] = z[i];
+  __syncthreads();
+  sgp_strip_fill<D, SGP_S16_THREADS>(Ks, zs, col, M, tid);
   __syncthreads();
 
   float csq[16], cu[16];
@@ -1362,53 +1187,17 @@ __device__ __forceinline__ void sgp_early_body(const SgpArgs<float>& a, const Cp
   if (ca.nside > 0 && w == 0) wt.wait(ca.sync + 3, (unsigned)ca.nside);
   __syncthreads();
 
-  // ---- K(z, x[strip]) -> LDS (as in the other forms: difference first, then the exp2 scale)
-  {
-    const int c = tid & 31, kq = tid >> 5;
-    const int cc = col0 + c < n ? col0 + c : n - 1;
-    float sc[D], xs[D];
+  // ---- K(z, x[strip]) -> LDS (x is a side job's output: agent-scope loads)
+  SgpStripColumn<D> col;
+  SgpStageZ<D, SGP_STRIP_THREADS> zst;
+  const int c = col0 + (tid & 31), cc = c < n ? c : n - 1;
+  col.scale(ell, a.dl);
 #pragma unroll
-    for (int dd = 0; dd < D; ++dd) {
-      sc[dd] = float(SGP_EXP2_SCALE) / ell[a.dl == 1 ? 0 : dd];
-      xs[dd] = sgp_ag_load(x + cc * D + dd);
-    }
-    constexpr int NTH = SGP_STRIP_THREADS;
-    constexpr int ZIT = (SGP_SM_MAX * D) / NTH;
-    float zt[ZIT];
-#pragma unroll
-    for (int it = 0; it < ZIT; ++it) {
-      const int i = tid + NTH * it;
-      zt[it] = z[i < M * D ? i : 0];
-    }
-#pragma unroll
-    for (int it = 0; it < ZIT; ++it) {
-      const int i = tid + NTH * it;
-      if (i < M * D) zs[i] = zt[it];
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int k4 = kq * 4; k4 < M; k4 += NTH / 8) {
-      float zq[4 * D];
-#pragma unroll
-      for (int q = 0; q < 4 * D; q += 4) {
-        const V4 zz = *reinterpret_cast<const V4*>(&zs[k4 * D + q]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) zq[q + s] = zz[s];
-      }
-      V4 v;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        float r2 = 0.f;
-#pragma unroll
-        for (int dd = 0; dd < D; ++dd) {
-          const float tt = (zq[q * D + dd] - xs[dd]) * sc[dd];
-          r2 += tt * tt;
-        }
-        v[q] = hb_exp2_neg<float>(r2);
-      }
-      *reinterpret_cast<V4*>(&Ks[c][k4]) = v;
-    }
-  }
+  for (int dd = 0; dd < D; ++dd) col.xs[dd] = sgp_ag_load(x + cc * D + dd);
+  zst.request(z, M, tid);
+  zst.store(zs, M, tid);
+  __syncthreads();
+  sgp_strip_fill<D, SGP_STRIP_THREADS>(Ks, zs, col, M, tid);
   __syncthreads();
 
   float csq[16], cu[16];
@@ -1692,41 +1481,16 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS) sgp_A_strip3_kernel(SgpArgs
   // ---- K(z, x[strip]) -> LDS as three bf16 planes [term][column][k]
   {
     const int c = tid & 31, kq = tid >> 5;
-    const int cc = col0 + c < n ? col0 + c : n - 1;
-    float sc[D], xs[D];
-#pragma unroll
-    for (int dd = 0; dd < D; ++dd) {
-      sc[dd] = float(SGP_EXP2_SCALE) / ell[a.dl == 1 ? 0 : dd];
-      xs[dd] = x[cc * D + dd];   // raw: the difference is taken first, then scaled (see hb_exp2_neg in sgp_strip.cuh)
-    }
     constexpr int NTH = SGP_STRIP_THREADS;
-    constexpr int ZIT = (SGP_SM_MAX * D) / NTH, UIT = SGP_SM_MAX / NTH;
-    float zt[ZIT], ut[4][UIT];
+    SgpStripColumn<D> col;
+    SgpStageZ<D, NTH> zst;
+    SgpStageU<NTH> ust;
     const int npu = a.part ? ((int)a.P < 4 ? (int)a.P : 4) : 0;
-#pragma unroll
-    for (int it = 0; it < ZIT; ++it) {
-      const int i = tid + NTH * it;
-      zt[it] = z[i < M * D ? i : 0];
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-      for (int it = 0; it < UIT; ++it) {
-        const int i = tid + NTH * it;
-        ut[p][it] = p < npu ? a.u[e * a.P * a.M + (long)p * M + (i < M ? i : 0)] : 0.f;
-      }
-#pragma unroll
-    for (int it = 0; it < ZIT; ++it) {
-      const int i = tid + NTH * it;
-      if (i < M * D) zs[i] = zt[it];
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-      for (int it = 0; it < UIT; ++it) {
-        const int i = tid + NTH * it;
-        if (p < npu && i < M) us[p][i] = ut[p][it];
-      }
+    col.load(x, ell, a.dl, col0, n, tid);
+    zst.request(z, M, tid);
+    ust.request(a.u + e * a.P * a.M, npu, M, tid);
+    zst.store(zs, M, tid);
+    ust.store(us, npu, M, tid);
     __syncthreads();
     // thread (c, kq) takes the groups of 8 consecutive k: kq*8, kq*8 + 128, ...
 #pragma unroll 2
@@ -1734,13 +1498,7 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS) sgp_A_strip3_kernel(SgpArgs
       B8 p0, p1, p2;
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        float r2 = 0.f;
-#pragma unroll
-        for (int dd = 0; dd < D; ++dd) {
-          const float tt = (zs[(k8 + q) * D + dd] - xs[dd]) * sc[dd];
-          r2 += tt * tt;
-        }
-        const float kv = hb_exp2_neg<float>(r2);
+        const float kv = col.value(&zs[(k8 + q) * D]);
         const __bf16 b0 = (__bf16)kv;
         const float r1 = kv - (float)b0;
         const __bf16 b1 = (__bf16)r1;
@@ -2487,48 +2245,24 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
   float* __restrict__ part = a.part + ((e * nS + bx) * (long)nq) * M;   // [2D + P][M] of this strip
 
   // ---- stage z, the strip's x (both raw: differences are scaled, not coordinates), u, the per-column residual coefficient and fbar
-  float sc[D];
+  SgpStripColumn<D> col;   // (only the scale: the strip's x goes to LDS, a lane's row gradients visit 16 columns)
+  col.scale(ell, a.dl);
+  SgpStageZ<D, SGP_STRIP_THREADS> zst;
+  SgpStageU<SGP_STRIP_THREADS> ust;
+  zst.request(z, M, tid);
+  ust.request(a.u + e * a.P * a.M, P, M, tid);
+  if (tid < SGP_SN) {
+    const int cc = col0 + tid;
+    const bool ok = cc < n;
+    const int cj = ok ? cc : n - 1;
+    cjs[tid] = ok ? sgp_resid_coef<float>(a.eps ? a.eps + e * a.n : nullptr, a.v + e * a.n, fbar, a.n, a.P, a.mode, cj) : 0.f;
 #pragma unroll
-  for (int dd = 0; dd < D; ++dd) sc[dd] = float(SGP_EXP2_SCALE) / ell[a.dl == 1 ? 0 : dd];
-  {
-    constexpr int NTH = SGP_STRIP_THREADS;
-    constexpr int ZIT = (SGP_SM_MAX * D) / NTH, UIT = SGP_SM_MAX / NTH;
-    float zt[ZIT], ut[4][UIT];
+    for (int p = 0; p < 4; ++p) fbs[p][tid] = (ok && p < P) ? fbar[(long)p * n + cj] : 0.f;
 #pragma unroll
-    for (int it = 0; it < ZIT; ++it) {
-      const int i = tid + NTH * it;
-      zt[it] = z[i < M * D ? i : 0];
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-      for (int it = 0; it < UIT; ++it) {
-        const int i = tid + NTH * it;
-        ut[p][it] = p < P ? a.u[e * a.P * a.M + (long)p * M + (i < M ? i : 0)] : 0.f;
-      }
-    if (tid < SGP_SN) {
-      const int cc = col0 + tid;
-      const bool ok = cc < n;
-      const int cj = ok ? cc : n - 1;
-      cjs[tid] = ok ? sgp_resid_coef<float>(a.eps ? a.eps + e * a.n : nullptr, a.v + e * a.n, fbar, a.n, a.P, a.mode, cj) : 0.f;
-#pragma unroll
-      for (int p = 0; p < 4; ++p) fbs[p][tid] = (ok && p < P) ? fbar[(long)p * n + cj] : 0.f;
-#pragma unroll
-      for (int dd = 0; dd < D; ++dd) xss[tid * D + dd] = x[cj * D + dd];
-    }
-#pragma unroll
-    for (int it = 0; it < ZIT; ++it) {
-      const int i = tid + NTH * it;
-      if (i < M * D) zs[i] = zt[it];
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-#pragma unroll
-      for (int it = 0; it < UIT; ++it) {
-        const int i = tid + NTH * it;
-        if (p < P && i < M) us[p][i] = ut[p][it];
-      }
+    for (int dd = 0; dd < D; ++dd) xss[tid * D + dd] = x[cj * D + dd];
   }
+  zst.store(zs, M, tid);
+  ust.store(us, P, M, tid);
   __syncthreads();
 
   // ---- Abar[:, strip] -> LDS ([column][k]); ubar partials of the strip on the way.
@@ -2723,7 +2457,7 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
       float tt[D], r2 = 0.f;
 #pragma unroll
       for (int dd = 0; dd < D; ++dd) {
-        tt[dd] = (zr[dd] - xss[c * D + dd]) * sc[dd];   // difference first, then the exp2 scale (coordinates staged raw)
+        tt[dd] = (zr[dd] - xss[c * D + dd]) * col.sc[dd];   // difference first, then the exp2 scale (coordinates staged raw)
         r2 += tt[dd] * tt[dd];
       }
       const float gk = kb[i] * hb_exp2_neg<float>(r2);   // (columns past n hold zeros)
@@ -2737,7 +2471,7 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
     for (int dd = 0; dd < D; ++dd) {
       zacc[dd] += __shfl_xor(zacc[dd], 32);
       // tt is in exp2-scaled units (t' = t * S, S = SGP_EXP2_SCALE): zbar = -(1/ell) sum g t, ell = (1/ell) sum g t^2
-      if (h == 0) part[(long)dd * M + row] = zacc[dd] * sc[dd] * float(1.0 / (SGP_EXP2_SCALE * SGP_EXP2_SCALE));
+      if (h == 0) part[(long)dd * M + row] = zacc[dd] * col.sc[dd] * float(1.0 / (SGP_EXP2_SCALE * SGP_EXP2_SCALE));
       lwave[dd] += lacc[dd];   // the lengthscale gradient is summed over the rows too: per lane, folded at the end
     }
 #pragma unroll
@@ -2840,7 +2574,7 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
     if (tid == dd) {
       float t = 0.f;
       for (int ww = 0; ww < SGP_STRIP_THREADS / 64; ++ww) t += red[ww * D + dd];
-      part[(long)(D + dd) * M] = t * sc[dd] * float(1.0 / (SGP_EXP2_SCALE * SGP_EXP2_SCALE * SGP_EXP2_SCALE));
+      part[(long)(D + dd) * M] = t * col.sc[dd] * float(1.0 / (SGP_EXP2_SCALE * SGP_EXP2_SCALE * SGP_EXP2_SCALE));
     }
 }
 

@@ -22,7 +22,6 @@
 #include "../../include/henbun_hip.h"
 
 #define PRED_THREADS 512          // 8 waves; wave w owns the row tiles w and nT - 1 - w (balanced triangular work)
-#define PRED_DMAX 4               // input dimensions the fused form takes (SGP_DREG of csrc/sgp.hip)
 #define PRED_PMAX 4               // latent functions whose means / variances the fused form keeps per thread
 #define PRED_RED_LD 260           // floats per column in the fold of the S^T A statistics (8 waves x 32 lanes + 4)
 #define HB_PRED_CHUNK 32768L      // columns per chunk of the chunked form (at most)
@@ -133,30 +132,17 @@ __global__ void __launch_bounds__(PRED_THREADS) sgp_predict_strip_kernel(PredArg
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 31, h = lane >> 5;
   const int nT = M / 32;
 
-  // ---- phase 1a: K(z, x[strip]) -> LDS (difference first, then the exp2 scale: csrc/sgp_strip.cuh)
+  // ---- phase 1a: K(z, x[strip]) -> LDS (the strip prologue of csrc/sgp_strip.cuh)
   {
-    const int c = tid & 31, kq = tid >> 5;
-    const int cc = col0 + c < n ? col0 + c : n - 1;   // columns past n: a copy of the last one (never written out)
-    float sc[D], xs[D];
-#pragma unroll
-    for (int dd = 0; dd < D; ++dd) {
-      sc[dd] = float(SGP_EXP2_SCALE) / ell[a.dl == 1 ? 0 : dd];
-      xs[dd] = x[(long)cc * D + dd];
-    }
+    SgpStripColumn<D> col;
+    col.load(x, ell, a.dl, col0, n, tid);
     for (int i = tid; i < M * D; i += PRED_THREADS) zs[i] = z[i];
     __syncthreads();
+    const int c = tid & 31, kq = tid >> 5;
     for (int k4 = kq * 4; k4 < M; k4 += PRED_THREADS / 8) {
       V4 v;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        float r2 = 0.f;
-#pragma unroll
-        for (int dd = 0; dd < D; ++dd) {
-          const float tt = (zs[(k4 + q) * D + dd] - xs[dd]) * sc[dd];
-          r2 += tt * tt;
-        }
-        v[q] = hb_exp2_neg<float>(r2);
-      }
+      for (int q = 0; q < 4; ++q) v[q] = col.value(&zs[(k4 + q) * D]);
       *reinterpret_cast<V4*>(&Ks[c * SGP_SLD + k4]) = v;
     }
   }
@@ -289,7 +275,7 @@ __global__ void __launch_bounds__(256) pred_colstat_kernel(const T* __restrict__
 }
 
 static inline bool pred_fused_ok(long E, long n, long M, long d, long P, int s_kind) {
-  return M >= 32 && M <= SGP_SM_MAX && M % 32 == 0 && d >= 1 && d <= PRED_DMAX && P >= 1 && P <= PRED_PMAX && n > 0 &&
+  return M >= 32 && M <= SGP_SM_MAX && M % 32 == 0 && d >= 1 && d <= SGP_DREG && P >= 1 && P <= PRED_PMAX && n > 0 &&
          E >= 1 && E <= 65535 && (s_kind == HB_SGP_S_DIAG || E * P == 1);
 }
 static inline long pred_chunk_cols(long E, long n, long M, long P, int s_kind) {

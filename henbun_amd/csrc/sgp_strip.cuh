@@ -1,5 +1,7 @@
-// Pieces of the column-strip sparse-GP kernels (csrc/sgp.hip) that other translation units share: the strip constants,
-// the exp2 form of the RBF value and the fragment-major store of a finished 32 x 32 tile.
+// Pieces of the column-strip sparse-GP kernels (csrc/sgp.hip, csrc/sgp_predict.hip) that every strip kernel repeats or
+// that other translation units share: the strip constants, the exp2 form of the RBF value, the strip prologue (one
+// column's coordinates and scale, register staging of z and u, the fp32 fill of the K block) and the fragment-major
+// store of a finished 32 x 32 tile.
 #ifndef HB_SGP_STRIP_CUH
 #define HB_SGP_STRIP_CUH
 #include "common.cuh"
@@ -17,6 +19,100 @@ template <> __device__ __forceinline__ double hb_exp2_neg<double>(double x) { re
 #define SGP_SN 32
 #define SGP_SM_MAX 512
 #define SGP_SLD (SGP_SM_MAX + 4)
+#define SGP_DREG 4  // input dims held in registers by the operand loaders
+
+// ---------------------------------------------------------------------------------------------------------------
+// Strip prologue: K(z, x[strip]) -> LDS as Ks[column][k], M x 32, synthesised once per workgroup.  A kernel issues
+// every global load (the column, the z / u requests, then loads of its own) before the first LDS store: a load -> LDS
+// store loop pays one dependent round trip per iteration (five of them, ~5 us, in the first version), and z read
+// straight from global inside the fill pays one per 16-byte group (~10 us).
+//
+// One column of the strip: thread tid works on column tid % 32; columns past n read a copy of the last one (never
+// written out).  Coordinates stay RAW: value() takes the difference first and scales it afterwards (see SGP_EXP2_SCALE).
+template <int D>
+struct SgpStripColumn {
+  float sc[D], xs[D];
+  __device__ __forceinline__ void scale(const float* __restrict__ ell, long dl) {
+#pragma unroll
+    for (int dd = 0; dd < D; ++dd) sc[dd] = float(SGP_EXP2_SCALE) / ell[dl == 1 ? 0 : dd];
+  }
+  __device__ __forceinline__ void load(const float* __restrict__ x, const float* __restrict__ ell, long dl, int col0, int n,
+                                       int tid) {
+    const int c = col0 + (tid & 31), cc = c < n ? c : n - 1;
+    scale(ell, dl);
+#pragma unroll
+    for (int dd = 0; dd < D; ++dd) xs[dd] = x[cc * D + dd];
+  }
+  // K(z_k, x) for the inducing point at zk[0 .. D-1]
+  __device__ __forceinline__ float value(const float* zk) const {
+    float r2 = 0.f;
+#pragma unroll
+    for (int dd = 0; dd < D; ++dd) {
+      const float tt = (zk[dd] - xs[dd]) * sc[dd];
+      r2 += tt * tt;
+    }
+    return hb_exp2_neg<float>(r2);
+  }
+};
+
+// z [M, D] -> zs through registers: request() issues the loads, store() writes them to LDS (barrier at the caller).
+template <int D, int NTH>
+struct SgpStageZ {
+  static constexpr int ZIT = (SGP_SM_MAX * D) / NTH;
+  static_assert(ZIT >= 1, "staging loop");
+  float zt[ZIT];
+  __device__ __forceinline__ void request(const float* __restrict__ z, int M, int tid) {
+#pragma unroll
+    for (int it = 0, i = tid; it < ZIT; ++it, i += NTH) zt[it] = z[i < M * D ? i : 0];
+  }
+  __device__ __forceinline__ void store(float* zs, int M, int tid) const {
+#pragma unroll
+    for (int it = 0, i = tid; it < ZIT; ++it, i += NTH)
+      if (i < M * D) zs[i] = zt[it];
+  }
+};
+// The same for the first np <= 4 rows of this expert's u [P, M] (the column means of the epilogues).
+template <int NTH>
+struct SgpStageU {
+  static constexpr int UIT = SGP_SM_MAX / NTH;
+  static_assert(UIT >= 1, "staging loop");
+  float ut[4][UIT];
+  __device__ __forceinline__ void request(const float* __restrict__ u_e, int np, int M, int tid) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int it = 0, i = tid; it < UIT; ++it, i += NTH) ut[p][it] = p < np ? u_e[(long)p * M + (i < M ? i : 0)] : 0.f;
+  }
+  __device__ __forceinline__ void store(float (*us)[SGP_SM_MAX], int np, int M, int tid) const {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int it = 0, i = tid; it < UIT; ++it, i += NTH)
+        if (p < np && i < M) us[p][i] = ut[p][it];
+  }
+};
+
+// fp32 fill of Ks[column][k] from the staged zs: thread (c = tid % 32, kq = tid / 32) takes the 16-byte
+// groups kq, kq + NTH / 32, ... of its column.
+template <int D, int NTH>
+__device__ __forceinline__ void sgp_strip_fill(float (*Ks)[SGP_SLD], const float* zs, const SgpStripColumn<D>& col, int M, int tid) {
+  typedef float V4 __attribute__((ext_vector_type(4)));
+  const int c = tid & 31, kq = tid >> 5;
+#pragma unroll 4
+  for (int k4 = kq * 4; k4 < M; k4 += NTH / 8) {
+    float zq[4 * D];
+#pragma unroll
+    for (int q = 0; q < 4 * D; q += 4) {
+      const V4 zz = *reinterpret_cast<const V4*>(&zs[k4 * D + q]);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) zq[q + s] = zz[s];
+    }
+    V4 v;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = col.value(&zq[q * D]);
+    *reinterpret_cast<V4*>(&Ks[c][k4]) = v;
+  }
+}
 
 // Fragment-major copy of a finished 32 x 32 tile (accumulator layout: column on the lane, rows in the registers) of
 // an [M, n] operand of the Lbar contraction: block (row tile t, strip s) holds, for v = 0..3, lane (li, h), s' = 0..3,

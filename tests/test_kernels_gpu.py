@@ -813,6 +813,64 @@ def test_fragment_major_copies_of_the_inverse(H):
         assert torch.equal(H.sgp_A(x, zz, ell, Wd), H.sgp_A(x, zz, ell, Wd, wfrag=frag))
 
 
+_STRIP_GRIDS = {(96, 2): (12, 8), (96, 3): (6, 4, 4), (96, 4): (4, 4, 3, 2), (384, 2): (24, 16)}
+
+
+@pytest.mark.parametrize("M,n,d,P,form", [(96, 70, 2, 1, "fp32"), (96, 70, 2, 3, "fp32"), (96, 70, 3, 1, "fp32"), (96, 70, 3, 3, "fp32"),
+                                           (96, 70, 4, 1, "fp32"), (96, 70, 4, 3, "fp32"), (384, 70, 2, 1, "form16"),
+                                           (96, 70, 2, 1, "bf16x3")])
+def test_strip_forms_with_several_input_dimensions(H, M, n, d, P, form):
+    """The D = 2, 3, 4 instantiations of the forward strip forms that read Wfrag, with ARD lengthscales: A keeps its bits
+    between the row-major strip form, the third form (P = 1), the second form (P = 3, or by switch) and hb_sgp_A, and is
+    the fp64 product W K(z, x) of the same fp32 W to the componentwise bound of test_sgp_fwd_bwd.  M = 96: three row
+    tiles (odd: the middle one is taken once, five waves idle); n = 70: three strips, the last with 6 live columns.
+    The sixteen-wave and bf16x3 forms are held to the bounds their d = 1 tests use."""
+    rng = np.random.RandomState(17 + d)
+    ellv = np.linspace(0.7, 1.3, d).astype(np.float32)        # distinct lengthscales, one per input dimension
+    grid = np.stack(np.meshgrid(*[np.arange(g, dtype=np.float64) for g in _STRIP_GRIDS[(M, d)]], indexing="ij"), -1).reshape(M, d)
+    z = ((grid + 0.1 * rng.uniform(-1, 1, (M, d))) * ellv).astype(np.float32)     # jittered grid, about one lengthscale apart
+    x = rng.uniform(z.min(0), z.max(0), (n, d)).astype(np.float32)
+    zz, ell, xx = dev(z, torch.float32), dev(ellv, torch.float32), dev(x, torch.float32)
+    u, eps = dev(rng.randn(P, M), torch.float32), dev(rng.randn(n), torch.float32)
+    K = H.gram_fwd(zz, zz, ell, diag_add=1e-3).reshape(M, M)
+    b3 = form == "bf16x3"
+    frag = torch.zeros((5 if b3 else 2) * M * M, dtype=torch.float32, device="cuda")
+    L, W, info = H.cholesky_inverse(K, frag=frag, frag_bf16x3=b3)
+    assert info.cpu().numpy().item() == 0
+    Wd = W.reshape(M, M)
+    # fp64 reference from the SAME fp32 factor and the same fp32 inputs
+    Wh = host(Wd)
+    Kzx = np.exp(-0.5 * (((z.astype(np.float64)[:, None, :] - x.astype(np.float64)[None, :, :]) / ellv.astype(np.float64)) ** 2).sum(-1))
+    Aref = Wh @ Kzx
+    tag = "sgp_strip[M%d,n%d,d%d,P%d,%s]/" % (M, n, d, P, form)
+    wf = H.sgp_fwd(xx, zz, ell, Wd, u, eps_in=eps, wfrag=frag)
+    if form == "bf16x3":
+        fb3 = H.sgp_fwd(xx, zz, ell, Wd, u, eps_in=eps, wfrag=frag, prec=H.PREC_BF16X3)
+        e32, eb3 = np.abs(host(wf[1]) - Aref).max(), np.abs(host(fb3[1]) - Aref).max()
+        print(tag + "e32 %.3e eb3 %.3e |Ab3 - A32| %.3e" % (e32, eb3, np.abs(host(fb3[1]) - host(wf[1])).max()))
+        assert eb3 <= 2.0 * e32 + 1e-6, (e32, eb3)
+        assert np.abs(host(fb3[1]) - host(wf[1])).max() <= 4.0 * e32 + 1e-6
+        return
+    if form == "form16":
+        H.debug_set("sgp_form16", 1)
+        try:
+            b16 = H.sgp_fwd(xx, zz, ell, Wd, u, eps_in=eps, wfrag=frag)
+        finally:
+            H.debug_set("sgp_form16", 0)
+        print(tag + "|A16 - A| / max|A| %.3e" % (float((b16[1] - wf[1]).abs().max()) / float(wf[1].abs().max())))
+        assert float((b16[1] - wf[1]).abs().max()) <= 1e-4 * float(wf[1].abs().max())
+        return
+    rm = H.sgp_fwd(xx, zz, ell, Wd, u, eps_in=eps)
+    H.debug_set("sgp_strip_form2", 1)
+    try:
+        f2 = H.sgp_fwd(xx, zz, ell, Wd, u, eps_in=eps, wfrag=frag)
+    finally:
+        H.debug_set("sgp_strip_form2", 0)
+    assert torch.equal(rm[1], wf[1]) and torch.equal(rm[1], f2[1])
+    assert torch.equal(H.sgp_A(xx, zz, ell, Wd, wfrag=frag), wf[1])
+    observe(tag + "A", prod_err(host(wf[1]), Aref, np.abs(Wh), np.abs(Kzx)), 8e-4)
+
+
 @pytest.mark.parametrize("E,M,n,d,P,mode", [(1, 512, 3000, 1, 1, "diagonal"), (2, 96, 257, 2, 3, "diagonal"),
                                              (1, 64, 64, 3, 1, "neglected"), (3, 160, 1000, 1, 2, "diagonal"),
                                              (96, 96, 2048, 1, 1, "diagonal")])   # many blocks, ragged 128-row blocks: sgp_lbar_lds_kernel
