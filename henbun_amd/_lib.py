@@ -135,6 +135,7 @@ _TYPED = {
     "hb_lik_predict": [I, P, P, D, P, P, L, P],
     "hb_sgp_select": [I, P, P, L, L, L, L, D, P, P, P, P, P, P],
     "hb_sgp_kgrad": [I, P, P, P, P, L, P, P, P, P, L, L, L, L, P, P],
+    "hb_sgp_wkgrad": [I, P, P, P, P, P, L, P, P, P, P, L, L, L, P, P],
     "hb_adam_step": [P, P, P, P, L, D, D, D, D, D, P, I, P, L, P, P, P],
     "hb_allreduce_sum": [P, L, P, P],
     "hb_dp_pack": [P, P, P, L, P],

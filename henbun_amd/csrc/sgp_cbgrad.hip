@@ -25,6 +25,12 @@
 // A second launch (sgp_kgrad_fold_kernel) adds the strips' partials in strip order and applies -1 / ell^2 and 1 / ell^3.
 // A launch boundary is the only synchronisation (no atomics, no flags): two runs return the same bits.
 // Every other shape: sgp_kgrad_plain_kernel, plain double loops, one column at a time per workgroup (parity, not speed).
+//
+// Column-weighted form (hb_sgp_wkgrad_*, the template flag WT of both kernels): Kbar_ij = w_j (Q K)_ij + R_i r_j with
+// per-point weights w, r [N] in double and P = 1 -- the gradient of the ELBO of a non-Gaussian likelihood through
+// K(z, X) at a fixed q(u) ("Hyper-parameter gradient at fixed q(u)").  r takes the place of Y[:, 0] in ys,
+// w is staged next to it and multiplies the accumulator before + R r; everything else is the code above, so w == 1,
+// r = Y[:, 0] returns the bits of hb_sgp_kgrad_* at P = 1 (x * 1.0 is exact).  Columns beyond N hold K = 0 as before.
 #include "common.cuh"
 #include "gram_value.cuh"
 #include "../../include/henbun_hip.h"
@@ -41,7 +47,9 @@
 template <typename T>
 struct KgArgs {
   const T* X;          // [N, d]
-  const T* Y;          // [N, P]
+  const T* Y;          // [N, P] (unweighted form)
+  const double* w;     // [N], [N]: the column weights and r of the weighted form (P = 1), else unused
+  const double* r;
   const double* z;     // [M, d]
   const double* ell;   // [dl]
   const double* Q;     // fast: fragment order; plain: row-major [M, M]
@@ -62,7 +70,12 @@ __global__ void __launch_bounds__(256) sgp_kgrad_pack_kernel(const double* __res
   }
 }
 
-template <typename T, int D>
+// doubles of LDS the strip kernel takes: K, xs, ys, (weighted: wv), red, zs
+static inline size_t kg_strip_lds_elems(long M, int D, bool weighted) {
+  return (size_t)(M * KG_NB + KG_NB * D + KG_NB * KG_PMAX + (weighted ? KG_NB : 0) + KG_NW * D + M * D);
+}
+
+template <typename T, int D, bool WT>
 __global__ void __launch_bounds__(KG_THREADS) sgp_kgrad_strip_kernel(KgArgs<T> a) {
   typedef Mma<double> MM;
   extern __shared__ __attribute__((aligned(16))) double kg_smem[];
@@ -70,7 +83,8 @@ __global__ void __launch_bounds__(KG_THREADS) sgp_kgrad_strip_kernel(KgArgs<T> a
   double* Ks = kg_smem;                // [M / 4][2][64] fragments
   double* xs = Ks + M * KG_NB;         // [KG_NB][D]
   double* ys = xs + KG_NB * D;         // [KG_NB][KG_PMAX]
-  double* red = ys + KG_NB * KG_PMAX;  // [KG_NW][D]
+  double* wv = ys + KG_NB * KG_PMAX;   // [KG_NB] (weighted form only)
+  double* red = wv + (WT ? KG_NB : 0); // [KG_NW][D]
   double* zs = red + KG_NW * D;        // [M][D]: zbar of the strip, every row's slots owned by one lane
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -89,7 +103,10 @@ __global__ void __launch_bounds__(KG_THREADS) sgp_kgrad_strip_kernel(KgArgs<T> a
       xs[tid] = j < N ? (double)a.X[j * D + tid % D] : 0.0;
     } else if (tid >= 128 && tid < 128 + KG_NB * KG_PMAX) {
       const int q = tid - 128, c = q / KG_PMAX, p = q % KG_PMAX;
-      ys[q] = (j0 + c < N && p < P) ? (double)a.Y[(j0 + c) * P + p] : 0.0;
+      if (WT) ys[q] = (j0 + c < N && p == 0) ? a.r[j0 + c] : 0.0;
+      else ys[q] = (j0 + c < N && p < P) ? (double)a.Y[(j0 + c) * P + p] : 0.0;
+    } else if (WT && tid >= 256 && tid < 256 + KG_NB) {
+      wv[tid - 256] = j0 + (tid - 256) < N ? a.w[j0 + (tid - 256)] : 0.0;
     }
     __syncthreads();
     // K[:, step] in fragment order; columns beyond N hold zeros (E = 0 there)
@@ -127,7 +144,7 @@ __global__ void __launch_bounds__(KG_THREADS) sgp_kgrad_strip_kernel(KgArgs<T> a
 #pragma unroll
         for (int jt = 0; jt < 2; ++jt) {
           const int c = 16 * jt + (lane & 15);
-          double kb = acc[jt][r];
+          double kb = WT ? acc[jt][r] * wv[c] : acc[jt][r];
 #pragma unroll
           for (int p = 0; p < KG_PMAX; ++p) kb = __builtin_fma(ri[p], ys[c * KG_PMAX + p], kb);
           const double e = kb * Ks[((4 * it + r) * 2 + jt) * 64 + lane];
@@ -169,13 +186,13 @@ __global__ void __launch_bounds__(KG_THREADS) sgp_kgrad_strip_kernel(KgArgs<T> a
 
 // plain form: a workgroup walks its columns one at a time; thread i (strided) owns row i and its slots of the partials
 // ([M, d] for zbar, then [M, d] row partials of ellbar)
-template <typename T>
+template <typename T, bool WT>
 __global__ void __launch_bounds__(KG_PLAIN_T) sgp_kgrad_plain_kernel(KgArgs<T> a) {
   extern __shared__ __attribute__((aligned(16))) double kg_smem[];
   const long M = a.M, N = a.N, d = a.d, P = a.P;
   double* Kc = kg_smem;   // [M]
   double* xc = Kc + M;    // [d]
-  double* yc = xc + d;    // [P]
+  double* yc = xc + d;    // [P], then the column's weight (weighted form)
   const int tid = threadIdx.x;
   double* zp = a.part + (long)blockIdx.x * a.stride;
   double* ep = zp + M * d;
@@ -185,9 +202,10 @@ __global__ void __launch_bounds__(KG_PLAIN_T) sgp_kgrad_plain_kernel(KgArgs<T> a
   const long c0 = (long)blockIdx.x * a.per, c1 = c0 + a.per < N ? c0 + a.per : N;
   for (long j = c0; j < c1; ++j) {
     __syncthreads();
-    for (long q = tid; q < d + P; q += KG_PLAIN_T) {
+    for (long q = tid; q < d + P + (WT ? 1 : 0); q += KG_PLAIN_T) {
       if (q < d) xc[q] = (double)a.X[j * d + q];
-      else yc[q - d] = (double)a.Y[j * P + (q - d)];
+      else if (q == d + P) yc[P] = a.w[j];
+      else yc[q - d] = WT ? a.r[j] : (double)a.Y[j * P + (q - d)];
     }
     __syncthreads();
     for (long k = tid; k < M; k += KG_PLAIN_T) Kc[k] = gram_value<double>(HB_KERN_RBF, a.z + k * d, xc, a.ell, a.dl, d);
@@ -196,6 +214,7 @@ __global__ void __launch_bounds__(KG_PLAIN_T) sgp_kgrad_plain_kernel(KgArgs<T> a
       double kb = 0.0;
       const double* qi = a.Q + i * M;
       for (long k = 0; k < M; ++k) kb = __builtin_fma(qi[k], Kc[k], kb);
+      if (WT) kb *= yc[P];
       for (long p = 0; p < P; ++p) kb = __builtin_fma(a.R[i * P + p], yc[p], kb);
       const double e = kb * Kc[i];
       for (long dd = 0; dd < d; ++dd) {
@@ -257,35 +276,37 @@ extern "C" long hb_sgp_kgrad_ws_elems(long N, long M, long d, long P) {
   return fast > plain ? fast : plain;
 }
 
-template <typename T, int D>
+template <typename T, int D, bool WT>
 static int kg_launch_strip(const KgArgs<T>& a, long G, hipStream_t st) {
-  const size_t lds = (size_t)(a.M * KG_NB + KG_NB * D + KG_NB * KG_PMAX + KG_NW * D + a.M * D) * sizeof(double);
+  const size_t lds = kg_strip_lds_elems(a.M, D, WT) * sizeof(double);
   static bool attr_set = false;   // once per instantiation: the largest M needs up to 150 KB of the CU's 160 KB
   if (!attr_set) {
-    const size_t lds_max = (size_t)(KG_MMAX * KG_NB + KG_NB * D + KG_NB * KG_PMAX + KG_NW * D + KG_MMAX * D) * sizeof(double);
-    HB_HIP(hipFuncSetAttribute((const void*)sgp_kgrad_strip_kernel<T, D>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    const size_t lds_max = kg_strip_lds_elems(KG_MMAX, D, WT) * sizeof(double);
+    HB_HIP(hipFuncSetAttribute((const void*)sgp_kgrad_strip_kernel<T, D, WT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lds_max));
     attr_set = true;
   }
-  hipLaunchKernelGGL((sgp_kgrad_strip_kernel<T, D>), dim3((unsigned)G), dim3(KG_THREADS), lds, st, a);
+  hipLaunchKernelGGL((sgp_kgrad_strip_kernel<T, D, WT>), dim3((unsigned)G), dim3(KG_THREADS), lds, st, a);
   HB_LAUNCH_CHECK();
   return 0;
 }
 
-template <typename T>
-static int sgp_kgrad(int kind, const T* X, const T* Y, const double* z, const double* ell, long dl, const double* Q,
-                     const double* R, double* zbar, double* ellbar, long N, long M, long d, long P, double* ws,
-                     hipStream_t st) {
-  HB_REQUIRE(kind == HB_KERN_RBF, "hb_sgp_kgrad: only the UnitRBF kernel is supported (kind=%d)", kind);
-  HB_REQUIRE(N >= 1 && M >= 1 && d >= 1 && P >= 1, "hb_sgp_kgrad: bad extents (N=%ld M=%ld d=%ld P=%ld)", N, M, d, P);
-  HB_REQUIRE(dl == 1 || dl == d, "hb_sgp_kgrad: lengthscales must have 1 or d entries");
-  HB_REQUIRE(X && Y && z && ell && Q && R, "hb_sgp_kgrad: NULL input pointer");
-  HB_REQUIRE(zbar && ellbar, "hb_sgp_kgrad: NULL output pointer");
-  HB_REQUIRE(d <= 256 && P <= 256 && M + d + P <= 8000, "hb_sgp_kgrad: M=%ld d=%ld P=%ld too large", M, d, P);
-  HB_REQUIRE(ws && (uintptr_t)ws % 16 == 0, "hb_sgp_kgrad: needs a 16-byte aligned workspace of %ld doubles",
+// WT: Y is NULL, P is 1 and w, r [N] are given (hb_sgp_wkgrad_*); else w, r are NULL (hb_sgp_kgrad_*)
+template <typename T, bool WT>
+static int sgp_kgrad(int kind, const T* X, const T* Y, const double* w, const double* r, const double* z, const double* ell,
+                     long dl, const double* Q, const double* R, double* zbar, double* ellbar, long N, long M, long d, long P,
+                     double* ws, hipStream_t st) {
+  const char* who = WT ? "hb_sgp_wkgrad" : "hb_sgp_kgrad";
+  HB_REQUIRE(kind == HB_KERN_RBF, "%s: only the UnitRBF kernel is supported (kind=%d)", who, kind);
+  HB_REQUIRE(N >= 1 && M >= 1 && d >= 1 && P >= 1, "%s: bad extents (N=%ld M=%ld d=%ld P=%ld)", who, N, M, d, P);
+  HB_REQUIRE(dl == 1 || dl == d, "%s: lengthscales must have 1 or d entries", who);
+  HB_REQUIRE(X && (WT ? (w && r) : Y != nullptr) && z && ell && Q && R, "%s: NULL input pointer", who);
+  HB_REQUIRE(zbar && ellbar, "%s: NULL output pointer", who);
+  HB_REQUIRE(d <= 256 && P <= 256 && M + d + P <= 8000, "%s: M=%ld d=%ld P=%ld too large", who, M, d, P);
+  HB_REQUIRE(ws && (uintptr_t)ws % 16 == 0, "%s: needs a 16-byte aligned workspace of %ld doubles", who,
              hb_sgp_kgrad_ws_elems(N, M, d, P));
   KgArgs<T> a;
-  a.X = X; a.Y = Y; a.z = z; a.ell = ell; a.R = R; a.dl = dl; a.N = N; a.M = M; a.d = d; a.P = P;
+  a.X = X; a.Y = Y; a.w = w; a.r = r; a.z = z; a.ell = ell; a.R = R; a.dl = dl; a.N = N; a.M = M; a.d = d; a.P = P;
   long G, ne;
   if (kg_is_fast(M, d, P)) {
     double* Qf = ws;
@@ -300,10 +321,10 @@ static int sgp_kgrad(int kind, const T* X, const T* Y, const double* z, const do
     ne = 1;
     int rc;
     switch (d) {
-      case 1: rc = kg_launch_strip<T, 1>(a, G, st); break;
-      case 2: rc = kg_launch_strip<T, 2>(a, G, st); break;
-      case 3: rc = kg_launch_strip<T, 3>(a, G, st); break;
-      default: rc = kg_launch_strip<T, 4>(a, G, st); break;
+      case 1: rc = kg_launch_strip<T, 1, WT>(a, G, st); break;
+      case 2: rc = kg_launch_strip<T, 2, WT>(a, G, st); break;
+      case 3: rc = kg_launch_strip<T, 3, WT>(a, G, st); break;
+      default: rc = kg_launch_strip<T, 4, WT>(a, G, st); break;
     }
     if (rc) return rc;
   } else {
@@ -314,8 +335,8 @@ static int sgp_kgrad(int kind, const T* X, const T* Y, const double* z, const do
     a.per = (N + KG_MAXG - 1) / KG_MAXG;
     G = (N + a.per - 1) / a.per;
     ne = M;
-    const size_t lds = (size_t)(M + d + P) * sizeof(double);
-    hipLaunchKernelGGL((sgp_kgrad_plain_kernel<T>), dim3((unsigned)G), dim3(KG_PLAIN_T), lds, st, a);
+    const size_t lds = (size_t)(M + d + P + (WT ? 1 : 0)) * sizeof(double);
+    hipLaunchKernelGGL((sgp_kgrad_plain_kernel<T, WT>), dim3((unsigned)G), dim3(KG_PLAIN_T), lds, st, a);
     HB_LAUNCH_CHECK();
   }
   const long fb = (M * d + 255) / 256 + 1;
@@ -328,10 +349,20 @@ static int sgp_kgrad(int kind, const T* X, const T* Y, const double* z, const do
 extern "C" int hb_sgp_kgrad_f32(int kind, const float* X, const float* Y, const double* z, const double* ell, long dl,
                                 const double* Q, const double* R, double* zbar, double* ellbar, long N, long M, long d, long P,
                                 double* ws, void* stream) {
-  return sgp_kgrad<float>(kind, X, Y, z, ell, dl, Q, R, zbar, ellbar, N, M, d, P, ws, (hipStream_t)stream);
+  return sgp_kgrad<float, false>(kind, X, Y, nullptr, nullptr, z, ell, dl, Q, R, zbar, ellbar, N, M, d, P, ws, (hipStream_t)stream);
 }
 extern "C" int hb_sgp_kgrad_f64(int kind, const double* X, const double* Y, const double* z, const double* ell, long dl,
                                 const double* Q, const double* R, double* zbar, double* ellbar, long N, long M, long d, long P,
                                 double* ws, void* stream) {
-  return sgp_kgrad<double>(kind, X, Y, z, ell, dl, Q, R, zbar, ellbar, N, M, d, P, ws, (hipStream_t)stream);
+  return sgp_kgrad<double, false>(kind, X, Y, nullptr, nullptr, z, ell, dl, Q, R, zbar, ellbar, N, M, d, P, ws, (hipStream_t)stream);
+}
+extern "C" int hb_sgp_wkgrad_f32(int kind, const float* X, const double* w, const double* r, const double* z, const double* ell,
+                                 long dl, const double* Q, const double* R, double* zbar, double* ellbar, long N, long M, long d,
+                                 double* ws, void* stream) {
+  return sgp_kgrad<float, true>(kind, X, nullptr, w, r, z, ell, dl, Q, R, zbar, ellbar, N, M, d, 1, ws, (hipStream_t)stream);
+}
+extern "C" int hb_sgp_wkgrad_f64(int kind, const double* X, const double* w, const double* r, const double* z, const double* ell,
+                                 long dl, const double* Q, const double* R, double* zbar, double* ellbar, long N, long M, long d,
+                                 double* ws, void* stream) {
+  return sgp_kgrad<double, true>(kind, X, nullptr, w, r, z, ell, dl, Q, R, zbar, ellbar, N, M, d, 1, ws, (hipStream_t)stream);
 }

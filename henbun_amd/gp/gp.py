@@ -434,7 +434,7 @@ class SparseGP(GP):
         stats = self._statistics_f64(sess, Xd, Yd, z, ell, W)
         return self._grad_from_statistics(sess, Xd, Yd, z, ell, W, stats, noise_var, k_var, residual)
 
-    def _grad_inputs(self, X, Y):
+    def _grad_inputs(self, X, Y, who="collapsed_bound_and_grad"):
         """(sess, Xd, Yd, z, ell, W): the data as the session stores it, z and the lengthscales as the session stores
         them carried in double, and W = chol(K(z, z) + jitter I)^-1 in double."""
         sess, zvar, ls = self._stats_session()
@@ -443,13 +443,11 @@ class SparseGP(GP):
         up = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=sess.np_dtype).astype(np.float64))).to(sess.device)
         z, ell = up(sess.read_value(zvar)), up(np.reshape(sess.read_value(ls), [-1]))
         if Xd.shape[0] != Yd.shape[0] or Xd.shape[1] != z.shape[1]:
-            raise ValueError("collapsed_bound_and_grad: X %s, Y %s do not match z %s"
-                             % (tuple(Xd.shape), tuple(Yd.shape), tuple(z.shape)))
+            raise ValueError("%s: X %s, Y %s do not match z %s" % (who, tuple(Xd.shape), tuple(Yd.shape), tuple(z.shape)))
         L, info = H.cholesky(H.gram_fwd(z, z, ell, diag_add=float(settings.numerics.jitter_level)))
         bad = int(info.cpu()[0])
         if bad != 0:
-            raise G.CholeskyError("collapsed_bound_and_grad: leading minor %d of K(z, z) + jitter I is not positive "
-                                  "definite" % bad)
+            raise G.CholeskyError("%s: leading minor %d of K(z, z) + jitter I is not positive definite" % (who, bad))
         return sess, Xd, Yd, z, ell, H.trinv(L)
 
     def _statistics_f64(self, sess, Xd, Yd, z, ell, W):
@@ -482,18 +480,7 @@ class SparseGP(GP):
         D = (H.matmul(m, m, transA=True, alpha=-0.5) - (0.5 * P) * H.matmul(V, V, transA=True)).contiguous()
         Gm = H.matutil((D * (k / s2)).contiguous(), H.MATUTIL_ADD_EYE, alpha=rho * P * k / (2.0 * s2))
         g = (m * (np.sqrt(k) / s2)).contiguous()
-        # streamed part: Q = 2 W^T G W, R = W^T g^T
-        Q = H.matmul(W, H.matmul(Gm, W), transA=True, alpha=2.0)
-        R = H.matmul(W, g, transA=True, transB=True)
-        zbar, ellbar = H.sgp_kgrad(Xd, Yd, z, ell, Q, R)
-        # Kmm part: L^T Lbar = T = -(2 G Phi + g^T b); the Cholesky VJP; the Gram VJP of K(z, z)
-        T = (H.matmul(Gm, Phi, alpha=-2.0) - H.matmul(g, b, transA=True)).contiguous()
-        S = H.matmul(W, H.matmul(H.matutil(T, H.MATUTIL_PHI), W), transA=True)
-        Kmmbar = H.matutil(S, H.MATUTIL_SYM)
-        zk = torch.empty((M, d), dtype=torch.float64, device=sess.device)
-        ek = torch.empty((ell.numel(),), dtype=torch.float64, device=sess.device)
-        H.gram_bwd_raw(H.KERN_RBF | H.KERN_KBAR_SYMMETRIC, z, 0, z, 0, ell, 0, ell.numel(), Kmmbar, zk, zk, ek, 1, M, M, d,
-                       H.workspace(torch.float64, sess.device, max(M * d, 1)))
+        zg, eg = self._kernel_grads(sess, z, ell, W, Gm, g, Phi, b, lambda Q, R: H.sgp_kgrad(Xd, Yd, z, ell, Q, R))
         # scalars and the value, on the host
         tau, mb, mc = float((D * Phi).sum().cpu()), float((m * b).sum().cpu()), float((m * c).sum().cpu())
         a2sum, yys = float(torch.diagonal(Phi).sum().cpu()), float(yy.sum().cpu())
@@ -504,9 +491,102 @@ class SparseGP(GP):
         dk = tau / s2 + mb / (2.0 * np.sqrt(k) * s2) - rho * P * (N - a2sum) / (2.0 * s2)
         ds2 = (-N * P / (2.0 * s2) + yys / (2.0 * s2 ** 2) - (k / s2 ** 2) * tau - mc / s2
                + rho * P * k * (N - a2sum) / (2.0 * s2 ** 2))
-        grad = dict(z=(zbar + zk).cpu().numpy(), lengthscales=(ellbar + ek).cpu().numpy(), noise_var=float(ds2),
-                    k_var=float(dk))
+        grad = dict(z=zg.cpu().numpy(), lengthscales=eg.cpu().numpy(), noise_var=float(ds2), k_var=float(dk))
         return float(val), grad
+
+    def _kernel_grads(self, sess, z, ell, W, Gm, g, Phi, b, streamed):
+        """(zbar [M, d], ellbar [dl]) of a bound whose dependence on A = W K(z, X) is Abar = 2 G A diag(w) + g^T r^T, given
+        G = `Gm` [M, M], g [P, M] and the statistics Phi = A diag(w) A^T, b = (A r)^T (w = 1, r = Y for the collapsed
+        bound).  `streamed(Q, R)` returns the part through K(z, X) for Q = 2 W^T G W, R = W^T g^T (hb_sgp_kgrad /
+        hb_sgp_wkgrad); the part through K(z, z) is L^T Lbar = T = -Abar A^T = -(2 G Phi + g^T b), the Cholesky VJP and
+        the symmetric Gram VJP."""
+        torch, H = sess.torch, sess.H
+        M, d = z.shape
+        Q = H.matmul(W, H.matmul(Gm, W), transA=True, alpha=2.0)
+        R = H.matmul(W, g, transA=True, transB=True)
+        zbar, ellbar = streamed(Q, R)
+        T = (H.matmul(Gm, Phi, alpha=-2.0) - H.matmul(g, b, transA=True)).contiguous()
+        S = H.matmul(W, H.matmul(H.matutil(T, H.MATUTIL_PHI), W), transA=True)
+        Kmmbar = H.matutil(S, H.MATUTIL_SYM)
+        zk = torch.empty((M, d), dtype=torch.float64, device=sess.device)
+        ek = torch.empty((ell.numel(),), dtype=torch.float64, device=sess.device)
+        H.gram_bwd_raw(H.KERN_RBF | H.KERN_KBAR_SYMMETRIC, z, 0, z, 0, ell, 0, ell.numel(), Kmmbar, zk, zk, ek, 1, M, M, d,
+                       H.workspace(torch.float64, sess.device, max(M * d, 1)))
+        return zbar + zk, ellbar + ek
+
+    def elbo_and_grad(self, X, Y, likelihood, q, k_var=1.0, residual="diagonal"):
+        """(value, grad): the ELBO sum_j E_q log p(y_j | f_j) - KL(q || N(0, I)) of a factorising likelihood at a FIXED
+        q(u) = N(m, S S^T), q = (m [1, M], S [M, M] lower), and its partial gradient with respect to the CONSTRAINED
+        z, lengthscales and k_var at that q: grad = dict(z=[M, d], lengthscales=[dl], k_var=float), float64 numpy.  At
+        the q natgrad_q converges to, the partial gradient is the total derivative of the fitted ELBO (envelope
+        property); with the Gaussian likelihood and q = optimal_q it is the gradient of collapsed_bound_and_grad.
+
+        With the sites lam_j = E[-d2 log p], gamma_j = E[d log p] of hb_lik_sites at the marginals mu_j, v_j:
+        dl_j/dmu_j = gamma_j, dl_j/dv_j = -lam_j / 2 (Stein's identity: exact for the Gaussian and Poisson sites, for
+        Bernoulli the derivative of the 20-node quadrature up to its error), so
+            Abar = 2 G A diag(lam) + g^T gamma^T,   G = -(k_var / 2) (S S^T - rho I),   g = sqrt(k_var) m
+        (rho = 1 for residual 'diagonal', 0 for 'neglected'; the |.| samples() applies to 1 - a_j^T a_j is ignored, as
+        for collapsed_bound), which is the form of the collapsed bound's gradient with column weights: the streamed part
+        is hb_sgp_wkgrad, the K(z, z) part needs Phi_w = A diag(lam) A^T and b_w = (A gamma)^T, and
+        dF/dk_var = sum_j (gamma_j mu_j - lam_j v_j) / (2 k_var).
+
+        FLOAT64 ARITHMETIC end to end whatever the session's dtype, for the reason collapsed_bound_and_grad gives.  The
+        data is walked in fixed-size column chunks up-converted to double: the marginals (hb_sgp_predict_f64), the
+        sites (hb_lik_sites_f64) and the weighted statistics (hb_sgp_wstats_f64), the chunks' sums added in chunk order;
+        then the M^3 tail, hb_sgp_wkgrad over all of X in its stored dtype and the Gram VJP of K(z, z).  Restrictions
+        and exception types are natgrad_q's: UnitRBF, one expert, Y [N, 1]; residual 'fullrank' and a mean-field q
+        raise NotImplementedError; a K(z, z) + jitter I that is not positive definite raises graph.CholeskyError; a
+        likelihood that is no henbun_amd.likelihoods.Likelihood raises TypeError."""
+        from ..likelihoods import Likelihood
+
+        self._check_residual(residual)
+        if not isinstance(likelihood, Likelihood):
+            raise TypeError("elbo_and_grad: likelihood must be a henbun_amd.likelihoods.Likelihood, got %s"
+                            % type(likelihood).__name__)
+        k = float(k_var)
+        if not k > 0.0:
+            raise ValueError("elbo_and_grad: k_var must be positive (got %r)" % (k_var,))
+        m0, S0 = (np.asarray(a, dtype=np.float64) for a in q)
+        if S0.ndim != 2:
+            raise NotImplementedError("elbo_and_grad: q must be a full-rank q, (m [1, M], S [M, M]); a mean-field q is "
+                                      "not covered")
+        sess, Xd, Yd, z, ell, W = self._grad_inputs(X, Y, "elbo_and_grad")
+        torch, H = sess.torch, sess.H
+        if Yd.shape[1] != 1:
+            raise NotImplementedError("elbo_and_grad: one latent function only (Y must be [N, 1], got %s)" % (tuple(Yd.shape),))
+        N, M = int(Xd.shape[0]), int(z.shape[0])
+        if m0.size != M or S0.shape != (M, M):
+            raise ValueError("elbo_and_grad: q = (m [1, %d], S [%d, %d]) expected, got %s %s" % (M, M, M, m0.shape, S0.shape))
+        rho = 1.0 if residual == "diagonal" else 0.0
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(sess.device)
+        m, S = up(m0.reshape(1, M)), up(np.tril(S0))
+        mode = H.SGP_DIAGONAL if residual == "diagonal" else H.SGP_NEGLECTED
+        lam = torch.empty((N,), dtype=torch.float64, device=sess.device)
+        gam = torch.empty_like(lam)
+        chunk = int(min(32768, max(32, (1 << 24) // M))) & ~31            # a multiple of 32: every chunk of lam stays 16-byte aligned
+        Phi = b = lsum = dks = None
+        for c0 in range(0, N, chunk):
+            Xc = Xd[c0:c0 + chunk].to(torch.float64).contiguous()
+            yc = Yd[c0:c0 + chunk, 0].to(torch.float64).contiguous()
+            mean, var = H.sgp_predict(Xc, z, ell, W, m, S, s_kind=H.SGP_S_TRIL, mode=mode)       # unit-variance moments [1, nc]
+            lc, bc = lam[c0:c0 + chunk], gam[c0:c0 + chunk]
+            _, _, ls = H.lik_sites(likelihood.lik_id, yc, mean, var, param=likelihood.param, mscale=np.sqrt(k), vscale=k,
+                                   out=(lc, bc))
+            mu = mean.reshape(-1) * np.sqrt(k)
+            bc -= lc * mu                                                   # gamma = beta - lam mu
+            Pc, rc, _ = H.sgp_wstats(Xc, lc, bc, z, ell, W)
+            dc = (bc * mu - lc * var.reshape(-1) * k).sum()
+            Phi, b, lsum, dks = (Pc, rc, ls, dc) if Phi is None else (Phi + Pc, b + rc, lsum + ls, dks + dc)
+        # tail: G = dF/dPhi_w, g = dF/db_w
+        Gm = H.matutil((H.matmul(S, S, transB=True) * (-0.5 * k)).contiguous(), H.MATUTIL_ADD_EYE, alpha=0.5 * rho * k)
+        g = (m * np.sqrt(k)).contiguous()
+        zg, eg = self._kernel_grads(sess, z, ell, W, Gm, g, Phi.contiguous(), b.contiguous(),
+                                    lambda Q, R: H.sgp_wkgrad(Xd, lam, gam, z, ell, Q, R))
+        # KL(q || N(0, I)) and dF/dk_var: scalars on the host
+        Sl = np.tril(S0)
+        kl = 0.5 * (float((Sl * Sl).sum()) + float((m0 * m0).sum()) - M) - float(np.log(np.abs(np.diagonal(Sl))).sum())
+        grad = dict(z=zg.cpu().numpy(), lengthscales=eg.cpu().numpy(), k_var=float(dks.cpu()) / (2.0 * k))
+        return float(lsum.cpu()[0]) - kl, grad
 
     def _predict_generic(self, x, m, s, s_kind, q_shape, jitter):
         """predict_f composed from generic graph ops (non-RBF kernels, 3-D x), the way samples() composes its draw."""

@@ -1225,6 +1225,36 @@ def sgp_kgrad(X, Y, z, ell, Q, R, ws=None):
     return zbar, ellbar
 
 
+def sgp_wkgrad(X, w, r, z, ell, Q, R, ws=None):
+    """Column-weighted form of sgp_kgrad (hb_sgp_wkgrad): Kbar_ij = w_j (Q K)_ij + R_i r_j, one latent function.  X [N, d]
+    in its storage dtype (float32 or float64); w [N], r [N], z [M, d], ell [dl], Q [M, M], R [M, 1] are float64 and all
+    arithmetic is float64.  Returns (zbar [M, d], ellbar [dl]) as sgp_kgrad does; w == 1, r = Y[:, 0] returns its bits at
+    P = 1; two calls on the same inputs return the same bits."""
+    for t in (X, w, r, z, ell, Q, R):
+        _chk(t)
+    if X.dim() != 2 or z.dim() != 2 or X.shape[1] != z.shape[1] or tuple(w.shape) != (X.shape[0],) or tuple(r.shape) != w.shape:
+        raise ValueError("sgp_wkgrad: X [N, d], w [N], r [N], z [M, d] expected, got %s %s %s %s"
+                         % (tuple(X.shape), tuple(w.shape), tuple(r.shape), tuple(z.shape)))
+    N, d = X.shape
+    M = z.shape[0]
+    if ell.dim() != 1 or ell.numel() not in (1, d) or tuple(Q.shape) != (M, M) or tuple(R.shape) != (M, 1):
+        raise ValueError("sgp_wkgrad: ell [1] or [d], Q [M, M], R [M, 1] expected, got %s %s %s"
+                         % (tuple(ell.shape), tuple(Q.shape), tuple(R.shape)))
+    if any(t.dtype != torch.float64 for t in (w, r, z, ell, Q, R)):
+        raise TypeError("sgp_wkgrad: X in its storage dtype; w, r, z, ell, Q, R must be float64")
+    dev = X.device
+    zbar = _empty((M, d), dtype=torch.float64, device=dev)
+    ellbar = _empty((ell.numel(),), dtype=torch.float64, device=dev)
+    need = sgp_kgrad_ws_elems(N, M, d, 1)
+    if ws is None:
+        ws = workspace(torch.float64, dev, max(need, 1))
+    if ws.dtype != torch.float64 or ws.numel() < need:
+        raise ValueError("sgp_wkgrad: the workspace must hold %d float64 elements (sgp_kgrad_ws_elems)" % need)
+    _lib.lib().call("hb_sgp_wkgrad" + _suf(X), KERN_RBF, _p(X), _p(w), _p(r), _p(z), _p(ell), ell.numel(), _p(Q), _p(R),
+                    _p(zbar), _p(ellbar), N, M, d, _p(ws), stream())
+    return zbar, ellbar
+
+
 def sgp_select_ws_elems(dtype, N, M, d):
     """Scratch elements hb_sgp_select needs: the history C [M, N], dvar [N] and the arg-max partials -- O(M N)."""
     return int(_lib.lib().raw("hb_sgp_select_ws_elems")(int(N), int(M), int(d), 4 if dtype == torch.float32 else 8))

@@ -12,6 +12,56 @@ import henbun_amd as hb  # noqa: E402  (the package is fully imported before thi
 tf = hb.tf
 
 
+def _adam_ascent(model, evaluate, steps, lr, train_z):
+    """The host-side float64 Adam ASCENT loop SVGP.fit_hyper and SVGPLik.fit_hyper share: `steps` steps on the raw
+    parameters of model._hyper_variables() (z only with train_z) with the (value, raw gradient) `evaluate()` returns,
+    written back after every step.  Returns the trace of values, steps + 1 entries.  A graph.CholeskyError out of
+    `evaluate` is re-raised with the raw parameters of the last successful evaluation restored."""
+    from henbun_amd.graph import CholeskyError
+
+    model.initialize()
+    sess = model._session
+    hv = model._hyper_variables()
+    names = [n for n in hv if train_z or n != "z"]
+    for v in hv.values():
+        sess.read_value(v)   # uploads a value that was assigned and not yet written
+    raw = {n: sess.read_raw(hv[n]).astype(np.float64) for n in names}
+    m1 = {n: np.zeros_like(raw[n]) for n in names}
+    m2 = {n: np.zeros_like(raw[n]) for n in names}
+    b1, b2, eps = 0.9, 0.999, 1e-8
+    good = {n: raw[n].copy() for n in names}
+    trace = []
+    for t in range(int(steps) + 1):
+        try:
+            value, grad = evaluate()
+        except CholeskyError:
+            for n in names:
+                sess.write_raw(hv[n], good[n])
+            raise
+        trace.append(value)
+        good = {n: raw[n].copy() for n in names}
+        if t == int(steps):
+            break
+        for n in names:
+            m1[n] = b1 * m1[n] + (1.0 - b1) * grad[n]
+            m2[n] = b2 * m2[n] + (1.0 - b2) * grad[n] ** 2
+            step = lr * (m1[n] / (1.0 - b1 ** (t + 1))) / (np.sqrt(m2[n] / (1.0 - b2 ** (t + 1))) + eps)
+            sess.write_raw(hv[n], raw[n] + step)
+            raw[n] = sess.read_raw(hv[n]).astype(np.float64)   # what the session holds (rounded in a float32 session)
+    return np.asarray(trace)
+
+
+def _chain_to_raw(model, cons):
+    """Gradients with respect to the RAW parameters of model._hyper_variables() from those with respect to the constrained
+    values `cons` (same names): shaped like the raw arrays and multiplied by the transforms' dforward, float64 numpy."""
+    sess = model._session
+    grad = {}
+    for name, v in model._hyper_variables().items():
+        raw = sess.read_raw(v)
+        grad[name] = np.reshape(np.asarray(cons[name], dtype=np.float64), raw.shape) * v.transform.dforward(raw)
+    return grad
+
+
 class SVGP(hb.model.Model):
     """Sparse variational GP regression: cfg 1/2 (q_shape='diagonal') and cfg 3 ('fullrank')."""
 
@@ -122,13 +172,7 @@ class SVGP(hb.model.Model):
         through the transforms' dforward."""
         X, Y, var, k_var = self._closed_form_inputs()
         value, gr = object.__getattribute__(self, "gp").collapsed_bound_and_grad(X, Y, var, k_var, residual=self.residual)
-        sess = self._session
-        cons = dict(z=gr["z"], lengthscales=gr["lengthscales"], k_var=gr["k_var"], var=gr["noise_var"])
-        grad = {}
-        for name, v in self._hyper_variables().items():
-            raw = sess.read_raw(v)
-            grad[name] = np.reshape(np.asarray(cons[name], dtype=np.float64), raw.shape) * v.transform.dforward(raw)
-        return value, grad
+        return value, _chain_to_raw(self, dict(z=gr["z"], lengthscales=gr["lengthscales"], k_var=gr["k_var"], var=gr["noise_var"]))
 
     def fit_hyper(self, steps, lr=0.01, train_z=True):
         """Full-batch fit of the hyper-parameters: `steps` Adam ASCENT steps on the collapsed bound in the raw
@@ -138,39 +182,9 @@ class SVGP(hb.model.Model):
         trace of bound values, steps + 1 entries: before the first step .. at the final parameters.  A step after
         which K(z, z) + jitter I or Lambda is no longer positive definite raises graph.CholeskyError with the last good
         parameters restored."""
-        from henbun_amd.graph import CholeskyError
-
-        self.initialize()
-        sess = self._session
-        hv = self._hyper_variables()
-        names = [n for n in hv if train_z or n != "z"]
-        for v in hv.values():
-            sess.read_value(v)   # uploads a value that was assigned and not yet written
-        raw = {n: sess.read_raw(hv[n]).astype(np.float64) for n in names}
-        m1 = {n: np.zeros_like(raw[n]) for n in names}
-        m2 = {n: np.zeros_like(raw[n]) for n in names}
-        b1, b2, eps = 0.9, 0.999, 1e-8
-        good = {n: raw[n].copy() for n in names}
-        trace = []
-        for t in range(int(steps) + 1):
-            try:
-                value, grad = self.collapsed_bound_and_grad()
-            except CholeskyError:
-                for n in names:
-                    sess.write_raw(hv[n], good[n])
-                raise
-            trace.append(value)
-            good = {n: raw[n].copy() for n in names}
-            if t == int(steps):
-                break
-            for n in names:
-                m1[n] = b1 * m1[n] + (1.0 - b1) * grad[n]
-                m2[n] = b2 * m2[n] + (1.0 - b2) * grad[n] ** 2
-                step = lr * (m1[n] / (1.0 - b1 ** (t + 1))) / (np.sqrt(m2[n] / (1.0 - b2 ** (t + 1))) + eps)
-                sess.write_raw(hv[n], raw[n] + step)
-                raw[n] = sess.read_raw(hv[n]).astype(np.float64)   # what the session holds (rounded in a float32 session)
+        trace = _adam_ascent(self, self.collapsed_bound_and_grad, steps, lr, train_z)
         self.fit_q()
-        return np.asarray(trace)
+        return trace
 
 
 class SVGPLik(hb.model.Model):
@@ -218,21 +232,78 @@ class SVGPLik(hb.model.Model):
         writes them for 'fullrank'.  Returns (m [1, M], S [M, M], info) as natgrad_q does.  A full step (rho = 1) from a q
         far from the optimum, such as a freshly initialised one, can overshoot before it settles: info['elbo'] shows it,
         and rho < 1 damps it."""
-        from henbun_amd.param import tri_pack, tri_unpack
+        from henbun_amd.param import tri_pack
 
         self.initialize()
         g = lambda k: object.__getattribute__(self, k)
         q, sess = g("u"), self._session
         q_mu, q_sqrt = object.__getattribute__(q, "q_mu"), object.__getattribute__(q, "q_sqrt")
-        M = q.size
-        S0 = np.asarray(sess.read_raw(q_sqrt), dtype=np.float64)
-        S0 = tri_unpack(S0.reshape(-1)) if q.packed else np.tril(S0.reshape(M, M))
-        m0 = np.asarray(sess.read_raw(q_mu), dtype=np.float64).reshape(1, M)
+        m0, S0 = self._current_q()
         m, S, info = g("gp").natgrad_q(g("X"), g("Y"), g("likelihood"), k_var=float(np.ravel(g("k_var").value)[0]),
                                        residual=self.residual, q0=(m0, S0), steps=steps, rho=rho, tol=tol)
         sess.write_raw(q_mu, m.reshape(-1))
         sess.write_raw(q_sqrt, tri_pack(S) if q.packed else S)
         return m, S, info
+
+    def reset_q(self):
+        """Set q(u) to the prior N(0, I), where natgrad_q's own default starts.  A freshly built model holds a RANDOM q(u),
+        from which a full natural-gradient step (rho = 1) overshoots: call this before the first fit_q() / fit_hyper()."""
+        from henbun_amd.param import tri_pack
+
+        self.initialize()
+        q, sess = object.__getattribute__(self, "u"), self._session
+        M = q.size
+        sess.write_raw(object.__getattribute__(q, "q_mu"), np.zeros(M))
+        sess.write_raw(object.__getattribute__(q, "q_sqrt"), tri_pack(np.eye(M)) if q.packed else np.eye(M))
+
+    def _current_q(self):
+        """(m [1, M], S [M, M] lower) of the model's q(u) as the session stores it, float64 numpy."""
+        from henbun_amd.param import tri_unpack
+
+        self.initialize()
+        q, sess = object.__getattribute__(self, "u"), self._session
+        M = q.size
+        S = np.asarray(sess.read_raw(object.__getattribute__(q, "q_sqrt")), dtype=np.float64)
+        S = tri_unpack(S.reshape(-1)) if q.packed else np.tril(S.reshape(M, M))
+        return np.asarray(sess.read_raw(object.__getattribute__(q, "q_mu")), dtype=np.float64).reshape(1, M), S
+
+    def _hyper_variables(self):
+        """The Variables the ELBO at a fixed q(u) depends on, by the names the gradient uses."""
+        g = object.__getattribute__
+        gp = g(self, "gp")
+        return dict(z=g(gp, "z"), lengthscales=g(g(gp, "kern"), "lengthscales"), k_var=g(self, "k_var"))
+
+    def elbo_and_grad(self):
+        """(value, grad): the ELBO over the model's full X, Y at the model's CURRENT q(u) and its partial gradient at
+        that q with respect to the RAW (free) parameters, grad = dict(z, lengthscales, k_var) in the shapes of the raw
+        arrays, float64 numpy.  SparseGP.elbo_and_grad (float64 arithmetic whatever the session's dtype), chained
+        through the transforms' dforward.  After fit_q() has converged this is the total derivative of the fitted ELBO."""
+        g = lambda k: object.__getattribute__(self, k)
+        q = self._current_q()
+        value, cons = g("gp").elbo_and_grad(g("X"), g("Y"), g("likelihood"), q, k_var=float(np.ravel(g("k_var").value)[0]),
+                                            residual=self.residual)
+        return value, _chain_to_raw(self, cons)
+
+    def fit_hyper(self, steps, lr=0.01, train_z=True, q_steps=5, rho=1.0):
+        """Deterministic full-batch fit of the hyper-parameters, alternating as GPflow's natural-gradient recipe does:
+        every outer step runs fit_q(steps=q_steps, rho=rho) from the current q(u), then takes ONE Adam ASCENT step on
+        elbo_and_grad() in the raw parameters of lengthscales, k_var and (train_z) z -- on the host in float64, the
+        loop of SVGP.fit_hyper.  No minibatch noise.  Ends with a fit_q() at the final parameters.  Returns the trace of
+        ELBO values, steps + 1 entries: after the first fit_q at the starting parameters .. after the closing fit_q()
+        at the final ones.  A step after which a factorisation fails raises graph.CholeskyError with the last good
+        parameters restored.  The first fit_q starts at the model's current q(u): from a freshly initialised (random)
+        q a full step overshoots (see fit_q), so call reset_q() first (or fit q(u) some other way, or pass rho < 1)."""
+        steps, done = int(steps), [0]
+
+        def evaluate():
+            if done[0] == steps:
+                self.fit_q()
+            else:
+                self.fit_q(steps=q_steps, rho=rho)
+            done[0] += 1
+            return self.elbo_and_grad()
+
+        return _adam_ascent(self, evaluate, steps, lr, train_z)
 
 
 class Amortised(hb.model.Model):

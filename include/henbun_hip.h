@@ -50,7 +50,7 @@ extern "C" {
  * conditional-variance selection of inducing points); hb_sgp_kgrad_f32 / _f64 and hb_sgp_kgrad_ws_elems (streamed part
  * of the gradient of the collapsed bound); hb_sgp_wstats_f32 / _f64, hb_sgp_wstats_ws_elems, hb_lik_sites_f32 / _f64,
  * hb_lik_sites_ws_elems, hb_lik_predict_f32 / _f64 and the enum values HB_LIK_* (natural-gradient fit of q(u) for
- * non-Gaussian likelihoods). */
+ * non-Gaussian likelihoods); hb_sgp_wkgrad_f32 / _f64 (streamed part of the gradient of the ELBO at a fixed q(u)). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -704,6 +704,20 @@ int hb_sgp_kgrad_f32(int kind, const float* X, const float* Y, const double* z, 
                      const double* R, double* zbar, double* ellbar, long N, long M, long d, long P, double* ws, void* stream);
 int hb_sgp_kgrad_f64(int kind, const double* X, const double* Y, const double* z, const double* ell, long dl, const double* Q,
                      const double* R, double* zbar, double* ellbar, long N, long M, long d, long P, double* ws, void* stream);
+/* Column-weighted form of hb_sgp_kgrad_* (same file; not in the reference), the streamed part of the gradient of the ELBO
+ * of a factorising likelihood at a fixed q(u) (SparseGP.elbo_and_grad): one latent function (P = 1) and
+ *   Kbar_ij = w_j (Q K)_ij + R_i r_j,  E = Kbar o K,  zbar and ellbar as above
+ * with per-point weights w [N], r [N] in DOUBLE whatever the storage type of X (any sign, zeros included; in the model
+ * w_j = E[-d2 log p_j], r_j = E[d log p_j]), R [M, 1].  The same kernels with one template flag: w is staged next to r
+ * and multiplies the accumulator of Q K before + R r, so w == 1, r = Y[:, 0] returns the bits of hb_sgp_kgrad_* at P = 1.
+ * Same shapes for the two forms, the same diagnostic switch, the same fold launch, two calls return the same bits;
+ * ws >= hb_sgp_kgrad_ws_elems(N, M, d, 1) doubles. */
+int hb_sgp_wkgrad_f32(int kind, const float* X, const double* w, const double* r, const double* z, const double* ell, long dl,
+                      const double* Q, const double* R, double* zbar, double* ellbar, long N, long M, long d, double* ws,
+                      void* stream);
+int hb_sgp_wkgrad_f64(int kind, const double* X, const double* w, const double* r, const double* z, const double* ell, long dl,
+                      const double* Q, const double* R, double* zbar, double* ellbar, long N, long M, long d, double* ws,
+                      void* stream);
 /* VJP given fbar [E,P,n]:
  *   Abar = u^T fbar + A diag(c),  c = -eps sign(v)/sqrt|v| * sum_p fbar_p
  *   Kbar = W^T Abar            [E,M,n]  (scratch output, kept for Lbar)
