@@ -13,17 +13,43 @@
 // hb_fma().
 #pragma clang fp contract(off)
 
+// Host builds that prove the step bound (tests/host_ew) count the trips of the recurrence through this hook.
+#ifndef HB_DIGAMMA_TRIP
+#define HB_DIGAMMA_TRIP()
+#endif
+#define HB_DIGAMMA_MAX_TRIPS 6
+
 template <typename T>
 __device__ __forceinline__ T hb_digamma(T x) {
-  // recurrence up to x >= 6, then asymptotic series
+  // Every bit pattern finishes within HB_DIGAMMA_MAX_TRIPS steps of the recurrence.
+  //   x > 0 (and +-0, NaN, +inf): recurrence up to x >= 6, then the asymptotic series.  A positive x needs at most six
+  //     steps (x + 1 == 1 for a tiny x, then 1..5); +0 -> -inf and -0 -> +inf through 1/x, NaN and +inf pass through.
+  //   x < 0: reflection psi(x) = psi(1 - x) + pi / tan(pi * fr), fr = (-x) - floor(-x) moved into [-1/2, 1/2] (both
+  //     steps exact, tan has period pi), so the argument of the recurrence is 1 - x > 1.  The poles (negative
+  //     integers, and with them every x <= -2^23 resp. -2^52, where only integers are left) and -inf return NaN.
+  // Accuracy: the series stops after the x^-10 term; the first one left out, 691 / (32760 x^12), is 1e-11 at x = 6 and
+  // falls from there.  That is below float's rounding but about 5e4 ulp of a double: hb_digamma<double> is good to
+  // 1e-11 absolute, no better, for x below about 15, and the tests (tests/ew_ref.py) allow it exactly that.  More
+  // terms or a later switch to the series would buy double precision at the cost of more steps.
+  T refl = T(0);
+  if (x < T(0)) {
+    const T y = -x;
+    T fr = y - hb_floor(y);
+    if (!(fr > T(0))) return hb_nan<T>();   // pole, or -inf (inf - inf)
+    if (fr > T(0.5)) fr -= T(1);
+    refl = T(3.14159265358979323846) / hb_tan(T(3.14159265358979323846) * fr);
+    x = T(1) + y;
+  }
   T r = T(0);
-  while (x < T(6)) {
+  for (int t = 0; t < HB_DIGAMMA_MAX_TRIPS && x < T(6); ++t) {
+    HB_DIGAMMA_TRIP();
     r -= T(1) / x;
     x += T(1);
   }
   const T f = T(1) / (x * x);
-  return r + hb_log(x) - T(0.5) / x -
-         f * (T(1.0 / 12) - f * (T(1.0 / 120) - f * (T(1.0 / 252) - f * (T(1.0 / 240) - f * T(1.0 / 132)))));
+  const T v = r + hb_log(x) - T(0.5) / x -
+              f * (T(1.0 / 12) - f * (T(1.0 / 120) - f * (T(1.0 / 252) - f * (T(1.0 / 240) - f * T(1.0 / 132)))));
+  return v + refl;
 }
 
 template <typename T>

@@ -62,6 +62,15 @@ template <> __device__ __forceinline__ double hb_tanh<double>(double x) { return
 template <typename T> __device__ __forceinline__ T hb_lgamma(T x);
 template <> __device__ __forceinline__ float hb_lgamma<float>(float x) { return lgammaf(x); }
 template <> __device__ __forceinline__ double hb_lgamma<double>(double x) { return lgamma(x); }
+template <typename T> __device__ __forceinline__ T hb_tan(T x);
+template <> __device__ __forceinline__ float hb_tan<float>(float x) { return tanf(x); }
+template <> __device__ __forceinline__ double hb_tan<double>(double x) { return tan(x); }
+template <typename T> __device__ __forceinline__ T hb_floor(T x);
+template <> __device__ __forceinline__ float hb_floor<float>(float x) { return __builtin_floorf(x); }
+template <> __device__ __forceinline__ double hb_floor<double>(double x) { return __builtin_floor(x); }
+template <typename T> __device__ __forceinline__ T hb_nan();
+template <> __device__ __forceinline__ float hb_nan<float>() { return __builtin_nanf(""); }
+template <> __device__ __forceinline__ double hb_nan<double>() { return __builtin_nan(""); }
 template <typename T> __device__ __forceinline__ T hb_pow(T x, T y);
 template <> __device__ __forceinline__ float hb_pow<float>(float x, float y) { return powf(x, y); }
 template <> __device__ __forceinline__ double hb_pow<double>(double x, double y) { return pow(x, y); }
@@ -85,7 +94,11 @@ __device__ __forceinline__ T hb_sigmoid(T x) {
 template <>
 __device__ __forceinline__ float hb_sigmoid<float>(float x) {
   // 1 / (1 + e^-x) as it stands: for x < -88 the exponential overflows to +inf and v_rcp_f32 returns 0, which is the
-  // value (6e-39 and below) to fp32 precision; everywhere else both factors are good to 1 ulp.  Four vector instructions
+  // value (6e-39 and below) to fp32 precision.  The two instructions are good to 1 ulp each, the result is not:
+  // __expf(-x) is v_exp_f32(round(log2(e) * -x)) with a float log2(e) (2^-26 off), so the exponential carries a
+  // relative error of |x| * (2^-24 + 2^-26) on top of the instruction's ulp.  For x >= 0 the factor e^-x / (1 + e^-x)
+  // damps it (below 3 ulp in all); in the negative tail it passes through whole: about 0.6 * |x| ulp, 55 ulp
+  // (7e-6 relative) at x = -87, where the value is 1.6e-38 (tests/ew_ref.py derives the bound).  Four vector instructions
   // instead of seven (the |x| form needed a compare, a select and a second multiply): in the epilogues of the fp32 MFMA
   // kernels every vector instruction is paid in full, the matrix instructions share that pipe.
   return __builtin_amdgcn_rcpf(1.0f + __expf(-x));
