@@ -133,6 +133,7 @@ _TYPED = {
     "hb_sgp_wstats": [I, P, P, P, P, P, L, P, P, P, P, P, L, L, L, P, P],
     "hb_lik_sites": [I, P, P, P, D, D, D, P, P, P, L, P, P],
     "hb_lik_predict": [I, P, P, D, P, P, L, P],
+    "hb_sgp_pathwise": [I, P, P, P, P, L, P, D, P, L, L, L, L, L, P],
     "hb_sgp_select": [I, P, P, L, L, L, L, D, P, P, P, P, P, P],
     "hb_sgp_kgrad": [I, P, P, P, P, L, P, P, P, P, L, L, L, L, P, P],
     "hb_sgp_wkgrad": [I, P, P, P, P, P, L, P, P, P, P, L, L, L, P, P],

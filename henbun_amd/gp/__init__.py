@@ -1,2 +1,2 @@
 from . import kernels
-from .gp import GP, SparseGP, greedy_inducing
+from .gp import GP, PathwiseDraws, SparseGP, greedy_inducing

@@ -208,7 +208,7 @@ class SparseGP(GP):
             z, ell = plan.buf(zt).clone().contiguous(), plan.buf(et).clone().contiguous()
         else:
             z, ell = up(sess.read_value(zvar)), up(np.reshape(sess.read_value(ls), [-1]))
-        if Xd.shape[0] != Yd.shape[0] or Xd.shape[1] != z.shape[1]:
+        if Xd is not None and (Xd.shape[0] != Yd.shape[0] or Xd.shape[1] != z.shape[1]):   # (pathwise_draws has no data)
             raise ValueError("%s: X %s, Y %s do not match z %s" % (who, tuple(Xd.shape), tuple(Yd.shape), tuple(z.shape)))
         M = z.shape[0]
         K = H.gram_fwd(z, z, ell, diag_add=float(settings.numerics.jitter_level))
@@ -588,6 +588,95 @@ class SparseGP(GP):
         grad = dict(z=zg.cpu().numpy(), lengthscales=eg.cpu().numpy(), k_var=float(dks.cpu()) / (2.0 * k))
         return float(lsum.cpu()[0]) - kl, grad
 
+    # -- pathwise posterior function draws (Wilson et al. 2020) -----------------------------------------------------
+    def pathwise_draws(self, q, num_samples, num_features=1024, k_var=1.0, seed=0, noise=None):
+        """num_samples posterior FUNCTION draws as a PathwiseDraws: each is drawn once, as 2 num_features + M
+        coefficients, and can then be evaluated anywhere at O((M + num_features) n) per draw -- no [n, n] covariance, no
+        factorisation, no jitter; the same object gives values of the same sample paths on every call.  For the whitened
+        model u ~ q = N(m, S S^T), with x~ = x / ell, W = Lm^-1, A(x) = W K(z, x) and L = num_features:
+            omega_l ~ N(0, I_d),  w_s ~ N(0, I_2L),  eps_s ~ N(0, I_M)
+            g_s(x) = L^-1/2 sum_l [ w_s,2l cos(omega_l . x~) + w_s,2l+1 sin(omega_l . x~) ]      (prior path, unit RBF)
+            u_s = m + eps_s S^T,   t_s = u_s - g_s(z) W^T,   v_s = t_s W
+            f_s(x) = sqrt(k_var) ( g_s(x) + v_s K(z, x) )  =  sqrt(k_var) ( g_s(x) + t_s A(x) ).
+        Given omega the draws are Gaussian with mean sqrt(k_var) m A(x) -- predict_f's mean exactly -- and covariance
+        k_var (C(x)^T C(x') + A^T S S^T A), C(x) = phi(x) - phi(z)^T W^T A(x), which tends to k_var (K(x, x') - A^T A +
+        A^T S S^T A) as L grows: the EXACT conditional, i.e. the 'fullrank' residual of predict_f(full_cov=True) without
+        its jitter term, whatever `residual` the model trains with.  The error of the covariance falls as 1 / sqrt(L)
+        (at most 8 / sqrt(L) observed inside the hull of the inducing points at moderate conditioning; outside the hull
+        the interpolation weights amplify the feature error, 13 / sqrt(L) was seen there).
+
+        q: a Normal / Gaussian Variational (read through its parameters by a plan: the values predict_f reads), or a
+        tuple (m [1, M], S [M, M] lower) or (m, s [M]) as numpy.  K(z, z) is factorised as the plans do it
+        (_whitening(as_plans=True)), so the draws live in the whitening predict_f and the ELBO use.  The M-sized tail runs
+        in float64 on the device whatever the session's dtype (forming t in float32 moves it by up to 9e-3 at
+        cond 1e6): g(z) by hb_sgp_pathwise_f64, the two products by hb_matmul_f64; omega and the
+        coefficients [w / sqrt(L) | v] are then stored in the session's dtype.  noise=None draws omega [L, d], w [S, 2L],
+        eps [S, M] from hip_ops.Rng(seed), in that order; noise=dict(omega=, w=, eps=) injects them (float64 arrays).
+        Restrictions and exception types are those of statistics(): UnitRBF, one expert, the lengthscales one Variable;
+        more than one latent function raises NotImplementedError; malformed q or noise raise ValueError."""
+        S, L, k_var = int(num_samples), int(num_features), float(k_var)
+        if not (S >= 1 and L >= 1 and k_var > 0.0):
+            raise ValueError("pathwise_draws: num_samples >= 1, num_features >= 1 and k_var > 0 expected (got %r, %r, %r)"
+                             % (num_samples, num_features, k_var))
+        sess, zvar, ls = self._stats_session()
+        torch, H = sess.torch, sess.H
+        M, d = int(zvar.shape[0]), int(zvar.shape[1])
+        f64 = dict(dtype=torch.float64, device=sess.device)
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(sess.device)
+        m, s = self._q_moments(sess, q, M)
+        z, ell, W, _ = self._whitening(sess, zvar, ls, None, None, "pathwise_draws", as_plans=True)
+        if noise is None:
+            rng = H.Rng(seed, device=sess.device)
+            omega, w, eps = (rng.normal(shape, dtype=torch.float64) for shape in ((L, d), (S, 2 * L), (S, M)))
+        else:
+            want = dict(omega=(L, d), w=(S, 2 * L), eps=(S, M))
+            if not isinstance(noise, dict) or set(noise) != set(want) or any(np.shape(noise[k]) != want[k] for k in want):
+                raise ValueError("pathwise_draws: noise must be dict(omega=%s, w=%s, eps=%s), got %s"
+                                 % (want["omega"], want["w"], want["eps"],
+                                    {k: np.shape(v) for k, v in noise.items()} if isinstance(noise, dict) else type(noise).__name__))
+            omega, w, eps = (up(noise[k]) for k in ("omega", "w", "eps"))
+        # the frequencies and the prior weights ARE what the session's dtype stores: g(z) below is taken from their
+        # rounded values, so the update interpolates the same prior path evaluate() adds it to
+        omega = omega.to(sess.torch_dtype).contiguous()
+        cw = (w * (1.0 / np.sqrt(L))).to(sess.torch_dtype).contiguous()
+        z64, ell64, W64 = z.to(torch.float64), ell.to(torch.float64), W.to(torch.float64)
+        U = m + (H.matmul(eps, s, transB=True) if s.dim() == 2 else eps * s)              # [S, M]
+        Gz = H.sgp_pathwise(z64, omega.to(torch.float64), None, ell64, cw.to(torch.float64))   # g_s(z_m)  [S, M]
+        T = (U - H.matmul(Gz, W64, transB=True)).contiguous()
+        V = H.matmul(T, W64)
+        coef = torch.cat([cw, V.to(sess.torch_dtype)], dim=1).contiguous()
+        return PathwiseDraws(sess, self._device_data, omega, coef, z, ell, float(np.sqrt(k_var)))
+
+    def _q_moments(self, sess, q, M):
+        """(m [1, M], S [M, M] lower or s [M]) of q(u) as float64 device tensors, for pathwise_draws."""
+        torch = sess.torch
+        if isinstance(q, (tuple, list)):
+            if len(q) != 2:
+                raise ValueError("pathwise_draws: q = (m [1, M], S [M, M] or s [M]) expected")
+            m, s = (np.asarray(a, dtype=np.float64) for a in q)
+        else:
+            mt, st, _ = _posterior_of(q)
+            from ..variationals import Gaussian
+
+            for v in ("q_mu", "q_sqrt") + (("scale",) if type(q) is Gaussian else ()):
+                sess.read_value(object.__getattribute__(q, v))      # uploads a value that was assigned and not yet written
+            plan = sess.make_plan([mt, st])
+            plan.run()
+            plan.check()
+            m, s = (np.asarray(plan.value(t), dtype=np.float64) for t in (mt, st))
+        if m.ndim >= 2 and int(np.prod(m.shape[:-1])) > 1:
+            raise NotImplementedError("pathwise_draws: one latent function only (q has shape %s)" % (m.shape,))
+        if s.ndim >= 2 and s.shape[-2:] == (M, M):
+            s = np.tril(s.reshape(M, M))
+        elif s.size == M:
+            s = s.reshape(M)
+        else:
+            raise ValueError("pathwise_draws: S [%d, %d] lower or s [%d] expected, got %s" % (M, M, M, s.shape))
+        if m.size != M:
+            raise ValueError("pathwise_draws: m [1, %d] expected, got %s" % (M, m.shape))
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(sess.device)
+        return up(m.reshape(1, M)), up(s)
+
     def _predict_generic(self, x, m, s, s_kind, q_shape, jitter):
         """predict_f composed from generic graph ops (non-RBF kernels, 3-D x), the way samples() composes its draw."""
         LnT = self._effective_LT(x)                       # 2-D x: [.., M, n];  3-D x [N, n, d]: [N, M, n]
@@ -657,6 +746,41 @@ class SparseGP(GP):
         if q_shape == "diagonal":
             return G.sub(kern.Kdiag(x), G.reduce_sum(G.square(LnT), -2))
         return G.sub(kern.K(x), G.matmul(LnT, LnT, transpose_a=True))
+
+
+class PathwiseDraws:
+    """S posterior function draws of a SparseGP (SparseGP.pathwise_draws): a snapshot of the frequencies omega [L, d], the
+    coefficient rows coef [S, 2L + M], z [M, d], the lengthscales and scale = sqrt(k_var), on the device in the session's
+    dtype.  Later changes to the model do not move it.  Every evaluation is ONE launch of hb_sgp_pathwise, linear in n;
+    the value at a point does not depend on the other points of the call, so the same draws can be evaluated in pieces,
+    on a grid now and at candidates later, and maximised."""
+
+    def __init__(self, sess, device_data, omega, coef, z, ell, scale):
+        self._sess, self._device_data = sess, device_data
+        self._omega, self._coef, self._z, self._ell, self.scale = omega, coef, z, ell, float(scale)
+        self.num_samples, self.num_features = int(coef.shape[0]), int(omega.shape[0])
+
+    def evaluate(self, X, out=None):
+        """The draws at the rows of X as a device tensor [S, n] of the session's dtype (`out`: written in place).  X: a
+        Data / MinibatchData of the model (read in full from its device buffer), a device tensor or an array [n, d]."""
+        Xd = self._device_data(self._sess, X, "X")
+        if Xd.shape[1] != self._z.shape[1]:
+            raise ValueError("PathwiseDraws: X %s does not match z %s" % (tuple(Xd.shape), tuple(self._z.shape)))
+        return self._sess.H.sgp_pathwise(Xd, self._omega, self._z, self._ell, self._coef, scale=self.scale, out=out)
+
+    def __call__(self, X):
+        """The draws at the rows of X as numpy [S, n]."""
+        return self.evaluate(X).cpu().numpy()
+
+    def _view(self, t):
+        a = t.cpu().numpy()
+        a.flags.writeable = False
+        return a
+
+    omega = property(lambda self: self._view(self._omega), doc="frequencies [L, d] (read-only numpy)")
+    coef = property(lambda self: self._view(self._coef), doc="coefficient rows [S, 2L + M] = [w / sqrt(L) | v]")
+    z = property(lambda self: self._view(self._z), doc="inducing points [M, d]")
+    lengthscales = property(lambda self: self._view(self._ell), doc="lengthscales [1] or [d]")
 
 
 def _posterior_of(q):

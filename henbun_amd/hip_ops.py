@@ -1157,6 +1157,34 @@ def sgp_wstats(X, w, r, z, ell, W, wfrag=None, ws=None):
     return Phi, b, tr
 
 
+def sgp_pathwise(x, omega, z, ell, coef, scale=1.0, out=None):
+    """S pathwise function draws at the rows of x (hb_sgp_pathwise): out [S, n] = scale coef [S, 2L + M] B(x) with
+    B = [cos / sin (omega_l . x / ell) interleaved | K(z_m, x)] synthesised inside the ONE launch.  x [n, d], omega [L, d],
+    z [M, d] or None (M = 0: the prior path alone), ell [1] or [d], coef [S, 2L + M], all of one dtype.  The value of a
+    column does not depend on the other columns: two calls, or x in pieces, return the same bits."""
+    for t in (x, omega, ell, coef) + (() if z is None else (z,)):
+        _chk(t)
+    if x.dim() != 2 or omega.dim() != 2 or coef.dim() != 2 or omega.shape[1] != x.shape[1] or (
+            z is not None and (z.dim() != 2 or z.shape[1] != x.shape[1])):
+        raise ValueError("sgp_pathwise: x [n, d], omega [L, d], z [M, d] or None, coef [S, 2L + M] expected, got %s %s %s %s"
+                         % (tuple(x.shape), tuple(omega.shape), None if z is None else tuple(z.shape), tuple(coef.shape)))
+    n, d = x.shape
+    L, M, S = omega.shape[0], 0 if z is None else z.shape[0], coef.shape[0]
+    if coef.shape[1] != 2 * L + M:
+        raise ValueError("sgp_pathwise: coef must hold 2L + M = %d columns, got %s" % (2 * L + M, tuple(coef.shape)))
+    if any(t.dtype != x.dtype for t in (omega, ell, coef)) or (z is not None and z.dtype != x.dtype):
+        raise TypeError("sgp_pathwise: all operands must share one dtype")
+    if out is None:
+        out = _empty((S, n), dtype=x.dtype, device=x.device)
+    else:
+        _chk(out)
+        if tuple(out.shape) != (S, n) or out.dtype != x.dtype:
+            raise ValueError("sgp_pathwise: out must be [%d, %d] of the operands' dtype" % (S, n))
+    _lib.lib().call("hb_sgp_pathwise" + _suf(x), KERN_RBF, _p(x), _p(omega), _p(z if M else None), _p(ell), ell.numel(), _p(coef),
+                    float(scale), _p(out), n, L, M, d, S, stream())
+    return out
+
+
 LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON = 0, 1, 2
 
 

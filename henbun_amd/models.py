@@ -121,6 +121,17 @@ class SVGP(hb.model.Model):
         """predict_f plus the Gaussian likelihood's variance: the predictive of a new observation y at Xnew."""
         return self._predict(Xnew, True)
 
+    def sample_functions(self, num_samples, num_features=1024, seed=0, noise=None):
+        """num_samples posterior function draws of the latent f as an hb.gp.PathwiseDraws (SparseGP.pathwise_draws at the
+        model's q(u), scaled by sqrt(k_var)): draws = model.sample_functions(16); draws(Xnew) is numpy [16, n], linear in
+        n, and every call evaluates the SAME sample paths.  The draws carry the exact conditional of the sparse GP (the
+        'fullrank' residual) whatever `residual` the model trains with; predict_f_samples stays the exact joint route for
+        small n."""
+        self.initialize()
+        g = lambda k: object.__getattribute__(self, k)
+        return g("gp").pathwise_draws(g("u"), num_samples, num_features=num_features,
+                                      k_var=float(np.ravel(g("k_var").value)[0]), seed=seed, noise=noise)
+
     def _closed_form_inputs(self):
         """(X, Y, noise variance, k_var) of the whole data set at the current hyper-parameters."""
         self.initialize()
@@ -213,6 +224,7 @@ class SVGPLik(hb.model.Model):
     _predict = SVGP._predict                      # reads gp, u, k_var and residual only when no noise is asked for
     predict_f = SVGP.predict_f
     predict_f_samples = SVGP.predict_f_samples
+    sample_functions = SVGP.sample_functions
     select_inducing = SVGP.select_inducing
 
     def predict_y(self, Xnew):

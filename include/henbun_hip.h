@@ -50,7 +50,8 @@ extern "C" {
  * conditional-variance selection of inducing points); hb_sgp_kgrad_f32 / _f64 and hb_sgp_kgrad_ws_elems (streamed part
  * of the gradient of the collapsed bound); hb_sgp_wstats_f32 / _f64, hb_sgp_wstats_ws_elems, hb_lik_sites_f32 / _f64,
  * hb_lik_sites_ws_elems, hb_lik_predict_f32 / _f64 and the enum values HB_LIK_* (natural-gradient fit of q(u) for
- * non-Gaussian likelihoods); hb_sgp_wkgrad_f32 / _f64 (streamed part of the gradient of the ELBO at a fixed q(u)). */
+ * non-Gaussian likelihoods); hb_sgp_wkgrad_f32 / _f64 (streamed part of the gradient of the ELBO at a fixed q(u));
+ * hb_sgp_pathwise_f32 / _f64 (pathwise posterior function draws, linear in n). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -668,6 +669,22 @@ int hb_lik_predict_f32(int lik, const float* mean, const float* var, double para
                        void* stream);
 int hb_lik_predict_f64(int lik, const double* mean, const double* var, double param, double* ymean, double* yvar, long N,
                        void* stream);
+/* Pathwise posterior function draws (csrc/sgp_pathwise.hip; not in the reference; Wilson et al. 2020).  S function draws,
+ * each a coefficient row coef[s] = [ w_s / sqrt(L) | v_s ] over 2L random Fourier features of the unit RBF kernel and the M
+ * canonical basis functions K(z_m, .), evaluated at n points:
+ *   out[s, j] = scale ( sum_{l<L} [ coef[s, 2l] cos(p_lj) + coef[s, 2l+1] sin(p_lj) ]
+ *                       + sum_{m<M} coef[s, 2L+m] exp(-1/2 sum_k ((z_mk - x_jk) / ell_k)^2) ),   p_lj = sum_k omega_lk x_jk / ell_k.
+ * x [n, d], omega [L, d], z [M, d], coef [S, 2L + M], out [S, n], row-major and contiguous; ell [dl], dl in {1, d}.  kind
+ * must be HB_KERN_RBF.  L >= 1, S >= 1, d >= 1; M = 0 is legal (the prior path alone; z may then be NULL); n = 0 returns
+ * without a launch; n, S (2L + M) and S n below 2^31.  No workspace: ONE launch, the basis is synthesised in LDS (one sincos
+ * per (l, j), phases reduced in double in revolutions: exact to the rounding of the result for |p| in the hundreds) and
+ * contracted on the 16 x 16 x 4 MFMA of the dtype, once for up to 64 draws.  The order of the sum over the 2L + M rows is
+ * fixed and the value of a column does not depend on the other columns of the call: two calls, or x evaluated in pieces,
+ * return the same bits.  Validated before any launch. */
+int hb_sgp_pathwise_f32(int kind, const float* x, const float* omega, const float* z, const float* ell, long dl,
+                        const float* coef, double scale, float* out, long n, long L, long M, long d, long S, void* stream);
+int hb_sgp_pathwise_f64(int kind, const double* x, const double* omega, const double* z, const double* ell, long dl,
+                        const double* coef, double scale, double* out, long n, long L, long M, long d, long S, void* stream);
 /* Greedy conditional-variance selection of M inducing points out of X [N, d] (csrc/sgp_select.hip; not in the reference;
  * Burt, Rasmussen, van der Wilk 2020): a pivoted incomplete Cholesky of K(X, X).  With dvar [N] = kdiag = 1 and the
  * history C [M, N], for j = 0 .. M - 1:
