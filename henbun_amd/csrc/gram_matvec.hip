@@ -1,0 +1,407 @@
+// Matrix-free kernel product (hb_gram_matvec_*) and the vector kernels of the lockstep preconditioned conjugate gradients
+// built on it (hb_pcg_*), include/henbun_hip.h; not in the reference; Gardner et al. 2018, Wang et al. 2019.
+//
+//     out[s, j] = scale * sum_{i < N} V[s, i] k(x2_i, x_j) + shift * V[s, j]
+//
+// K(x2, x) is never written to memory.  The kernel is the RBF section of sgp_pathwise_kernel -- a workgroup per strip of
+// GMV_CN columns (a wave per 32 of them) walks rows in K-steps of GMV_KT, each wave synthesises the GMV_KT x 32 block of
+// its own columns into LDS in the difference-then-scale exp2 form of sgp_strip.cuh, the workgroup stages the matching tile
+// of V through registers, and the product runs on the 16 x 16 x 4 MFMA of the dtype with the right-hand sides on the rows
+// -- with one change: the rows are cut into chunks of GMV_CHUNK and the grid is strips x chunks x tiles of GMV_SMAX
+// right-hand sides.  n = N = 8192 is then 256 workgroups instead of 64, and no accumulator of the storage type ever sums
+// more than GMV_CHUNK terms.  With more than one chunk a workgroup leaves its partial [S, strip] in the workspace and a
+// second launch adds the chunks in chunk order in double, applies scale and shift and writes out; with one chunk the same
+// finish runs in the kernel's epilogue and the workspace is not touched.  More than GMV_GROUP chunks are taken GMV_GROUP
+// at a time, the fold carrying its running double sum [S, n] from one group to the next: the same additions in the same
+// order, and a workspace of (GMV_GROUP sizeof(T) + 8) S n bytes whatever N.
+//
+// The order of every sum is fixed by N alone (K-steps inside a chunk, chunks in order): an output element does not
+// depend on the other columns, on S or on n, so two calls, or x evaluated in pieces, return the same bits.
+//
+// K(X, X) is symmetric and the symmetric call synthesises every value twice; halving that needs the transposed
+// accumulation of a block into other workgroups' columns ("Exact GP by conjugate gradients": the next step).
+#include "common.cuh"
+#include "mfma16.cuh"
+#include "sgp_strip.cuh"
+#include "../../include/henbun_hip.h"
+
+#define GMV_THREADS 256   // 4 waves, 32 columns each
+#define GMV_CN 128        // columns per workgroup
+#define GMV_KT 32         // rows per K-step
+#define GMV_SMAX 64       // right-hand sides per workgroup (4 row tiles of 16)
+#define GMV_CHUNK 2048    // rows per workgroup: fixed, whatever n, N and the device
+#define GMV_GROUP 16      // chunks per launch: bounds the workspace (fixed, like GMV_CHUNK)
+#define GMV_BLD 48        // row stride of a wave's K tile (sgp_pathwise.hip: PW_BLD)
+#define GMV_CLD (GMV_KT + 2)  // row stride of the V tile (PW_CLD)
+
+template <typename T>
+struct GmvArgs {
+  const T* x;     // [n, d]
+  const T* x2;    // [N, d]
+  const T* ell;   // [dl]
+  long dl;
+  const T* V;     // [S, N]
+  double scale, shift;
+  int shift_on;   // the symmetric form: shift * V[s, j] joins the finish
+  T* out;         // [S, n]
+  T* ws;          // [min(nchunk, GMV_GROUP), S, n] when nchunk > 1: the partials of the group in flight
+  double* acc;    // [S, n] when nchunk > GMV_GROUP: the fold's running sum between groups
+  int n, N, d, S, nstrip, nchunk;
+  int c0, gchunks;   // the group in flight: chunks c0 .. c0 + gchunks - 1
+};
+
+// scale * sum + shift * v, written so that the epilogue and the fold round alike
+template <typename T> __device__ __forceinline__ T gmv_finish(double scale, double shift, double sum, double v) {
+  return (T)fma(shift, v, scale * sum);
+}
+
+// D: the input dimension when it is at most 4 (the column's coordinates then live in registers), 0: any d, the
+// coordinates re-read from memory at every use.  NST: row tiles of 16 right-hand sides per workgroup.
+template <typename T, int D, int NST>
+__global__ void __launch_bounds__(GMV_THREADS) gram_matvec_kernel(GmvArgs<T> a) {
+  typedef PwMma<T> MM;
+  constexpr int SP = 16 * NST, DR = D ? D : 1;
+  __shared__ __attribute__((aligned(16))) T Bs[GMV_THREADS / 64][GMV_KT][GMV_BLD];
+  __shared__ __attribute__((aligned(16))) T Cs[SP][GMV_CLD];
+  const int n = a.n, N = a.N, S = a.S, d = D ? D : a.d;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c = lane & 31, h = lane >> 5;        // synthesis: column of the wave's tile, row parity
+  const int l16 = lane & 15, g = lane >> 4;      // MFMA operands
+  const int strip = blockIdx.x % a.nstrip, slot = blockIdx.x / a.nstrip, chunk = a.c0 + slot;
+  const int s0 = blockIdx.y * GMV_SMAX;
+  const long col0 = (long)strip * GMV_CN + 32 * w;   // long: n may end within 128 of 2^31
+  const int i0 = chunk * GMV_CHUNK, iend = N - i0 < GMV_CHUNK ? N : i0 + GMV_CHUNK;   // this workgroup's rows
+  const long jc = (col0 + c < n ? col0 + c : (long)n - 1) * d;   // columns past n: a copy of the last one (never written out)
+  const T* __restrict__ xj = a.x + jc;
+
+  T xs[DR], sc[DR];
+#pragma unroll
+  for (int k = 0; k < DR; ++k) {
+    if (D) {
+      xs[k] = xj[k];
+      sc[k] = T(SGP_EXP2_SCALE) / a.ell[a.dl == 1 ? 0 : k];
+    }
+  }
+  auto rbf = [&](const T* __restrict__ zm) {     // k(x2_i, x): the difference first, scaled afterwards (sgp_strip.cuh)
+    T r2 = T(0);
+    if (D) {
+#pragma unroll
+      for (int k = 0; k < DR; ++k) {
+        const T tt = (zm[k] - xs[k]) * sc[k];
+        r2 += tt * tt;
+      }
+    } else {
+      for (int k = 0; k < d; ++k) {
+        const T tt = (zm[k] - xj[k]) * (T(SGP_EXP2_SCALE) / a.ell[a.dl == 1 ? 0 : k]);
+        r2 += tt * tt;
+      }
+    }
+    return hb_exp2_neg<T>(r2);
+  };
+
+  // V tile of a K-step through registers: element e = tid + GMV_THREADS i is (right-hand side e / GMV_KT, row
+  // e % GMV_KT); rows past the chunk's end and right-hand sides past S are zeros
+  constexpr int CIT = SP * GMV_KT / GMV_THREADS;
+  T creg[CIT];
+  auto v_request = [&](int kb) {
+#pragma unroll
+    for (int i = 0; i < CIT; ++i) {
+      const int e = tid + GMV_THREADS * i, s = s0 + e / GMV_KT, k = e % GMV_KT;
+      const bool ok = s < S && k < iend - kb;
+      creg[i] = ok ? a.V[(long)s * N + kb + k] : T(0);
+    }
+  };
+  auto v_store = [&]() {
+#pragma unroll
+    for (int i = 0; i < CIT; ++i) {
+      const int e = tid + GMV_THREADS * i;
+      Cs[e / GMV_KT][e % GMV_KT] = creg[i];
+    }
+  };
+
+  typename MM::Acc acc[NST][2];
+#pragma unroll
+  for (int st = 0; st < NST; ++st)
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[st][ct][r] = T(0);
+
+  const int nK = (iend - i0 + GMV_KT - 1) / GMV_KT;
+  v_request(i0);
+#pragma nounroll
+  for (int t = 0; t < nK; ++t) {
+    const int kb = i0 + t * GMV_KT;
+    __syncthreads();   // the MFMAs of the step before have read both tiles
+    v_store();
+#pragma unroll
+    for (int i = 0; i < GMV_KT / 2; ++i) {
+      const int r = h + 2 * i;
+      const bool in = r < iend - kb;
+      const T v = rbf(a.x2 + (long)(in ? kb + r : iend - 1) * d);
+      Bs[w][r][c] = in ? v : T(0);
+    }
+    if (t + 1 < nK) v_request(kb + GMV_KT);   // the next step's V tile is in flight during the MFMAs
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < GMV_KT / 4; ++kk) {
+      const T b0 = Bs[w][4 * kk + g][l16], b1 = Bs[w][4 * kk + g][16 + l16];
+#pragma unroll
+      for (int st = 0; st < NST; ++st) {
+        const T av = Cs[16 * st + l16][4 * kk + g];
+        acc[st][0] = MM::mma(av, b0, acc[st][0]);
+        acc[st][1] = MM::mma(av, b1, acc[st][1]);
+      }
+    }
+  }
+
+  // masked store: register r of lane l is right-hand side s0 + 16 st + row(l, r), column col0 + 16 ct + l % 16
+#pragma unroll
+  for (int st = 0; st < NST; ++st)
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int s = s0 + 16 * st + MM::row(lane, r);
+        const long j = col0 + 16 * ct + l16;
+        if (s < S && j < n) {
+          if (a.nchunk == 1) {
+            const double v = a.shift_on ? (double)a.V[(long)s * N + j] : 0.0;
+            a.out[(long)s * n + j] = gmv_finish<T>(a.scale, a.shift, (double)acc[st][ct][r], v);
+          } else {
+            a.ws[((long)slot * S + s) * n + j] = acc[st][ct][r];
+          }
+        }
+      }
+}
+
+// out[s, j] = scale * (the chunks' partials added in chunk order, in double) + shift * V[s, j]; one call per group of
+// chunks, the running sum kept in a.acc from the first group to the last
+template <typename T>
+__global__ void __launch_bounds__(256) gram_matvec_fold_kernel(GmvArgs<T> a) {
+  const long total = (long)a.S * a.n;
+  const bool first = a.c0 == 0, last = a.c0 + a.gchunks == a.nchunk;
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    double sum = first ? 0.0 : a.acc[e];
+    for (int ch = 0; ch < a.gchunks; ++ch) sum += (double)a.ws[(long)ch * total + e];
+    if (last) {
+      const double v = a.shift_on ? (double)a.V[e] : 0.0;   // symmetric: N == n, V [S, n]
+      a.out[e] = gmv_finish<T>(a.scale, a.shift, sum, v);
+    } else {
+      a.acc[e] = sum;
+    }
+  }
+}
+
+template <typename T, int D>
+static void gram_matvec_launch_d(const GmvArgs<T>& a, int nst, dim3 grid, hipStream_t st) {
+  if (nst == 1)
+    hipLaunchKernelGGL((gram_matvec_kernel<T, D, 1>), grid, dim3(GMV_THREADS), 0, st, a);
+  else if (nst == 2)
+    hipLaunchKernelGGL((gram_matvec_kernel<T, D, 2>), grid, dim3(GMV_THREADS), 0, st, a);
+  else if (nst == 3)
+    hipLaunchKernelGGL((gram_matvec_kernel<T, D, 3>), grid, dim3(GMV_THREADS), 0, st, a);
+  else
+    hipLaunchKernelGGL((gram_matvec_kernel<T, D, 4>), grid, dim3(GMV_THREADS), 0, st, a);
+}
+
+extern "C" long hb_gram_matvec_chunk(void) { return GMV_CHUNK; }
+
+extern "C" long hb_gram_matvec_ws_elems(long n, long N, long S, int dtype_bytes) {
+  if (n <= 0 || N <= GMV_CHUNK || S <= 0) return 0;
+  const long nchunk = (N + GMV_CHUNK - 1) / GMV_CHUNK;
+  if (nchunk <= GMV_GROUP) return nchunk * S * n;
+  return GMV_GROUP * S * n + S * n * (8 / (dtype_bytes == 4 ? 4 : 8));   // the partials of a group + the double running sum
+}
+
+template <typename T>
+static int gram_matvec(int kind, const T* x, const T* x2, const T* ell, long dl, const T* V, double scale, double shift, T* out,
+                       long n, long N, long d, long S, T* ws, hipStream_t st) {
+  HB_REQUIRE(kind == HB_KERN_RBF, "hb_gram_matvec: the UnitRBF kernel only (kind=%d)", kind);
+  HB_REQUIRE(n >= 0 && N >= 0 && d >= 1 && S >= 1, "hb_gram_matvec: bad extents (n=%ld N=%ld d=%ld S=%ld)", n, N, d, S);
+  HB_REQUIRE(dl == 1 || dl == d, "hb_gram_matvec: lengthscales must have 1 or d entries");
+  HB_REQUIRE(x2 || N == n || N == 0, "hb_gram_matvec: x2 == NULL is the symmetric form, N must equal n (n=%ld N=%ld)", n, N);
+  HB_REQUIRE(!x2 || shift == 0.0, "hb_gram_matvec: shift != 0 is defined for the symmetric form (x2 == NULL) only");
+  HB_REQUIRE(ell && (n == 0 || (x && out)) && (V || N == 0), "hb_gram_matvec: NULL pointer");
+  const long nstrip = (n + GMV_CN - 1) / GMV_CN, nchunk = (N + GMV_CHUNK - 1) / GMV_CHUNK;
+  HB_REQUIRE(n <= 2147483647L && N <= 2147483647L && d <= 2147483647L && S <= 2147483647L &&
+                 nstrip * nchunk <= 2147483647L && hb_cdiv(S, GMV_SMAX) <= 65535,
+             "hb_gram_matvec: too large (n, N below 2^31, strips x chunks below 2^31, S at most 64 x 65535)");
+  HB_REQUIRE(ws || hb_gram_matvec_ws_elems(n, N, S, (int)sizeof(T)) == 0, "hb_gram_matvec: NULL workspace (hb_gram_matvec_ws_elems)");
+  if (n == 0) return 0;
+  if (N == 0) {
+    HB_HIP(hb_zero_async(out, (size_t)S * (size_t)n * sizeof(T), st));
+    return 0;
+  }
+  GmvArgs<T> a;
+  a.x = x; a.x2 = x2 ? x2 : x; a.ell = ell; a.dl = dl; a.V = V; a.scale = scale; a.shift = shift;
+  a.shift_on = x2 ? 0 : 1; a.out = out; a.ws = ws;
+  a.n = (int)n; a.N = (int)N; a.d = (int)d; a.S = (int)S; a.nstrip = (int)nstrip; a.nchunk = (int)nchunk;
+  a.acc = nchunk > GMV_GROUP ? reinterpret_cast<double*>(ws + (long)GMV_GROUP * S * n) : nullptr;
+  // every workgroup of the grid carries the same number of row tiles: those of min(S, GMV_SMAX) right-hand sides
+  const int nst = hb_cdiv(S < GMV_SMAX ? S : GMV_SMAX, 16);
+  for (long c0 = 0; c0 < nchunk; c0 += GMV_GROUP) {
+    a.c0 = (int)c0;
+    a.gchunks = (int)(nchunk - c0 < GMV_GROUP ? nchunk - c0 : GMV_GROUP);
+    const dim3 grid((unsigned)(nstrip * a.gchunks), (unsigned)hb_cdiv(S, GMV_SMAX), 1);
+    if (d == 1)
+      gram_matvec_launch_d<T, 1>(a, nst, grid, st);
+    else if (d == 2)
+      gram_matvec_launch_d<T, 2>(a, nst, grid, st);
+    else if (d == 3)
+      gram_matvec_launch_d<T, 3>(a, nst, grid, st);
+    else if (d == 4)
+      gram_matvec_launch_d<T, 4>(a, nst, grid, st);
+    else
+      gram_matvec_launch_d<T, 0>(a, nst, grid, st);
+    HB_LAUNCH_CHECK();
+    if (nchunk > 1) {
+      hipLaunchKernelGGL((gram_matvec_fold_kernel<T>), dim3(hb_stream_grid(S * n, 256)), dim3(256), 0, st, a);
+      HB_LAUNCH_CHECK();
+    }
+  }
+  return 0;
+}
+
+extern "C" int hb_gram_matvec_f32(int kind, const float* x, const float* x2, const float* ell, long dl, const float* V,
+                                  double scale, double shift, float* out, long n, long N, long d, long S, float* ws,
+                                  void* stream) {
+  return gram_matvec<float>(kind, x, x2, ell, dl, V, scale, shift, out, n, N, d, S, ws, (hipStream_t)stream);
+}
+extern "C" int hb_gram_matvec_f64(int kind, const double* x, const double* x2, const double* ell, long dl, const double* V,
+                                  double scale, double shift, double* out, long n, long N, long d, long S, double* ws,
+                                  void* stream) {
+  return gram_matvec<double>(kind, x, x2, ell, dl, V, scale, shift, out, n, N, d, S, ws, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Lockstep preconditioned conjugate gradients: S independent iterations over rows of length N, one workgroup per row.
+// Every dot product and every scalar (alpha, beta, |r|^2) is double whatever the storage type; a row's sums run in a
+// fixed order (a thread's stride, then a tree over the workgroup), so two solves return the same bits.  A row whose
+// |r|^2 has reached its threshold is skipped by both steps: its alpha is 0 and it stops moving.
+#define PCG_THREADS 1024
+
+__device__ __forceinline__ double pcg_block_sum(double v, double* red) {
+  const int tid = threadIdx.x;
+  __syncthreads();   // red may still be read from the sum before
+  red[tid] = v;
+  __syncthreads();
+#pragma unroll
+  for (int o = PCG_THREADS / 2; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// out[s] = sum_i a_si b_si
+template <typename T>
+__global__ void __launch_bounds__(PCG_THREADS) pcg_dot_kernel(const T* a, const T* b, double* out, long N) {
+  __shared__ double red[PCG_THREADS];
+  const long base = (long)blockIdx.x * N;
+  double acc = 0.0;
+  for (long i = threadIdx.x; i < N; i += PCG_THREADS) acc = fma((double)a[base + i], (double)b[base + i], acc);
+  const double tot = pcg_block_sum(acc, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = tot;
+}
+
+// alpha = rz / (p . Ap);  x += alpha p;  r -= alpha Ap;  rr = |r|^2
+template <typename T>
+__global__ void __launch_bounds__(PCG_THREADS) pcg_update_kernel(T* x, T* r, const T* p, const T* Ap, const double* rz, double* rr,
+                                                                 const double* thr, long N) {
+  __shared__ double red[PCG_THREADS];
+  const int s = blockIdx.x;
+  if (!(rr[s] > thr[s])) return;   // converged: alpha = 0
+  const long base = (long)s * N;
+  double acc = 0.0;
+  for (long i = threadIdx.x; i < N; i += PCG_THREADS) acc = fma((double)p[base + i], (double)Ap[base + i], acc);
+  const double pAp = pcg_block_sum(acc, red);
+  const double alpha = pAp > 0.0 ? rz[s] / pAp : 0.0;   // a direction of no curvature moves nothing
+  acc = 0.0;
+  for (long i = threadIdx.x; i < N; i += PCG_THREADS) {
+    const double rn = fma(-alpha, (double)Ap[base + i], (double)r[base + i]);
+    x[base + i] = (T)fma(alpha, (double)p[base + i], (double)x[base + i]);
+    const T rt = (T)rn;
+    r[base + i] = rt;
+    acc = fma((double)rt, (double)rt, acc);
+  }
+  const double tot = pcg_block_sum(acc, red);
+  if (threadIdx.x == 0) rr[s] = tot;
+}
+
+// z = (r - wscale w) zscale (w == NULL: z = r);  beta = (r . z) / rz (first: 0);  p = z + beta p;  rz = r . z
+template <typename T>
+__global__ void __launch_bounds__(PCG_THREADS) pcg_direction_kernel(const T* r, const T* w, T* p, double* rz, const double* rr,
+                                                                    const double* thr, double wscale, double zscale, int first,
+                                                                    long N) {
+  __shared__ double red[PCG_THREADS];
+  const int s = blockIdx.x;
+  if (!(rr[s] > thr[s])) return;
+  const long base = (long)s * N;
+  auto zval = [&](long i) {
+    const double rv = (double)r[base + i];
+    return w ? fma(-wscale, (double)w[base + i], rv) * zscale : rv;
+  };
+  double acc = 0.0;
+  for (long i = threadIdx.x; i < N; i += PCG_THREADS) acc = fma((double)r[base + i], zval(i), acc);
+  const double rzn = pcg_block_sum(acc, red);
+  const double rzo = rz[s];
+  const double beta = (first || !(rzo > 0.0)) ? 0.0 : rzn / rzo;
+  for (long i = threadIdx.x; i < N; i += PCG_THREADS) {
+    const double pv = first ? 0.0 : (double)p[base + i];
+    p[base + i] = (T)fma(beta, pv, zval(i));
+  }
+  __syncthreads();   // every thread has read rz[s]
+  if (threadIdx.x == 0) rz[s] = rzn;
+}
+
+template <typename T>
+static int pcg_dot(const T* a, const T* b, double* out, long S, long N, hipStream_t st) {
+  HB_REQUIRE(S >= 1 && S <= 2147483647L && N >= 0, "hb_pcg_dot: bad extents (S=%ld N=%ld)", S, N);
+  HB_REQUIRE(out && ((a && b) || N == 0), "hb_pcg_dot: NULL pointer");
+  hipLaunchKernelGGL((pcg_dot_kernel<T>), dim3((unsigned)S), dim3(PCG_THREADS), 0, st, a, b, out, N);
+  HB_LAUNCH_CHECK();
+  return 0;
+}
+template <typename T>
+static int pcg_update(T* x, T* r, const T* p, const T* Ap, const double* rz, double* rr, const double* thr, long S, long N,
+                      hipStream_t st) {
+  HB_REQUIRE(S >= 1 && S <= 2147483647L && N >= 1, "hb_pcg_update: bad extents (S=%ld N=%ld)", S, N);
+  HB_REQUIRE(x && r && p && Ap && rz && rr && thr, "hb_pcg_update: NULL pointer");
+  hipLaunchKernelGGL((pcg_update_kernel<T>), dim3((unsigned)S), dim3(PCG_THREADS), 0, st, x, r, p, Ap, rz, rr, thr, N);
+  HB_LAUNCH_CHECK();
+  return 0;
+}
+template <typename T>
+static int pcg_direction(const T* r, const T* w, T* p, double* rz, const double* rr, const double* thr, double wscale,
+                         double zscale, int first, long S, long N, hipStream_t st) {
+  HB_REQUIRE(S >= 1 && S <= 2147483647L && N >= 1, "hb_pcg_direction: bad extents (S=%ld N=%ld)", S, N);
+  HB_REQUIRE(r && p && rz && rr && thr, "hb_pcg_direction: NULL pointer");
+  hipLaunchKernelGGL((pcg_direction_kernel<T>), dim3((unsigned)S), dim3(PCG_THREADS), 0, st, r, w, p, rz, rr, thr, wscale, zscale,
+                     first, N);
+  HB_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int hb_pcg_dot_f32(const float* a, const float* b, double* out, long S, long N, void* stream) {
+  return pcg_dot<float>(a, b, out, S, N, (hipStream_t)stream);
+}
+extern "C" int hb_pcg_dot_f64(const double* a, const double* b, double* out, long S, long N, void* stream) {
+  return pcg_dot<double>(a, b, out, S, N, (hipStream_t)stream);
+}
+extern "C" int hb_pcg_update_f32(float* x, float* r, const float* p, const float* Ap, const double* rz, double* rr,
+                                 const double* thr, long S, long N, void* stream) {
+  return pcg_update<float>(x, r, p, Ap, rz, rr, thr, S, N, (hipStream_t)stream);
+}
+extern "C" int hb_pcg_update_f64(double* x, double* r, const double* p, const double* Ap, const double* rz, double* rr,
+                                 const double* thr, long S, long N, void* stream) {
+  return pcg_update<double>(x, r, p, Ap, rz, rr, thr, S, N, (hipStream_t)stream);
+}
+extern "C" int hb_pcg_direction_f32(const float* r, const float* w, float* p, double* rz, const double* rr, const double* thr,
+                                    double wscale, double zscale, int first, long S, long N, void* stream) {
+  return pcg_direction<float>(r, w, p, rz, rr, thr, wscale, zscale, first, S, N, (hipStream_t)stream);
+}
+extern "C" int hb_pcg_direction_f64(const double* r, const double* w, double* p, double* rz, const double* rr, const double* thr,
+                                    double wscale, double zscale, int first, long S, long N, void* stream) {
+  return pcg_direction<double>(r, w, p, rz, rr, thr, wscale, zscale, first, S, N, (hipStream_t)stream);
+}

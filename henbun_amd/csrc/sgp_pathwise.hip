@@ -24,6 +24,7 @@
 // on [-pi/4, pi/4] in double (6 + 6 terms for float, 9 + 10 for double: truncation below 1e-10 / 1e-18); the float kernel
 // rounds the finished value once.  DESIGN.md 3, "Pathwise function draws".
 #include "common.cuh"
+#include "mfma16.cuh"
 #include "sgp_strip.cuh"
 #include "../../include/henbun_hip.h"
 
@@ -33,20 +34,6 @@
 #define PW_SMAX 64       // draws per workgroup (4 row tiles of 16)
 #define PW_BLD 48        // row stride of a wave's basis tile: rows k, k + 1 of an operand read land on disjoint banks
 #define PW_CLD (PW_KT + 2)  // row stride of the coef tile: rows s, s + 1 two banks apart (four for double)
-
-// 16 x 16 x 4 MFMA of either dtype: lane l supplies A[row l % 16][k l / 16] and B[k l / 16][col l % 16]; accumulator
-// register r of lane l holds C[row(l, r)][col l % 16] (the two dtypes differ in the row map only).
-template <typename T> struct PwMma;
-template <> struct PwMma<float> {
-  typedef float Acc __attribute__((ext_vector_type(4)));
-  __device__ static __forceinline__ Acc mma(float a, float b, Acc c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-  __device__ static __forceinline__ int row(int lane, int r) { return 4 * (lane >> 4) + r; }
-};
-template <> struct PwMma<double> {
-  typedef double Acc __attribute__((ext_vector_type(4)));
-  __device__ static __forceinline__ Acc mma(double a, double b, Acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-  __device__ static __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }
-};
 
 // (sin, cos)(2 pi rev) in double.  rev - rint(rev) is exact; t = 4 frac in [-2, 2], q = rint(t) the quadrant,
 // r = (t - q) pi / 2 in [-pi/4, pi/4]; NS / NC Taylor terms of sin r / cos r.

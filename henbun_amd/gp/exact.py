@@ -1,0 +1,222 @@
+"""Exact GP regression by conjugate gradients (not in the reference; Gardner et al. 2018, Wang et al. 2019).
+
+K^ = k_var K(X, X) + noise_var I is never formed: every product K^ V is one hb_gram_matvec, which synthesises the kernel
+values in LDS and contracts them on the MFMA for up to 64 right-hand sides at a time.  Memory is O(N (S + R)) for S
+right-hand sides and a rank-R preconditioner -- five vectors [S, N], the factor [R, N] and the product's workspace, at
+most (16 sizeof(T) + 8) S N bytes (hb_gram_matvec_ws_elems); time is N^2 d kernel evaluations per iteration.  The vector
+updates, the dot products and every scalar of the iteration run in the library's own kernels (hb_pcg_*: the scalars in
+double); torch allocates, copies and converts dtypes, nothing else.
+
+Out of scope: the log marginal likelihood and its gradient (they need a stochastic log-determinant), kernels other than
+UnitRBF, non-Gaussian likelihoods.  Hyper-parameters come from SVGP.fit_hyper.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+
+class NotConverged(RuntimeError):
+    """pcg_solve did not reach its tolerance within max_iter; `info` is the dict a converged solve returns."""
+
+    def __init__(self, message, info):
+        RuntimeError.__init__(self, message)
+        self.info = info
+
+
+class Preconditioner:
+    """P = k_var C^T C + noise_var I with C [R, N] the pivoted incomplete Cholesky factor of K(X, X) that hb_sgp_select
+    leaves at the start of its workspace (threshold 0; R = the rows it produced, at most `rank`), in the dtype of X.
+    apply() forms w = C^T (noise_var I + k_var C C^T)^-1 C r, so that by Woodbury P^-1 r = (r - k_var w) / noise_var;
+    the R x R Cholesky and the two triangular products are float64, the two N-sized products run in the dtype of X."""
+
+    def __init__(self, sess, Xd, ell, k_var, noise_var, rank):
+        torch, H = sess.torch, sess.H
+        N, d = Xd.shape
+        self._H, self._torch = H, torch
+        self.k_var, self.noise_var = float(k_var), float(noise_var)
+        want = min(int(rank), N, 8192)
+        self.N, self.ld = N, (N + 63) // 64 * 64
+        self.C = torch.empty(H.sgp_select_ws_elems(Xd.dtype, N, want, d), dtype=Xd.dtype, device=Xd.device)
+        _, _, count, _ = H.sgp_select(Xd, ell, want, 0.0, ws=self.C)
+        self.rank = R = int(count.cpu()[0])       # the selection stops early when no conditional variance is left
+        G = H.matmul_ld(self.C, self.ld, self.C, self.ld, torch.empty((R, R), dtype=Xd.dtype, device=Xd.device), R, R, N,
+                        transB=True, alpha=self.k_var)
+        G = H.matutil(G.to(torch.float64), H.MATUTIL_ADD_EYE, alpha=self.noise_var)
+        L, info = H.cholesky(G)
+        if int(info.cpu()[0]) != 0:
+            raise RuntimeError("Preconditioner: noise_var I + k_var C C^T is not positive definite at rank %d" % R)
+        self.Linv = H.trinv(L)
+
+    def apply(self, r, out):
+        """out [S, N] = C^T (noise_var I + k_var C C^T)^-1 C r for the rows of r [S, N]."""
+        torch, H = self._torch, self._H
+        S, R, N = r.shape[0], self.rank, self.N
+        t = H.matmul_ld(r, N, self.C, self.ld, torch.empty((S, R), dtype=r.dtype, device=r.device), S, R, N, transB=True)
+        u = H.matmul(H.matmul(t.to(torch.float64), self.Linv, transB=True), self.Linv)
+        return H.matmul_ld(u.to(r.dtype).contiguous(), R, self.C, self.ld, out, S, N, R)
+
+
+def pcg_solve(sess, Xd, ell, k_var, noise_var, B, precond=None, tol=None, max_iter=1000):
+    """Solve (k_var K(X, X) + noise_var I) x_s = b_s for the S rows of B [S, N] by S preconditioned conjugate-gradient
+    iterations run in lockstep, each with its own alpha_s, beta_s: ONE hb_gram_matvec per iteration for all of them.
+    Xd [N, d], ell [1] or [d] and B are device tensors of one dtype.  precond: a Preconditioner of the same X and
+    hyper-parameters, or None for plain CG.  Stops when |r_s| <= tol |b_s| for every s (tol=None: 1e-6 in float64, 1e-3 in
+    float32); a row that has converged stops moving.  One host read-back per iteration (the S residual norms).  When the
+    recurrence reports convergence the residual b - K^ x is formed with one more product; should it be above the
+    tolerance (the recurrence drifts in float32) the iteration restarts from it.  Returns (x [S, N], info) with info =
+    dict(iterations, restarts, residual [S] = |b - K^ x| / |b| from that last product, converged, precond_rank):
+    `iterations` counts the products with a search direction, `restarts` the times the iteration was restarted (each
+    costs one product more, as does the final check); raises NotConverged, carrying the same info, after max_iter
+    iterations."""
+    torch, H = sess.torch, sess.H
+    S, N = B.shape
+    dt, dev = B.dtype, B.device
+    if tol is None:
+        tol = 1e-6 if dt == torch.float64 else 1e-3
+    tol, k_var, noise_var = float(tol), float(k_var), float(noise_var)
+    if not (tol > 0.0 and k_var > 0.0 and noise_var > 0.0):
+        raise ValueError("pcg_solve: tol, k_var and noise_var must be positive (got %r, %r, %r)" % (tol, k_var, noise_var))
+    if precond is not None and precond.rank == 0:
+        precond = None
+    new = lambda: torch.empty((S, N), dtype=dt, device=dev)
+    x, r, p, Ap = H.fill(new(), 0.0), H.ewise("COPY", [B]), new(), new()
+    w = new() if precond is not None else None
+    gws = torch.empty(max(H.gram_matvec_ws_elems(dt, N, N, S), 1), dtype=dt, device=dev)
+    product = lambda V: H.gram_matvec(Xd, None, ell, V, scale=k_var, shift=noise_var, out=Ap, ws=gws)
+
+    bb = H.pcg_dot(B, B)
+    rr, rz = H.ewise("COPY", [bb]), torch.empty_like(bb)
+    bb_h = bb.cpu().numpy()
+    thr_h = tol * tol * bb_h
+    thr = torch.as_tensor(thr_h).to(dev)
+
+    def direction(first):
+        if precond is not None:
+            precond.apply(r, w)
+        H.pcg_direction(r, w, p, rz, rr, thr, wscale=k_var, zscale=1.0 / noise_var if precond is not None else 1.0, first=first)
+
+    def true_residual():
+        product(x)
+        H.ewise("SUB", [B, Ap], out=r)
+        H.pcg_dot(r, r, out=rr)
+        return rr.cpu().numpy()
+
+    rr_h, it, restarts, converged = bb_h, 0, 0, False
+    direction(True)
+    while True:
+        if np.all(rr_h <= thr_h):
+            rr_h = true_residual()           # r and rr now hold the residual itself
+            if np.all(rr_h <= thr_h):
+                converged = True
+                break
+            if it >= max_iter:
+                break
+            direction(True)                  # the recurrence had drifted: restart from the residual
+            restarts += 1
+        elif it >= max_iter:
+            rr_h = true_residual()
+            break
+        product(p)
+        H.pcg_update(x, r, p, Ap, rz, rr, thr)
+        rr_h = rr.cpu().numpy()
+        it += 1
+        if not np.all(rr_h <= thr_h):
+            direction(False)
+    residual = np.sqrt(rr_h / np.where(bb_h > 0.0, bb_h, 1.0))
+    info = dict(iterations=it, restarts=restarts, residual=residual, converged=converged,
+                precond_rank=0 if precond is None else precond.rank)
+    if not converged:
+        raise NotConverged("pcg_solve: %d iterations did not reach |r| <= %g |b| (largest residual %g)"
+                           % (it, tol, float(residual.max())), info)
+    return x, info
+
+
+class ExactPosterior:
+    """The exact GP posterior given (X, Y) at fixed hyper-parameters (GP.condition): a snapshot, like PathwiseDraws, of X
+    [N, d], the lengthscales, k_var, noise_var, alpha = K^^-1 Y [P, N], the preconditioner and the solve's `info`, on the
+    device in the session's dtype.  Later changes to the model do not move it."""
+
+    def __init__(self, sess, device_data, X, Y, ell, k_var, noise_var, alpha, precond, info, tol, max_iter):
+        self._sess, self._device_data = sess, device_data
+        self._X, self._Y, self._ell, self._alpha, self._precond = X, Y, ell, alpha, precond
+        self.k_var, self.noise_var, self.info = float(k_var), float(noise_var), info
+        self.tol, self.max_iter = tol, int(max_iter)
+
+    alpha = property(lambda self: self._alpha.cpu().numpy(), doc="K^^-1 Y as numpy [P, N]")
+
+    def _solve(self, B):
+        return pcg_solve(self._sess, self._X, self._ell, self.k_var, self.noise_var, B, self._precond, self.tol, self.max_iter)
+
+    def _new_points(self, Xnew):
+        Xn = self._device_data(self._sess, Xnew, "Xnew")
+        if Xn.shape[1] != self._X.shape[1]:
+            raise ValueError("ExactPosterior: Xnew %s does not match X %s" % (tuple(Xn.shape), tuple(self._X.shape)))
+        return Xn
+
+    def predict_f(self, Xnew, var=True):
+        """(mean [P, n], var [n]) of the latent f at the rows of Xnew, as numpy.  The mean is ONE hb_gram_matvec,
+        k_var alpha K(X, Xnew).  var = k_var - k*^T K^^-1 k* costs ONE LOCKSTEP SOLVE PER 64 TEST POINTS, each as expensive
+        as the conditioning itself (right-hand sides k_var K(X, Xnew_block) from hb_gram_fwd); var=False skips it and
+        returns (mean, None)."""
+        torch, H = self._sess.torch, self._sess.H
+        Xn = self._new_points(Xnew)
+        n = Xn.shape[0]
+        mean = H.gram_matvec(Xn, self._X, self._ell, self._alpha, scale=self.k_var).cpu().numpy()
+        if not var:
+            return mean, None
+        out = np.empty(n, dtype=mean.dtype)
+        for a in range(0, n, 64):
+            blk = Xn[a:a + 64].contiguous()
+            rhs = H.ewise("AFFINE", [H.gram_fwd(blk, self._X, self._ell)], params=(self.k_var, 0.0))   # [nb, N]
+            sol, _ = self._solve(rhs)
+            q = H.ewise("AFFINE", [H.pcg_dot(rhs, sol)], params=(-1.0, self.k_var))                    # float64 [nb]
+            out[a:a + 64] = q.cpu().numpy()
+        return mean, out
+
+    def predict_y(self, Xnew, var=True):
+        """predict_f plus the noise variance: the predictive of a new observation."""
+        mean, v = self.predict_f(Xnew, var=var)
+        return mean, None if v is None else v + np.asarray(self.noise_var, dtype=v.dtype)
+
+    def sample_functions(self, num_samples, num_features=1024, seed=0, noise=None):
+        """num_samples posterior FUNCTION draws as a PathwiseDraws with z = X, M = N (pathwise conditioning on the data
+        themselves, Wilson et al. 2021).  With L = num_features, omega_l ~ N(0, I_d), w_s ~ N(0, I_2L), eps_s ~ N(0, I_N):
+            g_s(x) = L^-1/2 sum_l [ w_s,2l cos(omega_l . x~) + w_s,2l+1 sin(omega_l . x~) ]       (prior path, unit RBF)
+            v_s = sqrt(k_var) K^^-1 (y - sqrt(k_var) g_s(X) - sqrt(noise_var) eps_s)
+            f_s(x) = sqrt(k_var) ( g_s(x) + v_s K(X, x) ),
+        i.e. coefficient rows [w_s / sqrt(L) | v_s] under scale = sqrt(k_var), the conventions of SparseGP.pathwise_draws.
+        g_s(X) is hb_sgp_pathwise with M = 0; the v_s come from lockstep solves in blocks of 64 draws; evaluation is the
+        unchanged hb_sgp_pathwise, O((N + L) n) per draw.  noise=None draws omega [L, d], w [S, 2L], eps [S, N] from
+        hip_ops.Rng(seed), in that order; noise=dict(omega=, w=, eps=) injects them.  One output column (P = 1) only."""
+        from .gp import PathwiseDraws
+
+        sess = self._sess
+        torch, H = sess.torch, sess.H
+        S, L = int(num_samples), int(num_features)
+        if not (S >= 1 and L >= 1):
+            raise ValueError("sample_functions: num_samples >= 1 and num_features >= 1 expected (got %r, %r)"
+                             % (num_samples, num_features))
+        if self._Y.shape[0] != 1:
+            raise NotImplementedError("sample_functions: one latent function only (Y has %d columns)" % self._Y.shape[0])
+        N, d = self._X.shape
+        dt = sess.torch_dtype
+        if noise is None:
+            rng = H.Rng(seed, device=sess.device)
+            omega, w, eps = (rng.normal(shape, dtype=dt) for shape in ((L, d), (S, 2 * L), (S, N)))
+        else:
+            want = dict(omega=(L, d), w=(S, 2 * L), eps=(S, N))
+            if not isinstance(noise, dict) or set(noise) != set(want) or any(np.shape(noise[k]) != want[k] for k in want):
+                raise ValueError("sample_functions: noise must be dict(omega=%s, w=%s, eps=%s)"
+                                 % (want["omega"], want["w"], want["eps"]))
+            up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=sess.np_dtype)).to(sess.device)
+            omega, w, eps = (up(noise[k]) for k in ("omega", "w", "eps"))
+        cw = H.ewise("AFFINE", [w], params=(1.0 / np.sqrt(L), 0.0))
+        sk = float(np.sqrt(self.k_var))
+        prior = H.sgp_pathwise(self._X, omega, None, self._ell, cw, scale=sk)                           # [S, N]
+        rhs = H.ewise("SUB", [H.ewise("SUB", [self._Y, prior]), H.ewise("AFFINE", [eps], params=(np.sqrt(self.noise_var), 0.0))])
+        V = torch.empty((S, N), dtype=dt, device=sess.device)
+        for a in range(0, S, 64):
+            sol, _ = self._solve(rhs[a:a + 64].contiguous())
+            H.ewise("AFFINE", [sol], params=(sk, 0.0), out=V[a:a + 64])
+        coef = torch.cat([cw, V], dim=1).contiguous()
+        return PathwiseDraws(sess, self._device_data, omega, coef, self._X, self._ell, sk)

@@ -30,6 +30,53 @@ class GP(Parameterized):
         L = self._kern().Cholesky(x)
         return G.matmul(u, L, transpose_b=True)
 
+    # -- exact regression at scale: conjugate gradients on a matrix-free kernel product (gp/exact.py) ----------------
+    def condition(self, X, Y, noise_var, k_var=1.0, precond_rank=64, tol=None, max_iter=1000):
+        """The EXACT posterior of f ~ GP(0, k_var k) given Y = f(X) + N(0, noise_var) at the current lengthscales, as an
+        hb.gp.ExactPosterior: alpha = (k_var K(X, X) + noise_var I)^-1 Y from preconditioned conjugate gradients on the
+        matrix-free product hb_gram_matvec -- O(N (P + precond_rank)) memory, N^2 d kernel evaluations per iteration, so
+        N is limited by time, not by the [N, N] matrix DenseGPR factors.  X [N, d], Y [N, P] with P <= 64 (the columns are
+        solved in lockstep): Data / MinibatchData of the model, device tensors or arrays.  precond_rank: rank of the
+        pivoted incomplete Cholesky preconditioner (hb_sgp_select on X at threshold 0; 0: plain CG); 64 is a default, not
+        a measurement -- profiles/exact_gp_bench.txt records iterations against rank.  tol: |r| <= tol |y| per column on
+        the residual itself; None means 1e-6 in a float64 session and 1e-3 in a float32 one.  A float32 session has a
+        floor: on 600 points with cond(K^) = 4e3 the smallest tolerance it reached was 3e-5 (50 iterations at rank 64; at
+        1e-5 the residual stalls near 3e-5 -- profiles/exact_gp_bench.txt), and the floor rises with the conditioning.
+        Not reaching the tolerance within max_iter iterations raises hb.gp.NotConverged, which carries the solve's info.
+        UnitRBF with the lengthscales one Variable [dl] only, as SparseGP.statistics: anything else raises
+        NotImplementedError.  The log marginal likelihood and its gradient are out of scope: hyper-parameters come from
+        SVGP.fit_hyper."""
+        from . import exact
+
+        root = self.highest_parent
+        sess = getattr(root, "_session", None)
+        if sess is None:
+            raise ValueError("condition needs the GP to be part of a Model")
+        kern = self._kern()
+        if not isinstance(kern, UnitRBF):
+            raise NotImplementedError("condition: exact regression is implemented for the UnitRBF kernel only (got %s)"
+                                      % type(kern).__name__)
+        ls = object.__getattribute__(kern, "lengthscales")
+        if not isinstance(ls, Variable) or len(ls.shape) != 1:
+            raise NotImplementedError("condition: one expert only, the lengthscales must be one Variable [dl]")
+        root.initialize()
+        Xd, Yd = _device_data(sess, X, "X"), _device_data(sess, Y, "Y")
+        N, d = Xd.shape
+        if Yd.shape[0] != N or N < 1:
+            raise ValueError("condition: X %s and Y %s do not match" % (tuple(Xd.shape), tuple(Yd.shape)))
+        if Yd.shape[1] > 64:
+            raise NotImplementedError("condition: at most 64 output columns are solved in lockstep (Y has %d)" % Yd.shape[1])
+        if int(ls.shape[0]) not in (1, d):
+            raise ValueError("condition: %d lengthscales for X %s" % (int(ls.shape[0]), tuple(Xd.shape)))
+        torch = sess.torch
+        ell = torch.as_tensor(np.ascontiguousarray(np.reshape(sess.read_value(ls), [-1]).astype(sess.np_dtype))).to(sess.device)
+        if tol is None:
+            tol = 1e-6 if sess.torch_dtype == torch.float64 else 1e-3
+        precond = exact.Preconditioner(sess, Xd, ell, k_var, noise_var, precond_rank) if int(precond_rank) > 0 else None
+        Yt = Yd.t().contiguous()
+        alpha, info = exact.pcg_solve(sess, Xd, ell, k_var, noise_var, Yt, precond, tol, max_iter)
+        return exact.ExactPosterior(sess, _device_data, Xd, Yt, ell, k_var, noise_var, alpha, precond, info, tol, max_iter)
+
 
 class SparseGP(GP):
     def __init__(self, kern, z, collections=[graph_key.VARIABLES]):
@@ -160,20 +207,7 @@ class SparseGP(GP):
         return sess, zvar, ls
 
     def _device_data(self, sess, a, name):
-        """X / Y as a contiguous [N, k] device tensor of the session's dtype: a Data / MinibatchData of the model is read
-        from its device-resident buffer (all rows), a device tensor is taken as it is, anything else is uploaded."""
-        from ..param import Data
-
-        torch = sess.torch
-        if isinstance(a, Data):
-            t = sess.data_buffer(a)
-        elif isinstance(a, torch.Tensor):
-            t = a.to(device=sess.device, dtype=sess.torch_dtype)
-        else:
-            t = torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=sess.np_dtype))).to(sess.device)
-        if t.dim() != 2:
-            raise ValueError("%s must be 2-D [N, k], got %s" % (name, tuple(t.shape)))
-        return t.contiguous()
+        return _device_data(sess, a, name)
 
     def statistics(self, X, Y):
         """(Phi [M, M], b [P, M], yy [P], a2sum [1]) of the whole data set X [N, d], Y [N, P] for the current z,
@@ -781,6 +815,23 @@ class PathwiseDraws:
     coef = property(lambda self: self._view(self._coef), doc="coefficient rows [S, 2L + M] = [w / sqrt(L) | v]")
     z = property(lambda self: self._view(self._z), doc="inducing points [M, d]")
     lengthscales = property(lambda self: self._view(self._ell), doc="lengthscales [1] or [d]")
+
+
+def _device_data(sess, a, name):
+    """X / Y as a contiguous [N, k] device tensor of the session's dtype: a Data / MinibatchData of the model is read
+    from its device-resident buffer (all rows), a device tensor is taken as it is, anything else is uploaded."""
+    from ..param import Data
+
+    torch = sess.torch
+    if isinstance(a, Data):
+        t = sess.data_buffer(a)
+    elif isinstance(a, torch.Tensor):
+        t = a.to(device=sess.device, dtype=sess.torch_dtype)
+    else:
+        t = torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=sess.np_dtype))).to(sess.device)
+    if t.dim() != 2:
+        raise ValueError("%s must be 2-D [N, k], got %s" % (name, tuple(t.shape)))
+    return t.contiguous()
 
 
 def _posterior_of(q):

@@ -700,6 +700,21 @@ def matmul(A, B, transA=False, transB=False, alpha=1.0, bias=None, act="none", l
     return out
 
 
+def matmul_ld(A, lda, B, ldb, out, m, n, k, transB=False, alpha=1.0):
+    """out [m, n] (contiguous) = alpha op(A) op(B) with explicit row strides: A [m, k] at stride lda, B [k, n] (transB:
+    [n, k]) at stride ldb -- operands that are the leading rows of a wider buffer, such as the history of sgp_select."""
+    if A.dtype != B.dtype or out.dtype != A.dtype or out.numel() < m * n or not out.is_contiguous():
+        raise ValueError("matmul_ld: one dtype and a contiguous out of m n elements expected")
+    need_a = (m - 1) * lda + k
+    need_b = ((n - 1) * ldb + k) if transB else ((k - 1) * ldb + n)
+    if lda < k or ldb < (k if transB else n) or A.numel() < need_a or B.numel() < need_b:
+        raise ValueError("matmul_ld: operands shorter than their extents and strides")
+    ws = workspace(A.dtype, A.device, 1 << 22)
+    _lib.lib().call("hb_matmul" + _suf(A), _p(A), _p(B), _p(out), 1, m, n, k, lda, ldb, n, 0, 0, 0, 0, int(transB),
+                    float(alpha), 0.0, None, 0, ACT["none"], 0, _p(ws), ws.numel(), stream())
+    return out
+
+
 def matmul_colsum(A, B, out=None, colsum=None):
     """(A^T B, column sums of B) for A [K, M], B [K, N]: the weight and bias gradients of a MatBias layer from one pass over
     the incoming gradient (hb_matmul_colsum)."""
@@ -1183,6 +1198,91 @@ def sgp_pathwise(x, omega, z, ell, coef, scale=1.0, out=None):
     _lib.lib().call("hb_sgp_pathwise" + _suf(x), KERN_RBF, _p(x), _p(omega), _p(z if M else None), _p(ell), ell.numel(), _p(coef),
                     float(scale), _p(out), n, L, M, d, S, stream())
     return out
+
+
+def gram_matvec_chunk():
+    """Rows per workgroup of hb_gram_matvec: a compile-time constant of the library."""
+    return int(_lib.lib().raw("hb_gram_matvec_chunk")())
+
+
+def gram_matvec_ws_elems(dtype, n, N, S):
+    """Scratch elements hb_gram_matvec needs: 0 when N fits one chunk, chunks x S x n up to 16 chunks, beyond that 16 S n
+    plus S n doubles -- O(S n) whatever N."""
+    return int(_lib.lib().raw("hb_gram_matvec_ws_elems")(int(n), int(N), int(S), 4 if dtype == torch.float32 else 8))
+
+
+def gram_matvec(x, x2, ell, V, scale=1.0, shift=0.0, out=None, ws=None, kind=KERN_RBF):
+    """Matrix-free kernel product (hb_gram_matvec): out [S, n] = scale V [S, N] K(x2, x) + shift V with K never written.
+    x [n, d], x2 [N, d] or None (the symmetric form x2 = x; only then may shift be non-zero), ell [1] or [d], V [S, N], all
+    of one dtype.  The value of an output element depends neither on the other columns nor on the other rows of V: two
+    calls, x in pieces, or a subset of the rows return the same bits.  `ws`: gram_matvec_ws_elems elements (default: the
+    shared scratch of the stream)."""
+    for t in (x, ell, V) + (() if x2 is None else (x2,)):
+        _chk(t)
+    if x.dim() != 2 or V.dim() != 2 or ell.dim() != 1 or (x2 is not None and (x2.dim() != 2 or x2.shape[1] != x.shape[1])):
+        raise ValueError("gram_matvec: x [n, d], x2 [N, d] or None, ell [1] or [d], V [S, N] expected, got %s %s %s %s"
+                         % (tuple(x.shape), None if x2 is None else tuple(x2.shape), tuple(ell.shape), tuple(V.shape)))
+    n, d = x.shape
+    N = n if x2 is None else x2.shape[0]
+    S = V.shape[0]
+    if V.shape[1] != N:
+        raise ValueError("gram_matvec: V must hold N = %d columns, got %s" % (N, tuple(V.shape)))
+    if any(t.dtype != x.dtype for t in (ell, V)) or (x2 is not None and x2.dtype != x.dtype):
+        raise TypeError("gram_matvec: all operands must share one dtype")
+    if out is None:
+        out = _empty((S, n), dtype=x.dtype, device=x.device)
+    else:
+        _chk(out)
+        if tuple(out.shape) != (S, n) or out.dtype != x.dtype:
+            raise ValueError("gram_matvec: out must be [%d, %d] of the operands' dtype" % (S, n))
+    need = gram_matvec_ws_elems(x.dtype, n, N, S)
+    if ws is None:
+        ws = workspace(x.dtype, x.device, max(need, 1))
+    if ws.dtype != x.dtype or ws.numel() < need:
+        raise ValueError("gram_matvec: the workspace must hold %d elements of %s (gram_matvec_ws_elems)" % (need, x.dtype))
+    _lib.lib().call("hb_gram_matvec" + _suf(x), int(kind), _p(x), _p(x2), _p(ell), ell.numel(), _p(V), float(scale),
+                    float(shift), _p(out), n, N, d, S, _p(ws), stream())
+    return out
+
+
+def pcg_dot(a, b, out=None):
+    """out [S] float64 = sum_i a_si b_si (hb_pcg_dot), a, b [S, N]."""
+    _chk(a), _chk(b)
+    if a.dim() != 2 or a.shape != b.shape or a.dtype != b.dtype:
+        raise ValueError("pcg_dot: a, b [S, N] of one dtype expected, got %s %s" % (tuple(a.shape), tuple(b.shape)))
+    if out is None:
+        out = _empty((a.shape[0],), dtype=torch.float64, device=a.device)
+    _lib.lib().call("hb_pcg_dot" + _suf(a), _p(a), _p(b), _p(out), a.shape[0], a.shape[1], stream())
+    return out
+
+
+def _pcg_check(who, mats, vecs):
+    S, N = mats[0].shape
+    for t in mats:
+        if t is not None:
+            _chk(t)
+            if tuple(t.shape) != (S, N) or t.dtype != mats[0].dtype:
+                raise ValueError("%s: the vectors must be [%d, %d] of one dtype" % (who, S, N))
+    for t in vecs:
+        _chk(t)
+        if t.numel() != S or t.dtype != torch.float64:
+            raise ValueError("%s: the scalars must be float64 [%d]" % (who, S))
+    return S, N
+
+
+def pcg_update(x, r, p, Ap, rz, rr, thr):
+    """One lockstep CG update in place (hb_pcg_update): alpha = rz / (p . Ap), x += alpha p, r -= alpha Ap, rr = |r|^2 for
+    every row with rr > thr; x, r, p, Ap [S, N], rz, rr, thr float64 [S]."""
+    S, N = _pcg_check("pcg_update", (x, r, p, Ap), (rz, rr, thr))
+    _lib.lib().call("hb_pcg_update" + _suf(x), _p(x), _p(r), _p(p), _p(Ap), _p(rz), _p(rr), _p(thr), S, N, stream())
+
+
+def pcg_direction(r, w, p, rz, rr, thr, wscale=1.0, zscale=1.0, first=False):
+    """The next search directions in place (hb_pcg_direction): z = (r - wscale w) zscale (w None: z = r), beta = (r . z) /
+    rz (first: 0), p = z + beta p, rz = r . z for every row with rr > thr."""
+    S, N = _pcg_check("pcg_direction", (r, w, p), (rz, rr, thr))
+    _lib.lib().call("hb_pcg_direction" + _suf(r), _p(r), _p(w), _p(p), _p(rz), _p(rr), _p(thr), float(wscale), float(zscale),
+                    int(bool(first)), S, N, stream())
 
 
 LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON = 0, 1, 2

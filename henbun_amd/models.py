@@ -353,6 +353,50 @@ class DenseGPR(hb.model.Model):
         return tf.reduce_sum(hb.densities.gaussian(self.Y, f, self.var)) - self.KL()
 
 
+class ExactGPR(hb.model.Model):
+    """Exact GP regression at scale: kern, k_var and var as in SVGP, the posterior from conjugate gradients on the
+    matrix-free kernel product (GP.condition) instead of an [N, N] factorisation.  There is no objective to optimise here
+    (the log marginal likelihood is out of scope): set lengthscales, k_var and var -- from SVGP.fit_hyper, say -- then
+        m.fit();  mean, var = m.predict_y(Xnew);  draws = m.sample_functions(16)
+    Predictions are in data units: mean [P, n] and var [n] of f ~ GP(0, k_var k) given Y = f(X) + N(0, var)."""
+
+    def setUp(self, X, Y):
+        self.X = hb.param.Data(X)
+        self.Y = hb.param.Data(Y)
+        self.gp = hb.gp.GP(kern=hb.gp.kernels.UnitRBF(np.ones(1)))
+        self.k_var = hb.param.Variable([1], transform=hb.transforms.positive)
+        self.var = hb.param.Variable([1], transform=hb.transforms.positive)
+        self.posterior = None
+
+    def fit(self, precond_rank=64, tol=None, max_iter=1000):
+        """Condition on the model's X, Y at the CURRENT lengthscales, k_var and var and keep the hb.gp.ExactPosterior
+        (also returned as self.posterior); hyper-parameters changed afterwards need another fit().  Returns self."""
+        self.initialize()
+        g = lambda k: object.__getattribute__(self, k)
+        self.posterior = g("gp").condition(g("X"), g("Y"), float(np.ravel(g("var").value)[0]),
+                                           k_var=float(np.ravel(g("k_var").value)[0]), precond_rank=precond_rank, tol=tol,
+                                           max_iter=max_iter)
+        return self
+
+    def _posterior(self):
+        post = object.__getattribute__(self, "posterior")
+        if post is None:
+            raise ValueError("ExactGPR: call fit() first")
+        return post
+
+    def predict_f(self, Xnew, var=True):
+        """(mean [P, n], var [n]) of the latent f at Xnew; the variance costs one solve per 64 points (var=False skips it)."""
+        return self._posterior().predict_f(Xnew, var=var)
+
+    def predict_y(self, Xnew, var=True):
+        """predict_f plus the likelihood's variance."""
+        return self._posterior().predict_y(Xnew, var=var)
+
+    def sample_functions(self, num_samples, num_features=1024, seed=0, noise=None):
+        """num_samples exact posterior function draws as an hb.gp.PathwiseDraws (ExactPosterior.sample_functions)."""
+        return self._posterior().sample_functions(num_samples, num_features=num_features, seed=seed, noise=noise)
+
+
 def svgp_data(N, M, seed=0, domain=None, dtype=np.float64):
     """Synthetic regression set of the BASELINE configs: X ~ U(0, domain),
     Y = sin X + 0.3 eps, Z = linspace(0, domain, M) (spacing 0.5 lengthscales)."""

@@ -51,7 +51,8 @@ extern "C" {
  * of the gradient of the collapsed bound); hb_sgp_wstats_f32 / _f64, hb_sgp_wstats_ws_elems, hb_lik_sites_f32 / _f64,
  * hb_lik_sites_ws_elems, hb_lik_predict_f32 / _f64 and the enum values HB_LIK_* (natural-gradient fit of q(u) for
  * non-Gaussian likelihoods); hb_sgp_wkgrad_f32 / _f64 (streamed part of the gradient of the ELBO at a fixed q(u));
- * hb_sgp_pathwise_f32 / _f64 (pathwise posterior function draws, linear in n). */
+ * hb_sgp_pathwise_f32 / _f64 (pathwise posterior function draws, linear in n); hb_gram_matvec_f32 / _f64 and hb_pcg_*
+ * (matrix-free kernel product and the vector steps of lockstep preconditioned conjugate gradients: exact GP regression). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -685,6 +686,48 @@ int hb_sgp_pathwise_f32(int kind, const float* x, const float* omega, const floa
                         const float* coef, double scale, float* out, long n, long L, long M, long d, long S, void* stream);
 int hb_sgp_pathwise_f64(int kind, const double* x, const double* omega, const double* z, const double* ell, long dl,
                         const double* coef, double scale, double* out, long n, long L, long M, long d, long S, void* stream);
+/* Matrix-free kernel product (csrc/gram_matvec.hip; not in the reference; Gardner et al. 2018, Wang et al. 2019):
+ *   out[s, j] = scale * sum_{i<N} V[s, i] k(x2_i, x_j) + shift * V[s, j],     s < S, j < n,
+ * the product a conjugate-gradient solve with K(X, X) + sigma^2 I asks for, and the exact posterior mean at new points.
+ * x [n, d], x2 [N, d], V [S, N], out [S, n], row-major and contiguous; ell [dl], dl in {1, d}; kind must be HB_KERN_RBF.
+ * x2 == NULL is the symmetric form x2 = x (N must equal n); only then may shift be non-zero.  S >= 1, d >= 1; n = 0 or
+ * N = 0 returns without a kernel launch (N = 0: out is zero-filled).  k is the difference-then-scale exp2 form of the strip
+ * kernels (csrc/sgp_strip.cuh) and is never written to memory.  The rows i are cut into chunks of hb_gram_matvec_chunk()
+ * (a compile-time constant: it depends on nothing); the grid is column strips x row chunks x tiles of 64 right-hand
+ * sides, each workgroup contracts its block on the 16 x 16 x 4 MFMA of the dtype, and with more than one chunk a second
+ * launch adds the chunks' partials in chunk order IN DOUBLE (both dtypes), applies scale and shift and writes out; one
+ * chunk: the same finish in the first launch's epilogue, the workspace untouched.  No atomics.  The order of every sum is
+ * fixed by N alone: an output element depends neither on the other columns nor on S nor on n -- two calls, x evaluated in
+ * pieces, or a subset of the right-hand sides return the same bits.  n, N up to 2^31 - 1 (strips of 128 x chunks below
+ * 2^31); S N and S n are indexed in long.  More than 16 chunks are launched 16 at a time, the fold carrying its running
+ * double sum between the groups (the same additions in the same order), so the workspace is O(S n) whatever N:
+ * ws >= hb_gram_matvec_ws_elems(n, N, S, sizeof(T)) elements of T, 16-byte aligned -- 0 for one chunk (NULL allowed),
+ * chunks x S x n up to 16 chunks, beyond that 16 S n plus S n doubles.  Validated before any launch. */
+long hb_gram_matvec_chunk(void);
+long hb_gram_matvec_ws_elems(long n, long N, long S, int dtype_bytes);
+int hb_gram_matvec_f32(int kind, const float* x, const float* x2, const float* ell, long dl, const float* V, double scale,
+                       double shift, float* out, long n, long N, long d, long S, float* ws, void* stream);
+int hb_gram_matvec_f64(int kind, const double* x, const double* x2, const double* ell, long dl, const double* V, double scale,
+                       double shift, double* out, long n, long N, long d, long S, double* ws, void* stream);
+/* Vector steps of S preconditioned conjugate-gradient iterations run in lockstep on rows of length N (csrc/gram_matvec.hip;
+ * henbun_amd/gp/exact.py).  x, r, p, Ap, w [S, N] in the storage type; rz, rr, thr, out [S] DOUBLE: every dot product and
+ * scalar is double.  One workgroup per row, sums in a fixed order: two solves return the same bits.  A row with
+ * rr[s] <= thr[s] has converged and is left untouched by update and direction (its alpha is 0).
+ *   hb_pcg_dot:        out[s] = sum_i a_si b_si;
+ *   hb_pcg_update:     alpha_s = rz_s / (p_s . Ap_s) (0 when the curvature is not positive);  x_s += alpha_s p_s;
+ *                      r_s -= alpha_s Ap_s;  rr_s = |r_s|^2;
+ *   hb_pcg_direction:  z_s = (r_s - wscale w_s) zscale (w == NULL: z_s = r_s);  beta_s = (r_s . z_s) / rz_s (first != 0:
+ *                      0, p is not read);  p_s = z_s + beta_s p_s;  rz_s = r_s . z_s. */
+int hb_pcg_dot_f32(const float* a, const float* b, double* out, long S, long N, void* stream);
+int hb_pcg_dot_f64(const double* a, const double* b, double* out, long S, long N, void* stream);
+int hb_pcg_update_f32(float* x, float* r, const float* p, const float* Ap, const double* rz, double* rr, const double* thr,
+                      long S, long N, void* stream);
+int hb_pcg_update_f64(double* x, double* r, const double* p, const double* Ap, const double* rz, double* rr, const double* thr,
+                      long S, long N, void* stream);
+int hb_pcg_direction_f32(const float* r, const float* w, float* p, double* rz, const double* rr, const double* thr,
+                         double wscale, double zscale, int first, long S, long N, void* stream);
+int hb_pcg_direction_f64(const double* r, const double* w, double* p, double* rz, const double* rr, const double* thr,
+                         double wscale, double zscale, int first, long S, long N, void* stream);
 /* Greedy conditional-variance selection of M inducing points out of X [N, d] (csrc/sgp_select.hip; not in the reference;
  * Burt, Rasmussen, van der Wilk 2020): a pivoted incomplete Cholesky of K(X, X).  With dvar [N] = kdiag = 1 and the
  * history C [M, N], for j = 0 .. M - 1:
@@ -699,7 +742,10 @@ int hb_sgp_pathwise_f64(int kind, const double* x, const double* omega, const do
  * runs the same code in double.  M + 1 launches, one per chosen point plus a fold, no host synchronisation, no atomics:
  * two calls on the same inputs return the same bits.  ws >= hb_sgp_select_ws_elems(N, M, d, sizeof(T)) elements of T,
  * 16-byte aligned: the history, dvar and the arg-max partials -- O(M N): (M + 1) x (N rounded up to 64) + 12288 (float) /
- * 8192 (double).  Row j streams j rows of the history: N M^2 / 2 elements read in all. */
+ * 8192 (double).  Row j streams j rows of the history: N M^2 / 2 elements read in all.
+ * WORKSPACE LAYOUT (part of the contract: the preconditioner of henbun_amd/gp/exact.py reads it): the history C starts at
+ * ws[0], row j at ws + j ld with ld = N rounded up to 64 and zeros in the pad columns; after the call rows 0 .. count - 1
+ * hold the pivoted incomplete Cholesky factor, C^T C ~ K(X, X). */
 long hb_sgp_select_ws_elems(long N, long M, long d, int dtype_bytes);
 int hb_sgp_select_f32(int kind, const float* X, const float* ell, long dl, long N, long M, long d, double threshold, long* idx,
                       float* pivots, long* count, double* trace, float* ws, void* stream);
