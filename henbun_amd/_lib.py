@@ -52,6 +52,7 @@ _SIGS = {
     "hb_sgp_select_ws_elems": [L, L, L, I],
     "hb_gram_matvec_chunk": [],
     "hb_gram_matvec_ws_elems": [L, L, L, I],
+    "hb_gram_bilinear_grad_ws_elems": [L, L],
     "hb_sgp_kgrad_ws_elems": [L, L, L, L],
     "hb_sgp_wstats_ws_elems": [L, L, L, I],
     "hb_lik_sites_ws_elems": [L],
@@ -92,6 +93,7 @@ _RESTYPES = {"hb_last_error_string": c_char_p, "hb_sgp_ws_elems": c_long, "hb_ew
              "hb_sgp_predict_ws_elems": c_long, "hb_sgp_predict_cov_ws_elems": c_long,
              "hb_sgp_stats_ws_elems": c_long, "hb_sgp_select_ws_elems": c_long,
              "hb_gram_matvec_chunk": c_long, "hb_gram_matvec_ws_elems": c_long,
+             "hb_gram_bilinear_grad_ws_elems": c_long,
              "hb_sgp_kgrad_ws_elems": c_long, "hb_sgp_wstats_ws_elems": c_long, "hb_lik_sites_ws_elems": c_long}
 
 # entry points that exist as _f32 and _f64
@@ -142,6 +144,9 @@ _TYPED = {
     "hb_pcg_dot": [P, P, P, L, L, P],
     "hb_pcg_update": [P, P, P, P, P, P, P, L, L, P],
     "hb_pcg_direction": [P, P, P, P, P, P, D, D, I, L, L, P],
+    "hb_pcg_update_coef": [P, P, P, P, P, P, P, L, L, P, L, P],
+    "hb_pcg_direction_coef": [P, P, P, P, P, P, D, D, I, L, L, P, L, P],
+    "hb_gram_bilinear_grad": [I, P, P, L, P, P, P, P, L, L, L, P, P],
     "hb_sgp_kgrad": [I, P, P, P, P, L, P, P, P, P, L, L, L, L, P, P],
     "hb_sgp_wkgrad": [I, P, P, P, P, P, L, P, P, P, P, L, L, L, P, P],
     "hb_adam_step": [P, P, P, P, L, D, D, D, D, D, P, I, P, L, P, P, P],

@@ -278,7 +278,10 @@ extern "C" int hb_gram_matvec_f64(int kind, const double* x, const double* x2, c
 // Lockstep preconditioned conjugate gradients: S independent iterations over rows of length N, one workgroup per row.
 // Every dot product and every scalar (alpha, beta, |r|^2) is double whatever the storage type; a row's sums run in a
 // fixed order (a thread's stride, then a tree over the workgroup), so two solves return the same bits.  A row whose
-// |r|^2 has reached its threshold is skipped by both steps: its alpha is 0 and it stops moving.
+// |r|^2 has reached its threshold is skipped by both steps: its alpha is 0 and it stops moving.  The _coef entries log the
+// recurrence: with coef [2 iterations, S] non-NULL the update of iteration `it` leaves alpha_s in row 2 it and the direction
+// after it beta_s in row 2 it + 1 (a skipped row leaves nothing: the host pre-fills the log) -- the Lanczos tridiagonal of
+// the stochastic log-determinant (henbun_amd/gp/exact.py) at no extra product.  Nothing else changes with coef.
 #define PCG_THREADS 1024
 
 __device__ __forceinline__ double pcg_block_sum(double v, double* red) {
@@ -308,7 +311,7 @@ __global__ void __launch_bounds__(PCG_THREADS) pcg_dot_kernel(const T* a, const 
 // alpha = rz / (p . Ap);  x += alpha p;  r -= alpha Ap;  rr = |r|^2
 template <typename T>
 __global__ void __launch_bounds__(PCG_THREADS) pcg_update_kernel(T* x, T* r, const T* p, const T* Ap, const double* rz, double* rr,
-                                                                 const double* thr, long N) {
+                                                                 const double* thr, long N, double* coef, int it) {
   __shared__ double red[PCG_THREADS];
   const int s = blockIdx.x;
   if (!(rr[s] > thr[s])) return;   // converged: alpha = 0
@@ -317,6 +320,7 @@ __global__ void __launch_bounds__(PCG_THREADS) pcg_update_kernel(T* x, T* r, con
   for (long i = threadIdx.x; i < N; i += PCG_THREADS) acc = fma((double)p[base + i], (double)Ap[base + i], acc);
   const double pAp = pcg_block_sum(acc, red);
   const double alpha = pAp > 0.0 ? rz[s] / pAp : 0.0;   // a direction of no curvature moves nothing
+  if (coef && threadIdx.x == 0) coef[(2L * it) * gridDim.x + s] = alpha;
   acc = 0.0;
   for (long i = threadIdx.x; i < N; i += PCG_THREADS) {
     const double rn = fma(-alpha, (double)Ap[base + i], (double)r[base + i]);
@@ -333,7 +337,7 @@ __global__ void __launch_bounds__(PCG_THREADS) pcg_update_kernel(T* x, T* r, con
 template <typename T>
 __global__ void __launch_bounds__(PCG_THREADS) pcg_direction_kernel(const T* r, const T* w, T* p, double* rz, const double* rr,
                                                                     const double* thr, double wscale, double zscale, int first,
-                                                                    long N) {
+                                                                    long N, double* coef, int it) {
   __shared__ double red[PCG_THREADS];
   const int s = blockIdx.x;
   if (!(rr[s] > thr[s])) return;
@@ -347,6 +351,7 @@ __global__ void __launch_bounds__(PCG_THREADS) pcg_direction_kernel(const T* r, 
   const double rzn = pcg_block_sum(acc, red);
   const double rzo = rz[s];
   const double beta = (first || !(rzo > 0.0)) ? 0.0 : rzn / rzo;
+  if (coef && threadIdx.x == 0) coef[(2L * it + 1) * gridDim.x + s] = beta;
   for (long i = threadIdx.x; i < N; i += PCG_THREADS) {
     const double pv = first ? 0.0 : (double)p[base + i];
     p[base + i] = (T)fma(beta, pv, zval(i));
@@ -365,20 +370,23 @@ static int pcg_dot(const T* a, const T* b, double* out, long S, long N, hipStrea
 }
 template <typename T>
 static int pcg_update(T* x, T* r, const T* p, const T* Ap, const double* rz, double* rr, const double* thr, long S, long N,
-                      hipStream_t st) {
+                      double* coef, long it, hipStream_t st) {
   HB_REQUIRE(S >= 1 && S <= 2147483647L && N >= 1, "hb_pcg_update: bad extents (S=%ld N=%ld)", S, N);
   HB_REQUIRE(x && r && p && Ap && rz && rr && thr, "hb_pcg_update: NULL pointer");
-  hipLaunchKernelGGL((pcg_update_kernel<T>), dim3((unsigned)S), dim3(PCG_THREADS), 0, st, x, r, p, Ap, rz, rr, thr, N);
+  HB_REQUIRE(it >= 0 && it <= 1073741823L, "hb_pcg_update: bad iteration index (it=%ld)", it);
+  hipLaunchKernelGGL((pcg_update_kernel<T>), dim3((unsigned)S), dim3(PCG_THREADS), 0, st, x, r, p, Ap, rz, rr, thr, N, coef,
+                     (int)it);
   HB_LAUNCH_CHECK();
   return 0;
 }
 template <typename T>
 static int pcg_direction(const T* r, const T* w, T* p, double* rz, const double* rr, const double* thr, double wscale,
-                         double zscale, int first, long S, long N, hipStream_t st) {
+                         double zscale, int first, long S, long N, double* coef, long it, hipStream_t st) {
   HB_REQUIRE(S >= 1 && S <= 2147483647L && N >= 1, "hb_pcg_direction: bad extents (S=%ld N=%ld)", S, N);
   HB_REQUIRE(r && p && rz && rr && thr, "hb_pcg_direction: NULL pointer");
+  HB_REQUIRE(it >= 0 && it <= 1073741823L, "hb_pcg_direction: bad iteration index (it=%ld)", it);
   hipLaunchKernelGGL((pcg_direction_kernel<T>), dim3((unsigned)S), dim3(PCG_THREADS), 0, st, r, w, p, rz, rr, thr, wscale, zscale,
-                     first, N);
+                     first, N, coef, (int)it);
   HB_LAUNCH_CHECK();
   return 0;
 }
@@ -391,17 +399,36 @@ extern "C" int hb_pcg_dot_f64(const double* a, const double* b, double* out, lon
 }
 extern "C" int hb_pcg_update_f32(float* x, float* r, const float* p, const float* Ap, const double* rz, double* rr,
                                  const double* thr, long S, long N, void* stream) {
-  return pcg_update<float>(x, r, p, Ap, rz, rr, thr, S, N, (hipStream_t)stream);
+  return pcg_update<float>(x, r, p, Ap, rz, rr, thr, S, N, nullptr, 0, (hipStream_t)stream);
 }
 extern "C" int hb_pcg_update_f64(double* x, double* r, const double* p, const double* Ap, const double* rz, double* rr,
                                  const double* thr, long S, long N, void* stream) {
-  return pcg_update<double>(x, r, p, Ap, rz, rr, thr, S, N, (hipStream_t)stream);
+  return pcg_update<double>(x, r, p, Ap, rz, rr, thr, S, N, nullptr, 0, (hipStream_t)stream);
 }
 extern "C" int hb_pcg_direction_f32(const float* r, const float* w, float* p, double* rz, const double* rr, const double* thr,
                                     double wscale, double zscale, int first, long S, long N, void* stream) {
-  return pcg_direction<float>(r, w, p, rz, rr, thr, wscale, zscale, first, S, N, (hipStream_t)stream);
+  return pcg_direction<float>(r, w, p, rz, rr, thr, wscale, zscale, first, S, N, nullptr, 0, (hipStream_t)stream);
 }
 extern "C" int hb_pcg_direction_f64(const double* r, const double* w, double* p, double* rz, const double* rr, const double* thr,
                                     double wscale, double zscale, int first, long S, long N, void* stream) {
-  return pcg_direction<double>(r, w, p, rz, rr, thr, wscale, zscale, first, S, N, (hipStream_t)stream);
+  return pcg_direction<double>(r, w, p, rz, rr, thr, wscale, zscale, first, S, N, nullptr, 0, (hipStream_t)stream);
+}
+// the same steps with the recurrence coefficients logged: coef [2 iterations, S] double (NULL: exactly the entries above)
+extern "C" int hb_pcg_update_coef_f32(float* x, float* r, const float* p, const float* Ap, const double* rz, double* rr,
+                                      const double* thr, long S, long N, double* coef, long it, void* stream) {
+  return pcg_update<float>(x, r, p, Ap, rz, rr, thr, S, N, coef, it, (hipStream_t)stream);
+}
+extern "C" int hb_pcg_update_coef_f64(double* x, double* r, const double* p, const double* Ap, const double* rz, double* rr,
+                                      const double* thr, long S, long N, double* coef, long it, void* stream) {
+  return pcg_update<double>(x, r, p, Ap, rz, rr, thr, S, N, coef, it, (hipStream_t)stream);
+}
+extern "C" int hb_pcg_direction_coef_f32(const float* r, const float* w, float* p, double* rz, const double* rr,
+                                         const double* thr, double wscale, double zscale, int first, long S, long N,
+                                         double* coef, long it, void* stream) {
+  return pcg_direction<float>(r, w, p, rz, rr, thr, wscale, zscale, first, S, N, coef, it, (hipStream_t)stream);
+}
+extern "C" int hb_pcg_direction_coef_f64(const double* r, const double* w, double* p, double* rz, const double* rr,
+                                         const double* thr, double wscale, double zscale, int first, long S, long N,
+                                         double* coef, long it, void* stream) {
+  return pcg_direction<double>(r, w, p, rz, rr, thr, wscale, zscale, first, S, N, coef, it, (hipStream_t)stream);
 }

@@ -1,3 +1,3 @@
 from . import kernels
-from .exact import ExactPosterior, NotConverged, Preconditioner, pcg_solve
+from .exact import ExactPosterior, NotConverged, Preconditioner, log_marginal_likelihood, pcg_solve
 from .gp import GP, PathwiseDraws, SparseGP, greedy_inducing

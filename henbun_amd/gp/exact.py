@@ -7,8 +7,15 @@ most (16 sizeof(T) + 8) S N bytes (hb_gram_matvec_ws_elems); time is N^2 d kerne
 updates, the dot products and every scalar of the iteration run in the library's own kernels (hb_pcg_*: the scalars in
 double); torch allocates, copies and converts dtypes, nothing else.
 
-Out of scope: the log marginal likelihood and its gradient (they need a stochastic log-determinant), kernels other than
-UnitRBF, non-Gaussian likelihoods.  Hyper-parameters come from SVGP.fit_hyper.
+The log marginal likelihood and its gradient (log_marginal_likelihood below; GP.log_marginal_likelihood_and_grad,
+ExactGPR.fit_hyper) come from the same machinery: one lockstep solve over the rows [Y columns; probes] (per block of 64
+rows) whose recurrence
+coefficients, logged by hb_pcg_*_coef, give the log-determinant by stochastic Lanczos quadrature at no extra product, then
+ONE hb_gram_bilinear_grad -- a pass over the N^2 kernel entries that contracts K and dK/d ell against all the pairs of
+vectors of the gradient's traces -- and a host tail in float64.
+
+Out of scope: kernels other than UnitRBF, non-Gaussian likelihoods, variance reduction of the trace estimators beyond
+the preconditioner.
 """
 from __future__ import annotations
 
@@ -56,7 +63,41 @@ class Preconditioner:
         return H.matmul_ld(u.to(r.dtype).contiguous(), R, self.C, self.ld, out, S, N, R)
 
 
-def pcg_solve(sess, Xd, ell, k_var, noise_var, B, precond=None, tol=None, max_iter=1000):
+_COEF_BLOCK = 256   # iterations per block of the coefficient log (record=True)
+
+
+class _CoefLog:
+    """The coefficient log of a recorded solve: blocks [2 _COEF_BLOCK, S] of NaN that `new_block()` allocates as the
+    iteration reaches them (device tensors in pcg_solve; anything numpy converts elsewhere), handed to the recording steps
+    by slot(i) while the log is open.  stop() closes it (the first restart): later iterations get no slot and no block.
+    assemble(iterations, rows) turns the ONE read-back of the blocks into [iterations, 2, S] whatever was allocated -- iterations past
+    the last block (everything after a stop) are NaN rows, i.e. 'no coefficient'."""
+
+    def __init__(self, S, new_block, block=_COEF_BLOCK):
+        self.S, self.block, self._new, self.blocks, self.open = int(S), int(block), new_block, [], True
+
+    def slot(self, i):
+        """(the block iteration i writes to, i's index in it), or (None, 0) once the log is closed"""
+        if not self.open:
+            return None, 0
+        while i // self.block >= len(self.blocks):
+            self.blocks.append(self._new())
+        return self.blocks[i // self.block], i % self.block
+
+    def stop(self):
+        self.open = False
+
+    def assemble(self, iterations, rows):
+        """rows: the blocks concatenated, as numpy [2 block len(blocks), S] (None without blocks)"""
+        coef = np.full((iterations, 2, self.S), np.nan)
+        if rows is not None:
+            got = np.asarray(rows, dtype=np.float64).reshape(-1, 2, self.S)
+            n = min(iterations, got.shape[0])
+            coef[:n] = got[:n]
+        return coef
+
+
+def pcg_solve(sess, Xd, ell, k_var, noise_var, B, precond=None, tol=None, max_iter=1000, record=False):
     """Solve (k_var K(X, X) + noise_var I) x_s = b_s for the S rows of B [S, N] by S preconditioned conjugate-gradient
     iterations run in lockstep, each with its own alpha_s, beta_s: ONE hb_gram_matvec per iteration for all of them.
     Xd [N, d], ell [1] or [d] and B are device tensors of one dtype.  precond: a Preconditioner of the same X and
@@ -67,7 +108,11 @@ def pcg_solve(sess, Xd, ell, k_var, noise_var, B, precond=None, tol=None, max_it
     dict(iterations, restarts, residual [S] = |b - K^ x| / |b| from that last product, converged, precond_rank):
     `iterations` counts the products with a search direction, `restarts` the times the iteration was restarted (each
     costs one product more, as does the final check); raises NotConverged, carrying the same info, after max_iter
-    iterations."""
+    iterations.
+    record=True logs the recurrence (hb_pcg_update_coef / hb_pcg_direction_coef; x is the same bits) and adds to info
+    coef [iterations, 2, S] float64 -- alpha_j, beta_j per row, NaN from where a row had converged -- read back ONCE after
+    the loop, rz0 [S] = r . P^-1 r of the first direction, and lanczos_steps [S], the leading steps of each row that form
+    one three-term recurrence.  A restart breaks the recurrence: recording stops at the first one."""
     torch, H = sess.torch, sess.H
     S, N = B.shape
     dt, dev = B.dtype, B.device
@@ -90,10 +135,17 @@ def pcg_solve(sess, Xd, ell, k_var, noise_var, B, precond=None, tol=None, max_it
     thr_h = tol * tol * bb_h
     thr = torch.as_tensor(thr_h).to(dev)
 
-    def direction(first):
+    log = _CoefLog(S, lambda: H.fill(torch.empty((2 * _COEF_BLOCK, S), dtype=torch.float64, device=dev), float("nan")))
+    if not record:
+        log.stop()
+    log_of = log.slot
+
+    def direction(first, i=None):
         if precond is not None:
             precond.apply(r, w)
-        H.pcg_direction(r, w, p, rz, rr, thr, wscale=k_var, zscale=1.0 / noise_var if precond is not None else 1.0, first=first)
+        coef, at = (None, 0) if i is None else log_of(i)
+        H.pcg_direction(r, w, p, rz, rr, thr, wscale=k_var, zscale=1.0 / noise_var if precond is not None else 1.0, first=first,
+                        coef=coef, it=at)
 
     def true_residual():
         product(x)
@@ -103,6 +155,7 @@ def pcg_solve(sess, Xd, ell, k_var, noise_var, B, precond=None, tol=None, max_it
 
     rr_h, it, restarts, converged = bb_h, 0, 0, False
     direction(True)
+    rz0 = H.ewise("COPY", [rz]) if record else None
     while True:
         if np.all(rr_h <= thr_h):
             rr_h = true_residual()           # r and rr now hold the residual itself
@@ -113,22 +166,137 @@ def pcg_solve(sess, Xd, ell, k_var, noise_var, B, precond=None, tol=None, max_it
                 break
             direction(True)                  # the recurrence had drifted: restart from the residual
             restarts += 1
+            log.stop()
         elif it >= max_iter:
             rr_h = true_residual()
             break
         product(p)
-        H.pcg_update(x, r, p, Ap, rz, rr, thr)
+        coef, at = log_of(it)
+        H.pcg_update(x, r, p, Ap, rz, rr, thr, coef=coef, it=at)
         rr_h = rr.cpu().numpy()
         it += 1
         if not np.all(rr_h <= thr_h):
-            direction(False)
+            direction(False, it - 1)
     residual = np.sqrt(rr_h / np.where(bb_h > 0.0, bb_h, 1.0))
     info = dict(iterations=it, restarts=restarts, residual=residual, converged=converged,
                 precond_rank=0 if precond is None else precond.rank)
+    if record:
+        coef = log.assemble(it, torch.cat(log.blocks).cpu().numpy() if log.blocks else None)   # the one read-back
+        rz0_h = rz0.cpu().numpy()
+        rz0_h[~(bb_h > thr_h)] = 0.0          # a row that never started (b = 0) was never written
+        info.update(coef=coef, rz0=rz0_h, lanczos_steps=_lanczos_steps(coef))
     if not converged:
         raise NotConverged("pcg_solve: %d iterations did not reach |r| <= %g |b| (largest residual %g)"
                            % (it, tol, float(residual.max())), info)
     return x, info
+
+
+def _lanczos_steps(coef):
+    """[S]: the leading alpha_j of each row of coef [iterations, 2, S] that are positive (NaN: the row had stopped)."""
+    ok = coef[:, 0, :] > 0.0
+    return np.where(ok.all(0), coef.shape[0], np.argmin(ok, axis=0)).astype(np.int64) if coef.shape[0] else np.zeros(coef.shape[2], np.int64)
+
+
+def lanczos_logquad(alpha, beta):
+    """e_1^T log(T) e_1 for the Lanczos tridiagonal T [m, m] of a CG recurrence with coefficients alpha [m], beta [>= m - 1]:
+    diagonal 1 / alpha_0, then 1 / alpha_j + beta_{j-1} / alpha_{j-1}; off-diagonal sqrt(beta_{j-1}) / alpha_{j-1}.  numpy
+    float64 on the host (m is at most the iteration count); m = 0 gives 0."""
+    alpha = np.asarray(alpha, dtype=np.float64)
+    m = alpha.shape[0]
+    if m == 0:
+        return 0.0
+    beta = np.asarray(beta, dtype=np.float64)[:m - 1]
+    T = np.diag(1.0 / alpha)
+    if m > 1:
+        T[np.arange(1, m), np.arange(1, m)] += beta / alpha[:-1]
+        off = np.sqrt(beta) / alpha[:-1]
+        T[np.arange(1, m), np.arange(m - 1)] = off
+        T[np.arange(m - 1), np.arange(1, m)] = off
+    lam, V = np.linalg.eigh(T)
+    return float(np.sum(V[0] ** 2 * np.log(lam)))
+
+
+def log_marginal_likelihood(sess, Xd, Yt, ell, k_var, noise_var, precond, tol, max_iter, num_probes=16, seed=0, probes=None,
+                            grad=True):
+    """The log marginal likelihood of Y = f(X) + N(0, noise_var), f ~ GP(0, k_var k), and its gradient, without the [N, N]
+    matrix (Gardner et al. 2018).  With K^ = k_var K(X, X) + noise_var I, alpha_c = K^^-1 y_c, P_ the preconditioner (I
+    without one) and T probes z_t with E[z z^T] = P_, u_t = K^^-1 z_t:
+        L = -1/2 sum_c y_c . alpha_c - P/2 logdet K^ - N P / 2 log 2 pi
+        dL/dtheta = sum_c 1/2 alpha_c^T (dK^/dtheta) alpha_c - P / (2 T) sum_t u_t^T (dK^/dtheta) P_^-1 z_t
+        logdet K^ ~ logdet P_ + 1/T sum_t (z_t^T P_^-1 z_t) e_1^T log(T_t) e_1
+    T_t being the Lanczos tridiagonal of probe t's own CG recurrence (lanczos_logquad).  The rows [Y columns; probes] are
+    solved in lockstep by pcg_solve(record=True) -- ONE solve for P + T <= 64, otherwise one per block of 64 rows, each with
+    its own iteration count --, then ONE hb_gram_bilinear_grad over all P + T pairs and one hb_pcg_dot;
+    the N^2 work in the session's dtype, every scalar double.  Xd [N, d], Yt [P, N], ell device tensors of the session's
+    dtype; precond a Preconditioner of the same hyper-parameters or None.  Default probes: z_t = sqrt(k_var) eps1 C +
+    sqrt(noise_var) eps2 with eps1 [T, R], eps2 [T, N] from hip_ops.Rng(seed) in that order (no preconditioner: z_t = eps2);
+    probes= injects Z [T, N] as given.  Returns (value, grad, info): grad = dict(lengthscales [dl], k_var, noise_var)
+    float64 with respect to the constrained values (None with grad=False); info = the solve's info -- with several blocks
+    `iterations` and `restarts` are SUMS over the blocks' solves, residual / rz0 / coef concatenated over the rows, coef
+    NaN-padded to the longest block -- plus
+    logdet, logdet_precond, num_probes and lanczos_steps [T] (the probes' rows).  The estimate is a deterministic function
+    of (seed or probes); its distance from the exact value is the estimator's variance."""
+    torch, H = sess.torch, sess.H
+    P, N = Yt.shape
+    dt, dev = Yt.dtype, Yt.device
+    k_var, noise_var = float(k_var), float(noise_var)
+    if precond is not None and precond.rank == 0:
+        precond = None
+    if probes is None:
+        T = int(num_probes)
+        if T < 1:
+            raise ValueError("log_marginal_likelihood: num_probes >= 1 expected (got %r)" % (num_probes,))
+        rng = H.Rng(seed, device=dev)
+        if precond is None:
+            Z = rng.normal((T, N), dtype=dt)
+        else:
+            R = precond.rank
+            e1, e2 = rng.normal((T, R), dtype=dt), rng.normal((T, N), dtype=dt)
+            Z = H.matmul_ld(e1, R, precond.C, precond.ld, torch.empty((T, N), dtype=dt, device=dev), T, N, R,
+                            alpha=np.sqrt(k_var))
+            Z = H.ewise("ADD", [Z, H.ewise("AFFINE", [e2], params=(np.sqrt(noise_var), 0.0))])
+    else:
+        if np.ndim(probes) != 2 or np.shape(probes)[1] != N or np.shape(probes)[0] < 1:
+            raise ValueError("log_marginal_likelihood: probes must be [T, %d] (got %s)" % (N, np.shape(probes)))
+        Z = torch.as_tensor(np.ascontiguousarray(probes, dtype=sess.np_dtype)).to(dev)
+        T = Z.shape[0]
+    rows = torch.cat([Yt, Z]).contiguous()
+    S = P + T
+    sol = torch.empty((S, N), dtype=dt, device=dev)
+    infos = []
+    for a in range(0, S, 64):
+        x, inf = pcg_solve(sess, Xd, ell, k_var, noise_var, rows[a:a + 64].contiguous(), precond, tol, max_iter, record=True)
+        H.ewise("COPY", [x], out=sol[a:a + 64])
+        infos.append(inf)
+    iters = max(i["iterations"] for i in infos)
+    coef = np.full((iters, 2, S), np.nan)
+    for a, i in zip(range(0, S, 64), infos):
+        coef[:i["coef"].shape[0], :, a:a + 64] = i["coef"]
+    cat = lambda k: np.concatenate([i[k] for i in infos])
+    info = dict(iterations=sum(i["iterations"] for i in infos), restarts=sum(i["restarts"] for i in infos),
+                residual=cat("residual"), converged=all(i["converged"] for i in infos), precond_rank=infos[0]["precond_rank"],
+                coef=coef, rz0=cat("rz0"))
+    steps = cat("lanczos_steps")
+
+    if precond is None:
+        PinvZ, logdet_p = Z, 0.0
+    else:
+        PinvZ = H.ewise("AFFINE", [H.ewise("SUB", [Z, H.ewise("AFFINE", [precond.apply(Z, torch.empty_like(Z))],
+                                                           params=(k_var, 0.0))])], params=(1.0 / noise_var, 0.0))
+        # logdet(noise_var I + k_var C C^T) = 2 sum log diag L = -2 sum log diag L^-1
+        logdet_p = (N - precond.rank) * np.log(noise_var) - 2.0 * float(np.log(torch.diagonal(precond.Linv).cpu().numpy()).sum())
+    quad = [info["rz0"][P + t] * lanczos_logquad(coef[:steps[P + t], 0, P + t], coef[:steps[P + t], 1, P + t]) for t in range(T)]
+    logdet = logdet_p + float(np.sum(quad)) / T
+    fit = float(H.pcg_dot(Yt, sol[:P].contiguous()).cpu().numpy().sum())
+    value = -0.5 * fit - 0.5 * P * logdet - 0.5 * N * P * np.log(2.0 * np.pi)
+    info.update(logdet=logdet, logdet_precond=logdet_p, num_probes=T, lanczos_steps=steps[P:])
+    if not grad:
+        return value, None, info
+    Bm = torch.cat([sol[:P], PinvZ]).contiguous()
+    wts = np.concatenate([np.full(P, 0.5), np.full(T, -0.5 * P / T)])
+    g = H.gram_bilinear_grad(Xd, ell, sol, Bm, wts).cpu().numpy()
+    dots = H.pcg_dot(sol, Bm).cpu().numpy()
+    return value, dict(lengthscales=k_var * g[1:], k_var=float(g[0]), noise_var=float(wts @ dots)), info
 
 
 class ExactPosterior:

@@ -44,38 +44,67 @@ class GP(Parameterized):
         1e-5 the residual stalls near 3e-5 -- profiles/exact_gp_bench.txt), and the floor rises with the conditioning.
         Not reaching the tolerance within max_iter iterations raises hb.gp.NotConverged, which carries the solve's info.
         UnitRBF with the lengthscales one Variable [dl] only, as SparseGP.statistics: anything else raises
-        NotImplementedError.  The log marginal likelihood and its gradient are out of scope: hyper-parameters come from
-        SVGP.fit_hyper."""
+        NotImplementedError.  Hyper-parameters: log_marginal_likelihood_and_grad below (ExactGPR.fit_hyper)."""
+        from . import exact
+
+        sess, Xd, Yt, ell, tol, precond = self._exact_inputs("condition", X, Y, noise_var, k_var, precond_rank, tol)
+        alpha, info = exact.pcg_solve(sess, Xd, ell, k_var, noise_var, Yt, precond, tol, max_iter)
+        return exact.ExactPosterior(sess, _device_data, Xd, Yt, ell, k_var, noise_var, alpha, precond, info, tol, max_iter)
+
+    def _exact_inputs(self, who, X, Y, noise_var, k_var, precond_rank, tol):
+        """The validation condition and log_marginal_likelihood share -> (sess, Xd [N, d], Yt [P, N], ell, tol, precond)."""
         from . import exact
 
         root = self.highest_parent
         sess = getattr(root, "_session", None)
         if sess is None:
-            raise ValueError("condition needs the GP to be part of a Model")
+            raise ValueError("%s needs the GP to be part of a Model" % who)
         kern = self._kern()
         if not isinstance(kern, UnitRBF):
-            raise NotImplementedError("condition: exact regression is implemented for the UnitRBF kernel only (got %s)"
-                                      % type(kern).__name__)
+            raise NotImplementedError("%s: exact regression is implemented for the UnitRBF kernel only (got %s)"
+                                      % (who, type(kern).__name__))
         ls = object.__getattribute__(kern, "lengthscales")
         if not isinstance(ls, Variable) or len(ls.shape) != 1:
-            raise NotImplementedError("condition: one expert only, the lengthscales must be one Variable [dl]")
+            raise NotImplementedError("%s: one expert only, the lengthscales must be one Variable [dl]" % who)
         root.initialize()
         Xd, Yd = _device_data(sess, X, "X"), _device_data(sess, Y, "Y")
         N, d = Xd.shape
         if Yd.shape[0] != N or N < 1:
-            raise ValueError("condition: X %s and Y %s do not match" % (tuple(Xd.shape), tuple(Yd.shape)))
+            raise ValueError("%s: X %s and Y %s do not match" % (who, tuple(Xd.shape), tuple(Yd.shape)))
         if Yd.shape[1] > 64:
-            raise NotImplementedError("condition: at most 64 output columns are solved in lockstep (Y has %d)" % Yd.shape[1])
+            raise NotImplementedError("%s: at most 64 output columns are solved in lockstep (Y has %d)" % (who, Yd.shape[1]))
         if int(ls.shape[0]) not in (1, d):
-            raise ValueError("condition: %d lengthscales for X %s" % (int(ls.shape[0]), tuple(Xd.shape)))
+            raise ValueError("%s: %d lengthscales for X %s" % (who, int(ls.shape[0]), tuple(Xd.shape)))
         torch = sess.torch
         ell = torch.as_tensor(np.ascontiguousarray(np.reshape(sess.read_value(ls), [-1]).astype(sess.np_dtype))).to(sess.device)
         if tol is None:
             tol = 1e-6 if sess.torch_dtype == torch.float64 else 1e-3
         precond = exact.Preconditioner(sess, Xd, ell, k_var, noise_var, precond_rank) if int(precond_rank) > 0 else None
-        Yt = Yd.t().contiguous()
-        alpha, info = exact.pcg_solve(sess, Xd, ell, k_var, noise_var, Yt, precond, tol, max_iter)
-        return exact.ExactPosterior(sess, _device_data, Xd, Yt, ell, k_var, noise_var, alpha, precond, info, tol, max_iter)
+        return sess, Xd, Yd.t().contiguous(), ell, tol, precond
+
+    def log_marginal_likelihood_and_grad(self, X, Y, noise_var, k_var=1.0, precond_rank=64, tol=None, max_iter=1000,
+                                         num_probes=16, seed=0, probes=None, grad=True):
+        """(value, grad, info): the log marginal likelihood log p(Y | X) of Y = f(X) + N(0, noise_var), f ~ GP(0, k_var k),
+        at the current lengthscales and its gradient grad = dict(lengthscales [dl], k_var, noise_var) (float64, with
+        respect to the constrained values), from conjugate gradients on the matrix-free product -- no [N, N] matrix, no
+        factorisation (gp/exact.py: log_marginal_likelihood).  The data-fit term is exact to the solve's tolerance; the
+        log-determinant and the traces of the gradient are stochastic estimates from num_probes probe vectors, Lanczos
+        quadrature on the coefficients of the probes' own solves and one hb_gram_bilinear_grad pass over the kernel
+        entries.  The result is a deterministic function of `seed` (common random numbers: the same seed at every step of
+        an optimiser gives it a fixed function to climb); probes= injects the probe vectors [T, N], which should have
+        covariance P = k_var C^T C + noise_var I, the preconditioner (I at precond_rank = 0).  16 probes is a default,
+        not a measurement.  Arguments, validation and NotConverged as for condition."""
+        from . import exact
+
+        sess, Xd, Yt, ell, tol, precond = self._exact_inputs("log_marginal_likelihood", X, Y, noise_var, k_var, precond_rank, tol)
+        return exact.log_marginal_likelihood(sess, Xd, Yt, ell, k_var, noise_var, precond, tol, max_iter, num_probes=num_probes,
+                                             seed=seed, probes=probes, grad=grad)
+
+    def log_marginal_likelihood(self, X, Y, noise_var, k_var=1.0, precond_rank=64, tol=None, max_iter=1000, num_probes=16,
+                                seed=0, probes=None):
+        """The value of log_marginal_likelihood_and_grad alone (the pass over the kernel entries is skipped)."""
+        return self.log_marginal_likelihood_and_grad(X, Y, noise_var, k_var, precond_rank, tol, max_iter, num_probes, seed,
+                                                     probes, grad=False)[0]
 
 
 class SparseGP(GP):

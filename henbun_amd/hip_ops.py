@@ -1270,19 +1270,79 @@ def _pcg_check(who, mats, vecs):
     return S, N
 
 
-def pcg_update(x, r, p, Ap, rz, rr, thr):
+def _pcg_coef(who, coef, it, S):
+    _chk(coef)
+    it = int(it)
+    if coef.dtype != torch.float64 or coef.dim() != 2 or coef.shape[1] != S or not 0 <= it < coef.shape[0] // 2:
+        raise ValueError("%s: coef must be float64 [2 iterations, %d] with it below its iterations" % (who, S))
+    return it
+
+
+def pcg_update(x, r, p, Ap, rz, rr, thr, coef=None, it=0):
     """One lockstep CG update in place (hb_pcg_update): alpha = rz / (p . Ap), x += alpha p, r -= alpha Ap, rr = |r|^2 for
-    every row with rr > thr; x, r, p, Ap [S, N], rz, rr, thr float64 [S]."""
+    every row with rr > thr; x, r, p, Ap [S, N], rz, rr, thr float64 [S].  coef (float64 [2 iterations, S]): alpha is also
+    stored in coef[2 it] (hb_pcg_update_coef); the vectors and scalars are the same bits."""
     S, N = _pcg_check("pcg_update", (x, r, p, Ap), (rz, rr, thr))
-    _lib.lib().call("hb_pcg_update" + _suf(x), _p(x), _p(r), _p(p), _p(Ap), _p(rz), _p(rr), _p(thr), S, N, stream())
+    if coef is None:
+        _lib.lib().call("hb_pcg_update" + _suf(x), _p(x), _p(r), _p(p), _p(Ap), _p(rz), _p(rr), _p(thr), S, N, stream())
+    else:
+        it = _pcg_coef("pcg_update", coef, it, S)
+        _lib.lib().call("hb_pcg_update_coef" + _suf(x), _p(x), _p(r), _p(p), _p(Ap), _p(rz), _p(rr), _p(thr), S, N, _p(coef), it,
+                        stream())
 
 
-def pcg_direction(r, w, p, rz, rr, thr, wscale=1.0, zscale=1.0, first=False):
+def pcg_direction(r, w, p, rz, rr, thr, wscale=1.0, zscale=1.0, first=False, coef=None, it=0):
     """The next search directions in place (hb_pcg_direction): z = (r - wscale w) zscale (w None: z = r), beta = (r . z) /
-    rz (first: 0), p = z + beta p, rz = r . z for every row with rr > thr."""
+    rz (first: 0), p = z + beta p, rz = r . z for every row with rr > thr.  coef (float64 [2 iterations, S]): beta is also
+    stored in coef[2 it + 1] (hb_pcg_direction_coef)."""
     S, N = _pcg_check("pcg_direction", (r, w, p), (rz, rr, thr))
-    _lib.lib().call("hb_pcg_direction" + _suf(r), _p(r), _p(w), _p(p), _p(rz), _p(rr), _p(thr), float(wscale), float(zscale),
-                    int(bool(first)), S, N, stream())
+    if coef is None:
+        _lib.lib().call("hb_pcg_direction" + _suf(r), _p(r), _p(w), _p(p), _p(rz), _p(rr), _p(thr), float(wscale), float(zscale),
+                        int(bool(first)), S, N, stream())
+    else:
+        it = _pcg_coef("pcg_direction", coef, it, S)
+        _lib.lib().call("hb_pcg_direction_coef" + _suf(r), _p(r), _p(w), _p(p), _p(rz), _p(rr), _p(thr), float(wscale),
+                        float(zscale), int(bool(first)), S, N, _p(coef), it, stream())
+
+
+def gram_bilinear_grad_ws_elems(N, dl):
+    """Scratch DOUBLES hb_gram_bilinear_grad needs: min(chunks, 16) x strips x (1 + dl) -- O(N), whatever S."""
+    return int(_lib.lib().raw("hb_gram_bilinear_grad_ws_elems")(int(N), int(dl)))
+
+
+def gram_bilinear_grad(x, ell, A, B, w, out=None, ws=None, kind=KERN_RBF):
+    """g [1 + dl] float64 (hb_gram_bilinear_grad): g[0] = sum_s w_s A_s K(x, x) B_s^T and g[1 + k] = sum_s w_s sum_ij A_si
+    B_sj K_ij (x_ik - x_jk)^2 / ell_k^3 (dl = 1: summed over k), with neither K nor sum_s w_s A_s (x) B_s written to memory.
+    x [N, d], ell [1] or [d], A, B [S, N] of one dtype; w [S] float64 (a device tensor, or anything numpy converts).  Two
+    calls return the same bits.  `ws`: gram_bilinear_grad_ws_elems doubles (default: the shared scratch of the stream)."""
+    for t in (x, ell, A, B):
+        _chk(t)
+    if x.dim() != 2 or ell.dim() != 1 or A.dim() != 2 or tuple(A.shape) != tuple(B.shape) or A.shape[1] != x.shape[0]:
+        raise ValueError("gram_bilinear_grad: x [N, d], ell [1] or [d], A, B [S, N] expected, got %s %s %s %s"
+                         % (tuple(x.shape), tuple(ell.shape), tuple(A.shape), tuple(B.shape)))
+    if any(t.dtype != x.dtype for t in (ell, A, B)):
+        raise TypeError("gram_bilinear_grad: x, ell, A and B must share one dtype")
+    N, d = x.shape
+    S, dl = A.shape[0], ell.numel()
+    if not torch.is_tensor(w):
+        w = torch.as_tensor(np.ascontiguousarray(w, dtype=np.float64)).to(x.device)
+    _chk(w)
+    if w.dtype != torch.float64 or w.numel() != S:
+        raise ValueError("gram_bilinear_grad: w must be float64 [%d]" % S)
+    if out is None:
+        out = _empty((1 + dl,), dtype=torch.float64, device=x.device)
+    else:
+        _chk(out)
+        if out.dtype != torch.float64 or out.numel() != 1 + dl:
+            raise ValueError("gram_bilinear_grad: out must be float64 [%d]" % (1 + dl))
+    need = gram_bilinear_grad_ws_elems(N, dl)
+    if ws is None:
+        ws = workspace(torch.float64, x.device, max(need, 1))
+    if ws.dtype != torch.float64 or ws.numel() < need:
+        raise ValueError("gram_bilinear_grad: the workspace must hold %d doubles (gram_bilinear_grad_ws_elems)" % need)
+    _lib.lib().call("hb_gram_bilinear_grad" + _suf(x), int(kind), _p(x), _p(ell), dl, _p(A), _p(B), _p(w), _p(out), N, d, S,
+                    _p(ws), stream())
+    return out
 
 
 LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON = 0, 1, 2

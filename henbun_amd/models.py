@@ -355,9 +355,10 @@ class DenseGPR(hb.model.Model):
 
 class ExactGPR(hb.model.Model):
     """Exact GP regression at scale: kern, k_var and var as in SVGP, the posterior from conjugate gradients on the
-    matrix-free kernel product (GP.condition) instead of an [N, N] factorisation.  There is no objective to optimise here
-    (the log marginal likelihood is out of scope): set lengthscales, k_var and var -- from SVGP.fit_hyper, say -- then
-        m.fit();  mean, var = m.predict_y(Xnew);  draws = m.sample_functions(16)
+    matrix-free kernel product (GP.condition) instead of an [N, N] factorisation.  The objective is the log marginal
+    likelihood, estimated with its gradient from the same solves (GP.log_marginal_likelihood_and_grad):
+        m.fit_hyper(100, lr=0.05);  mean, var = m.predict_y(Xnew);  draws = m.sample_functions(16)
+    or set lengthscales, k_var and var by hand and call m.fit().
     Predictions are in data units: mean [P, n] and var [n] of f ~ GP(0, k_var k) given Y = f(X) + N(0, var)."""
 
     def setUp(self, X, Y):
@@ -377,6 +378,43 @@ class ExactGPR(hb.model.Model):
                                            k_var=float(np.ravel(g("k_var").value)[0]), precond_rank=precond_rank, tol=tol,
                                            max_iter=max_iter)
         return self
+
+    def _hyper_variables(self):
+        """The Variables the log marginal likelihood depends on, by the names the gradient uses."""
+        g = object.__getattribute__
+        return dict(lengthscales=g(g(g(self, "gp"), "kern"), "lengthscales"), k_var=g(self, "k_var"), var=g(self, "var"))
+
+    def log_marginal_likelihood_and_grad(self, num_probes=16, seed=0, precond_rank=64, tol=None, max_iter=1000, probes=None):
+        """(value, grad): the log marginal likelihood of the model's X, Y at the current hyper-parameters and its gradient
+        with respect to the RAW (free) parameters, grad = dict(lengthscales, k_var, var) in the shapes of the raw arrays,
+        float64 numpy: GP.log_marginal_likelihood_and_grad chained through the transforms' dforward.  A stochastic
+        estimate, deterministic given `seed` (or `probes`)."""
+        self.initialize()
+        g = lambda k: object.__getattribute__(self, k)
+        value, gr, _ = g("gp").log_marginal_likelihood_and_grad(
+            g("X"), g("Y"), float(np.ravel(g("var").value)[0]), k_var=float(np.ravel(g("k_var").value)[0]),
+            precond_rank=precond_rank, tol=tol, max_iter=max_iter, num_probes=num_probes, seed=seed, probes=probes)
+        return value, _chain_to_raw(self, dict(lengthscales=gr["lengthscales"], k_var=gr["k_var"], var=gr["noise_var"]))
+
+    def log_marginal_likelihood(self, num_probes=16, seed=0, precond_rank=64, tol=None, max_iter=1000, probes=None):
+        """The value alone (no pass over the kernel entries)."""
+        self.initialize()
+        g = lambda k: object.__getattribute__(self, k)
+        return g("gp").log_marginal_likelihood(
+            g("X"), g("Y"), float(np.ravel(g("var").value)[0]), k_var=float(np.ravel(g("k_var").value)[0]),
+            precond_rank=precond_rank, tol=tol, max_iter=max_iter, num_probes=num_probes, seed=seed, probes=probes)
+
+    def fit_hyper(self, steps, lr=0.01, num_probes=16, seed=0, precond_rank=64, tol=None):
+        """Fit lengthscales, k_var and var: `steps` Adam ASCENT steps on log_marginal_likelihood_and_grad in the raw
+        parameters, on the host in float64 (the loop of SVGP.fit_hyper), with the SAME seed at every step -- common random
+        numbers, so the function climbed is deterministic -- then fit() at the final parameters.  Each step is one
+        lockstep solve of 1 + num_probes rows and one pass over the kernel entries.  Returns the trace of the estimated
+        objective, steps + 1 entries: before the first step .. at the final parameters.  hb.gp.NotConverged propagates."""
+        evaluate = lambda: self.log_marginal_likelihood_and_grad(num_probes=num_probes, seed=seed, precond_rank=precond_rank,
+                                                                 tol=tol)
+        trace = _adam_ascent(self, evaluate, steps, lr, True)
+        self.fit(precond_rank=precond_rank, tol=tol)
+        return trace
 
     def _posterior(self):
         post = object.__getattribute__(self, "posterior")

@@ -52,7 +52,8 @@ extern "C" {
  * hb_lik_sites_ws_elems, hb_lik_predict_f32 / _f64 and the enum values HB_LIK_* (natural-gradient fit of q(u) for
  * non-Gaussian likelihoods); hb_sgp_wkgrad_f32 / _f64 (streamed part of the gradient of the ELBO at a fixed q(u));
  * hb_sgp_pathwise_f32 / _f64 (pathwise posterior function draws, linear in n); hb_gram_matvec_f32 / _f64 and hb_pcg_*
- * (matrix-free kernel product and the vector steps of lockstep preconditioned conjugate gradients: exact GP regression). */
+ * (matrix-free kernel product and the vector steps of lockstep preconditioned conjugate gradients: exact GP regression);
+ * hb_gram_bilinear_grad_f32 / _f64 and hb_pcg_*_coef (the exact GP's log marginal likelihood and its gradient). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -728,6 +729,38 @@ int hb_pcg_direction_f32(const float* r, const float* w, float* p, double* rz, c
                          double wscale, double zscale, int first, long S, long N, void* stream);
 int hb_pcg_direction_f64(const double* r, const double* w, double* p, double* rz, const double* rr, const double* thr,
                          double wscale, double zscale, int first, long S, long N, void* stream);
+/* hb_pcg_update / hb_pcg_direction with the recurrence coefficients logged: coef [2 iterations, S] DOUBLE or NULL.  With
+ * coef != NULL the update of iteration `it` stores alpha_s at coef[(2 it) S + s] and the direction after it beta_s at
+ * coef[(2 it + 1) S + s]; a converged row (skipped) stores nothing, so a log the host pre-filled with NaN marks where a
+ * row's recurrence ended.  From these the host builds the Lanczos tridiagonal of the preconditioned matrix (stochastic
+ * Lanczos quadrature of log det, henbun_amd/gp/exact.py).  x, r, p, rz, rr are the bits of the entries above; coef ==
+ * NULL is exactly those entries. */
+int hb_pcg_update_coef_f32(float* x, float* r, const float* p, const float* Ap, const double* rz, double* rr,
+                           const double* thr, long S, long N, double* coef, long it, void* stream);
+int hb_pcg_update_coef_f64(double* x, double* r, const double* p, const double* Ap, const double* rz, double* rr,
+                           const double* thr, long S, long N, double* coef, long it, void* stream);
+int hb_pcg_direction_coef_f32(const float* r, const float* w, float* p, double* rz, const double* rr, const double* thr,
+                              double wscale, double zscale, int first, long S, long N, double* coef, long it, void* stream);
+int hb_pcg_direction_coef_f64(const double* r, const double* w, double* p, double* rz, const double* rr, const double* thr,
+                              double wscale, double zscale, int first, long S, long N, double* coef, long it, void* stream);
+/* Bilinear contraction of K = K(x, x) and of its lengthscale derivative against S weighted pairs of vectors
+ * (csrc/gram_grad.hip; not in the reference): the traces of the gradient of the exact GP's log marginal likelihood.
+ *   g[0]     = sum_s w_s sum_ij A_si B_sj K_ij
+ *   g[1 + k] = sum_s w_s sum_ij A_si B_sj K_ij (x_ik - x_jk)^2 / ell_k^3,   k < dl  (dl = 1: summed over k, ell_0^3)
+ * x [N, d], A, B [S, N] row-major and contiguous in the storage type; ell [dl], dl in {1, d}; w [S] and g [1 + dl] DOUBLE;
+ * kind must be HB_KERN_RBF.  Neither K nor W = sum_s w_s A_s (x) B_s is written to memory: workgroups of column strips x
+ * row chunks (the decomposition of hb_gram_matvec) form 32 x 32 tiles of W on the 16 x 16 x 4 MFMA with the pair index
+ * contracted, evaluate K and the squared differences at the accumulator positions and add into per-lane DOUBLE sums.  No
+ * atomics: one partial per workgroup, folded in a fixed order in double by a second launch; more than 16 chunks or 64
+ * pairs are taken 16 / 64 at a time with the fold carrying its sum in g.  Two calls return the same bits.  ARD
+ * lengthscales with d > 4 run four dimensions per grid z-slice.  ws >= hb_gram_bilinear_grad_ws_elems(N, dl) DOUBLES =
+ * min(chunks, 16) x strips x (1 + dl), whatever S.  N = 0: g is zero-filled, no kernel of the contraction runs.
+ * Validated before any launch. */
+long hb_gram_bilinear_grad_ws_elems(long N, long dl);
+int hb_gram_bilinear_grad_f32(int kind, const float* x, const float* ell, long dl, const float* A, const float* B,
+                              const double* w, double* g, long N, long d, long S, double* ws, void* stream);
+int hb_gram_bilinear_grad_f64(int kind, const double* x, const double* ell, long dl, const double* A, const double* B,
+                              const double* w, double* g, long N, long d, long S, double* ws, void* stream);
 /* Greedy conditional-variance selection of M inducing points out of X [N, d] (csrc/sgp_select.hip; not in the reference;
  * Burt, Rasmussen, van der Wilk 2020): a pivoted incomplete Cholesky of K(X, X).  With dvar [N] = kdiag = 1 and the
  * history C [M, N], for j = 0 .. M - 1:
