@@ -44,6 +44,8 @@ _SIGS = {
     "hb_rng_randint": [P, L, P, L, L, L, P],
     "hb_sgp_ws_elems": [L, L, L, L, L],
     "hb_sgp_strip_path": [L, L, L, L, L, I],
+    "hb_sgp_bwd_phi_supported": [L, L, L, L, L],
+    "hb_sgp_bwd_phi_f32": [I, I, P, L, P, P, L, P, P, P, P, P, P, P, P, P, P, P, P, L, L, L, L, L, P, P],
     "hb_sgp_head_units": [L, L, L, L, L, I, I, I, L],
     "hb_sgp_rider_supported": [L, L, L, L, L, I, I, I, L],
     "hb_sgp_predict_ws_elems": [L, L, L, L, L, I, I, I],

@@ -2069,6 +2069,7 @@ struct SgpBwdArgs {
   T* part;        // [E, nS, 2d + P, M] strip partials of zbar, ell, ubar
   const T* Af;    // fragment-major A (written by the forward strip kernel), or nullptr: read A row-major
   T* Kf;          // fragment-major Kbar output for the Lbar contraction, or nullptr
+  T* Abf;         // fragment-major Abar output (hb_sgp_bwd_phi: the contraction then forms Abar A^T and Kf is not stored), or nullptr
 };
 
 template <typename T>
@@ -2273,6 +2274,7 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
     const long fplane = (long)a.plane3 / a.M * 32 * nS;   // elements per bf16 plane of a fragment-major operand
     for (int t = w; t < nTp; t += SGP_STRIP_THREADS / 64) {
       float avals[16];
+      long abf_off = 0;
       if (BF3) {
         const __bf16* blk = reinterpret_cast<const __bf16*>(a.Af) + ((((long)e * nTp + t) * nS + bx) << 10) + 8 * lane;
         B8 pl[3][2];
@@ -2285,7 +2287,8 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
 #pragma unroll
           for (int j = 0; j < 8; ++j) avals[8 * q + j] = ((float)pl[2][q][j] + (float)pl[1][q][j]) + (float)pl[0][q][j];
       } else {
-        const float* blk = a.Af + ((((long)e * nTp + t) * nS + bx) << 10) + 4 * lane;
+        abf_off = ((((long)e * nTp + t) * nS + bx) << 10) + 4 * lane;
+        const float* blk = a.Af + abf_off;
         V4 av[4];
 #pragma unroll
         for (int v = 0; v < 4; ++v) av[v] = *reinterpret_cast<const V4*>(blk + 256 * v);
@@ -2304,6 +2307,7 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
         V4 fb4[4];
 #pragma unroll
         for (int p = 0; p < 4; ++p) fb4[p] = *reinterpret_cast<const V4*>(&fbs[p][16 * h + 4 * v]);
+        V4 ab4;
 #pragma unroll
         for (int s2 = 0; s2 < 4; ++s2) {
           const int c = 16 * h + 4 * v + s2;
@@ -2322,8 +2326,11 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
             K3[0][c][k] = b0, K3[1][c][k] = b1, K3[2][c][k] = (__bf16)(r1 - (float)b1);
           } else {
             Ks[c][k] = val;
+            ab4[s2] = val;
           }
         }
+        // the Abar image, addressed like the A fragment it was built from (columns past n: cjs and fbs are zero there)
+        if (!BF3 && a.Abf) *reinterpret_cast<V4*>(a.Abf + abf_off + 256 * v) = ab4;
       }
 #pragma unroll
       for (int p = 0; p < 4; ++p)
@@ -2444,7 +2451,7 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
           if (col0 + 16 * h + i < n) kp[i] = kb[i];
       }
     }
-    if (a.Kf && !BF3) sgp_store_frag_rows(a.Kf, kb, e, nT, nS, tile, bx, col0, n, lane);   // one contiguous KB per store
+    if (a.Kf && !BF3 && !a.Abf) sgp_store_frag_rows(a.Kf, kb, e, nT, nS, tile, bx, col0, n, lane);   // one contiguous KB per store
     if (BF3 && a.Kf)   // ... as three bf16 planes for the bf16x3 Lbar contraction
       sgp_store_frag3_row(reinterpret_cast<__bf16*>(a.Kf), (long)a.plane3 / a.M * 32 * nS, kb, e, nT, nS, tile, bx, lane);
     const int row = 32 * tile + li;
@@ -2899,6 +2906,74 @@ __device__ __forceinline__ void sgp_lbar_finish_body(const T* __restrict__ slabs
     Lbar[t] = acc;
   }
 }
+// The same fold for hb_sgp_bwd_phi, whose slabs hold the lower tiles of Abar A^T:  Phi = Phisym(-sum_s slab_s), i.e.
+// Phi_rc = Phi_cr = -0.5 * (sum_s slab_s)_{max(r,c), min(r,c)}, the diagonal included (matutil mode 4).  A workgroup pass
+// takes 16 rows of one 32 x 32 lower tile (ti >= tj), two elements per thread: the sums are read once, coalesced, in the
+// slab order of the body above with every load of a group of four slabs in flight together, and written twice -- in
+// place, and mirrored into tile (tj, ti) through an LDS transpose (64-byte row segments).  M % 32 == 0.
+template <typename T>
+__device__ __forceinline__ void sgp_phi_finish_body(const T* __restrict__ slabs, int S, long E, long M, T* __restrict__ Phi,
+                                                    long vblock, long nvblocks, T (*tile)[33]) {
+  const long total = E * M * M;
+  const int nT = (int)(M / 32), pairs = nT * (nT + 1) / 2;
+  const long units = E * pairs * 2;
+  for (long unit = vblock; unit < units; unit += nvblocks) {
+    const long e = unit / (2 * pairs);
+    const int rest = (int)(unit - e * 2 * pairs), pair = rest >> 1, r0 = 16 * (rest & 1);
+    int ti = (int)((sqrtf(8.f * (float)pair + 1.f) - 1.f) * 0.5f);
+    while (ti * (ti + 1) / 2 > pair) --ti;
+    while ((ti + 1) * (ti + 2) / 2 <= pair) ++ti;
+    const int tj = pair - ti * (ti + 1) / 2;
+    const bool diag = ti == tj;
+    long t[2];
+    T a[2][4], val[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int idx = threadIdx.x + 256 * k, r = idx >> 5, c = idx & 31;
+      t[k] = (e * M + 32 * ti + r0 + r) * M + 32 * tj + c;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) a[k][q] = T(0);
+    }
+    int s = 0;
+    for (; s + 4 <= S; s += 4) {
+      T v[2][4];
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[k][q] = slabs[(long)(s + q) * total + t[k]];
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a[k][q] += v[k][q];
+    }
+    {
+      T v[2][3];
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) v[k][q] = s + q < S ? slabs[(long)(s + q) * total + t[k]] : T(0);
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+          if (s + q < S) a[k][0] += v[k][q];
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int idx = threadIdx.x + 256 * k, r = idx >> 5, c = idx & 31;
+      val[k] = T(0.5) * -((a[k][0] + a[k][1]) + (a[k][2] + a[k][3]));
+      tile[r][c] = val[k];
+      if (!diag || c <= r0 + r) Phi[t[k]] = val[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int idx = threadIdx.x + 256 * k, c = idx >> 4, r = idx & 15;
+      if (!diag || c < r0 + r) Phi[(e * M + 32 * tj + c) * M + 32 * ti + r0 + r] = tile[r][c];
+    }
+    __syncthreads();
+  }
+}
 template <typename T>
 __global__ void __launch_bounds__(256) sgp_lbar_finish_kernel(const T* __restrict__ slabs, int S, long E, long M,
                                                               T* __restrict__ Lbar) {
@@ -2980,14 +3055,17 @@ __global__ void __launch_bounds__(256) sgp_bwd_finish_kernel(const T* __restrict
                                                              long P, T* __restrict__ zbar, T* __restrict__ ellbar,
                                                              T* __restrict__ ubar, int nb_strip, int nbx,
                                                              const T* __restrict__ slabs, int S, long E,
-                                                             T* __restrict__ Lbar) {
+                                                             T* __restrict__ Lbar, int phi) {
   __shared__ T red[4][64];
   __shared__ T smem[16];
+  __shared__ T tile[32][33];
   if ((int)blockIdx.x < nb_strip) {
     const int nq = (int)(2 * d + P);
     const int vb = blockIdx.x;
     sgp_strip_finish_body<T>(part, nS, M, d, dl, P, zbar, ellbar, ubar, vb % nbx, (vb / nbx) % nq, (long)(vb / (nbx * nq)), red,
                              smem);
+  } else if (phi) {   // (hb_sgp_bwd_phi: `Lbar` receives Phisym(-Abar A^T), both triangles)
+    sgp_phi_finish_body<T>(slabs, S, E, M, Lbar, (long)blockIdx.x - nb_strip, (long)gridDim.x - nb_strip, tile);
   } else {
     sgp_lbar_finish_body<T>(slabs, S, E, M, Lbar, (long)blockIdx.x - nb_strip, (long)gridDim.x - nb_strip);
   }
@@ -3300,7 +3378,7 @@ template <typename T>
 static int sgp_bwd(int kind, int mode, const T* x, long sx, const T* z, const T* ell, long dl, const T* W,
                    const T* Wfrag, int prec, const T* u, const T* eps, const T* A, const T* A_frag, const T* v,
                    const T* fbar, T* Kbar, T* Kbar_frag, T* Lbar, T* ubar, T* zbar, T* ellbar, T* xbar, long E, long n,
-                   long M, long d, long P, T* ws, hipStream_t stream) {
+                   long M, long d, long P, T* ws, hipStream_t stream, T* Abar_frag = nullptr) {
   HB_REQUIRE(prec == HB_PREC_NATIVE || prec == HB_PREC_BF16X3, "hb_sgp_bwd: unknown precision %d", prec);
   HB_REQUIRE(kind == HB_KERN_RBF, "hb_sgp_bwd: only the UnitRBF kernel is fused (kind=%d)", kind);
   HB_REQUIRE(mode == HB_SGP_NEGLECTED || mode == HB_SGP_DIAGONAL, "hb_sgp_bwd: unknown mode %d", mode);
@@ -3324,6 +3402,9 @@ static int sgp_bwd(int kind, int mode, const T* x, long sx, const T* z, const T*
   HB_REQUIRE(strip || (A && Kbar), "hb_sgp_bwd: row-major A and Kbar required outside the column-strip form");
   HB_REQUIRE(prec == HB_PREC_NATIVE || strip, "hb_sgp_bwd: bf16x3 needs the column-strip form (fp32, Wfrag, M %% 32 == 0, M <= %d, "
              "d <= %d, P <= 4, no xbar)", SGP_SM_MAX, SGP_DREG);
+  // hb_sgp_bwd_phi: Abar is exchanged instead of Kbar and `Lbar` receives Phisym(-Abar A^T)
+  HB_REQUIRE(!Abar_frag || (strip && A_frag && prec == HB_PREC_NATIVE),
+             "hb_sgp_bwd_phi: needs the column-strip form in native precision with a fragment-major A (see hb_sgp_bwd_phi_supported)");
   if (strip) {
     SgpBwdArgs<T> a;
     a.W = W; a.u = u; a.A = A; a.fbar = fbar; a.eps = eps; a.v = v; a.Kbar = Kbar;
@@ -3334,7 +3415,7 @@ static int sgp_bwd(int kind, int mode, const T* x, long sx, const T* z, const T*
                                    : nullptr;
     a.plane3 = E * M * M;
     a.part = mmws;   // consumed by the finish kernel before the Lbar contraction reuses the space
-    a.Af = A_frag; a.Kf = Kbar_frag;
+    a.Af = A_frag; a.Kf = Kbar_frag; a.Abf = Abar_frag;
     if (A_frag) a.Kbar = nullptr;   // Kbar only feeds the Lbar contraction: the fragment-major copy is enough
     int rc = sgp_bwd_strip_launch(a, E, nS, stream);
     if (rc) return rc;
@@ -3344,11 +3425,13 @@ static int sgp_bwd(int kind, int mode, const T* x, long sx, const T* z, const T*
       const long slab_cap = (mmws_elems - npart) / (E * M * M);
       HB_REQUIRE(slab_cap >= 1, "hb_sgp_bwd: workspace too small for the Lbar slabs");
       int S = 0;
-      rc = sgp_lbar_frag_launch(Kbar_frag, A_frag, mmws + npart, slab_cap > 32 ? 32 : slab_cap, E, M, nS, prec, &S, stream);
+      rc = sgp_lbar_frag_launch(Abar_frag ? Abar_frag : Kbar_frag, A_frag, mmws + npart, slab_cap > 32 ? 32 : slab_cap, E, M, nS, prec, &S, stream);
       if (rc) return rc;
       const int nbx = (int)hb_cdiv(M, 64), nb_strip = nbx * (int)(2 * d + P) * (int)E;
-      hipLaunchKernelGGL(sgp_bwd_finish_kernel<T>, dim3((unsigned)(nb_strip + hb_stream_grid(E * M * M, 256))), dim3(256), 0, stream,
-                         mmws, (int)nS, M, d, dl, P, zbar, ellbar, ubar, nb_strip, nbx, mmws + npart, S, E, Lbar);
+      const long nTl = M / 32, phi_units = E * nTl * (nTl + 1);   // (16 rows of a 32 x 32 lower tile each)
+      const long nb_fold = Abar_frag ? (phi_units < 2048 ? phi_units : 2048) : (long)hb_stream_grid(E * M * M, 256);
+      hipLaunchKernelGGL(sgp_bwd_finish_kernel<T>, dim3((unsigned)(nb_strip + nb_fold)), dim3(256), 0, stream,
+                         mmws, (int)nS, M, d, dl, P, zbar, ellbar, ubar, nb_strip, nbx, mmws + npart, S, E, Lbar, Abar_frag ? 1 : 0);
       HB_LAUNCH_CHECK();
       return 0;
     }
@@ -3364,7 +3447,7 @@ static int sgp_bwd(int kind, int mode, const T* x, long sx, const T* z, const T*
     a.W = W; a.u = u; a.A = A; a.fbar = fbar; a.eps = eps; a.v = v; a.Kbar = Kbar;
     a.n = n; a.M = M; a.P = P; a.mode = mode;
     a.x = nullptr; a.sx = 0; a.z = nullptr; a.ell = nullptr; a.dl = 0; a.d = d; a.WTf = nullptr; a.WT3 = nullptr;
-    a.plane3 = 0; a.part = nullptr; a.Af = nullptr; a.Kf = nullptr;
+    a.plane3 = 0; a.part = nullptr; a.Af = nullptr; a.Kf = nullptr; a.Abf = nullptr;
     const int nRB = hb_cdiv(M, SGP_BM);
     dim3 grid = sgp_grid(hb_cdiv(n, SGP_BN), sgp_grid_y(E, n, nRB), E, a.efast);
     constexpr long VECH = 16 / sizeof(T);
@@ -3432,4 +3515,26 @@ extern "C" int hb_sgp_bwd_f64(int kind, int mode, const double* x, long sx, cons
                               long E, long n, long M, long d, long P, double* ws, void* stream) {
   return sgp_bwd<double>(kind, mode, x, sx, z, ell, dl, W, Wfrag, prec, u, eps, A, A_frag, v, fbar, Kbar, Kbar_frag, Lbar,
                          ubar, zbar, ellbar, xbar, E, n, M, d, P, ws, (hipStream_t)stream);
+}
+
+// 1 when hb_sgp_bwd_phi_f32 serves this shape: the column-strip form in native precision (hb_sgp_strip_path) and the
+// diagnostic switch hb_debug_set("sgp_phi_direct", 0) not set.  The planner asks once, when it builds a plan.
+extern "C" int hb_sgp_bwd_phi_supported(long E, long n, long M, long d, long P) {
+  if (hb_debug_get("sgp_phi_direct", 1) == 0) return 0;
+  return hb_sgp_strip_path(E, n, M, d, P, HB_PREC_NATIVE);
+}
+
+// hb_sgp_bwd_f32 for the pipeline whose only reader of Lbar is the Cholesky VJP's first product, Phisym(L^T tril(Lbar)):
+// with Lbar = -tril(W^T Abar A^T) and L^T W^T = I that product is Phisym(-Abar A^T), so the strip kernel leaves the
+// fragment-major image of Abar (in Abar_frag, laid out like A_frag) where hb_sgp_bwd leaves Kbar's, the same contraction
+// kernels form Abar A^T, and the finish pass writes Phi -- both triangles -- instead of Lbar.  ubar, zbar and ellbar are
+// those of hb_sgp_bwd_f32, bit for bit.  fp32, column-strip form, native precision, fragment-major A only.
+extern "C" int hb_sgp_bwd_phi_f32(int kind, int mode, const float* x, long sx, const float* z, const float* ell, long dl,
+                                  const float* W, const float* Wfrag, const float* u, const float* eps, const float* A_frag,
+                                  const float* v, const float* fbar, float* Abar_frag, float* Phi, float* ubar, float* zbar,
+                                  float* ellbar, long E, long n, long M, long d, long P, float* ws, void* stream) {
+  HB_REQUIRE(Wfrag && A_frag && Abar_frag && Phi, "hb_sgp_bwd_phi: NULL pointer");
+  HB_REQUIRE(hb_sgp_strip_path(E, n, M, d, P, HB_PREC_NATIVE), "hb_sgp_bwd_phi: shape outside the column-strip form (see hb_sgp_strip_path)");
+  return sgp_bwd<float>(kind, mode, x, sx, z, ell, dl, W, Wfrag, HB_PREC_NATIVE, u, eps, nullptr, A_frag, v, fbar, nullptr,
+                        Abar_frag, Phi, ubar, zbar, ellbar, nullptr, E, n, M, d, P, ws, (hipStream_t)stream, Abar_frag);
 }

@@ -920,6 +920,8 @@ def matmul(a, b, transpose_a=False, transpose_b=False, bias=None, act="none") ->
 
 def _matmul_emit(plan, node):
     H = plan.H
+    if node.id in plan._phi_direct:
+        return  # Phisym(L^T Lbar) was written by the sparse-GP backward (_sgp_grad_emit)
     a, b = plan.buf(node.inputs[0]), plan.buf(node.inputs[1])
     bias = plan.buf(node.inputs[2]) if len(node.inputs) > 2 else None
     at = node.attrs
@@ -1096,8 +1098,8 @@ def add_eye(x, alpha):
 
 
 def _matutil_emit(plan, node):
-    if node.id in plan._fused_matutil:
-        return  # folded into the producing GEMM's epilogue
+    if node.id in plan._fused_matutil or node.id in plan._phi_direct:
+        return  # folded into the producing GEMM's epilogue (or, with it, into the sparse-GP backward)
     H = plan.H
     x, out = plan.buf(node.inputs[0]), plan.out(node.outputs[0])
     a = node.attrs
@@ -1859,11 +1861,77 @@ def _sgp_vjp(node, gs):
     return [xb, zb, lb, Lb, None, ub] + [None] * (len(node.inputs) - 6)
 
 
+PHI_DIRECT = "Cholesky VJP's first product folded into the sparse-GP backward (hb_sgp_bwd_phi)"
+
+
+def _phi_direct_match(plan, node, a_frag, prec, need_x):
+    """The Cholesky VJP's first product, P = Phisym(L^T tril(Lbar)), read off the graph behind sgp_grad `node`.
+
+    Lbar = -tril(W^T Abar A^T) and L^T W^T = I give P = Phisym(-Abar A^T) (Phisym reads the lower triangle only, and L^T
+    is upper triangular, so the tril in between drops out): when Lbar feeds nothing but that product, the backward can
+    write P itself (hb_sgp_bwd_phi_f32) and the product is not launched.  Returns ((Phisym node, ids of the nodes that
+    then emit nothing), None), or (None, why not).  The traced graph is left as it is."""
+    H = plan.H
+    if a_frag is None:
+        return None, "A is exchanged row-major (no column-strip form, or A / xbar is read elsewhere)"
+    if plan.dtype != plan.torch.float32 or prec != H.PREC_NATIVE or need_x:
+        return None, "needs fp32 operands in native precision"
+    Lb, skipped = node.outputs[0], []
+
+    def private(t):
+        return len(plan._consumers.get(t, [])) == 1 and t not in plan.outputs and t not in plan._bind
+
+    if not private(Lb):
+        return None, "Lbar is a plan output, or has a reader besides the Cholesky VJP's product"
+    c = plan._consumers[Lb][0]
+    t = Lb
+    if c.op == "matutil" and c.attrs["mode"] == 0 and c.attrs["lower"] < 0 and c.attrs["upper"] == 0:   # band_part(-1, 0)
+        t = c.outputs[0]
+        if not private(t):
+            return None, "tril(Lbar) is a plan output, or has a second reader"
+        skipped.append(c.id)
+        c = plan._consumers[t][0]
+    at = c.attrs
+    if not (c.op == "matmul" and len(c.inputs) == 2 and c.inputs[1] is t and c.inputs[0] is not t and at["ta"] and not at["tb"]
+            and at["act"] == "none" and not at.get("actgrad")):
+        return None, "Lbar does not feed the product L^T tril(Lbar)"
+    L, Q = c.inputs[0], c.outputs[0]
+    Wsrc, fwd = _through_stop_gradient(node.inputs[3]), node.inputs[6].node
+    if not (Wsrc.node.op == "trinv" and Wsrc.node.inputs[0] is L and fwd.op == "sgp" and fwd.inputs[3] is L
+            and _through_stop_gradient(fwd.inputs[4]) is Wsrc):
+        return None, "the product's left operand is not the factor L whose inverse whitened the draw"
+    if not private(Q) or c.id in plan._colsum_of or c.id in getattr(plan, "_mm_head", {}):
+        return None, "L^T tril(Lbar) is a plan output, or has a reader besides Phisym"
+    mu = plan._consumers[Q][0]
+    if not (mu.op == "matutil" and mu.attrs["mode"] == 4):
+        return None, "L^T tril(Lbar) is not followed by Phisym (matutil mode 4)"
+    zsh, xsh = node.inputs[1].shape, node.inputs[0].shape
+    E, M, n, d, P = int(np.prod(zsh[:-2])) if len(zsh) > 2 else 1, zsh[-2], xsh[-2], xsh[-1], node.inputs[4].shape[-2]
+    if not H.sgp_bwd_phi_supported(E, n, M, d, P):
+        return None, "shape outside the column-strip form, or switched off (hb_debug_set sgp_phi_direct 0)"
+    return (mu, skipped + [c.id, mu.id]), None
+
+
 def _sgp_grad_emit(plan, node):
     H = plan.H
     x, z, ell, W, u, eps, A, v, gf = (plan.buf(t) for t in node.inputs)
-    Lb, ub, zb, lb, xb = (plan.out(t) for t in node.outputs)
     mode = SGP_MODES[node.attrs["mode"]]
+    if plan.needed(node.outputs[0]):
+        a_frag, fprec = plan._afrag.get(node.inputs[6], (None, None))
+        hit, why = _phi_direct_match(plan, node, a_frag, fprec, plan.needed(node.outputs[4]))
+        plan.note(PHI_DIRECT, node, hit is not None, why or "")
+        if hit is not None:
+            # the backward writes Phisym(-Abar A^T) into the Phisym node's buffer: tril, product and Phisym emit nothing, and
+            # Lbar itself is never formed
+            mu, skipped = hit
+            plan._phi_direct.update(skipped)
+            wfrag = plan._wfrag[_through_stop_gradient(node.inputs[3])][0]
+            outs = (plan.out(mu.outputs[0]),) + tuple(plan.out(t) for t in node.outputs[1:4])
+            abar_frag = plan.scratch((a_frag.numel(),))
+            plan.steps.append(lambda: H.sgp_bwd_phi(x, z, ell, W, u, eps, v, gf, wfrag, a_frag, mode=mode, out=outs,
+                                                    abar_frag=abar_frag))
+            return
+    Lb, ub, zb, lb, xb = (plan.out(t) for t in node.outputs)
     need_x = plan.needed(node.outputs[4])
     if need_x and len(node.inputs[1].shape) > 2 and len(node.inputs[0].shape) == 2:
         raise NotImplementedError("gradient w.r.t. an x shared by several experts")
@@ -2438,6 +2506,7 @@ class Plan:
         self._wfrag: Dict[Tensor, object] = {}   # W tensor -> fragment-major copies written by the fused factorisation
         self._afrag: Dict[Tensor, object] = {}   # A tensor of an sgp op -> its fragment-major copy (read by sgp_grad)
         self._fused_matutil = set()
+        self._phi_direct = set()    # ids of the tril / product / Phisym nodes whose result the sparse-GP backward writes
         self._fused_concat = set()
         self._lazy_cols: Dict[Tensor, object] = {}
         for t, b in (binds or []):

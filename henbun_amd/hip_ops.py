@@ -1509,6 +1509,32 @@ def sgp_bwd(x, z, ell, W, u, eps, A, v, fbar, mode=SGP_DIAGONAL, need_xbar=False
     return Lbar, ubar, zbar, ellbar, xbar
 
 
+def sgp_bwd_phi_supported(E, n, M, d, P):
+    """True when sgp_bwd_phi serves this shape (column-strip form in native precision) and the diagnostic switch
+    sgp_phi_direct is not 0.  The planner asks when it builds a plan."""
+    return bool(_lib.lib().raw("hb_sgp_bwd_phi_supported")(E, n, M, d, P))
+
+
+def sgp_bwd_phi(x, z, ell, W, u, eps, v, fbar, wfrag, a_frag, mode=SGP_DIAGONAL, out=None, abar_frag=None):
+    """sgp_bwd whose first result is the Cholesky VJP's operand Phi = Phisym(-Abar A^T) (= Phisym(L^T Lbar), both
+    triangles) instead of Lbar: hb_sgp_bwd_phi_f32.  fp32, fragment-major W and A.  Returns (Phi, ubar, zbar, ellbar)."""
+    E, n, M, d, P, sx = _sgp_dims(x, z, u)
+    dev, dt = x.device, x.dtype
+    assert dt == torch.float32 and wfrag is not None and a_frag is not None
+    dl = ell.numel() // E
+    if out is None:
+        Phi, ubar, zbar, ellbar = _empty_like(W), _empty_like(u), _empty_like(z), _empty_like(ell)
+    else:
+        Phi, ubar, zbar, ellbar = out
+    ws = workspace(dt, dev, _lib.lib().raw("hb_sgp_ws_elems")(E, n, M, d, P))
+    if abar_frag is None:
+        abar_frag = _empty(a_frag.numel(), dtype=dt, device=dev)
+    assert abar_frag.numel() >= sgp_frag_elems(E, n, M)
+    _lib.lib().call("hb_sgp_bwd_phi_f32", KERN_RBF, mode, _p(x), sx, _p(z), _p(ell), dl, _p(W), _p(wfrag), _p(u), _p(eps), _p(a_frag),
+                    _p(v), _p(fbar), _p(abar_frag), _p(Phi), _p(ubar), _p(zbar), _p(ellbar), E, n, M, d, P, _p(ws), stream())
+    return Phi, ubar, zbar, ellbar
+
+
 # ---- K9 Adam ---------------------------------------------------------------------
 def adam_step(theta, g, m, v, t, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8, gscale=1.0, tick=True, info=None, dpflag=None,
               fail=None):

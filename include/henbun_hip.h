@@ -53,7 +53,9 @@ extern "C" {
  * non-Gaussian likelihoods); hb_sgp_wkgrad_f32 / _f64 (streamed part of the gradient of the ELBO at a fixed q(u));
  * hb_sgp_pathwise_f32 / _f64 (pathwise posterior function draws, linear in n); hb_gram_matvec_f32 / _f64 and hb_pcg_*
  * (matrix-free kernel product and the vector steps of lockstep preconditioned conjugate gradients: exact GP regression);
- * hb_gram_bilinear_grad_f32 / _f64 and hb_pcg_*_coef (the exact GP's log marginal likelihood and its gradient). */
+ * hb_gram_bilinear_grad_f32 / _f64 and hb_pcg_*_coef (the exact GP's log marginal likelihood and its gradient);
+ * hb_sgp_bwd_phi_f32 and hb_sgp_bwd_phi_supported (the sparse-GP backward that writes the Cholesky VJP's operand
+ * Phisym(-Abar A^T) where hb_sgp_bwd_f32 writes Lbar). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -66,7 +68,8 @@ const char* hb_last_error_string(void);
  * lbar_force_s, lbar_no_lds, sgp_stats_no_A, sgp_stats_no_syrk (hb_sgp_stats_* without its first / second pass: timing
  * only, the outputs are then meaningless), sgp_stats_target_wg (tiles x K-splits aimed at; hb_sgp_stats_ws_elems follows), sgp_select_block (64 / 256: the workgroup
  * size of hb_sgp_select_*; the results do not depend on it), sgp_kgrad_plain (hb_sgp_kgrad_* in its plain-loop form for
- * every shape).  hb_debug_clear() drops every entry. */
+ * every shape), sgp_phi_direct (0: hb_sgp_bwd_phi_supported answers 0, so a plan built then keeps hb_sgp_bwd and the
+ * Cholesky VJP's first product).  hb_debug_clear() drops every entry. */
 int hb_debug_set(const char* key, long value);
 int hb_debug_clear(void);
 /* device name / arch of the current device into (host) buf; returns 0 or hipError */
@@ -830,6 +833,19 @@ int hb_sgp_bwd_f32(int kind, int mode, const float* x, long sx, const float* z, 
                    const float* A, const float* A_frag, const float* v, const float* fbar, float* Kbar,
                    float* Kbar_frag, float* Lbar, float* ubar, float* zbar, float* ellbar, float* xbar,
                    long E, long n, long M, long d, long P, float* ws, void* stream);
+/* hb_sgp_bwd_f32 for a caller whose only use of Lbar is the Cholesky VJP's first product Phisym(L^T tril(Lbar))
+ * (Phisym(Q)_ij = Q_{max(i,j),min(i,j)} / 2, hb_matutil mode 4): with W = L^-1 that product equals Phisym(-Abar A^T),
+ * Abar = u^T fbar + A diag(c), so W^T never multiplies the M x M result and L^T never multiplies it back.
+ *   Phi [E,M,M] (both triangles written) replaces Lbar; Abar_frag (E*M*32*ceil(n/32) elements, the layout of A_frag)
+ *   is scratch: the strip kernel leaves Abar there, where hb_sgp_bwd_f32 leaves Kbar in Kbar_frag.
+ * ubar, zbar and ellbar are those of hb_sgp_bwd_f32, bit for bit.  fp32, native precision, fragment-major A only, and
+ * only where hb_sgp_bwd_phi_supported(...) == 1: hb_sgp_strip_path for HB_PREC_NATIVE, and the diagnostic switch
+ * sgp_phi_direct not set to 0 (the switch is read by _supported alone: ask once, when the call sequence is planned). */
+int hb_sgp_bwd_phi_supported(long E, long n, long M, long d, long P);
+int hb_sgp_bwd_phi_f32(int kind, int mode, const float* x, long sx, const float* z, const float* ell, long dl,
+                       const float* W, const float* Wfrag, const float* u, const float* eps, const float* A_frag,
+                       const float* v, const float* fbar, float* Abar_frag, float* Phi, float* ubar, float* zbar,
+                       float* ellbar, long E, long n, long M, long d, long P, float* ws, void* stream);
 int hb_sgp_bwd_f64(int kind, int mode, const double* x, long sx, const double* z, const double* ell,
                    long dl, const double* W, const double* Wfrag, int prec, const double* u,
                    const double* eps, const double* A, const double* A_frag, const double* v,
