@@ -1,3 +1,4 @@
 from . import kernels
 from .exact import ExactPosterior, NotConverged, Preconditioner, log_marginal_likelihood, pcg_solve
-from .gp import GP, PathwiseDraws, SparseGP, greedy_inducing
+from .gp import GP, SparseGP
+from .sparse import PathwiseDraws, greedy_inducing

@@ -21,6 +21,9 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _host
+from .sparse import PathwiseDraws
+
 
 class NotConverged(RuntimeError):
     """pcg_solve did not reach its tolerance within max_iter; `info` is the dict a converged solve returns."""
@@ -49,10 +52,7 @@ class Preconditioner:
         G = H.matmul_ld(self.C, self.ld, self.C, self.ld, torch.empty((R, R), dtype=Xd.dtype, device=Xd.device), R, R, N,
                         transB=True, alpha=self.k_var)
         G = H.matutil(G.to(torch.float64), H.MATUTIL_ADD_EYE, alpha=self.noise_var)
-        L, info = H.cholesky(G)
-        if int(info.cpu()[0]) != 0:
-            raise RuntimeError("Preconditioner: noise_var I + k_var C C^T is not positive definite at rank %d" % R)
-        self.Linv = H.trinv(L)
+        self.Linv = H.trinv(_host.factor(H, G, "Preconditioner", "noise_var I + k_var C C^T (rank %d)" % R, RuntimeError))
 
     def apply(self, r, out):
         """out [S, N] = C^T (noise_var I + k_var C C^T)^-1 C r for the rows of r [S, N]."""
@@ -258,7 +258,7 @@ def log_marginal_likelihood(sess, Xd, Yt, ell, k_var, noise_var, precond, tol, m
     else:
         if np.ndim(probes) != 2 or np.shape(probes)[1] != N or np.shape(probes)[0] < 1:
             raise ValueError("log_marginal_likelihood: probes must be [T, %d] (got %s)" % (N, np.shape(probes)))
-        Z = torch.as_tensor(np.ascontiguousarray(probes, dtype=sess.np_dtype)).to(dev)
+        Z = _host.upload(sess, probes)
         T = Z.shape[0]
     rows = torch.cat([Yt, Z]).contiguous()
     S = P + T
@@ -304,8 +304,8 @@ class ExactPosterior:
     [N, d], the lengthscales, k_var, noise_var, alpha = K^^-1 Y [P, N], the preconditioner and the solve's `info`, on the
     device in the session's dtype.  Later changes to the model do not move it."""
 
-    def __init__(self, sess, device_data, X, Y, ell, k_var, noise_var, alpha, precond, info, tol, max_iter):
-        self._sess, self._device_data = sess, device_data
+    def __init__(self, sess, X, Y, ell, k_var, noise_var, alpha, precond, info, tol, max_iter):
+        self._sess = sess
         self._X, self._Y, self._ell, self._alpha, self._precond = X, Y, ell, alpha, precond
         self.k_var, self.noise_var, self.info = float(k_var), float(noise_var), info
         self.tol, self.max_iter = tol, int(max_iter)
@@ -316,7 +316,7 @@ class ExactPosterior:
         return pcg_solve(self._sess, self._X, self._ell, self.k_var, self.noise_var, B, self._precond, self.tol, self.max_iter)
 
     def _new_points(self, Xnew):
-        Xn = self._device_data(self._sess, Xnew, "Xnew")
+        Xn = _host.device_data(self._sess, Xnew, "Xnew")
         if Xn.shape[1] != self._X.shape[1]:
             raise ValueError("ExactPosterior: Xnew %s does not match X %s" % (tuple(Xn.shape), tuple(self._X.shape)))
         return Xn
@@ -356,8 +356,6 @@ class ExactPosterior:
         g_s(X) is hb_sgp_pathwise with M = 0; the v_s come from lockstep solves in blocks of 64 draws; evaluation is the
         unchanged hb_sgp_pathwise, O((N + L) n) per draw.  noise=None draws omega [L, d], w [S, 2L], eps [S, N] from
         hip_ops.Rng(seed), in that order; noise=dict(omega=, w=, eps=) injects them.  One output column (P = 1) only."""
-        from .gp import PathwiseDraws
-
         sess = self._sess
         torch, H = sess.torch, sess.H
         S, L = int(num_samples), int(num_features)
@@ -368,16 +366,7 @@ class ExactPosterior:
             raise NotImplementedError("sample_functions: one latent function only (Y has %d columns)" % self._Y.shape[0])
         N, d = self._X.shape
         dt = sess.torch_dtype
-        if noise is None:
-            rng = H.Rng(seed, device=sess.device)
-            omega, w, eps = (rng.normal(shape, dtype=dt) for shape in ((L, d), (S, 2 * L), (S, N)))
-        else:
-            want = dict(omega=(L, d), w=(S, 2 * L), eps=(S, N))
-            if not isinstance(noise, dict) or set(noise) != set(want) or any(np.shape(noise[k]) != want[k] for k in want):
-                raise ValueError("sample_functions: noise must be dict(omega=%s, w=%s, eps=%s)"
-                                 % (want["omega"], want["w"], want["eps"]))
-            up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=sess.np_dtype)).to(sess.device)
-            omega, w, eps = (up(noise[k]) for k in ("omega", "w", "eps"))
+        omega, w, eps = _host.pathwise_noise(sess, "sample_functions", noise, seed, ((L, d), (S, 2 * L), (S, N)))
         cw = H.ewise("AFFINE", [w], params=(1.0 / np.sqrt(L), 0.0))
         sk = float(np.sqrt(self.k_var))
         prior = H.sgp_pathwise(self._X, omega, None, self._ell, cw, scale=sk)                           # [S, N]
@@ -387,4 +376,4 @@ class ExactPosterior:
             sol, _ = self._solve(rhs[a:a + 64].contiguous())
             H.ewise("AFFINE", [sol], params=(sk, 0.0), out=V[a:a + 64])
         coef = torch.cat([cw, V], dim=1).contiguous()
-        return PathwiseDraws(sess, self._device_data, omega, coef, self._X, self._ell, sk)
+        return PathwiseDraws(sess, omega, coef, self._X, self._ell, sk)

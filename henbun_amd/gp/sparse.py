@@ -1,0 +1,569 @@
+"""The direct (eager, non-graph) inference routes of SparseGP: closed-form q(u) and collapsed bound (Titsias 2009), their
+float64 gradients, the natural-gradient fit for non-Gaussian likelihoods, greedy inducing-point selection and pathwise
+function draws.  None of it is in the reference.  gp.py traces graphs; this module and exact.py call hip_ops on device
+tensors as they go, and _host.py holds the host steps both share.  `SparseInference` is mixed into gp.SparseGP, which
+owns every public method below.
+"""
+import numpy as np
+
+from .. import graph as G
+from .._settings import settings
+from ..likelihoods import Likelihood
+from ..param import Data
+from ..variationals import Gaussian
+from . import _host
+
+
+def _check_residual(residual):
+    if residual == "fullrank":
+        raise NotImplementedError("the closed-form posterior is implemented for residual 'diagonal' and 'neglected' "
+                                  "(the 'fullrank' residual couples the data points)")
+    if residual not in ("diagonal", "neglected"):
+        raise ValueError("residual must be 'diagonal' or 'neglected', got %r" % (residual,))
+
+
+def _check_lik_inputs(who, likelihood, k_var, residual, q, Yd, M):
+    """The argument checks natgrad_q and elbo_and_grad share: residual, a henbun_amd.likelihoods.Likelihood (TypeError),
+    k_var > 0, Y [N, 1] and q = (m [1, M], S [M, M]) or None.  Returns (m, S) as float64 numpy, or None."""
+    _check_residual(residual)
+    if not isinstance(likelihood, Likelihood):
+        raise TypeError("%s: likelihood must be a henbun_amd.likelihoods.Likelihood, got %s" % (who, type(likelihood).__name__))
+    if not float(k_var) > 0.0:
+        raise ValueError("%s: k_var must be positive (got %r)" % (who, k_var))
+    if Yd.shape[1] != 1:
+        raise NotImplementedError("%s: one latent function only (Y must be [N, 1], got %s)" % (who, tuple(Yd.shape)))
+    if q is None:
+        return None
+    m0, S0 = (np.asarray(a, dtype=np.float64) for a in q)
+    if S0.ndim != 2:
+        raise NotImplementedError("%s: q must be a full-rank q, (m [1, M], S [M, M]); a mean-field q is not covered" % who)
+    if m0.size != M or S0.shape != (M, M):
+        raise ValueError("%s: q = (m [1, %d], S [%d, %d]) expected, got %s %s" % (who, M, M, M, m0.shape, S0.shape))
+    return m0, S0
+
+
+def _q_tail(H, Lam, c, who, of="Lambda"):
+    """(L, V, t), the float64 tail every route shares: Lambda = L L^T (one read-back), V = L^-1, t = c V^T [P, M]; the
+    mean is m = t V.  (m and Sigma are separate steps: a route that needs neither launches neither.)"""
+    L = _host.factor(H, Lam.contiguous(), who, of)
+    V = H.trinv(L)
+    return L, V, H.matmul(c.contiguous(), V, transB=True)
+
+
+def _q_cov(H, V, who):
+    """(Sigma, S) on top of _q_tail: Sigma = Lambda^-1 = V^T V and its lower factor S (one more read-back)."""
+    Sig = H.matmul(V, V, transA=True)
+    return Sig, _host.factor(H, Sig, who, "Lambda^-1")
+
+
+def _walk_f64(torch, Xd, Yd, M, align, per_chunk):
+    """The float64 walk over the data: row chunks of Xd, Yd (f64_chunk_rows(M, align) rows) are up-converted to double
+    and handed to per_chunk(c0, Xc, Yc), whose tuples are added entry by entry in chunk order."""
+    chunk = _host.f64_chunk_rows(M, align)
+    total = None
+    for c0 in range(0, Xd.shape[0], chunk):
+        Xc = Xd[c0:c0 + chunk].to(torch.float64).contiguous()
+        Yc = Yd[c0:c0 + chunk].to(torch.float64).contiguous()
+        parts = per_chunk(c0, Xc, Yc)
+        total = parts if total is None else tuple(a + b for a, b in zip(total, parts))
+    return total
+
+
+class SparseInference:
+    """The eager methods of gp.SparseGP, a mixin: it reads the `kern` and `z` a SparseGP holds."""
+
+    # -- closed-form posterior (Titsias 2009; the whitened model of models.SVGP) ------------------------------------
+    def _stats_session(self, who):
+        zvar = object.__getattribute__(self, "z")
+        if len(zvar.shape) != 2:
+            raise NotImplementedError("%s: one expert only (z must be [M, d], got %s)" % (who, tuple(zvar.shape)))
+        sess, _, ls = _host.rbf_model_inputs(self, who)
+        return sess, zvar, ls
+
+    def statistics(self, X, Y):
+        """(Phi [M, M], b [P, M], yy [P], a2sum [1]) of the whole data set X [N, d], Y [N, P] for the current z,
+        lengthscales and settings.numerics.jitter_level, as float64 device tensors (hb_sgp_stats: one streaming pass):
+        Phi = A A^T, b = (A Y)^T, yy_p = sum_j Y_jp^2, a2sum = tr Phi, A = Lm^-1 K(z, X), Lm = chol(K(z, z) + jitter I)
+        from the fused factor + inverse the plans use.  A failed factorisation raises graph.CholeskyError."""
+        sess, zvar, ls = self._stats_session("statistics")
+        Xd, Yd = _host.device_data(sess, X, "X"), _host.device_data(sess, Y, "Y")
+        z, ell, W, frag = self._whitening(sess, zvar, ls, Xd, Yd, "statistics")
+        return sess.H.sgp_stats(Xd, Yd, z, ell, W, wfrag=frag)
+
+    def _whitening(self, sess, zvar, ls, Xd, Yd, who, as_plans=False):
+        """(z, ell, W, frag) on the device in the session's dtype: W = chol(K(z, z) + jitter I)^-1 from the fused factor
+        + inverse the plans use, frag its fragment-major images (float32, M % 32 == 0; else None).
+        z and the lengthscales are their transforms of the raw parameters taken on the host in double and rounded;
+        as_plans=True takes them from a plan instead, i.e. as the session's dtype transforms them on the device -- the
+        values predict_f and the ELBO see.  In a float32 session the two can differ in the last bit of a lengthscale,
+        which moves W by cond(K(z, z)) times that; a q(u) that a plan reads must be fitted in the plan's whitening
+        ("Natural-gradient fit")."""
+        torch, H = sess.torch, sess.H
+        if as_plans:
+            sess.read_value(zvar), sess.read_value(ls)      # uploads a value that was assigned and not yet written
+            cache = object.__getattribute__(self, "__dict__").setdefault("_whitening_plans", {})
+            key = (id(sess), sess.layout_version, id(zvar), id(ls))
+            if key not in cache:
+                zt, et = zvar.tensor(), G.reshape(ls.tensor(), [-1])
+                cache.clear()
+                cache[key] = (sess.make_plan([zt, et]), zt, et)
+            plan, zt, et = cache[key]
+            plan.run()
+            z, ell = plan.buf(zt).clone().contiguous(), plan.buf(et).clone().contiguous()
+        else:
+            z, ell = _host.upload(sess, sess.read_value(zvar)), _host.lengthscales(sess, ls)
+        if Xd is not None and (Xd.shape[0] != Yd.shape[0] or Xd.shape[1] != z.shape[1]):   # (pathwise_draws has no data)
+            raise ValueError("%s: X %s, Y %s do not match z %s" % (who, tuple(Xd.shape), tuple(Yd.shape), tuple(z.shape)))
+        M = z.shape[0]
+        K = H.gram_fwd(z, z, ell, diag_add=float(settings.numerics.jitter_level))
+        frag = None
+        if sess.torch_dtype == torch.float32 and M % 32 == 0:
+            frag = torch.empty(2 * M * M, dtype=sess.torch_dtype, device=sess.device)
+        _, W, info = H.cholesky_inverse(K, frag=frag)
+        _host.check_info(info, who, "K(z, z) + jitter I")
+        return z, ell, W, frag
+
+    def select_inducing(self, X, threshold=None):
+        """Move z to the M = z.shape[0] rows of X [N, d] that greedy conditional-variance selection picks at the CURRENT
+        lengthscales (hb_sgp_select; see greedy_inducing), in selection order, and return their row indices as numpy
+        int64 [M].  X: a Data / MinibatchData of the model (read in full from its device buffer), a device tensor or an
+        array.  threshold=None: settings.numerics.jitter_level.  Same restrictions and exception types as statistics():
+        UnitRBF, one expert, the lengthscales one Variable.  If fewer than M points have a conditional variance above
+        the threshold, ValueError is raised and z is left untouched.  q(u) is not touched: the optimum for the new z is
+        one optimal_q / fit_q away."""
+        sess, zvar, ls = self._stats_session("select_inducing")
+        Xd = _host.device_data(sess, X, "X")
+        M, d = int(zvar.shape[0]), int(zvar.shape[1])
+        if Xd.shape[1] != d:
+            raise ValueError("select_inducing: X %s does not match z %s" % (tuple(Xd.shape), tuple(zvar.shape)))
+        if M > Xd.shape[0]:
+            raise ValueError("select_inducing: z holds %d points, X only %d rows" % (M, Xd.shape[0]))
+        thr = float(settings.numerics.jitter_level if threshold is None else threshold)
+        idx, _, count, _ = sess.H.sgp_select(Xd, _host.lengthscales(sess, ls), M, thr)
+        count = int(count.cpu()[0])
+        if count < M:
+            raise ValueError("select_inducing: only %d of the %d points asked for have a conditional variance above the "
+                             "threshold %g; z is unchanged (use fewer inducing points or a lower threshold)"
+                             % (count, M, thr))
+        Z = Xd[idx].cpu().numpy()
+        sess.write_raw(zvar, zvar.transform.backward(Z.astype(np.float64)))
+        return idx.cpu().numpy()
+
+    def _lambda_solve(self, stats, noise_var, k_var):
+        """(Lam, L, V, t, c): Lambda = I + (k_var / noise_var) Phi = L L^T, V = L^-1, c = sqrt(k_var) b / noise_var [P, M],
+        t = c V^T [P, M] (so |t_p|^2 = c_p^T Lambda^-1 c_p and t V = Lambda^-1 c), float64 on the device."""
+        H = self.highest_parent._session.H
+        Phi, b = stats[0], stats[1]
+        noise_var, k_var = float(noise_var), float(k_var)
+        if not (noise_var > 0.0 and k_var > 0.0):
+            raise ValueError("noise_var and k_var must be positive (got %r, %r)" % (noise_var, k_var))
+        Lam = H.matutil((Phi * (k_var / noise_var)).contiguous(), H.MATUTIL_ADD_EYE, alpha=1.0)
+        c = (b * (np.sqrt(k_var) / noise_var)).contiguous()
+        return (Lam,) + _q_tail(H, Lam, c, "optimal_q", "Lambda = I + (k_var / noise_var) Phi") + (c,)
+
+    def optimal_q(self, X, Y, noise_var, k_var=1.0, q_shape="fullrank", residual="diagonal", stats=None):
+        """The optimum of the ELBO over q(u_p) = N(m_p, S S^T) at fixed hyper-parameters, for the whitened model
+        u_p ~ N(0, I), f_p = sqrt(k_var) (u_p A + residual), Y_p ~ N(f_p, noise_var):
+            Lambda = I + (k_var / noise_var) Phi,  c_p = sqrt(k_var) b_p / noise_var,  m_p = Lambda^-1 c_p,
+        q_shape 'fullrank': S = chol(Lambda^-1), lower-triangular [M, M] with a positive diagonal, the same for every p;
+        'diagonal': s = diag(Lambda)^-1/2 [M], the optimum of the mean-field family (the mean is the same).
+        Returns (m [P, M], S or s) as float64 numpy.  `residual` ('diagonal' / 'neglected') does not change q*: that
+        term of the ELBO does not depend on q.  The M^3 tail runs on the device in float64 (hb_cholesky, hb_trinv,
+        hb_matmul).  `stats`: the tuple statistics(X, Y) returned, to share one pass between calls."""
+        _check_residual(residual)
+        if q_shape not in ("fullrank", "diagonal"):
+            raise ValueError("q_shape must be 'fullrank' or 'diagonal', got %r" % (q_shape,))
+        if stats is None:
+            stats = self.statistics(X, Y)
+        H = self.highest_parent._session.H
+        Lam, _, V, t, _ = self._lambda_solve(stats, noise_var, k_var)
+        m = H.matmul(t, V).cpu().numpy()
+        if q_shape == "diagonal":
+            return m, 1.0 / np.sqrt(np.diagonal(Lam.cpu().numpy()).copy())
+        return m, np.tril(_q_cov(H, V, "optimal_q")[1].cpu().numpy())
+
+    def collapsed_bound(self, X, Y, noise_var, k_var=1.0, residual="diagonal", stats=None):
+        """The ELBO at the optimal q(u) of optimal_q (the collapsed bound), a float:
+            sum_p [ -N/2 log(2 pi noise_var) - yy_p / (2 noise_var) + 1/2 c_p^T Lambda^-1 c_p ] - P/2 log|Lambda|
+            - P k_var (N - a2sum) / (2 noise_var)          ('diagonal'; 'neglected' drops the last term).
+        N - a2sum is sum_j (kdiag_j - sum_m A_mj^2) for the unit-variance kernel.  samples() takes the absolute value of
+        that difference per point, so the two agree except where round-off makes a term negative."""
+        _check_residual(residual)
+        if stats is None:
+            stats = self.statistics(X, Y)
+        _, L, _, t, _ = self._lambda_solve(stats, noise_var, k_var)
+        yy, a2sum = stats[2].cpu().numpy(), float(stats[3].cpu()[0])
+        # N from X's shape, not through device_data: that would upload a host array only to count its rows
+        N = int(self.highest_parent._session.data_buffer(X).shape[0] if isinstance(X, Data) else np.shape(X)[0])
+        quad = (t.cpu().numpy() ** 2).sum(-1)                                  # [P]
+        logdet = 2.0 * float(np.log(np.diagonal(L.cpu().numpy())).sum())
+        return _host.collapsed_value(N, yy.shape[0], noise_var, k_var, yy, quad, logdet, a2sum, residual)
+
+    def natgrad_q(self, X, Y, likelihood, k_var=1.0, residual="diagonal", q0=None, steps=20, rho=1.0, tol=1e-8):
+        """Natural-gradient fit of q(u) = N(m, S S^T) for a factorising likelihood (henbun_amd.likelihoods: Gaussian,
+        Bernoulli, Poisson) at fixed hyper-parameters, for the whitened model u ~ N(0, I), f = sqrt(k_var) (u A +
+        residual), y_j ~ p(y_j | f_j).  q is kept as Lambda = (S S^T)^-1, eta = Lambda m; one step is the conjugate
+        update with per-point pseudo-observations (conjugate-computation VI, Khan & Lin 2017):
+            mu_j, v_j            the marginals of f_j under q                         (hb_sgp_predict, one pass over X)
+            lam_j, beta_j, l_j   E[-d2 log p], E[d log p] + lam_j mu_j, E[log p]      (hb_lik_sites)
+            Phi = A diag(lam) A^T,  b = A beta                                        (hb_sgp_wstats, one pass over X)
+            Lambda <- (1 - rho) Lambda + rho (I + k_var Phi),   eta <- (1 - rho) eta + rho sqrt(k_var) b
+        and m = Lambda^-1 eta, S = chol(Lambda^-1) from the float64 tail of optimal_q.  With the Gaussian likelihood one
+        step at rho = 1 is optimal_q.  K(z, z) is factorised once per call, from z and the lengthscales as the session's
+        plans transform them on the device, so the q(u) returned lives in the whitening predict_f and the ELBO use.
+        Returns (m [1, M], S [M, M] lower with a positive diagonal, info) as float64 numpy; info = dict(elbo, residual,
+        steps): the ELBO sum_j l_j - KL(q || N(0, I)) and the fixed-point residual max|Lambda - (I + k_var Phi)| /
+        max|I + k_var Phi| at every iterate, the starting one included (steps + 1 entries), and the steps taken.  m, S
+        are the last iterate evaluated.  q0=None starts at the prior; q0 = (m, S) at a given full-rank q.  Stops when
+        the relative change of the ELBO is <= tol, or after `steps`.  X, Y as for statistics(), Y [N, 1].  Same
+        restrictions and exception types as statistics(); residual 'fullrank' and a mean-field q0 raise
+        NotImplementedError; a Lambda that is not positive definite raises graph.CholeskyError.  A full step (rho = 1)
+        is not guaranteed to raise the ELBO from a q far from the optimum (info['elbo'] shows an overshoot): start at
+        the prior or damp with rho < 1."""
+        sess, zvar, ls = self._stats_session("natgrad_q")
+        torch, H = sess.torch, sess.H
+        Xd, Yd = _host.device_data(sess, X, "X"), _host.device_data(sess, Y, "Y")
+        M = int(zvar.shape[0])
+        q0 = _check_lik_inputs("natgrad_q", likelihood, k_var, residual, q0, Yd, M)
+        k_var, rho, steps = float(k_var), float(rho), int(steps)
+        if not (0.0 < rho <= 1.0 and steps >= 0):
+            raise ValueError("natgrad_q: 0 < rho <= 1 and steps >= 0 expected (got %r, %r)" % (rho, steps))
+        z, ell, W, frag = self._whitening(sess, zvar, ls, Xd, Yd, "natgrad_q", as_plans=True)
+        N, d = Xd.shape
+        f64 = dict(dtype=torch.float64, device=sess.device)
+        if q0 is None:
+            Lam, eta = torch.eye(M, **f64), torch.zeros((1, M), **f64)
+        else:
+            Sinv = H.trinv(_host.upload(sess, np.tril(q0[1]), np.float64))
+            Lam = H.matmul(Sinv, Sinv, transA=True)
+            eta = H.matmul(_host.upload(sess, q0[0].reshape(1, M), np.float64), Lam)
+        mode = H.SGP_DIAGONAL if residual == "diagonal" else H.SGP_NEGLECTED
+        fused = bool(getattr(settings.runtime, "fused_predict", True)) and H.sgp_predict_fused(
+            sess.torch_dtype, 1, N, M, d, 1, H.SGP_S_TRIL, frag is not None)
+        mean = torch.empty((1, N), dtype=sess.torch_dtype, device=sess.device)
+        var, lam, beta = (torch.empty_like(mean) for _ in range(3))
+        eye = torch.eye(M, **f64)
+        elbo, resid = [], []
+        for it in range(steps + 1):
+            who = "natgrad_q (step %d)" % it
+            L, V, t = _q_tail(H, Lam, eta, who)
+            m = H.matmul(t, V)
+            Sig, S = _q_cov(H, V, who)
+            H.sgp_predict(Xd, z, ell, W, m.to(sess.torch_dtype), S.to(sess.torch_dtype), s_kind=H.SGP_S_TRIL, mode=mode,
+                          out=(mean, var), wfrag=frag if fused else None)
+            _, _, lsum = H.lik_sites(likelihood.lik_id, Yd, mean, var, param=likelihood.param, mscale=np.sqrt(k_var),
+                                     vscale=k_var, out=(lam, beta))
+            Phi, b, _ = H.sgp_wstats(Xd, lam, beta, z, ell, W, wfrag=frag)
+            Lt, et = Phi * k_var + eye, b * np.sqrt(k_var)
+            # KL(q || N(0, I)) from Sigma and the factor of Lambda.  elbo_and_grad forms it from S instead: equal in
+            # exact arithmetic, not in the last bits, so neither borrows the other's
+            kl = 0.5 * (float(torch.diagonal(Sig).sum().cpu()) + float((m * m).sum().cpu()) - M
+                        + 2.0 * float(np.log(np.diagonal(L.cpu().numpy())).sum()))
+            elbo.append(float(lsum.cpu()[0]) - kl)
+            resid.append(float(((Lam - Lt).abs().max() / Lt.abs().max()).cpu()))
+            if it == steps or (it > 0 and abs(elbo[-1] - elbo[-2]) <= tol * abs(elbo[-1])):
+                break
+            Lam, eta = (1.0 - rho) * Lam + rho * Lt, (1.0 - rho) * eta + rho * et
+        return (m.cpu().numpy(), np.tril(S.cpu().numpy()),
+                dict(elbo=np.asarray(elbo), residual=np.asarray(resid), steps=it))
+
+    def collapsed_bound_and_grad(self, X, Y, noise_var, k_var=1.0, residual="diagonal"):
+        """(value, grad): the collapsed bound of collapsed_bound() and its exact gradient with respect to the CONSTRAINED
+        values, grad = dict(z=[M, d], lengthscales=[dl], noise_var=float, k_var=float), float64 numpy.  One pass over
+        the data for the statistics, the M^3 tail, one more pass for the part of the gradient that goes through
+        K(z, X) (hb_sgp_kgrad) and the Gram VJP of K(z, z) + jitter I.
+
+        Everything is FLOAT64 ARITHMETIC on the device whatever the session's dtype: the z gradient is the difference of
+        two terms about 1000 times its size whose weights carry Lm^-1 twice, and float32 anywhere in the chain --
+        reusing the float32-formed Phi, b of statistics() included -- returns noise ("Gradient of the
+        collapsed bound").  A float32 session's X, Y, z, lengthscales are read as they are stored and are exact in
+        double.  `value` is the bound of this same float64 evaluation, so value and gradient are consistent; in a
+        float32 session it can differ from collapsed_bound() by the float32 error of statistics().  Same restrictions
+        and exception types as statistics(): UnitRBF, one expert, the lengthscales one Variable; residual 'fullrank'
+        raises NotImplementedError; a K(z, z) + jitter I or Lambda that is not positive definite raises
+        graph.CholeskyError."""
+        _check_residual(residual)
+        if not (float(noise_var) > 0.0 and float(k_var) > 0.0):
+            raise ValueError("noise_var and k_var must be positive (got %r, %r)" % (noise_var, k_var))
+        sess, Xd, Yd, z, ell, W = self._grad_inputs(X, Y)
+        stats = self._statistics_f64(sess, Xd, Yd, z, ell, W)
+        return self._grad_from_statistics(sess, Xd, Yd, z, ell, W, stats, noise_var, k_var, residual)
+
+    def _grad_inputs(self, X, Y, who="collapsed_bound_and_grad"):
+        """(sess, Xd, Yd, z, ell, W): the data as the session stores it, z and the lengthscales as the session stores
+        them carried in double, and W = chol(K(z, z) + jitter I)^-1 in double."""
+        sess, zvar, ls = self._stats_session(who)
+        H = sess.H
+        Xd, Yd = _host.device_data(sess, X, "X"), _host.device_data(sess, Y, "Y")
+        z = _host.upload(sess, sess.read_value(zvar), carry=np.float64)
+        ell = _host.lengthscales(sess, ls, carry=np.float64)
+        if Xd.shape[0] != Yd.shape[0] or Xd.shape[1] != z.shape[1]:
+            raise ValueError("%s: X %s, Y %s do not match z %s" % (who, tuple(Xd.shape), tuple(Yd.shape), tuple(z.shape)))
+        L = _host.factor(H, H.gram_fwd(z, z, ell, diag_add=float(settings.numerics.jitter_level)), who, "K(z, z) + jitter I")
+        return sess, Xd, Yd, z, ell, H.trinv(L)
+
+    def _statistics_f64(self, sess, Xd, Yd, z, ell, W):
+        """(Phi [M, M], b [P, M], yy [P]) with float64 ARITHMETIC whatever the storage type of Xd, Yd: column chunks are
+        up-converted, A_c = W K(z, X_c) by hb_sgp_A_f64, the three products by hb_matmul_f64, the chunks' results added in
+        chunk order.  (statistics() forms A in the session's dtype: its float32 rounding of Phi, b is harmless for
+        optimal_q and collapsed_bound and fatal for the gradient)"""
+        torch, H = sess.torch, sess.H
+
+        def per_chunk(c0, Xc, Yc):
+            A = H.sgp_A(Xc, z, ell, W)                                      # [M, nc]
+            return H.matmul(A, A, transB=True), H.matmul(Yc, A, transA=True, transB=True), H.matmul(Yc, Yc, transA=True)
+
+        Phi, b, yy = _walk_f64(torch, Xd, Yd, z.shape[0], 1, per_chunk)
+        return H.matutil(Phi.contiguous(), H.MATUTIL_SYM), b.contiguous(), torch.diagonal(yy).contiguous()
+
+    def _grad_from_statistics(self, sess, Xd, Yd, z, ell, W, stats, noise_var, k_var, residual):
+        """The tail and the two gradient passes of collapsed_bound_and_grad for given float64 (Phi, b, yy)."""
+        torch, H = sess.torch, sess.H
+        Phi, b, yy = stats
+        s2, k = float(noise_var), float(k_var)
+        rho = 1.0 if residual == "diagonal" else 0.0
+        N, P = int(Xd.shape[0]), int(Yd.shape[1])
+        # tail: D = dF/dLambda, G = dF/dPhi, g = dF/db
+        _, LL, V, t, c = self._lambda_solve((Phi, b), s2, k)                  # t [P, M], |t_p|^2 = c_p^T Lambda^-1 c_p
+        m = H.matmul(t, V)                                                   # [P, M] = c Lambda^-1
+        D = (H.matmul(m, m, transA=True, alpha=-0.5) - (0.5 * P) * H.matmul(V, V, transA=True)).contiguous()
+        Gm = H.matutil((D * (k / s2)).contiguous(), H.MATUTIL_ADD_EYE, alpha=rho * P * k / (2.0 * s2))
+        g = (m * (np.sqrt(k) / s2)).contiguous()
+        zg, eg = self._kernel_grads(sess, z, ell, W, Gm, g, Phi, b, lambda Q, R: H.sgp_kgrad(Xd, Yd, z, ell, Q, R))
+        # scalars and the value, on the host
+        tau, mb, mc = float((D * Phi).sum().cpu()), float((m * b).sum().cpu()), float((m * c).sum().cpu())
+        a2sum, yys = float(torch.diagonal(Phi).sum().cpu()), float(yy.sum().cpu())
+        quad = float((t * t).sum().cpu())
+        logdet = 2.0 * float(np.log(np.diagonal(LL.cpu().numpy())).sum())
+        val = _host.collapsed_value(N, P, s2, k, yys, quad, logdet, a2sum, residual)
+        dk = tau / s2 + mb / (2.0 * np.sqrt(k) * s2) - rho * P * (N - a2sum) / (2.0 * s2)
+        ds2 = (-N * P / (2.0 * s2) + yys / (2.0 * s2 ** 2) - (k / s2 ** 2) * tau - mc / s2
+               + rho * P * k * (N - a2sum) / (2.0 * s2 ** 2))
+        grad = dict(z=zg.cpu().numpy(), lengthscales=eg.cpu().numpy(), noise_var=float(ds2), k_var=float(dk))
+        return val, grad
+
+    def _kernel_grads(self, sess, z, ell, W, Gm, g, Phi, b, streamed):
+        """(zbar [M, d], ellbar [dl]) of a bound whose dependence on A = W K(z, X) is Abar = 2 G A diag(w) + g^T r^T, given
+        G = `Gm` [M, M], g [P, M] and the statistics Phi = A diag(w) A^T, b = (A r)^T (w = 1, r = Y for the collapsed
+        bound).  `streamed(Q, R)` returns the part through K(z, X) for Q = 2 W^T G W, R = W^T g^T (hb_sgp_kgrad /
+        hb_sgp_wkgrad); the part through K(z, z) is L^T Lbar = T = -Abar A^T = -(2 G Phi + g^T b), the Cholesky VJP and
+        the symmetric Gram VJP."""
+        torch, H = sess.torch, sess.H
+        M, d = z.shape
+        Q = H.matmul(W, H.matmul(Gm, W), transA=True, alpha=2.0)
+        R = H.matmul(W, g, transA=True, transB=True)
+        zbar, ellbar = streamed(Q, R)
+        T = (H.matmul(Gm, Phi, alpha=-2.0) - H.matmul(g, b, transA=True)).contiguous()
+        S = H.matmul(W, H.matmul(H.matutil(T, H.MATUTIL_PHI), W), transA=True)
+        Kmmbar = H.matutil(S, H.MATUTIL_SYM)
+        zk = torch.empty((M, d), dtype=torch.float64, device=sess.device)
+        ek = torch.empty((ell.numel(),), dtype=torch.float64, device=sess.device)
+        H.gram_bwd_raw(H.KERN_RBF | H.KERN_KBAR_SYMMETRIC, z, 0, z, 0, ell, 0, ell.numel(), Kmmbar, zk, zk, ek, 1, M, M, d,
+                       H.workspace(torch.float64, sess.device, max(M * d, 1)))
+        return zbar + zk, ellbar + ek
+
+    def elbo_and_grad(self, X, Y, likelihood, q, k_var=1.0, residual="diagonal"):
+        """(value, grad): the ELBO sum_j E_q log p(y_j | f_j) - KL(q || N(0, I)) of a factorising likelihood at a FIXED
+        q(u) = N(m, S S^T), q = (m [1, M], S [M, M] lower), and its partial gradient with respect to the CONSTRAINED
+        z, lengthscales and k_var at that q: grad = dict(z=[M, d], lengthscales=[dl], k_var=float), float64 numpy.  At
+        the q natgrad_q converges to, the partial gradient is the total derivative of the fitted ELBO (envelope
+        property); with the Gaussian likelihood and q = optimal_q it is the gradient of collapsed_bound_and_grad.
+
+        With the sites lam_j = E[-d2 log p], gamma_j = E[d log p] of hb_lik_sites at the marginals mu_j, v_j:
+        dl_j/dmu_j = gamma_j, dl_j/dv_j = -lam_j / 2 (Stein's identity: exact for the Gaussian and Poisson sites, for
+        Bernoulli the derivative of the 20-node quadrature up to its error), so
+            Abar = 2 G A diag(lam) + g^T gamma^T,   G = -(k_var / 2) (S S^T - rho I),   g = sqrt(k_var) m
+        (rho = 1 for residual 'diagonal', 0 for 'neglected'; the |.| samples() applies to 1 - a_j^T a_j is ignored, as
+        for collapsed_bound), which is the form of the collapsed bound's gradient with column weights: the streamed part
+        is hb_sgp_wkgrad, the K(z, z) part needs Phi_w = A diag(lam) A^T and b_w = (A gamma)^T, and
+        dF/dk_var = sum_j (gamma_j mu_j - lam_j v_j) / (2 k_var).
+
+        FLOAT64 ARITHMETIC end to end whatever the session's dtype, for the reason collapsed_bound_and_grad gives.  The
+        data is walked in fixed-size column chunks up-converted to double: the marginals (hb_sgp_predict_f64), the
+        sites (hb_lik_sites_f64) and the weighted statistics (hb_sgp_wstats_f64), the chunks' sums added in chunk order;
+        then the M^3 tail, hb_sgp_wkgrad over all of X in its stored dtype and the Gram VJP of K(z, z).  Restrictions
+        and exception types are natgrad_q's: UnitRBF, one expert, Y [N, 1]; residual 'fullrank' and a mean-field q
+        raise NotImplementedError; a K(z, z) + jitter I that is not positive definite raises graph.CholeskyError; a
+        likelihood that is no henbun_amd.likelihoods.Likelihood raises TypeError."""
+        sess, Xd, Yd, z, ell, W = self._grad_inputs(X, Y, "elbo_and_grad")
+        torch, H = sess.torch, sess.H
+        N, M = int(Xd.shape[0]), int(z.shape[0])
+        m0, S0 = _check_lik_inputs("elbo_and_grad", likelihood, k_var, residual, q, Yd, M)
+        k = float(k_var)
+        rho = 1.0 if residual == "diagonal" else 0.0
+        m, S = _host.upload(sess, m0.reshape(1, M), np.float64), _host.upload(sess, np.tril(S0), np.float64)
+        mode = H.SGP_DIAGONAL if residual == "diagonal" else H.SGP_NEGLECTED
+        lam = torch.empty((N,), dtype=torch.float64, device=sess.device)
+        gam = torch.empty_like(lam)
+
+        def per_chunk(c0, Xc, Yc):
+            mean, var = H.sgp_predict(Xc, z, ell, W, m, S, s_kind=H.SGP_S_TRIL, mode=mode)       # unit-variance moments [1, nc]
+            lc, bc = lam[c0:c0 + Xc.shape[0]], gam[c0:c0 + Xc.shape[0]]
+            _, _, ls = H.lik_sites(likelihood.lik_id, Yc.reshape(-1), mean, var, param=likelihood.param, mscale=np.sqrt(k),
+                                   vscale=k, out=(lc, bc))
+            mu = mean.reshape(-1) * np.sqrt(k)
+            bc -= lc * mu                                                   # gamma = beta - lam mu
+            Pc, rc, _ = H.sgp_wstats(Xc, lc, bc, z, ell, W)
+            return Pc, rc, ls, (bc * mu - lc * var.reshape(-1) * k).sum()
+
+        # chunks of a multiple of 32 rows: every chunk of lam stays 16-byte aligned
+        Phi, b, lsum, dks = _walk_f64(torch, Xd, Yd, M, 32, per_chunk)
+        # tail: G = dF/dPhi_w, g = dF/db_w
+        Gm = H.matutil((H.matmul(S, S, transB=True) * (-0.5 * k)).contiguous(), H.MATUTIL_ADD_EYE, alpha=0.5 * rho * k)
+        g = (m * np.sqrt(k)).contiguous()
+        zg, eg = self._kernel_grads(sess, z, ell, W, Gm, g, Phi.contiguous(), b.contiguous(),
+                                    lambda Q, R: H.sgp_wkgrad(Xd, lam, gam, z, ell, Q, R))
+        # KL(q || N(0, I)) from S itself (natgrad_q forms it from Sigma and the factor of Lambda; see there), and
+        # dF/dk_var: scalars on the host
+        Sl = np.tril(S0)
+        kl = 0.5 * (float((Sl * Sl).sum()) + float((m0 * m0).sum()) - M) - float(np.log(np.abs(np.diagonal(Sl))).sum())
+        grad = dict(z=zg.cpu().numpy(), lengthscales=eg.cpu().numpy(), k_var=float(dks.cpu()) / (2.0 * k))
+        return float(lsum.cpu()[0]) - kl, grad
+
+    # -- pathwise posterior function draws (Wilson et al. 2020) -----------------------------------------------------
+    def pathwise_draws(self, q, num_samples, num_features=1024, k_var=1.0, seed=0, noise=None):
+        """num_samples posterior FUNCTION draws as a PathwiseDraws: each is drawn once, as 2 num_features + M
+        coefficients, and can then be evaluated anywhere at O((M + num_features) n) per draw -- no [n, n] covariance, no
+        factorisation, no jitter; the same object gives values of the same sample paths on every call.  For the whitened
+        model u ~ q = N(m, S S^T), with x~ = x / ell, W = Lm^-1, A(x) = W K(z, x) and L = num_features:
+            omega_l ~ N(0, I_d),  w_s ~ N(0, I_2L),  eps_s ~ N(0, I_M)
+            g_s(x) = L^-1/2 sum_l [ w_s,2l cos(omega_l . x~) + w_s,2l+1 sin(omega_l . x~) ]      (prior path, unit RBF)
+            u_s = m + eps_s S^T,   t_s = u_s - g_s(z) W^T,   v_s = t_s W
+            f_s(x) = sqrt(k_var) ( g_s(x) + v_s K(z, x) )  =  sqrt(k_var) ( g_s(x) + t_s A(x) ).
+        Given omega the draws are Gaussian with mean sqrt(k_var) m A(x) -- predict_f's mean exactly -- and covariance
+        k_var (C(x)^T C(x') + A^T S S^T A), C(x) = phi(x) - phi(z)^T W^T A(x), which tends to k_var (K(x, x') - A^T A +
+        A^T S S^T A) as L grows: the EXACT conditional, i.e. the 'fullrank' residual of predict_f(full_cov=True) without
+        its jitter term, whatever `residual` the model trains with.  The error of the covariance falls as 1 / sqrt(L)
+        (at most 8 / sqrt(L) observed inside the hull of the inducing points at moderate conditioning; outside the hull
+        the interpolation weights amplify the feature error, 13 / sqrt(L) was seen there).
+
+        q: a Normal / Gaussian Variational (read through its parameters by a plan: the values predict_f reads), or a
+        tuple (m [1, M], S [M, M] lower) or (m, s [M]) as numpy.  K(z, z) is factorised as the plans do it
+        (_whitening(as_plans=True)), so the draws live in the whitening predict_f and the ELBO use.  The M-sized tail runs
+        in float64 on the device whatever the session's dtype (forming t in float32 moves it by up to 9e-3 at
+        cond 1e6): g(z) by hb_sgp_pathwise_f64, the two products by hb_matmul_f64; omega and the
+        coefficients [w / sqrt(L) | v] are then stored in the session's dtype.  noise=None draws omega [L, d], w [S, 2L],
+        eps [S, M] from hip_ops.Rng(seed), in that order; noise=dict(omega=, w=, eps=) injects them (float64 arrays).
+        Restrictions and exception types are those of statistics(): UnitRBF, one expert, the lengthscales one Variable;
+        more than one latent function raises NotImplementedError; malformed q or noise raise ValueError."""
+        S, L, k_var = int(num_samples), int(num_features), float(k_var)
+        if not (S >= 1 and L >= 1 and k_var > 0.0):
+            raise ValueError("pathwise_draws: num_samples >= 1, num_features >= 1 and k_var > 0 expected (got %r, %r, %r)"
+                             % (num_samples, num_features, k_var))
+        sess, zvar, ls = self._stats_session("pathwise_draws")
+        torch, H = sess.torch, sess.H
+        M, d = int(zvar.shape[0]), int(zvar.shape[1])
+        m, s = self._q_moments(sess, q, M)
+        z, ell, W, _ = self._whitening(sess, zvar, ls, None, None, "pathwise_draws", as_plans=True)
+        omega, w, eps = _host.pathwise_noise(sess, "pathwise_draws", noise, seed, ((L, d), (S, 2 * L), (S, M)), double=True)
+        # the frequencies and the prior weights ARE what the session's dtype stores: g(z) below is taken from their
+        # rounded values, so the update interpolates the same prior path evaluate() adds it to
+        omega = omega.to(sess.torch_dtype).contiguous()
+        cw = (w * (1.0 / np.sqrt(L))).to(sess.torch_dtype).contiguous()
+        z64, ell64, W64 = z.to(torch.float64), ell.to(torch.float64), W.to(torch.float64)
+        U = m + (H.matmul(eps, s, transB=True) if s.dim() == 2 else eps * s)              # [S, M]
+        Gz = H.sgp_pathwise(z64, omega.to(torch.float64), None, ell64, cw.to(torch.float64))   # g_s(z_m)  [S, M]
+        T = (U - H.matmul(Gz, W64, transB=True)).contiguous()
+        V = H.matmul(T, W64)
+        coef = torch.cat([cw, V.to(sess.torch_dtype)], dim=1).contiguous()
+        return PathwiseDraws(sess, omega, coef, z, ell, float(np.sqrt(k_var)))
+
+    def _q_moments(self, sess, q, M):
+        """(m [1, M], S [M, M] lower or s [M]) of q(u) as float64 device tensors, for pathwise_draws."""
+        if isinstance(q, (tuple, list)):
+            if len(q) != 2:
+                raise ValueError("pathwise_draws: q = (m [1, M], S [M, M] or s [M]) expected")
+            m, s = (np.asarray(a, dtype=np.float64) for a in q)
+        else:
+            from .gp import _posterior_of
+
+            mt, st, _ = _posterior_of(q)
+            for v in ("q_mu", "q_sqrt") + (("scale",) if type(q) is Gaussian else ()):
+                sess.read_value(object.__getattribute__(q, v))      # uploads a value that was assigned and not yet written
+            plan = sess.make_plan([mt, st])
+            plan.run()
+            plan.check()
+            m, s = (np.asarray(plan.value(t), dtype=np.float64) for t in (mt, st))
+        if m.ndim >= 2 and int(np.prod(m.shape[:-1])) > 1:
+            raise NotImplementedError("pathwise_draws: one latent function only (q has shape %s)" % (m.shape,))
+        if s.ndim >= 2 and s.shape[-2:] == (M, M):
+            s = np.tril(s.reshape(M, M))
+        elif s.size == M:
+            s = s.reshape(M)
+        else:
+            raise ValueError("pathwise_draws: S [%d, %d] lower or s [%d] expected, got %s" % (M, M, M, s.shape))
+        if m.size != M:
+            raise ValueError("pathwise_draws: m [1, %d] expected, got %s" % (M, m.shape))
+        return _host.upload(sess, m.reshape(1, M), np.float64), _host.upload(sess, s, np.float64)
+
+
+class PathwiseDraws:
+    """S posterior function draws of a SparseGP (SparseGP.pathwise_draws): a snapshot of the frequencies omega [L, d], the
+    coefficient rows coef [S, 2L + M], z [M, d], the lengthscales and scale = sqrt(k_var), on the device in the session's
+    dtype.  Later changes to the model do not move it.  Every evaluation is ONE launch of hb_sgp_pathwise, linear in n;
+    the value at a point does not depend on the other points of the call, so the same draws can be evaluated in pieces,
+    on a grid now and at candidates later, and maximised."""
+
+    def __init__(self, sess, omega, coef, z, ell, scale):
+        self._sess = sess
+        self._omega, self._coef, self._z, self._ell, self.scale = omega, coef, z, ell, float(scale)
+        self.num_samples, self.num_features = int(coef.shape[0]), int(omega.shape[0])
+
+    def evaluate(self, X, out=None):
+        """The draws at the rows of X as a device tensor [S, n] of the session's dtype (`out`: written in place).  X: a
+        Data / MinibatchData of the model (read in full from its device buffer), a device tensor or an array [n, d]."""
+        Xd = _host.device_data(self._sess, X, "X")
+        if Xd.shape[1] != self._z.shape[1]:
+            raise ValueError("PathwiseDraws: X %s does not match z %s" % (tuple(Xd.shape), tuple(self._z.shape)))
+        return self._sess.H.sgp_pathwise(Xd, self._omega, self._z, self._ell, self._coef, scale=self.scale, out=out)
+
+    def __call__(self, X):
+        """The draws at the rows of X as numpy [S, n]."""
+        return self.evaluate(X).cpu().numpy()
+
+    def _view(self, t):
+        a = t.cpu().numpy()
+        a.flags.writeable = False
+        return a
+
+    omega = property(lambda self: self._view(self._omega), doc="frequencies [L, d] (read-only numpy)")
+    coef = property(lambda self: self._view(self._coef), doc="coefficient rows [S, 2L + M] = [w / sqrt(L) | v]")
+    z = property(lambda self: self._view(self._z), doc="inducing points [M, d]")
+    lengthscales = property(lambda self: self._view(self._ell), doc="lengthscales [1] or [d]")
+
+
+def greedy_inducing(X, M, lengthscales=1.0, threshold=None, return_info=False, dtype=None):
+    """Z [M, d] (numpy, selection order): the M rows of X [N, d] that greedy conditional-variance selection picks for the
+    UnitRBF kernel with the given lengthscales (a scalar, [1] or [d]) -- a pivoted incomplete Cholesky of K(X, X) (Burt,
+    Rasmussen, van der Wilk 2020), each step taking the point whose variance given the points chosen so far is largest
+    (exact ties: the lowest row, so X[0] is always first).  Deterministic; needs no model, so it can make the Z a model
+    is built with.  X is uploaded in the configured float type (`dtype`: as for Model) to the device a Session would
+    pick; the work is M launches of hb_sgp_select with no read-back, and O(M N) device memory for the duration.
+    threshold=None: settings.numerics.jitter_level -- a point whose conditional variance is below the jitter adds
+    nothing that K(z, z) + jitter I can resolve.  If fewer than M points clear the threshold ValueError is raised, naming
+    the count reached.  return_info=True: (Z, dict(idx int64 [M], pivots [M], trace float, count int)); trace is the
+    residual tr(K_XX - K_XZ K_ZZ^-1 K_ZX), the N - a2sum term of collapsed_bound at zero jitter."""
+    from ..session import Session
+
+    sess = Session(None, dtype=dtype)
+    sess._ensure_device()
+    X = np.asarray(X, dtype=sess.np_dtype)
+    if X.ndim != 2:
+        raise ValueError("greedy_inducing: X must be 2-D [N, d], got %s" % (X.shape,))
+    ell = np.reshape(np.asarray(lengthscales, dtype=sess.np_dtype), [-1])
+    if ell.size not in (1, X.shape[1]) or not np.all(ell > 0):
+        raise ValueError("greedy_inducing: lengthscales must be positive, a scalar or one per column of X")
+    M = int(M)
+    if not 1 <= M <= X.shape[0]:
+        raise ValueError("greedy_inducing: 1 <= M <= N expected, got M=%d, N=%d" % (M, X.shape[0]))
+    thr = float(settings.numerics.jitter_level if threshold is None else threshold)
+    idx, pivots, count, trace = sess.H.sgp_select(_host.upload(sess, X), _host.upload(sess, ell), M, thr)
+    count = int(count.cpu()[0])
+    if count < M:
+        raise ValueError("greedy_inducing: only %d of the %d points asked for have a conditional variance above the "
+                         "threshold %g (use fewer inducing points or a lower threshold)" % (count, M, thr))
+    idx = idx.cpu().numpy()
+    Z = X[idx].copy()
+    if not return_info:
+        return Z
+    return Z, dict(idx=idx, pivots=pivots.cpu().numpy(), trace=float(trace.cpu()[0]), count=count)

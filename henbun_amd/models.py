@@ -8,6 +8,8 @@ reference notebooks/GaussianProcess.ipynb:109-159), with `tf = hb.tf`.
 import numpy as np
 
 import henbun_amd as hb  # noqa: E402  (the package is fully imported before this module is)
+from henbun_amd.gp._host import upload
+from henbun_amd.param import tri_pack, tri_unpack
 
 tf = hb.tf
 
@@ -62,6 +64,27 @@ def _chain_to_raw(model, cons):
     return grad
 
 
+def _part(model, name):
+    """The child object `name` itself, also inside tf_mode (where plain attribute access hands out its tensor)."""
+    return object.__getattribute__(model, name)
+
+
+def _scalar(model, name):
+    """The value of the [1] Variable `name` as a float."""
+    return float(np.ravel(_part(model, name).value)[0])
+
+
+def _write_q(model, m, S):
+    """Write q(u) = N(m, S S^T) into model.u in its own parametrisation: q_mu = m; q_sqrt = the log standard deviations
+    for q_shape 'diagonal' (S is then s [M]), the lower-triangular factor (packed or dense) for 'fullrank'."""
+    q, sess = _part(model, "u"), model._session
+    sess.write_raw(_part(q, "q_mu"), np.reshape(m, -1))
+    if q.q_shape == "diagonal":
+        sess.write_raw(_part(q, "q_sqrt"), np.log(S))
+    else:
+        sess.write_raw(_part(q, "q_sqrt"), tri_pack(S) if q.packed else S)
+
+
 class SVGP(hb.model.Model):
     """Sparse variational GP regression: cfg 1/2 (q_shape='diagonal') and cfg 3 ('fullrank')."""
 
@@ -88,7 +111,7 @@ class SVGP(hb.model.Model):
         covariance [1, n, n] times k_var instead of var; with num_samples joint draws [num_samples, n] of f (the model's
         ELBO convention f = samples * sqrt(k_var) for all three)."""
         Xnew = np.asarray(Xnew)
-        q = object.__getattribute__(self, "u")
+        q = _part(self, "u")
         self.initialize()
         with self.tf_mode():
             if num_samples is not None:
@@ -128,33 +151,22 @@ class SVGP(hb.model.Model):
         'fullrank' residual) whatever `residual` the model trains with; predict_f_samples stays the exact joint route for
         small n."""
         self.initialize()
-        g = lambda k: object.__getattribute__(self, k)
-        return g("gp").pathwise_draws(g("u"), num_samples, num_features=num_features,
-                                      k_var=float(np.ravel(g("k_var").value)[0]), seed=seed, noise=noise)
+        return _part(self, "gp").pathwise_draws(_part(self, "u"), num_samples, num_features=num_features,
+                                                k_var=_scalar(self, "k_var"), seed=seed, noise=noise)
 
     def _closed_form_inputs(self):
         """(X, Y, noise variance, k_var) of the whole data set at the current hyper-parameters."""
         self.initialize()
-        g = lambda k: object.__getattribute__(self, k)
-        return g("X"), g("Y"), float(np.ravel(g("var").value)[0]), float(np.ravel(g("k_var").value)[0])
+        return _part(self, "X"), _part(self, "Y"), _scalar(self, "var"), _scalar(self, "k_var")
 
     def fit_q(self):
         """Set q(u) to its closed-form optimum at the current z, lengthscales, k_var and var, from ONE pass over the
         model's full device-resident X, Y (SparseGP.optimal_q; not a minibatch, no Adam step).  u.q_mu / u.q_sqrt are
         written in their own parametrisation -- log standard deviations for q_shape 'diagonal' (the mean-field optimum),
         the lower-triangular factor (packed or dense) for 'fullrank'.  Returns (m [1, M], S or s) as optimal_q does."""
-        from henbun_amd.param import tri_pack
-
         X, Y, var, k_var = self._closed_form_inputs()
-        q = object.__getattribute__(self, "u")
-        m, S = object.__getattribute__(self, "gp").optimal_q(X, Y, var, k_var, q_shape=q.q_shape, residual=self.residual)
-        sess = self._session
-        q_mu, q_sqrt = object.__getattribute__(q, "q_mu"), object.__getattribute__(q, "q_sqrt")
-        sess.write_raw(q_mu, m.reshape(-1))
-        if q.q_shape == "diagonal":
-            sess.write_raw(q_sqrt, np.log(S))
-        else:
-            sess.write_raw(q_sqrt, tri_pack(S) if q.packed else S)
+        m, S = _part(self, "gp").optimal_q(X, Y, var, k_var, q_shape=_part(self, "u").q_shape, residual=self.residual)
+        _write_q(self, m, S)
         return m, S
 
     def select_inducing(self, threshold=None):
@@ -162,19 +174,19 @@ class SVGP(hb.model.Model):
         lengthscales (SparseGP.select_inducing: one launch per point over the device-resident X); returns their row
         indices.  q(u) is NOT touched and no longer fits the new z: call fit_q() afterwards."""
         self.initialize()
-        return object.__getattribute__(self, "gp").select_inducing(object.__getattribute__(self, "X"), threshold=threshold)
+        return _part(self, "gp").select_inducing(_part(self, "X"), threshold=threshold)
 
     def collapsed_bound(self):
         """The ELBO at the optimal q(u) for the current hyper-parameters (SparseGP.collapsed_bound on the full X, Y):
         what fit_q() followed by an exact evaluation of ELBO over all rows would give."""
         X, Y, var, k_var = self._closed_form_inputs()
-        return object.__getattribute__(self, "gp").collapsed_bound(X, Y, var, k_var, residual=self.residual)
+        return _part(self, "gp").collapsed_bound(X, Y, var, k_var, residual=self.residual)
 
     def _hyper_variables(self):
         """The Variables collapsed_bound() depends on, by the names the gradient uses."""
-        g = object.__getattribute__
-        gp = g(self, "gp")
-        return dict(z=g(gp, "z"), lengthscales=g(g(gp, "kern"), "lengthscales"), k_var=g(self, "k_var"), var=g(self, "var"))
+        gp = _part(self, "gp")
+        return dict(z=_part(gp, "z"), lengthscales=_part(_part(gp, "kern"), "lengthscales"), k_var=_part(self, "k_var"),
+                    var=_part(self, "var"))
 
     def collapsed_bound_and_grad(self):
         """(value, grad): the collapsed bound and its exact gradient with respect to the RAW (free) parameters,
@@ -182,7 +194,7 @@ class SVGP(hb.model.Model):
         SparseGP.collapsed_bound_and_grad on the full X, Y (float64 arithmetic whatever the session's dtype), chained
         through the transforms' dforward."""
         X, Y, var, k_var = self._closed_form_inputs()
-        value, gr = object.__getattribute__(self, "gp").collapsed_bound_and_grad(X, Y, var, k_var, residual=self.residual)
+        value, gr = _part(self, "gp").collapsed_bound_and_grad(X, Y, var, k_var, residual=self.residual)
         return value, _chain_to_raw(self, dict(z=gr["z"], lengthscales=gr["lengthscales"], k_var=gr["k_var"], var=gr["noise_var"]))
 
     def fit_hyper(self, steps, lr=0.01, train_z=True):
@@ -231,10 +243,8 @@ class SVGPLik(hb.model.Model):
         """Mean and variance [1, n] of a new observation y at Xnew [n, 1]: the likelihood's predictive under the
         Gaussian marginals of predict_f (hb_lik_predict)."""
         mean, var = self.predict_f(Xnew)
-        sess = self._session
-        torch, lik = sess.torch, object.__getattribute__(self, "likelihood")
-        up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=sess.np_dtype)).to(sess.device)
-        ym, yv = sess.H.lik_predict(lik.lik_id, up(mean), up(var), param=lik.param)
+        sess, lik = self._session, _part(self, "likelihood")
+        ym, yv = sess.H.lik_predict(lik.lik_id, upload(sess, mean), upload(sess, var), param=lik.param)
         return ym.cpu().numpy(), yv.cpu().numpy()
 
     def fit_q(self, steps=20, rho=1.0, tol=1e-8):
@@ -244,56 +254,41 @@ class SVGPLik(hb.model.Model):
         writes them for 'fullrank'.  Returns (m [1, M], S [M, M], info) as natgrad_q does.  A full step (rho = 1) from a q
         far from the optimum, such as a freshly initialised one, can overshoot before it settles: info['elbo'] shows it,
         and rho < 1 damps it."""
-        from henbun_amd.param import tri_pack
-
         self.initialize()
-        g = lambda k: object.__getattribute__(self, k)
-        q, sess = g("u"), self._session
-        q_mu, q_sqrt = object.__getattribute__(q, "q_mu"), object.__getattribute__(q, "q_sqrt")
-        m0, S0 = self._current_q()
-        m, S, info = g("gp").natgrad_q(g("X"), g("Y"), g("likelihood"), k_var=float(np.ravel(g("k_var").value)[0]),
-                                       residual=self.residual, q0=(m0, S0), steps=steps, rho=rho, tol=tol)
-        sess.write_raw(q_mu, m.reshape(-1))
-        sess.write_raw(q_sqrt, tri_pack(S) if q.packed else S)
+        m, S, info = _part(self, "gp").natgrad_q(_part(self, "X"), _part(self, "Y"), _part(self, "likelihood"),
+                                                 k_var=_scalar(self, "k_var"), residual=self.residual,
+                                                 q0=self._current_q(), steps=steps, rho=rho, tol=tol)
+        _write_q(self, m, S)
         return m, S, info
 
     def reset_q(self):
         """Set q(u) to the prior N(0, I), where natgrad_q's own default starts.  A freshly built model holds a RANDOM q(u),
         from which a full natural-gradient step (rho = 1) overshoots: call this before the first fit_q() / fit_hyper()."""
-        from henbun_amd.param import tri_pack
-
         self.initialize()
-        q, sess = object.__getattribute__(self, "u"), self._session
-        M = q.size
-        sess.write_raw(object.__getattribute__(q, "q_mu"), np.zeros(M))
-        sess.write_raw(object.__getattribute__(q, "q_sqrt"), tri_pack(np.eye(M)) if q.packed else np.eye(M))
+        M = _part(self, "u").size
+        _write_q(self, np.zeros(M), np.eye(M))
 
     def _current_q(self):
         """(m [1, M], S [M, M] lower) of the model's q(u) as the session stores it, float64 numpy."""
-        from henbun_amd.param import tri_unpack
-
         self.initialize()
-        q, sess = object.__getattribute__(self, "u"), self._session
+        q, sess = _part(self, "u"), self._session
         M = q.size
-        S = np.asarray(sess.read_raw(object.__getattribute__(q, "q_sqrt")), dtype=np.float64)
+        S = np.asarray(sess.read_raw(_part(q, "q_sqrt")), dtype=np.float64)
         S = tri_unpack(S.reshape(-1)) if q.packed else np.tril(S.reshape(M, M))
-        return np.asarray(sess.read_raw(object.__getattribute__(q, "q_mu")), dtype=np.float64).reshape(1, M), S
+        return np.asarray(sess.read_raw(_part(q, "q_mu")), dtype=np.float64).reshape(1, M), S
 
     def _hyper_variables(self):
         """The Variables the ELBO at a fixed q(u) depends on, by the names the gradient uses."""
-        g = object.__getattribute__
-        gp = g(self, "gp")
-        return dict(z=g(gp, "z"), lengthscales=g(g(gp, "kern"), "lengthscales"), k_var=g(self, "k_var"))
+        gp = _part(self, "gp")
+        return dict(z=_part(gp, "z"), lengthscales=_part(_part(gp, "kern"), "lengthscales"), k_var=_part(self, "k_var"))
 
     def elbo_and_grad(self):
         """(value, grad): the ELBO over the model's full X, Y at the model's CURRENT q(u) and its partial gradient at
         that q with respect to the RAW (free) parameters, grad = dict(z, lengthscales, k_var) in the shapes of the raw
         arrays, float64 numpy.  SparseGP.elbo_and_grad (float64 arithmetic whatever the session's dtype), chained
         through the transforms' dforward.  After fit_q() has converged this is the total derivative of the fitted ELBO."""
-        g = lambda k: object.__getattribute__(self, k)
-        q = self._current_q()
-        value, cons = g("gp").elbo_and_grad(g("X"), g("Y"), g("likelihood"), q, k_var=float(np.ravel(g("k_var").value)[0]),
-                                            residual=self.residual)
+        value, cons = _part(self, "gp").elbo_and_grad(_part(self, "X"), _part(self, "Y"), _part(self, "likelihood"),
+                                                      self._current_q(), k_var=_scalar(self, "k_var"), residual=self.residual)
         return value, _chain_to_raw(self, cons)
 
     def fit_hyper(self, steps, lr=0.01, train_z=True, q_steps=5, rho=1.0):
@@ -372,37 +367,34 @@ class ExactGPR(hb.model.Model):
     def fit(self, precond_rank=64, tol=None, max_iter=1000):
         """Condition on the model's X, Y at the CURRENT lengthscales, k_var and var and keep the hb.gp.ExactPosterior
         (also returned as self.posterior); hyper-parameters changed afterwards need another fit().  Returns self."""
-        self.initialize()
-        g = lambda k: object.__getattribute__(self, k)
-        self.posterior = g("gp").condition(g("X"), g("Y"), float(np.ravel(g("var").value)[0]),
-                                           k_var=float(np.ravel(g("k_var").value)[0]), precond_rank=precond_rank, tol=tol,
-                                           max_iter=max_iter)
+        X, Y, var, k_var = self._closed_form_inputs()
+        self.posterior = _part(self, "gp").condition(X, Y, var, k_var=k_var, precond_rank=precond_rank, tol=tol, max_iter=max_iter)
         return self
+
+    _closed_form_inputs = SVGP._closed_form_inputs
 
     def _hyper_variables(self):
         """The Variables the log marginal likelihood depends on, by the names the gradient uses."""
-        g = object.__getattribute__
-        return dict(lengthscales=g(g(g(self, "gp"), "kern"), "lengthscales"), k_var=g(self, "k_var"), var=g(self, "var"))
+        return dict(lengthscales=_part(_part(_part(self, "gp"), "kern"), "lengthscales"), k_var=_part(self, "k_var"),
+                    var=_part(self, "var"))
 
     def log_marginal_likelihood_and_grad(self, num_probes=16, seed=0, precond_rank=64, tol=None, max_iter=1000, probes=None):
         """(value, grad): the log marginal likelihood of the model's X, Y at the current hyper-parameters and its gradient
         with respect to the RAW (free) parameters, grad = dict(lengthscales, k_var, var) in the shapes of the raw arrays,
         float64 numpy: GP.log_marginal_likelihood_and_grad chained through the transforms' dforward.  A stochastic
         estimate, deterministic given `seed` (or `probes`)."""
-        self.initialize()
-        g = lambda k: object.__getattribute__(self, k)
-        value, gr, _ = g("gp").log_marginal_likelihood_and_grad(
-            g("X"), g("Y"), float(np.ravel(g("var").value)[0]), k_var=float(np.ravel(g("k_var").value)[0]),
-            precond_rank=precond_rank, tol=tol, max_iter=max_iter, num_probes=num_probes, seed=seed, probes=probes)
+        X, Y, var, k_var = self._closed_form_inputs()
+        value, gr, _ = _part(self, "gp").log_marginal_likelihood_and_grad(
+            X, Y, var, k_var=k_var, precond_rank=precond_rank, tol=tol, max_iter=max_iter, num_probes=num_probes, seed=seed,
+            probes=probes)
         return value, _chain_to_raw(self, dict(lengthscales=gr["lengthscales"], k_var=gr["k_var"], var=gr["noise_var"]))
 
     def log_marginal_likelihood(self, num_probes=16, seed=0, precond_rank=64, tol=None, max_iter=1000, probes=None):
         """The value alone (no pass over the kernel entries)."""
-        self.initialize()
-        g = lambda k: object.__getattribute__(self, k)
-        return g("gp").log_marginal_likelihood(
-            g("X"), g("Y"), float(np.ravel(g("var").value)[0]), k_var=float(np.ravel(g("k_var").value)[0]),
-            precond_rank=precond_rank, tol=tol, max_iter=max_iter, num_probes=num_probes, seed=seed, probes=probes)
+        X, Y, var, k_var = self._closed_form_inputs()
+        return _part(self, "gp").log_marginal_likelihood(
+            X, Y, var, k_var=k_var, precond_rank=precond_rank, tol=tol, max_iter=max_iter, num_probes=num_probes, seed=seed,
+            probes=probes)
 
     def fit_hyper(self, steps, lr=0.01, num_probes=16, seed=0, precond_rank=64, tol=None):
         """Fit lengthscales, k_var and var: `steps` Adam ASCENT steps on log_marginal_likelihood_and_grad in the raw
@@ -417,7 +409,7 @@ class ExactGPR(hb.model.Model):
         return trace
 
     def _posterior(self):
-        post = object.__getattribute__(self, "posterior")
+        post = _part(self, "posterior")
         if post is None:
             raise ValueError("ExactGPR: call fit() first")
         return post
