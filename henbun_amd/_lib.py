@@ -52,6 +52,7 @@ _SIGS = {
     "hb_sgp_predict_cov_ws_elems": [L, L, L, L, I, I],
     "hb_sgp_stats_ws_elems": [L, L, L, L, I],
     "hb_sgp_select_ws_elems": [L, L, L, I],
+    "hb_sgp_pathwise_argmax_ws_elems": [L, L],
     "hb_gram_matvec_chunk": [],
     "hb_gram_matvec_ws_elems": [L, L, L, I],
     "hb_gram_bilinear_grad_ws_elems": [L, L],
@@ -94,6 +95,7 @@ _RESTYPES = {"hb_last_error_string": c_char_p, "hb_sgp_ws_elems": c_long, "hb_ew
              "hb_sgp_head_units": c_long, "hb_matmul_gauss_units": c_long, "hb_matmul_gram_vjp_ws_elems": c_long, "hb_cholesky_inverse_ws_elems": c_long, "hb_mlp2_sample_ws_elems": c_long,
              "hb_sgp_predict_ws_elems": c_long, "hb_sgp_predict_cov_ws_elems": c_long,
              "hb_sgp_stats_ws_elems": c_long, "hb_sgp_select_ws_elems": c_long,
+             "hb_sgp_pathwise_argmax_ws_elems": c_long,
              "hb_gram_matvec_chunk": c_long, "hb_gram_matvec_ws_elems": c_long,
              "hb_gram_bilinear_grad_ws_elems": c_long,
              "hb_sgp_kgrad_ws_elems": c_long, "hb_sgp_wstats_ws_elems": c_long, "hb_lik_sites_ws_elems": c_long}
@@ -141,6 +143,8 @@ _TYPED = {
     "hb_lik_sites": [I, P, P, P, D, D, D, P, P, P, L, P, P],
     "hb_lik_predict": [I, P, P, D, P, P, L, P],
     "hb_sgp_pathwise": [I, P, P, P, P, L, P, D, P, L, L, L, L, L, P],
+    "hb_sgp_pathwise_grad": [I, P, P, P, P, L, P, D, P, P, L, L, L, L, L, P],
+    "hb_sgp_pathwise_argmax": [I, P, P, P, P, L, P, D, I, P, P, L, L, L, L, L, P, P],
     "hb_sgp_select": [I, P, P, L, L, L, L, D, P, P, P, P, P, P],
     "hb_gram_matvec": [I, P, P, P, L, P, D, D, P, L, L, L, L, P, P],
     "hb_pcg_dot": [P, P, P, L, L, P],

@@ -355,7 +355,8 @@ class ExactPosterior:
         i.e. coefficient rows [w_s / sqrt(L) | v_s] under scale = sqrt(k_var), the conventions of SparseGP.pathwise_draws.
         g_s(X) is hb_sgp_pathwise with M = 0; the v_s come from lockstep solves in blocks of 64 draws; evaluation is the
         unchanged hb_sgp_pathwise, O((N + L) n) per draw.  noise=None draws omega [L, d], w [S, 2L], eps [S, N] from
-        hip_ops.Rng(seed), in that order; noise=dict(omega=, w=, eps=) injects them.  One output column (P = 1) only."""
+        hip_ops.Rng(seed), in that order; noise=dict(omega=, w=, eps=) injects them.  One output column (P = 1) only.  The object's
+        grad, argmax and maximise (PathwiseDraws) run unchanged on it: z = X is all the kernels see."""
         sess = self._sess
         torch, H = sess.torch, sess.H
         S, L = int(num_samples), int(num_features)

@@ -502,7 +502,9 @@ class PathwiseDraws:
     coefficient rows coef [S, 2L + M], z [M, d], the lengthscales and scale = sqrt(k_var), on the device in the session's
     dtype.  Later changes to the model do not move it.  Every evaluation is ONE launch of hb_sgp_pathwise, linear in n;
     the value at a point does not depend on the other points of the call, so the same draws can be evaluated in pieces,
-    on a grid now and at candidates later, and maximised."""
+    on a grid now and at candidates later, and maximised: evaluate_grad / grad give the exact input gradient in one launch
+    (hb_sgp_pathwise_grad), argmax the best of any number of candidates without writing the [S, n] values
+    (hb_sgp_pathwise_argmax), maximise refines each draw's best candidate by gradient ascent (Thompson sampling)."""
 
     def __init__(self, sess, omega, coef, z, ell, scale):
         self._sess = sess
@@ -512,14 +514,99 @@ class PathwiseDraws:
     def evaluate(self, X, out=None):
         """The draws at the rows of X as a device tensor [S, n] of the session's dtype (`out`: written in place).  X: a
         Data / MinibatchData of the model (read in full from its device buffer), a device tensor or an array [n, d]."""
-        Xd = _host.device_data(self._sess, X, "X")
-        if Xd.shape[1] != self._z.shape[1]:
-            raise ValueError("PathwiseDraws: X %s does not match z %s" % (tuple(Xd.shape), tuple(self._z.shape)))
-        return self._sess.H.sgp_pathwise(Xd, self._omega, self._z, self._ell, self._coef, scale=self.scale, out=out)
+        return self._sess.H.sgp_pathwise(self._points(X), self._omega, self._z, self._ell, self._coef, scale=self.scale, out=out)
 
     def __call__(self, X):
         """The draws at the rows of X as numpy [S, n]."""
         return self.evaluate(X).cpu().numpy()
+
+    def _points(self, X):
+        Xd = _host.device_data(self._sess, X, "X")
+        if Xd.shape[1] != self._z.shape[1]:
+            raise ValueError("PathwiseDraws: X %s does not match z %s" % (tuple(Xd.shape), tuple(self._z.shape)))
+        return Xd
+
+    def evaluate_grad(self, X, values=True):
+        """(values [S, n] or None, grad [S, n, d]) as device tensors: grad[s, j, k] = d f_s(x_j) / d x_jk, exact (a draw is
+        a closed-form function), from ONE launch of hb_sgp_pathwise_grad.  The values are the bits of evaluate(X)."""
+        return self._sess.H.sgp_pathwise_grad(self._points(X), self._omega, self._z, self._ell, self._coef, scale=self.scale,
+                                              values=values)
+
+    def grad(self, X):
+        """The input gradients of the draws at the rows of X as numpy [S, n, d]."""
+        return self.evaluate_grad(X, values=False)[1].cpu().numpy()
+
+    def argmax(self, X, largest=True):
+        """(idx int64 [S], value [S]) as numpy: for every draw the row of X at which it is largest (smallest with
+        largest=False; ties: the first row) and its value there -- np.argmax(draws(X), 1) and the values it points at, bit
+        for bit, from hb_sgp_pathwise_argmax: the [S, n] matrix is never written, so n can be millions of candidates."""
+        best, idx = self._sess.H.sgp_pathwise_argmax(self._points(X), self._omega, self._z, self._ell, self._coef,
+                                                     scale=self.scale, largest=largest)
+        return idx.cpu().numpy(), best.cpu().numpy()
+
+    def maximise(self, X, steps=50, lr=0.05, bounds=None, largest=True):
+        """(x_best [S, d], f_best [S], info): every draw maximised (minimised with largest=False) over the box `bounds`,
+        starting from its own best candidate among the rows of X (argmax) and refined by `steps` steps of Adam ascent on
+        the exact input gradient.  The optimiser runs on the host in float64 (beta = 0.9 / 0.999, epsilon = 1e-8, as the
+        hyper-parameter fits) in lengthscale units u = x / ell, d f / d u = ell d f / d x, so that lr is a fraction of a
+        lengthscale whatever the units of the data; after each step u is projected onto the box.  bounds = (lo [d],
+        hi [d]); default: the per-column minimum and maximum of the candidates.  Each evaluation is ONE evaluate_grad launch
+        at the S current points rounded to the session's dtype (the diagonal of its [S, S] result is used); `steps` steps
+        take steps + 1 of them -- the start, for its gradient, and the point after every step -- on top of the two
+        launches of argmax; steps = 0 takes none.  The best (value,
+        point) seen is kept per draw, the start included: f_best is never worse than the candidates' extremum, and it is
+        the bits of evaluate(x_best)[s, s].  info = dict(start_idx int64 [S], start_value [S], steps).  steps = 50 and
+        lr = 0.05 are defaults, not measurements: with Adam's unit-sized steps they move a point by at most about 2.5
+        lengthscales and settle within a few hundredths of one.  steps < 0, lr <= 0, bounds of another shape or with
+        lo > hi, and X of another width raise ValueError."""
+        sess = self._sess
+        Xd = self._points(X)
+        d, S, dt = int(Xd.shape[1]), self.num_samples, np.dtype(sess.np_dtype).type
+        steps = int(steps)
+        if steps < 0 or not float(lr) > 0.0:
+            raise ValueError("maximise: steps >= 0 and lr > 0 expected (got %r, %r)" % (steps, lr))
+        if Xd.shape[0] < 1:
+            raise ValueError("maximise: at least one candidate expected")
+        if bounds is None:
+            lo, hi = (np.asarray(t.cpu().numpy(), np.float64) for t in (Xd.min(dim=0).values, Xd.max(dim=0).values))
+        else:
+            if len(bounds) != 2:
+                raise ValueError("maximise: bounds = (lo [d], hi [d]) expected")
+            lo, hi = (np.asarray(b, np.float64) for b in bounds)
+            if lo.shape != (d,) or hi.shape != (d,) or not np.all(lo <= hi):
+                raise ValueError("maximise: bounds = (lo [%d], hi [%d]) with lo <= hi expected" % (d, d))
+        # the box as the session's dtype can hold it: the rounded iterates stay inside [lo, hi]
+        lo_r, hi_r = lo.astype(dt), hi.astype(dt)
+        lo_r = np.where(lo_r < lo, np.nextafter(lo_r, dt(np.inf)), lo_r)
+        hi_r = np.where(hi_r > hi, np.nextafter(hi_r, dt(-np.inf)), hi_r)
+        ell = np.broadcast_to(np.asarray(self._ell.cpu().numpy(), np.float64), (d,))
+        sign = 1.0 if largest else -1.0
+        idx, f0 = self.argmax(Xd, largest=largest)
+        if np.any(idx < 0):
+            raise ValueError("maximise: draw %d has no comparable value among the candidates" % int(np.argmax(idx < 0)))
+        x = Xd[sess.torch.as_tensor(idx, device=Xd.device)].cpu().numpy()       # [S, d], the session's dtype
+        x_best, f_best = x.copy(), f0.copy()
+        info = dict(start_idx=idx, start_value=f0.copy(), steps=steps)
+        u = x.astype(np.float64) / ell
+        m1, m2 = np.zeros_like(u), np.zeros_like(u)
+        b1, b2, eps = 0.9, 0.999, 1e-8
+        ar = np.arange(S)
+        if steps:   # steps + 1 evaluations: t = 0 is the start (its value is known, its gradient is not)
+            for t in range(steps + 1):
+                f, g = self.evaluate_grad(x)
+                f, g = f.cpu().numpy()[ar, ar], g.cpu().numpy()[ar, ar].astype(np.float64)
+                better = sign * f.astype(np.float64) > sign * f_best.astype(np.float64)
+                x_best[better], f_best[better] = x[better], f[better]
+                if t == steps:
+                    break
+                gu = sign * ell * g
+                m1 = b1 * m1 + (1.0 - b1) * gu
+                m2 = b2 * m2 + (1.0 - b2) * gu ** 2
+                u = u + float(lr) * (m1 / (1.0 - b1 ** (t + 1))) / (np.sqrt(m2 / (1.0 - b2 ** (t + 1))) + eps)
+                u = np.clip(u, lo / ell, hi / ell)
+                x = np.clip((u * ell).astype(dt), lo_r, hi_r)
+                x = np.where(u >= hi / ell, hi_r, np.where(u <= lo / ell, lo_r, x))   # on a face: the face itself, exactly
+        return x_best, f_best, info
 
     def _view(self, t):
         a = t.cpu().numpy()

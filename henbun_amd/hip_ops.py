@@ -1177,18 +1177,7 @@ def sgp_pathwise(x, omega, z, ell, coef, scale=1.0, out=None):
     B = [cos / sin (omega_l . x / ell) interleaved | K(z_m, x)] synthesised inside the ONE launch.  x [n, d], omega [L, d],
     z [M, d] or None (M = 0: the prior path alone), ell [1] or [d], coef [S, 2L + M], all of one dtype.  The value of a
     column does not depend on the other columns: two calls, or x in pieces, return the same bits."""
-    for t in (x, omega, ell, coef) + (() if z is None else (z,)):
-        _chk(t)
-    if x.dim() != 2 or omega.dim() != 2 or coef.dim() != 2 or omega.shape[1] != x.shape[1] or (
-            z is not None and (z.dim() != 2 or z.shape[1] != x.shape[1])):
-        raise ValueError("sgp_pathwise: x [n, d], omega [L, d], z [M, d] or None, coef [S, 2L + M] expected, got %s %s %s %s"
-                         % (tuple(x.shape), tuple(omega.shape), None if z is None else tuple(z.shape), tuple(coef.shape)))
-    n, d = x.shape
-    L, M, S = omega.shape[0], 0 if z is None else z.shape[0], coef.shape[0]
-    if coef.shape[1] != 2 * L + M:
-        raise ValueError("sgp_pathwise: coef must hold 2L + M = %d columns, got %s" % (2 * L + M, tuple(coef.shape)))
-    if any(t.dtype != x.dtype for t in (omega, ell, coef)) or (z is not None and z.dtype != x.dtype):
-        raise TypeError("sgp_pathwise: all operands must share one dtype")
+    n, d, L, M, S = _pathwise_shapes("sgp_pathwise", x, omega, z, ell, coef)
     if out is None:
         out = _empty((S, n), dtype=x.dtype, device=x.device)
     else:
@@ -1198,6 +1187,77 @@ def sgp_pathwise(x, omega, z, ell, coef, scale=1.0, out=None):
     _lib.lib().call("hb_sgp_pathwise" + _suf(x), KERN_RBF, _p(x), _p(omega), _p(z if M else None), _p(ell), ell.numel(), _p(coef),
                     float(scale), _p(out), n, L, M, d, S, stream())
     return out
+
+
+def _pathwise_shapes(who, x, omega, z, ell, coef):
+    """(n, d, L, M, S) of the operands of a pathwise entry (sgp_pathwise, sgp_pathwise_grad, sgp_pathwise_argmax), checked:
+    on the device, contiguous, shapes that fit, one dtype."""
+    for t in (x, omega, ell, coef) + (() if z is None else (z,)):
+        _chk(t)
+    if x.dim() != 2 or omega.dim() != 2 or coef.dim() != 2 or omega.shape[1] != x.shape[1] or (
+            z is not None and (z.dim() != 2 or z.shape[1] != x.shape[1])):
+        raise ValueError("%s: x [n, d], omega [L, d], z [M, d] or None, coef [S, 2L + M] expected, got %s %s %s %s"
+                         % (who, tuple(x.shape), tuple(omega.shape), None if z is None else tuple(z.shape), tuple(coef.shape)))
+    n, d = x.shape
+    L, M, S = omega.shape[0], 0 if z is None else z.shape[0], coef.shape[0]
+    if coef.shape[1] != 2 * L + M:
+        raise ValueError("%s: coef must hold 2L + M = %d columns, got %s" % (who, 2 * L + M, tuple(coef.shape)))
+    if any(t.dtype != x.dtype for t in (omega, ell, coef)) or (z is not None and z.dtype != x.dtype):
+        raise TypeError("%s: all operands must share one dtype" % who)
+    return n, d, L, M, S
+
+
+def sgp_pathwise_grad(x, omega, z, ell, coef, scale=1.0, out=None, grad=None, values=True):
+    """Values and input gradients of S pathwise function draws in ONE launch (hb_sgp_pathwise_grad): (out [S, n], grad
+    [S, n, d]) with grad[s, j, k] = d out[s, j] / d x_jk, operands as for sgp_pathwise.  values=False: the values are not
+    stored, `out` (if given) is left untouched and None is returned in its place.  `out` carries the bits of sgp_pathwise;
+    out[s, j] and grad[s, j, :] depend neither on the other columns nor on the other draws: two calls, x in pieces, or a
+    subset of the draws return the same bits."""
+    n, d, L, M, S = _pathwise_shapes("sgp_pathwise_grad", x, omega, z, ell, coef)
+    if values:
+        if out is None:
+            out = _empty((S, n), dtype=x.dtype, device=x.device)
+        else:
+            _chk(out)
+            if tuple(out.shape) != (S, n) or out.dtype != x.dtype:
+                raise ValueError("sgp_pathwise_grad: out must be [%d, %d] of the operands' dtype" % (S, n))
+    if grad is None:
+        grad = _empty((S, n, d), dtype=x.dtype, device=x.device)
+    else:
+        _chk(grad)
+        if tuple(grad.shape) != (S, n, d) or grad.dtype != x.dtype:
+            raise ValueError("sgp_pathwise_grad: grad must be [%d, %d, %d] of the operands' dtype" % (S, n, d))
+    _lib.lib().call("hb_sgp_pathwise_grad" + _suf(x), KERN_RBF, _p(x), _p(omega), _p(z if M else None), _p(ell), ell.numel(),
+                    _p(coef), float(scale), _p(out if values else None), _p(grad), n, L, M, d, S, stream())
+    return (out if values else None), grad
+
+
+def sgp_pathwise_argmax_ws_elems(dtype, n, S):
+    """Scratch elements (of the operands' dtype, whichever it is) hb_sgp_pathwise_argmax needs: 2 S ceil(n / 128)."""
+    return int(_lib.lib().raw("hb_sgp_pathwise_argmax_ws_elems")(int(n), int(S)))
+
+
+def sgp_pathwise_argmax(x, omega, z, ell, coef, scale=1.0, largest=True, ws=None):
+    """The extremum of each of S pathwise function draws over the rows of x (hb_sgp_pathwise_argmax): (best [S], idx int64
+    [S]) device tensors with best[s] = max_j (largest) or min_j of sgp_pathwise(...)[s, j] -- those bits -- and idx[s] its
+    first column; the [S, n] values are never written.  A NaN is never chosen; a draw with no comparable value reports
+    idx = -1 and best = -inf (+inf for the minimum).  n >= 1.  `ws`: sgp_pathwise_argmax_ws_elems elements (default: the
+    shared scratch of the stream)."""
+    n, d, L, M, S = _pathwise_shapes("sgp_pathwise_argmax", x, omega, z, ell, coef)
+    if n < 1:
+        raise ValueError("sgp_pathwise_argmax: at least one candidate expected, got x %s" % (tuple(x.shape),))
+    best = _empty((S,), dtype=x.dtype, device=x.device)
+    idx = _empty((S,), dtype=torch.int64, device=x.device)
+    need = sgp_pathwise_argmax_ws_elems(x.dtype, n, S)
+    if ws is None:
+        ws = workspace(x.dtype, x.device, max(need, 1))
+    _chk(ws)
+    if ws.dtype != x.dtype or ws.numel() < need:
+        raise ValueError("sgp_pathwise_argmax: the workspace must hold %d elements of %s (sgp_pathwise_argmax_ws_elems)"
+                         % (need, x.dtype))
+    _lib.lib().call("hb_sgp_pathwise_argmax" + _suf(x), KERN_RBF, _p(x), _p(omega), _p(z if M else None), _p(ell), ell.numel(),
+                    _p(coef), float(scale), 1 if largest else 0, _p(best), _p(idx), n, L, M, d, S, _p(ws), stream())
+    return best, idx
 
 
 def gram_matvec_chunk():

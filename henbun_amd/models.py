@@ -149,7 +149,7 @@ class SVGP(hb.model.Model):
         model's q(u), scaled by sqrt(k_var)): draws = model.sample_functions(16); draws(Xnew) is numpy [16, n], linear in
         n, and every call evaluates the SAME sample paths.  The draws carry the exact conditional of the sparse GP (the
         'fullrank' residual) whatever `residual` the model trains with; predict_f_samples stays the exact joint route for
-        small n."""
+        small n.  draws.argmax(candidates) and draws.maximise(candidates) pick each draw's next point (Thompson sampling)."""
         self.initialize()
         return _part(self, "gp").pathwise_draws(_part(self, "u"), num_samples, num_features=num_features,
                                                 k_var=_scalar(self, "k_var"), seed=seed, noise=noise)
@@ -423,7 +423,8 @@ class ExactGPR(hb.model.Model):
         return self._posterior().predict_y(Xnew, var=var)
 
     def sample_functions(self, num_samples, num_features=1024, seed=0, noise=None):
-        """num_samples exact posterior function draws as an hb.gp.PathwiseDraws (ExactPosterior.sample_functions)."""
+        """num_samples exact posterior function draws as an hb.gp.PathwiseDraws (ExactPosterior.sample_functions); its
+        grad, argmax and maximise work as for the sparse models."""
         return self._posterior().sample_functions(num_samples, num_features=num_features, seed=seed, noise=noise)
 
 

@@ -55,7 +55,8 @@ extern "C" {
  * (matrix-free kernel product and the vector steps of lockstep preconditioned conjugate gradients: exact GP regression);
  * hb_gram_bilinear_grad_f32 / _f64 and hb_pcg_*_coef (the exact GP's log marginal likelihood and its gradient);
  * hb_sgp_bwd_phi_f32 and hb_sgp_bwd_phi_supported (the sparse-GP backward that writes the Cholesky VJP's operand
- * Phisym(-Abar A^T) where hb_sgp_bwd_f32 writes Lbar). */
+ * Phisym(-Abar A^T) where hb_sgp_bwd_f32 writes Lbar); hb_sgp_pathwise_grad_f32 / _f64, hb_sgp_pathwise_argmax_f32 / _f64
+ * and hb_sgp_pathwise_argmax_ws_elems (input gradients and the per-draw extremum of pathwise function draws). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -690,6 +691,40 @@ int hb_sgp_pathwise_f32(int kind, const float* x, const float* omega, const floa
                         const float* coef, double scale, float* out, long n, long L, long M, long d, long S, void* stream);
 int hb_sgp_pathwise_f64(int kind, const double* x, const double* omega, const double* z, const double* ell, long dl,
                         const double* coef, double scale, double* out, long n, long L, long M, long d, long S, void* stream);
+/* Maximising pathwise function draws (csrc/sgp_pathwise_grad.hip; not in the reference).  Arguments, limits and validation
+ * are those of hb_sgp_pathwise_* unless stated; both share its synthesis, coef staging and K order (csrc/sgp_pathwise.cuh).
+ *
+ * hb_sgp_pathwise_grad: values and input gradients in ONE launch,
+ *   grad[s, j, k] = d out[s, j] / d x_jk
+ *                 = scale ( sum_{l<L} (omega_lk / ell_k) [ -coef[s, 2l] sin(p_lj) + coef[s, 2l+1] cos(p_lj) ]
+ *                           + sum_{m<M} coef[s, 2L+m] K(z_m, x_j) (z_mk - x_jk) / ell_k^2 ),
+ * grad [S, n, d] row-major, non-NULL; out [S, n] or NULL (the values are then not stored).  The derivative operands are
+ * formed in registers from the value tile (trig rows swapped and scaled by the signed omega_lk / ell_k, RBF rows scaled by
+ * (z_mk - x_jk) / ell_k^2): no transcendental beyond those of the value.  32 draws per workgroup (16 for double at d >= 3);
+ * d <= 4 in one workgroup, larger d in groups of 4 dimensions on the grid's z.  n = 0 returns without a launch; additionally S n d must be below
+ * 2^31.  `out` is bit-identical to hb_sgp_pathwise on the same inputs; every out[s, j] and grad[s, j, :] is independent of
+ * the other columns and of the other draws: two calls, x in pieces, or a subset of the draws return the same bits.
+ *
+ * hb_sgp_pathwise_argmax: best[s] = max_j out[s, j] (largest != 0) or min_j (largest == 0) and idx[s] its first column,
+ * out[s, j] being exactly the number hb_sgp_pathwise stores -- and [S, n] is never written.  Each workgroup reduces its
+ * strip of 128 columns per draw (registers, lanes, the four waves through LDS) into ws; a second launch, a workgroup per
+ * draw, folds the strips.  No atomics; comparisons are strict and ties go to the lowest column, so a NaN is never chosen:
+ * a draw with no comparable value reports idx = -1 and best = -inf (largest) or +inf.  best [S], idx [S] (long), non-NULL;
+ * n = 0 is rejected (bad extents); ws >= hb_sgp_pathwise_argmax_ws_elems(n, S) = 2 S ceil(n / 128) elements of T, NULL
+ * rejected.  Two calls return the same bits.  Both entries are validated before any launch. */
+int hb_sgp_pathwise_grad_f32(int kind, const float* x, const float* omega, const float* z, const float* ell, long dl,
+                             const float* coef, double scale, float* out, float* grad, long n, long L, long M, long d, long S,
+                             void* stream);
+int hb_sgp_pathwise_grad_f64(int kind, const double* x, const double* omega, const double* z, const double* ell, long dl,
+                             const double* coef, double scale, double* out, double* grad, long n, long L, long M, long d, long S,
+                             void* stream);
+long hb_sgp_pathwise_argmax_ws_elems(long n, long S);
+int hb_sgp_pathwise_argmax_f32(int kind, const float* x, const float* omega, const float* z, const float* ell, long dl,
+                               const float* coef, double scale, int largest, float* best, long* idx, long n, long L, long M,
+                               long d, long S, float* ws, void* stream);
+int hb_sgp_pathwise_argmax_f64(int kind, const double* x, const double* omega, const double* z, const double* ell, long dl,
+                               const double* coef, double scale, int largest, double* best, long* idx, long n, long L, long M,
+                               long d, long S, double* ws, void* stream);
 /* Matrix-free kernel product (csrc/gram_matvec.hip; not in the reference; Gardner et al. 2018, Wang et al. 2019):
  *   out[s, j] = scale * sum_{i<N} V[s, i] k(x2_i, x_j) + shift * V[s, j],     s < S, j < n,
  * the product a conjugate-gradient solve with K(X, X) + sigma^2 I asks for, and the exact posterior mean at new points.
