@@ -162,12 +162,7 @@ struct Mma<double> {
 #include "rng_core.cuh"      // HbRng, rng_load / rng_store
 #include "chain_bodies.cuh"  // bodies of the small kernels (shared with the run-time generated serial chains)
 
-__host__ __device__ static inline uint64_t hb_splitmix64(uint64_t& x) {
-  uint64_t z = (x += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+#include "rng_seed.cuh"      // hb_splitmix64, hb_rng_seed_lane
 
 // l = sqrt(d), inv = 1/l.  fp32: one v_rsq_f32 (1 ulp) + one multiply instead of the IEEE sqrt and
 // divide sequences (~25 instructions on the critical path of every column); fp64 keeps the exact forms.

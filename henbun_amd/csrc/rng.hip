@@ -14,11 +14,8 @@ __global__ void __launch_bounds__(256) rng_init_kernel(uint64_t* state, long nla
                                                        uint64_t stream_id) {
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nlanes) return;
-  uint64_t x = seed ^ (stream_id * 0xD1342543DE82EF95ull) ^ ((uint64_t)t * 0x9E3779B97F4A7C15ull);
-  x = hb_splitmix64(x) ^ (uint64_t)t;
-  uint64_t a = hb_splitmix64(x);
-  uint64_t b = hb_splitmix64(x);
-  if (a == 0 && b == 0) b = 0x9E3779B97F4A7C15ull;
+  uint64_t a, b;
+  hb_rng_seed_lane(seed, stream_id, (uint64_t)t, a, b);
   state[t] = a;
   state[nlanes + t] = b;
 }
