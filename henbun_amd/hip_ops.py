@@ -5,6 +5,10 @@ memory, `tensor.data_ptr()` for the raw pointer and the current stream handle.
 No torch op computes anything on this path -- every function below is one (or
 a fixed few) launches of hand-written HIP kernels through ctypes.  If the
 backend library is missing, `_lib.lib()` raises; there is no fallback.
+
+The header is the only place that states an enum value or a signature: the
+constants below are looked up in `_lib.constants()`, and `_lib` binds every
+entry point from its prototype and rejects a call with the wrong argument count.
 """
 from __future__ import annotations
 
@@ -16,29 +20,28 @@ import torch
 
 from . import _lib
 
-# ---- enums mirrored from include/henbun_hip.h -------------------------------
-EW = dict(
-    NEG=1, EXP=2, LOG=3, SQRT=4, SQUARE=5, ABS=6, SIGN=7, SIGMOID=8, RELU=9, SOFTPLUS=10, TANH=11,
-    RECIP=12, RSQRT=13, STEP=14, AFFINE=15, CLIP=16, CLIPMASK=17, LGAMMA=18, POWC=19, LOG1P=20,
-    COPY=21, DIGAMMA=22,
-    ADD=32, SUB=33, MUL=34, DIV=35, MAX=36, MIN=37, POW=38, GT=39, GE=40, LT=41, LE=42, EQ=43,
-    SIGMOID_GRAD=44, TANH_GRAD=45, RELU_GRAD=46, SOFTPLUS_GRAD=47, CLIP_GRAD=48,
-    WHERE=64, FMA=65, GAUSS_LOGPDF=66,
-    GAUSS_LOGPDF_GRAD=80,
-)
-RED_SUM, RED_MAX = 0, 1
-KERN_RBF, KERN_CSYM_RBF, KERN_SQDIST = 0, 1, 2
-KERN_KBAR_SYMMETRIC = 256   # OR-ed into the kind of gram_bwd: Kbar is symmetric (no transposed reads)
-EW_PROG_SUM = 256
-MM_LOWER_OUT = 1
-MM_TRIL_OUT = 2
-MM_PHI_OUT = 4
-MM_SYM_OUT = 8
-MM_SYMLOW_OUT = 32
-MM_ACTGRAD = 16
-ACT = dict(none=0, sigmoid=1, relu=2, tanh=3)
-SGP_NEGLECTED, SGP_DIAGONAL, SGP_FULLRANK = 0, 1, 2
-SGP_S_DIAG, SGP_S_TRIL = 0, 1
+# ---- enums of include/henbun_hip.h: read from the header, never restated --------
+_C = _lib.constants()
+
+
+def _hb(*names):
+    return [_C["HB_" + n] for n in names]
+
+
+EW = {k[len("HB_EW_"):]: v for k, v in _C.items() if k.startswith("HB_EW_") and k != "HB_EW_PROG_SUM"}
+RED_SUM, RED_MAX = _hb("RED_SUM", "RED_MAX")
+KERN_RBF, KERN_CSYM_RBF, KERN_SQDIST = _hb("KERN_RBF", "KERN_CSYM_RBF", "KERN_SQDIST")
+KERN_KBAR_SYMMETRIC = _C["HB_KERN_KBAR_SYMMETRIC"]   # OR-ed into the kind of gram_bwd: Kbar is symmetric (no transposed reads)
+EW_PROG_SUM = _C["HB_EW_PROG_SUM"]
+COLPROG_SUM, COLPROG_MAX = _hb("COLPROG_SUM", "COLPROG_MAX")   # row reductions of a column program
+MM_LOWER_OUT, MM_TRIL_OUT, MM_PHI_OUT, MM_SYM_OUT = _hb("MM_LOWER_OUT", "MM_TRIL_OUT", "MM_PHI_OUT", "MM_SYM_OUT")
+MM_SYMLOW_OUT, MM_ACTGRAD = _hb("MM_SYMLOW_OUT", "MM_ACTGRAD")
+ACT = {k[len("HB_ACT_"):].lower(): v for k, v in _C.items() if k.startswith("HB_ACT_")}
+SGP_NEGLECTED, SGP_DIAGONAL, SGP_FULLRANK = _hb("SGP_NEGLECTED", "SGP_DIAGONAL", "SGP_FULLRANK")
+SGP_S_DIAG, SGP_S_TRIL = _hb("SGP_S_DIAG", "SGP_S_TRIL")
+PREC_NATIVE, PREC_BF16X3 = _hb("PREC_NATIVE", "PREC_BF16X3")
+LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON = _hb("LIK_GAUSSIAN", "LIK_BERNOULLI", "LIK_POISSON")
+# hb_matutil's modes are plain integers in the header
 MATUTIL_BAND, MATUTIL_ADD_EYE, MATUTIL_PHI, MATUTIL_SYM = 0, 1, 2, 3
 
 WS_ELEMS = 1 << 16  # generic scratch (elements) for reductions / KL partials
@@ -50,6 +53,10 @@ def _suf(t: torch.Tensor) -> str:
     if t.dtype == torch.float64:
         return "_f64"
     raise TypeError("henbun_amd kernels compute in float32 or float64, got %s" % t.dtype)
+
+
+def _elem_bytes(dtype) -> int:
+    return 4 if dtype == torch.float32 else 8
 
 
 def stream() -> int:
@@ -242,7 +249,6 @@ class EwiseProgram:
                 pass
 
 
-COLPROG_SUM, COLPROG_MAX = -1, -2   # row reductions of a column program (HB_COLPROG_* in include/henbun_hip.h)
 
 
 class ColProgram:
@@ -733,7 +739,6 @@ def matmul_colsum(A, B, out=None, colsum=None):
     return out, colsum
 
 
-ACTS = {"none": 0, "sigmoid": 1, "relu": 2, "tanh": 3}
 
 
 def mlp2_sample_supported(n, din, hid, nout, rng_lanes=0, has_u=True):
@@ -759,7 +764,7 @@ def mlp2_sample_fwd(y, w0, b0, w1, b1, act, u_in=None, rng=None, out=None, ws=No
     x, kl, u, o = out
     if ws is None:
         ws = mlp2_sample_ws(n, din, hid, y.device)
-    _lib.lib().call("hb_mlp2_sample_fwd_f32", _p(y), _p(w0), _p(b0), _p(w1), _p(b1), ACTS[act], _p(u_in),
+    _lib.lib().call("hb_mlp2_sample_fwd_f32", _p(y), _p(w0), _p(b0), _p(w1), _p(b1), ACT[act], _p(u_in),
                     _p(rng.state) if (rng is not None and u_in is None) else None, rng.nlanes if rng is not None else 0,
                     _p(x), _p(kl), _p(u), _p(o), n, din, hid, _p(ws), stream())
     return x, kl, u, o
@@ -774,7 +779,7 @@ def mlp2_sample_bwd(y, w0, b0, w1, act, o, u, x, xbar, klbar, out=None, ws=None)
     dw0, db0, dw1, db1 = out
     if ws is None:
         ws = mlp2_sample_ws(n, din, hid, y.device)
-    _lib.lib().call("hb_mlp2_sample_bwd_f32", _p(y), _p(w0), _p(b0), _p(w1), ACTS[act], _p(o), _p(u), _p(x), _p(xbar), _p(klbar),
+    _lib.lib().call("hb_mlp2_sample_bwd_f32", _p(y), _p(w0), _p(b0), _p(w1), ACT[act], _p(o), _p(u), _p(x), _p(xbar), _p(klbar),
                     _p(dw0), _p(db0), _p(dw1), _p(db1), n, din, hid, _p(ws), stream())
     return dw0, db0, dw1, db1
 
@@ -799,7 +804,6 @@ def cholesky(A, out=None, info=None):
     return out, info
 
 
-PREC_NATIVE, PREC_BF16X3 = 0, 1
 
 _chol_ws_cache = {}
 
@@ -814,7 +818,7 @@ def debug_clear():
 
 
 def cholesky_ws_elems(B, M, dtype):
-    return int(_lib.lib().raw("hb_cholesky_inverse_ws_elems")(B, M, 4 if dtype == torch.float32 else 8))
+    return int(_lib.lib().raw("hb_cholesky_inverse_ws_elems")(B, M, _elem_bytes(dtype)))
 
 
 def cholesky_workspace(dtype, device, B, M):
@@ -853,7 +857,7 @@ def cholesky_inverse(A, out=None, inv=None, info=None, ws=None, frag=None, frag_
 
 def cholesky_persistent_shape(B, M, dtype):
     """hb_cholesky_inverse takes its one-launch persistent form for this (B, M, dtype)."""
-    return bool(_lib.lib().raw("hb_cholesky_persistent_shape")(B, M, 4 if dtype == torch.float32 else 8))
+    return bool(_lib.lib().raw("hb_cholesky_persistent_shape")(B, M, _elem_bytes(dtype)))
 
 
 def gram_cholesky_inverse(X, ell, diag_add, kind=KERN_RBF, out=None, inv=None, info=None, ws=None, frag=None, frag_bf16x3=False):
@@ -1060,7 +1064,7 @@ def sgp_predict_fused(dtype, E, n, M, d, P, s_kind, has_wfrag):
 def sgp_predict_ws_elems(dtype, E, n, M, d, P, s_kind, has_wfrag):
     """Scratch elements hb_sgp_predict needs (bounded by one column chunk, not by n)."""
     return int(_lib.lib().raw("hb_sgp_predict_ws_elems")(int(E), int(n), int(M), int(d), int(P), int(s_kind),
-                                                         int(bool(has_wfrag)), 4 if dtype == torch.float32 else 8))
+                                                         int(bool(has_wfrag)), _elem_bytes(dtype)))
 
 
 def sgp_predict(x, z, ell, W, m, s, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, jitter=0.0, out=None, wfrag=None, ws=None):
@@ -1087,7 +1091,7 @@ def sgp_predict(x, z, ell, W, m, s, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, jitter
 def sgp_predict_cov_ws_elems(dtype, E, n, M, P, s_kind):
     """Scratch elements hb_sgp_predict_cov needs: A [E, M, n], C = S^T A [M, n] (full-rank S), a2 [E, n] -- linear in n."""
     return int(_lib.lib().raw("hb_sgp_predict_cov_ws_elems")(int(E), int(n), int(M), int(P), int(s_kind),
-                                                             4 if dtype == torch.float32 else 8))
+                                                             _elem_bytes(dtype)))
 
 
 def sgp_predict_cov(x, z, ell, W, s, P, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, jitter=0.0, out=None, wfrag=None, ws=None):
@@ -1111,7 +1115,7 @@ def sgp_predict_cov(x, z, ell, W, s, P, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, ji
 def sgp_stats_ws_elems(dtype, N, M, d, P):
     """Scratch elements hb_sgp_stats needs: one column chunk of A plus the K-split partial tiles -- the same for every
     N above one chunk."""
-    return int(_lib.lib().raw("hb_sgp_stats_ws_elems")(int(N), int(M), int(d), int(P), 4 if dtype == torch.float32 else 8))
+    return int(_lib.lib().raw("hb_sgp_stats_ws_elems")(int(N), int(M), int(d), int(P), _elem_bytes(dtype)))
 
 
 def sgp_stats(X, Y, z, ell, W, wfrag=None, ws=None):
@@ -1144,7 +1148,7 @@ def sgp_stats(X, Y, z, ell, W, wfrag=None, ws=None):
 
 def sgp_wstats_ws_elems(dtype, N, M, d):
     """Scratch elements hb_sgp_wstats needs (those of hb_sgp_stats with P = 1; the same for every N above one chunk)."""
-    return int(_lib.lib().raw("hb_sgp_wstats_ws_elems")(int(N), int(M), int(d), 4 if dtype == torch.float32 else 8))
+    return int(_lib.lib().raw("hb_sgp_wstats_ws_elems")(int(N), int(M), int(d), _elem_bytes(dtype)))
 
 
 def sgp_wstats(X, w, r, z, ell, W, wfrag=None, ws=None):
@@ -1268,7 +1272,7 @@ def gram_matvec_chunk():
 def gram_matvec_ws_elems(dtype, n, N, S):
     """Scratch elements hb_gram_matvec needs: 0 when N fits one chunk, chunks x S x n up to 16 chunks, beyond that 16 S n
     plus S n doubles -- O(S n) whatever N."""
-    return int(_lib.lib().raw("hb_gram_matvec_ws_elems")(int(n), int(N), int(S), 4 if dtype == torch.float32 else 8))
+    return int(_lib.lib().raw("hb_gram_matvec_ws_elems")(int(n), int(N), int(S), _elem_bytes(dtype)))
 
 
 def gram_matvec(x, x2, ell, V, scale=1.0, shift=0.0, out=None, ws=None, kind=KERN_RBF):
@@ -1405,7 +1409,6 @@ def gram_bilinear_grad(x, ell, A, B, w, out=None, ws=None, kind=KERN_RBF):
     return out
 
 
-LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON = 0, 1, 2
 
 
 def lik_sites(lik, y, mean, var, param=1.0, mscale=1.0, vscale=1.0, out=None):
@@ -1505,7 +1508,7 @@ def sgp_wkgrad(X, w, r, z, ell, Q, R, ws=None):
 
 def sgp_select_ws_elems(dtype, N, M, d):
     """Scratch elements hb_sgp_select needs: the history C [M, N], dvar [N] and the arg-max partials -- O(M N)."""
-    return int(_lib.lib().raw("hb_sgp_select_ws_elems")(int(N), int(M), int(d), 4 if dtype == torch.float32 else 8))
+    return int(_lib.lib().raw("hb_sgp_select_ws_elems")(int(N), int(M), int(d), _elem_bytes(dtype)))
 
 
 def sgp_select(X, ell, M, threshold=0.0, ws=None):
