@@ -48,6 +48,13 @@ template <> __device__ __forceinline__ void pw_sincos<float>(double rev, float& 
 }
 template <> __device__ __forceinline__ void pw_sincos<double>(double rev, double& s, double& c) { pw_sincos_rev<9, 10>(rev, s, c); }
 
+// The arg-max rule of hb_sgp_pathwise_argmax and hb_sgp_acq (comparisons strict, ties to the lowest column, a NaN or an
+// empty slot j < 0 never taken): (k2, j2) takes over from (k1, j1): it holds a value, and the other holds none, a smaller key, or the same at a later column
+template <typename T>
+__device__ __forceinline__ bool pw_takes(T k2, long j2, T k1, long j1) {
+  return j2 >= 0 && (j1 < 0 || k2 > k1 || (k2 == k1 && j2 < j1));
+}
+
 template <typename T>
 struct PwArgs {
   const T* x;      // [n, d]

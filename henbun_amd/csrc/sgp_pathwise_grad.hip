@@ -179,12 +179,6 @@ struct PwArgmaxArgs {
   T* ws;           // keys [S, strips], then columns within the strip [S, strips] (-1: no comparable value)
 };
 
-// (k2, j2) takes over from (k1, j1): it holds a value, and the other holds none, a smaller key, or the same at a later column
-template <typename T>
-__device__ __forceinline__ bool pw_takes(T k2, long j2, T k1, long j1) {
-  return j2 >= 0 && (j1 < 0 || k2 > k1 || (k2 == k1 && j2 < j1));
-}
-
 template <typename T, int D, int NST>
 __global__ void __launch_bounds__(PW_THREADS) sgp_pathwise_argmax_kernel(PwArgmaxArgs<T> aa) {
   typedef PwMma<T> MM;

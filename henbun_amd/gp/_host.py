@@ -66,6 +66,53 @@ def pathwise_noise(sess, who, noise, seed, shapes, double=False):
     return tuple(upload(sess, noise[k], np.float64 if double else None) for k in names)
 
 
+def ascent_box(who, Xd, bounds, d, dt):
+    """(lo, hi, lo_r, hi_r) of a projected ascent over candidates Xd [n, d]: bounds = (lo [d], hi [d]) in float64 (None:
+    the per-column minimum and maximum of the candidates) and the box as the numpy type `dt` can hold it, so that the
+    rounded iterates stay inside [lo, hi].  Bounds of another shape or with lo > hi raise ValueError."""
+    if bounds is None:
+        lo, hi = (np.asarray(t.cpu().numpy(), np.float64) for t in (Xd.min(dim=0).values, Xd.max(dim=0).values))
+    else:
+        if len(bounds) != 2:
+            raise ValueError("%s: bounds = (lo [d], hi [d]) expected" % who)
+        lo, hi = (np.asarray(b, np.float64) for b in bounds)
+        if lo.shape != (d,) or hi.shape != (d,) or not np.all(lo <= hi):
+            raise ValueError("%s: bounds = (lo [%d], hi [%d]) with lo <= hi expected" % (who, d, d))
+    lo_r, hi_r = lo.astype(dt), hi.astype(dt)
+    lo_r = np.where(lo_r < lo, np.nextafter(lo_r, dt(np.inf)), lo_r)
+    hi_r = np.where(hi_r > hi, np.nextafter(hi_r, dt(-np.inf)), hi_r)
+    return lo, hi, lo_r, hi_r
+
+
+def adam_ascent(evaluate, x, f0, ell, box, sign, steps, lr, dt):
+    """(x_best [R, d], f_best [R]): R independent projected Adam ascents (descents with sign = -1) from the rows of x
+    [R, d] (numpy, type `dt`) whose values f0 [R] are known.  evaluate(x) -> (f [R], g [R, d] float64) at the current
+    points.  The optimiser runs on the host in float64 (beta = 0.9 / 0.999, epsilon = 1e-8) in lengthscale units
+    u = x / ell, d f / d u = ell d f / d x; after each step u is projected onto `box` (ascent_box) and rounded to `dt`.
+    `steps` steps take steps + 1 evaluations -- the start, for its gradient, and the point after every step; steps = 0
+    takes none.  The best (value, point) seen is kept per row, the start included."""
+    lo, hi, lo_r, hi_r = box
+    x_best, f_best = x.copy(), f0.copy()
+    u = x.astype(np.float64) / ell
+    m1, m2 = np.zeros_like(u), np.zeros_like(u)
+    b1, b2, eps = 0.9, 0.999, 1e-8
+    if steps:   # steps + 1 evaluations: t = 0 is the start (its value is known, its gradient is not)
+        for t in range(steps + 1):
+            f, g = evaluate(x)
+            better = sign * f.astype(np.float64) > sign * f_best.astype(np.float64)
+            x_best[better], f_best[better] = x[better], f[better]
+            if t == steps:
+                break
+            gu = sign * ell * g
+            m1 = b1 * m1 + (1.0 - b1) * gu
+            m2 = b2 * m2 + (1.0 - b2) * gu ** 2
+            u = u + float(lr) * (m1 / (1.0 - b1 ** (t + 1))) / (np.sqrt(m2 / (1.0 - b2 ** (t + 1))) + eps)
+            u = np.clip(u, lo / ell, hi / ell)
+            x = np.clip((u * ell).astype(dt), lo_r, hi_r)
+            x = np.where(u >= hi / ell, hi_r, np.where(u <= lo / ell, lo_r, x))   # on a face: the face itself, exactly
+    return x_best, f_best
+
+
 def check_info(info, who, of, exc=G.CholeskyError):
     """ONE read-back of a factorisation's `info`; a leading minor of `of` that is not positive raises `exc`."""
     bad = int(info.cpu()[0])

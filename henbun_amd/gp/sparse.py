@@ -468,11 +468,32 @@ class SparseInference:
         coef = torch.cat([cw, V.to(sess.torch_dtype)], dim=1).contiguous()
         return PathwiseDraws(sess, omega, coef, z, ell, float(np.sqrt(k_var)))
 
-    def _q_moments(self, sess, q, M):
-        """(m [1, M], S [M, M] lower or s [M]) of q(u) as float64 device tensors, for pathwise_draws."""
+    # -- closed-form posterior: input gradients and acquisition functions ----------------------------------------------
+    def posterior(self, q, k_var=1.0, residual="diagonal"):
+        """The closed-form posterior of f = sqrt(k_var) (u A(x) + residual) under q(u) as a SparsePosterior: a snapshot
+        (like PathwiseDraws) of z, the lengthscales, W = Lm^-1 with its fragment-major images, and (m, S) of q(u), on the
+        device in the session's dtype, from which predict / predict_grad / acquisition / argmax / maximise run without
+        a graph: the mean and variance of predict_f, their exact input gradients, and the closed-form acquisition
+        functions EI, PI and UCB with their gradients and arg-max over any number of candidates (hb_sgp_predict_grad,
+        hb_sgp_acq).  q as for pathwise_draws; K(z, z) is factorised as the plans do it (_whitening(as_plans=True)).
+        residual: 'diagonal' or 'neglected'.  Restrictions and exception types are those of pathwise_draws."""
+        _check_residual(residual)
+        k_var = float(k_var)
+        if not k_var > 0.0:
+            raise ValueError("posterior: k_var > 0 expected (got %r)" % (k_var,))
+        sess, zvar, ls = self._stats_session("posterior")
+        M = int(zvar.shape[0])
+        m, s = self._q_moments(sess, q, M, who="posterior")
+        z, ell, W, frag = self._whitening(sess, zvar, ls, None, None, "posterior", as_plans=True)
+        dt = sess.torch_dtype
+        return SparsePosterior(sess, z, ell, W, frag, m.reshape(M).to(dt).contiguous(), s.to(dt).contiguous(), residual,
+                               float(settings.numerics.jitter_level), k_var)
+
+    def _q_moments(self, sess, q, M, who="pathwise_draws"):
+        """(m [1, M], S [M, M] lower or s [M]) of q(u) as float64 device tensors, for pathwise_draws and posterior."""
         if isinstance(q, (tuple, list)):
             if len(q) != 2:
-                raise ValueError("pathwise_draws: q = (m [1, M], S [M, M] or s [M]) expected")
+                raise ValueError("%s: q = (m [1, M], S [M, M] or s [M]) expected" % who)
             m, s = (np.asarray(a, dtype=np.float64) for a in q)
         else:
             from .gp import _posterior_of
@@ -485,15 +506,15 @@ class SparseInference:
             plan.check()
             m, s = (np.asarray(plan.value(t), dtype=np.float64) for t in (mt, st))
         if m.ndim >= 2 and int(np.prod(m.shape[:-1])) > 1:
-            raise NotImplementedError("pathwise_draws: one latent function only (q has shape %s)" % (m.shape,))
+            raise NotImplementedError("%s: one latent function only (q has shape %s)" % (who, m.shape))
         if s.ndim >= 2 and s.shape[-2:] == (M, M):
             s = np.tril(s.reshape(M, M))
         elif s.size == M:
             s = s.reshape(M)
         else:
-            raise ValueError("pathwise_draws: S [%d, %d] lower or s [%d] expected, got %s" % (M, M, M, s.shape))
+            raise ValueError("%s: S [%d, %d] lower or s [%d] expected, got %s" % (who, M, M, M, s.shape))
         if m.size != M:
-            raise ValueError("pathwise_draws: m [1, %d] expected, got %s" % (M, m.shape))
+            raise ValueError("%s: m [1, %d] expected, got %s" % (who, M, m.shape))
         return _host.upload(sess, m.reshape(1, M), np.float64), _host.upload(sess, s, np.float64)
 
 
@@ -567,45 +588,20 @@ class PathwiseDraws:
             raise ValueError("maximise: steps >= 0 and lr > 0 expected (got %r, %r)" % (steps, lr))
         if Xd.shape[0] < 1:
             raise ValueError("maximise: at least one candidate expected")
-        if bounds is None:
-            lo, hi = (np.asarray(t.cpu().numpy(), np.float64) for t in (Xd.min(dim=0).values, Xd.max(dim=0).values))
-        else:
-            if len(bounds) != 2:
-                raise ValueError("maximise: bounds = (lo [d], hi [d]) expected")
-            lo, hi = (np.asarray(b, np.float64) for b in bounds)
-            if lo.shape != (d,) or hi.shape != (d,) or not np.all(lo <= hi):
-                raise ValueError("maximise: bounds = (lo [%d], hi [%d]) with lo <= hi expected" % (d, d))
-        # the box as the session's dtype can hold it: the rounded iterates stay inside [lo, hi]
-        lo_r, hi_r = lo.astype(dt), hi.astype(dt)
-        lo_r = np.where(lo_r < lo, np.nextafter(lo_r, dt(np.inf)), lo_r)
-        hi_r = np.where(hi_r > hi, np.nextafter(hi_r, dt(-np.inf)), hi_r)
+        box = _host.ascent_box("maximise", Xd, bounds, d, dt)
         ell = np.broadcast_to(np.asarray(self._ell.cpu().numpy(), np.float64), (d,))
-        sign = 1.0 if largest else -1.0
         idx, f0 = self.argmax(Xd, largest=largest)
         if np.any(idx < 0):
             raise ValueError("maximise: draw %d has no comparable value among the candidates" % int(np.argmax(idx < 0)))
         x = Xd[sess.torch.as_tensor(idx, device=Xd.device)].cpu().numpy()       # [S, d], the session's dtype
-        x_best, f_best = x.copy(), f0.copy()
         info = dict(start_idx=idx, start_value=f0.copy(), steps=steps)
-        u = x.astype(np.float64) / ell
-        m1, m2 = np.zeros_like(u), np.zeros_like(u)
-        b1, b2, eps = 0.9, 0.999, 1e-8
         ar = np.arange(S)
-        if steps:   # steps + 1 evaluations: t = 0 is the start (its value is known, its gradient is not)
-            for t in range(steps + 1):
-                f, g = self.evaluate_grad(x)
-                f, g = f.cpu().numpy()[ar, ar], g.cpu().numpy()[ar, ar].astype(np.float64)
-                better = sign * f.astype(np.float64) > sign * f_best.astype(np.float64)
-                x_best[better], f_best[better] = x[better], f[better]
-                if t == steps:
-                    break
-                gu = sign * ell * g
-                m1 = b1 * m1 + (1.0 - b1) * gu
-                m2 = b2 * m2 + (1.0 - b2) * gu ** 2
-                u = u + float(lr) * (m1 / (1.0 - b1 ** (t + 1))) / (np.sqrt(m2 / (1.0 - b2 ** (t + 1))) + eps)
-                u = np.clip(u, lo / ell, hi / ell)
-                x = np.clip((u * ell).astype(dt), lo_r, hi_r)
-                x = np.where(u >= hi / ell, hi_r, np.where(u <= lo / ell, lo_r, x))   # on a face: the face itself, exactly
+
+        def evaluate(xc):   # ONE launch at the S current points; the diagonal of its [S, S] result
+            f, g = self.evaluate_grad(xc)
+            return f.cpu().numpy()[ar, ar], g.cpu().numpy()[ar, ar].astype(np.float64)
+
+        x_best, f_best = _host.adam_ascent(evaluate, x, f0, ell, box, 1.0 if largest else -1.0, steps, float(lr), dt)
         return x_best, f_best, info
 
     def _view(self, t):
@@ -617,6 +613,143 @@ class PathwiseDraws:
     coef = property(lambda self: self._view(self._coef), doc="coefficient rows [S, 2L + M] = [w / sqrt(L) | v]")
     z = property(lambda self: self._view(self._z), doc="inducing points [M, d]")
     lengthscales = property(lambda self: self._view(self._ell), doc="lengthscales [1] or [d]")
+
+
+class SparsePosterior:
+    """The closed-form posterior of a SparseGP at one q(u) (SparseGP.posterior): a snapshot of z [M, d], the lengthscales,
+    W = chol(K(z, z) + jitter I)^-1 with its fragment-major images, m [M] and S ([M, M] lower, or s [M]) of q(u), the
+    residual mode, the jitter and k_var, on the device in the session's dtype.  Later changes to the model do not move it.
+    Inputs are a Data / MinibatchData of the model (read in full from its device buffer), a device tensor or an array
+    [n, d]; outputs are numpy.  Every result at a point is independent of the other points of the call."""
+
+    KINDS = ("ei", "pi", "ucb")
+
+    def __init__(self, sess, z, ell, W, frag, m, s, residual, jitter, k_var):
+        self._sess = sess
+        self._z, self._ell, self._W, self._frag, self._m, self._s = z, ell, W, frag, m, s
+        H = sess.H
+        self._s_kind = H.SGP_S_TRIL if s.dim() == 2 else H.SGP_S_DIAG
+        self._mode = H.SGP_DIAGONAL if residual == "diagonal" else H.SGP_NEGLECTED
+        self.residual, self.jitter, self.k_var = residual, float(jitter), float(k_var)
+
+    def _points(self, X, who="X"):
+        Xd = _host.device_data(self._sess, X, who)
+        if Xd.shape[1] != self._z.shape[1]:
+            raise ValueError("SparsePosterior: %s %s does not match z %s" % (who, tuple(Xd.shape), tuple(self._z.shape)))
+        return Xd
+
+    def _model(self):
+        return (self._z, self._ell, self._W, self._m, self._s)
+
+    def _kw(self):
+        return dict(s_kind=self._s_kind, mode=self._mode, jitter=self.jitter, wfrag=self._frag)
+
+    def predict(self, X):
+        """(mean [n], var [n]) of f at the rows of X: the numbers of SVGP.predict_f (hb_sgp_predict, scaled by
+        sqrt(k_var) / k_var)."""
+        H = self._sess.H
+        z, ell, W, m, s = self._model()
+        mean, var = H.sgp_predict(self._points(X), z, ell, W, m.reshape(1, -1), s, **self._kw())
+        return np.sqrt(self.k_var) * mean.cpu().numpy().reshape(-1), self.k_var * var.cpu().numpy().reshape(-1)
+
+    def predict_grad(self, X):
+        """(mean [n], var [n], dmean [n, d], dvar [n, d]): predict's moments and their exact input gradients
+        dmean[j, k] = d mean[j] / d x_jk from ONE pass (hb_sgp_predict_grad), scaled by sqrt(k_var) / k_var."""
+        out = self._sess.H.sgp_predict_grad(self._points(X), *self._model(), **self._kw())
+        mean, var, dmean, dvar = (t.cpu().numpy() for t in out)
+        sc = np.sqrt(self.k_var)
+        return sc * mean, self.k_var * var, sc * dmean, self.k_var * dvar
+
+    def _acq_args(self, who, kind, best, xi, beta, var_floor):
+        if kind not in self.KINDS:
+            raise ValueError("%s: kind must be one of %s, got %r" % (who, self.KINDS, kind))
+        if kind != "ucb" and best is None:
+            raise ValueError("%s: the acquisition %r needs `best`, the incumbent value" % (who, kind))
+        var_floor = self.k_var * self.jitter if var_floor is None else float(var_floor)
+        if not var_floor >= 0.0:
+            raise ValueError("%s: var_floor >= 0 expected (got %r)" % (who, var_floor))
+        return dict(best=0.0 if best is None else float(best), param=float(beta if kind == "ucb" else xi),
+                    scale=float(np.sqrt(self.k_var)), var_floor=var_floor)
+
+    def _acq(self, Xd, kind, largest, args, **what):
+        return self._sess.H.sgp_acq(Xd, *self._model(), kind, largest=bool(largest), **args, **self._kw(), **what)
+
+    def acquisition(self, X, kind, best=None, xi=0.0, beta=2.0, largest=True, grad=False, var_floor=None):
+        """The acquisition function `kind` at the rows of X, as numpy [n] -- with grad=True (values [n], gradient [n, d]):
+        'ei'  expected improvement       sigma (u Phi(u) + phi(u)),   u = (s mean - s best - xi) / sigma
+        'pi'  probability of improvement Phi(u)
+        'ucb' upper confidence bound     s mean + beta sigma
+        for maximising f (largest, s = +1) or minimising it (s = -1; every acquisition itself is to be MAXIMISED), with
+        mean and sigma^2 = max(var, var_floor) those of predict.  `best`, the incumbent value of f, is required for 'ei'
+        and 'pi' (ValueError without it).  var_floor=None: k_var * jitter_level; where the variance was clamped the
+        gradient does not pass through it.  The tail is evaluated per point in double whatever the session's dtype
+        (hb_sgp_acq)."""
+        args = self._acq_args("acquisition", kind, best, xi, beta, var_floor)
+        val, g, _, _ = self._acq(self._points(X), kind, largest, args, value=True, grad=bool(grad))
+        return (val.cpu().numpy(), g.cpu().numpy()) if grad else val.cpu().numpy()
+
+    def argmax(self, X, kind, best=None, xi=0.0, beta=2.0, largest=True, var_floor=None):
+        """(idx, value): the row of X at which the acquisition is largest (ties: the first row; a NaN is never chosen) and
+        its value there -- np.argmax(acquisition(X)) and the value it points at, bit for bit, without writing anything of
+        size n, so X can be millions of candidates.  No comparable value: (-1, -inf)."""
+        args = self._acq_args("argmax", kind, best, xi, beta, var_floor)
+        Xd = self._points(X)
+        if Xd.shape[0] < 1:
+            raise ValueError("argmax: at least one candidate expected")
+        _, _, bv, bi = self._acq(Xd, kind, largest, args, value=False, argmax=True)
+        return int(bi.cpu().numpy()[0]), bv.cpu().numpy()[0]
+
+    def maximise(self, X, kind, best=None, xi=0.0, beta=2.0, largest=True, var_floor=None, steps=50, lr=0.05, bounds=None,
+                 starts=None):
+        """(x_best [R, d], a_best [R], info): the acquisition maximised over the box `bounds` by `steps` steps of projected
+        Adam ascent on its exact input gradient, from its best candidate among the rows of X (R = 1), or from every row
+        of starts [R, d].  The optimiser is the one of PathwiseDraws.maximise: on the host in float64, in lengthscale
+        units so that lr is a fraction of a lengthscale, each evaluation ONE hb_sgp_acq launch at the R current points
+        rounded to the session's dtype; bounds = (lo [d], hi [d]), default the per-column minimum and maximum of X.  The
+        best (value, point) seen is kept, the start included: a_best is never below the start's value and is the bits
+        of acquisition(x_best).  info = dict(start_idx (None with starts), start_value [R], steps).  steps < 0, lr <= 0,
+        malformed bounds or starts and X of another width raise ValueError."""
+        sess = self._sess
+        args = self._acq_args("maximise", kind, best, xi, beta, var_floor)
+        Xd = self._points(X)
+        d, dt = int(Xd.shape[1]), np.dtype(sess.np_dtype).type
+        steps = int(steps)
+        if steps < 0 or not float(lr) > 0.0:
+            raise ValueError("maximise: steps >= 0 and lr > 0 expected (got %r, %r)" % (steps, lr))
+        if Xd.shape[0] < 1:
+            raise ValueError("maximise: at least one candidate expected")
+        box = _host.ascent_box("maximise", Xd, bounds, d, dt)
+        ell = np.broadcast_to(np.asarray(self._ell.cpu().numpy(), np.float64), (d,))
+
+        def evaluate(xc):
+            val, g, _, _ = self._acq(_host.upload(sess, xc), kind, largest, args, value=True, grad=True)
+            return val.cpu().numpy(), g.cpu().numpy().astype(np.float64)
+
+        if starts is None:
+            _, _, bv, bi = self._acq(Xd, kind, largest, args, value=False, argmax=True)
+            idx, f0 = bi.cpu().numpy(), bv.cpu().numpy()
+            if idx[0] < 0:
+                raise ValueError("maximise: the acquisition has no comparable value among the candidates")
+            x = Xd[bi].cpu().numpy()
+        else:
+            x = np.ascontiguousarray(np.asarray(starts, dtype=dt))
+            if x.ndim != 2 or x.shape[1] != d or x.shape[0] < 1:
+                raise ValueError("maximise: starts [R, %d] expected, got %s" % (d, x.shape))
+            idx, f0 = None, evaluate(x)[0]
+        info = dict(start_idx=idx, start_value=f0.copy(), steps=steps)
+        x_best, a_best = _host.adam_ascent(evaluate, x, f0, ell, box, 1.0, steps, float(lr), dt)
+        return x_best, a_best, info
+
+    def _view(self, t):
+        a = t.cpu().numpy()
+        a.flags.writeable = False
+        return a
+
+    z = property(lambda self: self._view(self._z), doc="inducing points [M, d] (read-only numpy)")
+    lengthscales = property(lambda self: self._view(self._ell), doc="lengthscales [1] or [d]")
+    W = property(lambda self: self._view(self._W), doc="W = chol(K(z, z) + jitter I)^-1 [M, M]")
+    m = property(lambda self: self._view(self._m), doc="mean of q(u) [M]")
+    S = property(lambda self: self._view(self._s), doc="factor of q(u): [M, M] lower, or the standard deviations [M]")
 
 
 def greedy_inducing(X, M, lengthscales=1.0, threshold=None, return_info=False, dtype=None):

@@ -39,6 +39,7 @@ MM_SYMLOW_OUT, MM_ACTGRAD = _hb("MM_SYMLOW_OUT", "MM_ACTGRAD")
 ACT = {k[len("HB_ACT_"):].lower(): v for k, v in _C.items() if k.startswith("HB_ACT_")}
 SGP_NEGLECTED, SGP_DIAGONAL, SGP_FULLRANK = _hb("SGP_NEGLECTED", "SGP_DIAGONAL", "SGP_FULLRANK")
 SGP_S_DIAG, SGP_S_TRIL = _hb("SGP_S_DIAG", "SGP_S_TRIL")
+ACQ = {k[len("HB_ACQ_"):].lower(): v for k, v in _C.items() if k.startswith("HB_ACQ_")}   # 'ei', 'pi', 'ucb'
 PREC_NATIVE, PREC_BF16X3 = _hb("PREC_NATIVE", "PREC_BF16X3")
 LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON = _hb("LIK_GAUSSIAN", "LIK_BERNOULLI", "LIK_POISSON")
 # hb_matutil's modes are plain integers in the header
@@ -1086,6 +1087,101 @@ def sgp_predict(x, z, ell, W, m, s, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, jitter
     _lib.lib().call("hb_sgp_predict" + _suf(x), KERN_RBF, _p(x), sx, _p(z), _p(ell), ell.numel() // E, _p(W), _p(wfrag), _p(m),
                     _p(s), int(s_kind), int(mode), float(jitter), _p(mean), _p(var), E, n, M, d, P, _p(ws), stream())
     return mean, var
+
+
+def _predict_grad_shapes(who, x, z, ell, W, m, s, s_kind, wfrag):
+    """(n, M, d) of the operands of sgp_predict_grad / sgp_acq, checked: on the device, contiguous, one expert and one
+    latent function, shapes that fit, one dtype."""
+    for t in (x, z, ell, W, m, s) + (() if wfrag is None else (wfrag,)):
+        _chk(t)
+    if x.dim() != 2 or z.dim() != 2 or z.shape[1] != x.shape[1] or tuple(W.shape) != (z.shape[0], z.shape[0]):
+        raise ValueError("%s: x [n, d], z [M, d], W [M, M] expected, got %s %s %s"
+                         % (who, tuple(x.shape), tuple(z.shape), tuple(W.shape)))
+    (n, d), M = x.shape, z.shape[0]
+    if m.numel() != M or ell.numel() not in (1, d):
+        raise ValueError("%s: m [M] and 1 or d lengthscales expected, got %s %s" % (who, tuple(m.shape), tuple(ell.shape)))
+    if s_kind not in (SGP_S_DIAG, SGP_S_TRIL) or s.numel() != (M if s_kind == SGP_S_DIAG else M * M):
+        raise ValueError("%s: s must be [M] (SGP_S_DIAG) or [M, M] (SGP_S_TRIL), got %s" % (who, tuple(s.shape)))
+    if any(t.dtype != x.dtype for t in (z, ell, W, m, s)) or (wfrag is not None and wfrag.dtype != x.dtype):
+        raise TypeError("%s: all operands must share one dtype" % who)
+    if wfrag is not None and wfrag.numel() < 2 * M * M:
+        raise ValueError("%s: wfrag must hold the two fragment-major images of W (2 M^2 elements)" % who)
+    return n, M, d
+
+
+def _predict_grad_ws(who, ws, x, need):
+    if ws is None:
+        return workspace(x.dtype, x.device, max(need, 1))
+    _chk(ws)
+    if ws.dtype != x.dtype or ws.numel() < need:
+        raise ValueError("%s: the workspace must hold %d elements of %s" % (who, need, x.dtype))
+    return ws
+
+
+def _predict_grad_out(who, t, shape, x, name):
+    if t is None:
+        return _empty(shape, dtype=x.dtype, device=x.device)
+    _chk(t)
+    if tuple(t.shape) != tuple(shape) or t.dtype != x.dtype:
+        raise ValueError("%s: %s must be %s of the operands' dtype" % (who, name, list(shape)))
+    return t
+
+
+def sgp_predict_grad_ws_elems(dtype, n, M, d, s_kind, has_wfrag):
+    """Scratch elements hb_sgp_predict_grad / hb_sgp_acq need (bounded by one column chunk, not by n)."""
+    return int(_lib.lib().raw("hb_sgp_predict_grad_ws_elems")(int(n), int(M), int(d), int(s_kind), int(bool(has_wfrag)),
+                                                              _elem_bytes(dtype)))
+
+
+def sgp_predict_grad(x, z, ell, W, m, s, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, jitter=0.0, out=None, wfrag=None, ws=None,
+                     values=True):
+    """sgp_predict's moments and their input gradients for one expert and one latent function (hb_sgp_predict_grad):
+    (mean [n], var [n], dmean [n, d], dvar [n, d]) with dmean[j, k] = d mean[j] / d x_jk.  x [n, d], z [M, d], ell [1] or
+    [d], W [M, M], m [M] (any shape of M elements), s [M] standard deviations (SGP_S_DIAG) or [M, M] lower (SGP_S_TRIL).
+    mean and var are the bits of sgp_predict; values=False: they are not stored, those of `out` (if given) are left
+    untouched and None is returned in their place.  `out`: (mean, var, dmean, dvar) written in place.  A column's results
+    do not depend on the other columns: two calls, or x in pieces, return the same bits."""
+    who = "sgp_predict_grad"
+    n, M, d = _predict_grad_shapes(who, x, z, ell, W, m, s, s_kind, wfrag)
+    o = (None,) * 4 if out is None else tuple(out)
+    mean = _predict_grad_out(who, o[0], (n,), x, "mean") if values else None
+    var = _predict_grad_out(who, o[1], (n,), x, "var") if values else None
+    dmean = _predict_grad_out(who, o[2], (n, d), x, "dmean")
+    dvar = _predict_grad_out(who, o[3], (n, d), x, "dvar")
+    ws = _predict_grad_ws(who, ws, x, sgp_predict_grad_ws_elems(x.dtype, n, M, d, s_kind, wfrag is not None))
+    _lib.lib().call("hb_sgp_predict_grad" + _suf(x), KERN_RBF, _p(x), _p(z), _p(ell), ell.numel(), _p(W), _p(wfrag), _p(m), _p(s),
+                    int(s_kind), int(mode), float(jitter), _p(mean), _p(var), _p(dmean), _p(dvar), n, M, d, _p(ws), stream())
+    return mean, var, dmean, dvar
+
+
+def sgp_acq(x, z, ell, W, m, s, acq, best=0.0, param=0.0, scale=1.0, largest=True, var_floor=0.0, s_kind=SGP_S_DIAG,
+            mode=SGP_DIAGONAL, jitter=0.0, wfrag=None, ws=None, value=True, grad=False, argmax=False):
+    """A closed-form acquisition function of the model f = scale * (sgp_predict's latent) at the rows of x (hb_sgp_acq):
+    acq 'ei' / 'pi' (param = xi, improvement over `best`) or 'ucb' (param = beta), for maximising (largest) or minimising
+    f; the tail is evaluated per point in double.  Returns (val [n], grad [n, d], best_val [1], best_idx int64 [1]) device
+    tensors, None for each output not asked for (value / grad / argmax); with argmax alone nothing of size n is written.
+    best_val = max_j val[j], those bits, best_idx its first row; a NaN is never chosen, no comparable value: -1 and -inf.
+    Model operands as for sgp_predict_grad."""
+    who = "sgp_acq"
+    n, M, d = _predict_grad_shapes(who, x, z, ell, W, m, s, s_kind, wfrag)
+    code = ACQ.get(acq, None) if isinstance(acq, str) else acq
+    if code not in ACQ.values():
+        raise ValueError("%s: acq must be one of %s, got %r" % (who, sorted(ACQ), acq))
+    if not (value or grad or argmax):
+        raise ValueError("%s: at least one of value, grad, argmax expected" % who)
+    if argmax and n < 1:
+        raise ValueError("%s: at least one candidate expected, got x %s" % (who, tuple(x.shape)))
+    val = _empty((n,), dtype=x.dtype, device=x.device) if value else None
+    g = _empty((n, d), dtype=x.dtype, device=x.device) if grad else None
+    bv = _empty((1,), dtype=x.dtype, device=x.device) if argmax else None
+    bi = _empty((1,), dtype=torch.int64, device=x.device) if argmax else None
+    need = int(_lib.lib().raw("hb_sgp_acq_ws_elems")(int(n), int(M), int(d), int(s_kind), int(wfrag is not None),
+                                                     _elem_bytes(x.dtype)))
+    ws = _predict_grad_ws(who, ws, x, need)
+    _lib.lib().call("hb_sgp_acq" + _suf(x), KERN_RBF, _p(x), _p(z), _p(ell), ell.numel(), _p(W), _p(wfrag), _p(m), _p(s),
+                    int(s_kind), int(mode), float(jitter), int(code), float(best), float(param), float(scale),
+                    1 if largest else 0, float(var_floor), _p(val), _p(g), _p(bv), _p(bi), n, M, d, _p(ws), stream())
+    return val, g, bv, bi
 
 
 def sgp_predict_cov_ws_elems(dtype, E, n, M, P, s_kind):

@@ -154,6 +154,25 @@ class SVGP(hb.model.Model):
         return _part(self, "gp").pathwise_draws(_part(self, "u"), num_samples, num_features=num_features,
                                                 k_var=_scalar(self, "k_var"), seed=seed, noise=noise)
 
+    def posterior(self):
+        """The closed-form posterior of the latent f at the model's q(u) as an hb.gp.SparsePosterior (SparseGP.posterior
+        with the model's k_var and residual): post.predict(X) are the numbers of predict_f, post.predict_grad(X) their
+        input gradients, post.acquisition / argmax / maximise the closed-form EI, PI and UCB over candidates."""
+        self.initialize()
+        return _part(self, "gp").posterior(_part(self, "u"), k_var=_scalar(self, "k_var"), residual=self.residual)
+
+    def suggest(self, Xcand, kind="ei", largest=True, steps=50, **kw):
+        """(x_next [d], value, info): the next point of a sequential design -- the acquisition `kind` ('ei', 'pi', 'ucb')
+        of posterior() maximised from its best candidate among the rows of Xcand [n, d] (SparsePosterior.maximise; **kw:
+        xi, beta, var_floor, lr, bounds).  The incumbent `best` is the largest (smallest with largest=False) posterior
+        mean over the model's training inputs, from one predict pass; info also holds it."""
+        post = self.posterior()
+        mean, _ = post.predict(_part(self, "X"))
+        best = float(mean.max() if largest else mean.min())
+        x, a, info = post.maximise(Xcand, kind, best=best, largest=largest, steps=steps, **kw)
+        info["best"] = best
+        return x[0], a[0], info
+
     def _closed_form_inputs(self):
         """(X, Y, noise variance, k_var) of the whole data set at the current hyper-parameters."""
         self.initialize()
@@ -238,6 +257,7 @@ class SVGPLik(hb.model.Model):
     predict_f_samples = SVGP.predict_f_samples
     sample_functions = SVGP.sample_functions
     select_inducing = SVGP.select_inducing
+    posterior = SVGP.posterior
 
     def predict_y(self, Xnew):
         """Mean and variance [1, n] of a new observation y at Xnew [n, 1]: the likelihood's predictive under the

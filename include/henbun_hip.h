@@ -56,7 +56,9 @@ extern "C" {
  * hb_gram_bilinear_grad_f32 / _f64 and hb_pcg_*_coef (the exact GP's log marginal likelihood and its gradient);
  * hb_sgp_bwd_phi_f32 and hb_sgp_bwd_phi_supported (the sparse-GP backward that writes the Cholesky VJP's operand
  * Phisym(-Abar A^T) where hb_sgp_bwd_f32 writes Lbar); hb_sgp_pathwise_grad_f32 / _f64, hb_sgp_pathwise_argmax_f32 / _f64
- * and hb_sgp_pathwise_argmax_ws_elems (input gradients and the per-draw extremum of pathwise function draws). */
+ * and hb_sgp_pathwise_argmax_ws_elems (input gradients and the per-draw extremum of pathwise function draws);
+ * hb_sgp_predict_grad_f32 / _f64, hb_sgp_predict_grad_ws_elems, hb_sgp_acq_f32 / _f64, hb_sgp_acq_ws_elems and the enum
+ * values HB_ACQ_* (input gradients of the closed-form predictive and closed-form acquisition functions). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -725,6 +727,56 @@ int hb_sgp_pathwise_argmax_f32(int kind, const float* x, const float* omega, con
 int hb_sgp_pathwise_argmax_f64(int kind, const double* x, const double* omega, const double* z, const double* ell, long dl,
                                const double* coef, double scale, int largest, double* best, long* idx, long n, long L, long M,
                                long d, long S, double* ws, void* stream);
+/* Input gradients of hb_sgp_predict's moments and closed-form acquisition functions (csrc/sgp_predict_grad.hip; not in
+ * the reference).  One expert, one latent function (E = P = 1 of hb_sgp_predict_*), kind must be HB_KERN_RBF; x [n, d],
+ * z [M, d], ell [dl], W, Wfrag, m [M], s ([M] standard deviations or [M, M] lower), s_kind, mode, jitter as there.  With
+ * K_kj = k(z_k, x_j), t_kjd = (z_kd - x_jd) / ell_d^2, A = W K, C = S^T A:
+ *   dmean[j, d] = sum_k alpha_k K_kj t_kjd,     alpha = W^T m^T
+ *   dvar [j, d] = 2 sum_k G_kj K_kj t_kjd,      G = W^T (S C - A diag rho),
+ *   rho_j = sign(1 - sum_m A_mj^2) (HB_SGP_DIAGONAL), 0 (HB_SGP_NEGLECTED), 1 (HB_SGP_FULLRANK)
+ * -- formed from A itself, like the variance, never as a quadratic form in Kmm^-1.
+ *
+ * hb_sgp_predict_grad: mean [n], var [n] (each nullable: then not stored), dmean [n, d], dvar [n, d] row-major, non-NULL.
+ * mean and var are bit-identical to hb_sgp_predict's (the same code).  n = 0 returns without a launch.
+ *
+ * hb_sgp_acq: the acquisition `acq` of the scaled model f = scale * (..) at every row of x, its tail evaluated per point in
+ * double whatever the storage type.  With k_var = scale^2, s = +1 (largest != 0) or -1, mu' = s scale mean,
+ * v = max(k_var var, var_floor), sigma = sqrt(v), u = (mu' - s best - param) / sigma, Phi(u) = erfc(-u / sqrt 2) / 2:
+ *   HB_ACQ_EI   sigma (u Phi + phi)    (param = xi)
+ *   HB_ACQ_PI   Phi                    (param = xi)
+ *   HB_ACQ_UCB  mu' + param sigma      (param = beta; best unused)
+ * val [n], grad [n, d] = d val / d x (zero through v where it was clamped), best_val [1] = max_j val[j] -- those bits --
+ * and best_idx [1] (long) its first row: every output is nullable, at least one must be given; when only best_val /
+ * best_idx are asked for nothing of size n is written.  The arg-max follows hb_sgp_pathwise_argmax: workgroup partials
+ * in ws, a second launch folds them, comparisons strict, ties to the lowest row, a NaN never chosen, no comparable value:
+ * idx = -1 and best_val = -inf; n = 0 is rejected for an arg-max and returns without a launch otherwise.
+ *
+ * Fused form under the conditions of hb_sgp_predict's fused form: fp32, Wfrag, M % 32 == 0, 32 <= M <= 512, d <= 4.  One
+ * workgroup per 32-column strip, A, C, V = S C - A diag rho and G on MFMA in LDS, no [M, n] intermediate in memory.
+ * V, G and the fold are formed only when a gradient output (dmean / dvar, grad) is given: values or the arg-max alone cost
+ * what hb_sgp_predict costs and carry the same bits.  Everything else runs in column chunks over hb_sgp_A_* and hb_matmul_*.  No atomics: two calls return the same bits, and
+ * a column's results do not depend on the other columns of the call.  ws >= hb_sgp_predict_grad_ws_elems /
+ * hb_sgp_acq_ws_elems(n, M, d, s_kind, Wfrag != NULL, sizeof(T)) elements (16-byte aligned, bounded by one chunk of
+ * columns, not by n).  Validated before any launch. */
+enum { HB_ACQ_EI = 0, HB_ACQ_PI = 1, HB_ACQ_UCB = 2 };
+long hb_sgp_predict_grad_ws_elems(long n, long M, long d, int s_kind, int has_wfrag, int dtype_bytes);
+int hb_sgp_predict_grad_f32(int kind, const float* x, const float* z, const float* ell, long dl, const float* W,
+                            const float* Wfrag, const float* m, const float* s, int s_kind, int mode, double jitter,
+                            float* mean, float* var, float* dmean, float* dvar, long n, long M, long d, float* ws,
+                            void* stream);
+int hb_sgp_predict_grad_f64(int kind, const double* x, const double* z, const double* ell, long dl, const double* W,
+                            const double* Wfrag, const double* m, const double* s, int s_kind, int mode, double jitter,
+                            double* mean, double* var, double* dmean, double* dvar, long n, long M, long d, double* ws,
+                            void* stream);
+long hb_sgp_acq_ws_elems(long n, long M, long d, int s_kind, int has_wfrag, int dtype_bytes);
+int hb_sgp_acq_f32(int kind, const float* x, const float* z, const float* ell, long dl, const float* W, const float* Wfrag,
+                   const float* m, const float* s, int s_kind, int mode, double jitter, int acq, double best, double param,
+                   double scale, int largest, double var_floor, float* val, float* grad, float* best_val, long* best_idx,
+                   long n, long M, long d, float* ws, void* stream);
+int hb_sgp_acq_f64(int kind, const double* x, const double* z, const double* ell, long dl, const double* W,
+                   const double* Wfrag, const double* m, const double* s, int s_kind, int mode, double jitter, int acq,
+                   double best, double param, double scale, int largest, double var_floor, double* val, double* grad,
+                   double* best_val, long* best_idx, long n, long M, long d, double* ws, void* stream);
 /* Matrix-free kernel product (csrc/gram_matvec.hip; not in the reference; Gardner et al. 2018, Wang et al. 2019):
  *   out[s, j] = scale * sum_{i<N} V[s, i] k(x2_i, x_j) + shift * V[s, j],     s < S, j < n,
  * the product a conjugate-gradient solve with K(X, X) + sigma^2 I asks for, and the exact posterior mean at new points.
