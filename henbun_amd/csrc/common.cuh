@@ -55,6 +55,25 @@ static inline int hb_stream_grid(long n, int block) {
   return (int)g;
 }
 
+// Layout of Wfrag, the fragment-major images hb_cholesky_inverse leaves of W = L^-1 (include/henbun_hip.h), in elements
+// of the arithmetic type from the start of the buffer.  The ONE statement of it for host code: the writers (tril_inplace_kernel,
+// chol_persist_body) and the device-side readers index the same planes from the base pointer they are handed.
+struct HbWfragLayout {
+  long plane;  // B*M*M: the elements of one image, and the bf16 entries of one bf16 plane
+  long wt;     // the image of W^T (the image of W is at 0)
+  long bf16;   // bf16x3 only: three bf16 planes of W (hi, mid, lo), then three of W^T -- 3 * plane elements of fp32 storage
+  long total;  // hb_cholesky_frag_elems
+  template <typename T>
+  const void* w3(const T* frag) const { return frag + bf16; }
+  template <typename T>
+  const void* wt3(const T* frag) const { return reinterpret_cast<const unsigned short*>(frag + bf16) + 3 * plane; }
+};
+static inline HbWfragLayout hb_wfrag_layout(long B, long M, bool bf16x3) {
+  HbWfragLayout l;
+  l.plane = B * M * M, l.wt = l.plane, l.bf16 = 2 * l.plane, l.total = (bf16x3 ? 5 : 2) * l.plane;
+  return l;
+}
+
 // ---------------------------------------------------------------------------
 // Device-side zero fill / copy.  hipMemsetAsync / hipMemcpyAsync are NOT used on
 // any path that may run inside a hipGraph capture: measured on ROCm 7.2 / gfx950,

@@ -986,16 +986,16 @@ __global__ void __launch_bounds__(256) matutil_kernel(const T* __restrict__ in, 
     const long rem = t - b * R * C;
     const long i = rem / C, j = rem - i * C;
     T v = in[t];
-    if (mode == 0) {
+    if (mode == HB_MATUTIL_BAND) {
       const bool keep = (lower < 0 || i - j <= lower) && (upper < 0 || j - i <= upper);
       v = keep ? v : T(0);
-    } else if (mode == 1) {
+    } else if (mode == HB_MATUTIL_ADD_EYE) {
       if (i == j) v += alpha;
-    } else if (mode == 2) {
+    } else if (mode == HB_MATUTIL_PHI) {
       v = (i > j) ? v : (i == j ? T(0.5) * v : T(0));
-    } else if (mode == 3) {
+    } else if (mode == HB_MATUTIL_SYM) {
       v = T(0.5) * (v + in[b * R * C + j * C + i]);
-    } else if (mode == 4) {
+    } else if (mode == HB_MATUTIL_SYMLOW) {
       v = T(0.5) * (i >= j ? v : in[b * R * C + j * C + i]);
     }
     out[t] = v;
@@ -1005,8 +1005,8 @@ template <typename T>
 static int matutil_launch(const T* in, T* out, long B, long R, long C, int mode, long lower, long upper, double alpha,
                           hipStream_t stream) {
   HB_REQUIRE(B >= 0 && R >= 0 && C >= 0, "hb_matutil: negative extent");
-  HB_REQUIRE(mode >= 0 && mode <= 4, "hb_matutil: bad mode %d", mode);
-  HB_REQUIRE((mode != 3 && mode != 4) || (R == C && in != out), "hb_matutil: symmetrise needs square, out-of-place");
+  HB_REQUIRE(mode >= HB_MATUTIL_BAND && mode <= HB_MATUTIL_SYMLOW, "hb_matutil: bad mode %d", mode);
+  HB_REQUIRE((mode != HB_MATUTIL_SYM && mode != HB_MATUTIL_SYMLOW) || (R == C && in != out), "hb_matutil: symmetrise needs square, out-of-place");
   const long n = B * R * C;
   if (n == 0) return 0;
   hipLaunchKernelGGL(matutil_kernel<T>, dim3(hb_stream_grid(n, 256)), dim3(256), 0, stream, in, out, B, R, C, mode,

@@ -562,18 +562,20 @@ __global__ void __launch_bounds__(256) matmul_wgk_kernel(MmArgs<float> a, int no
   }
 }
 
-// eligibility of the in-workgroup split-K kernel (fp32 only)
+// eligibility of the in-workgroup split-K kernel (fp32 only).  hb_matmul_wgk_shape: its shape part alone, what a planner
+// may ask before it knows the operands (the mm_no_wgk switch, alignment and flags are left to matmul_wgk_ok)
+extern "C" int hb_matmul_wgk_shape(long M, long N, long K, long batch) {
+  if (M % 32 || N % 32 || K % 128 || K < 128 || K > 4096) return 0;
+  return (M / 32) * (N / 32) * batch <= 1024 && batch <= 65535 ? 1 : 0;
+}
 template <typename T>
 static bool matmul_wgk_ok(const MmArgs<T>&, long, long, long, long, int, bool) { return false; }
 template <>
 bool matmul_wgk_ok<float>(const MmArgs<float>& a, long M, long N, long K, long batch, int flags, bool aligned) {
   const bool off = hb_debug_get("mm_no_wgk", 0) != 0;  // diagnostic A/B switch (hb_debug_set)
-  if (off || !aligned) return false;
-  if (M % 32 || N % 32 || K % 128 || K < 128 || K > 4096) return false;
+  if (off || !aligned || !hb_matmul_wgk_shape(M, N, K, batch)) return false;
   if (flags & HB_MM_ACTGRAD) return false;
-  if ((flags & HB_MM_SYM_OUT) && M != N) return false;
-  const long tiles = (M / 32) * (N / 32) * batch;
-  return tiles <= 1024 && batch <= 65535;
+  return !((flags & HB_MM_SYM_OUT) && M != N);
 }
 template <typename T>
 static int matmul_wgk_launch(const MmArgs<T>&, int, int, hipStream_t) { return -1; }
@@ -2354,6 +2356,7 @@ static int chol_persist_launch(const float* A, const CpGram& g, float* L, float*
 static inline bool chol_persist_shape(long B, long M, size_t elem) {
   return elem == 4 && M >= CP_NB && M % CP_NB == 0 && M <= 8192 && B >= 1 && B * (M / CP_NB) * (M / CP_NB) <= 65536;
 }
+extern "C" long hb_cholesky_frag_elems(long B, long M, int bf16x3) { return hb_wfrag_layout(B, M, bf16x3 != 0).total; }
 extern "C" int hb_cholesky_persistent_shape(long B, long M, int elem_bytes) {
   return chol_persist_shape(B, M, (size_t)elem_bytes) && hb_debug_get("chol_persist", 1) != 0 ? 1 : 0;
 }

@@ -1392,22 +1392,123 @@ __global__ void __launch_bounds__(512, 4) chol_sgp_fwd_kernel(CpArgs ca, HbSideJ
   sgp_early_body<D>(a, ca, lds, (int)t - ca.total - ca.nside);
 }
 
+// ---- Where a form is decided.  sgp_ws() is the one description of the workspace, sgp_form() the one place that says which
+// kernel a call runs and which fusions it may carry: the exported queries (hb_sgp_strip_path, hb_sgp_head_units,
+// hb_sgp_rider_supported, hb_sgp_bwd_phi_supported, hb_sgp_ws_elems) and the launchers read the two structs, nothing else.
+
+// paired grid when it already gives the chip ~1.5 workgroups per CU, else one row block per workgroup
+static inline int sgp_grid_y(long E, long n, int nRB) {
+  const long paired = (long)hb_cdiv(n, SGP_BN) * ((nRB + 1) / 2) * E;
+  return (paired < 384 && nRB > 1) ? nRB : (nRB + 1) / 2;
+}
+
+// The workspace of hb_sgp_fwd / hb_sgp_bwd, in elements from its start: E*n reserved ones (unused since the residual
+// coefficient is computed in-kernel), then
+struct SgpWs {
+  long ellpart;      // lengthscale partials [E, M, d]
+  long shared;       // forward: column partials [E, row blocks, 5, n];  backward: split-K scratch, or strip partials + Lbar slabs
+  long mm_elems;     // 32 E M^2: the extent of the shared region the backward works in
+  long strip_elems;  // backward strip partials [E][nS][2d + P][M] at `shared` (consumed by the finish kernel) ...
+  long slabs;        // ... and, behind them rounded up to 64 elements, the Lbar slabs of E*M*M elements each
+  long slab_cap;     // how many slabs fit
+  long total;        // hb_sgp_ws_elems
+};
+static inline SgpWs sgp_ws(long E, long n, long M, long d, long P) {
+  SgpWs w;
+  const long gy = (M + SGP_BM - 1) / SGP_BM;  // most row blocks a column's statistics can be split over
+  const long fwd_part = 5 * E * gy * n, nS = hb_cdiv(n, SGP_SN);
+  w.ellpart = E * n, w.shared = w.ellpart + E * M * d;
+  w.mm_elems = 32 * E * M * M, w.strip_elems = nS * (2 * d + P) * M * E;
+  const long padded = ((w.strip_elems + 63) / 64) * 64;
+  w.slabs = w.shared + padded;
+  w.slab_cap = E * M > 0 ? (w.mm_elems - padded) / (E * M * M) : 0;
+  w.total = w.shared + (w.mm_elems > fwd_part ? w.mm_elems : fwd_part);
+  return w;
+}
+extern "C" long hb_sgp_ws_elems(long E, long n, long M, long d, long P) { return sgp_ws(E, n, M, d, P).total; }
+
+enum { SGP_CALL_FWD, SGP_CALL_A, SGP_CALL_BWD };
+enum { SGP_K_TILED, SGP_K_STRIP, SGP_K_STRIP2, SGP_K_STRIP2T, SGP_K_STRIP16, SGP_K_STRIP3 };
+struct SgpForm {
+  bool path;        // hb_sgp_strip_path: with Wfrag the call runs as column strips and may exchange A / Kbar fragment-major
+  int kernel;       // SGP_K_* of the forward contraction (SGP_K_STRIP16 stands until the launcher has seen the CU count)
+  bool partials;    // the forward leaves column partials in the workspace (else: the plain finishing kernel reads A)
+  int part_rows;    // partial rows of the column statistics
+  bool fin;         // the finishing pass runs inside the contraction kernel
+  long head_units;  // > 0: a likelihood head may ride (hb_sgp_head_units)
+  bool record;      // the call may be recorded after hb_sgp_rider_begin ...
+  bool rider;       // ... and a persistent factorisation of this shape takes it into its launch (hb_sgp_rider_supported)
+  bool bwd_strip;   // the backward runs in column-strip form
+  bool bwd_phi;     // hb_sgp_bwd_phi is served (hb_sgp_bwd_phi_supported)
+  SgpWs ws;
+};
+static SgpForm sgp_form(int call, int elem_bytes, long E, long n, long M, long d, long P, int prec, bool has_wfrag, bool w_aligned,
+                        bool has_ws, bool draw, long rng_lanes, bool want_xbar) {
+  // the diagnostic switches (hb_debug_set), each read here and nowhere else
+  const bool no_strip = hb_debug_get("sgp_no_strip", 0) != 0;                // the tiled kernels (A/B timing)
+  const bool force_strip = hb_debug_get("sgp_force_strip", 0) != 0;          // without Wfrag: strip form whenever it is applicable
+  const bool old_crossover = hb_debug_get("sgp_tiled_crossover", 0) != 0;    // round 1's crossover between tiled and strip
+  const bool form2 = hb_debug_get("sgp_strip_form2", 0) != 0;                // keeps the second form (it agrees bit for bit in A with the third)
+  const bool no_fused_finish = hb_debug_get("sgp_no_fused_finish", 0) != 0;  // the finishing pass as a launch of its own
+  // (stand-alone 5-7 % faster than the third form at cfg 2, 26.2 / 25.4 against 28.2 / 26.7 us; inside the step 1.2 us SLOWER)
+  const bool form16 = hb_debug_get("sgp_form16", 0) != 0;
+  const bool early = hb_debug_get("sgp_early", 1) != 0;                      // 0: no forward rides in the factorisation's launch
+  const bool phi_direct = hb_debug_get("sgp_phi_direct", 1) != 0;            // 0: plans keep hb_sgp_bwd and the Cholesky VJP's first product
+  SgpForm f;
+  f.ws = sgp_ws(E, n, M, d, P);
+  const bool fp32 = elem_bytes == 4, bf16x3 = prec == HB_PREC_BF16X3;
+  const long nS = hb_cdiv(n, SGP_SN);
+  const long tiled_wgs = E * hb_cdiv(n, SGP_BN) * ((hb_cdiv(M, SGP_BM) + 1) / 2);
+  const bool strip_M = M >= 32 && M <= SGP_SM_MAX && M % 32 == 0;
+  // With Wfrag.  Round 1's crossover (tiled kernels for many experts / long minibatches: 1.68 vs 1.76 ms at cfg 5 with the
+  // first strip kernel) no longer holds with the fragment-major W / A / Kbar exchange: cfg 5 (E = 8, n = 65536) runs
+  // 6.03 ms per step tiled against 5.33 ms in strip form (sgp_grad 3742 -> 3371 us, sgp 1554 -> 1479 us).
+  // (the backward's strip partials [nS][2d + P][M] and at least one Lbar slab must fit the 32 M^2 workspace per expert)
+  f.path = !no_strip && strip_M && d >= 1 && d <= SGP_DREG && P <= 4 && n > 0 && E >= 1 &&
+           (bf16x3 || (old_crossover ? tiled_wgs < 1024 && E * nS <= 4096 : E * nS <= (1L << 22) && nS * (2 * d + P) <= 31 * M));
+  // Without Wfrag: the first strip form wins when the tiled kernel would leave ~one workgroup per CU (cfg 2: 33.5 -> 28.8 us);
+  // with many experts / a long minibatch the tiled kernel runs several workgroups per CU and stays the faster one
+  // (cfg 5, E = 8, n = 65536: 1.68 ms tiled vs 1.76 ms strip under sgp_force_strip).
+  const bool plain_strip = !no_strip && strip_M && d <= SGP_DREG && w_aligned && (tiled_wgs < 1024 || force_strip);
+  f.partials = call != SGP_CALL_A && M > 0 && P <= 4 && has_ws;
+  // hb_sgp_A alone: it has never consulted f.path, so a Wfrag does not widen its rule beyond plain_strip (hb_sgp_A and
+  // hb_sgp_fwd can pick different kernels for the same operands), and bf16x3 operands always run strip3, sgp_no_strip or not.
+  const bool strip = fp32 && (call == SGP_CALL_A ? plain_strip || bf16x3 : f.partials && ((has_wfrag && f.path) || plain_strip));
+  // third form (transposed accumulators, two workgroups per CU) whenever its one column mean suffices; sixteen-wave form:
+  // where every CU gets at most ONE strip (the launcher's part of the rule), so that the third form could not put two
+  // workgroups on it (M >= 384: at least 12 of the 16 waves own a pair of sub-tiles)
+  const bool form3 = (!f.partials || P <= 1) && !form2;
+  f.kernel = !strip ? SGP_K_TILED : bf16x3 ? SGP_K_STRIP3 : !has_wfrag ? SGP_K_STRIP : !form3 ? SGP_K_STRIP2
+             : (form16 && M >= 384) ? SGP_K_STRIP16 : SGP_K_STRIP2T;
+  f.part_rows = strip ? 1 : sgp_grid_y(E, n, hb_cdiv(M, SGP_BM));
+  // third strip form with one column mean: the finishing pass (and a likelihood head) runs inside the contraction kernel
+  f.fin = call == SGP_CALL_FWD && strip && has_wfrag && !bf16x3 && f.path && !no_fused_finish && !form2 && P <= 1 && n % 2 == 0 &&
+          (!draw || rng_lanes >= (E * n + 1) / 2);
+  f.head_units = f.fin && P == 1 ? E * nS : 0;
+  f.record = f.fin && d <= SGP_E_DMAX;
+  f.rider = f.record && early && M % CP_NB == 0 && hb_cholesky_persistent_shape(E, M, 4);
+  // column-strip backward: fp32, fragment-major W^T available, small d and P, no xbar, the strip partials fit
+  f.bwd_strip = fp32 && has_wfrag && !want_xbar && f.path && f.ws.strip_elems <= f.ws.mm_elems;
+  f.bwd_phi = !bf16x3 && f.path && phi_direct;
+  return f;
+}
+// the exported queries speak of an fp32 call with a 16-byte aligned W and a workspace
+static inline SgpForm sgp_form_query(long E, long n, long M, long d, long P, int prec, bool has_wfrag, bool draw, long rng_lanes) {
+  return sgp_form(SGP_CALL_FWD, 4, E, n, M, d, P, prec, has_wfrag, true, true, draw, rng_lanes, false);
+}
+
 // ---- the recorded forward ("rider"): hb_sgp_rider_begin() ... hb_sgp_fwd_* ... hb_cholesky_inverse_f32 / hb_gram_cholesky_inverse_f32
 struct SgpRider {
   bool armed = false, valid = false;
   SgpArgs<float> a;
+  SgpForm form;
   long E = 0;
 };
 static thread_local SgpRider g_rider;
-static int sgp_A_strip_launch(SgpArgs<float> a, long E, hipStream_t stream);
-static inline bool sgp_fused_finish_ok(long E, long n, long M, long d, long P, int prec, bool has_wfrag, bool draw, long rng_lanes);
+static int sgp_A_strip_launch(SgpArgs<float> a, long E, int kernel, hipStream_t stream);
 
 extern "C" int hb_sgp_rider_supported(long E, long n, long M, long d, long P, int prec, int has_wfrag, int draw, long rng_lanes) {
-  if (hb_debug_get("sgp_early", 1) == 0) return 0;
-  return sgp_fused_finish_ok(E, n, M, d, P, prec, has_wfrag != 0, draw != 0, rng_lanes) && d <= SGP_E_DMAX && M % CP_NB == 0 &&
-                 hb_cholesky_persistent_shape(E, M, 4)
-             ? 1
-             : 0;
+  return sgp_form_query(E, n, M, d, P, prec, has_wfrag != 0, draw != 0, rng_lanes).rider ? 1 : 0;
 }
 extern "C" int hb_sgp_rider_begin(void) {
   HB_REQUIRE(!g_rider.valid, "hb_sgp_rider_begin: a recorded forward is still pending (hb_sgp_rider_flush)");
@@ -1419,7 +1520,7 @@ int hb_sgp_rider_launch_alone(hipStream_t stream) {
   g_rider.armed = false;
   if (!g_rider.valid) return 0;
   g_rider.valid = false;
-  return sgp_A_strip_launch(g_rider.a, g_rider.E, stream);
+  return sgp_A_strip_launch(g_rider.a, g_rider.E, g_rider.form.kernel, stream);
 }
 extern "C" int hb_sgp_rider_flush(void* stream) { return hb_sgp_rider_launch_alone((hipStream_t)stream); }
 
@@ -1429,8 +1530,9 @@ int hb_sgp_rider_launch_with(CpArgs& ca, const HbSideJobs& sj, hipStream_t strea
   const long E = g_rider.E, nS = hb_cdiv(a.n, SGP_SN);
   static int cus = 0;   // (one device per process)
   if (cus == 0 && (hb_device_info(nullptr, 0, &cus) || cus <= 0)) cus = 256;
-  const bool ok = a.Wf == ca.Wf && !ca.bf16x3 && E == ca.B && a.M == ca.M && a.M <= SGP_SM_MAX && a.d >= 1 && a.d <= SGP_E_DMAX &&
-                  a.fin && !a.W3 && (long)ca.total + sj.total + E * nS <= 2L * cus && hb_debug_get("sgp_early", 1) != 0;
+  // (the recorded call's own part of the rule is g_rider.form.rider; what is left is whether THIS factorisation writes its operands)
+  const bool ok = g_rider.form.rider && a.Wf == ca.Wf && !ca.bf16x3 && E == ca.B && a.M == ca.M &&
+                  (long)ca.total + sj.total + E * nS <= 2L * cus;
   if (!ok) return 0;   // (the caller launches the factorisation alone, then hb_sgp_rider_launch_alone)
   ca.early = 1 | ((int)(hb_debug_get("sgp_early_diag", 0) & 3) << 1), ca.nside = sj.total, ca.arrive = ca.total + (int)(E * nS);   // (diag: timing variants)
   g_rider.valid = false, g_rider.armed = false;
@@ -1612,57 +1714,34 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS) sgp_A_strip3_kernel(SgpArgs
   }
 }
 
-// diagnostic switch: HB_SGP_NO_STRIP=1 forces the tiled kernels (A/B timing)
-static inline bool hb_sgp_no_strip() {
-  return hb_debug_get("sgp_no_strip", 0) != 0;   // diagnostic (hb_debug_set)
-}
-// The strip form wins when the tiled kernel would leave ~one workgroup per CU (cfg 2: 33.5 -> 28.8 us); with
-// many experts / a long minibatch the tiled kernel runs several workgroups per CU and stays the faster one
-// (cfg 5, E = 8, n = 65536: 1.68 ms tiled vs 1.76 ms strip, HB_SGP_FORCE_STRIP=1).
-static inline bool sgp_strip_ok(long E, long n, long M, long d, const void* W) {
-  const long tiled_wgs = E * hb_cdiv(n, SGP_BN) * ((hb_cdiv(M, SGP_BM) + 1) / 2);
-  const bool force = hb_debug_get("sgp_force_strip", 0) != 0;  // diagnostic: strip form whenever it is applicable
-  return M >= 32 && M <= SGP_SM_MAX && M % 32 == 0 && d <= SGP_DREG && ((uintptr_t)W % 16 == 0) && (tiled_wgs < 1024 || force);
-}
-
 // 1 when hb_sgp_fwd / hb_sgp_bwd, given the fragment-major images of W (Wfrag), run in column-strip form -- the form
 // that can also exchange A and Kbar in fragment-major layout (A_frag / Kbar_frag)
 extern "C" int hb_sgp_strip_path(long E, long n, long M, long d, long P, int prec) {
-  if (hb_sgp_no_strip()) return 0;
-  if (!(M >= 32 && M <= SGP_SM_MAX && M % 32 == 0 && d >= 1 && d <= SGP_DREG && P <= 4 && n > 0 && E >= 1)) return 0;
-  if (prec == HB_PREC_BF16X3) return 1;
-  // Round 1's crossover (tiled kernels for many experts / long minibatches: 1.68 vs 1.76 ms at cfg 5 with the first
-  // strip kernel) no longer holds with the fragment-major W / A / Kbar exchange: cfg 5 (E = 8, n = 65536) runs
-  // 6.03 ms per step tiled against 5.33 ms in strip form (sgp_grad 3742 -> 3371 us, sgp 1554 -> 1479 us).
-  // HB_SGP_TILED_CROSSOVER=1 restores the old rule (diagnostic).
-  const bool old_rule = hb_debug_get("sgp_tiled_crossover", 0) != 0;
-  // (the backward's strip partials [nS][2d + P][M] and at least one Lbar slab must fit the 32 M^2 workspace per expert)
-  if (!old_rule) return (E * hb_cdiv(n, SGP_SN) <= (1L << 22) && (long)hb_cdiv(n, SGP_SN) * (2 * d + P) <= 31 * M) ? 1 : 0;
-  const long tiled_wgs = E * hb_cdiv(n, SGP_BN) * ((hb_cdiv(M, SGP_BM) + 1) / 2);
-  return (tiled_wgs < 1024 && E * hb_cdiv(n, SGP_SN) <= 4096) ? 1 : 0;
+  return sgp_form_query(E, n, M, d, P, prec, true, false, 0).path ? 1 : 0;
 }
 
-static int sgp_A_strip_launch(SgpArgs<float> a, long E, hipStream_t stream) {
+// fp32 elements of a fragment-major [E, M, n] operand (A_frag / Kbar_frag / Abar_frag): columns padded to whole strips; the bf16x3
+// form holds three bf16 planes instead of one fp32 image
+extern "C" long hb_sgp_frag_elems(long E, long n, long M, int prec) {
+  const long base = E * M * SGP_SN * hb_cdiv(n, SGP_SN);
+  return prec == HB_PREC_BF16X3 ? base * 3 / 2 : base;
+}
+
+static int sgp_A_strip_launch(SgpArgs<float> a, long E, int kernel, hipStream_t stream) {
   dim3 grid = sgp_grid(hb_cdiv(a.n, SGP_SN), 1, E, a.efast);
-  // third form (transposed accumulators, two workgroups per CU) whenever its one column mean suffices;
-  // HB_SGP_STRIP_FORM2=1 keeps the second form (diagnostic: A/B timing, the two forms agree bit for bit in A)
-  const bool form3 = (!a.part || a.P <= 1) && hb_debug_get("sgp_strip_form2", 0) == 0;
-  // sixteen-wave form: where every CU gets at most ONE strip, so that the third form could not put two workgroups on it
-  // (M >= 384: at least 12 of the 16 waves own a pair of sub-tiles)
+  // the device's part of the sixteen-wave rule: every CU gets at most ONE strip
   static int cus = 0;
   if (cus == 0 && (hb_device_info(nullptr, 0, &cus) || cus <= 0)) cus = 256;
-  // OFF by default: stand-alone it is 5-7 % faster than the third form at cfg 2 (26.2 / 25.4 against 28.2 / 26.7 us), inside
-  // the step it is 1.2 us SLOWER (201.5 against 200.3 us per step, tools/ab_step.py) -- hb_debug_set("sgp_form16", 1) selects it
-  const bool form16 = a.M >= 384 && a.M % 32 == 0 && E * hb_cdiv(a.n, SGP_SN) <= cus + cus / 4 && hb_debug_get("sgp_form16", 0) != 0;
+  if (kernel == SGP_K_STRIP16 && E * hb_cdiv(a.n, SGP_SN) > cus + cus / 4) kernel = SGP_K_STRIP2T;
 #define HB_STRIP(D_)                                                                                          \
   do {                                                                                                        \
-    if (a.W3)                                                                                                 \
+    if (kernel == SGP_K_STRIP3)                                                                               \
       hipLaunchKernelGGL((sgp_A_strip3_kernel<D_>), grid, dim3(SGP_STRIP_THREADS), 0, stream, a);             \
-    else if (a.Wf && form3 && form16)                                                                         \
+    else if (kernel == SGP_K_STRIP16)                                                                         \
       hipLaunchKernelGGL((sgp_A_strip16_kernel<D_>), grid, dim3(SGP_S16_THREADS), 0, stream, a);              \
-    else if (a.Wf && form3)                                                                                   \
+    else if (kernel == SGP_K_STRIP2T)                                                                         \
       hipLaunchKernelGGL((sgp_A_strip2t_kernel<D_>), grid, dim3(SGP_STRIP_THREADS), 0, stream, a);            \
-    else if (a.Wf)                                                                                            \
+    else if (kernel == SGP_K_STRIP2)                                                                          \
       hipLaunchKernelGGL((sgp_A_strip2_kernel<D_>), grid, dim3(SGP_STRIP_THREADS), 0, stream, a);             \
     else                                                                                                      \
       hipLaunchKernelGGL((sgp_A_strip_kernel<D_, false>), grid, dim3(SGP_STRIP_THREADS), 0, stream, a);       \
@@ -1679,7 +1758,7 @@ static int sgp_A_strip_launch(SgpArgs<float> a, long E, hipStream_t stream) {
   HB_LAUNCH_CHECK();
   return 0;
 }
-static int sgp_A_strip_launch(SgpArgs<double>, long, hipStream_t) { return -1; }  // fp32 only
+static int sgp_A_strip_launch(SgpArgs<double>, long, int, hipStream_t) { return -1; }  // fp32 only
 
 // D dispatch: z staged in LDS when d <= SGP_DREG; vector operand path when, in
 // addition, M is a multiple of 16 and W is 16-byte aligned.
@@ -1790,19 +1869,6 @@ __global__ void __launch_bounds__(256) sgp_rng_fill_kernel(uint64_t* state, long
   rng_store(state, nlanes, t, g);
 }
 
-extern "C" long hb_sgp_ws_elems(long E, long n, long M, long d, long P) {
-  (void)P;
-  const long gy = (M + SGP_BM - 1) / SGP_BM;  // most row blocks a column's statistics can be split over
-  const long mm = 32 * E * M * M, part = 5 * E * gy * n;  // backward split-K slabs / forward column partials
-  return E * n + E * M * d + (mm > part ? mm : part);
-}
-
-// paired grid when it already gives the chip ~1.5 workgroups per CU, else one row block per workgroup
-static inline int sgp_grid_y(long E, long n, int nRB) {
-  const long paired = (long)hb_cdiv(n, SGP_BN) * ((nRB + 1) / 2) * E;
-  return (paired < 384 && nRB > 1) ? nRB : (nRB + 1) / 2;
-}
-
 // the likelihood head that may ride in the forward strip kernel (hb_sgp_fwd_gauss)
 template <typename T>
 struct SgpHead {
@@ -1815,22 +1881,36 @@ struct SgpHead {
   T* part = nullptr;
   long units = 0;
 };
-// can hb_sgp_fwd run its finishing pass (and a likelihood head) inside the third strip form for this call?
-static inline bool sgp_fused_finish_ok(long E, long n, long M, long d, long P, int prec, bool has_wfrag, bool draw, long rng_lanes) {
-  const bool nofuse = hb_debug_get("sgp_no_fused_finish", 0) != 0 || hb_debug_get("sgp_strip_form2", 0) != 0;   // (diagnostic)
-  return !nofuse && has_wfrag && prec == HB_PREC_NATIVE && hb_sgp_strip_path(E, n, M, d, P, prec) && P <= 1 && n % 2 == 0 &&
-         (!draw || rng_lanes >= (E * n + 1) / 2);
-}
 extern "C" long hb_sgp_head_units(long E, long n, long M, long d, long P, int prec, int has_wfrag, int draw, long rng_lanes) {
-  if (P != 1 || !sgp_fused_finish_ok(E, n, M, d, P, prec, has_wfrag != 0, draw != 0, rng_lanes)) return 0;
-  return E * hb_cdiv(n, SGP_SN);
+  return sgp_form_query(E, n, M, d, P, prec, has_wfrag != 0, draw != 0, rng_lanes).head_units;
+}
+
+// the operands of a forward contraction (Wf == nullptr: no fragment-major images; `part`: the column partials, or nullptr)
+template <typename T>
+static SgpArgs<T> sgp_args(const T* x, long sx, const T* z, const T* ell, long dl, const T* W, const T* Wf, int prec, const T* u,
+                           T* A, T* A_frag, T* part, long E, long n, long M, long d, long P) {
+  const HbWfragLayout lay = hb_wfrag_layout(E, M, prec == HB_PREC_BF16X3);
+  SgpArgs<T> a;
+  a.x = x; a.sx = sx; a.z = z; a.ell = ell; a.dl = dl; a.W = W; a.Wf = Wf; a.u = u; a.A = A;
+  a.n = n; a.M = M; a.d = d; a.P = P;
+  a.W3 = Wf && prec == HB_PREC_BF16X3 ? lay.w3(Wf) : nullptr;
+  a.plane3 = Wf ? lay.plane : 0;
+  a.Af = A_frag;
+  a.part = part;
+  return a;
 }
 
 template <typename T>
 static int sgp_fwd(int kind, int mode, const T* x, long sx, const T* z, const T* ell, long dl, const T* W, const T* Wf,
                    int prec, const T* u, const T* eps_in, uint64_t* rng, long rng_lanes, T* eps_out, T* A, T* A_frag, T* f,
                    T* v, long E, long n, long M, long d, long P, T* ws, hipStream_t stream, const SgpHead<T>* head = nullptr) {
-  HB_REQUIRE(!A_frag || (sizeof(T) == 4 && Wf && ws && hb_sgp_strip_path(E, n, M, d, P, prec)),
+  const bool diag = mode == HB_SGP_DIAGONAL, draw = diag && !eps_in;
+  const T* fin_eps_in = diag ? eps_in : nullptr;   // what the finishing pass, wherever it runs, reads and writes
+  uint64_t* fin_rng = draw ? rng : nullptr;
+  T* fin_eps_out = diag ? eps_out : nullptr;
+  const SgpForm form = sgp_form(SGP_CALL_FWD, (int)sizeof(T), E, n, M, d, P, prec, Wf != nullptr, (uintptr_t)W % 16 == 0, ws != nullptr,
+                                draw, rng_lanes, false);
+  HB_REQUIRE(!A_frag || (sizeof(T) == 4 && Wf && ws && form.path),
              "hb_sgp_fwd: a fragment-major A needs the column-strip form (fp32, Wfrag, hb_sgp_strip_path)");
   if (hb_chain_recording()) {
     const int crc = hb_chain_flush(stream);   // whatever was recorded before this call runs before its contraction
@@ -1847,38 +1927,20 @@ static int sgp_fwd(int kind, int mode, const T* x, long sx, const T* z, const T*
   HB_REQUIRE(E <= 65535, "hb_sgp_fwd: too many experts");
   HB_REQUIRE(M * n < 2147483647L && M * M < 2147483647L && n * d < 2147483647L, "hb_sgp_fwd: matrix too large for 32-bit indexing");
   if (E * n == 0) return 0;
-  const bool draw = mode == HB_SGP_DIAGONAL && !eps_in;
   if (draw) HB_REQUIRE(rng && rng_lanes > 0 && eps_out, "hb_sgp_fwd: need eps_in, or rng and eps_out");
   HB_REQUIRE(!head || (M > 0 && P == 1 && ws && Wf), "hb_sgp_fwd_gauss: needs Wfrag, a workspace and P == 1");
-  const int nRB = hb_cdiv(M, SGP_BM);
-  const int gy = sgp_grid_y(E, n, nRB);
   // fused path: the contraction kernel leaves per-column partial sums, one small kernel finishes f, v (and draws eps)
-  if (M > 0 && P <= 4 && ws) {
-    SgpArgs<T> a;
-    a.x = x; a.sx = sx; a.z = z; a.ell = ell; a.dl = dl; a.W = W; a.Wf = Wf; a.u = u; a.A = A;
-    a.n = n; a.M = M; a.d = d; a.P = P;
-    a.W3 = prec == HB_PREC_BF16X3 ? (const void*)(Wf + 2 * E * M * M) : nullptr;
-    a.plane3 = E * M * M;
-    a.Af = A_frag;
-    a.part = ws + E * n + E * M * d;
-    const bool strip = sizeof(T) == 4 && ((Wf && hb_sgp_strip_path(E, n, M, d, P, prec)) ||
-                                          (sgp_strip_ok(E, n, M, d, W) && !hb_sgp_no_strip()));
-    const int gyp = strip ? 1 : gy;  // partial rows of the column statistics
+  if (form.partials) {
+    SgpArgs<T> a = sgp_args<T>(x, sx, z, ell, dl, W, Wf, prec, u, A, A_frag, ws + form.ws.shared, E, n, M, d, P);
+    const int gyp = form.part_rows;   // (the tiled kernels' row blocks; the strip forms leave one partial row)
     int rc;
     a.fin = 0;
-    if (strip) {
-      // third strip form with one column mean: the finishing pass runs inside the contraction kernel
-      if (sizeof(T) == 4 && sgp_fused_finish_ok(E, n, M, d, P, prec, a.Wf != nullptr && !a.W3, draw, rng_lanes)) {
-        a.fin = 1;
-        a.fin_diag = mode == HB_SGP_DIAGONAL;
-        a.fin_eps_in = mode == HB_SGP_DIAGONAL ? eps_in : (const T*)nullptr;
-        a.fin_rng = draw ? rng : (uint64_t*)nullptr;
-        a.fin_lanes = rng_lanes;
-        a.fin_eps_out = mode == HB_SGP_DIAGONAL ? eps_out : (T*)nullptr;
-        a.fin_f = f;
-        a.fin_v = v;
+    if (form.kernel != SGP_K_TILED) {
+      if (form.fin) {
+        a.fin = 1, a.fin_diag = diag, a.fin_eps_in = fin_eps_in, a.fin_rng = fin_rng, a.fin_lanes = rng_lanes;
+        a.fin_eps_out = fin_eps_out, a.fin_f = f, a.fin_v = v;
         if (head) {
-          HB_REQUIRE(P == 1 && head->units == E * hb_cdiv(n, SGP_SN), "hb_sgp_fwd_gauss: units must be hb_sgp_head_units(...)");
+          HB_REQUIRE(form.head_units > 0 && head->units == form.head_units, "hb_sgp_fwd_gauss: units must be hb_sgp_head_units(...)");
           a.head = 1;
           a.hy = head->y, a.hscale = head->scale, a.hvar = head->var;
           a.hdmu = head->dmu, a.hfbar = head->fbar, a.hpost = (T)head->post;
@@ -1889,17 +1951,17 @@ static int sgp_fwd(int kind, int mode, const T* x, long sx, const T* z, const T*
       if constexpr (std::is_same<T, float>::value) {
         if (g_rider.armed) {
           // recorded, not launched: the factorisation that produces W / Wfrag launches it inside its own grid (early-start form)
-          HB_REQUIRE(a.fin && !a.W3 && d <= SGP_E_DMAX, "hb_sgp_fwd after hb_sgp_rider_begin: this call cannot ride (hb_sgp_rider_supported)");
+          HB_REQUIRE(form.record, "hb_sgp_fwd after hb_sgp_rider_begin: this call cannot ride (hb_sgp_rider_supported)");
           sgp_grid(hb_cdiv(a.n, SGP_SN), 1, E, a.efast);
-          g_rider.a = a, g_rider.E = E, g_rider.valid = true, g_rider.armed = false;
+          g_rider.a = a, g_rider.form = form, g_rider.E = E, g_rider.valid = true, g_rider.armed = false;
           return 0;
         }
       }
-      rc = sgp_A_strip_launch(a, E, stream);
+      rc = sgp_A_strip_launch(a, E, form.kernel, stream);
       if (rc) return rc;
       if (a.fin) return 0;
     } else {
-      dim3 grid = sgp_grid(hb_cdiv(n, SGP_BN), gy, E, a.efast);
+      dim3 grid = sgp_grid(hb_cdiv(n, SGP_BN), gyp, E, a.efast);
       rc = sgp_A_launch<T>(a, grid, stream);
     }
     if (rc) return rc;
@@ -1909,22 +1971,16 @@ static int sgp_fwd(int kind, int mode, const T* x, long sx, const T* z, const T*
       HbChainJob j;
       j.kind = HB_CHAIN_SGP_FINISH;
       j.is64 = sizeof(T) == 8;
-      j.p[0] = a.part;
-      j.p[1] = mode == HB_SGP_DIAGONAL ? eps_in : (const T*)nullptr;
-      j.p[2] = draw ? rng : (uint64_t*)nullptr;
-      j.p[3] = mode == HB_SGP_DIAGONAL ? eps_out : (T*)nullptr;
-      j.p[4] = f;
-      j.p[5] = v;
-      j.l[0] = gyp, j.l[1] = rng_lanes, j.l[2] = total, j.l[3] = n, j.l[4] = P, j.l[5] = mode == HB_SGP_DIAGONAL;
+      j.p[0] = a.part, j.p[1] = fin_eps_in, j.p[2] = fin_rng, j.p[3] = fin_eps_out, j.p[4] = f, j.p[5] = v;
+      j.l[0] = gyp, j.l[1] = rng_lanes, j.l[2] = total, j.l[3] = n, j.l[4] = P, j.l[5] = diag;
       const long tb = total * (long)sizeof(T);
       j.span(0, tb * gyp * 5, HB_CHAIN_READ), j.span(1, tb, HB_CHAIN_READ), j.span(2, 2 * rng_lanes * (long)sizeof(uint64_t), HB_CHAIN_RW);
       j.span(3, tb, HB_CHAIN_WRITE), j.span(4, tb * P, HB_CHAIN_WRITE), j.span(5, tb, HB_CHAIN_WRITE);
       return hb_chain_push(j, stream);
     }
     const int fgrid = draw ? hb_cdiv(rng_lanes, 256) : hb_stream_grid((total + 1) / 2, 256);
-    hipLaunchKernelGGL(sgp_finish_part_kernel<T>, dim3(fgrid), dim3(256), 0, stream, a.part, gyp,
-                       mode == HB_SGP_DIAGONAL ? eps_in : (const T*)nullptr, draw ? rng : (uint64_t*)nullptr, rng_lanes,
-                       mode == HB_SGP_DIAGONAL ? eps_out : (T*)nullptr, f, v, total, n, P, mode);
+    hipLaunchKernelGGL(sgp_finish_part_kernel<T>, dim3(fgrid), dim3(256), 0, stream, a.part, gyp, fin_eps_in, fin_rng, rng_lanes,
+                       fin_eps_out, f, v, total, n, P, mode);
     HB_LAUNCH_CHECK();
     return 0;
   }
@@ -1940,12 +1996,8 @@ static int sgp_fwd(int kind, int mode, const T* x, long sx, const T* z, const T*
     }
   }
   if (M > 0) {
-    SgpArgs<T> a;
-    a.x = x; a.sx = sx; a.z = z; a.ell = ell; a.dl = dl; a.W = W; a.Wf = nullptr; a.u = u; a.A = A;
-    a.n = n; a.M = M; a.d = d; a.P = P;
-    a.W3 = nullptr; a.plane3 = 0; a.Af = nullptr;
-    a.part = nullptr;
-    dim3 grid = sgp_grid(hb_cdiv(n, SGP_BN), gy, E, a.efast);
+    SgpArgs<T> a = sgp_args<T>(x, sx, z, ell, dl, W, nullptr, HB_PREC_NATIVE, u, A, nullptr, nullptr, E, n, M, d, P);
+    dim3 grid = sgp_grid(hb_cdiv(n, SGP_BN), form.part_rows, E, a.efast);
     int rc = sgp_A_launch<T>(a, grid, stream);
     if (rc) return rc;
   }
@@ -1970,17 +2022,10 @@ static int sgp_A_only(int kind, const T* x, long sx, const T* z, const T* ell, l
   HB_REQUIRE(E <= 65535, "hb_sgp_A: too many experts");
   HB_REQUIRE(M * n < 2147483647L && M * M < 2147483647L && n * d < 2147483647L, "hb_sgp_A: matrix too large");
   if (E * n * M == 0) return 0;
-  SgpArgs<T> a;
-  a.x = x; a.sx = sx; a.z = z; a.ell = ell; a.dl = dl; a.W = W; a.Wf = Wf; a.u = nullptr; a.A = A;
-  a.n = n; a.M = M; a.d = d; a.P = 0;
-  a.W3 = prec == HB_PREC_BF16X3 ? (const void*)(Wf + 2 * E * M * M) : nullptr;
-  a.plane3 = E * M * M;
-  a.Af = nullptr;
-  a.part = nullptr;
-  if (sizeof(T) == 4 && ((sgp_strip_ok(E, n, M, d, W) && !hb_sgp_no_strip()) || prec == HB_PREC_BF16X3))
-    return sgp_A_strip_launch(a, E, stream);
-  const int nRB = hb_cdiv(M, SGP_BM);
-  dim3 grid = sgp_grid(hb_cdiv(n, SGP_BN), sgp_grid_y(E, n, nRB), E, a.efast);
+  SgpArgs<T> a = sgp_args<T>(x, sx, z, ell, dl, W, Wf, prec, nullptr, A, nullptr, nullptr, E, n, M, d, 0);
+  const SgpForm form = sgp_form(SGP_CALL_A, (int)sizeof(T), E, n, M, d, 0, prec, Wf != nullptr, (uintptr_t)W % 16 == 0, false, false, 0, false);
+  if (form.kernel != SGP_K_TILED) return sgp_A_strip_launch(a, E, form.kernel, stream);
+  dim3 grid = sgp_grid(hb_cdiv(n, SGP_BN), form.part_rows, E, a.efast);
   return sgp_A_launch<T>(a, grid, stream);
 }
 extern "C" int hb_sgp_A_f32(int kind, const float* x, long sx, const float* z, const float* ell, long dl,
@@ -3374,6 +3419,18 @@ static int sgp_lbar_frag_launch(const float* Kf, const float* Af, float* slabs, 
 }
 static int sgp_lbar_frag_launch(const double*, const double*, double*, long, long, long, long, int, int*, hipStream_t) { return -1; }
 
+// the operands every backward form reads; the strip form adds its own (x, z, ell, the W^T images, the fragment-major buffers)
+template <typename T>
+static SgpBwdArgs<T> sgp_bwd_args(const T* W, const T* u, const T* A, const T* fbar, const T* eps, const T* v, T* Kbar, long n, long M,
+                                  long d, long P, int mode) {
+  SgpBwdArgs<T> a;
+  a.W = W; a.u = u; a.A = A; a.fbar = fbar; a.eps = eps; a.v = v; a.Kbar = Kbar;
+  a.n = n; a.M = M; a.P = P; a.mode = mode;
+  a.x = nullptr; a.sx = 0; a.z = nullptr; a.ell = nullptr; a.dl = 0; a.d = d; a.WTf = nullptr; a.WT3 = nullptr;
+  a.plane3 = 0; a.part = nullptr; a.Af = nullptr; a.Kf = nullptr; a.Abf = nullptr;
+  return a;
+}
+
 template <typename T>
 static int sgp_bwd(int kind, int mode, const T* x, long sx, const T* z, const T* ell, long dl, const T* W,
                    const T* Wfrag, int prec, const T* u, const T* eps, const T* A, const T* A_frag, const T* v,
@@ -3391,13 +3448,13 @@ static int sgp_bwd(int kind, int mode, const T* x, long sx, const T* z, const T*
   HB_REQUIRE(E <= 65535, "hb_sgp_bwd: too many experts");
   HB_REQUIRE(M * n < 2147483647L && M * M < 2147483647L && n * d < 2147483647L, "hb_sgp_bwd: matrix too large for 32-bit indexing");
   if (E * M == 0) return 0;
-  T* ellpart = ws + E * n;  // (the first E*n elements of ws are unused since the residual coefficient is computed in-kernel)
-  T* mmws = ellpart + E * M * d;
-  const long mmws_elems = 32 * E * M * M;
-  // column-strip form: fp32, fragment-major W^T available, M a multiple of 32 up to SGP_SM_MAX, small d and P, no xbar
+  const SgpForm form = sgp_form(SGP_CALL_BWD, (int)sizeof(T), E, n, M, d, P, prec, Wfrag != nullptr, (uintptr_t)W % 16 == 0, true, false, 0,
+                                xbar != nullptr);
+  T* ellpart = ws + form.ws.ellpart;
+  T* mmws = ws + form.ws.shared;
+  const long mmws_elems = form.ws.mm_elems;
   const long nS = hb_cdiv(n, SGP_SN);
-  const bool strip = sizeof(T) == 4 && Wfrag && !xbar && hb_sgp_strip_path(E, n, M, d, P, prec) &&
-                     nS * (2 * d + P) * M * E <= mmws_elems;
+  const bool strip = form.bwd_strip;
   HB_REQUIRE(!A_frag || strip, "hb_sgp_bwd: fragment-major A / Kbar need the column-strip form (see hb_sgp_strip_path)");
   HB_REQUIRE(strip || (A && Kbar), "hb_sgp_bwd: row-major A and Kbar required outside the column-strip form");
   HB_REQUIRE(prec == HB_PREC_NATIVE || strip, "hb_sgp_bwd: bf16x3 needs the column-strip form (fp32, Wfrag, M %% 32 == 0, M <= %d, "
@@ -3406,32 +3463,31 @@ static int sgp_bwd(int kind, int mode, const T* x, long sx, const T* z, const T*
   HB_REQUIRE(!Abar_frag || (strip && A_frag && prec == HB_PREC_NATIVE),
              "hb_sgp_bwd_phi: needs the column-strip form in native precision with a fragment-major A (see hb_sgp_bwd_phi_supported)");
   if (strip) {
-    SgpBwdArgs<T> a;
-    a.W = W; a.u = u; a.A = A; a.fbar = fbar; a.eps = eps; a.v = v; a.Kbar = Kbar;
-    a.n = n; a.M = M; a.P = P; a.mode = mode;
-    a.x = x; a.sx = sx; a.z = z; a.ell = ell; a.dl = dl; a.d = d;
-    a.WTf = Wfrag + E * M * M;
-    a.WT3 = prec == HB_PREC_BF16X3 ? (const void*)(reinterpret_cast<const unsigned short*>(Wfrag + 2 * E * M * M) + 3 * E * M * M)
-                                   : nullptr;
-    a.plane3 = E * M * M;
-    a.part = mmws;   // consumed by the finish kernel before the Lbar contraction reuses the space
+    // (mmws: the strip partials, consumed by the finish kernel before the Lbar contraction reuses the space)
+    SgpBwdArgs<T> a = sgp_bwd_args<T>(W, u, A, fbar, eps, v, Kbar, n, M, d, P, mode);
+    const HbWfragLayout lay = hb_wfrag_layout(E, M, prec == HB_PREC_BF16X3);
+    a.x = x; a.sx = sx; a.z = z; a.ell = ell; a.dl = dl;
+    a.WTf = Wfrag + lay.wt;
+    a.WT3 = prec == HB_PREC_BF16X3 ? lay.wt3(Wfrag) : nullptr;
+    a.plane3 = lay.plane;
+    a.part = mmws;
     a.Af = A_frag; a.Kf = Kbar_frag; a.Abf = Abar_frag;
     if (A_frag) a.Kbar = nullptr;   // Kbar only feeds the Lbar contraction: the fragment-major copy is enough
     int rc = sgp_bwd_strip_launch(a, E, nS, stream);
     if (rc) return rc;
     if (A_frag) {
       // strip partials and Lbar slabs side by side in the workspace; ONE finish launch folds both
-      const long npart = ((nS * (2 * d + P) * M * E + 63) / 64) * 64;
-      const long slab_cap = (mmws_elems - npart) / (E * M * M);
+      T* slabs = ws + form.ws.slabs;
+      const long slab_cap = form.ws.slab_cap;
       HB_REQUIRE(slab_cap >= 1, "hb_sgp_bwd: workspace too small for the Lbar slabs");
       int S = 0;
-      rc = sgp_lbar_frag_launch(Abar_frag ? Abar_frag : Kbar_frag, A_frag, mmws + npart, slab_cap > 32 ? 32 : slab_cap, E, M, nS, prec, &S, stream);
+      rc = sgp_lbar_frag_launch(Abar_frag ? Abar_frag : Kbar_frag, A_frag, slabs, slab_cap > 32 ? 32 : slab_cap, E, M, nS, prec, &S, stream);
       if (rc) return rc;
       const int nbx = (int)hb_cdiv(M, 64), nb_strip = nbx * (int)(2 * d + P) * (int)E;
       const long nTl = M / 32, phi_units = E * nTl * (nTl + 1);   // (16 rows of a 32 x 32 lower tile each)
       const long nb_fold = Abar_frag ? (phi_units < 2048 ? phi_units : 2048) : (long)hb_stream_grid(E * M * M, 256);
       hipLaunchKernelGGL(sgp_bwd_finish_kernel<T>, dim3((unsigned)(nb_strip + nb_fold)), dim3(256), 0, stream,
-                         mmws, (int)nS, M, d, dl, P, zbar, ellbar, ubar, nb_strip, nbx, mmws + npart, S, E, Lbar, Abar_frag ? 1 : 0);
+                         mmws, (int)nS, M, d, dl, P, zbar, ellbar, ubar, nb_strip, nbx, slabs, S, E, Lbar, Abar_frag ? 1 : 0);
       HB_LAUNCH_CHECK();
       return 0;
     }
@@ -3443,11 +3499,7 @@ static int sgp_bwd(int kind, int mode, const T* x, long sx, const T* z, const T*
     return rc2;
   }
   if (n > 0) {
-    SgpBwdArgs<T> a;
-    a.W = W; a.u = u; a.A = A; a.fbar = fbar; a.eps = eps; a.v = v; a.Kbar = Kbar;
-    a.n = n; a.M = M; a.P = P; a.mode = mode;
-    a.x = nullptr; a.sx = 0; a.z = nullptr; a.ell = nullptr; a.dl = 0; a.d = d; a.WTf = nullptr; a.WT3 = nullptr;
-    a.plane3 = 0; a.part = nullptr; a.Af = nullptr; a.Kf = nullptr; a.Abf = nullptr;
+    SgpBwdArgs<T> a = sgp_bwd_args<T>(W, u, A, fbar, eps, v, Kbar, n, M, d, P, mode);
     const int nRB = hb_cdiv(M, SGP_BM);
     dim3 grid = sgp_grid(hb_cdiv(n, SGP_BN), sgp_grid_y(E, n, nRB), E, a.efast);
     constexpr long VECH = 16 / sizeof(T);
@@ -3520,8 +3572,7 @@ extern "C" int hb_sgp_bwd_f64(int kind, int mode, const double* x, long sx, cons
 // 1 when hb_sgp_bwd_phi_f32 serves this shape: the column-strip form in native precision (hb_sgp_strip_path) and the
 // diagnostic switch hb_debug_set("sgp_phi_direct", 0) not set.  The planner asks once, when it builds a plan.
 extern "C" int hb_sgp_bwd_phi_supported(long E, long n, long M, long d, long P) {
-  if (hb_debug_get("sgp_phi_direct", 1) == 0) return 0;
-  return hb_sgp_strip_path(E, n, M, d, P, HB_PREC_NATIVE);
+  return sgp_form_query(E, n, M, d, P, HB_PREC_NATIVE, true, false, 0).bwd_phi ? 1 : 0;
 }
 
 // hb_sgp_bwd_f32 for the pipeline whose only reader of Lbar is the Cholesky VJP's first product, Phisym(L^T tril(Lbar)):
@@ -3534,7 +3585,7 @@ extern "C" int hb_sgp_bwd_phi_f32(int kind, int mode, const float* x, long sx, c
                                   const float* v, const float* fbar, float* Abar_frag, float* Phi, float* ubar, float* zbar,
                                   float* ellbar, long E, long n, long M, long d, long P, float* ws, void* stream) {
   HB_REQUIRE(Wfrag && A_frag && Abar_frag && Phi, "hb_sgp_bwd_phi: NULL pointer");
-  HB_REQUIRE(hb_sgp_strip_path(E, n, M, d, P, HB_PREC_NATIVE), "hb_sgp_bwd_phi: shape outside the column-strip form (see hb_sgp_strip_path)");
+  HB_REQUIRE(sgp_form_query(E, n, M, d, P, HB_PREC_NATIVE, true, false, 0).path, "hb_sgp_bwd_phi: shape outside the column-strip form (see hb_sgp_strip_path)");
   return sgp_bwd<float>(kind, mode, x, sx, z, ell, dl, W, Wfrag, HB_PREC_NATIVE, u, eps, nullptr, A_frag, v, fbar, nullptr,
                         Abar_frag, Phi, ubar, zbar, ellbar, nullptr, E, n, M, d, P, ws, (hipStream_t)stream, Abar_frag);
 }

@@ -53,6 +53,9 @@ static inline long pred_chunk_cols(long E, long n, long M, long P, int s_kind) {
   return c < n32 ? c : (n32 > 0 ? n32 : 32);
 }
 
+extern "C" int hb_sgp_predict_fused(long E, long n, long M, long d, long P, int s_kind, int has_wfrag, int dtype_bytes) {
+  return pred_is_fused(E, n, M, d, P, s_kind, has_wfrag != 0, dtype_bytes) ? 1 : 0;
+}
 extern "C" long hb_sgp_predict_ws_elems(long E, long n, long M, long d, long P, int s_kind, int has_wfrag, int dtype_bytes) {
   if (E <= 0 || n <= 0 || M <= 0 || P <= 0) return 0;
   if (pred_is_fused(E, n, M, d, P, s_kind, has_wfrag != 0, dtype_bytes)) return s_kind == HB_SGP_S_TRIL ? M * M : 0;

@@ -21,6 +21,11 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._lib import HipBackendError as _HipBackendError
+from ._lib import constants as _constants
+
+# hb_matutil's modes (include/henbun_hip.h)
+MATUTIL_BAND, MATUTIL_ADD_EYE, MATUTIL_PHI, MATUTIL_SYM, MATUTIL_SYMLOW = (
+    _constants()["HB_MATUTIL_" + k] for k in ("BAND", "ADD_EYE", "PHI", "SYM", "SYMLOW"))
 
 _uid = itertools.count()
 
@@ -955,13 +960,8 @@ def _matmul_emit(plan, node):
     if (not at.get("actgrad") and len(cons) == 1 and cons[0].op == "matutil" and bias is None and at["act"] == "none" and y.shape[-1] == y.shape[-2]
             and y not in plan.outputs and y not in plan._bind):
         ma = cons[0].attrs
-        if ma["mode"] == 2:
-            epi = H.MM_PHI_OUT
-        elif ma["mode"] == 3:
-            epi = H.MM_SYM_OUT
-        elif ma["mode"] == 4:
-            epi = H.MM_SYMLOW_OUT
-        elif ma["mode"] == 0 and ma["lower"] < 0 and ma["upper"] == 0:
+        epi = {MATUTIL_PHI: H.MM_PHI_OUT, MATUTIL_SYM: H.MM_SYM_OUT, MATUTIL_SYMLOW: H.MM_SYMLOW_OUT}.get(ma["mode"], 0)
+        if ma["mode"] == MATUTIL_BAND and ma["lower"] < 0 and ma["upper"] == 0:
             epi = H.MM_TRIL_OUT
     if epi:
         out = plan.out(cons[0].outputs[0])
@@ -980,8 +980,8 @@ def _matmul_emit(plan, node):
     # the in-workgroup split-K form (small square-ish fp32 products: the Cholesky VJP) hosts pending side jobs
     ysh = y.shape
     kk = node.inputs[0].shape[-2] if at["ta"] else node.inputs[0].shape[-1]
-    wgk_like = (plan.dtype == plan.torch.float32 and bias is None and ysh[-1] % 32 == 0 and ysh[-2] % 32 == 0 and kk % 128 == 0
-                and 128 <= kk <= 4096 and (ysh[-1] // 32) * (ysh[-2] // 32) * int(np.prod(ysh[:-2]) if len(ysh) > 2 else 1) <= 1024)
+    wgk_like = (plan.dtype == plan.torch.float32 and bias is None
+                and H.matmul_wgk_shape(ysh[-2], ysh[-1], kk, int(np.prod(ysh[:-2])) if len(ysh) > 2 else 1))
     host = wgk_like and plan.attach_side(node)
     # The product whose result is Kbar of a Gram matrix K(X, X) and feeds nothing but that Gram matrix's VJP (the last
     # product of the Cholesky VJP): the VJP runs in the product's epilogue (hb_matmul_gram_vjp), gram_grad keeps the fold.
@@ -1002,7 +1002,7 @@ def _matmul_emit(plan, node):
             X, ell = plan.buf(tX), plan.buf(tell)
             oX = plan.out(gg.outputs[0])
             lws = plan.scratch((max(B * n * d, 1),))
-            part = plan.scratch((B * (n // 32) * (n // 32) * 32 * 2 * d,))
+            part = plan.scratch((H.matmul_gram_vjp_ws_elems(B, n, d),))
             counters = plan.torch.zeros((B * (n // 32),), dtype=plan.torch.int32, device=plan.device)
             plan._gram_in_mm[gg.id] = (lws, (n if sEll != 0 else B * n), d, dl, (B if sEll != 0 else 1))
             plan.steps.append(lambda: H.matmul_gram_vjp(a, b, out, at["ta"], at["tb"], X, sX, ell, sEll, dl, d, oX, lws, part, counters))
@@ -1080,7 +1080,7 @@ def _known_lower(t) -> bool:
     if n.op == "sgp_grad":
         return t.index == 0
     if n.op == "matutil":
-        return n.attrs["mode"] == 2 or (n.attrs["mode"] == 0 and n.attrs["upper"] == 0)
+        return n.attrs["mode"] == MATUTIL_PHI or (n.attrs["mode"] == MATUTIL_BAND and n.attrs["upper"] == 0)
     if n.op == "stop_gradient":
         return _known_lower(n.inputs[0])
     return False
@@ -1090,11 +1090,11 @@ def band_part(x, num_lower, num_upper):
     x = as_tensor(x)
     if int(num_lower) < 0 and int(num_upper) == 0 and _known_lower(x):
         return x  # tril of a matrix that is already lower-triangular
-    return matutil(x, 0, num_lower, num_upper)
+    return matutil(x, MATUTIL_BAND, num_lower, num_upper)
 
 
 def add_eye(x, alpha):
-    return matutil(x, 1, alpha=alpha)
+    return matutil(x, MATUTIL_ADD_EYE, alpha=alpha)
 
 
 def _matutil_emit(plan, node):
@@ -1111,15 +1111,15 @@ def _matutil_vjp(node, gs):
     if g is None:
         return [None]
     a = node.attrs
-    if a["mode"] == 0:
-        return [matutil(g, 0, a["lower"], a["upper"])]
-    if a["mode"] == 1:
+    if a["mode"] == MATUTIL_BAND:
+        return [matutil(g, MATUTIL_BAND, a["lower"], a["upper"])]
+    if a["mode"] == MATUTIL_ADD_EYE:
         return [g]
-    if a["mode"] == 2:
-        return [matutil(g, 2)]
-    if a["mode"] == 4:
-        return [matutil(matutil(g, 3), 2)]   # y_ij = x_{max,min} / 2:  xbar = Phi((g + g^T) / 2)
-    return [matutil(g, 3)]
+    if a["mode"] == MATUTIL_PHI:
+        return [matutil(g, MATUTIL_PHI)]
+    if a["mode"] == MATUTIL_SYMLOW:
+        return [matutil(matutil(g, MATUTIL_SYM), MATUTIL_PHI)]   # y_ij = x_{max,min} / 2:  xbar = Phi((g + g^T) / 2)
+    return [matutil(g, MATUTIL_SYM)]
 
 
 defop("matutil", _matutil_emit, _matutil_vjp)
@@ -1182,7 +1182,7 @@ def _cholesky_emit(plan, node):
             # Not requested by sgp_predict / sgp_predict_cov: prediction runs in native precision only.
             bf3 = (str(getattr(_st.numerics, "contraction", "native")) == "bf16x3" and M <= 512
                    and any(c.op in ("sgp", "sgp_grad") for c in users))
-            frag = plan.scratch(((5 if bf3 else 2) * max(int(np.prod(node.outputs[0].shape)), 1),))
+            frag = plan.scratch((H.cholesky_frag_elems(B, M, bf3),))
             plan._wfrag[inv_node.outputs[0]] = (frag, bf3)
         # launch 0 of the 64-column chain hosts pending side jobs (minibatch gather, the sample of q(u))
         host = plan.dtype == plan.torch.float32 and M % 64 == 0 and plan.attach_side(node)
@@ -1243,7 +1243,7 @@ def _cholesky_vjp(node, gs):
         return [None]
     L = node.outputs[0]
     W = trinv(L)
-    P = matutil(matmul(L, band_part(g, -1, 0), transpose_a=True), 4)
+    P = matutil(matmul(L, band_part(g, -1, 0), transpose_a=True), MATUTIL_SYMLOW)
     res = matmul(matmul(W, P, transpose_a=True), W)
     res.node.attrs["sym_result"] = True   # L^-T Psym L^-1: symmetric (to rounding); gram_grad then skips the transposed reads
     return [res]
@@ -1648,7 +1648,7 @@ def _gram_emit(plan, node):
     y = node.outputs[0]
     # K + jitter*I (kern.Cholesky, reference gp/kernels.py:101) as the Gram kernel's own diagonal term
     cons = plan._consumers.get(y, [])
-    if (len(cons) == 1 and cons[0].op == "matutil" and cons[0].attrs["mode"] == 1 and y.shape[-1] == y.shape[-2]
+    if (len(cons) == 1 and cons[0].op == "matutil" and cons[0].attrs["mode"] == MATUTIL_ADD_EYE and y.shape[-1] == y.shape[-2]
             and y not in plan.outputs and y not in plan._bind):
         jit = cons[0].attrs["alpha"]
         # K(z, z) + jitter I whose ONLY reader is a factor + inverse in persistent form (fp32, M % 64 == 0): the Cholesky
@@ -1885,7 +1885,7 @@ def _phi_direct_match(plan, node, a_frag, prec, need_x):
         return None, "Lbar is a plan output, or has a reader besides the Cholesky VJP's product"
     c = plan._consumers[Lb][0]
     t = Lb
-    if c.op == "matutil" and c.attrs["mode"] == 0 and c.attrs["lower"] < 0 and c.attrs["upper"] == 0:   # band_part(-1, 0)
+    if c.op == "matutil" and c.attrs["mode"] == MATUTIL_BAND and c.attrs["lower"] < 0 and c.attrs["upper"] == 0:   # band_part(-1, 0)
         t = c.outputs[0]
         if not private(t):
             return None, "tril(Lbar) is a plan output, or has a second reader"
@@ -1903,7 +1903,7 @@ def _phi_direct_match(plan, node, a_frag, prec, need_x):
     if not private(Q) or c.id in plan._colsum_of or c.id in getattr(plan, "_mm_head", {}):
         return None, "L^T tril(Lbar) is a plan output, or has a reader besides Phisym"
     mu = plan._consumers[Q][0]
-    if not (mu.op == "matutil" and mu.attrs["mode"] == 4):
+    if not (mu.op == "matutil" and mu.attrs["mode"] == MATUTIL_SYMLOW):
         return None, "L^T tril(Lbar) is not followed by Phisym (matutil mode 4)"
     zsh, xsh = node.inputs[1].shape, node.inputs[0].shape
     E, M, n, d, P = int(np.prod(zsh[:-2])) if len(zsh) > 2 else 1, zsh[-2], xsh[-2], xsh[-1], node.inputs[4].shape[-2]

@@ -42,8 +42,8 @@ SGP_S_DIAG, SGP_S_TRIL = _hb("SGP_S_DIAG", "SGP_S_TRIL")
 ACQ = {k[len("HB_ACQ_"):].lower(): v for k, v in _C.items() if k.startswith("HB_ACQ_")}   # 'ei', 'pi', 'ucb'
 PREC_NATIVE, PREC_BF16X3 = _hb("PREC_NATIVE", "PREC_BF16X3")
 LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON = _hb("LIK_GAUSSIAN", "LIK_BERNOULLI", "LIK_POISSON")
-# hb_matutil's modes are plain integers in the header
-MATUTIL_BAND, MATUTIL_ADD_EYE, MATUTIL_PHI, MATUTIL_SYM = 0, 1, 2, 3
+MATUTIL_BAND, MATUTIL_ADD_EYE, MATUTIL_PHI, MATUTIL_SYM, MATUTIL_SYMLOW = _hb("MATUTIL_BAND", "MATUTIL_ADD_EYE", "MATUTIL_PHI",
+                                                                              "MATUTIL_SYM", "MATUTIL_SYMLOW")
 
 WS_ELEMS = 1 << 16  # generic scratch (elements) for reductions / KL partials
 
@@ -850,10 +850,15 @@ def cholesky_inverse(A, out=None, inv=None, info=None, ws=None, frag=None, frag_
         ws = cholesky_workspace(A.dtype, A.device, B, M)
     assert ws.numel() >= cholesky_ws_elems(B, M, A.dtype), "hb_cholesky_inverse: workspace too small (cholesky_ws_elems)"
     if frag is not None:
-        assert frag.numel() >= (5 if frag_bf16x3 else 2) * B * M * M and M % 32 == 0 and frag.dtype == A.dtype
+        assert frag.numel() >= cholesky_frag_elems(B, M, frag_bf16x3) and M % 32 == 0 and frag.dtype == A.dtype
     _lib.lib().call("hb_cholesky_inverse" + _suf(A), _p(A), _p(out), _p(inv), B, M, _p(info), _p(ws), _p(frag),
                     int(bool(frag_bf16x3 and frag is not None)), stream())
     return out, inv, info
+
+
+def cholesky_frag_elems(B, M, bf16x3=False):
+    """Elements of cholesky_inverse's `frag` buffer: the images of W and W^T, and the bf16x3 planes behind them if asked for."""
+    return int(_lib.lib().raw("hb_cholesky_frag_elems")(int(B), int(M), int(bool(bf16x3))))
 
 
 def cholesky_persistent_shape(B, M, dtype):
@@ -885,7 +890,7 @@ def gram_cholesky_inverse(X, ell, diag_add, kind=KERN_RBF, out=None, inv=None, i
         ws = cholesky_workspace(X.dtype, X.device, B, M)
     assert ws.numel() >= cholesky_ws_elems(B, M, X.dtype)
     if frag is not None:
-        assert frag.numel() >= (5 if frag_bf16x3 else 2) * B * M * M and frag.dtype == X.dtype
+        assert frag.numel() >= cholesky_frag_elems(B, M, frag_bf16x3) and frag.dtype == X.dtype
     _lib.lib().call("hb_gram_cholesky_inverse_f32", kind, _p(X), sX, _p(ell), sEll, dl, d, float(diag_add), _p(out), _p(inv), B, M,
                     _p(info), _p(ws), _p(frag), int(bool(frag_bf16x3 and frag is not None)), stream())
     return out, inv, info
@@ -921,17 +926,20 @@ def sgp_strip_path(E, n, M, d, P, prec=PREC_NATIVE):
 def sgp_frag_elems(E, n, M, prec=PREC_NATIVE):
     """fp32 elements of a fragment-major [E, M, n] operand buffer (columns padded to whole strips of 32); the bf16x3
     form holds three bf16 planes instead of one fp32 image: 1.5 times the bytes."""
-    base = E * M * 32 * ((n + 31) // 32)
-    return base * 3 // 2 if prec == PREC_BF16X3 else base
+    return int(_lib.lib().raw("hb_sgp_frag_elems")(int(E), int(n), int(M), int(prec)))
+
+
+def _sgp_fwd_query(name, x, z, u, prec, has_wfrag, draw, rng):
+    """A query of the library about the sgp_fwd call with these operands (0 for anything but fp32)."""
+    E, n, M, d, P, _ = _sgp_dims(x, z, u)
+    if x.dtype != torch.float32:
+        return 0
+    return int(_lib.lib().raw(name)(E, n, M, d, P, int(prec), int(bool(has_wfrag)), int(bool(draw)), rng.nlanes if rng is not None else 0))
 
 
 def sgp_head_units(x, z, u, prec, has_wfrag, draw, rng):
     """Number of partial-sum units hb_sgp_fwd_gauss leaves for this call (0: the likelihood head cannot ride in it)."""
-    E, n, M, d, P, _ = _sgp_dims(x, z, u)
-    if x.dtype != torch.float32:
-        return 0
-    return int(_lib.lib().raw("hb_sgp_head_units")(E, n, M, d, P, int(prec), int(bool(has_wfrag)), int(bool(draw)),
-                                                  rng.nlanes if rng is not None else 0))
+    return _sgp_fwd_query("hb_sgp_head_units", x, z, u, prec, has_wfrag, draw, rng)
 
 
 def matmul_gram_vjp_ok(M, K, batch, d, dtype):
@@ -939,6 +947,17 @@ def matmul_gram_vjp_ok(M, K, batch, d, dtype):
     if dtype != torch.float32:
         return False
     return bool(_lib.lib().raw("hb_matmul_gram_vjp_ok")(int(M), int(K), int(batch), int(d)))
+
+
+def matmul_gram_vjp_ws_elems(batch, M, d):
+    """Scratch elements of matmul_gram_vjp's `part` (hb_matmul_gram_vjp_ws_elems)."""
+    return int(_lib.lib().raw("hb_matmul_gram_vjp_ws_elems")(int(batch), int(M), int(d)))
+
+
+def matmul_wgk_shape(M, N, K, batch):
+    """The shape [batch, M, K] x [batch, K, N] lies inside hb_matmul_f32's in-workgroup split-K form (hb_matmul_wgk_shape:
+    the shape part of the rule only -- alignment, flags and the mm_no_wgk switch are the call's own business)."""
+    return bool(_lib.lib().raw("hb_matmul_wgk_shape")(int(M), int(N), int(K), int(batch)))
 
 
 def matmul_gram_vjp(a, b, out, transA, transB, X, sX, ell, sEll, dl, d, xbar, ell_partial, part, counters):
@@ -981,11 +1000,7 @@ def matmul_gauss(x, w, bias, head):
 def sgp_rider_supported(x, z, u, prec, has_wfrag, draw, rng):
     """1 when this forward call can be recorded (sgp_rider_begin) and start inside the launch of the persistent
     factorisation that produces its W (hb_sgp_rider_supported)."""
-    E, n, M, d, P, _ = _sgp_dims(x, z, u)
-    if x.dtype != torch.float32:
-        return False
-    return bool(_lib.lib().raw("hb_sgp_rider_supported")(E, n, M, d, P, int(prec), int(bool(has_wfrag)), int(bool(draw)),
-                                                         rng.nlanes if rng is not None else 0))
+    return bool(_sgp_fwd_query("hb_sgp_rider_supported", x, z, u, prec, has_wfrag, draw, rng))
 
 
 def sgp_rider_begin():
@@ -1055,11 +1070,10 @@ def sgp_A(x, z, ell, W, out=None, wfrag=None, prec=PREC_NATIVE):
 
 
 def sgp_predict_fused(dtype, E, n, M, d, P, s_kind, has_wfrag):
-    """True when hb_sgp_predict runs its fused streaming kernel for these extents (the rule of csrc/sgp_predict.hip,
-    pred_is_fused): fp32 with the fragment-major W images, M % 32 == 0, 32 <= M <= 512, d <= 4, P <= 4, and a full-rank
-    S only for one latent function of one expert.  Everything else runs in column chunks."""
-    return (dtype == torch.float32 and bool(has_wfrag) and 32 <= M <= 512 and M % 32 == 0 and 1 <= d <= 4 and 1 <= P <= 4
-            and n > 0 and 1 <= E <= 65535 and (s_kind == SGP_S_DIAG or E * P == 1))
+    """True when hb_sgp_predict runs its fused streaming kernel for these extents (hb_sgp_predict_fused); everything else
+    runs in column chunks."""
+    return bool(_lib.lib().raw("hb_sgp_predict_fused")(int(E), int(n), int(M), int(d), int(P), int(s_kind), int(bool(has_wfrag)),
+                                                       _elem_bytes(dtype)))
 
 
 def sgp_predict_ws_elems(dtype, E, n, M, d, P, s_kind, has_wfrag):

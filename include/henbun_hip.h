@@ -58,7 +58,9 @@ extern "C" {
  * Phisym(-Abar A^T) where hb_sgp_bwd_f32 writes Lbar); hb_sgp_pathwise_grad_f32 / _f64, hb_sgp_pathwise_argmax_f32 / _f64
  * and hb_sgp_pathwise_argmax_ws_elems (input gradients and the per-draw extremum of pathwise function draws);
  * hb_sgp_predict_grad_f32 / _f64, hb_sgp_predict_grad_ws_elems, hb_sgp_acq_f32 / _f64, hb_sgp_acq_ws_elems and the enum
- * values HB_ACQ_* (input gradients of the closed-form predictive and closed-form acquisition functions). */
+ * values HB_ACQ_* (input gradients of the closed-form predictive and closed-form acquisition functions);
+ * hb_sgp_predict_fused, hb_sgp_frag_elems, hb_cholesky_frag_elems, hb_matmul_wgk_shape and the enum values HB_MATUTIL_*
+ * (rules and sizes a planner asks for instead of restating them). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -247,13 +249,14 @@ int hb_gather_rows_multi_draw_f64(int narr, const double* const* srcs, const lon
                                   long nsrc, uint64_t* state, long nlanes, long lo, long hi, long* idx_out,
                                   const long* perm, long n, int* err, void* stream);
 
-/* batched [B,R,C] matrix utilities.  mode 0 = tf.matrix_band_part(lower,upper)
- * (reference variationals.py:145); 1 = + alpha*I (kernels.py:100 jitter);
- * 2 = Phi (lower triangle, halved diagonal) of the Cholesky gradient;
- * 3 = 0.5*(A + A^T);
- * 4 = symmetric matrix built from HALF the lower triangle: out[i][j] = out[j][i] = 0.5*A[max(i,j)][min(i,j)]
+/* batched [B,R,C] matrix utilities.  mode BAND (0) = tf.matrix_band_part(lower,upper)
+ * (reference variationals.py:145); ADD_EYE (1) = + alpha*I (kernels.py:100 jitter);
+ * PHI (2) = Phi (lower triangle, halved diagonal) of the Cholesky gradient;
+ * SYM (3) = 0.5*(A + A^T);
+ * SYMLOW (4) = symmetric matrix built from HALF the lower triangle: out[i][j] = out[j][i] = 0.5*A[max(i,j)][min(i,j)]
  *     (= (Phi(A) + Phi(A)^T)/2, the operand that makes the Cholesky gradient's L^-T Phi(.) L^-1 symmetric by
  *     construction, so no symmetrising pass over the result is needed). */
+enum { HB_MATUTIL_BAND = 0, HB_MATUTIL_ADD_EYE = 1, HB_MATUTIL_PHI = 2, HB_MATUTIL_SYM = 3, HB_MATUTIL_SYMLOW = 4 };
 int hb_matutil_f32(const float* in, float* out, long B, long R, long C, int mode, long lower,
                    long upper, double alpha, void* stream);
 int hb_matutil_f64(const double* in, double* out, long B, long R, long C, int mode, long lower,
@@ -453,6 +456,8 @@ int hb_cholesky_f64(const double* A, double* L, long B, long M, int* info, void*
  * operand images of W and W^T (3 + 3 planes of B*M*M bf16: each fp32 entry split into hi + mid + lo bf16 terms;
  * [term][B][t][Q][k16-step q][64 lanes][8] = X[32t+li][32Q+16q+8h+j]) for the HB_PREC_BF16X3 contractions. */
 long hb_cholesky_inverse_ws_elems(long B, long M, int elem_bytes);
+/* elements of Wfrag for this (B, M): 2*B*M*M, or 5*B*M*M with the bf16x3 planes */
+long hb_cholesky_frag_elems(long B, long M, int bf16x3);
 /* 1 when hb_cholesky_inverse_f32 takes the persistent launch for this (B, M) (and the diagnostic switch leaves it on). */
 int hb_cholesky_persistent_shape(long B, long M, int elem_bytes);
 /* hb_gram_fwd with X2 = X and a diag_add, followed by hb_cholesky_inverse, as one launch: the persistent kernel synthesises its tiles of
@@ -500,6 +505,9 @@ long hb_sgp_ws_elems(long E, long n, long M, long d, long P);
  *   A_frag [E][M/32 row tiles t][nS = ceil(n/32) strips s][4 v][64 lanes (li + 32 h)][4 s'] = A[32t+li][32s+16h+4v+s']
  * (zeros past column n): the MFMA operand fragments of the Lbar contraction over the data axis, in load order. */
 int hb_sgp_strip_path(long E, long n, long M, long d, long P, int prec);
+/* elements (of the arithmetic type) of a fragment-major [E, M, n] buffer -- A_frag, Kbar_frag, Abar_frag: E*M*32*ceil(n/32),
+ * or for HB_PREC_BF16X3 three bf16 planes of that many entries (1.5 times the elements) */
+long hb_sgp_frag_elems(long E, long n, long M, int prec);
 int hb_sgp_fwd_f32(int kind, int mode, const float* x, long sx, const float* z, const float* ell,
                    long dl, const float* W, const float* Wfrag, int prec, const float* u,
                    const float* eps_in, uint64_t* rng, long rng_lanes, float* eps_out, float* A,
@@ -546,6 +554,10 @@ int hb_sgp_rider_flush(void* stream);
  * hb_matmul_gram_vjp_ws_elems(batch, M, d) scratch elements; `counters`: batch * M / 32 zero 32-bit words, left zero.
  * hb_gram_ell_fold_* folds the partials into ellbar (the last launch of hb_gram_bwd on its own; chain-aware). */
 int hb_matmul_gram_vjp_ok(long M, long K, long batch, long d);
+/* The shape part of the rule by which hb_matmul_f32 takes its in-workgroup split-K form (M % 32 == 0, N % 32 == 0,
+ * K % 128 == 0, 128 <= K <= 4096, <= 1024 tiles): what a planner may ask before the operands exist.  Alignment, flags
+ * and the diagnostic switch mm_no_wgk are NOT part of it -- a call may still take another form. */
+int hb_matmul_wgk_shape(long M, long N, long K, long batch);
 long hb_matmul_gram_vjp_ws_elems(long batch, long M, long d);
 int hb_matmul_gram_vjp_f32(const float* A, const float* B, float* C, long batch, long M, long K, long lda, long ldb,
                            long ldc, long sA, long sB, long sC, int transA, int transB, const float* X, long sX,
@@ -591,6 +603,8 @@ int hb_sgp_A_f64(int kind, const double* x, long sx, const double* z, const doub
  * statistics kernel.  ws >= hb_sgp_predict_ws_elems(E, n, M, d, P, s_kind, Wfrag != NULL, sizeof(T)) elements (16-byte
  * aligned; independent of n beyond one chunk). */
 long hb_sgp_predict_ws_elems(long E, long n, long M, long d, long P, int s_kind, int has_wfrag, int dtype_bytes);
+/* 1 when hb_sgp_predict_* runs its fused streaming kernel for these extents (else: column chunks) */
+int hb_sgp_predict_fused(long E, long n, long M, long d, long P, int s_kind, int has_wfrag, int dtype_bytes);
 int hb_sgp_predict_f32(int kind, const float* x, long sx, const float* z, const float* ell, long dl, const float* W,
                        const float* Wfrag, const float* m, const float* s, int s_kind, int mode, double jitter, float* mean,
                        float* var, long E, long n, long M, long d, long P, float* ws, void* stream);
