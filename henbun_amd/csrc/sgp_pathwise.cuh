@@ -1,14 +1,17 @@
 // What the kernels over pathwise function draws share (csrc/sgp_pathwise.hip: values; csrc/sgp_pathwise_grad.hip: input
-// gradients and the per-draw extremum): the tile constants, the double-revolution sincos, the synthesis of a column's basis
+// gradients and the per-draw extremum; csrc/sgp_pathwise_acq.hip: the acquisition reduced over the draws): the tile
+// constants, the double-revolution sincos, the synthesis of a column's basis
 // values, the staging of the coef tile and the K-loop of the value contraction.  One definition of each -- but for the
 // K-loop, which the gradient kernel repeats with its own operands (see pw_value_tiles) -- so that every kernel forms the
-// same basis values and the same k-ordered fma chains: their outputs agree to the bit.
+// same basis values and the same k-ordered fma chains: their outputs agree to the bit.  At the end, the host-side checks
+// and argument packing the entries have in common.
 #ifndef HB_SGP_PATHWISE_CUH
 #define HB_SGP_PATHWISE_CUH
 
 #include "common.cuh"
 #include "mfma16.cuh"
 #include "sgp_strip.cuh"
+#include "../../include/henbun_hip.h"
 
 #define PW_THREADS 256   // 4 waves, 32 columns each
 #define PW_CN 128        // columns per workgroup
@@ -233,6 +236,30 @@ __device__ __forceinline__ void pw_value_tiles(const PwArgs<T>& a, int s0, typen
       }
     }
   }
+}
+
+// ------------------------------------------------------------------------------------------------ host
+// the checks hb_sgp_pathwise makes, under the caller's name; the entry's own output pointers are checked by the caller
+template <typename T>
+static int pathwise_check(const char* who, int kind, const T* x, const T* omega, const T* z, const T* ell, long dl, const T* coef,
+                          bool outputs, long n, long nmin, long L, long M, long d, long S, long smax) {
+  HB_REQUIRE(kind == HB_KERN_RBF, "%s: the random-feature prior path is that of the UnitRBF kernel only (kind=%d)", who, kind);
+  HB_REQUIRE(n >= nmin && L >= 1 && M >= 0 && d >= 1 && S >= 1, "%s: bad extents (n=%ld L=%ld M=%ld d=%ld S=%ld)", who, n, L, M, d, S);
+  HB_REQUIRE(dl == 1 || dl == d, "%s: lengthscales must have 1 or d entries", who);
+  HB_REQUIRE(x && omega && ell && coef && outputs && (z || M == 0), "%s: NULL pointer", who);
+  HB_REQUIRE(n < 2147483647L && L < (1L << 29) && M < (1L << 29) && S * (2 * L + M) < 2147483647L && S * n < 2147483647L &&
+                 d < 2147483647L && hb_cdiv(S, smax) <= 65535,
+             "%s: too large (n, S (2L + M) and S n must be below 2^31)", who);
+  return 0;
+}
+
+template <typename T>
+static PwArgs<T> pathwise_args(const T* x, const T* omega, const T* z, const T* ell, long dl, const T* coef, double scale, T* out,
+                               long n, long L, long M, long d, long S) {
+  PwArgs<T> a;
+  a.x = x; a.omega = omega; a.z = z; a.ell = ell; a.dl = dl; a.coef = coef; a.scale = (T)scale; a.out = out;
+  a.n = (int)n; a.L = (int)L; a.M = (int)M; a.d = (int)d; a.S = (int)S;
+  return a;
 }
 
 #endif  // HB_SGP_PATHWISE_CUH

@@ -262,29 +262,6 @@ __global__ void __launch_bounds__(PW_THREADS) sgp_pathwise_argmax_fold_kernel(co
 }
 
 // ------------------------------------------------------------------------------------------------ host
-// the checks hb_sgp_pathwise makes, under the caller's name; the entry's own output pointers are checked by the caller
-template <typename T>
-static int pathwise_check(const char* who, int kind, const T* x, const T* omega, const T* z, const T* ell, long dl, const T* coef,
-                          bool outputs, long n, long nmin, long L, long M, long d, long S, long smax) {
-  HB_REQUIRE(kind == HB_KERN_RBF, "%s: the random-feature prior path is that of the UnitRBF kernel only (kind=%d)", who, kind);
-  HB_REQUIRE(n >= nmin && L >= 1 && M >= 0 && d >= 1 && S >= 1, "%s: bad extents (n=%ld L=%ld M=%ld d=%ld S=%ld)", who, n, L, M, d, S);
-  HB_REQUIRE(dl == 1 || dl == d, "%s: lengthscales must have 1 or d entries", who);
-  HB_REQUIRE(x && omega && ell && coef && outputs && (z || M == 0), "%s: NULL pointer", who);
-  HB_REQUIRE(n < 2147483647L && L < (1L << 29) && M < (1L << 29) && S * (2 * L + M) < 2147483647L && S * n < 2147483647L &&
-                 d < 2147483647L && hb_cdiv(S, smax) <= 65535,
-             "%s: too large (n, S (2L + M) and S n must be below 2^31)", who);
-  return 0;
-}
-
-template <typename T>
-static PwArgs<T> pathwise_args(const T* x, const T* omega, const T* z, const T* ell, long dl, const T* coef, double scale, T* out,
-                               long n, long L, long M, long d, long S) {
-  PwArgs<T> a;
-  a.x = x; a.omega = omega; a.z = z; a.ell = ell; a.dl = dl; a.coef = coef; a.scale = (T)scale; a.out = out;
-  a.n = (int)n; a.L = (int)L; a.M = (int)M; a.d = (int)d; a.S = (int)S;
-  return a;
-}
-
 template <typename T, int D>
 static void pathwise_grad_launch_d(const PwGradArgs<T>& a, int nst, dim3 grid, hipStream_t st) {
   if constexpr (sizeof(T) == 8 && (D == 0 || D >= 3)) {   // pwg_smax: one row tile

@@ -113,6 +113,28 @@ def adam_ascent(evaluate, x, f0, ell, box, sign, steps, lr, dt):
     return x_best, f_best
 
 
+def greedy_batch(argmax_fn, eval_fn, b0, q, sign):
+    """(picks, gains float64 [q'], b [S]): the greedy construction of a batch for the joint Monte-Carlo improvement
+    E max_i (sign (f(x_i) - b0))_+ of S function draws with per-draw incumbents b0 [S] (Wilson et al. 2020, section 5).
+    Up to q times: argmax_fn(b) -> (idx, gain, x), the best next point under the current incumbents b and its marginal
+    gain mean_s (sign (f_s(x) - b_s))_+; the loop ends early, before taking the point, when idx < 0 (nothing comparable)
+    or the gain is exactly 0 (no draw improves anywhere: every further gain would be 0 too), so q' <= q; otherwise
+    eval_fn(x) -> f [S], the draws at the point, and b <- max(b, f) (min for sign = -1).  picks: the (idx, x) pairs in
+    order.  The gains telescope: their sum is mean_s sign (b_s - b0_s), the joint improvement of the batch; with exact
+    arg-max values they never increase, since b only rises.  Callables only: runs without a device."""
+    b = np.array(b0, copy=True)
+    picks, gains = [], []
+    for _ in range(int(q)):
+        idx, gain, x = argmax_fn(b)
+        if idx < 0 or gain == 0:
+            break
+        f = np.asarray(eval_fn(x), dtype=b.dtype).reshape(b.shape)
+        b = np.maximum(b, f) if sign > 0 else np.minimum(b, f)
+        picks.append((int(idx), x))
+        gains.append(float(gain))
+    return picks, np.asarray(gains, np.float64), b
+
+
 def check_info(info, who, of, exc=G.CholeskyError):
     """ONE read-back of a factorisation's `info`; a leading minor of `of` that is not positive raises `exc`."""
     bad = int(info.cpu()[0])

@@ -525,7 +525,9 @@ class PathwiseDraws:
     the value at a point does not depend on the other points of the call, so the same draws can be evaluated in pieces,
     on a grid now and at candidates later, and maximised: evaluate_grad / grad give the exact input gradient in one launch
     (hb_sgp_pathwise_grad), argmax the best of any number of candidates without writing the [S, n] values
-    (hb_sgp_pathwise_argmax), maximise refines each draw's best candidate by gradient ascent (Thompson sampling)."""
+    (hb_sgp_pathwise_argmax), maximise refines each draw's best candidate by gradient ascent (Thompson sampling);
+    acquisition / acquisition_argmax reduce the draws to a Monte-Carlo EI / PI over per-draw incumbents inside the kernel
+    (hb_sgp_pathwise_acq) and select_batch builds a batch of q points from it."""
 
     def __init__(self, sess, omega, coef, z, ell, scale):
         self._sess = sess
@@ -603,6 +605,96 @@ class PathwiseDraws:
 
         x_best, f_best = _host.adam_ascent(evaluate, x, f0, ell, box, 1.0 if largest else -1.0, steps, float(lr), dt)
         return x_best, f_best, info
+
+    ACQ_KINDS = ("ei", "pi")
+
+    def _acq_inputs(self, who, X, kind, best):
+        """(candidates on the device, per-draw incumbents [S] as numpy of the session's dtype), checked."""
+        if kind not in self.ACQ_KINDS:
+            raise ValueError("%s: kind must be one of %s, got %r" % (who, self.ACQ_KINDS, kind))
+        Xd = self._points(X)
+        if Xd.shape[0] < 1:
+            raise ValueError("%s: at least one candidate expected" % who)
+        b = np.asarray(best, dtype=np.float64)
+        if b.ndim == 0:
+            if not np.isfinite(b):
+                raise ValueError("%s: a finite incumbent `best` expected, got %r" % (who, best))
+            b = np.full(self.num_samples, float(b))
+        elif b.shape != (self.num_samples,):
+            raise ValueError("%s: best must be a scalar or [%d] (one incumbent per draw), got %s" % (who, self.num_samples, b.shape))
+        return Xd, b.astype(self._sess.np_dtype)
+
+    def _acq(self, Xd, kind, b, largest, values):
+        return self._sess.H.sgp_pathwise_acq(Xd, self._omega, self._z, self._ell, self._coef, _host.upload(self._sess, b),
+                                             scale=self.scale, acq=kind, largest=bool(largest), values=values)
+
+    def acquisition(self, X, kind="ei", best=0.0, largest=True):
+        """The Monte-Carlo acquisition of the draws at the rows of X, as numpy [n]:
+        'ei'  mean_s max(sigma (f_s(x) - best_s), 0)      'pi'  mean_s 1[sigma (f_s(x) - best_s) > 0]
+        for maximising f (largest, sigma = +1) or minimising it (sigma = -1; the acquisition itself is to be MAXIMISED).
+        `best`: the incumbent value of f, a finite scalar, or [S] -- one incumbent per draw, which is what makes the joint
+        improvement of a BATCH cheap (select_batch).  The draws are reduced inside the evaluating kernel
+        (hb_sgp_pathwise_acq), summed in double: the [S, n] values are never written, and the value at a point does not
+        depend on the other points.  Another kind or shape of best, or an empty X, raise ValueError."""
+        Xd, b = self._acq_inputs("acquisition", X, kind, best)
+        return self._acq(Xd, kind, b, largest, True)[0].cpu().numpy()
+
+    def acquisition_argmax(self, X, kind="ei", best=0.0, largest=True):
+        """(idx, value): the row of X at which acquisition(X, ...) is largest (ties: the first row; a NaN is never chosen)
+        and its value there, bit for bit, without writing anything of size n.  No comparable value: (-1, -inf)."""
+        Xd, b = self._acq_inputs("acquisition_argmax", X, kind, best)
+        _, bv, bi = self._acq(Xd, kind, b, largest, False)
+        return int(bi.cpu().numpy()[0]), bv.cpu().numpy()[0]
+
+    def select_batch(self, X, q, best, kind="ei", largest=True, steps=0, lr=0.05, bounds=None):
+        """(x [q', d], gains [q'], info): a batch of up to q points to evaluate in parallel, built greedily for the joint
+        improvement  qEI(x_1 .. x_q) = E max_i (sigma (f(x_i) - best))_+  ~  mean_s max_i (sigma (f_s(x_i) - best_s))_+
+        of the draws (Wilson et al. 2020, section 5; kind 'pi': the probability that some point of the batch improves).
+        Each round is ONE acquisition_argmax launch over the rows of X under PER-DRAW incumbents b_s -- its value the
+        marginal gain of the point given the points before it -- and one evaluate at the chosen point x*, after which
+        b_s <- max(b_s, f_s(x*)) (min with largest=False) on the host.  The loop ends early once the gain is exactly 0,
+        so q' <= q.  steps > 0 ('ei' only): every chosen candidate is first refined by `steps` steps of the projected
+        Adam ascent of maximise (_host.adam_ascent; lr, bounds as there) on its marginal gain mean_s (sigma (f_s - b_s))_+
+        with the gradient mean_s 1[sigma (f_s - b_s) > 0] sigma grad f_s, both from ONE evaluate_grad launch at the
+        current point; the best point seen is kept, the candidate included.  gains: float64; with steps = 0 they are the
+        kernel's values and never increase.  info = dict(idx int64 [q'] the starting candidates, incumbents [S] the final
+        b, joint = sum of the gains = the joint acquisition of the batch, steps).  q < 1, an empty X, X of another width,
+        steps < 0, lr <= 0, malformed bounds or best, and steps > 0 with 'pi' (its gradient is zero almost everywhere)
+        raise ValueError."""
+        who = "select_batch"
+        sess = self._sess
+        Xd, b0 = self._acq_inputs(who, X, kind, best)
+        d, dt, steps = int(Xd.shape[1]), np.dtype(sess.np_dtype).type, int(steps)
+        if int(q) < 1:
+            raise ValueError("%s: q >= 1 expected (got %r)" % (who, q))
+        if steps < 0 or not float(lr) > 0.0:
+            raise ValueError("%s: steps >= 0 and lr > 0 expected (got %r, %r)" % (who, steps, lr))
+        if steps and kind != "ei":
+            raise ValueError("%s: steps > 0 needs kind 'ei' (the gradient of %r is zero almost everywhere)" % (who, kind))
+        box = _host.ascent_box(who, Xd, bounds, d, dt)
+        ell = np.broadcast_to(np.asarray(self._ell.cpu().numpy(), np.float64), (d,))
+        sign = 1.0 if largest else -1.0
+
+        def argmax_fn(b):
+            _, bv, bi = self._acq(Xd, kind, b, largest, False)
+            idx, gain = int(bi.cpu().numpy()[0]), float(bv.cpu().numpy()[0])
+            if idx < 0 or gain == 0 or not steps:
+                return idx, gain, (Xd[idx:idx + 1].cpu().numpy() if idx >= 0 else None)
+            b64 = b.astype(np.float64)[:, None]
+
+            def evaluate(xc):   # ONE launch at the single current point: the gain and its gradient
+                f, g = self.evaluate_grad(xc)
+                t = sign * (f.cpu().numpy().astype(np.float64) - b64)                        # [S, 1]
+                on = (t > 0.0)[:, :, None]
+                return np.maximum(t, 0.0).mean(0), (on * (sign * g.cpu().numpy().astype(np.float64))).mean(0)
+
+            x, a = _host.adam_ascent(evaluate, Xd[idx:idx + 1].cpu().numpy(), np.array([gain]), ell, box, 1.0, steps, float(lr), dt)
+            return idx, float(a[0]), x
+
+        picks, gains, b = _host.greedy_batch(argmax_fn, lambda x: self.evaluate(x).cpu().numpy()[:, 0], b0, int(q), sign)
+        xs = np.concatenate([x for _, x in picks], 0) if picks else np.zeros((0, d), dt)
+        info = dict(idx=np.asarray([i for i, _ in picks], np.int64), incumbents=b, joint=float(np.sum(gains)), steps=steps)
+        return xs, gains, info
 
     def _view(self, t):
         a = t.cpu().numpy()

@@ -40,6 +40,7 @@ ACT = {k[len("HB_ACT_"):].lower(): v for k, v in _C.items() if k.startswith("HB_
 SGP_NEGLECTED, SGP_DIAGONAL, SGP_FULLRANK = _hb("SGP_NEGLECTED", "SGP_DIAGONAL", "SGP_FULLRANK")
 SGP_S_DIAG, SGP_S_TRIL = _hb("SGP_S_DIAG", "SGP_S_TRIL")
 ACQ = {k[len("HB_ACQ_"):].lower(): v for k, v in _C.items() if k.startswith("HB_ACQ_")}   # 'ei', 'pi', 'ucb'
+PWACQ = {k[len("HB_PWACQ_"):].lower(): v for k, v in _C.items() if k.startswith("HB_PWACQ_")}   # 'ei', 'pi': over function draws
 PREC_NATIVE, PREC_BF16X3 = _hb("PREC_NATIVE", "PREC_BF16X3")
 LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON = _hb("LIK_GAUSSIAN", "LIK_BERNOULLI", "LIK_POISSON")
 MATUTIL_BAND, MATUTIL_ADD_EYE, MATUTIL_PHI, MATUTIL_SYM, MATUTIL_SYMLOW = _hb("MATUTIL_BAND", "MATUTIL_ADD_EYE", "MATUTIL_PHI",
@@ -1304,7 +1305,7 @@ def sgp_pathwise(x, omega, z, ell, coef, scale=1.0, out=None):
 
 
 def _pathwise_shapes(who, x, omega, z, ell, coef):
-    """(n, d, L, M, S) of the operands of a pathwise entry (sgp_pathwise, sgp_pathwise_grad, sgp_pathwise_argmax), checked:
+    """(n, d, L, M, S) of the operands of a pathwise entry (sgp_pathwise, _grad, _argmax, _acq), checked:
     on the device, contiguous, shapes that fit, one dtype."""
     for t in (x, omega, ell, coef) + (() if z is None else (z,)):
         _chk(t)
@@ -1372,6 +1373,56 @@ def sgp_pathwise_argmax(x, omega, z, ell, coef, scale=1.0, largest=True, ws=None
     _lib.lib().call("hb_sgp_pathwise_argmax" + _suf(x), KERN_RBF, _p(x), _p(omega), _p(z if M else None), _p(ell), ell.numel(),
                     _p(coef), float(scale), 1 if largest else 0, _p(best), _p(idx), n, L, M, d, S, _p(ws), stream())
     return best, idx
+
+
+def sgp_pathwise_acq_ws_elems(n, S):
+    """Scratch DOUBLES (whatever the operands' dtype) hb_sgp_pathwise_acq needs: 2 ceil(n / 128) for S <= 64, and
+    ceil(S / 64) n more beyond."""
+    return int(_lib.lib().raw("hb_sgp_pathwise_acq_ws_elems")(int(n), int(S)))
+
+
+def sgp_pathwise_acq(x, omega, z, ell, coef, incumbent, scale=1.0, acq="ei", largest=True, values=True, ws=None, out=None):
+    """The Monte-Carlo acquisition of S pathwise function draws over per-draw incumbents at the rows of x
+    (hb_sgp_pathwise_acq): (value [n] or None, best [1], idx int64 [1]) device tensors with, for F = sgp_pathwise(...),
+    value[j] = mean_s max(sigma (F[s, j] - incumbent[s]), 0) ('ei') or mean_s 1[sigma (F[s, j] - incumbent[s]) > 0] ('pi'),
+    sigma = +1 (largest) or -1, summed in double and rounded once; idx the first row with the largest value, best the
+    value there, bit for bit; F is never written.  values=False: value is not stored either (`out`, if given, is left untouched and
+    None is returned) -- for S <= 64 nothing of size n is written.  `out`: value written in place.  A NaN is never chosen; no comparable value: idx = -1 and best = -inf.  n >= 1.
+    incumbent [S] of the operands' dtype; other operands as for sgp_pathwise.  `ws`: sgp_pathwise_acq_ws_elems float64
+    elements (default: the shared float64 scratch of the stream)."""
+    who = "sgp_pathwise_acq"
+    n, d, L, M, S = _pathwise_shapes(who, x, omega, z, ell, coef)
+    if n < 1:
+        raise ValueError("%s: at least one candidate expected, got x %s" % (who, tuple(x.shape)))
+    code = PWACQ.get(acq, None) if isinstance(acq, str) else acq
+    if code not in PWACQ.values():
+        raise ValueError("%s: acq must be one of %s, got %r" % (who, sorted(PWACQ), acq))
+    if incumbent is None:
+        raise ValueError("%s: incumbent [S] expected, got None" % who)
+    _chk(incumbent, "incumbent")
+    if tuple(incumbent.shape) != (S,) or incumbent.dtype != x.dtype:
+        raise ValueError("%s: incumbent must be [%d] of the operands' dtype, got %s %s"
+                         % (who, S, tuple(incumbent.shape), incumbent.dtype))
+    value = None
+    if values:
+        if out is None:
+            value = _empty((n,), dtype=x.dtype, device=x.device)
+        else:
+            value = _chk(out, "out")
+            if tuple(out.shape) != (n,) or out.dtype != x.dtype:
+                raise ValueError("%s: out must be [%d] of the operands' dtype" % (who, n))
+    best = _empty((1,), dtype=x.dtype, device=x.device)
+    idx = _empty((1,), dtype=torch.int64, device=x.device)
+    need = sgp_pathwise_acq_ws_elems(n, S)
+    if ws is None:
+        ws = workspace(torch.float64, x.device, max(need, 1))
+    _chk(ws)
+    if ws.dtype != torch.float64 or ws.numel() < need:
+        raise ValueError("%s: the workspace must hold %d elements of float64 (sgp_pathwise_acq_ws_elems)" % (who, need))
+    _lib.lib().call("hb_sgp_pathwise_acq" + _suf(x), KERN_RBF, _p(x), _p(omega), _p(z if M else None), _p(ell), ell.numel(),
+                    _p(coef), float(scale), int(code), 1 if largest else 0, _p(incumbent), _p(value), _p(best), _p(idx), n, L, M, d,
+                    S, _p(ws), stream())
+    return value, best, idx
 
 
 def gram_matvec_chunk():

@@ -85,6 +85,16 @@ def _write_q(model, m, S):
         sess.write_raw(_part(q, "q_sqrt"), tri_pack(S) if q.packed else S)
 
 
+def _suggest_batch(model, mean, Xcand, q, kind, largest, num_samples, num_features, seed, steps, kw):
+    """The shared body of the models' suggest_batch: the incumbent from the posterior mean over the training inputs,
+    the draws from sample_functions, the batch from PathwiseDraws.select_batch."""
+    best = float(np.max(mean) if largest else np.min(mean))
+    draws = model.sample_functions(num_samples, num_features=num_features, seed=seed)
+    x, gains, info = draws.select_batch(Xcand, q, best, kind=kind, largest=largest, steps=steps, **kw)
+    info["best"], info["draws"] = best, draws
+    return x, gains, info
+
+
 class SVGP(hb.model.Model):
     """Sparse variational GP regression: cfg 1/2 (q_shape='diagonal') and cfg 3 ('fullrank')."""
 
@@ -173,6 +183,17 @@ class SVGP(hb.model.Model):
         info["best"] = best
         return x[0], a[0], info
 
+    def suggest_batch(self, Xcand, q, kind="ei", largest=True, num_samples=64, num_features=1024, seed=0, steps=0, **kw):
+        """(X_next [q', d], gains [q'], info): up to q points of Xcand [n, d] to evaluate IN PARALLEL -- the greedy batch
+        for the joint Monte-Carlo improvement ('ei'; 'pi': probability of improvement) of num_samples posterior function
+        draws (sample_functions(num_samples, num_features, seed); PathwiseDraws.select_batch; **kw: lr, bounds).  The
+        incumbent is suggest's: the largest (smallest with largest=False) posterior mean over the model's training
+        inputs.  gains[i] is the marginal gain of point i given the points before it and info['joint'] their sum, the
+        joint acquisition of the batch; info also holds 'best', the incumbent, and 'draws', the PathwiseDraws used.
+        steps > 0 refines every point by gradient ascent ('ei' only); q' < q when no draw improves any further."""
+        mean, _ = self.posterior().predict(_part(self, "X"))
+        return _suggest_batch(self, mean, Xcand, q, kind, largest, num_samples, num_features, seed, steps, kw)
+
     def _closed_form_inputs(self):
         """(X, Y, noise variance, k_var) of the whole data set at the current hyper-parameters."""
         self.initialize()
@@ -258,6 +279,7 @@ class SVGPLik(hb.model.Model):
     sample_functions = SVGP.sample_functions
     select_inducing = SVGP.select_inducing
     posterior = SVGP.posterior
+    suggest_batch = SVGP.suggest_batch
 
     def predict_y(self, Xnew):
         """Mean and variance [1, n] of a new observation y at Xnew [n, 1]: the likelihood's predictive under the
@@ -446,6 +468,13 @@ class ExactGPR(hb.model.Model):
         """num_samples exact posterior function draws as an hb.gp.PathwiseDraws (ExactPosterior.sample_functions); its
         grad, argmax and maximise work as for the sparse models."""
         return self._posterior().sample_functions(num_samples, num_features=num_features, seed=seed, noise=noise)
+
+    def suggest_batch(self, Xcand, q, kind="ei", largest=True, num_samples=64, num_features=1024, seed=0, steps=0, **kw):
+        """(X_next [q', d], gains [q'], info) as SVGP.suggest_batch: the exact GP's acquisition -- EI / PI and batches
+        from its function draws, with no predictive variance (a solve per 64 points) anywhere.  The incumbent is the
+        largest (smallest) posterior mean over the training inputs, predict_f(X, var=False)."""
+        mean, _ = self.predict_f(_part(self, "X"), var=False)
+        return _suggest_batch(self, mean, Xcand, q, kind, largest, num_samples, num_features, seed, steps, kw)
 
 
 def svgp_data(N, M, seed=0, domain=None, dtype=np.float64):

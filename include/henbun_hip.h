@@ -60,7 +60,8 @@ extern "C" {
  * hb_sgp_predict_grad_f32 / _f64, hb_sgp_predict_grad_ws_elems, hb_sgp_acq_f32 / _f64, hb_sgp_acq_ws_elems and the enum
  * values HB_ACQ_* (input gradients of the closed-form predictive and closed-form acquisition functions);
  * hb_sgp_predict_fused, hb_sgp_frag_elems, hb_cholesky_frag_elems, hb_matmul_wgk_shape and the enum values HB_MATUTIL_*
- * (rules and sizes a planner asks for instead of restating them). */
+ * (rules and sizes a planner asks for instead of restating them); hb_sgp_pathwise_acq_f32 / _f64,
+ * hb_sgp_pathwise_acq_ws_elems and the enum values HB_PWACQ_* (batch acquisition from pathwise function draws). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -741,6 +742,32 @@ int hb_sgp_pathwise_argmax_f32(int kind, const float* x, const float* omega, con
 int hb_sgp_pathwise_argmax_f64(int kind, const double* x, const double* omega, const double* z, const double* ell, long dl,
                                const double* coef, double scale, int largest, double* best, long* idx, long n, long L, long M,
                                long d, long S, double* ws, void* stream);
+/* Batch acquisition from pathwise function draws (csrc/sgp_pathwise_acq.hip; not in the reference; Wilson et al. 2020,
+ * section 5): the Monte-Carlo acquisition of S coherent function draws over PER-DRAW incumbents, reduced over the draws
+ * inside the pathwise kernel -- [S, n] is never written.  Arguments, limits and validation are those of
+ * hb_sgp_pathwise_argmax_* (n >= 1, kind must be HB_KERN_RBF).  With v_sj the number hb_sgp_pathwise stores for draw s and
+ * column j (those bits), sigma = +1 (largest != 0) or -1, t_sj = sigma ((double) v_sj - (double) incumbent[s]):
+ *   HB_PWACQ_EI   u_sj = max(t_sj, 0)         (expected improvement: greedy q-EI with incumbent[s] <- max(., f_s(x*)))
+ *   HB_PWACQ_PI   u_sj = t_sj > 0 ? 1 : 0     (probability of improvement)
+ *   value[j] = (T) ( (sum_s u_sj) / S ),
+ * the sum over all S draws in double in an order fixed by S alone (a lane's registers, the four lane groups of a wave, the
+ * row tiles, then the tiles of 64 draws in tile order); a NaN v_sj makes value[j] NaN.  idx [1] (long) = the first j with
+ * the largest value[j] among the comparable ones and best [1] = value[idx]: comparisons strict, ties to the lowest
+ * column, a NaN never chosen, no comparable value: idx = -1 and best = -inf.  incumbent [S] non-NULL; value [n] nullable;
+ * best and idx are given together or not at all; at least one of value / (best, idx) must be given.  acq must be one
+ * of the two ids.  value[j] depends neither on the other columns nor on n: two calls, or x in pieces, return the same
+ * bits.  No atomics.  One launch of the pathwise kernel with the reducing epilogue, for S > 64 a second that adds the
+ * tiles of draws, and one workgroup that folds the strips' arg-max pairs.  ws >= hb_sgp_pathwise_acq_ws_elems(n, S)
+ * DOUBLES (whatever the dtype), NULL rejected: 2 ceil(n / 128) for S <= 64 -- with value == NULL nothing of size n is
+ * written anywhere -- and ceil(S / 64) n more for S > 64.  Validated before any launch. */
+enum { HB_PWACQ_EI = 0, HB_PWACQ_PI = 1 };
+long hb_sgp_pathwise_acq_ws_elems(long n, long S);
+int hb_sgp_pathwise_acq_f32(int kind, const float* x, const float* omega, const float* z, const float* ell, long dl,
+                            const float* coef, double scale, int acq, int largest, const float* incumbent, float* value,
+                            float* best, long* idx, long n, long L, long M, long d, long S, double* ws, void* stream);
+int hb_sgp_pathwise_acq_f64(int kind, const double* x, const double* omega, const double* z, const double* ell, long dl,
+                            const double* coef, double scale, int acq, int largest, const double* incumbent, double* value,
+                            double* best, long* idx, long n, long L, long M, long d, long S, double* ws, void* stream);
 /* Input gradients of hb_sgp_predict's moments and closed-form acquisition functions (csrc/sgp_predict_grad.hip; not in
  * the reference).  One expert, one latent function (E = P = 1 of hb_sgp_predict_*), kind must be HB_KERN_RBF; x [n, d],
  * z [M, d], ell [dl], W, Wfrag, m [M], s ([M] standard deviations or [M, M] lower), s_kind, mode, jitter as there.  With
