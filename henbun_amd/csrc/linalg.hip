@@ -296,7 +296,6 @@ __global__ void __launch_bounds__(256) matmul_splitk_finish_kernel(MmArgs<T> a) 
       cp[0] = T(0.5) * (acc + acc2);
       continue;
     }
-    if ((a.flags & HB_MM_PHI_OUT) && c == r) acc *= T(0.5);
     if (a.flags & HB_MM_ACTGRAD) {
       cp[0] = acc * act_grad<T>(a.act, a.bias[b * a.sBias + r * a.N + c]);
       continue;
@@ -304,6 +303,8 @@ __global__ void __launch_bounds__(256) matmul_splitk_finish_kernel(MmArgs<T> a) 
     if (a.bias) acc += a.bias[b * a.sBias + c];
     acc = apply_act<T>(a.act, acc);
     if (a.beta != T(0)) acc += a.beta * cp[0];
+    // Phi halves the diagonal of the whole result, bias / activation / beta included, as the unsplit forms do
+    if ((a.flags & HB_MM_PHI_OUT) && c == r) acc *= T(0.5);
     cp[0] = acc;
   }
 }
@@ -1025,6 +1026,14 @@ bool matmul_rows_ok<float>(const MmArgs<float>& a, int transA, int transB) {
   if (transB && ((uintptr_t)a.B % 16 != 0 || a.ldb % 4 != 0)) return false;
   return a.M * a.lda < 2147483647L && a.M * a.ldc < 2147483647L;
 }
+// which of the two row forms a call that passed matmul_rows_ok takes (matmul_rows_launch asks the same function)
+template <typename T>
+static bool matmul_rows_reg(const MmArgs<T>&) { return false; }
+template <>
+bool matmul_rows_reg<float>(const MmArgs<float>& a) {
+  int G, KC;
+  return matmul_rowsreg_ok(a, G, KC);
+}
 template <typename T>
 static int matmul_rows_launch(const MmArgs<T>&, int, hipStream_t) { return -1; }
 template <>
@@ -1071,55 +1080,39 @@ int matmul_rows_launch<float>(const MmArgs<float>& a, int transB, hipStream_t st
   return 0;
 }
 
+// The dispatch rules of hb_matmul_* / hb_matmul_colsum_*, in one place: matmul_launch launches what this returns and
+// hb_matmul_form reports it.  `a` carries the extents, strides, flags, beta and the operand pointers (only their alignment
+// is looked at); ws_elems: what the split-K slabs may use (0: no workspace).
+struct MmForm {
+  int form;          // HB_MM_FORM_*
+  int bt;            // tile edge of the tile engine (64 / 128)
+  int S;             // contraction slabs of the tile engine (1: no split)
+  int to_ws;         // the result goes through the workspace (S > 1 or SYM_OUT): the in-workgroup form if it may, else a finish launch
+  int vec;           // the tile engine's 16-byte operand path
+  int bfast;         // batch index fastest in blockIdx.x
+  int colsum_fused;  // hb_matmul_colsum: the column sums ride in the product
+};
 template <typename T>
-static int matmul_launch(const T* A, const T* B, T* C, long batch, long M, long N, long K, long lda, long ldb,
-                         long ldc, long sA, long sB, long sC, int transA, int transB, double alpha, double beta,
-                         const T* bias, long sBias, int act, int flags, T* ws, long ws_elems, hipStream_t stream,
-                         T* colsum = nullptr) {
-  HB_REQUIRE(batch >= 0 && M >= 0 && N >= 0 && K >= 0, "hb_matmul: negative extent");
-  HB_REQUIRE(A && B && C, "hb_matmul: NULL pointer");
-  HB_REQUIRE(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N, "hb_matmul: leading dimension too small");
-  HB_REQUIRE(batch <= 65535, "hb_matmul: batch too large");
-  HB_REQUIRE((transA ? K : M) * lda < 2147483647L && (transB ? N : K) * ldb < 2147483647L,
-             "hb_matmul: operand too large for 32-bit indexing");
-  HB_REQUIRE(act >= HB_ACT_NONE && act <= HB_ACT_TANH, "hb_matmul: unknown activation %d", act);
-  if (batch * M * N == 0) return 0;
-  MmArgs<T> a;
-  a.A = A; a.B = B; a.C = C;
-  a.M = M; a.N = N; a.K = K;
-  a.lda = lda; a.ldb = ldb; a.ldc = ldc;
-  a.sA = sA; a.sB = sB; a.sC = sC;
-  a.batch = batch;
-  a.alpha = (T)alpha; a.beta = (T)beta;
-  a.bias = bias; a.sBias = sBias;
-  a.act = act; a.flags = flags;
-  a.ws = ws;
-  a.colsum = nullptr;
-  a.colsum_ws = nullptr;
-  if (colsum) {
-    // the slab partials of the column sums sit at the end of the workspace (128 slabs at most)
-    HB_REQUIRE(ws && ws_elems > 128 * N, "hb_matmul_colsum: workspace too small");
-    ws_elems -= 128 * N;
-    a.colsum_ws = ws + ws_elems;
+static MmForm matmul_decide(const MmArgs<T>& a, int transA, int transB, long ws_elems, bool colsum) {
+  const long M = a.M, N = a.N, K = a.K, batch = a.batch, lda = a.lda, ldb = a.ldb, sA = a.sA, sB = a.sB;
+  const int flags = a.flags;
+  const bool ws = ws_elems > 0;
+  MmForm f = {};
+  f.form = HB_MM_FORM_TILE64, f.bt = 64, f.S = 1;
+  if (!colsum && matmul_rows_ok<T>(a, transA, transB)) {
+    f.form = matmul_rows_reg<T>(a) ? HB_MM_FORM_ROWSREG : HB_MM_FORM_ROWS;
+    return f;
   }
-  // Tile / split choice.  These are latency-and-occupancy problems more often than throughput ones: a
-  // 128x128 tile (64x64 per wave: 4 MFMAs per fragment pair) has the lowest staging cost per MFMA but
-  // only pays when there are enough of them to cover the 256 CUs; otherwise 64x64 tiles, and the
-  // contraction is split until ~2.5 workgroups per CU are in flight (each slice >= 64 deep).
-  HB_REQUIRE(!(flags & HB_MM_SYM_OUT) || (M == N && ws && ws_elems >= batch * M * N && !bias && act == HB_ACT_NONE &&
-                                          beta == 0.0 && !(flags & ~HB_MM_SYM_OUT)),
-             "hb_matmul: SYM_OUT needs a square result, a workspace, and no other epilogue");
-  HB_REQUIRE(!(flags & HB_MM_ACTGRAD) || (bias && beta == 0.0 && flags == HB_MM_ACTGRAD),
-             "hb_matmul: ACTGRAD needs Y in `bias`, beta = 0 and no other flag");
-  HB_REQUIRE(!(flags & HB_MM_SYMLOW_OUT) || (M == N && !bias && act == HB_ACT_NONE && beta == 0.0 && flags == HB_MM_SYMLOW_OUT),
-             "hb_matmul: SYMLOW_OUT needs a square result and no other epilogue");
-  if (!colsum && matmul_rows_ok<T>(a, transA, transB)) return matmul_rows_launch<T>(a, transB, stream);   // tall A, small op(B)
   // (A^T B over a minibatch into a small result -- the weight gradients of cfg 4 -- stays on the tile engine below.  A
   //  form with both operands read straight from global memory as MFMA fragments (64 x 64 block and one slab of rows per
   //  workgroup, four waves taking the slab's 32-row chunks in turn) was built twice: with `in range ? v : 0` on every
   //  loaded element the compiler issued a chunk's 96 loads two at a time with a full wait behind each pair (54 / 47 / 16 us
   //  per product); with a select-free common path 19.5 / 13.9 / 17.3 us -- against 15.2 each for the tile engine.  Removed;
   //  what it left behind is the split-K finish with sixteen slab loads in flight (7.5 -> 5.0 us).)
+  // Tile / split choice.  These are latency-and-occupancy problems more often than throughput ones: a
+  // 128x128 tile (64x64 per wave: 4 MFMAs per fragment pair) has the lowest staging cost per MFMA but
+  // only pays when there are enough of them to cover the 256 CUs; otherwise 64x64 tiles, and the
+  // contraction is split until ~2.5 workgroups per CU are in flight (each slice >= 64 deep).
   const bool lower = (flags & (HB_MM_LOWER_OUT | HB_MM_TRIL_OUT | HB_MM_PHI_OUT | HB_MM_SYMLOW_OUT)) != 0;
   auto active_tiles = [&](int bt) -> long {
     const long tr = hb_cdiv(M, bt), tc = hb_cdiv(N, bt);
@@ -1134,7 +1127,6 @@ static int matmul_launch(const T* A, const T* B, T* C, long batch, long M, long 
       BT = 128;  // enough big tiles to cover the chip
     }
   }
-  a.tile = BT;
   const long tiles = (long)hb_cdiv(M, BT) * hb_cdiv(N, BT);
   const long active = active_tiles(BT);
   if (BT == 64 && ws && (active * batch < 320 || K >= 32768) && K >= 128) {
@@ -1159,7 +1151,6 @@ static int matmul_launch(const T* A, const T* B, T* C, long batch, long M, long 
     const long fbt = hb_debug_get("mm_force_bt", 0), fs = hb_debug_get("mm_force_s", 0);
     if (fbt) {
       BT = fbt == 128 ? 128 : 64;
-      a.tile = BT;
     }
     if (fs && ws) {
       long s = fs;
@@ -1170,34 +1161,111 @@ static int matmul_launch(const T* A, const T* B, T* C, long batch, long M, long 
     }
   }
   if (S > 8) S -= S % 8;  // slab <-> XCD affinity (see matmul_kernel)
-  a.S = S;
-  a.to_ws = (S > 1 || (flags & HB_MM_SYM_OUT)) ? 1 : 0;
+  f.bt = BT, f.S = S;
+  f.to_ws = (S > 1 || (flags & HB_MM_SYM_OUT)) ? 1 : 0;
+  if (BT == 128) f.form = HB_MM_FORM_TILE128;
   {
     // results that would go through slabs + a finish launch: one 32x32 tile per workgroup with the contraction
     // split over its four waves instead (matmul_wgk_kernel)
     constexpr long VEC0 = 16 / sizeof(T);
-    const bool aligned0 = ((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && lda % VEC0 == 0 && ldb % VEC0 == 0 &&
+    const bool aligned0 = ((uintptr_t)a.A % 16 == 0) && ((uintptr_t)a.B % 16 == 0) && lda % VEC0 == 0 && ldb % VEC0 == 0 &&
                           sA % VEC0 == 0 && sB % VEC0 == 0;
-    if (!colsum && a.to_ws && matmul_wgk_ok<T>(a, M, N, K, batch, flags, aligned0))
-      return matmul_wgk_launch<T>(a, transA, transB, stream);
+    if (!colsum && f.to_ws && matmul_wgk_ok<T>(a, M, N, K, batch, flags, aligned0)) {
+      f.form = HB_MM_FORM_WGK;
+      return f;
+    }
   }
-  const long tiles_final = (long)hb_cdiv(M, BT) * hb_cdiv(N, BT);
-  HB_REQUIRE(tiles_final * S * batch < 2147483647L, "hb_matmul: grid too large");
-  a.bfast = (batch > 1 && batch % 8 == 0) ? 1 : 0;
-  dim3 grid = a.bfast ? dim3((unsigned)(tiles_final * S * batch), 1, 1) : dim3((unsigned)(tiles_final * S), (unsigned)batch, 1);
+  f.bfast = (batch > 1 && batch % 8 == 0) ? 1 : 0;
   constexpr long VEC = 16 / sizeof(T);
-  const bool aligned = ((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && lda % VEC == 0 && ldb % VEC == 0 &&
+  const bool aligned = ((uintptr_t)a.A % 16 == 0) && ((uintptr_t)a.B % 16 == 0) && lda % VEC == 0 && ldb % VEC == 0 &&
                        sA % VEC == 0 && sB % VEC == 0;
   const bool fast = aligned && K % 16 == 0 && K > 0 && (!transA || M % VEC == 0) && (transB || N % VEC == 0);
   // column sums inside the GEMM: the vector path of the A^T B form, 64-tiles, every slab a whole number of k-steps
-  bool colsum_fused = false;
   if (colsum) {
     const long kchunk = (((K + S - 1) / S + 15) / 16) * 16;
-    colsum_fused = fast && transA && !transB && batch == 1 && BT == 64 && K % 16 == 0 && (K % kchunk) % 16 == 0;
-    if (colsum_fused) {
-      a.flags |= HB_MM_COLSUM_B;
-      a.colsum = colsum;
-    }
+    f.colsum_fused = fast && transA && !transB && batch == 1 && BT == 64 && K % 16 == 0 && (K % kchunk) % 16 == 0;
+  }
+  f.vec = fast ? 1 : 0;
+  return f;
+}
+
+// What hb_matmul_* rejects that can be told without the pointers, in one place for matmul_launch and hb_matmul_form:
+// the message of the first failed requirement, or nullptr.  (What needs `bias`, `act` or the pointers themselves stays
+// with the launcher.)  matmul_reject_extents comes before the empty-product return, matmul_reject_flags after it, with
+// ws_elems = what the slabs may use (0: no workspace).
+static const char* matmul_reject_extents(long batch, long M, long N, long K, long lda, long ldb, long ldc, int transA,
+                                         int transB) {
+  if (!(batch >= 0 && M >= 0 && N >= 0 && K >= 0)) return "hb_matmul: negative extent";
+  if (!(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N)) return "hb_matmul: leading dimension too small";
+  if (!(batch <= 65535)) return "hb_matmul: batch too large";
+  if (!((transA ? K : M) * lda < 2147483647L && (transB ? N : K) * ldb < 2147483647L))
+    return "hb_matmul: operand too large for 32-bit indexing";
+  return nullptr;
+}
+static const char* matmul_reject_flags(long batch, long M, long N, double beta, int flags, long ws_elems) {
+  if ((flags & HB_MM_SYM_OUT) && !(M == N && ws_elems >= batch * M * N && beta == 0.0 && !(flags & ~HB_MM_SYM_OUT)))
+    return "hb_matmul: SYM_OUT needs a square result, a workspace, and no other epilogue";
+  if ((flags & HB_MM_ACTGRAD) && !(beta == 0.0 && flags == HB_MM_ACTGRAD))
+    return "hb_matmul: ACTGRAD needs Y in `bias`, beta = 0 and no other flag";
+  if ((flags & HB_MM_SYMLOW_OUT) && !(M == N && beta == 0.0 && flags == HB_MM_SYMLOW_OUT))
+    return "hb_matmul: SYMLOW_OUT needs a square result and no other epilogue";
+  return nullptr;
+}
+static bool matmul_grid_ok(const MmForm& f, long batch, long M, long N) {
+  return (long)hb_cdiv(M, f.bt) * hb_cdiv(N, f.bt) * f.S * batch < 2147483647L;
+}
+
+template <typename T>
+static int matmul_launch(const T* A, const T* B, T* C, long batch, long M, long N, long K, long lda, long ldb,
+                         long ldc, long sA, long sB, long sC, int transA, int transB, double alpha, double beta,
+                         const T* bias, long sBias, int act, int flags, T* ws, long ws_elems, hipStream_t stream,
+                         T* colsum = nullptr) {
+  HB_REQUIRE(A && B && C, "hb_matmul: NULL pointer");
+  const char* why = matmul_reject_extents(batch, M, N, K, lda, ldb, ldc, transA, transB);
+  HB_REQUIRE(!why, "%s", why);
+  HB_REQUIRE(act >= HB_ACT_NONE && act <= HB_ACT_TANH, "hb_matmul: unknown activation %d", act);
+  if (batch * M * N == 0) return 0;
+  MmArgs<T> a;
+  a.A = A; a.B = B; a.C = C;
+  a.M = M; a.N = N; a.K = K;
+  a.lda = lda; a.ldb = ldb; a.ldc = ldc;
+  a.sA = sA; a.sB = sB; a.sC = sC;
+  a.batch = batch;
+  a.alpha = (T)alpha; a.beta = (T)beta;
+  a.bias = bias; a.sBias = sBias;
+  a.act = act; a.flags = flags;
+  a.ws = ws;
+  a.colsum = nullptr;
+  a.colsum_ws = nullptr;
+  if (colsum) {
+    // the slab partials of the column sums sit at the end of the workspace (128 slabs at most)
+    HB_REQUIRE(ws && ws_elems > 128 * N, "hb_matmul_colsum: workspace too small");
+    ws_elems -= 128 * N;
+    a.colsum_ws = ws + ws_elems;
+  }
+  // the pointer-free part of each requirement is matmul_reject_flags, shared with hb_matmul_form
+  why = matmul_reject_flags(batch, M, N, beta, flags, ws ? ws_elems : 0);
+  HB_REQUIRE(!why, "%s", why);
+  HB_REQUIRE(!(flags & HB_MM_SYM_OUT) || (!bias && act == HB_ACT_NONE),
+             "hb_matmul: SYM_OUT needs a square result, a workspace, and no other epilogue");
+  HB_REQUIRE(!(flags & HB_MM_ACTGRAD) || bias, "hb_matmul: ACTGRAD needs Y in `bias`, beta = 0 and no other flag");
+  HB_REQUIRE(!(flags & HB_MM_SYMLOW_OUT) || (!bias && act == HB_ACT_NONE),
+             "hb_matmul: SYMLOW_OUT needs a square result and no other epilogue");
+  const MmForm f = matmul_decide<T>(a, transA, transB, ws ? ws_elems : 0, colsum != nullptr);
+  if (f.form == HB_MM_FORM_ROWS || f.form == HB_MM_FORM_ROWSREG) return matmul_rows_launch<T>(a, transB, stream);   // tall A, small op(B)
+  const int BT = f.bt, S = f.S;
+  a.tile = BT;
+  a.S = S;
+  a.to_ws = f.to_ws;
+  if (f.form == HB_MM_FORM_WGK) return matmul_wgk_launch<T>(a, transA, transB, stream);
+  const long tiles_final = (long)hb_cdiv(M, BT) * hb_cdiv(N, BT);
+  HB_REQUIRE(matmul_grid_ok(f, batch, M, N), "hb_matmul: grid too large");
+  a.bfast = f.bfast;
+  dim3 grid = a.bfast ? dim3((unsigned)(tiles_final * S * batch), 1, 1) : dim3((unsigned)(tiles_final * S), (unsigned)batch, 1);
+  const bool fast = f.vec != 0, colsum_fused = f.colsum_fused != 0;
+  if (colsum_fused) {
+    a.flags |= HB_MM_COLSUM_B;
+    a.colsum = colsum;
   }
 #define HB_MM_LAUNCH2(TA_, TB_, F_)                                                                 \
   do {                                                                                              \
@@ -1258,6 +1326,47 @@ extern "C" int hb_matmul_f32(const float* A, const float* B, float* C, long batc
   return matmul_launch<float>(A, B, C, batch, M, N, K, lda, ldb, ldc, sA, sB, sC, transA, transB, alpha, beta, bias,
                               sBias, act, flags, ws, ws_elems, (hipStream_t)stream);
 }
+// What matmul_launch would launch for this call, asked on the host (nothing is launched): matmul_decide over the same
+// arguments, the operand pointers replaced by stand-ins of the stated alignment.
+template <typename T>
+static int matmul_form_query(long batch, long M, long N, long K, long lda, long ldb, long ldc, long sA, long sB, int transA,
+                             int transB, double beta, int flags, int a_aligned, int b_aligned, long ws_elems, int colsum,
+                             int* S, int* vec, int* finish, int* bfast, int* colsum_fused) {
+  MmArgs<T> a = {};
+  a.A = (const T*)(uintptr_t)(a_aligned ? 256 : 256 + sizeof(T));
+  a.B = (const T*)(uintptr_t)(b_aligned ? 256 : 256 + sizeof(T));
+  a.M = M, a.N = N, a.K = K, a.lda = lda, a.ldb = ldb, a.ldc = ldc, a.sA = sA, a.sB = sB, a.batch = batch;
+  a.beta = (T)beta, a.flags = flags;
+  if (colsum) ws_elems -= 128 * N;   // the slab partials of the column sums (matmul_launch)
+  if (ws_elems < 0) ws_elems = 0;
+  if (matmul_reject_flags(batch, M, N, beta, flags, ws_elems)) return -1;
+  const MmForm f = matmul_decide<T>(a, transA, transB, ws_elems, colsum != 0);
+  const bool tile = f.form == HB_MM_FORM_TILE64 || f.form == HB_MM_FORM_TILE128;
+  if (tile && !matmul_grid_ok(f, batch, M, N)) return -1;
+  if (S) *S = tile ? f.S : 1;
+  if (vec) *vec = tile ? f.vec : 0;
+  if (finish) *finish = tile ? f.to_ws : 0;
+  if (bfast) *bfast = tile ? f.bfast : 0;
+  if (colsum_fused) *colsum_fused = tile ? f.colsum_fused : 0;
+  return f.form;
+}
+extern "C" int hb_matmul_form(int elem_bytes, long batch, long M, long N, long K, long lda, long ldb, long ldc, long sA, long sB,
+                              int transA, int transB, double beta, int flags, int a_aligned, int b_aligned, long ws_elems,
+                              int colsum, int* S, int* vec, int* finish, int* bfast, int* colsum_fused) {
+  // nothing hb_matmul_* would launch: an empty product, or extents, strides and flags it rejects (the launcher's own
+  // requirements: matmul_reject_extents here, matmul_reject_flags and the grid limit in matmul_form_query)
+  if ((elem_bytes != 4 && elem_bytes != 8) || batch < 1 || M < 1 || N < 1 ||
+      matmul_reject_extents(batch, M, N, K, lda, ldb, ldc, transA, transB) || (colsum && ws_elems <= 128 * N))
+    return -1;
+  // hb_matmul_colsum_* is one A^T B product over contiguous B with no epilogue
+  if (colsum && (batch != 1 || !transA || transB || ldb != N || flags != 0 || beta != 0.0)) return -1;
+  if (elem_bytes == 4)
+    return matmul_form_query<float>(batch, M, N, K, lda, ldb, ldc, sA, sB, transA, transB, beta, flags, a_aligned, b_aligned,
+                                    ws_elems, colsum, S, vec, finish, bfast, colsum_fused);
+  return matmul_form_query<double>(batch, M, N, K, lda, ldb, ldc, sA, sB, transA, transB, beta, flags, a_aligned, b_aligned,
+                                   ws_elems, colsum, S, vec, finish, bfast, colsum_fused);
+}
+
 // The square product whose result is Kbar of a Gram matrix K(X, X), with that Gram matrix's VJP in its epilogue (MmGramVjp).
 extern "C" int hb_matmul_gram_vjp_ok(long M, long K, long batch, long d) {
   MmArgs<float> t = {};

@@ -12,6 +12,7 @@ entry point from its prototype and rejects a call with the wrong argument count.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 from ctypes import c_double, c_int, c_long, c_void_p
 
@@ -36,6 +37,7 @@ EW_PROG_SUM = _C["HB_EW_PROG_SUM"]
 COLPROG_SUM, COLPROG_MAX = _hb("COLPROG_SUM", "COLPROG_MAX")   # row reductions of a column program
 MM_LOWER_OUT, MM_TRIL_OUT, MM_PHI_OUT, MM_SYM_OUT = _hb("MM_LOWER_OUT", "MM_TRIL_OUT", "MM_PHI_OUT", "MM_SYM_OUT")
 MM_SYMLOW_OUT, MM_ACTGRAD = _hb("MM_SYMLOW_OUT", "MM_ACTGRAD")
+MM_FORM = {k[len("HB_MM_FORM_"):].lower(): v for k, v in _C.items() if k.startswith("HB_MM_FORM_")}   # hb_matmul_form
 ACT = {k[len("HB_ACT_"):].lower(): v for k, v in _C.items() if k.startswith("HB_ACT_")}
 SGP_NEGLECTED, SGP_DIAGONAL, SGP_FULLRANK = _hb("SGP_NEGLECTED", "SGP_DIAGONAL", "SGP_FULLRANK")
 SGP_S_DIAG, SGP_S_TRIL = _hb("SGP_S_DIAG", "SGP_S_TRIL")
@@ -959,6 +961,29 @@ def matmul_wgk_shape(M, N, K, batch):
     """The shape [batch, M, K] x [batch, K, N] lies inside hb_matmul_f32's in-workgroup split-K form (hb_matmul_wgk_shape:
     the shape part of the rule only -- alignment, flags and the mm_no_wgk switch are the call's own business)."""
     return bool(_lib.lib().raw("hb_matmul_wgk_shape")(int(M), int(N), int(K), int(batch)))
+
+
+MatmulForm = collections.namedtuple("MatmulForm", "form S vec finish bfast colsum_fused")
+
+
+def matmul_form(dtype, batch, M, N, K, lda=None, ldb=None, ldc=None, sA=None, sB=None, transA=False, transB=False, beta=0.0,
+                flags=0, a_aligned=True, b_aligned=True, ws_elems=1 << 22, colsum=False):
+    """What hb_matmul_* (colsum: hb_matmul_colsum_*) launches for this call, asked on the host (hb_matmul_form: the
+    launcher's own decision function; nothing runs): MatmulForm(form in MM_FORM, S slabs, vector operand path, finish
+    launch, batch-fastest grid, fused column sums).  Strides default to contiguous operands; ws_elems to matmul()'s."""
+    lda = (M if transA else K) if lda is None else lda
+    ldb = (K if transB else N) if ldb is None else ldb
+    ldc = N if ldc is None else ldc
+    sA = (M * K if batch > 1 else 0) if sA is None else sA
+    sB = (K * N if batch > 1 else 0) if sB is None else sB
+    o = [ctypes.c_int(0) for _ in range(5)]
+    form = _lib.lib().raw("hb_matmul_form")(_elem_bytes(dtype), int(batch), int(M), int(N), int(K), int(lda), int(ldb), int(ldc),
+                                            int(sA), int(sB), int(bool(transA)), int(bool(transB)), float(beta), int(flags),
+                                            int(bool(a_aligned)), int(bool(b_aligned)), int(ws_elems), int(bool(colsum)),
+                                            *[ctypes.byref(v) for v in o])
+    if form < 0:
+        raise ValueError("matmul_form: an empty product, or arguments hb_matmul rejects")
+    return MatmulForm(int(form), o[0].value, bool(o[1].value), bool(o[2].value), bool(o[3].value), bool(o[4].value))
 
 
 def matmul_gram_vjp(a, b, out, transA, transB, X, sX, ell, sEll, dl, d, xbar, ell_partial, part, counters):

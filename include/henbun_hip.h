@@ -61,7 +61,9 @@ extern "C" {
  * values HB_ACQ_* (input gradients of the closed-form predictive and closed-form acquisition functions);
  * hb_sgp_predict_fused, hb_sgp_frag_elems, hb_cholesky_frag_elems, hb_matmul_wgk_shape and the enum values HB_MATUTIL_*
  * (rules and sizes a planner asks for instead of restating them); hb_sgp_pathwise_acq_f32 / _f64,
- * hb_sgp_pathwise_acq_ws_elems and the enum values HB_PWACQ_* (batch acquisition from pathwise function draws). */
+ * hb_sgp_pathwise_acq_ws_elems and the enum values HB_PWACQ_* (batch acquisition from pathwise function draws);
+ * hb_matmul_form and the enum values HB_MM_FORM_* (which kernel form, slab count and operand path hb_matmul_* takes for
+ * a call: a host-side query that launches nothing). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -408,6 +410,29 @@ int hb_matmul_colsum_f32(const float* A, const float* B, float* C, float* colsum
                          long ldc, float* ws, long ws_elems, void* stream);
 int hb_matmul_colsum_f64(const double* A, const double* B, double* C, double* colsum, long M, long N, long K, long lda,
                          long ldb, long ldc, double* ws, long ws_elems, void* stream);
+
+/* Which form hb_matmul_f32 / _f64 (colsum != 0: hb_matmul_colsum_*) takes for a call, asked on the host: the launcher
+ * and this query share one decision function, and nothing is launched.  elem_bytes: 4 / 8; the extents, strides, transposes,
+ * beta and flags as the call passes them; a_aligned / b_aligned: the A / B base pointer is 16-byte aligned; ws_elems: as
+ * passed (0: no workspace).  Returns HB_MM_FORM_*, or -1 for an empty product and for whatever the call rejects that
+ * these arguments show: a leading dimension too small, batch > 65535, an operand past 32-bit indexing, a grid too
+ * large, SYM_OUT / SYMLOW_OUT / ACTGRAD with M != N, beta != 0, another flag or (SYM_OUT) too small a workspace, and
+ * with colsum != 0 anything but one A^T B product over contiguous B (the launcher tests through the same functions).
+ * What the call rejects by `bias`, `act` or a NULL pointer the query does not see.  Where the pointers are not NULL,
+ * for the two tile-engine forms: *S = contraction slabs (1: no split), *vec = the 16-byte operand
+ * path, *finish = a finish launch follows (S > 1 or SYM_OUT), *bfast = the batch index is fastest in the grid
+ * (batch % 8 == 0), *colsum_fused = the column sums ride in the product (0: a reduction launch of their own).  For the
+ * other forms S = 1 and the rest are 0.  The mm_* switches of hb_debug_set are honoured. */
+enum {
+  HB_MM_FORM_TILE64 = 0,  /* matmul_kernel, 64 x 64 tiles */
+  HB_MM_FORM_TILE128 = 1, /* matmul_kernel, 128 x 128 tiles */
+  HB_MM_FORM_WGK = 2,     /* matmul_wgk_kernel: split-K inside the workgroup (fp32) */
+  HB_MM_FORM_ROWS = 3,    /* matmul_rows_kernel: tall A, weights resident in LDS (fp32) */
+  HB_MM_FORM_ROWSREG = 4  /* matmul_rowsreg_kernel: tall A, weights in registers (fp32) */
+};
+int hb_matmul_form(int elem_bytes, long batch, long M, long N, long K, long lda, long ldb, long ldc, long sA, long sB,
+                   int transA, int transB, double beta, int flags, int a_aligned, int b_aligned, long ws_elems, int colsum,
+                   int* S, int* vec, int* finish, int* bfast, int* colsum_fused);
 
 /* ---- K7 fused: the amortised encoder in one launch per direction (csrc/mlp.hip; round 4).
  * o = act(y w0 + b0) w1 + b1   [n, 32] = [q_mu (16) | q_sqrt = log-std (16)]   (NeuralNet of two MatBias layers,

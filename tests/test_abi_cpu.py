@@ -73,7 +73,8 @@ def _assertions(sigs, consts):
 
 def test_compiler_agrees_with_every_parsed_signature_and_constant(tmp_path):
     sigs, consts = _signatures(), _lib.constants()
-    assert len(sigs) >= 178 and len(consts) >= 75
+    assert len(sigs) >= 192 and len(consts) >= 90   # with hb_matmul_form and HB_MM_FORM_* (profiles/abi_binding.txt, 5)
+    assert "hb_matmul_form" in sigs and consts["HB_MM_FORM_ROWSREG"] == 4
     r = _syntax_check(_SIG_CHECK + _assertions(sigs, consts), tmp_path)
     assert r.returncode == 0, r.stderr[-4000:]
     # the same oracle for the forms the real header does not use today (an enum whose first value is implicit, ...)
