@@ -1,5 +1,7 @@
-// Matrix-free kernel product (hb_gram_matvec_*) and the vector kernels of the lockstep preconditioned conjugate gradients
-// built on it (hb_pcg_*), include/henbun_hip.h; not in the reference; Gardner et al. 2018, Wang et al. 2019.
+// Matrix-free kernel product (hb_gram_matvec_*), the exact GP's predictive pass built on the same kernel (hb_gram_predict_*:
+// mean, cached variance bound, closed-form acquisition and its arg-max; further down) and the vector kernels of the
+// lockstep preconditioned conjugate gradients (hb_pcg_*), include/henbun_hip.h; not in the reference; Gardner et al. 2018,
+// Wang et al. 2019.
 //
 //     out[s, j] = scale * sum_{i < N} V[s, i] k(x2_i, x_j) + shift * V[s, j]
 //
@@ -23,6 +25,8 @@
 #include "common.cuh"
 #include "mfma16.cuh"
 #include "sgp_strip.cuh"
+#include "sgp_pathwise.cuh"   // pw_takes: the arg-max rule
+#include "acq_tail.cuh"
 #include "../../include/henbun_hip.h"
 
 #define GMV_THREADS 256   // 4 waves, 32 columns each
@@ -48,6 +52,7 @@ struct GmvArgs {
   double* acc;    // [S, n] when nchunk > GMV_GROUP: the fold's running sum between groups
   int n, N, d, S, nstrip, nchunk;
   int c0, gchunks;   // the group in flight: chunks c0 .. c0 + gchunks - 1
+  int to_ws;         // hb_gram_predict: a single chunk leaves its partial in the workspace too (out is not written)
 };
 
 // scale * sum + shift * v, written so that the epilogue and the fold round alike
@@ -165,7 +170,7 @@ __global__ void __launch_bounds__(GMV_THREADS) gram_matvec_kernel(GmvArgs<T> a) 
         const int s = s0 + 16 * st + MM::row(lane, r);
         const long j = col0 + 16 * ct + l16;
         if (s < S && j < n) {
-          if (a.nchunk == 1) {
+          if (a.nchunk == 1 && !a.to_ws) {
             const double v = a.shift_on ? (double)a.V[(long)s * N + j] : 0.0;
             a.out[(long)s * n + j] = gmv_finish<T>(a.scale, a.shift, (double)acc[st][ct][r], v);
           } else {
@@ -205,6 +210,24 @@ static void gram_matvec_launch_d(const GmvArgs<T>& a, int nst, dim3 grid, hipStr
     hipLaunchKernelGGL((gram_matvec_kernel<T, D, 4>), grid, dim3(GMV_THREADS), 0, st, a);
 }
 
+// phase 1 of one group of chunks: shared by hb_gram_matvec and hb_gram_predict
+template <typename T>
+static void gram_matvec_launch(const GmvArgs<T>& a, hipStream_t st) {
+  // every workgroup of the grid carries the same number of row tiles: those of min(S, GMV_SMAX) right-hand sides
+  const int nst = hb_cdiv(a.S < GMV_SMAX ? a.S : GMV_SMAX, 16);
+  const dim3 grid((unsigned)((long)a.nstrip * a.gchunks), (unsigned)hb_cdiv(a.S, GMV_SMAX), 1);
+  if (a.d == 1)
+    gram_matvec_launch_d<T, 1>(a, nst, grid, st);
+  else if (a.d == 2)
+    gram_matvec_launch_d<T, 2>(a, nst, grid, st);
+  else if (a.d == 3)
+    gram_matvec_launch_d<T, 3>(a, nst, grid, st);
+  else if (a.d == 4)
+    gram_matvec_launch_d<T, 4>(a, nst, grid, st);
+  else
+    gram_matvec_launch_d<T, 0>(a, nst, grid, st);
+}
+
 extern "C" long hb_gram_matvec_chunk(void) { return GMV_CHUNK; }
 
 extern "C" long hb_gram_matvec_ws_elems(long n, long N, long S, int dtype_bytes) {
@@ -235,25 +258,13 @@ static int gram_matvec(int kind, const T* x, const T* x2, const T* ell, long dl,
   }
   GmvArgs<T> a;
   a.x = x; a.x2 = x2 ? x2 : x; a.ell = ell; a.dl = dl; a.V = V; a.scale = scale; a.shift = shift;
-  a.shift_on = x2 ? 0 : 1; a.out = out; a.ws = ws;
+  a.shift_on = x2 ? 0 : 1; a.out = out; a.ws = ws; a.to_ws = 0;
   a.n = (int)n; a.N = (int)N; a.d = (int)d; a.S = (int)S; a.nstrip = (int)nstrip; a.nchunk = (int)nchunk;
   a.acc = nchunk > GMV_GROUP ? reinterpret_cast<double*>(ws + (long)GMV_GROUP * S * n) : nullptr;
-  // every workgroup of the grid carries the same number of row tiles: those of min(S, GMV_SMAX) right-hand sides
-  const int nst = hb_cdiv(S < GMV_SMAX ? S : GMV_SMAX, 16);
   for (long c0 = 0; c0 < nchunk; c0 += GMV_GROUP) {
     a.c0 = (int)c0;
     a.gchunks = (int)(nchunk - c0 < GMV_GROUP ? nchunk - c0 : GMV_GROUP);
-    const dim3 grid((unsigned)(nstrip * a.gchunks), (unsigned)hb_cdiv(S, GMV_SMAX), 1);
-    if (d == 1)
-      gram_matvec_launch_d<T, 1>(a, nst, grid, st);
-    else if (d == 2)
-      gram_matvec_launch_d<T, 2>(a, nst, grid, st);
-    else if (d == 3)
-      gram_matvec_launch_d<T, 3>(a, nst, grid, st);
-    else if (d == 4)
-      gram_matvec_launch_d<T, 4>(a, nst, grid, st);
-    else
-      gram_matvec_launch_d<T, 0>(a, nst, grid, st);
+    gram_matvec_launch<T>(a, st);
     HB_LAUNCH_CHECK();
     if (nchunk > 1) {
       hipLaunchKernelGGL((gram_matvec_fold_kernel<T>), dim3(hb_stream_grid(S * n, 256)), dim3(256), 0, st, a);
@@ -272,6 +283,195 @@ extern "C" int hb_gram_matvec_f64(int kind, const double* x, const double* x2, c
                                   double scale, double shift, double* out, long n, long N, long d, long S, double* ws,
                                   void* stream) {
   return gram_matvec<double>(kind, x, x2, ell, dl, V, scale, shift, out, n, N, d, S, ws, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// hb_gram_predict: predictive mean rows, a cached predictive variance and a closed-form acquisition from ONE product.
+// With t[s, j] the double hb_gram_matvec holds before its final rounding (the chunks' partials added in chunk order, times
+// scale, no shift), V = [P mean rows; S - P cache rows]:
+//     mean[p, j] = (T) t[p, j]            q_j = sum_{s >= P} t[s, j]^2  (double, s ascending)
+//     var[j] = (T) max(prior - q_j, 0)    val[j] = (T) acq_point(t[0, j], prior - q_j)   (P = 1)
+// Phase 1 is gram_matvec_kernel with to_ws set: every chunk, a single one too, leaves its partial in the workspace.
+// Phase 2, one thread per column, folds the chunks of each row in double (carrying the running sum between groups, as
+// gram_matvec_fold_kernel does) and, on the last group, emits the column's outputs and a per-workgroup arg-max partial;
+// a one-workgroup launch folds those in block order (pw_takes).  No atomics; a column's outputs depend on nothing but
+// the column.
+#define GPR_THREADS 256   // columns per workgroup of the fold
+
+template <typename T>
+struct GprArgs {
+  GmvArgs<T> g;
+  int P;
+  double prior;
+  AcqTail t;
+  T* mean;        // [P, n], nullable
+  T* var;         // [n], nullable
+  T* val;         // [n], nullable
+  double* pkey;   // arg-max partials [blocks]: the best value of the block's columns ...
+  long* pcol;     // ... and its column (-1: none comparable); nullable together
+};
+
+template <typename T>
+__global__ void __launch_bounds__(GPR_THREADS) gram_predict_fold_kernel(GprArgs<T> p) {
+  __shared__ double Rk[GPR_THREADS];
+  __shared__ long Rj[GPR_THREADS];
+  const GmvArgs<T>& a = p.g;
+  const int tid = threadIdx.x;
+  const long n = a.n, S = a.S, j = (long)blockIdx.x * GPR_THREADS + tid;
+  const bool first = a.c0 == 0, last = a.c0 + a.gchunks == a.nchunk;
+  double key = 0.0;
+  long jb = -1;
+  if (j < n) {
+    double q = 0.0, t0 = 0.0;
+    for (long s = 0; s < S; ++s) {
+      const long e = s * n + j;
+      double sum = first ? 0.0 : a.acc[e];
+      for (int ch = 0; ch < a.gchunks; ++ch) sum += (double)a.ws[(long)ch * S * n + e];
+      if (!last) {
+        a.acc[e] = sum;
+        continue;
+      }
+      const double t = a.scale * sum;
+      if (s == 0) t0 = t;
+      if (s < p.P) {
+        if (p.mean) p.mean[e] = gmv_finish<T>(a.scale, 0.0, sum, 0.0);   // the bits of hb_gram_matvec
+      } else {
+#pragma clang fp contract(off)   // two roundings, never an fma: a host can restate the sum exactly
+        const double sq = t * t;
+        q = q + sq;
+      }
+    }
+    if (last) {
+      const double vr = p.prior - q;
+      if (p.var) p.var[j] = (T)(vr < 0.0 ? 0.0 : vr);
+      if (p.t.acq != ACQ_NONE) {
+        const T v = (T)acq_point(p.t, t0, vr).val;
+        if (p.val) p.val[j] = v;
+        key = (double)v;
+        if (key == key) jb = j;
+      }
+    }
+  }
+  if (p.pkey && last) {   // (uniform)
+    Rk[tid] = key, Rj[tid] = jb;
+    __syncthreads();
+    for (int m = GPR_THREADS / 2; m > 0; m >>= 1) {
+      if (tid < m && pw_takes<double>(Rk[tid + m], Rj[tid + m], Rk[tid], Rj[tid])) Rk[tid] = Rk[tid + m], Rj[tid] = Rj[tid + m];
+      __syncthreads();
+    }
+    if (tid == 0) p.pkey[blockIdx.x] = Rk[0], p.pcol[blockIdx.x] = Rj[0];
+  }
+}
+
+// one workgroup: the blocks' partials in block order; no comparable value at all: idx = -1 and best_val = -inf
+__global__ void __launch_bounds__(GPR_THREADS) gram_predict_argmax_kernel(const double* __restrict__ pkey, const long* __restrict__ pcol,
+                                                                          long nb, double* __restrict__ best_val,
+                                                                          long* __restrict__ best_idx) {
+  __shared__ double Rk[GPR_THREADS];
+  __shared__ long Rj[GPR_THREADS];
+  const int tid = threadIdx.x;
+  double bk = -INFINITY;
+  long bj = -1;
+  for (long b = tid; b < nb; b += GPR_THREADS)
+    if (pw_takes<double>(pkey[b], pcol[b], bk, bj)) bk = pkey[b], bj = pcol[b];
+  Rk[tid] = bk, Rj[tid] = bj;
+  __syncthreads();
+  for (int m = GPR_THREADS / 2; m > 0; m >>= 1) {
+    if (tid < m && pw_takes<double>(Rk[tid + m], Rj[tid + m], Rk[tid], Rj[tid])) Rk[tid] = Rk[tid + m], Rj[tid] = Rj[tid + m];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    if (best_val) *best_val = Rj[0] < 0 ? -INFINITY : Rk[0];
+    if (best_idx) *best_idx = Rj[0];
+  }
+}
+
+// workspace, in elements of T: the partials of a group (rounded up to 8 bytes), the running double sum [S, n] beyond one
+// group, the arg-max partials (a double and a long per GPR_THREADS columns)
+static inline long gpr_part_elems(long n, long N, long S, int bytes) {
+  const long nchunk = (N + GMV_CHUNK - 1) / GMV_CHUNK, g = nchunk < GMV_GROUP ? nchunk : GMV_GROUP;
+  const long e = g * S * n;
+  return bytes == 4 ? (e + 1) & ~1L : e;
+}
+extern "C" long hb_gram_predict_ws_elems(long n, long N, long S, int dtype_bytes) {
+  if (n <= 0 || N <= 0 || S <= 0) return 0;
+  const int bytes = dtype_bytes == 4 ? 4 : 8;
+  const long per = 8 / bytes, nchunk = (N + GMV_CHUNK - 1) / GMV_CHUNK;
+  return gpr_part_elems(n, N, S, bytes) + (nchunk > GMV_GROUP ? S * n * per : 0) + 2 * per * ((n + GPR_THREADS - 1) / GPR_THREADS);
+}
+
+template <typename T>
+static int gram_predict(int kind, const T* x, const T* x2, const T* ell, long dl, const T* V, long P, double scale, double prior,
+                        int acq, double best, double param, int largest, double var_floor, T* mean, T* var, T* val,
+                        double* best_val, long* best_idx, long n, long N, long d, long S, T* ws, hipStream_t st) {
+  HB_REQUIRE(kind == HB_KERN_RBF, "hb_gram_predict: the UnitRBF kernel only (kind=%d)", kind);
+  HB_REQUIRE(n >= 0 && N >= 1 && d >= 1 && S >= 1, "hb_gram_predict: bad extents (n=%ld N=%ld d=%ld S=%ld)", n, N, d, S);
+  HB_REQUIRE(P >= 1 && P <= S, "hb_gram_predict: 1 <= P <= S mean rows expected (P=%ld S=%ld)", P, S);
+  HB_REQUIRE(dl == 1 || dl == d, "hb_gram_predict: lengthscales must have 1 or d entries");
+  HB_REQUIRE(ell && x2 && V && (n == 0 || x), "hb_gram_predict: NULL pointer");
+  const bool amax = best_val || best_idx;
+  if (acq == ACQ_NONE) {
+    HB_REQUIRE(!val && !amax, "hb_gram_predict: val, best_val and best_idx need an acquisition (acq=%d)", acq);
+    HB_REQUIRE(mean || var, "hb_gram_predict: at least one of mean, var must be given");
+  } else {
+    HB_REQUIRE(acq == HB_ACQ_EI || acq == HB_ACQ_PI || acq == HB_ACQ_UCB, "hb_gram_predict: unknown acquisition %d", acq);
+    HB_REQUIRE(P == 1, "hb_gram_predict: an acquisition is defined for one latent function only (P=%ld)", P);
+    HB_REQUIRE(mean || var || val || amax, "hb_gram_predict: at least one output must be given");
+    HB_REQUIRE(var_floor >= 0.0 && best == best && param == param,
+               "hb_gram_predict: var_floor >= 0 and numbers for best and param expected (var_floor=%g best=%g param=%g)", var_floor,
+               best, param);
+    HB_REQUIRE(!amax || n >= 1, "hb_gram_predict: an arg-max needs at least one candidate (n=%ld)", n);
+  }
+  HB_REQUIRE(prior == prior && scale == scale, "hb_gram_predict: numbers for scale and prior expected");
+  const long nstrip = (n + GMV_CN - 1) / GMV_CN, nchunk = (N + GMV_CHUNK - 1) / GMV_CHUNK;
+  HB_REQUIRE(n <= 2147483647L && N <= 2147483647L && d <= 2147483647L && S <= 2147483647L &&
+                 nstrip * (nchunk < GMV_GROUP ? nchunk : GMV_GROUP) <= 2147483647L && hb_cdiv(S, GMV_SMAX) <= 65535,
+             "hb_gram_predict: too large (n, N below 2^31, strips x chunks of a group below 2^31, S at most 64 x 65535)");
+  if (n == 0) return 0;
+  HB_REQUIRE(ws && (uintptr_t)ws % 16 == 0, "hb_gram_predict: needs a 16-byte aligned workspace (hb_gram_predict_ws_elems)");
+
+  GprArgs<T> p;
+  GmvArgs<T>& a = p.g;
+  a.x = x; a.x2 = x2; a.ell = ell; a.dl = dl; a.V = V; a.scale = scale; a.shift = 0.0; a.shift_on = 0; a.out = nullptr;
+  a.ws = ws; a.to_ws = 1;
+  a.n = (int)n; a.N = (int)N; a.d = (int)d; a.S = (int)S; a.nstrip = (int)nstrip; a.nchunk = (int)nchunk;
+  T* after = ws + gpr_part_elems(n, N, S, (int)sizeof(T));
+  a.acc = nchunk > GMV_GROUP ? reinterpret_cast<double*>(after) : nullptr;
+  if (a.acc) after += S * n * (long)(8 / sizeof(T));
+  const long nb = (n + GPR_THREADS - 1) / GPR_THREADS;
+  p.pkey = amax ? reinterpret_cast<double*>(after) : nullptr;
+  p.pcol = amax ? reinterpret_cast<long*>(after) + nb : nullptr;
+  p.P = (int)P; p.prior = prior; p.mean = mean; p.var = var; p.val = val;
+  p.t.acq = acq; p.t.largest = largest != 0; p.t.best = best; p.t.param = param; p.t.scale = 1.0; p.t.var_floor = var_floor;
+  for (long c0 = 0; c0 < nchunk; c0 += GMV_GROUP) {
+    a.c0 = (int)c0;
+    a.gchunks = (int)(nchunk - c0 < GMV_GROUP ? nchunk - c0 : GMV_GROUP);
+    gram_matvec_launch<T>(a, st);
+    HB_LAUNCH_CHECK();
+    hipLaunchKernelGGL((gram_predict_fold_kernel<T>), dim3((unsigned)nb), dim3(GPR_THREADS), 0, st, p);
+    HB_LAUNCH_CHECK();
+  }
+  if (amax) {
+    hipLaunchKernelGGL(gram_predict_argmax_kernel, dim3(1), dim3(GPR_THREADS), 0, st, (const double*)p.pkey, (const long*)p.pcol, nb,
+                       best_val, best_idx);
+    HB_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int hb_gram_predict_f32(int kind, const float* x, const float* x2, const float* ell, long dl, const float* V, long P,
+                                   double scale, double prior, int acq, double best, double param, int largest, double var_floor,
+                                   float* mean, float* var, float* val, double* best_val, long* best_idx, long n, long N, long d,
+                                   long S, float* ws, void* stream) {
+  return gram_predict<float>(kind, x, x2, ell, dl, V, P, scale, prior, acq, best, param, largest, var_floor, mean, var, val, best_val,
+                             best_idx, n, N, d, S, ws, (hipStream_t)stream);
+}
+extern "C" int hb_gram_predict_f64(int kind, const double* x, const double* x2, const double* ell, long dl, const double* V, long P,
+                                   double scale, double prior, int acq, double best, double param, int largest, double var_floor,
+                                   double* mean, double* var, double* val, double* best_val, long* best_idx, long n, long N,
+                                   long d, long S, double* ws, void* stream) {
+  return gram_predict<double>(kind, x, x2, ell, dl, V, P, scale, prior, acq, best, param, largest, var_floor, mean, var, val, best_val,
+                              best_idx, n, N, d, S, ws, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

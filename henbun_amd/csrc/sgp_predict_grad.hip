@@ -37,48 +37,13 @@
 // rule of hb_sgp_pathwise_argmax (pw_takes: strict comparisons, ties to the lowest column, a NaN never chosen).
 #include "sgp_predict.cuh"
 #include "sgp_pathwise.cuh"
+#include "acq_tail.cuh"   // AcqTail, AcqPoint, acq_point, ACQ_NONE: shared with hb_gram_predict
 
-#define ACQ_NONE (-1)                 // no tail: hb_sgp_predict_grad
 #define ACQ_FUSED_CHUNK (1L << 20)    // columns per launch of the fused form (bounds the arg-max partials)
 #define ACQ_COL_THREADS 256           // columns per workgroup of the general form's column kernel
 #define ACQ_CHUNK_ELEMS (1L << 24)    // scratch of one chunk of the general form (elements, at most): A, C / G, V
 #define ACQ_WS_HEAD 4                 // the arg-max carry: key at element 0, the column (long) 8 or 16 bytes further on
 
-struct AcqTail {
-  int acq;       // HB_ACQ_* or ACQ_NONE
-  int largest;
-  double best, param, scale, var_floor;
-};
-struct AcqPoint {
-  double val, a_mu, a_v;
-};
-
-__device__ __forceinline__ AcqPoint acq_point(const AcqTail& t, double mean, double var) {
-  const double s = t.largest ? 1.0 : -1.0, kvar = t.scale * t.scale;
-  const double mu = s * t.scale * mean, vraw = kvar * var;
-  const bool clamped = vraw < t.var_floor;
-  const double v = clamped ? t.var_floor : vraw, sg = sqrt(v);
-  AcqPoint o;
-  if (t.acq == HB_ACQ_UCB) {
-    o.val = mu + t.param * sg;
-    o.a_mu = 1.0;
-    o.a_v = t.param / (2.0 * sg);
-  } else {
-    const double u = (mu - s * t.best - t.param) / sg;
-    const double Phi = 0.5 * erfc(-u * 0.70710678118654752440), phi = 0.39894228040143267794 * exp(-0.5 * u * u);
-    if (t.acq == HB_ACQ_EI) {
-      o.val = sg * (u * Phi + phi);
-      o.a_mu = Phi;
-      o.a_v = phi / (2.0 * sg);
-    } else {
-      o.val = Phi;
-      o.a_mu = phi / sg;
-      o.a_v = -u * phi / (2.0 * v);
-    }
-  }
-  if (clamped) o.a_v = 0.0;
-  return o;
-}
 // d acq / d x_jd from the gradients of hb_sgp_predict's mean and var
 __device__ __forceinline__ double acq_grad(const AcqTail& t, const AcqPoint& q, double dmean, double dvar) {
   return (t.largest ? t.scale : -t.scale) * q.a_mu * dmean + t.scale * t.scale * q.a_v * dvar;

@@ -1,4 +1,4 @@
 from . import kernels
-from .exact import ExactPosterior, NotConverged, Preconditioner, log_marginal_likelihood, pcg_solve
+from .exact import ExactPosterior, NotConverged, Preconditioner, VarianceCache, log_marginal_likelihood, pcg_solve
 from .gp import GP, SparseGP
 from .sparse import PathwiseDraws, SparsePosterior, greedy_inducing

@@ -14,6 +14,10 @@ coefficients, logged by hb_pcg_*_coef, give the log-determinant by stochastic La
 ONE hb_gram_bilinear_grad -- a pass over the N^2 kernel entries that contracts K and dK/d ell against all the pairs of
 vectors of the gradient's traces -- and a host tail in float64.
 
+The predictive variance costs a solve per 64 test points; VarianceCache below replaces it, where an upper bound will do,
+by the Galerkin restriction of K^^-1 to the span of the preconditioner's basis: predict_f(var='cache'), acquisition and
+argmax are then ONE hb_gram_predict pass over any number of points.
+
 Out of scope: kernels other than UnitRBF, non-Gaussian likelihoods, variance reduction of the trace estimators beyond
 the preconditioner.
 """
@@ -21,6 +25,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from .._settings import settings
 from . import _host
 from .sparse import PathwiseDraws
 
@@ -299,16 +304,87 @@ def log_marginal_likelihood(sess, Xd, Yt, ell, k_var, noise_var, precond, tol, m
     return value, dict(lengthscales=k_var * g[1:], k_var=float(g[0]), noise_var=float(wts @ dots)), info
 
 
+_CACHE_JITTER = 1e-13        # VarianceCache: T + eps tr(T) / r I is factorised, eps from here ...
+_CACHE_JITTER_TRIES = 3      # ... multiplied by 100 after a failed factorisation, at most this many times
+_CACHE_PRODUCT_BYTES = 1 << 30   # workspace of the product K^ C above which the rows of C are taken in blocks
+
+
+class VarianceCache:
+    """A cached upper bound of the exact GP's predictive variance (ExactPosterior.build_cache).  For a full-row-rank
+    basis C [r, N], the Galerkin restriction of K^ = k_var K(X, X) + noise_var I to span(C^T) gives
+        G = C^T (C K^ C^T)^-1 C  <=  K^^-1     (positive semi-definite order),
+    so that v_cache(x) = k_var - k*^T G k* = k_var - |R_c k*|^2, R_c = L_T^-1 C, T = C K^ C^T = L_T L_T^T, is
+      - an UPPER bound of the exact variance k_var - k*^T K^^-1 k* at every x (conservative error bars),
+      - non-increasing as rows are appended to C, and the exact variance once C spans the numerical range of K,
+      - one kernel product per point, with no Krylov iteration and no random numbers.
+    C is the pivoted incomplete Cholesky factor hb_sgp_select leaves in its workspace (the preconditioner's basis), its
+    rows scaled to unit norm; T, its Cholesky factor and R_c are float64 whatever the session's dtype, R_c is rounded
+    ONCE to the session's dtype.  The jitter added to T replaces (C K^ C^T)^-1 by something smaller: it can only loosen
+    the bound, never break it.  HONEST LIMIT: the bound is tight once r reaches the number of eigenvalues of K that
+    matter -- roughly the volume of the data in lengthscale units; on a domain of hundreds of lengthscales a small r
+    leaves it loose (still an upper bound).  predict_f(var=True) stays the exact route.
+    Building needs 2 r N 8 bytes transiently (C and K^ C, then C and R_c, in float64) beside the selection's own
+    workspace; the cache keeps Rc and the basis C, [r, N] each, in the session's dtype."""
+
+    def __init__(self, sess, Xd, ell, k_var, noise_var, rank, threshold, precond=None):
+        torch, H = sess.torch, sess.H
+        N, d = Xd.shape
+        dt, dev, f64 = Xd.dtype, Xd.device, torch.float64
+        want = min(int(rank), N, 8192)
+        ld = (N + 63) // 64 * 64
+        if precond is not None and float(threshold) == 0.0 and precond.rank == want and precond.N == N:
+            hist, r = precond.C, precond.rank     # the same selection: its first `want` rows
+        else:
+            hist = torch.empty(H.sgp_select_ws_elems(dt, N, want, d), dtype=dt, device=dev)
+            _, _, count, _ = H.sgp_select(Xd, ell, want, float(threshold), ws=hist)
+            r = int(count.cpu()[0])
+        if r < 1:
+            raise ValueError("build_cache: the selection produced no row (threshold %r)" % (threshold,))
+        self.basis = hist[:r * ld].view(r, ld)[:, :N].contiguous()     # C as the selection left it
+        C = self.basis.to(f64)
+        del hist
+        C = H.ewise("MUL", [C, H.ewise("RSQRT", [H.pcg_dot(C, C)]).reshape(r, 1)])      # unit rows
+        X64, ell64 = Xd.to(f64), ell.to(f64)
+        KC = torch.empty((r, N), dtype=f64, device=dev)
+        rows = r
+        while rows > 64 and H.gram_matvec_ws_elems(f64, N, N, rows) * 8 > _CACHE_PRODUCT_BYTES:
+            rows = (rows // 2 + 63) // 64 * 64    # (a row of the product does not depend on the others: the same bits)
+        gws = torch.empty(max(H.gram_matvec_ws_elems(f64, N, N, rows), 1), dtype=f64, device=dev)
+        for a in range(0, r, rows):
+            H.gram_matvec(X64, None, ell64, C[a:a + rows], scale=float(k_var), shift=float(noise_var), out=KC[a:a + rows], ws=gws)
+        del gws
+        T = H.matutil(H.matmul(KC, C, transB=True), H.MATUTIL_SYM)
+        del KC
+        trace = float(torch.diagonal(T).cpu().numpy().sum())
+        eps = _CACHE_JITTER
+        for attempt in range(_CACHE_JITTER_TRIES + 1):
+            try:
+                L = _host.factor(H, H.matutil(T, H.MATUTIL_ADD_EYE, alpha=eps * trace / r), "build_cache",
+                                 "C K^ C^T + %g tr / r I (rank %d)" % (eps, r), RuntimeError)
+                break
+            except RuntimeError:
+                if attempt == _CACHE_JITTER_TRIES:
+                    raise
+                eps *= 100.0
+        self.Rc = H.matmul(H.trinv(L), C).to(dt).contiguous()            # rounded once
+        self.rank = r
+        self.info = dict(rank=r, asked=int(rank), jitter=eps, trace=trace)
+
+
 class ExactPosterior:
     """The exact GP posterior given (X, Y) at fixed hyper-parameters (GP.condition): a snapshot, like PathwiseDraws, of X
     [N, d], the lengthscales, k_var, noise_var, alpha = K^^-1 Y [P, N], the preconditioner and the solve's `info`, on the
-    device in the session's dtype.  Later changes to the model do not move it."""
+    device in the session's dtype.  Later changes to the model do not move it.  build_cache() adds a VarianceCache:
+    predict_f(var='cache'), acquisition and argmax then cost ONE kernel product over the candidates, however many."""
+
+    KINDS = ("ei", "pi", "ucb")
 
     def __init__(self, sess, X, Y, ell, k_var, noise_var, alpha, precond, info, tol, max_iter):
         self._sess = sess
         self._X, self._Y, self._ell, self._alpha, self._precond = X, Y, ell, alpha, precond
         self.k_var, self.noise_var, self.info = float(k_var), float(noise_var), info
         self.tol, self.max_iter = tol, int(max_iter)
+        self._cache, self._V, self.cache_info = None, None, None
 
     alpha = property(lambda self: self._alpha.cpu().numpy(), doc="K^^-1 Y as numpy [P, N]")
 
@@ -321,11 +397,45 @@ class ExactPosterior:
             raise ValueError("ExactPosterior: Xnew %s does not match X %s" % (tuple(Xn.shape), tuple(self._X.shape)))
         return Xn
 
+    def build_cache(self, rank=256, threshold=None):
+        """Build the VarianceCache of this posterior (see there for what it bounds and where it is loose) and return
+        self.  rank: rows of the pivoted incomplete Cholesky basis asked for (at most N and 8192); the selection stops
+        earlier once no conditional variance exceeds `threshold` (None: settings.numerics.jitter_level, the convention
+        of greedy_inducing).  The preconditioner's basis is reused when its rank and threshold (0) match.  cache_info =
+        dict(rank = rows produced, asked, jitter = the eps of T + eps tr(T) / r I that factorised, trace = tr T).
+        Needs 2 r N 8 bytes transiently whatever the session's dtype."""
+        thr = float(settings.numerics.jitter_level if threshold is None else threshold)
+        if not (int(rank) >= 1 and thr >= 0.0):
+            raise ValueError("build_cache: rank >= 1 and threshold >= 0 expected (got %r, %r)" % (rank, threshold))
+        self._cache = VarianceCache(self._sess, self._X, self._ell, self.k_var, self.noise_var, rank, thr, self._precond)
+        self._V = self._sess.torch.cat([self._alpha, self._cache.Rc]).contiguous()     # [P + r, N]: mean rows, cache rows
+        self.cache_info = dict(self._cache.info)
+        return self
+
+    cache_basis = property(lambda self: self._need_cache("cache_basis").basis.cpu().numpy(),
+                           doc="the basis C [r, N] of the cache as the selection produced it (numpy)")
+
+    def _need_cache(self, who):
+        if self._cache is None:
+            raise ValueError("%s: no variance cache, call build_cache() first" % who)
+        return self._cache
+
+    def _cached(self, Xn, **kw):
+        P = self._alpha.shape[0]
+        return self._sess.H.gram_predict(Xn, self._X, self._ell, self._V, P=P, scale=self.k_var, prior=self.k_var, **kw)
+
     def predict_f(self, Xnew, var=True):
         """(mean [P, n], var [n]) of the latent f at the rows of Xnew, as numpy.  The mean is ONE hb_gram_matvec,
         k_var alpha K(X, Xnew).  var = k_var - k*^T K^^-1 k* costs ONE LOCKSTEP SOLVE PER 64 TEST POINTS, each as expensive
         as the conditioning itself (right-hand sides k_var K(X, Xnew_block) from hb_gram_fwd); var=False skips it and
-        returns (mean, None)."""
+        returns (mean, None).  var='cache': (mean, var_upper) from ONE hb_gram_predict pass over Xnew -- the same mean
+        bits and the VarianceCache's upper bound of the variance (build_cache() first, else ValueError)."""
+        if isinstance(var, str):
+            if var != "cache":
+                raise ValueError("predict_f: var must be True, False or 'cache' (got %r)" % (var,))
+            self._need_cache("predict_f(var='cache')")
+            mean, v, _, _, _ = self._cached(self._new_points(Xnew))
+            return mean.cpu().numpy(), v.cpu().numpy()
         torch, H = self._sess.torch, self._sess.H
         Xn = self._new_points(Xnew)
         n = Xn.shape[0]
@@ -342,9 +452,44 @@ class ExactPosterior:
         return mean, out
 
     def predict_y(self, Xnew, var=True):
-        """predict_f plus the noise variance: the predictive of a new observation."""
+        """predict_f plus the noise variance: the predictive of a new observation (var='cache': of the upper bound)."""
         mean, v = self.predict_f(Xnew, var=var)
         return mean, None if v is None else v + np.asarray(self.noise_var, dtype=v.dtype)
+
+    def _acq_args(self, who, kind, best, param, var_floor):
+        if kind not in self.KINDS:
+            raise ValueError("%s: kind must be one of %s, got %r" % (who, self.KINDS, kind))
+        if self._alpha.shape[0] != 1:
+            raise NotImplementedError("%s: one latent function only (Y has %d columns)" % (who, self._alpha.shape[0]))
+        if kind != "ucb" and best is None:
+            raise ValueError("%s: the acquisition %r needs `best`, the incumbent value" % (who, kind))
+        self._need_cache(who)
+        var_floor = self.k_var * float(settings.numerics.jitter_level) if var_floor is None else float(var_floor)
+        if not var_floor >= 0.0:
+            raise ValueError("%s: var_floor >= 0 expected (got %r)" % (who, var_floor))
+        return dict(acq=kind, best=0.0 if best is None else float(best), param=float(param), var_floor=var_floor)
+
+    def acquisition(self, X, kind, best=None, param=0.0, largest=True, var_floor=None):
+        """The closed-form acquisition `kind` ('ei', 'pi': param = xi, improvement over `best`; 'ucb': param = beta) at
+        the rows of X, as numpy [n], from the exact mean and the CACHED variance bound (build_cache() first): ONE
+        hb_gram_predict pass, the tail of SparsePosterior.acquisition per point in double.  For maximising f (largest) or
+        minimising it; sigma^2 = max(var_upper, var_floor), var_floor=None: k_var * jitter_level as there.  The bound
+        makes sigma conservative: exploration is never under-weighted.  One latent function only; no input gradient
+        yet (the gradient of the cached variance is the follow-up)."""
+        args = self._acq_args("acquisition", kind, best, param, var_floor)
+        _, _, val, _, _ = self._cached(self._new_points(X), largest=bool(largest), mean=False, var=False, value=True, **args)
+        return val.cpu().numpy()
+
+    def argmax(self, X, kind, best=None, param=0.0, largest=True, var_floor=None):
+        """(index, value): the row of X at which acquisition(X, ...) is largest (ties: the first row; a NaN is never
+        chosen) and its value there, without writing anything of size n, so X can be millions of candidates.  No
+        comparable value: (-1, -inf)."""
+        args = self._acq_args("argmax", kind, best, param, var_floor)
+        Xd = self._new_points(X)
+        if Xd.shape[0] < 1:
+            raise ValueError("argmax: at least one candidate expected")
+        _, _, _, bv, bi = self._cached(Xd, largest=bool(largest), mean=False, var=False, value=False, argmax=True, **args)
+        return int(bi.cpu().numpy()[0]), self._sess.np_dtype(bv.cpu().numpy()[0])
 
     def sample_functions(self, num_samples, num_features=1024, seed=0, noise=None):
         """num_samples posterior FUNCTION draws as a PathwiseDraws with z = X, M = N (pathwise conditioning on the data

@@ -1495,6 +1495,103 @@ def gram_matvec(x, x2, ell, V, scale=1.0, shift=0.0, out=None, ws=None, kind=KER
     return out
 
 
+GRAM_PREDICT_WS_BYTES = 1 << 30   # gram_predict cuts x into pieces so that hb_gram_predict's workspace stays under this
+
+
+def gram_predict_ws_elems(dtype, n, N, S):
+    """Scratch elements hb_gram_predict needs: min(chunks, 16) x S x n partials (one chunk included), S n doubles beyond
+    16 chunks, and a double and a long per 256 columns for the arg-max."""
+    return int(_lib.lib().raw("hb_gram_predict_ws_elems")(int(n), int(N), int(S), _elem_bytes(dtype)))
+
+
+def _gram_predict_piece(n, N, S, dtype):
+    """Columns per call of gram_predict: the largest multiple of 128 whose workspace fits GRAM_PREDICT_WS_BYTES (at least
+    128), or n when all of x fits."""
+    if gram_predict_ws_elems(dtype, n, N, S) * _elem_bytes(dtype) <= GRAM_PREDICT_WS_BYTES:
+        return max(n, 1)
+    per128 = gram_predict_ws_elems(dtype, 128, N, S) * _elem_bytes(dtype)
+    return max(int(GRAM_PREDICT_WS_BYTES) // per128, 1) * 128
+
+
+def gram_predict(x, x2, ell, V, P=1, scale=1.0, prior=1.0, acq=None, best=0.0, param=0.0, largest=True, var_floor=0.0,
+                 mean=True, var=True, value=None, argmax=False, kind=KERN_RBF):
+    """Predictive mean, cached predictive variance and closed-form acquisition from ONE kernel product (hb_gram_predict).
+    x [n, d], x2 [N, d], ell [1] or [d], V [S, N] = P mean rows, then S - P cache rows, all of one dtype.  With
+    t = scale V K(x2, x) held in double:  mean [P, n] = t[:P] (the bits of gram_matvec on those rows),
+    var [n] = max(prior - sum_{s >= P} t[s]^2, 0), and with acq 'ei' / 'pi' (param = xi, improvement over `best`) or 'ucb'
+    (param = beta) the tail of sgp_acq at (t[0], prior - sum ..) for maximising (largest) or minimising; an acquisition
+    needs P == 1.  Returns (mean, var, val [n], best_val float64 [1], best_idx int64 [1]) device tensors, None for each
+    output not asked for (mean / var / value / argmax; value=None: values exactly when an acquisition is given and no
+    arg-max).  best_val = max_j val[j], best_idx its first column; a NaN is never chosen, no comparable value: -1 and
+    -inf; with argmax alone nothing of size n is written.  A column's results do not depend on the other columns: x is cut
+    into pieces of a multiple of 128 columns so that the workspace stays under GRAM_PREDICT_WS_BYTES, the pieces' arg-max
+    combined by the same strict rule, and the bits are those of one call."""
+    who = "gram_predict"
+    for t in (x, x2, ell, V):
+        _chk(t)
+    if x.dim() != 2 or V.dim() != 2 or ell.dim() != 1 or x2.dim() != 2 or x2.shape[1] != x.shape[1]:
+        raise ValueError("%s: x [n, d], x2 [N, d], ell [1] or [d], V [S, N] expected, got %s %s %s %s"
+                         % (who, tuple(x.shape), tuple(x2.shape), tuple(ell.shape), tuple(V.shape)))
+    (n, d), N, S, P = x.shape, x2.shape[0], V.shape[0], int(P)
+    if V.shape[1] != N or N < 1 or ell.numel() not in (1, d):
+        raise ValueError("%s: V must hold N = %d >= 1 columns and ell 1 or %d entries, got %s %s"
+                         % (who, N, d, tuple(V.shape), tuple(ell.shape)))
+    if any(t.dtype != x.dtype for t in (x2, ell, V)):
+        raise TypeError("%s: all operands must share one dtype" % who)
+    if not 1 <= P <= S:
+        raise ValueError("%s: 1 <= P <= S mean rows expected, got P=%d, S=%d" % (who, P, S))
+    if acq is None:
+        code = -1
+        if value or argmax:
+            raise ValueError("%s: value and argmax need an acquisition" % who)
+        value = False
+    else:
+        code = ACQ.get(acq, None) if isinstance(acq, str) else acq
+        if code not in ACQ.values():
+            raise ValueError("%s: acq must be one of %s, got %r" % (who, sorted(ACQ), acq))
+        if P != 1:
+            raise ValueError("%s: an acquisition is defined for one latent function only (P=%d)" % (who, P))
+        if not float(var_floor) >= 0.0:
+            raise ValueError("%s: var_floor >= 0 expected (got %r)" % (who, var_floor))
+        value = (not argmax) if value is None else bool(value)
+    if not (mean or var or value or argmax):
+        raise ValueError("%s: at least one of mean, var, value, argmax expected" % who)
+    if argmax and n < 1:
+        raise ValueError("%s: at least one candidate expected, got x %s" % (who, tuple(x.shape)))
+    dt, dev = x.dtype, x.device
+    piece = _gram_predict_piece(n, N, S, dt)
+    o_mean = _empty((P, n), dtype=dt, device=dev) if mean else None
+    o_var = _empty((n,), dtype=dt, device=dev) if var else None
+    o_val = _empty((n,), dtype=dt, device=dev) if value else None
+    ws = workspace(dt, dev, max(gram_predict_ws_elems(dt, min(n, piece), N, S), 1))
+    bests = []
+    for a in range(0, n, piece):
+        b = min(a + piece, n)
+        whole = a == 0 and b == n
+        m_p = o_mean if whole or not mean else _empty((P, b - a), dtype=dt, device=dev)
+        bv = _empty((1,), dtype=torch.float64, device=dev) if argmax else None
+        bi = _empty((1,), dtype=torch.int64, device=dev) if argmax else None
+        _lib.lib().call("hb_gram_predict" + _suf(x), int(kind), _p(x[a:b]), _p(x2), _p(ell), ell.numel(), _p(V), P, float(scale),
+                        float(prior), int(code), float(best), float(param), 1 if largest else 0, float(var_floor), _p(m_p),
+                        _p(None if o_var is None else o_var[a:b]), _p(None if o_val is None else o_val[a:b]), _p(bv), _p(bi),
+                        b - a, N, d, S, _p(ws), stream())
+        if mean and not whole:
+            o_mean[:, a:b].copy_(m_p)
+        bests.append((a, bv, bi))
+    if not argmax:
+        return o_mean, o_var, o_val, None, None
+    if len(bests) == 1:
+        return o_mean, o_var, o_val, bests[0][1], bests[0][2]
+    keys = torch.cat([bv for _, bv, _ in bests]).cpu().numpy()   # ONE read-back pair for all the pieces
+    cols = torch.cat([bi for _, _, bi in bests]).cpu().numpy()
+    bk, bj = -np.inf, -1
+    for (a, _, _), k, j in zip(bests, keys, cols):   # pw_takes: strict, ties to the lowest column, an empty piece never
+        if j >= 0 and (bj < 0 or k > bk):
+            bk, bj = float(k), a + int(j)
+    return (o_mean, o_var, o_val, torch.as_tensor([bk], dtype=torch.float64).to(dev),
+            torch.as_tensor([bj], dtype=torch.int64).to(dev))
+
+
 def pcg_dot(a, b, out=None):
     """out [S] float64 = sum_i a_si b_si (hb_pcg_dot), a, b [S, N]."""
     _chk(a), _chk(b)

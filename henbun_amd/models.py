@@ -406,11 +406,16 @@ class ExactGPR(hb.model.Model):
         self.var = hb.param.Variable([1], transform=hb.transforms.positive)
         self.posterior = None
 
-    def fit(self, precond_rank=64, tol=None, max_iter=1000):
+    def fit(self, precond_rank=64, tol=None, max_iter=1000, cache_rank=None):
         """Condition on the model's X, Y at the CURRENT lengthscales, k_var and var and keep the hb.gp.ExactPosterior
-        (also returned as self.posterior); hyper-parameters changed afterwards need another fit().  Returns self."""
+        (also returned as self.posterior); hyper-parameters changed afterwards need another fit().  cache_rank: also
+        build the posterior's variance cache at that rank (ExactPosterior.build_cache), for predict_f(var='cache') and
+        suggest.  Returns self."""
         X, Y, var, k_var = self._closed_form_inputs()
-        self.posterior = _part(self, "gp").condition(X, Y, var, k_var=k_var, precond_rank=precond_rank, tol=tol, max_iter=max_iter)
+        post = _part(self, "gp").condition(X, Y, var, k_var=k_var, precond_rank=precond_rank, tol=tol, max_iter=max_iter)
+        if cache_rank is not None:
+            post.build_cache(rank=cache_rank)
+        self.posterior = post
         return self
 
     _closed_form_inputs = SVGP._closed_form_inputs
@@ -457,12 +462,34 @@ class ExactGPR(hb.model.Model):
         return post
 
     def predict_f(self, Xnew, var=True):
-        """(mean [P, n], var [n]) of the latent f at Xnew; the variance costs one solve per 64 points (var=False skips it)."""
+        """(mean [P, n], var [n]) of the latent f at Xnew; the variance costs one solve per 64 points (var=False skips it).
+        var='cache': the cached upper bound of the variance instead, from ONE pass over Xnew (fit(cache_rank=...) or
+        posterior.build_cache() first) -- tight once the rank covers the data's volume in lengthscale units, loose but
+        still an upper bound below that."""
         return self._posterior().predict_f(Xnew, var=var)
 
     def predict_y(self, Xnew, var=True):
         """predict_f plus the likelihood's variance."""
         return self._posterior().predict_y(Xnew, var=var)
+
+    def suggest(self, Xcand, kind="ei", largest=True, cache_rank=256, **kw):
+        """(x_next [d], value, info): the next point of a sequential design -- the row of Xcand [n, d] at which the
+        closed-form acquisition `kind` ('ei', 'pi', 'ucb') of the exact posterior is largest, from ONE arg-max pass over
+        the candidates (ExactPosterior.argmax; **kw: param, var_floor), however many there are.  The incumbent is
+        suggest_batch's: the largest (smallest with largest=False) posterior mean over the training inputs,
+        predict_f(X, var=False).  The variance is the cached upper bound, built at cache_rank if the posterior has none.
+        info = dict(best, index, cache = the posterior's cache_info).  No gradient ascent from the candidate: input
+        gradients of the cached variance are the follow-up."""
+        post = self._posterior()
+        mean, _ = post.predict_f(_part(self, "X"), var=False)
+        best = float(mean.max() if largest else mean.min())
+        if post.cache_info is None:
+            post.build_cache(rank=cache_rank)
+        Xd = post._new_points(Xcand)
+        idx, value = post.argmax(Xd, kind, best=best, largest=largest, **kw)
+        if idx < 0:
+            raise ValueError("suggest: no candidate has a comparable acquisition value")
+        return Xd[idx].cpu().numpy(), value, dict(best=best, index=idx, cache=dict(post.cache_info))
 
     def sample_functions(self, num_samples, num_features=1024, seed=0, noise=None):
         """num_samples exact posterior function draws as an hb.gp.PathwiseDraws (ExactPosterior.sample_functions); its

@@ -63,7 +63,8 @@ extern "C" {
  * (rules and sizes a planner asks for instead of restating them); hb_sgp_pathwise_acq_f32 / _f64,
  * hb_sgp_pathwise_acq_ws_elems and the enum values HB_PWACQ_* (batch acquisition from pathwise function draws);
  * hb_matmul_form and the enum values HB_MM_FORM_* (which kernel form, slab count and operand path hb_matmul_* takes for
- * a call: a host-side query that launches nothing). */
+ * a call: a host-side query that launches nothing); hb_gram_predict_f32 / _f64 and hb_gram_predict_ws_elems (exact GP:
+ * predictive mean, cached upper bound of the predictive variance and closed-form acquisition from one kernel product). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -866,6 +867,39 @@ int hb_gram_matvec_f32(int kind, const float* x, const float* x2, const float* e
                        double shift, float* out, long n, long N, long d, long S, float* ws, void* stream);
 int hb_gram_matvec_f64(int kind, const double* x, const double* x2, const double* ell, long dl, const double* V, double scale,
                        double shift, double* out, long n, long N, long d, long S, double* ws, void* stream);
+/* Predictive mean, cached predictive variance and closed-form acquisition of an exact GP from ONE kernel product
+ * (csrc/gram_matvec.hip; not in the reference).  V [S, N] holds P mean rows first (1 <= P <= S), then S - P cache rows.
+ * With t[s, j] the DOUBLE that hb_gram_matvec holds for the same x, x2, V and scale (no shift) before its final rounding -- the chunks' partials
+ * added in chunk order, or the one chunk's accumulator, times scale:
+ *   mean[p, j] = (T) t[p, j], p < P              -- the bits of hb_gram_matvec on those rows;
+ *   q_j = sum_{s >= P} t[s, j]^2                  -- in double, s ascending, each square and each sum rounded once;
+ *   var[j] = (T) max(prior - q_j, 0);
+ *   val[j] = (T) the tail of hb_sgp_acq -- HB_ACQ_EI / _PI / _UCB with best, param, largest, var_floor as there, scale = 1 --
+ *            evaluated in double at (t[0, j], prior - q_j); needs P == 1.  acq = -1: no acquisition (val, best_val and
+ *            best_idx must then be NULL).
+ * With V = [alpha; R_c], scale = prior = k_var, R_c = L_T^-1 C and T = C K^ C^T = L_T L_T^T for any full-row-rank C [r, N],
+ * var is k_var - k*^T C^T (C K^ C^T)^-1 C k* >= k_var - k*^T K^^-1 k*: an UPPER bound of the exact predictive variance
+ * (the Galerkin restriction of K^^-1 to span(C^T); henbun_amd/gp/exact.py: VarianceCache).
+ * Outputs, each nullable, at least one given: mean [P, n], var [n], val [n] in the storage type, best_val [1] DOUBLE =
+ * max_j val[j] (those bits, widened) and best_idx [1] (long) its first column, by the rule of hb_sgp_acq: comparisons
+ * strict, ties to the lowest column, a NaN never chosen, no comparable value: -1 and -inf.  With only best_val / best_idx
+ * asked for nothing of size n is written except the workspace.  n = 0 returns without a launch (rejected for an arg-max).
+ * Phase 1 is the kernel of hb_gram_matvec, every chunk's partial left in the workspace (a single chunk's too); phase 2,
+ * one thread per column, adds the chunks in chunk order in double (16 chunks at a time, the running sum carried between
+ * the groups) and finishes the column; a one-workgroup launch folds the per-workgroup arg-max partials.  No atomics: two
+ * calls return the same bits, and a column's outputs depend neither on n nor on the other columns nor on how x is cut
+ * into pieces.  x [n, d], x2 [N, d] (non-NULL, N >= 1), ell [dl], dl in {1, d}; kind must be HB_KERN_RBF.
+ * ws >= hb_gram_predict_ws_elems(n, N, S, sizeof(T)) elements of T, 16-byte aligned: min(chunks, 16) S n partials, S n
+ * doubles beyond 16 chunks, a double and a long per 256 columns.  Validated before any launch. */
+long hb_gram_predict_ws_elems(long n, long N, long S, int dtype_bytes);
+int hb_gram_predict_f32(int kind, const float* x, const float* x2, const float* ell, long dl, const float* V, long P,
+                        double scale, double prior, int acq, double best, double param, int largest, double var_floor,
+                        float* mean, float* var, float* val, double* best_val, long* best_idx, long n, long N, long d, long S,
+                        float* ws, void* stream);
+int hb_gram_predict_f64(int kind, const double* x, const double* x2, const double* ell, long dl, const double* V, long P,
+                        double scale, double prior, int acq, double best, double param, int largest, double var_floor,
+                        double* mean, double* var, double* val, double* best_val, long* best_idx, long n, long N, long d,
+                        long S, double* ws, void* stream);
 /* Vector steps of S preconditioned conjugate-gradient iterations run in lockstep on rows of length N (csrc/gram_matvec.hip;
  * henbun_amd/gp/exact.py).  x, r, p, Ap, w [S, N] in the storage type; rz, rr, thr, out [S] DOUBLE: every dot product and
  * scalar is double.  One workgroup per row, sums in a fixed order: two solves return the same bits.  A row with
