@@ -8,7 +8,8 @@
 //   hb_chain_end(stream);                   runs what is still recorded, stops recording
 //
 // Only entry points that know about chains may be called between begin and end (henbun_amd/graph.py wraps exactly those
-// steps): hb_ewise_jit_run, hb_gauss_ll, hb_adam_step, hb_sgp_fwd (its finishing pass), hb_gram_bwd (its lengthscale fold).
+// steps): hb_ewise_jit_run, hb_gauss_ll, hb_adam_step, hb_sgp_fwd (its finishing pass), hb_gram_bwd (its lengthscale fold),
+// hb_gram_ell_fold, hb_gram_tiles_fold.
 // Where hiprtc is unavailable hb_chain_begin records nothing and every call launches as usual.
 //
 // The generated kernel does not load job by job: whatever a job reads that no earlier job of the chain writes is final
@@ -20,7 +21,7 @@
 #include "common.cuh"
 #include "ew_prog.cuh"
 
-enum { HB_CHAIN_PROG = 1, HB_CHAIN_ADAM = 2, HB_CHAIN_GLL = 3, HB_CHAIN_SGP_FINISH = 4, HB_CHAIN_GRAM_ELL = 5, HB_CHAIN_GLL_FOLD = 6 };
+enum { HB_CHAIN_PROG = 1, HB_CHAIN_ADAM = 2, HB_CHAIN_GLL = 3, HB_CHAIN_SGP_FINISH = 4, HB_CHAIN_GRAM_ELL = 5, HB_CHAIN_GLL_FOLD = 6, HB_CHAIN_GRAM_TILES = 7 };
 #define HB_CHAIN_MAX_JOBS 6
 // A chain is ONE workgroup, and one CU streams ~10 bytes per cycle (24 GB/s): a job that moves more than a few tens
 // of KB costs more inside a chain than the ~4.5 us kernel boundary it saves (measured: the sparse-GP finishing pass at
@@ -31,6 +32,7 @@ enum { HB_CHAIN_PROG = 1, HB_CHAIN_ADAM = 2, HB_CHAIN_GLL = 3, HB_CHAIN_SGP_FINI
 #define HB_CHAIN_ADAM_MAX_N 4096      // parameters of an Adam update
 #define HB_CHAIN_ELL_MAX_N 16384      // partials of a lengthscale fold
 #define HB_CHAIN_GLL_FOLD_MAX_N 4096  // units of a likelihood-head fold
+#define HB_CHAIN_TILES_MAX_N 16384     // tile partials of a Gram VJP that ran in a product's epilogue (16 per thread, one load phase)
 
 enum { HB_CHAIN_READ = 1, HB_CHAIN_WRITE = 2, HB_CHAIN_RW = 3 };
 

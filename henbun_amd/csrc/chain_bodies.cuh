@@ -439,6 +439,83 @@ __device__ __forceinline__ void hb_gram_ell_body(const T* __restrict__ partial, 
   hb_gram_ell_body<T, 1>(h, partial, rows, d, dl, c, ellbar, smem, mir);
 }
 
+// --------------------------------------------------------------- fold of a Gram VJP's tile partials (hb_gram_tiles_fold)
+// part[B][tiles][tiles][32][2 d] is what the tiles-mode product (csrc/linalg.hip, matmul_wgk_kernel<.., TILES>) leaves: for
+// every 32 x 32 tile of Kbar, per row, d point-gradient shares and then d lengthscale shares.  Output o of the fold,
+// o = (b M + row) 2 d + q, is the sum of the tiles_n shares of its row in ascending tile order: q < d goes to
+// Xbar[(b M + row) d + q], q >= d into the lengthscale sum (column q - d, or the one column when dl == 1), which is then
+// folded over the rows and the batch into ellbar[dl].  One workgroup; thread t owns the outputs t, t + blockDim.x, ...
+// Load part: the shares of the thread's first S outputs (S * TN values); compute part: their sums, any further output from
+// memory in the order of the plain loop, the stores and the block sums.  on_xbar(address, value) sees every Xbar stored (a
+// serial chain mirrors them into the LDS window of a later job); mir (nullable): an LDS slot that also gets ellbar[0].
+#define HB_GRAM_TILES_MAXD 4
+// (32-bit index arithmetic: outs and the partials are bounded by HB_CHAIN_TILES_MAX_N where the fold is launched)
+__device__ __forceinline__ long hb_gram_tiles_addr(long o, long tiles_n, long d) {
+  const unsigned w = 64u * (unsigned)d, g = (unsigned)o / w;   // g = b tiles_m + ti; o - g w = r 2 d + q
+  return (long)(g * (unsigned)tiles_n * w + ((unsigned)o - g * w));
+}
+template <typename T, int S, int TN>
+__device__ __forceinline__ void hb_gram_tiles_load(const T* __restrict__ part, long outs, long d, T (&h)[S * TN > 0 ? S * TN : 1]) {
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const long o = (long)threadIdx.x + (long)s * blockDim.x, oc = o < outs ? o : outs - 1;
+    const T* p = part + hb_gram_tiles_addr(oc, TN, d);
+#pragma unroll
+    for (int t = 0; t < TN; ++t) h[s * TN + t] = p[(long)t * 64 * d];
+  }
+}
+template <typename T, int S, int TN, typename F>
+__device__ __forceinline__ void hb_gram_tiles_body(const T (&h)[S * TN > 0 ? S * TN : 1], const T* __restrict__ part, long outs, long tiles_n, long d,
+                                                   long dl, T* __restrict__ Xbar, T* __restrict__ ellbar, T* smem, F on_xbar,
+                                                   T* mir = nullptr) {
+  T lp[HB_GRAM_TILES_MAXD];
+#pragma unroll
+  for (int k = 0; k < HB_GRAM_TILES_MAXD; ++k) lp[k] = T(0);
+  auto put = [&](long o, T v) {
+    const long row = (long)((unsigned)o / (2u * (unsigned)d)), q = o - row * 2 * d;
+    if (q < d) {
+      Xbar[row * d + q] = v;
+      on_xbar(Xbar + row * d + q, v);
+    } else {
+      const long c = dl == 1 ? 0 : q - d;
+#pragma unroll
+      for (int k = 0; k < HB_GRAM_TILES_MAXD; ++k)
+        if (c == k) lp[k] += v;
+    }
+  };
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const long o = (long)threadIdx.x + (long)s * blockDim.x;
+    T acc = T(0);
+#pragma unroll
+    for (int t = 0; t < TN; ++t) acc += h[s * TN + t];
+    if (o < outs) put(o, acc);
+  }
+  for (long o = (long)threadIdx.x + (long)S * blockDim.x; o < outs; o += blockDim.x) {
+    const T* p = part + hb_gram_tiles_addr(o, tiles_n, d);
+    T acc = T(0);
+    for (long t = 0; t < tiles_n; ++t) acc += p[t * 64 * d];
+    put(o, acc);
+  }
+#pragma unroll
+  for (int k = 0; k < HB_GRAM_TILES_MAXD; ++k) {
+    if (k < dl) {   // (uniform)
+      const T e = block_sum(lp[k], smem);
+      if (threadIdx.x == 0) {
+        ellbar[k] = e;
+        if (mir && k == 0) mir[0] = e;
+      }
+    }
+  }
+}
+// the composition: nothing preloaded, every output from memory
+template <typename T, typename F>
+__device__ __forceinline__ void hb_gram_tiles_body(const T* __restrict__ part, long outs, long tiles_n, long d, long dl,
+                                                   T* __restrict__ Xbar, T* __restrict__ ellbar, T* smem, F on_xbar) {
+  const T h[1] = {T(0)};
+  hb_gram_tiles_body<T, 0, 1, F>(h, part, outs, tiles_n, d, dl, Xbar, ellbar, smem, on_xbar);
+}
+
 // ------------------------------------------------------------------------- serial chains: LDS windows (csrc/jit.hip)
 // A window holds the n elements from `base` on that a later job of the chain reads: filled from memory in the load phase
 // (hb_chain_win_load requests, hb_chain_win_store writes the LDS copy), then every store of an earlier job that falls

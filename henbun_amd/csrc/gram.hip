@@ -235,6 +235,34 @@ extern "C" int hb_gram_ell_fold_f64(const double* partial, long rows, long d, lo
   return gram_ell_fold<double>(partial, rows, d, dl, groups, ellbar, (hipStream_t)stream);
 }
 
+// The fold of the tile partials part[batch][M/32][M/32][32][2 d] that the tiles-mode product left behind
+// (hb_matmul_gram_vjp_tiles): Xbar[batch][M][d] and ellbar[dl] (lengthscales shared by the batch), every sum in a fixed
+// order.  Chain-aware: at the head of a serial chain its loads join the chain's load phase; alone, one workgroup.
+__global__ void __launch_bounds__(1024) gram_tiles_fold_kernel(const float* __restrict__ part, long outs, long tiles_n, long d, long dl,
+                                                               float* __restrict__ Xbar, float* __restrict__ ellbar) {
+  __shared__ float smem[16];
+  hb_gram_tiles_body<float>(part, outs, tiles_n, d, dl, Xbar, ellbar, smem, HbNoMirror());
+}
+extern "C" int hb_gram_tiles_fold_f32(const float* part, long batch, long M, long d, long dl, float* Xbar, float* ellbar, void* stream) {
+  HB_REQUIRE(part && Xbar && ellbar, "hb_gram_tiles_fold: NULL pointer");
+  HB_REQUIRE(batch >= 1 && M >= 32 && M % 32 == 0 && d >= 1 && d <= HB_GRAM_TILES_MAXD && (dl == 1 || dl == d), "hb_gram_tiles_fold: bad arguments");
+  const long tiles = M / 32, elems = batch * tiles * tiles * 64 * d;
+  HB_REQUIRE(elems <= HB_CHAIN_TILES_MAX_N, "hb_gram_tiles_fold: %ld partials, more than one workgroup folds (%d)", elems, HB_CHAIN_TILES_MAX_N);
+  if (hb_chain_recording()) {
+    HbChainJob j;
+    j.kind = HB_CHAIN_GRAM_TILES;
+    j.is64 = 0;
+    j.p[0] = part, j.p[1] = Xbar, j.p[2] = ellbar;
+    j.l[0] = batch * M * 2 * d, j.l[1] = tiles, j.l[2] = d, j.l[3] = dl;   // outputs, tiles per row
+    j.span(0, elems * (long)sizeof(float), HB_CHAIN_READ);
+    j.span(1, batch * M * d * (long)sizeof(float), HB_CHAIN_WRITE), j.span(2, dl * (long)sizeof(float), HB_CHAIN_WRITE);
+    return hb_chain_push(j, (hipStream_t)stream);
+  }
+  hipLaunchKernelGGL(gram_tiles_fold_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, part, batch * M * 2 * d, tiles, d, dl, Xbar, ellbar);
+  HB_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int hb_gram_bwd_f32(int kind, const float* X, long sX, const float* X2, long sX2, const float* ell,
                                long sEll, long dl, const float* Kbar, float* Xbar, float* X2bar, float* ellbar,
                                long B, long n, long n2, long d, float* ws, void* stream) {

@@ -9,6 +9,7 @@
 #include "sgp_strip.cuh"
 #include "side_jobs.cuh"
 #include "gemm_tile.cuh"
+#include "chain.cuh"   // HB_CHAIN_TILES_MAX_N: what a serial chain loads of a tiles-mode Gram VJP
 #include "../../include/henbun_hip.h"
 
 // ===========================================================================
@@ -337,10 +338,59 @@ struct MmGramVjp {
   float* Xbar = nullptr;        // [B][M][d]
   float* ell_partial = nullptr; // [B * M][d]
   float* part = nullptr;        // [B][tiles_m][tiles_n][32][2 d]
-  unsigned* counters = nullptr; // [B][tiles_m]
+  unsigned* counters = nullptr; // [B][tiles_m]; TILES: unused
 };
 #define HB_MMG_MAXD 4
-template <bool TA, bool TB, bool SYM>
+// Tiles mode, the epilogue proper for d == D: this thread's four elements of Kbar (rows (tid >> 5) + 8 e, column tid & 31)
+// against the prefetched points -- the formulas of the last-arriver form below, element by element, and the same 32-lane
+// butterfly sums.  The 8 D sums of a thread go through each butterfly level TOGETHER: one level is one LDS-crossbar round
+// trip, and taken one sum after the other the 20 D dependent levels were 2.5 us of this launch (profiles/gram_tiles.txt).
+template <int D>
+__device__ __forceinline__ void wgk_tiles_vjp(const float (&gval)[4], const float (&pxi)[4][HB_MMG_MAXD], const float (&pxj)[HB_MMG_MAXD],
+                                              const float (&pel)[HB_MMG_MAXD], float* __restrict__ pt, int tid) {
+  float il[D], v[4][2 * D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) il[k] = 1.f / pel[k];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float dm[D], r2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      dm[k] = pxi[e][k] * il[k] - pxj[k] * il[k];
+      r2 += dm[k] * dm[k];
+    }
+    const float km = hb_exp(-0.5f * r2), kb = gval[e];
+    const float em = kb * km, gm = (kb + kb) * km;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      v[e][k] = (-dm[k] * gm) * il[k];
+      v[e][D + k] = (dm[k] * dm[k] * em) * il[k];
+    }
+  }
+#pragma unroll
+  for (int off = 16; off > 0; off >>= 1) {
+    float t[4][2 * D];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int q = 0; q < 2 * D; ++q) t[e][q] = __shfl_xor(v[e][q], off, 32);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int q = 0; q < 2 * D; ++q) v[e][q] += t[e][q];
+  }
+  if ((tid & 31) == 0) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+      for (int q = 0; q < 2 * D; ++q) pt[((tid >> 5) + 8 * e) * 2 * D + q] = v[e][q];
+  }
+}
+// TILES (instantiated for SYM == false only): the same epilogue VJP, but the tile partials are the launch's RESULT.  No
+// counter, no drain, no last arriver: the kernel boundary behind this launch publishes `part`, and the serial chain that
+// follows folds it in its load phase (hb_gram_tiles_fold, chain_bodies.cuh).  The points and lengthscales the epilogue needs
+// are requested in front of the operand loads and arrive under their round trip; S itself is stored only when a.C != NULL.
+template <bool TA, bool TB, bool SYM, bool TILES = false>
 __global__ void __launch_bounds__(256) matmul_wgk_kernel(MmArgs<float> a, int nown, HbSideJobs side, MmGramVjp gv) {
   if ((int)blockIdx.x >= nown) {   // side jobs riding on this launch (side_jobs.cuh)
     if (blockIdx.y == 0) hb_side_run(side, (int)blockIdx.x - nown);
@@ -430,6 +480,22 @@ __global__ void __launch_bounds__(256) matmul_wgk_kernel(MmArgs<float> a, int no
       }
     }
   };
+  // TILES: this thread's column point, the points of its four rows and the lengthscales (indices clamped, not branched on:
+  // a load under a condition is waited for at the end of its block)
+  float pxj[HB_MMG_MAXD], pxi[4][HB_MMG_MAXD], pel[HB_MMG_MAXD];
+  if (TILES) {
+    const int d = (int)gv.d;
+    const float* Xb = gv.X + b * gv.sX;
+    const float* eb = gv.ell + b * gv.sEll;
+#pragma unroll
+    for (int k = 0; k < HB_MMG_MAXD; ++k) {
+      const int kc = k < d ? k : 0;
+      pel[k] = eb[gv.dl == 1 ? 0 : kc];
+      pxj[k] = Xb[(long)(col0 + (tid & 31)) * d + kc];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) pxi[e][k] = Xb[(long)(row0 + (tid >> 5) + 8 * e) * d + kc];
+    }
+  }
   {
     Frag fa, fb;
     load(fa, 0);
@@ -479,9 +545,20 @@ __global__ void __launch_bounds__(256) matmul_wgk_kernel(MmArgs<float> a, int no
     if (a.beta != 0.f) v += a.beta * Cb[gr * a.ldc + gcn];
     if ((a.flags & (HB_MM_TRIL_OUT | HB_MM_PHI_OUT)) && gcn > gr) v = 0.f;
     if ((a.flags & HB_MM_PHI_OUT) && gcn == gr) v *= 0.5f;
-    Cb[gr * a.ldc + gcn] = v;
+    if (!TILES || a.C != nullptr) Cb[gr * a.ldc + gcn] = v;
   }
-  if (!SYM && gv.X) {
+  if (!SYM && TILES) {
+    // ---- the tile's share of the Gram VJP (wgk_tiles_vjp above); plain stores, the kernel boundary publishes them
+    const int d = (int)gv.d;
+    float* pt = gv.part + ((((long)b * (M / 32) + ti) * tiles_n + tj) * 32) * 2 * d;
+    switch (d) {
+      case 1: wgk_tiles_vjp<1>(gval, pxi, pxj, pel, pt, tid); break;
+      case 2: wgk_tiles_vjp<2>(gval, pxi, pxj, pel, pt, tid); break;
+      case 3: wgk_tiles_vjp<3>(gval, pxi, pxj, pel, pt, tid); break;
+      default: wgk_tiles_vjp<4>(gval, pxi, pxj, pel, pt, tid); break;
+    }
+  }
+  if (!SYM && !TILES && gv.X) {
     // ---- the tile's share of the Gram VJP: rows (tid >> 5) + 8 e, column tid & 31; 32-lane sums over the columns
     const int d = (int)gv.d, c = tid & 31;
     const float* Xb = gv.X + b * gv.sX;
@@ -580,10 +657,10 @@ bool matmul_wgk_ok<float>(const MmArgs<float>& a, long M, long N, long K, long b
 }
 template <typename T>
 static int matmul_wgk_launch(const MmArgs<T>&, int, int, hipStream_t) { return -1; }
-int matmul_wgk_launch_g(const MmArgs<float>& a, int transA, int transB, hipStream_t stream, const MmGramVjp& gv);
+int matmul_wgk_launch_g(const MmArgs<float>& a, int transA, int transB, hipStream_t stream, const MmGramVjp& gv, bool tiles = false);
 template <>
 int matmul_wgk_launch<float>(const MmArgs<float>& a, int transA, int transB, hipStream_t stream) { return matmul_wgk_launch_g(a, transA, transB, stream, MmGramVjp()); }
-int matmul_wgk_launch_g(const MmArgs<float>& a, int transA, int transB, hipStream_t stream, const MmGramVjp& gv) {
+int matmul_wgk_launch_g(const MmArgs<float>& a, int transA, int transB, hipStream_t stream, const MmGramVjp& gv, bool tiles) {
   const bool sym = (a.flags & HB_MM_SYM_OUT) != 0;
   const long nt = a.M / 32;
   const int nown = (int)(sym ? nt * (nt + 1) / 2 : (a.M / 32) * (a.N / 32));
@@ -593,6 +670,8 @@ int matmul_wgk_launch_g(const MmArgs<float>& a, int transA, int transB, hipStrea
   do {                                                                                                     \
     if (sym)                                                                                               \
       hipLaunchKernelGGL((matmul_wgk_kernel<TA_, TB_, true>), grid, dim3(256), 0, stream, a, nown, sj, gv);    \
+    else if (tiles)                                                                                        \
+      hipLaunchKernelGGL((matmul_wgk_kernel<TA_, TB_, false, true>), grid, dim3(256), 0, stream, a, nown, sj, gv); \
     else                                                                                                   \
       hipLaunchKernelGGL((matmul_wgk_kernel<TA_, TB_, false>), grid, dim3(256), 0, stream, a, nown, sj, gv);   \
   } while (0)
@@ -1392,6 +1471,35 @@ extern "C" int hb_matmul_gram_vjp_f32(const float* A, const float* B, float* C, 
   gv.X = X, gv.sX = sX, gv.ell = ell, gv.sEll = sEll, gv.dl = dl, gv.d = d;
   gv.Xbar = Xbar, gv.ell_partial = ell_partial, gv.part = part, gv.counters = counters;
   return matmul_wgk_launch_g(a, transA, transB, (hipStream_t)stream, gv);
+}
+
+// Tiles mode: the same product and epilogue VJP, the tile partials handed to hb_gram_tiles_fold across the launch boundary.
+// The rule: the last-arriver form's, plus partials that one chain workgroup loads in one phase (HB_CHAIN_TILES_MAX_N: the
+// cfg 2 size, hb_matmul_gram_vjp_ws_elems(1, 512, 1)); hb_debug_set("gram_vjp_tiles", 0) answers 0 (A/B switch).
+extern "C" int hb_matmul_gram_vjp_tiles_ok(long M, long K, long batch, long d) {
+  if (hb_debug_get("gram_vjp_tiles", 1) == 0 || !hb_matmul_gram_vjp_ok(M, K, batch, d)) return 0;
+  return hb_matmul_gram_vjp_ws_elems(batch, M, d) <= HB_CHAIN_TILES_MAX_N ? 1 : 0;
+}
+extern "C" int hb_matmul_gram_vjp_tiles_f32(const float* A, const float* B, float* C, long batch, long M, long K, long lda, long ldb,
+                                            long ldc, long sA, long sB, long sC, int transA, int transB, const float* X, long sX,
+                                            const float* ell, long sEll, long dl, long d, float* part, void* stream) {
+  HB_REQUIRE(A && B && X && ell && part, "hb_matmul_gram_vjp_tiles: NULL pointer");
+  HB_REQUIRE(hb_matmul_gram_vjp_tiles_ok(M, K, batch, d), "hb_matmul_gram_vjp_tiles: shape outside the tiles form (hb_matmul_gram_vjp_tiles_ok)");
+  HB_REQUIRE(dl == 1 || dl == d, "hb_matmul_gram_vjp_tiles: lengthscales must have 1 or d entries");
+  HB_REQUIRE(sX == 0 || sX == M * d, "hb_matmul_gram_vjp_tiles: point batch stride must be 0 or M * d");
+  HB_REQUIRE(sEll == 0 || sEll == dl, "hb_matmul_gram_vjp_tiles: lengthscale batch stride must be 0 or dl");
+  if (C == nullptr) ldc = M, sC = 0;   // S has no reader besides the epilogue: it is not stored
+  const bool aligned = ((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && ((uintptr_t)C % 16 == 0) && lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0;
+  HB_REQUIRE(aligned, "hb_matmul_gram_vjp_tiles: operands must be 16-byte aligned with leading dimensions %% 4 == 0");
+  HB_REQUIRE(lda >= (transA ? M : K) && ldb >= (transB ? K : M) && ldc >= M, "hb_matmul_gram_vjp_tiles: leading dimension too small");
+  MmArgs<float> a = {};
+  a.A = A, a.B = B, a.C = C;
+  a.M = M, a.N = M, a.K = K, a.lda = lda, a.ldb = ldb, a.ldc = ldc, a.sA = sA, a.sB = sB, a.sC = sC, a.batch = batch;
+  a.alpha = 1.f, a.beta = 0.f, a.act = HB_ACT_NONE, a.flags = 0;
+  MmGramVjp gv;
+  gv.X = X, gv.sX = sX, gv.ell = ell, gv.sEll = sEll, gv.dl = dl, gv.d = d;
+  gv.part = part;
+  return matmul_wgk_launch_g(a, transA, transB, (hipStream_t)stream, gv, true);
 }
 
 // The Gaussian likelihood head of a MatBias layer (reference nn.py:31-32 feeding densities.py:25-27 under tf.reduce_sum):

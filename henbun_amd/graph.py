@@ -988,12 +988,29 @@ def _matmul_emit(plan, node):
     # settings.runtime.gram_vjp_in_product, OFF by default: one launch less, but the tile partials' way through memory
     # (write-through, drain, counter, last arriver's loads) is a longer dependent chain than the launch it replaces --
     # cfg 2: 197.3 -> 202.4 us per step (tools/ab_step.py)
+    # Tiles mode (GRAM_TILES, on by default): the same epilogue, but the launch boundary behind the product is the hand-off
+    # -- the product leaves the tile partials, the fold at the head of the serial chain that follows (gram_grad's step)
+    # sums them inside the chain's load phase.  Kbar itself is not stored.  hb_debug_set("gram_vjp_tiles", 0): off.
     gg = cons[0] if (len(cons) == 1 and cons[0].op == "gram_grad") else None
     gp = "Gram VJP inside the product that computes Kbar (hb_matmul_gram_vjp)"
     if gg is not None and not epi and bias is None:
         from ._settings import settings as _st
         tX, tX2, tell, tg = gg.inputs
         B, BX, BX2, n, n2, d, sX, sX2, sEll, dl = _gram_layout(tX, tX2, tell)
+        pair = (wgk_like and gg.attrs.get("sym") and tg is y and node.attrs.get("sym_result") and gg.attrs["kind"] == "rbf"
+                and not (BX == 1 and B > 1) and y not in plan.outputs and y not in plan._bind and n == ysh[-1])
+        tiles = bool(pair and sEll == 0 and not getattr(_st.runtime, "gram_vjp_in_product", False)
+                     and H.matmul_gram_vjp_tiles_ok(n, kk, B, d, plan.dtype))
+        plan.note(GRAM_TILES, gg, tiles, "" if tiles else "needs the pairing of the in-product Gram VJP, lengthscales shared by the batch, at most "
+                  "16384 tile partials (hb_matmul_gram_vjp_tiles_ok) and hb_debug_set gram_vjp_tiles 1")
+        if tiles:
+            X, ell = plan.buf(tX), plan.buf(tell)
+            part = plan.scratch((H.matmul_gram_vjp_ws_elems(B, n, d),))
+            plan._gram_tiles[gg.id] = (part, B, n, d, dl)
+            plan.steps.append(lambda: H.matmul_gram_vjp_tiles(a, b, None, at["ta"], at["tb"], X, sX, ell, sEll, dl, d, part))
+            if host:
+                plan.steps.append(lambda: H.side_flush())
+            return
         ok = (bool(getattr(_st.runtime, "gram_vjp_in_product", False)) and wgk_like and gg.attrs.get("sym") and tg is y
               and node.attrs.get("sym_result") and gg.attrs["kind"] == "rbf" and not (BX == 1 and B > 1) and y not in plan.outputs
               and y not in plan._bind and n == ysh[-1] and H.matmul_gram_vjp_ok(n, kk, B, d, plan.dtype))
@@ -1610,6 +1627,7 @@ defop("tri_to_vec", lambda plan, node: (lambda a, o: plan.steps.append(lambda: p
     plan.buf(node.inputs[0]), plan.out(node.outputs[0])), lambda node, gs: [None if gs[0] is None else vec_to_tri(gs[0])])
 
 KERN_KINDS = {"rbf": 0, "csym_rbf": 1, "sqdist": 2}
+GRAM_TILES = "Gram VJP's tile partials from the product that computes Kbar, folded by the serial chain (hb_matmul_gram_vjp_tiles)"
 
 
 def gram(X, X2, ell, kind="rbf") -> Tensor:
@@ -1694,6 +1712,15 @@ def _gram_vjp(node, gs):
 
 def _gram_grad_emit(plan, node):
     H = plan.H
+    tiles = plan._gram_tiles.get(node.id)
+    if tiles is not None:
+        # the product that computed Kbar left the tile partials of this VJP (_matmul_emit): their fold, at the head of a serial chain
+        part, B_, n_, d_, dl_ = tiles
+        oX, oL = plan.out(node.outputs[0]), plan.out(node.outputs[1])
+        fold = lambda: H.gram_tiles_fold(part, B_, n_, d_, dl_, oX, oL)
+        plan.steps.append(fold)
+        plan.chain_kind[id(fold)] = "full"
+        return
     fused = plan._gram_in_mm.get(node.id)
     if fused is not None:
         # the point gradient and the lengthscale row partials came out of the product that computed Kbar (_matmul_emit)
@@ -2649,6 +2676,7 @@ class Plan:
         # the columns of G while it streams them, and the stand-alone reduction launches (two per layer) disappear.
         self._gram_for_chol: Dict[int, tuple] = {}   # cholesky node id -> (points, lengthscales, kind, jitter) of its folded Gram
         self._gram_in_mm: Dict[int, tuple] = {}      # gram_grad node id -> (lengthscale partials, rows, d, dl, groups): set by _matmul_emit
+        self._gram_tiles: Dict[int, tuple] = {}      # gram_grad node id -> (tile partials, batch, M, d, dl): set by _matmul_emit
         self._chol_rider: Dict[Tensor, dict] = {}    # inverse tensor -> the persistent factorisation step's rider cell (_cholesky_emit)
         self.step_riders: Dict[int, Node] = {}       # id(step closure) -> node whose work rides in that step's launch
         self._mlp2: Dict[int, dict] = {}             # mlp2_sample_kl node id -> {fused, ws | h}

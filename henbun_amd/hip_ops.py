@@ -1004,6 +1004,32 @@ def gram_ell_fold(partial, rows, d, dl, groups, ellbar):
     _lib.lib().call("hb_gram_ell_fold" + _suf(partial), _p(partial), int(rows), int(d), int(dl), int(groups), _p(ellbar), stream())
 
 
+def matmul_gram_vjp_tiles_ok(M, K, batch, d, dtype):
+    """The square product can leave the tile partials of its result's Gram VJP for gram_tiles_fold
+    (hb_matmul_gram_vjp_tiles_ok; hb_debug_set("gram_vjp_tiles", 0) answers no)."""
+    if dtype != torch.float32:
+        return False
+    return bool(_lib.lib().raw("hb_matmul_gram_vjp_tiles_ok")(int(M), int(K), int(batch), int(d)))
+
+
+def matmul_gram_vjp_tiles(a, b, out, transA, transB, X, sX, ell, sEll, dl, d, part):
+    """The tile partials `part` of the one-pass symmetric Gram VJP of op(a) op(b) as Kbar, from the product's own launch
+    (hb_matmul_gram_vjp_tiles_f32).  out: the product itself, or None when nothing else reads it."""
+    M = a.shape[-1] if transA else a.shape[-2]
+    K = a.shape[-2] if transA else a.shape[-1]
+    batch = a.numel() // (M * K) if a.dim() == 3 else (b.numel() // (M * K) if b.dim() == 3 else 1)
+    sA = a.stride(0) if a.dim() == 3 and a.shape[0] > 1 else 0
+    sB = b.stride(0) if b.dim() == 3 and b.shape[0] > 1 else 0
+    _lib.lib().call("hb_matmul_gram_vjp_tiles_f32", _p(a), _p(b), _p(out) if out is not None else None, batch, M, K, a.stride(-2),
+                    b.stride(-2), out.stride(-2) if out is not None else M, sA, sB, M * M, int(bool(transA)), int(bool(transB)),
+                    _p(X), int(sX), _p(ell), int(sEll), int(dl), int(d), _p(part), stream())
+
+
+def gram_tiles_fold(part, batch, M, d, dl, xbar, ellbar):
+    """xbar and ellbar from the tile partials of matmul_gram_vjp_tiles (hb_gram_tiles_fold_f32; chain-aware)."""
+    _lib.lib().call("hb_gram_tiles_fold_f32", _p(part), int(batch), int(M), int(d), int(dl), _p(xbar), _p(ellbar), stream())
+
+
 def matmul_gauss_units(n, K, N, dtype):
     """Partial-sum units of hb_matmul_gauss for an [n, K] x [K, N] MatBias layer feeding a Gaussian head (0: not this shape)."""
     if dtype != torch.float32:

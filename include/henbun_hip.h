@@ -64,7 +64,9 @@ extern "C" {
  * hb_sgp_pathwise_acq_ws_elems and the enum values HB_PWACQ_* (batch acquisition from pathwise function draws);
  * hb_matmul_form and the enum values HB_MM_FORM_* (which kernel form, slab count and operand path hb_matmul_* takes for
  * a call: a host-side query that launches nothing); hb_gram_predict_f32 / _f64 and hb_gram_predict_ws_elems (exact GP:
- * predictive mean, cached upper bound of the predictive variance and closed-form acquisition from one kernel product). */
+ * predictive mean, cached upper bound of the predictive variance and closed-form acquisition from one kernel product);
+ * hb_matmul_gram_vjp_tiles_ok / _tiles_f32 and hb_gram_tiles_fold_f32 (the Gram VJP's tile partials from the product that
+ * computes Kbar, folded at the head of a serial chain). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -78,7 +80,8 @@ const char* hb_last_error_string(void);
  * only, the outputs are then meaningless), sgp_stats_target_wg (tiles x K-splits aimed at; hb_sgp_stats_ws_elems follows), sgp_select_block (64 / 256: the workgroup
  * size of hb_sgp_select_*; the results do not depend on it), sgp_kgrad_plain (hb_sgp_kgrad_* in its plain-loop form for
  * every shape), sgp_phi_direct (0: hb_sgp_bwd_phi_supported answers 0, so a plan built then keeps hb_sgp_bwd and the
- * Cholesky VJP's first product).  hb_debug_clear() drops every entry. */
+ * Cholesky VJP's first product), gram_vjp_tiles (0: hb_matmul_gram_vjp_tiles_ok answers 0, so a plan built then runs the
+ * Gram VJP of K(z, z) as launches of its own).  hb_debug_clear() drops every entry. */
 int hb_debug_set(const char* key, long value);
 int hb_debug_clear(void);
 /* device name / arch of the current device into (host) buf; returns 0 or hipError */
@@ -592,6 +595,18 @@ int hb_matmul_gram_vjp_f32(const float* A, const float* B, float* C, long batch,
                            float* part, unsigned* counters, void* stream);
 int hb_gram_ell_fold_f32(const float* partial, long rows, long d, long dl, long groups, float* ellbar, void* stream);
 int hb_gram_ell_fold_f64(const double* partial, long rows, long d, long dl, long groups, double* ellbar, void* stream);
+/* The same product and epilogue VJP with the launch boundary as the hand-off ("tiles mode"): the launch leaves only the tile
+ * partials part[batch][M/32][M/32][32][2 d] (hb_matmul_gram_vjp_ws_elems; plain stores, no counters), and
+ * hb_gram_tiles_fold_f32 sums them, every sum in a fixed order, into Xbar[batch, M, d] and ellbar[dl] (lengthscales shared
+ * by the batch).  The fold is chain-aware: at the head of a serial chain its loads join the chain's one load phase.
+ * C may be NULL: S is then not stored (its only reader was the epilogue).  hb_matmul_gram_vjp_tiles_ok: the rule of
+ * hb_matmul_gram_vjp_ok and at most 16384 partials (one chain workgroup, 16 per thread); 0 under
+ * hb_debug_set("gram_vjp_tiles", 0). */
+int hb_matmul_gram_vjp_tiles_ok(long M, long K, long batch, long d);
+int hb_matmul_gram_vjp_tiles_f32(const float* A, const float* B, float* C, long batch, long M, long K, long lda, long ldb,
+                                 long ldc, long sA, long sB, long sC, int transA, int transB, const float* X, long sX,
+                                 const float* ell, long sEll, long dl, long d, float* part, void* stream);
+int hb_gram_tiles_fold_f32(const float* part, long batch, long M, long d, long dl, float* Xbar, float* ellbar, void* stream);
 /* The Gaussian likelihood head of a MatBias layer in the layer's own launch (round 4; reference nn.py:31-32 feeding
  * densities.py:25-27 under tf.reduce_sum): f = A[n, K] B[K, N] + bias[N] is consumed in the epilogue of the row-streaming
  * product and never written -- dmu[n, N] = (y - f s) / var, fbar = s (post dmu) when fbar != NULL, and one partial triple
