@@ -2632,11 +2632,12 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
 
 // ---------------------------------------------------------------------------------------------------------------
 // Lbar = -tril(Kbar A^T) from the FRAGMENT-MAJOR Kbar and A that the strip kernels leave (contraction over the data
-// axis, M^2 n flops on the lower tiles).  Workgroup = one 32 x 32 output tile (t >= t') x one slab of 32 strips; its
-// eight waves take four strips each -- all eight operand loads of a wave are issued before its 64 MFMAs, and every
-// load is one contiguous kilobyte -- and meet in LDS; the workgroup writes ONE partial tile.  sgp_lbar_finish_kernel
-// sums the slabs (fixed order), negates and clears the upper triangle.  Replaces the LDS-staged split-K GEMM over
-// the row-major operands (36.8 + 5.4 us at cfg 2, 33 % of its LDS cycles bank conflicts).
+// axis, M^2 n flops on the lower tiles).  Workgroup = one 64 x 64 output block (2 x 2 tiles, on or below the
+// diagonal) x one of S slabs of the data axis; its four waves split the slab, each walks its share in groups of four
+// quarter-strips (8 data columns, one contiguous kilobyte per tile: 16 loads in flight under the 64 MFMAs of the
+// group before), and they meet in LDS: the workgroup writes ONE partial block.  sgp_bwd_finish_kernel sums the slabs
+// (fixed order), negates and clears the upper triangle.  Replaces the LDS-staged split-K GEMM over the row-major
+// operands (36.8 + 5.4 us at cfg 2, 33 % of its LDS cycles bank conflicts).
 // ---------------------------------------------------------------------------------------------------------------
 #ifndef HB_LSTAMP
 #define HB_LSTAMP(i)
@@ -2645,15 +2646,19 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
 // (285 MB out of L2 at cfg 2 for 33.5 MB of operands) -- not the MFMAs -- set the time (32-41 us in two variants).
 // A WAVE therefore owns a 64 x 64 block (2 x 2 tiles, four accumulators): per strip it loads two Kbar and two A
 // fragment sets (16 contiguous-kilobyte loads) for 64 MFMAs, halving the bytes per flop; the four waves of a
-// workgroup split a slab of strips and meet in LDS; S slabs give ~2 waves per SIMD.  On the diagonal blocks the
-// tile above the diagonal is skipped.
+// workgroup split a slab and meet in LDS; S slabs give one workgroup per CU.  On the diagonal blocks the tile above
+// the diagonal is skipped.  Every workgroup is resident at once, so the launch lasts as long as its longest wave: the
+// split is made in quarter-strips (`gran` = 1), not whole strips (`gran` = 4: 640 MFMAs on the longest wave of cfg 2
+// against a mean of 544; 592 in quarter-strips), which the fragment-major layout allows at any alignment.
 template <bool BF3>
 __global__ void __launch_bounds__(256) sgp_lbar_frag_kernel(const float* __restrict__ Kf, const float* __restrict__ Af,
                                                             float* __restrict__ slabs, int M, int nS, int S, long E,
-                                                            int pairs) {
+                                                            int pairs, int gran) {
   typedef __bf16 B8 __attribute__((ext_vector_type(8)));
   typedef float V4 __attribute__((ext_vector_type(4)));
   typedef Mma<float> MM;
+  typedef std::integral_constant<bool, true> Yes;
+  typedef std::integral_constant<bool, false> No;
   __shared__ float red[4][32][33];   // one tile at a time (16.5 KB: several workgroups per CU)
   const int nT = M / 32, nB = (nT + 1) / 2;             // 64-row blocks (the last one may hold a single tile)
   // XCD-aware unit order: workgroup w runs on XCD w % 8 (round-robin dispatch), each XCD has its own L2, and the
@@ -2673,10 +2678,14 @@ __global__ void __launch_bounds__(256) sgp_lbar_frag_kernel(const float* __restr
   const int bj = pair - bi * (bi + 1) / 2;
   (void)nB;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int base = nS / S, rem = nS % S;
+  // K-split: the 4 nS quarter-strips are dealt out in units of `gran` of them (4: whole strips), first to the slabs,
+  // then to the four waves of the workgroup, the remainders to the first ones.  Wave range: quarter-strips [q0, q1).
+  const int nU = 4 * nS / gran;
+  const int base = nU / S, rem = nU % S;
   const int sb = slab * base + (slab < rem ? slab : rem), se = sb + base + (slab < rem ? 1 : 0);
   const int cnt = se - sb, wq = cnt / 4, wr = cnt % 4;
-  const int s0 = sb + w * wq + (w < wr ? w : wr), s1 = s0 + wq + (w < wr ? 1 : 0);
+  const int u0 = sb + w * wq + (w < wr ? w : wr);
+  const int q0 = gran * u0, q1 = gran * (u0 + wq + (w < wr ? 1 : 0));
   // tiles of the block: rows 2bi, 2bi+1 (the second may not exist), columns 2bj, 2bj+1
   const int ti0 = 2 * bi, ti1 = 2 * bi + 1 < nT ? 2 * bi + 1 : ti0, tj0 = 2 * bj, tj1 = 2 * bj + 1 < nT ? 2 * bj + 1 : tj0;
   const bool has_i1 = 2 * bi + 1 < nT, has_j1 = 2 * bj + 1 < nT;
@@ -2694,48 +2703,72 @@ __global__ void __launch_bounds__(256) sgp_lbar_frag_kernel(const float* __restr
     struct Frag {
       V4 a0[4], a1[4], b0[4], b1[4];
     };
-    auto load = [&](Frag& f, int sidx) {
-      const int sc = sidx < s1 ? sidx : (s1 > s0 ? s1 - 1 : s0);
-      const long off = (long)sc << 10;
+    // A group is four consecutive quarter-strips from g on (any alignment: quarter-strip q of a tile is the contiguous
+    // kilobyte at 256 q).  A range that is no multiple of four starts with a short group of `tail` quarter-strips, so
+    // the pipelined loop sees whole groups only; loads past the end re-read the last quarter-strip (never used).
+    const int tail = (q1 - q0) & 3, qf = q0 + tail;
+    auto load_quarter = [&](Frag& f, int v, int q) {
+      const int qc = q < q1 ? q : q1 - 1;
+      const long off = (long)qc << 8;
+      f.a0[v] = *reinterpret_cast<const V4*>(kbase + ti0 * tstride + off);
+      f.a1[v] = *reinterpret_cast<const V4*>(kbase + ti1 * tstride + off);
+      f.b0[v] = *reinterpret_cast<const V4*>(abase + tj0 * tstride + off);
+      f.b1[v] = *reinterpret_cast<const V4*>(abase + tj1 * tstride + off);
+    };
+    auto load = [&](Frag& f, int g) {
 #pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        f.a0[v] = *reinterpret_cast<const V4*>(kbase + ti0 * tstride + off + 256 * v);
-        f.a1[v] = *reinterpret_cast<const V4*>(kbase + ti1 * tstride + off + 256 * v);
-        f.b0[v] = *reinterpret_cast<const V4*>(abase + tj0 * tstride + off + 256 * v);
-        f.b1[v] = *reinterpret_cast<const V4*>(abase + tj1 * tstride + off + 256 * v);
+      for (int v = 0; v < 4; ++v) load_quarter(f, v, g + v);
+    };
+    // one quarter-strip: the accumulators take turns, each in the order (v, s2) of its own
+    auto quarter = [&](const Frag& f, int v, auto four) {
+#pragma unroll
+      for (int s2 = 0; s2 < 4; ++s2) {
+        acc[0] = MM::mma(f.a0[v][s2], f.b0[v][s2], acc[0]);
+        if (decltype(four)::value) acc[1] = MM::mma(f.a0[v][s2], f.b1[v][s2], acc[1]);
+        acc[2] = MM::mma(f.a1[v][s2], f.b0[v][s2], acc[2]);
+        acc[3] = MM::mma(f.a1[v][s2], f.b1[v][s2], acc[3]);
       }
     };
-    auto compute = [&](const Frag& f, int sidx) {
-      if (sidx >= s1) return;  // uniform
+    auto compute = [&](const Frag& f, auto four) {
 #pragma unroll
-      for (int v = 0; v < 4; ++v)
-#pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2) {
-          acc[0] = MM::mma(f.a0[v][s2], f.b0[v][s2], acc[0]);
-          acc[2] = MM::mma(f.a1[v][s2], f.b0[v][s2], acc[2]);
-          acc[3] = MM::mma(f.a1[v][s2], f.b1[v][s2], acc[3]);
-        }
-      if (!upper01) {   // (uniform; kept out of the MFMA stream above)
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-#pragma unroll
-          for (int s2 = 0; s2 < 4; ++s2) acc[1] = MM::mma(f.a0[v][s2], f.b1[v][s2], acc[1]);
-      }
+      for (int v = 0; v < 4; ++v) quarter(f, v, four);
     };
-    if (s1 > s0) {
+    auto walk = [&](auto four) {
       Frag fa, fb;
-      load(fa, s0);
-#pragma nounroll
-      for (int sidx = s0; sidx < s1; sidx += 2) {
-        load(fb, sidx + 1);
+      {
+        Frag ft;
+#pragma unroll
+        for (int v = 0; v < 3; ++v)
+          if (v < tail) load_quarter(ft, v, q0 + v);   // (uniform)
+        load(fa, qf);
         __builtin_amdgcn_sched_barrier(0);
-        compute(fa, sidx);
-        __builtin_amdgcn_sched_barrier(0);
-        load(fa, sidx + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(fb, sidx + 1);
+#pragma unroll
+        for (int v = 0; v < 3; ++v)
+          if (v < tail) quarter(ft, v, four);
         __builtin_amdgcn_sched_barrier(0);
       }
+      // Two whole groups per round, neither compute under a condition of its own: a guarded one takes the loads of its
+      // operands into its block with it, and they are then waited for where they are issued (no prefetch).
+      int g = qf;
+#pragma nounroll
+      for (; g + 8 <= q1; g += 8) {
+        load(fb, g + 4);
+        __builtin_amdgcn_sched_barrier(0);
+        compute(fa, four);
+        __builtin_amdgcn_sched_barrier(0);
+        load(fa, g + 8);
+        __builtin_amdgcn_sched_barrier(0);
+        compute(fb, four);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (g < q1) compute(fa, four);   // an odd group is left: requested by the last round (or before the first)
+    };
+    if (q1 > q0) {
+      // (one choice per workgroup: a diagonal block has no tile (ti0, tj1) and keeps three accumulators)
+      if (upper01)
+        walk(No());
+      else
+        walk(Yes());
     }
   } else {
     // bf16x3 operands: three bf16 planes per operand (written by the strip kernels), six cross products per k16-step
@@ -2745,18 +2778,24 @@ __global__ void __launch_bounds__(256) sgp_lbar_frag_kernel(const float* __restr
     struct Frag3 {
       B8 a0[3][2], a1[3][2], b0[3][2], b1[3][2];
     };
-    auto load = [&](Frag3& f, int sidx) {
-      const int sc = sidx < s1 ? sidx : (s1 > s0 ? s1 - 1 : s0);
-      const long off = (long)sc << 10;
+    // One MFMA takes 16 data columns here, so the finest unit is the HALF-strip (the launcher keeps `gran` even: q0, q1
+    // and every group start are even); half-strip hq of a tile is the contiguous kilobyte at 512 hq of each plane.  A
+    // range of an odd number of half-strips starts with a single one.
+    const int tail = (q1 - q0) & 2, qf = q0 + tail;
+    auto load_half = [&](Frag3& f, int q, int g) {
+      const int hc = g < q1 ? g >> 1 : (q1 >> 1) - 1;
+      const long off = (long)hc << 9;
 #pragma unroll
-      for (int p = 0; p < 3; ++p)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          f.a0[p][q] = *reinterpret_cast<const B8*>(k3 + p * plane + ti0 * tstride + off + 512 * q);
-          f.a1[p][q] = *reinterpret_cast<const B8*>(k3 + p * plane + ti1 * tstride + off + 512 * q);
-          f.b0[p][q] = *reinterpret_cast<const B8*>(a3 + p * plane + tj0 * tstride + off + 512 * q);
-          f.b1[p][q] = *reinterpret_cast<const B8*>(a3 + p * plane + tj1 * tstride + off + 512 * q);
-        }
+      for (int p = 0; p < 3; ++p) {
+        f.a0[p][q] = *reinterpret_cast<const B8*>(k3 + p * plane + ti0 * tstride + off);
+        f.a1[p][q] = *reinterpret_cast<const B8*>(k3 + p * plane + ti1 * tstride + off);
+        f.b0[p][q] = *reinterpret_cast<const B8*>(a3 + p * plane + tj0 * tstride + off);
+        f.b1[p][q] = *reinterpret_cast<const B8*>(a3 + p * plane + tj1 * tstride + off);
+      }
+    };
+    auto load = [&](Frag3& f, int g) {
+      load_half(f, 0, g);
+      load_half(f, 1, g + 2);
     };
     auto six = [&](const B8 (&x)[3][2], const B8 (&y)[3][2], int q, typename MM::Acc c) {
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[2][q], y[0][q], c, 0, 0, 0);
@@ -2767,30 +2806,36 @@ __global__ void __launch_bounds__(256) sgp_lbar_frag_kernel(const float* __restr
       c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0][q], y[0][q], c, 0, 0, 0);
       return c;
     };
-    auto compute = [&](const Frag3& f, int sidx) {
-      if (sidx >= s1) return;  // uniform
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        acc[0] = six(f.a0, f.b0, q, acc[0]);
-        acc[2] = six(f.a1, f.b0, q, acc[2]);
-        acc[3] = six(f.a1, f.b1, q, acc[3]);
-        if (!upper01) acc[1] = six(f.a0, f.b1, q, acc[1]);
-      }
+    auto half = [&](const Frag3& f, int q) {
+      acc[0] = six(f.a0, f.b0, q, acc[0]);
+      acc[2] = six(f.a1, f.b0, q, acc[2]);
+      acc[3] = six(f.a1, f.b1, q, acc[3]);
+      if (!upper01) acc[1] = six(f.a0, f.b1, q, acc[1]);
     };
-    if (s1 > s0) {
+    auto compute = [&](const Frag3& f) {
+      half(f, 0);
+      half(f, 1);
+    };
+    if (q1 > q0) {
       Frag3 fa, fb;
-      load(fa, s0);
+      if (tail) load_half(fb, 0, q0);   // (uniform)
+      load(fa, qf);
+      __builtin_amdgcn_sched_barrier(0);
+      if (tail) half(fb, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      int g = qf;   // (two whole groups per round and an odd one after the loop, as in the fp32 walk)
 #pragma nounroll
-      for (int sidx = s0; sidx < s1; sidx += 2) {
-        load(fb, sidx + 1);
+      for (; g + 8 <= q1; g += 8) {
+        load(fb, g + 4);
         __builtin_amdgcn_sched_barrier(0);
-        compute(fa, sidx);
+        compute(fa);
         __builtin_amdgcn_sched_barrier(0);
-        load(fa, sidx + 2);
+        load(fa, g + 8);
         __builtin_amdgcn_sched_barrier(0);
-        compute(fb, sidx + 1);
+        compute(fb);
         __builtin_amdgcn_sched_barrier(0);
       }
+      if (g < q1) compute(fa);
     }
   }
   HB_LSTAMP(1);
@@ -3406,13 +3451,16 @@ static int sgp_lbar_frag_launch(const float* Kf, const float* Af, float* slabs, 
       }
     }
   }
+  // unit of the K-split in quarter-strips: 1, or 4 = whole strips (A/B switch); a bf16x3 MFMA takes a half-strip
+  int gran = hb_debug_get("lbar_gran", 1) == 4 ? 4 : 1;
+  if (prec == HB_PREC_BF16X3 && gran < 2) gran = 2;
   dim3 grid((unsigned)(pairs * S * E), 1, 1);
   if (prec == HB_PREC_BF16X3)
     hipLaunchKernelGGL(sgp_lbar_frag_kernel<true>, grid, dim3(256), 0, stream, Kf, Af, slabs, (int)M, (int)nS, (int)S, E,
-                       (int)pairs);
+                       (int)pairs, gran);
   else
     hipLaunchKernelGGL(sgp_lbar_frag_kernel<false>, grid, dim3(256), 0, stream, Kf, Af, slabs, (int)M, (int)nS, (int)S, E,
-                       (int)pairs);
+                       (int)pairs, gran);
   HB_LAUNCH_CHECK();
   *S_out = (int)S;
   return 0;
