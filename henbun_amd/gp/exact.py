@@ -375,7 +375,8 @@ class ExactPosterior:
     """The exact GP posterior given (X, Y) at fixed hyper-parameters (GP.condition): a snapshot, like PathwiseDraws, of X
     [N, d], the lengthscales, k_var, noise_var, alpha = K^^-1 Y [P, N], the preconditioner and the solve's `info`, on the
     device in the session's dtype.  Later changes to the model do not move it.  build_cache() adds a VarianceCache:
-    predict_f(var='cache'), acquisition and argmax then cost ONE kernel product over the candidates, however many."""
+    predict_f(var='cache'), acquisition and argmax then cost ONE kernel product over the candidates, however many, and
+    predict_grad, acquisition(grad=True) and maximise add their exact input gradients at 1 + d times that product."""
 
     KINDS = ("ei", "pi", "ucb")
 
@@ -469,14 +470,31 @@ class ExactPosterior:
             raise ValueError("%s: var_floor >= 0 expected (got %r)" % (who, var_floor))
         return dict(acq=kind, best=0.0 if best is None else float(best), param=float(param), var_floor=var_floor)
 
-    def acquisition(self, X, kind, best=None, param=0.0, largest=True, var_floor=None):
+    def _cached_grad(self, Xn, **kw):
+        P = self._alpha.shape[0]
+        return self._sess.H.gram_predict_grad(Xn, self._X, self._ell, self._V, P=P, scale=self.k_var, prior=self.k_var, **kw)
+
+    def predict_grad(self, X):
+        """(mean [P, n], var_upper [n], dmean [P, n, d], dvar [n, d]) as numpy: the moments of predict_f(X, var='cache'),
+        bit for bit, and their exact input gradients dmean[p, j, k] = d mean[p, j] / d x_jk from ONE hb_gram_predict_grad
+        pass (build_cache() first, else ValueError).  dvar is exactly 0 where the bound was clamped to 0."""
+        self._need_cache("predict_grad")
+        mean, v, _, dmean, dvar, _ = self._cached_grad(self._new_points(X))
+        return mean.cpu().numpy(), v.cpu().numpy(), dmean.cpu().numpy(), dvar.cpu().numpy()
+
+    def acquisition(self, X, kind, best=None, param=0.0, largest=True, var_floor=None, grad=False):
         """The closed-form acquisition `kind` ('ei', 'pi': param = xi, improvement over `best`; 'ucb': param = beta) at
         the rows of X, as numpy [n], from the exact mean and the CACHED variance bound (build_cache() first): ONE
         hb_gram_predict pass, the tail of SparsePosterior.acquisition per point in double.  For maximising f (largest) or
         minimising it; sigma^2 = max(var_upper, var_floor), var_floor=None: k_var * jitter_level as there.  The bound
-        makes sigma conservative: exploration is never under-weighted.  One latent function only; no input gradient
-        yet (the gradient of the cached variance is the follow-up)."""
+        makes sigma conservative: exploration is never under-weighted.  One latent function only.  grad=True: (values
+        [n], gradient [n, d]), the exact input gradient from ONE hb_gram_predict_grad pass (the same value bits); where
+        the variance was clamped the gradient does not pass through it."""
         args = self._acq_args("acquisition", kind, best, param, var_floor)
+        if grad:
+            _, _, val, _, _, g = self._cached_grad(self._new_points(X), largest=bool(largest), mean=False, var=False, dmean=False,
+                                                   dvar=False, **args)
+            return val.cpu().numpy(), g.cpu().numpy()
         _, _, val, _, _ = self._cached(self._new_points(X), largest=bool(largest), mean=False, var=False, value=True, **args)
         return val.cpu().numpy()
 
@@ -490,6 +508,48 @@ class ExactPosterior:
             raise ValueError("argmax: at least one candidate expected")
         _, _, _, bv, bi = self._cached(Xd, largest=bool(largest), mean=False, var=False, value=False, argmax=True, **args)
         return int(bi.cpu().numpy()[0]), self._sess.np_dtype(bv.cpu().numpy()[0])
+
+    def maximise(self, X, kind, best=None, param=0.0, largest=True, var_floor=None, steps=50, lr=0.05, bounds=None, starts=None):
+        """(x_best [R, d], a_best [R], info): the acquisition maximised over the box `bounds` by `steps` steps of projected
+        Adam ascent on its exact input gradient, from its best candidate among the rows of X (R = 1, found by argmax), or
+        from every row of starts [R, d].  The contract of SparsePosterior.maximise: the optimiser runs on the host in
+        float64, in lengthscale units so that lr is a fraction of a lengthscale, each evaluation ONE
+        hb_gram_predict_grad pass at the R current points rounded to the session's dtype; bounds = (lo [d], hi [d]),
+        default the per-column minimum and maximum of X.  The best (value, point) seen is kept, the start included:
+        a_best is never below the start's value and is the bits of acquisition(x_best).  info = dict(start_idx (None
+        with starts), start_value [R], steps).  steps < 0, lr <= 0, malformed bounds or starts and X of another width
+        raise ValueError."""
+        sess = self._sess
+        args = self._acq_args("maximise", kind, best, param, var_floor)
+        Xd = self._new_points(X)
+        d, dt = int(Xd.shape[1]), np.dtype(sess.np_dtype).type
+        steps = int(steps)
+        if steps < 0 or not float(lr) > 0.0:
+            raise ValueError("maximise: steps >= 0 and lr > 0 expected (got %r, %r)" % (steps, lr))
+        if Xd.shape[0] < 1:
+            raise ValueError("maximise: at least one candidate expected")
+        box = _host.ascent_box("maximise", Xd, bounds, d, dt)
+        ell = np.broadcast_to(np.asarray(self._ell.cpu().numpy(), np.float64), (d,))
+
+        def evaluate(xc):
+            _, _, val, _, _, g = self._cached_grad(_host.upload(sess, xc), largest=bool(largest), mean=False, var=False,
+                                                   dmean=False, dvar=False, **args)
+            return val.cpu().numpy(), g.cpu().numpy().astype(np.float64)
+
+        if starts is None:
+            _, _, _, bv, bi = self._cached(Xd, largest=bool(largest), mean=False, var=False, value=False, argmax=True, **args)
+            idx, f0 = bi.cpu().numpy(), bv.cpu().numpy().astype(dt)   # (best_val is the value's bits, widened)
+            if idx[0] < 0:
+                raise ValueError("maximise: the acquisition has no comparable value among the candidates")
+            x = Xd[bi].cpu().numpy()
+        else:
+            x = np.ascontiguousarray(np.asarray(starts, dtype=dt))
+            if x.ndim != 2 or x.shape[1] != d or x.shape[0] < 1:
+                raise ValueError("maximise: starts [R, %d] expected, got %s" % (d, x.shape))
+            idx, f0 = None, evaluate(x)[0]
+        info = dict(start_idx=idx, start_value=f0.copy(), steps=steps)
+        x_best, a_best = _host.adam_ascent(evaluate, x, f0, ell, box, 1.0, steps, float(lr), dt)
+        return x_best, a_best, info
 
     def sample_functions(self, num_samples, num_features=1024, seed=0, noise=None):
         """num_samples posterior FUNCTION draws as a PathwiseDraws with z = X, M = N (pathwise conditioning on the data

@@ -1618,6 +1618,87 @@ def gram_predict(x, x2, ell, V, P=1, scale=1.0, prior=1.0, acq=None, best=0.0, p
             torch.as_tensor([bj], dtype=torch.int64).to(dev))
 
 
+def gram_predict_grad_ws_elems(dtype, n, N, d, S):
+    """Scratch elements hb_gram_predict_grad needs: 1 + d times the min(chunks, 16) x S x n partials of gram_predict and,
+    beyond 16 chunks, 1 + d times S n doubles; no arg-max partials."""
+    return int(_lib.lib().raw("hb_gram_predict_grad_ws_elems")(int(n), int(N), int(d), int(S), _elem_bytes(dtype)))
+
+
+def _gram_predict_grad_piece(n, N, d, S, dtype):
+    """Columns per call of gram_predict_grad: as _gram_predict_piece, for its workspace."""
+    if gram_predict_grad_ws_elems(dtype, n, N, d, S) * _elem_bytes(dtype) <= GRAM_PREDICT_WS_BYTES:
+        return max(n, 1)
+    per128 = gram_predict_grad_ws_elems(dtype, 128, N, d, S) * _elem_bytes(dtype)
+    return max(int(GRAM_PREDICT_WS_BYTES) // per128, 1) * 128
+
+
+def gram_predict_grad(x, x2, ell, V, P=1, scale=1.0, prior=1.0, acq=None, best=0.0, param=0.0, largest=True, var_floor=0.0,
+                      mean=True, var=True, value=None, dmean=True, dvar=True, dvalue=None, kind=KERN_RBF):
+    """gram_predict's outputs and their input gradients from ONE kernel product (hb_gram_predict_grad).  Operands and the
+    tail's arguments as for gram_predict.  With t as there and u[s, j, k] = d t[s, j] / d x_jk held in double the same way:
+    dmean [P, n, d] = u[:P], dvar [n, d] = -2 sum_{s >= P} t[s] u[s] (exactly 0 where the variance was clamped to 0 and
+    without cache rows), dval [n, d] = sgn a_mu u[0] + a_v (-2 sum ..) with a_mu, a_v the derivatives of the tail (a_v = 0
+    where var_floor clamps); an acquisition needs P == 1.  Returns (mean, var, val, dmean, dvar, dval) device tensors, None
+    for each output not asked for (value / dvalue = None: exactly when an acquisition is given); mean, var and val are the
+    bits of gram_predict.  A column's results do not depend on the other columns: x is cut into pieces of a multiple of
+    128 columns so that the workspace stays under GRAM_PREDICT_WS_BYTES, and the bits are those of one call."""
+    who = "gram_predict_grad"
+    for t in (x, x2, ell, V):
+        _chk(t)
+    if x.dim() != 2 or V.dim() != 2 or ell.dim() != 1 or x2.dim() != 2 or x2.shape[1] != x.shape[1]:
+        raise ValueError("%s: x [n, d], x2 [N, d], ell [1] or [d], V [S, N] expected, got %s %s %s %s"
+                         % (who, tuple(x.shape), tuple(x2.shape), tuple(ell.shape), tuple(V.shape)))
+    (n, d), N, S, P = x.shape, x2.shape[0], V.shape[0], int(P)
+    if V.shape[1] != N or N < 1 or ell.numel() not in (1, d):
+        raise ValueError("%s: V must hold N = %d >= 1 columns and ell 1 or %d entries, got %s %s"
+                         % (who, N, d, tuple(V.shape), tuple(ell.shape)))
+    if any(t.dtype != x.dtype for t in (x2, ell, V)):
+        raise TypeError("%s: all operands must share one dtype" % who)
+    if not 1 <= P <= S:
+        raise ValueError("%s: 1 <= P <= S mean rows expected, got P=%d, S=%d" % (who, P, S))
+    if acq is None:
+        code = -1
+        if value or dvalue:
+            raise ValueError("%s: value and dvalue need an acquisition" % who)
+        value = dvalue = False
+    else:
+        code = ACQ.get(acq, None) if isinstance(acq, str) else acq
+        if code not in ACQ.values():
+            raise ValueError("%s: acq must be one of %s, got %r" % (who, sorted(ACQ), acq))
+        if P != 1:
+            raise ValueError("%s: an acquisition is defined for one latent function only (P=%d)" % (who, P))
+        if not float(var_floor) >= 0.0:
+            raise ValueError("%s: var_floor >= 0 expected (got %r)" % (who, var_floor))
+        value = True if value is None else bool(value)
+        dvalue = True if dvalue is None else bool(dvalue)
+    if not (mean or var or value or dmean or dvar or dvalue):
+        raise ValueError("%s: at least one of mean, var, value, dmean, dvar, dvalue expected" % who)
+    dt, dev = x.dtype, x.device
+    piece = _gram_predict_grad_piece(n, N, d, S, dt)
+    o_mean = _empty((P, n), dtype=dt, device=dev) if mean else None
+    o_var = _empty((n,), dtype=dt, device=dev) if var else None
+    o_val = _empty((n,), dtype=dt, device=dev) if value else None
+    o_dmean = _empty((P, n, d), dtype=dt, device=dev) if dmean else None
+    o_dvar = _empty((n, d), dtype=dt, device=dev) if dvar else None
+    o_dval = _empty((n, d), dtype=dt, device=dev) if dvalue else None
+    ws = workspace(dt, dev, max(gram_predict_grad_ws_elems(dt, min(n, piece), N, d, S), 1))
+    cut = lambda t, a, b: None if t is None else t[a:b]
+    for a in range(0, n, piece):
+        b = min(a + piece, n)
+        whole = a == 0 and b == n
+        m_p = o_mean if whole or not mean else _empty((P, b - a), dtype=dt, device=dev)
+        dm_p = o_dmean if whole or not dmean else _empty((P, b - a, d), dtype=dt, device=dev)
+        _lib.lib().call("hb_gram_predict_grad" + _suf(x), int(kind), _p(x[a:b]), _p(x2), _p(ell), ell.numel(), _p(V), P,
+                        float(scale), float(prior), int(code), float(best), float(param), 1 if largest else 0, float(var_floor),
+                        _p(m_p), _p(cut(o_var, a, b)), _p(cut(o_val, a, b)), _p(dm_p), _p(cut(o_dvar, a, b)),
+                        _p(cut(o_dval, a, b)), b - a, N, d, S, _p(ws), stream())
+        if mean and not whole:
+            o_mean[:, a:b].copy_(m_p)
+        if dmean and not whole:
+            o_dmean[:, a:b].copy_(dm_p)
+    return o_mean, o_var, o_val, o_dmean, o_dvar, o_dval
+
+
 def pcg_dot(a, b, out=None):
     """out [S] float64 = sum_i a_si b_si (hb_pcg_dot), a, b [S, N]."""
     _chk(a), _chk(b)

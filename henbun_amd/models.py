@@ -472,14 +472,18 @@ class ExactGPR(hb.model.Model):
         """predict_f plus the likelihood's variance."""
         return self._posterior().predict_y(Xnew, var=var)
 
-    def suggest(self, Xcand, kind="ei", largest=True, cache_rank=256, **kw):
+    def suggest(self, Xcand, kind="ei", largest=True, cache_rank=256, steps=0, lr=0.05, bounds=None, **kw):
         """(x_next [d], value, info): the next point of a sequential design -- the row of Xcand [n, d] at which the
         closed-form acquisition `kind` ('ei', 'pi', 'ucb') of the exact posterior is largest, from ONE arg-max pass over
         the candidates (ExactPosterior.argmax; **kw: param, var_floor), however many there are.  The incumbent is
         suggest_batch's: the largest (smallest with largest=False) posterior mean over the training inputs,
         predict_f(X, var=False).  The variance is the cached upper bound, built at cache_rank if the posterior has none.
-        info = dict(best, index, cache = the posterior's cache_info).  No gradient ascent from the candidate: input
-        gradients of the cached variance are the follow-up."""
+        info = dict(best, index, cache = the posterior's cache_info).  steps > 0 then refines that candidate by `steps`
+        steps of projected gradient ascent on the acquisition's exact input gradient (ExactPosterior.maximise with lr
+        and bounds, default the candidates' box): x_next leaves the grid, value is the acquisition there (never below
+        the candidate's) and info also holds start_value, the candidate's value, and steps."""
+        if int(steps) < 0:
+            raise ValueError("suggest: steps >= 0 expected (got %r)" % (steps,))
         post = self._posterior()
         mean, _ = post.predict_f(_part(self, "X"), var=False)
         best = float(mean.max() if largest else mean.min())
@@ -489,7 +493,13 @@ class ExactGPR(hb.model.Model):
         idx, value = post.argmax(Xd, kind, best=best, largest=largest, **kw)
         if idx < 0:
             raise ValueError("suggest: no candidate has a comparable acquisition value")
-        return Xd[idx].cpu().numpy(), value, dict(best=best, index=idx, cache=dict(post.cache_info))
+        x_next, info = Xd[idx].cpu().numpy(), dict(best=best, index=idx, cache=dict(post.cache_info))
+        if int(steps) > 0:
+            xb, ab, _ = post.maximise(Xd, kind, best=best, largest=largest, steps=steps, lr=lr, bounds=bounds, starts=x_next[None],
+                                      **kw)
+            info.update(start_value=value, steps=int(steps))
+            x_next, value = xb[0], ab[0]
+        return x_next, value, info
 
     def sample_functions(self, num_samples, num_features=1024, seed=0, noise=None):
         """num_samples exact posterior function draws as an hb.gp.PathwiseDraws (ExactPosterior.sample_functions); its

@@ -66,7 +66,8 @@ extern "C" {
  * a call: a host-side query that launches nothing); hb_gram_predict_f32 / _f64 and hb_gram_predict_ws_elems (exact GP:
  * predictive mean, cached upper bound of the predictive variance and closed-form acquisition from one kernel product);
  * hb_matmul_gram_vjp_tiles_ok / _tiles_f32 and hb_gram_tiles_fold_f32 (the Gram VJP's tile partials from the product that
- * computes Kbar, folded at the head of a serial chain). */
+ * computes Kbar, folded at the head of a serial chain); hb_gram_predict_grad_f32 / _f64 and hb_gram_predict_grad_ws_elems
+ * (exact GP: input gradients of the cached predictive and of its closed-form acquisition). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -915,6 +916,36 @@ int hb_gram_predict_f64(int kind, const double* x, const double* x2, const doubl
                         double scale, double prior, int acq, double best, double param, int largest, double var_floor,
                         double* mean, double* var, double* val, double* best_val, long* best_idx, long n, long N, long d,
                         long S, double* ws, void* stream);
+/* Input gradients of hb_gram_predict's outputs from ONE kernel product (csrc/gram_predict_grad.hip; not in the reference).
+ * Arguments as for hb_gram_predict, without the arg-max.  With t[s, j] as there and
+ *   u[s, j, k] = d t[s, j] / d x_jk = scale * sum_{i<N} V[s, i] k(x2_i, x_j) (x2_ik - x_jk) / ell_k^2
+ * held in DOUBLE the same way (the chunks' partials added in chunk order, times scale):
+ *   dmean[p, j, k] = (T) u[p, j, k], p < P;
+ *   dvar[j, k]     = (T) (-2 sum_{s >= P} t[s, j] u[s, j, k])   -- in double, s ascending, each product and each sum rounded
+ *                    once; exactly 0 where prior - q_j < 0 (var was clamped to 0) and without cache rows (S == P);
+ *   dval[j, k]     = (T) (sgn a_mu u[0, j, k] + a_v (-2 sum ..)) -- sgn = +1 (largest) / -1, a_mu and a_v the derivatives of
+ *                    the tail of hb_sgp_acq at (t[0, j], prior - q_j); a_v is 0 where var_floor clamps.  Needs P == 1.
+ * Outputs, each nullable, at least one given: mean [P, n], var [n], val [n] -- the BITS of hb_gram_predict -- and
+ * dmean [P, n, d], dvar [n, d], dval [n, d]; val and dval need an acquisition (acq != -1).
+ * Phase 1 is the loop of hb_gram_matvec's kernel with 1 + min(d, 4) accumulator sets: the operand of dimension k is the
+ * value tile times (x2_rk - x_ck) (1 / ell_k^2), formed in registers as the MFMA loop reads the tile (no second exp2);
+ * 32 right-hand sides per workgroup (16 for double at d >= 3), d > 4 in groups of 4 dimensions on the grid's z.  Every
+ * workgroup leaves its value partial and its derivative partials in the workspace; phase 2, one thread per column and
+ * dimension (each folds the value rows itself; the thread of dimension 0 also writes mean, var and val), adds the chunks
+ * in chunk order in double (16 chunks at a time, running sums [1 + d, S, n] carried between the groups) and finishes the
+ * column's outputs of that dimension.  No atomics: two calls return the same bits, and a column's outputs depend neither on n nor on
+ * the other columns nor on how x is cut into pieces.  n = 0 returns without a launch.
+ * ws >= hb_gram_predict_grad_ws_elems(n, N, d, S, sizeof(T)) elements of T, 16-byte aligned: 1 + d times the partials
+ * (min(chunks, 16) S n, rounded up to 8 bytes) and, beyond 16 chunks, 1 + d times S n doubles.  Validated before any launch. */
+long hb_gram_predict_grad_ws_elems(long n, long N, long d, long S, int dtype_bytes);
+int hb_gram_predict_grad_f32(int kind, const float* x, const float* x2, const float* ell, long dl, const float* V, long P,
+                             double scale, double prior, int acq, double best, double param, int largest, double var_floor,
+                             float* mean, float* var, float* val, float* dmean, float* dvar, float* dval, long n, long N,
+                             long d, long S, float* ws, void* stream);
+int hb_gram_predict_grad_f64(int kind, const double* x, const double* x2, const double* ell, long dl, const double* V, long P,
+                             double scale, double prior, int acq, double best, double param, int largest, double var_floor,
+                             double* mean, double* var, double* val, double* dmean, double* dvar, double* dval, long n, long N,
+                             long d, long S, double* ws, void* stream);
 /* Vector steps of S preconditioned conjugate-gradient iterations run in lockstep on rows of length N (csrc/gram_matvec.hip;
  * henbun_amd/gp/exact.py).  x, r, p, Ap, w [S, N] in the storage type; rz, rr, thr, out [S] DOUBLE: every dot product and
  * scalar is double.  One workgroup per row, sums in a fixed order: two solves return the same bits.  A row with
