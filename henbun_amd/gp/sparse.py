@@ -201,7 +201,8 @@ class SparseInference:
 
     def natgrad_q(self, X, Y, likelihood, k_var=1.0, residual="diagonal", q0=None, steps=20, rho=1.0, tol=1e-8):
         """Natural-gradient fit of q(u) = N(m, S S^T) for a factorising likelihood (henbun_amd.likelihoods: Gaussian,
-        Bernoulli, Poisson) at fixed hyper-parameters, for the whitened model u ~ N(0, I), f = sqrt(k_var) (u A +
+        Bernoulli, Poisson, Laplace, Gamma, Exponential, NegativeBinomial, Binomial -- all log-concave in f, so lam_j >= 0
+        and Lambda stays positive definite) at fixed hyper-parameters, for the whitened model u ~ N(0, I), f = sqrt(k_var) (u A +
         residual), y_j ~ p(y_j | f_j).  q is kept as Lambda = (S S^T)^-1, eta = Lambda m; one step is the conjugate
         update with per-point pseudo-observations (conjugate-computation VI, Khan & Lin 2017):
             mu_j, v_j            the marginals of f_j under q                         (hb_sgp_predict, one pass over X)
@@ -362,7 +363,7 @@ class SparseInference:
                        H.workspace(torch.float64, sess.device, max(M * d, 1)))
         return zbar + zk, ellbar + ek
 
-    def elbo_and_grad(self, X, Y, likelihood, q, k_var=1.0, residual="diagonal"):
+    def elbo_and_grad(self, X, Y, likelihood, q, k_var=1.0, residual="diagonal", lik_grad=False):
         """(value, grad): the ELBO sum_j E_q log p(y_j | f_j) - KL(q || N(0, I)) of a factorising likelihood at a FIXED
         q(u) = N(m, S S^T), q = (m [1, M], S [M, M] lower), and its partial gradient with respect to the CONSTRAINED
         z, lengthscales and k_var at that q: grad = dict(z=[M, d], lengthscales=[dl], k_var=float), float64 numpy.  At
@@ -384,7 +385,17 @@ class SparseInference:
         then the M^3 tail, hb_sgp_wkgrad over all of X in its stored dtype and the Gram VJP of K(z, z).  Restrictions
         and exception types are natgrad_q's: UnitRBF, one expert, Y [N, 1]; residual 'fullrank' and a mean-field q
         raise NotImplementedError; a K(z, z) + jitter I that is not positive definite raises graph.CholeskyError; a
-        likelihood that is no henbun_amd.likelihoods.Likelihood raises TypeError."""
+        likelihood that is no henbun_amd.likelihoods.Likelihood raises TypeError.
+
+        lik_grad=True: grad also holds lik_param, the derivative with respect to the likelihood's own parameter
+        (likelihood.param: the Gaussian variance, the Laplace scale, the Gamma shape, the negative binomial dispersion) --
+        sum_j dl_j / dparam at the marginals of that q (hb_lik_param_grad_f64 on every chunk of the same walk, added in
+        chunk order).  Like the other entries it is the partial derivative at fixed q, hence the total derivative at the
+        fitted q.  A likelihood that is not `trainable` raises ValueError.  The other entries and the value are the bits
+        of lik_grad=False."""
+        if lik_grad and not getattr(likelihood, "trainable", False):
+            raise ValueError("elbo_and_grad: lik_grad=True needs a likelihood with a continuous parameter (got %s)"
+                             % type(likelihood).__name__)
         sess, Xd, Yd, z, ell, W = self._grad_inputs(X, Y, "elbo_and_grad")
         torch, H = sess.torch, sess.H
         N, M = int(Xd.shape[0]), int(z.shape[0])
@@ -404,10 +415,14 @@ class SparseInference:
             mu = mean.reshape(-1) * np.sqrt(k)
             bc -= lc * mu                                                   # gamma = beta - lam mu
             Pc, rc, _ = H.sgp_wstats(Xc, lc, bc, z, ell, W)
-            return Pc, rc, ls, (bc * mu - lc * var.reshape(-1) * k).sum()
+            parts = (Pc, rc, ls, (bc * mu - lc * var.reshape(-1) * k).sum())
+            if lik_grad:
+                parts += (H.lik_param_grad(likelihood.lik_id, Yc.reshape(-1), mean, var, param=likelihood.param,
+                                           mscale=np.sqrt(k), vscale=k)[1:],)
+            return parts
 
         # chunks of a multiple of 32 rows: every chunk of lam stays 16-byte aligned
-        Phi, b, lsum, dks = _walk_f64(torch, Xd, Yd, M, 32, per_chunk)
+        Phi, b, lsum, dks, *dps = _walk_f64(torch, Xd, Yd, M, 32, per_chunk)
         # tail: G = dF/dPhi_w, g = dF/db_w
         Gm = H.matutil((H.matmul(S, S, transB=True) * (-0.5 * k)).contiguous(), H.MATUTIL_ADD_EYE, alpha=0.5 * rho * k)
         g = (m * np.sqrt(k)).contiguous()
@@ -418,6 +433,8 @@ class SparseInference:
         Sl = np.tril(S0)
         kl = 0.5 * (float((Sl * Sl).sum()) + float((m0 * m0).sum()) - M) - float(np.log(np.abs(np.diagonal(Sl))).sum())
         grad = dict(z=zg.cpu().numpy(), lengthscales=eg.cpu().numpy(), k_var=float(dks.cpu()) / (2.0 * k))
+        if lik_grad:
+            grad["lik_param"] = float(dps[0].cpu()[0])
         return float(lsum.cpu()[0]) - kl, grad
 
     # -- pathwise posterior function draws (Wilson et al. 2020) -----------------------------------------------------

@@ -45,6 +45,7 @@ ACQ = {k[len("HB_ACQ_"):].lower(): v for k, v in _C.items() if k.startswith("HB_
 PWACQ = {k[len("HB_PWACQ_"):].lower(): v for k, v in _C.items() if k.startswith("HB_PWACQ_")}   # 'ei', 'pi': over function draws
 PREC_NATIVE, PREC_BF16X3 = _hb("PREC_NATIVE", "PREC_BF16X3")
 LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON = _hb("LIK_GAUSSIAN", "LIK_BERNOULLI", "LIK_POISSON")
+LIK_LAPLACE, LIK_GAMMA, LIK_NEGBINOMIAL, LIK_BINOMIAL = _hb("LIK_LAPLACE", "LIK_GAMMA", "LIK_NEGBINOMIAL", "LIK_BINOMIAL")
 MATUTIL_BAND, MATUTIL_ADD_EYE, MATUTIL_PHI, MATUTIL_SYM, MATUTIL_SYMLOW = _hb("MATUTIL_BAND", "MATUTIL_ADD_EYE", "MATUTIL_PHI",
                                                                               "MATUTIL_SYM", "MATUTIL_SYMLOW")
 
@@ -1804,7 +1805,9 @@ def gram_bilinear_grad(x, ell, A, B, w, out=None, ws=None, kind=KERN_RBF):
 def lik_sites(lik, y, mean, var, param=1.0, mscale=1.0, vscale=1.0, out=None):
     """Sites of a factorising likelihood under f_j ~ N(mscale mean_j, vscale var_j) (hb_lik_sites): (lam [N], beta [N]) in
     the dtype of the inputs and sum_j E[log p(y_j | f_j)] as a float64 device tensor [1].  lik: LIK_GAUSSIAN (param = the
-    variance), LIK_BERNOULLI (logit link), LIK_POISSON (exp link).  Double arithmetic; two calls return the same bits."""
+    variance), LIK_BERNOULLI (logit link), LIK_POISSON (exp link), LIK_LAPLACE (param = the scale), LIK_GAMMA (exp link,
+    param = the shape, y > 0), LIK_NEGBINOMIAL (exp link, param = the dispersion), LIK_BINOMIAL (logit link, param = the
+    total count).  Double arithmetic; two calls return the same bits."""
     for t in (y, mean, var):
         _chk(t)
     N = y.numel()
@@ -1817,6 +1820,41 @@ def lik_sites(lik, y, mean, var, param=1.0, mscale=1.0, vscale=1.0, out=None):
     _lib.lib().call("hb_lik_sites" + _suf(y), int(lik), _p(y), _p(mean), _p(var), float(mscale), float(vscale), float(param),
                     _p(lam), _p(beta), _p(ell), N, _p(ws), stream())
     return lam, beta, ell
+
+
+def _lik_inputs(who, y, mean, var):
+    for t in (y, mean, var):
+        _chk(t)
+    N = y.numel()
+    if mean.numel() != N or var.numel() != N or mean.dtype != y.dtype or var.dtype != y.dtype:
+        raise ValueError("%s: y, mean, var must hold N elements of one dtype" % who)
+    return N
+
+
+def lik_param_grad(lik, y, mean, var, param=1.0, mscale=1.0, vscale=1.0):
+    """(sum_j E[log p(y_j | f_j)], its derivative with respect to the likelihood's own parameter at fixed moments) as a
+    float64 device tensor [2], for f_j ~ N(mscale mean_j, vscale var_j) (hb_lik_param_grad).  lik: LIK_GAUSSIAN (d/dvar),
+    LIK_LAPLACE (d/dscale), LIK_GAMMA (d/dshape), LIK_NEGBINOMIAL (d/ddispersion); the others have no continuous
+    parameter and are refused.  Double arithmetic; two calls return the same bits."""
+    N = _lik_inputs("lik_param_grad", y, mean, var)
+    out = _empty((2,), dtype=torch.float64, device=y.device)
+    ws = workspace(torch.float64, y.device, int(_lib.lib().raw("hb_lik_param_grad_ws_elems")(N)))
+    _lib.lib().call("hb_lik_param_grad" + _suf(y), int(lik), _p(y), _p(mean), _p(var), float(mscale), float(vscale),
+                    float(param), _p(out), N, _p(ws), stream())
+    return out
+
+
+def lik_logdens(lik, y, mean, var, param=1.0, mscale=1.0, vscale=1.0, pointwise=True):
+    """Predictive log density log E p(y_j | f_j), f_j ~ N(mscale mean_j, vscale var_j), of any LIK_* (hb_lik_logdens):
+    (per point [N] in the dtype of the inputs, or None with pointwise=False; their sum as a float64 device tensor [1]).
+    Closed form for LIK_GAUSSIAN and LIK_LAPLACE, the 20-node rule combined by log-sum-exp for the others."""
+    N = _lik_inputs("lik_logdens", y, mean, var)
+    out = _empty((N,), dtype=y.dtype, device=y.device) if pointwise else None
+    total = _empty((1,), dtype=torch.float64, device=y.device)
+    ws = workspace(torch.float64, y.device, int(_lib.lib().raw("hb_lik_sites_ws_elems")(N)))
+    _lib.lib().call("hb_lik_logdens" + _suf(y), int(lik), _p(y), _p(mean), _p(var), float(mscale), float(vscale), float(param),
+                    _p(out), _p(total), N, _p(ws), stream())
+    return out, total
 
 
 def lik_predict(lik, mean, var, param=1.0):

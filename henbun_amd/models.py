@@ -251,11 +251,19 @@ class SVGP(hb.model.Model):
 
 
 class SVGPLik(hb.model.Model):
-    """Sparse variational GP with a non-conjugate factorising likelihood (hb.likelihoods: Bernoulli, Poisson, Gaussian)
-    and a full-rank q(u): SVGP's latent model, the sampled ELBO with likelihood.logp, and a deterministic fit of q(u) by
-    natural-gradient steps (SparseGP.natgrad_q)."""
+    """Sparse variational GP with a non-conjugate factorising likelihood (hb.likelihoods: Bernoulli, Poisson, Gaussian,
+    Laplace, Gamma, Exponential, NegativeBinomial, Binomial) and a full-rank q(u): SVGP's latent model, the sampled ELBO
+    with likelihood.logp, and a deterministic fit of q(u) by natural-gradient steps (SparseGP.natgrad_q).
 
-    def setUp(self, X, Y, Z, likelihood, residual="diagonal", eps=None):
+    learn_likelihood=True (a `trainable` likelihood only: ValueError otherwise) makes the likelihood's own parameter a
+    positive Variable `lik_param`, initialised to likelihood.param: the sampled ELBO reads it, fit_q, predict_y,
+    predict_log_density and elbo_and_grad use its current value, and fit_hyper learns it with the other
+    hyper-parameters.  The likelihood object handed in is never modified; current_likelihood() is the one in use."""
+
+    def setUp(self, X, Y, Z, likelihood, residual="diagonal", eps=None, learn_likelihood=False):
+        if learn_likelihood and not getattr(likelihood, "trainable", False):
+            raise ValueError("SVGPLik: learn_likelihood=True needs a likelihood with a continuous parameter (got %s)"
+                             % type(likelihood).__name__)
         self.N = X.shape[0]
         self.X = hb.param.MinibatchData(X)
         self.Y = hb.param.MinibatchData(Y)
@@ -263,6 +271,10 @@ class SVGPLik(hb.model.Model):
         self.u = hb.variationals.Normal(shape=[1, Z.shape[0]], q_shape="fullrank")
         self.k_var = hb.param.Variable([1], transform=hb.transforms.positive)
         self.likelihood = likelihood
+        self.learn_likelihood = bool(learn_likelihood)
+        if self.learn_likelihood:
+            self.lik_param = hb.param.Variable([1], transform=hb.transforms.positive)
+            self.lik_param = np.ones(1) * likelihood.param
         self.residual = residual
         self.eps = None if eps is None else hb.param.MinibatchData(eps)  # injected residual noise (parity runs)
 
@@ -270,8 +282,20 @@ class SVGPLik(hb.model.Model):
     def ELBO(self):
         f = self.gp.samples(self.X, self.u, q_shape=self.residual, eps=self.eps) * tf.sqrt(self.k_var)
         n = tf.shape(self.X)[0]
-        ll = tf.reduce_sum(self.likelihood.logp(f, tf.transpose(self.Y)))
+        if self.learn_likelihood:
+            ll = tf.reduce_sum(self.likelihood.logp(f, tf.transpose(self.Y), param=self.lik_param))
+        else:
+            ll = tf.reduce_sum(self.likelihood.logp(f, tf.transpose(self.Y)))
         return (self.N / n) * ll - self.KL()
+
+    def current_likelihood(self):
+        """The likelihood in use: the one handed in, or with learn_likelihood=True a copy that carries the current value
+        of lik_param."""
+        lik = _part(self, "likelihood")
+        if not _part(self, "learn_likelihood"):
+            return lik
+        self.initialize()
+        return lik.with_param(_scalar(self, "lik_param"))
 
     _predict = SVGP._predict                      # reads gp, u, k_var and residual only when no noise is asked for
     predict_f = SVGP.predict_f
@@ -285,19 +309,36 @@ class SVGPLik(hb.model.Model):
         """Mean and variance [1, n] of a new observation y at Xnew [n, 1]: the likelihood's predictive under the
         Gaussian marginals of predict_f (hb_lik_predict)."""
         mean, var = self.predict_f(Xnew)
-        sess, lik = self._session, _part(self, "likelihood")
+        sess, lik = self._session, self.current_likelihood()
         ym, yv = sess.H.lik_predict(lik.lik_id, upload(sess, mean), upload(sess, var), param=lik.param)
         return ym.cpu().numpy(), yv.cpu().numpy()
 
-    def fit_q(self, steps=20, rho=1.0, tol=1e-8):
+    def predict_log_density(self, Xnew, Ynew):
+        """(per point [1, n], their sum as a float): the predictive log density log E p(y_j | f_j) of observations Ynew
+        [n, 1] at Xnew [n, 1] under the Gaussian marginals of predict_f (hb_lik_logdens), for any likelihood -- the
+        figure two likelihoods are compared on with held-out data.  Closed form for Gaussian and Laplace, the 20-node
+        rule combined by log-sum-exp for the others; the sum is taken in double on the device."""
+        mean, var = self.predict_f(Xnew)
+        Ynew = np.asarray(Ynew)
+        if Ynew.size != mean.size:
+            raise ValueError("predict_log_density: Ynew must hold one observation per row of Xnew (got %s for %d rows)"
+                             % (Ynew.shape, mean.size))
+        sess, lik = self._session, self.current_likelihood()
+        yd = upload(sess, Ynew.reshape(mean.shape))
+        out, total = sess.H.lik_logdens(lik.lik_id, yd.reshape(-1), upload(sess, mean).reshape(-1),
+                                        upload(sess, var).reshape(-1), param=lik.param)
+        return out.cpu().numpy().reshape(mean.shape), float(total.cpu()[0])
+
+    def fit_q(self, steps=20, rho=None, tol=1e-8):
         """Fit q(u) at the current z, lengthscales and k_var by natural-gradient steps from the model's CURRENT q, over
         the model's full device-resident X, Y (SparseGP.natgrad_q: per step one marginals pass, the sites, one weighted
         statistics pass and the M^3 tail; no minibatch, no Adam step).  u.q_mu / u.q_sqrt are written as SVGP.fit_q
         writes them for 'fullrank'.  Returns (m [1, M], S [M, M], info) as natgrad_q does.  A full step (rho = 1) from a q
         far from the optimum, such as a freshly initialised one, can overshoot before it settles: info['elbo'] shows it,
-        and rho < 1 damps it."""
+        and rho < 1 damps it.  rho=None takes the likelihood's natgrad_rho: 1, except Laplace's 0.25."""
         self.initialize()
-        m, S, info = _part(self, "gp").natgrad_q(_part(self, "X"), _part(self, "Y"), _part(self, "likelihood"),
+        rho = _part(self, "likelihood").natgrad_rho if rho is None else rho
+        m, S, info = _part(self, "gp").natgrad_q(_part(self, "X"), _part(self, "Y"), self.current_likelihood(),
                                                  k_var=_scalar(self, "k_var"), residual=self.residual,
                                                  q0=self._current_q(), steps=steps, rho=rho, tol=tol)
         _write_q(self, m, S)
@@ -322,26 +363,35 @@ class SVGPLik(hb.model.Model):
     def _hyper_variables(self):
         """The Variables the ELBO at a fixed q(u) depends on, by the names the gradient uses."""
         gp = _part(self, "gp")
-        return dict(z=_part(gp, "z"), lengthscales=_part(_part(gp, "kern"), "lengthscales"), k_var=_part(self, "k_var"))
+        hv = dict(z=_part(gp, "z"), lengthscales=_part(_part(gp, "kern"), "lengthscales"), k_var=_part(self, "k_var"))
+        if _part(self, "learn_likelihood"):
+            hv["lik_param"] = _part(self, "lik_param")
+        return hv
 
     def elbo_and_grad(self):
         """(value, grad): the ELBO over the model's full X, Y at the model's CURRENT q(u) and its partial gradient at
         that q with respect to the RAW (free) parameters, grad = dict(z, lengthscales, k_var) in the shapes of the raw
         arrays, float64 numpy.  SparseGP.elbo_and_grad (float64 arithmetic whatever the session's dtype), chained
-        through the transforms' dforward.  After fit_q() has converged this is the total derivative of the fitted ELBO."""
-        value, cons = _part(self, "gp").elbo_and_grad(_part(self, "X"), _part(self, "Y"), _part(self, "likelihood"),
-                                                      self._current_q(), k_var=_scalar(self, "k_var"), residual=self.residual)
+        through the transforms' dforward.  After fit_q() has converged this is the total derivative of the fitted ELBO.
+        With learn_likelihood=True grad also holds lik_param."""
+        learn = _part(self, "learn_likelihood")
+        kw = dict(lik_grad=True) if learn else {}
+        value, cons = _part(self, "gp").elbo_and_grad(_part(self, "X"), _part(self, "Y"), self.current_likelihood(),
+                                                      self._current_q(), k_var=_scalar(self, "k_var"), residual=self.residual,
+                                                      **kw)
         return value, _chain_to_raw(self, cons)
 
-    def fit_hyper(self, steps, lr=0.01, train_z=True, q_steps=5, rho=1.0):
+    def fit_hyper(self, steps, lr=0.01, train_z=True, q_steps=5, rho=None):
         """Deterministic full-batch fit of the hyper-parameters, alternating as GPflow's natural-gradient recipe does:
         every outer step runs fit_q(steps=q_steps, rho=rho) from the current q(u), then takes ONE Adam ASCENT step on
-        elbo_and_grad() in the raw parameters of lengthscales, k_var and (train_z) z -- on the host in float64, the
-        loop of SVGP.fit_hyper.  No minibatch noise.  Ends with a fit_q() at the final parameters.  Returns the trace of
-        ELBO values, steps + 1 entries: after the first fit_q at the starting parameters .. after the closing fit_q()
+        elbo_and_grad() in the raw parameters of lengthscales, k_var, (train_z) z and, with learn_likelihood=True, the
+        likelihood's parameter -- on the host in float64, the loop of SVGP.fit_hyper.  No minibatch noise.  Ends with a
+        fit_q() at the final parameters (at the likelihood's natgrad_rho, whatever `rho`).  Returns the trace of ELBO
+        values, steps + 1 entries: after the first fit_q at the starting parameters .. after the closing fit_q()
         at the final ones.  A step after which a factorisation fails raises graph.CholeskyError with the last good
         parameters restored.  The first fit_q starts at the model's current q(u): from a freshly initialised (random)
-        q a full step overshoots (see fit_q), so call reset_q() first (or fit q(u) some other way, or pass rho < 1)."""
+        q a full step overshoots (see fit_q), so call reset_q() first (or fit q(u) some other way, or pass rho < 1).
+        rho=None: the likelihood's natgrad_rho, as for fit_q."""
         steps, done = int(steps), [0]
 
         def evaluate():

@@ -50,7 +50,8 @@ extern "C" {
  * conditional-variance selection of inducing points); hb_sgp_kgrad_f32 / _f64 and hb_sgp_kgrad_ws_elems (streamed part
  * of the gradient of the collapsed bound); hb_sgp_wstats_f32 / _f64, hb_sgp_wstats_ws_elems, hb_lik_sites_f32 / _f64,
  * hb_lik_sites_ws_elems, hb_lik_predict_f32 / _f64 and the enum values HB_LIK_* (natural-gradient fit of q(u) for
- * non-Gaussian likelihoods); hb_sgp_wkgrad_f32 / _f64 (streamed part of the gradient of the ELBO at a fixed q(u));
+ * non-Gaussian likelihoods); hb_lik_param_grad_f32 / _f64, hb_lik_param_grad_ws_elems, hb_lik_logdens_f32 / _f64 and
+ * HB_LIK_LAPLACE .. HB_LIK_BINOMIAL (likelihoods with a parameter of their own, its gradient, predictive log density); hb_sgp_wkgrad_f32 / _f64 (streamed part of the gradient of the ELBO at a fixed q(u));
  * hb_sgp_pathwise_f32 / _f64 (pathwise posterior function draws, linear in n); hb_gram_matvec_f32 / _f64 and hb_pcg_*
  * (matrix-free kernel product and the vector steps of lockstep preconditioned conjugate gradients: exact GP regression);
  * hb_gram_bilinear_grad_f32 / _f64 and hb_pcg_*_coef (the exact GP's log marginal likelihood and its gradient);
@@ -723,8 +724,53 @@ int hb_sgp_wstats_f64(int kind, const double* X, const double* w, const double* 
  * no atomics -- two calls return the same bits.  ws >= hb_lik_sites_ws_elems(N) doubles (at most 1024).  Validated before
  * any launch: the id, N >= 0, param > 0 for HB_LIK_GAUSSIAN, vscale >= 0.
  * hb_lik_predict_*: mean and variance of a new y given f ~ N(mean[j], var[j]): (mean, var + param); (p, p (1 - p)) with
- * p = E sigmoid(f) by the same rule; (e, e + (exp(var) - 1) e^2). */
-enum { HB_LIK_GAUSSIAN = 0, HB_LIK_BERNOULLI = 1, HB_LIK_POISSON = 2 };
+ * p = E sigmoid(f) by the same rule; (e, e + (exp(var) - 1) e^2).
+ *
+ * Likelihoods with a parameter of their own (ids from 16; all log-concave in f, so lam >= 0).  delta = mu - y:
+ *   HB_LIK_LAPLACE      param = the scale b > 0, log p = -log 2b - |y - f| / b.  Closed form (the kink defeats the rule):
+ *                       A = E|y - f| = sqrt(2 v / pi) exp(-delta^2 / 2v) + delta erf(delta / sqrt(2 v)),
+ *                       l = -log 2b - A / b, g = erf((y - mu) / sqrt(2 v)) / b, lam = (2 / b) exp(-delta^2 / 2v) / sqrt(2 pi v)
+ *                       (v = 0: A = |delta|, g = sign(y - mu) / b, lam = 0).  Predictive (mu, v + 2 b^2)
+ *   HB_LIK_GAMMA        param = the shape a > 0, mean exp(f), y > 0 IS THE CALLER'S DUTY (log y is taken as it comes):
+ *                       log p = a log a - lgamma(a) + (a - 1) log y - a f - a y exp(-f).  Closed form with
+ *                       E = exp(-mu + v / 2): l = a log a - lgamma(a) + (a - 1) log y - a mu - a y E, g = -a + a y E,
+ *                       lam = a y E.  Predictive, e = exp(mu + v / 2): (e, e^2 (expm1(v) + exp(v) / a)).  a = 1: exponential
+ *   HB_LIK_NEGBINOMIAL  param = the dispersion r > 0, mean exp(f), variance mean + mean^2 / r.  With t = f - log r:
+ *                       log p = lgamma(y + r) - lgamma(r) - lgamma(y + 1) + y t - (y + r) softplus(t); 20-node rule,
+ *                       g = E[y sigmoid(-t) - r sigmoid(t)], lam = (y + r) E[sigmoid(t) sigmoid(-t)].
+ *                       Predictive (e, e + e^2 (expm1(v) + exp(v) / r))
+ *   HB_LIK_BINOMIAL     param = the total count n >= 1, integer-valued; logit link, y in {0, .., n}:
+ *                       log p = lgamma(n + 1) - lgamma(y + 1) - lgamma(n - y + 1) + y f - n softplus(f); 20-node rule,
+ *                       g = E[y sigmoid(-f) - (n - y) sigmoid(f)], lam = n E[sigmoid(f) sigmoid(-f)].  Predictive with
+ *                       p = E sigmoid: (n p, n E[sigmoid(f) sigmoid(-f)] + n^2 E[(sigmoid(f) - p)^2]), the second
+ *                       expectation taken over the nodes once p is known (no E sigmoid^2 - p^2)
+ * Validated before any launch as well: param > 0 for the first three, param >= 1 and integer-valued for HB_LIK_BINOMIAL.
+ *
+ * hb_lik_param_grad_*: out[0] = sum_j l_j and out[1] = sum_j dl_j / dparam at fixed mu_j, v_j, for the likelihoods whose
+ * parameter is continuous; any other known id returns < 0 ("no continuous parameter").  Same scales, grid, per-block
+ * partials and fold as hb_lik_sites_* (two calls return the same bits); ws >= hb_lik_param_grad_ws_elems(N) doubles.
+ *   HB_LIK_GAUSSIAN     d/dvar:  -1 / (2 s2) + ((y - mu)^2 + v) / (2 s2^2)
+ *   HB_LIK_LAPLACE      d/db:    -1 / b + A / b^2
+ *   HB_LIK_GAMMA        d/da:    log a + 1 - psi(a) + log y - mu - y E
+ *   HB_LIK_NEGBINOMIAL  d/dr:    psi(y + r) - psi(r) - y / r - E[softplus(t)] + (y + r) / r E[sigmoid(t)]   (20-node rule)
+ * psi is evaluated in double on the device: the recurrence up to x >= 10, then the asymptotic series through x^-14 (the
+ * first term left out is below 5e-17 there; the elementwise table's HB_EW_DIGAMMA stops at 1e-11 and is not used).
+ *
+ * hb_lik_logdens_*: out[j] = log integral p(y_j | f) N(f; mu_j, v_j) df (out may be NULL) and sum[0] = sum_j out[j] in
+ * double by the same fold, for all seven ids; ws >= hb_lik_sites_ws_elems(N) doubles.  Gaussian: the density of
+ * N(mu, v + param).  Laplace: closed form, p = e^(v / 2b^2) [e^(-d/b) erfc((v/b - d) / sqrt(2v)) + e^(d/b) erfc((v/b + d) /
+ * sqrt(2v))] / 4b with d = y - mu, evaluated in log space through erfcx (a term whose erfc argument z is >= 0 is
+ * -d^2 / 2v + log erfcx(z)), so neither |d| / b large nor v small overflows or loses the tail.  The others: the 20-node
+ * rule over p(y | f_i), combined by log-sum-exp. */
+enum {
+  HB_LIK_GAUSSIAN = 0,
+  HB_LIK_BERNOULLI = 1,
+  HB_LIK_POISSON = 2,
+  HB_LIK_LAPLACE = 16,
+  HB_LIK_GAMMA = 17,
+  HB_LIK_NEGBINOMIAL = 18,
+  HB_LIK_BINOMIAL = 19
+};
 long hb_lik_sites_ws_elems(long N);
 int hb_lik_sites_f32(int lik, const float* y, const float* mean, const float* var, double mscale, double vscale, double param,
                      float* lam, float* beta, double* ell_sum, long N, double* ws, void* stream);
@@ -734,6 +780,15 @@ int hb_lik_predict_f32(int lik, const float* mean, const float* var, double para
                        void* stream);
 int hb_lik_predict_f64(int lik, const double* mean, const double* var, double param, double* ymean, double* yvar, long N,
                        void* stream);
+long hb_lik_param_grad_ws_elems(long N);
+int hb_lik_param_grad_f32(int lik, const float* y, const float* mean, const float* var, double mscale, double vscale,
+                          double param, double* out, long N, double* ws, void* stream);
+int hb_lik_param_grad_f64(int lik, const double* y, const double* mean, const double* var, double mscale, double vscale,
+                          double param, double* out, long N, double* ws, void* stream);
+int hb_lik_logdens_f32(int lik, const float* y, const float* mean, const float* var, double mscale, double vscale, double param,
+                       float* out, double* sum, long N, double* ws, void* stream);
+int hb_lik_logdens_f64(int lik, const double* y, const double* mean, const double* var, double mscale, double vscale,
+                       double param, double* out, double* sum, long N, double* ws, void* stream);
 /* Pathwise posterior function draws (csrc/sgp_pathwise.hip; not in the reference; Wilson et al. 2020).  S function draws,
  * each a coefficient row coef[s] = [ w_s / sqrt(L) | v_s ] over 2L random Fourier features of the unit RBF kernel and the M
  * canonical basis functions K(z_m, .), evaluated at n points:

@@ -7,6 +7,8 @@ Forms, fp32 (device events around `iters` calls; `reps` rounds, ALTERNATING betw
     wstats     hb_sgp_wstats_f32                     (Phi = A diag(lam) A^T, b = A beta)
     marginals  hb_sgp_predict_f32, full-rank S       (mean, var of f at every row of X)
     sites      hb_lik_sites_f32, Bernoulli           (lam, beta, sum l)
+    sites_*    hb_lik_sites_f32 for Laplace(0.3), Gamma(4), NegativeBinomial(2), Binomial(12) on labels drawn from each at the
+               same latent function; param_grad_negbinomial / logdens_negbinomial: hb_lik_param_grad_f32 / hb_lik_logdens_f32
     iteration  marginals + sites + wstats + the float64 M^3 tail (two Cholesky factors, an inverse, three products)
 and, once, a Bernoulli fit to tol = 1e-8 from the prior through models.SVGPLik.fit_q (host clock around a synchronise)."""
 import argparse
@@ -74,6 +76,25 @@ def main():
     def wstats():
         return H.sgp_wstats(X, lam, beta, z, ell, W, wfrag=frag, ws=ws)
 
+    latent = 1.5 * np.sin(Xh)
+    zoo = dict(laplace=(H.LIK_LAPLACE, 0.3, latent + rng.laplace(0.0, 0.3, latent.shape)),
+               gamma=(H.LIK_GAMMA, 4.0, rng.gamma(4.0, np.exp(latent) / 4.0)),
+               negbinomial=(H.LIK_NEGBINOMIAL, 2.0, rng.negative_binomial(2.0, 2.0 / (2.0 + np.exp(latent)))),
+               binomial=(H.LIK_BINOMIAL, 12.0, rng.binomial(12, 1.0 / (1.0 + np.exp(-latent)))))
+    zoo = {k: (lik, p, f32(yk)) for k, (lik, p, yk) in zoo.items()}
+
+    def zoo_sites(name):
+        lik, p, yk = zoo[name]
+        return lambda: H.lik_sites(lik, yk, mean, var, param=p, out=(lam, beta))
+
+    def param_grad():
+        lik, p, yk = zoo["negbinomial"]
+        return H.lik_param_grad(lik, yk.reshape(-1), mean.reshape(-1), var.reshape(-1), param=p)
+
+    def logdens():
+        lik, p, yk = zoo["negbinomial"]
+        return H.lik_logdens(lik, yk.reshape(-1), mean.reshape(-1), var.reshape(-1), param=p)
+
     def iteration():
         L, _ = H.cholesky(Lam)
         V = H.trinv(L)
@@ -85,6 +106,8 @@ def main():
         wstats()
 
     forms = dict(stats=stats, wstats=wstats, marginals=marginals, sites=sites, iteration=iteration)
+    forms.update({"sites_" + k: zoo_sites(k) for k in zoo})
+    forms.update(param_grad_negbinomial=param_grad, logdens_negbinomial=logdens)
     marginals()
     sites()
     Phi, b, _ = wstats()                   # one real step from the prior: the timed forms see the weights of a fit
