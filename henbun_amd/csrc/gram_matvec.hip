@@ -23,11 +23,9 @@
 // K(X, X) is symmetric and the symmetric call synthesises every value twice; halving that needs the transposed
 // accumulation of a block into other workgroups' columns ("Exact GP by conjugate gradients": the next step).
 #include "common.cuh"
-#include "mfma16.cuh"
-#include "sgp_strip.cuh"
 #include "sgp_pathwise.cuh"   // pw_takes: the arg-max rule
 #include "acq_tail.cuh"
-#include "gram_matvec.cuh"   // GMV_*, GmvArgs, gmv_finish, GPR_THREADS, GprArgs, gpr_part_elems: shared with gram_predict_grad.hip
+#include "gram_matvec.cuh"   // GMV_*, GmvArgs, gmv_tiles, gmv_finish, GPR_THREADS, GprArgs, gpr_part_elems: shared with gram_predict_grad.hip
 #include "../../include/henbun_hip.h"
 
 // D: the input dimension when it is at most 4 (the column's coordinates then live in registers), 0: any d, the
@@ -35,100 +33,13 @@
 template <typename T, int D, int NST>
 __global__ void __launch_bounds__(GMV_THREADS) gram_matvec_kernel(GmvArgs<T> a) {
   typedef PwMma<T> MM;
-  constexpr int SP = 16 * NST, DR = D ? D : 1;
-  __shared__ __attribute__((aligned(16))) T Bs[GMV_THREADS / 64][GMV_KT][GMV_BLD];
-  __shared__ __attribute__((aligned(16))) T Cs[SP][GMV_CLD];
-  const int n = a.n, N = a.N, S = a.S, d = D ? D : a.d;
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 31, h = lane >> 5;        // synthesis: column of the wave's tile, row parity
-  const int l16 = lane & 15, g = lane >> 4;      // MFMA operands
-  const int strip = blockIdx.x % a.nstrip, slot = blockIdx.x / a.nstrip, chunk = a.c0 + slot;
+  const int n = a.n, N = a.N, S = a.S;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l16 = lane & 15;
+  const int strip = blockIdx.x % a.nstrip, slot = blockIdx.x / a.nstrip;
   const int s0 = blockIdx.y * GMV_SMAX;
   const long col0 = (long)strip * GMV_CN + 32 * w;   // long: n may end within 128 of 2^31
-  const int i0 = chunk * GMV_CHUNK, iend = N - i0 < GMV_CHUNK ? N : i0 + GMV_CHUNK;   // this workgroup's rows
-  const long jc = (col0 + c < n ? col0 + c : (long)n - 1) * d;   // columns past n: a copy of the last one (never written out)
-  const T* __restrict__ xj = a.x + jc;
-
-  T xs[DR], sc[DR];
-#pragma unroll
-  for (int k = 0; k < DR; ++k) {
-    if (D) {
-      xs[k] = xj[k];
-      sc[k] = T(SGP_EXP2_SCALE) / a.ell[a.dl == 1 ? 0 : k];
-    }
-  }
-  auto rbf = [&](const T* __restrict__ zm) {     // k(x2_i, x): the difference first, scaled afterwards (sgp_strip.cuh)
-    T r2 = T(0);
-    if (D) {
-#pragma unroll
-      for (int k = 0; k < DR; ++k) {
-        const T tt = (zm[k] - xs[k]) * sc[k];
-        r2 += tt * tt;
-      }
-    } else {
-      for (int k = 0; k < d; ++k) {
-        const T tt = (zm[k] - xj[k]) * (T(SGP_EXP2_SCALE) / a.ell[a.dl == 1 ? 0 : k]);
-        r2 += tt * tt;
-      }
-    }
-    return hb_exp2_neg<T>(r2);
-  };
-
-  // V tile of a K-step through registers: element e = tid + GMV_THREADS i is (right-hand side e / GMV_KT, row
-  // e % GMV_KT); rows past the chunk's end and right-hand sides past S are zeros
-  constexpr int CIT = SP * GMV_KT / GMV_THREADS;
-  T creg[CIT];
-  auto v_request = [&](int kb) {
-#pragma unroll
-    for (int i = 0; i < CIT; ++i) {
-      const int e = tid + GMV_THREADS * i, s = s0 + e / GMV_KT, k = e % GMV_KT;
-      const bool ok = s < S && k < iend - kb;
-      creg[i] = ok ? a.V[(long)s * N + kb + k] : T(0);
-    }
-  };
-  auto v_store = [&]() {
-#pragma unroll
-    for (int i = 0; i < CIT; ++i) {
-      const int e = tid + GMV_THREADS * i;
-      Cs[e / GMV_KT][e % GMV_KT] = creg[i];
-    }
-  };
-
-  typename MM::Acc acc[NST][2];
-#pragma unroll
-  for (int st = 0; st < NST; ++st)
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[st][ct][r] = T(0);
-
-  const int nK = (iend - i0 + GMV_KT - 1) / GMV_KT;
-  v_request(i0);
-#pragma nounroll
-  for (int t = 0; t < nK; ++t) {
-    const int kb = i0 + t * GMV_KT;
-    __syncthreads();   // the MFMAs of the step before have read both tiles
-    v_store();
-#pragma unroll
-    for (int i = 0; i < GMV_KT / 2; ++i) {
-      const int r = h + 2 * i;
-      const bool in = r < iend - kb;
-      const T v = rbf(a.x2 + (long)(in ? kb + r : iend - 1) * d);
-      Bs[w][r][c] = in ? v : T(0);
-    }
-    if (t + 1 < nK) v_request(kb + GMV_KT);   // the next step's V tile is in flight during the MFMAs
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < GMV_KT / 4; ++kk) {
-      const T b0 = Bs[w][4 * kk + g][l16], b1 = Bs[w][4 * kk + g][16 + l16];
-#pragma unroll
-      for (int st = 0; st < NST; ++st) {
-        const T av = Cs[16 * st + l16][4 * kk + g];
-        acc[st][0] = MM::mma(av, b0, acc[st][0]);
-        acc[st][1] = MM::mma(av, b1, acc[st][1]);
-      }
-    }
-  }
+  typename MM::Acc acc[NST][2], none[1][NST][2];
+  gmv_tiles<T, D, NST, 0>(a, s0, 0, acc, none);
 
   // masked store: register r of lane l is right-hand side s0 + 16 st + row(l, r), column col0 + 16 ct + l % 16
 #pragma unroll

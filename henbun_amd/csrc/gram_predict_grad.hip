@@ -9,20 +9,18 @@
 // keeps all its dimensions in one workgroup, larger d takes them in groups of 4 on blockIdx.z, the K block synthesised
 // again per group and the values stored by group 0.
 //
-// Phase 1 is gram_matvec_kernel's loop (csrc/gram_matvec.hip) -- the same K-block synthesis, the same V staging, the same K
-// order, so every value accumulator tile sees the MFMA sequence it sees there and mean, var and val are the bits of
-// hb_gram_predict -- on a grid of strips x chunks; every workgroup leaves its value partial and its d derivative partials
-// in the workspace, plane q of it holding [chunks of the group, S, n] for the value (q = 0) and dimension q - 1.  Phase 2
-// folds the chunks of every plane in chunk order in double per column (carrying running sums [1 + d, S, n]
-// between groups of GMV_GROUP chunks; one thread per dimension too, each folding the value rows itself) and on the last
-// group emits
+// Phase 1 is gram_matvec_kernel's loop (gmv_tiles, csrc/gram_matvec.cuh, here with its derivative operands) -- the one
+// K-block synthesis, V staging and K order, so every value accumulator tile sees the MFMA sequence it sees there and mean,
+// var and val are the bits of hb_gram_predict -- on a grid of strips x chunks; every workgroup leaves its value partial
+// and its d derivative partials in the workspace, plane q of it holding [chunks of the group, S, n] for the value (q = 0)
+// and dimension q - 1.  Phase 2 folds the chunks of every plane in chunk order in double per column (carrying running
+// sums [1 + d, S, n] between groups of GMV_GROUP chunks; one thread per dimension too, each folding the value rows
+// itself) and on the last group emits
 //     dmean[p, j, k] = (T) u[p, j, k]                           dvar[j, k] = (T) (-2 sum_{s >= P} t[s, j] u[s, j, k])
 //     dval[j, k] = (T) (sgn a_mu u[0, j, k] + a_v (-2 sum ..))  (P = 1; a_mu, a_v: acq_point at (t[0, j], prior - q_j))
 // with dvar exactly 0 where prior - q_j < 0 (the variance was clamped) and without cache rows.  No atomics; the order of
 // every sum is fixed by N alone, so a column's outputs depend on nothing but the column.
 #include "common.cuh"
-#include "mfma16.cuh"
-#include "sgp_strip.cuh"
 #include "acq_tail.cuh"
 #include "gram_matvec.cuh"
 #include "../../include/henbun_hip.h"
@@ -42,145 +40,20 @@ struct GpgArgs {
   T* dval;         // [n, d], nullable
 };
 
-// D: as for gram_matvec_kernel; DG = D dimensions (all of them) for D in 1 .. 4, GPG_DG per blockIdx.z for D == 0.
-// SECOND COPY of gram_matvec_kernel's loop (csrc/gram_matvec.hip): the synthesis, the V staging, the two barriers and the
-// value MFMAs below repeat it line for line, with the table of x2 rows and the derivative operands added; a change to
-// either copy is made in both -- the value partials here are promised to be that kernel's bits.
+// D: as for gram_matvec_kernel; DG = D dimensions (all of them) for D in 1 .. 4, GPG_DG per blockIdx.z for D == 0
 template <typename T, int D, int NST>
 __global__ void __launch_bounds__(GMV_THREADS) gram_predict_grad_kernel(GpgArgs<T> ga) {
   typedef PwMma<T> MM;
-  constexpr int SP = 16 * NST, DR = D ? D : 1, DG = D ? D : GPG_DG;
-  __shared__ __attribute__((aligned(16))) T Bs[GMV_THREADS / 64][GMV_KT][GMV_BLD];
-  __shared__ __attribute__((aligned(16))) T Cs[SP][GMV_CLD];
-  __shared__ T Fs[DG][GMV_KT];   // x2_rk of the step's rows, per dimension of this workgroup
+  constexpr int DG = D ? D : GPG_DG;
   const GmvArgs<T>& a = ga.p.g;
-  const int n = a.n, N = a.N, S = a.S, d = D ? D : a.d;
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 31, h = lane >> 5;        // synthesis: column of the wave's tile, row parity
-  const int l16 = lane & 15, g = lane >> 4;      // MFMA operands
-  const int strip = blockIdx.x % a.nstrip, slot = blockIdx.x / a.nstrip, chunk = a.c0 + slot;
-  const int s0 = blockIdx.y * SP;                // (the host launches NST = its right-hand sides per workgroup / 16)
+  const int n = a.n, S = a.S, d = D ? D : a.d;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l16 = lane & 15;
+  const int strip = blockIdx.x % a.nstrip, slot = blockIdx.x / a.nstrip;
+  const int s0 = blockIdx.y * 16 * NST;          // (the host launches NST = its right-hand sides per workgroup / 16)
   const int k0 = D ? 0 : blockIdx.z * GPG_DG;    // first dimension of this workgroup
   const long col0 = (long)strip * GMV_CN + 32 * w;   // long: n may end within 128 of 2^31
-  const int i0 = chunk * GMV_CHUNK, iend = N - i0 < GMV_CHUNK ? N : i0 + GMV_CHUNK;   // this workgroup's rows
-  const long jc = (col0 + c < n ? col0 + c : (long)n - 1) * d;   // columns past n: a copy of the last one (never written out)
-  const T* __restrict__ xj = a.x + jc;
-
-  T xs[DR], sc[DR];
-#pragma unroll
-  for (int k = 0; k < DR; ++k) {
-    if (D) {
-      xs[k] = xj[k];
-      sc[k] = T(SGP_EXP2_SCALE) / a.ell[a.dl == 1 ? 0 : k];
-    }
-  }
-  auto rbf = [&](const T* __restrict__ zm) {     // k(x2_i, x): the difference first, scaled afterwards (sgp_strip.cuh)
-    T r2 = T(0);
-    if (D) {
-#pragma unroll
-      for (int k = 0; k < DR; ++k) {
-        const T tt = (zm[k] - xs[k]) * sc[k];
-        r2 += tt * tt;
-      }
-    } else {
-      for (int k = 0; k < d; ++k) {
-        const T tt = (zm[k] - xj[k]) * (T(SGP_EXP2_SCALE) / a.ell[a.dl == 1 ? 0 : k]);
-        r2 += tt * tt;
-      }
-    }
-    return hb_exp2_neg<T>(r2);
-  };
-
-  // the two columns this lane holds in the MFMA's B operand: their coordinates and 1 / ell^2 for the derivative factor
-  T xm[2][DG], ie2[DG];
-#pragma unroll
-  for (int k = 0; k < DG; ++k) {
-    const bool ok = k0 + k < d;
-    const T e = a.ell[a.dl == 1 || !ok ? 0 : k0 + k];
-    ie2[k] = ok ? T(1) / (e * e) : T(0);
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-      const long j = col0 + 16 * cc + l16;
-      xm[cc][k] = ok ? a.x[(j < n ? j : (long)n - 1) * d + k0 + k] : T(0);
-    }
-  }
-  // this thread's entry of the table: dimension k0 + fk, row fr
-  const int fk = tid / GMV_KT, fr = tid % GMV_KT;
-  const bool fok = fk < DG && k0 + fk < d;
-
-  // V tile of a K-step through registers: element e = tid + GMV_THREADS i is (right-hand side e / GMV_KT, row
-  // e % GMV_KT); rows past the chunk's end and right-hand sides past S are zeros
-  constexpr int CIT = SP * GMV_KT / GMV_THREADS;
-  T creg[CIT];
-  auto v_request = [&](int kb) {
-#pragma unroll
-    for (int i = 0; i < CIT; ++i) {
-      const int e = tid + GMV_THREADS * i, s = s0 + e / GMV_KT, k = e % GMV_KT;
-      const bool ok = s < S && k < iend - kb;
-      creg[i] = ok ? a.V[(long)s * N + kb + k] : T(0);
-    }
-  };
-  auto v_store = [&]() {
-#pragma unroll
-    for (int i = 0; i < CIT; ++i) {
-      const int e = tid + GMV_THREADS * i;
-      Cs[e / GMV_KT][e % GMV_KT] = creg[i];
-    }
-  };
-
   typename MM::Acc acc[NST][2], accd[DG][NST][2];
-#pragma unroll
-  for (int st = 0; st < NST; ++st)
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc[st][ct][r] = T(0);
-#pragma unroll
-        for (int k = 0; k < DG; ++k) accd[k][st][ct][r] = T(0);
-      }
-
-  const int nK = (iend - i0 + GMV_KT - 1) / GMV_KT;
-  v_request(i0);
-#pragma nounroll
-  for (int t = 0; t < nK; ++t) {
-    const int kb = i0 + t * GMV_KT;
-    __syncthreads();   // the MFMAs of the step before have read both tiles and the table
-    v_store();
-#pragma unroll
-    for (int i = 0; i < GMV_KT / 2; ++i) {
-      const int r = h + 2 * i;
-      const bool in = r < iend - kb;
-      const T v = rbf(a.x2 + (long)(in ? kb + r : iend - 1) * d);
-      Bs[w][r][c] = in ? v : T(0);
-    }
-    if (fk < DG)   // rows past the chunk's end: the K value is 0, any finite coordinate will do
-      Fs[fk][fr] = fok ? a.x2[(long)(fr < iend - kb ? kb + fr : iend - 1) * d + k0 + fk] : T(0);
-    if (t + 1 < nK) v_request(kb + GMV_KT);   // the next step's V tile is in flight during the MFMAs
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < GMV_KT / 4; ++kk) {
-      const int r = 4 * kk + g;
-      const T b0 = Bs[w][r][l16], b1 = Bs[w][r][16 + l16];
-      T e0[DG], e1[DG];
-#pragma unroll
-      for (int k = 0; k < DG; ++k) {
-        const T f = Fs[k][r];
-        e0[k] = b0 * ((f - xm[0][k]) * ie2[k]), e1[k] = b1 * ((f - xm[1][k]) * ie2[k]);
-      }
-#pragma unroll
-      for (int st = 0; st < NST; ++st) {
-        const T av = Cs[16 * st + l16][4 * kk + g];
-        acc[st][0] = MM::mma(av, b0, acc[st][0]);
-        acc[st][1] = MM::mma(av, b1, acc[st][1]);
-#pragma unroll
-        for (int k = 0; k < DG; ++k) {
-          accd[k][st][0] = MM::mma(av, e0[k], accd[k][st][0]);
-          accd[k][st][1] = MM::mma(av, e1[k], accd[k][st][1]);
-        }
-      }
-    }
-  }
+  gmv_tiles<T, D, NST, DG>(a, s0, k0, acc, accd);
 
   // masked store: register r of lane l is right-hand side s0 + 16 st + row(l, r), column col0 + 16 ct + l % 16
 #pragma unroll

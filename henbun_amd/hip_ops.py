@@ -1531,13 +1531,46 @@ def gram_predict_ws_elems(dtype, n, N, S):
     return int(_lib.lib().raw("hb_gram_predict_ws_elems")(int(n), int(N), int(S), _elem_bytes(dtype)))
 
 
-def _gram_predict_piece(n, N, S, dtype):
-    """Columns per call of gram_predict: the largest multiple of 128 whose workspace fits GRAM_PREDICT_WS_BYTES (at least
-    128), or n when all of x fits."""
-    if gram_predict_ws_elems(dtype, n, N, S) * _elem_bytes(dtype) <= GRAM_PREDICT_WS_BYTES:
+def _gram_piece(ws_elems_of_n, dtype, n):
+    """Columns per call of gram_predict / gram_predict_grad: the largest multiple of 128 whose workspace
+    (ws_elems_of_n(columns) elements) fits GRAM_PREDICT_WS_BYTES (at least 128), or n when all of x fits."""
+    if ws_elems_of_n(n) * _elem_bytes(dtype) <= GRAM_PREDICT_WS_BYTES:
         return max(n, 1)
-    per128 = gram_predict_ws_elems(dtype, 128, N, S) * _elem_bytes(dtype)
+    per128 = ws_elems_of_n(128) * _elem_bytes(dtype)
     return max(int(GRAM_PREDICT_WS_BYTES) // per128, 1) * 128
+
+
+def _gram_predict_piece(n, N, S, dtype):
+    """Columns per call of gram_predict (_gram_piece for its workspace)."""
+    return _gram_piece(lambda m: gram_predict_ws_elems(dtype, m, N, S), dtype, n)
+
+
+def _gram_predict_operands(who, x, x2, ell, V, P, acq, var_floor):
+    """(n, d, N, S, P, code) of the operands of gram_predict / gram_predict_grad, checked: on the device, contiguous,
+    shapes that fit, one dtype, 1 <= P <= S; code: the acquisition's (-1 for None), which needs P == 1 and var_floor >= 0."""
+    for t in (x, x2, ell, V):
+        _chk(t)
+    if x.dim() != 2 or V.dim() != 2 or ell.dim() != 1 or x2.dim() != 2 or x2.shape[1] != x.shape[1]:
+        raise ValueError("%s: x [n, d], x2 [N, d], ell [1] or [d], V [S, N] expected, got %s %s %s %s"
+                         % (who, tuple(x.shape), tuple(x2.shape), tuple(ell.shape), tuple(V.shape)))
+    (n, d), N, S, P = x.shape, x2.shape[0], V.shape[0], int(P)
+    if V.shape[1] != N or N < 1 or ell.numel() not in (1, d):
+        raise ValueError("%s: V must hold N = %d >= 1 columns and ell 1 or %d entries, got %s %s"
+                         % (who, N, d, tuple(V.shape), tuple(ell.shape)))
+    if any(t.dtype != x.dtype for t in (x2, ell, V)):
+        raise TypeError("%s: all operands must share one dtype" % who)
+    if not 1 <= P <= S:
+        raise ValueError("%s: 1 <= P <= S mean rows expected, got P=%d, S=%d" % (who, P, S))
+    if acq is None:
+        return n, d, N, S, P, -1
+    code = ACQ.get(acq, None) if isinstance(acq, str) else acq
+    if code not in ACQ.values():
+        raise ValueError("%s: acq must be one of %s, got %r" % (who, sorted(ACQ), acq))
+    if P != 1:
+        raise ValueError("%s: an acquisition is defined for one latent function only (P=%d)" % (who, P))
+    if not float(var_floor) >= 0.0:
+        raise ValueError("%s: var_floor >= 0 expected (got %r)" % (who, var_floor))
+    return n, d, N, S, P, code
 
 
 def gram_predict(x, x2, ell, V, P=1, scale=1.0, prior=1.0, acq=None, best=0.0, param=0.0, largest=True, var_floor=0.0,
@@ -1554,32 +1587,12 @@ def gram_predict(x, x2, ell, V, P=1, scale=1.0, prior=1.0, acq=None, best=0.0, p
     into pieces of a multiple of 128 columns so that the workspace stays under GRAM_PREDICT_WS_BYTES, the pieces' arg-max
     combined by the same strict rule, and the bits are those of one call."""
     who = "gram_predict"
-    for t in (x, x2, ell, V):
-        _chk(t)
-    if x.dim() != 2 or V.dim() != 2 or ell.dim() != 1 or x2.dim() != 2 or x2.shape[1] != x.shape[1]:
-        raise ValueError("%s: x [n, d], x2 [N, d], ell [1] or [d], V [S, N] expected, got %s %s %s %s"
-                         % (who, tuple(x.shape), tuple(x2.shape), tuple(ell.shape), tuple(V.shape)))
-    (n, d), N, S, P = x.shape, x2.shape[0], V.shape[0], int(P)
-    if V.shape[1] != N or N < 1 or ell.numel() not in (1, d):
-        raise ValueError("%s: V must hold N = %d >= 1 columns and ell 1 or %d entries, got %s %s"
-                         % (who, N, d, tuple(V.shape), tuple(ell.shape)))
-    if any(t.dtype != x.dtype for t in (x2, ell, V)):
-        raise TypeError("%s: all operands must share one dtype" % who)
-    if not 1 <= P <= S:
-        raise ValueError("%s: 1 <= P <= S mean rows expected, got P=%d, S=%d" % (who, P, S))
+    n, d, N, S, P, code = _gram_predict_operands(who, x, x2, ell, V, P, acq, var_floor)
     if acq is None:
-        code = -1
         if value or argmax:
             raise ValueError("%s: value and argmax need an acquisition" % who)
         value = False
     else:
-        code = ACQ.get(acq, None) if isinstance(acq, str) else acq
-        if code not in ACQ.values():
-            raise ValueError("%s: acq must be one of %s, got %r" % (who, sorted(ACQ), acq))
-        if P != 1:
-            raise ValueError("%s: an acquisition is defined for one latent function only (P=%d)" % (who, P))
-        if not float(var_floor) >= 0.0:
-            raise ValueError("%s: var_floor >= 0 expected (got %r)" % (who, var_floor))
         value = (not argmax) if value is None else bool(value)
     if not (mean or var or value or argmax):
         raise ValueError("%s: at least one of mean, var, value, argmax expected" % who)
@@ -1626,11 +1639,8 @@ def gram_predict_grad_ws_elems(dtype, n, N, d, S):
 
 
 def _gram_predict_grad_piece(n, N, d, S, dtype):
-    """Columns per call of gram_predict_grad: as _gram_predict_piece, for its workspace."""
-    if gram_predict_grad_ws_elems(dtype, n, N, d, S) * _elem_bytes(dtype) <= GRAM_PREDICT_WS_BYTES:
-        return max(n, 1)
-    per128 = gram_predict_grad_ws_elems(dtype, 128, N, d, S) * _elem_bytes(dtype)
-    return max(int(GRAM_PREDICT_WS_BYTES) // per128, 1) * 128
+    """Columns per call of gram_predict_grad (_gram_piece for its workspace)."""
+    return _gram_piece(lambda m: gram_predict_grad_ws_elems(dtype, m, N, d, S), dtype, n)
 
 
 def gram_predict_grad(x, x2, ell, V, P=1, scale=1.0, prior=1.0, acq=None, best=0.0, param=0.0, largest=True, var_floor=0.0,
@@ -1644,32 +1654,12 @@ def gram_predict_grad(x, x2, ell, V, P=1, scale=1.0, prior=1.0, acq=None, best=0
     bits of gram_predict.  A column's results do not depend on the other columns: x is cut into pieces of a multiple of
     128 columns so that the workspace stays under GRAM_PREDICT_WS_BYTES, and the bits are those of one call."""
     who = "gram_predict_grad"
-    for t in (x, x2, ell, V):
-        _chk(t)
-    if x.dim() != 2 or V.dim() != 2 or ell.dim() != 1 or x2.dim() != 2 or x2.shape[1] != x.shape[1]:
-        raise ValueError("%s: x [n, d], x2 [N, d], ell [1] or [d], V [S, N] expected, got %s %s %s %s"
-                         % (who, tuple(x.shape), tuple(x2.shape), tuple(ell.shape), tuple(V.shape)))
-    (n, d), N, S, P = x.shape, x2.shape[0], V.shape[0], int(P)
-    if V.shape[1] != N or N < 1 or ell.numel() not in (1, d):
-        raise ValueError("%s: V must hold N = %d >= 1 columns and ell 1 or %d entries, got %s %s"
-                         % (who, N, d, tuple(V.shape), tuple(ell.shape)))
-    if any(t.dtype != x.dtype for t in (x2, ell, V)):
-        raise TypeError("%s: all operands must share one dtype" % who)
-    if not 1 <= P <= S:
-        raise ValueError("%s: 1 <= P <= S mean rows expected, got P=%d, S=%d" % (who, P, S))
+    n, d, N, S, P, code = _gram_predict_operands(who, x, x2, ell, V, P, acq, var_floor)
     if acq is None:
-        code = -1
         if value or dvalue:
             raise ValueError("%s: value and dvalue need an acquisition" % who)
         value = dvalue = False
     else:
-        code = ACQ.get(acq, None) if isinstance(acq, str) else acq
-        if code not in ACQ.values():
-            raise ValueError("%s: acq must be one of %s, got %r" % (who, sorted(ACQ), acq))
-        if P != 1:
-            raise ValueError("%s: an acquisition is defined for one latent function only (P=%d)" % (who, P))
-        if not float(var_floor) >= 0.0:
-            raise ValueError("%s: var_floor >= 0 expected (got %r)" % (who, var_floor))
         value = True if value is None else bool(value)
         dvalue = True if dvalue is None else bool(dvalue)
     if not (mean or var or value or dmean or dvar or dvalue):
