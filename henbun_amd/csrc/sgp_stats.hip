@@ -364,11 +364,16 @@ static inline int st_sgp_A(int kind, const double* x, const double* z, const dou
   return hb_sgp_A_f64(kind, x, 0, z, ell, dl, W, Wf, HB_PREC_NATIVE, A, 1, n, M, d, st);
 }
 
-// hb_sgp_stats_* (WGT false: w NULL) and hb_sgp_wstats_* (WGT true: Y is r [N], P = 1, yy NULL) share every launch
+// hb_sgp_stats_* (WGT false: w NULL) and hb_sgp_wstats_* (WGT true: Y is r [N], P = 1, yy NULL) share every launch.
+// hb_sgp_mwstats_* is the weighted form for C weight sets: set c reads w + c ldw and r + c ldw and writes Phi + c M^2,
+// b + c M, a2sum + c.  A_c is formed ONCE per chunk; the rank update and its fold then run set by set over it, through the
+// one set of partial tiles (the stream orders fold c before update c + 1), so set c sees the launches -- chunk size,
+// K-splits, fold order, mirror -- a hb_sgp_wstats_* call with its w and r would make, and returns its bits.  C = 1: the
+// launches as they were.
 template <typename T, bool WGT>
 static int sgp_stats(const char* who, int kind, const T* X, const T* Y, const T* w, const T* z, const T* ell, long dl, const T* W,
                      const T* Wf, double* Phi, double* b, double* yy, double* a2sum, long N, long M, long d, long P, T* ws,
-                     hipStream_t st) {
+                     hipStream_t st, long C = 1, long ldw = 0) {
   HB_REQUIRE(kind == HB_KERN_RBF, "%s: only the UnitRBF kernel is supported (kind=%d)", who, kind);
   HB_REQUIRE(N >= 1 && M >= 1 && d >= 1 && P >= 1, "%s: bad extents (N=%ld M=%ld d=%ld P=%ld)", who, N, M, d, P);
   HB_REQUIRE(dl == 1 || dl == d, "%s: lengthscales must have 1 or d entries", who);
@@ -377,6 +382,9 @@ static int sgp_stats(const char* who, int kind, const T* X, const T* Y, const T*
   HB_REQUIRE(M * M < 2147483647L && M <= 16384, "%s: M=%ld too large", who, M);
   HB_REQUIRE(!Wf || ((uintptr_t)Wf % 16 == 0 && M % 32 == 0), "%s: Wfrag needs 16-byte alignment and M %% 32 == 0", who);
   HB_REQUIRE(!WGT || (uintptr_t)w % 16 == 0, "%s: the weights need 16-byte alignment", who);
+  HB_REQUIRE(C >= 1 && (C == 1 || (WGT && P == 1 && ldw >= N)), "%s: bad weight sets (C=%ld ldw=%ld N=%ld)", who, C, ldw, N);
+  for (long c = 1; c < C; ++c)
+    HB_REQUIRE((uintptr_t)(w + c * ldw) % 16 == 0, "%s: every row of the weights needs 16-byte alignment (ldw=%ld)", who, ldw);
   const long need = hb_sgp_stats_ws_elems(N, M, d, P, (int)sizeof(T));
   HB_REQUIRE(ws && (uintptr_t)ws % 16 == 0, "%s: needs a 16-byte aligned workspace of %ld elements", who, need);
   const long nc_max = st_chunk_cols(N, M);
@@ -394,38 +402,46 @@ static int sgp_stats(const char* who, int kind, const T* X, const T* Y, const T*
       if (rc) return rc;
     }
     if (no_syrk) continue;
-    if constexpr (sizeof(T) == 4) {
-      if (mfma) {
-        long Tn, nt, ks, splits;
-        st_split(M, nc, &Tn, &nt, &ks, &splits);   // splits <= st_max_splits(Tn): the workspace holds them
-        StatsArgs a;
-        a.A = Abuf; a.ld = nc; a.Y = Y + c0 * P; a.P = P; a.M = M; a.nc = nc; a.ks = ks; a.T = Tn; a.nt = nt;
-        a.w = WGT ? w + c0 : nullptr;   // c0 is a multiple of 32: the chunk's weights stay 16-byte aligned
-        a.part = ws + st_round(M * nc_max);
-        a.bpart = a.part + st_round(st_max_splits(Tn) * Tn * ST_TILE);
-        const dim3 grid((unsigned)(Tn * splits), 1, 1);
-        if (nc % 4 == 0)
-          hipLaunchKernelGGL((sgp_stats_syrk_kernel<true, WGT>), grid, dim3(ST_THREADS), 0, st, a);
-        else
-          hipLaunchKernelGGL((sgp_stats_syrk_kernel<false, WGT>), grid, dim3(ST_THREADS), 0, st, a);
-        HB_LAUNCH_CHECK();
-        const long fb = 64 * Tn + (P * M + 255) / 256 + 1;
-        hipLaunchKernelGGL(sgp_stats_fold_kernel, dim3((unsigned)fb), dim3(256), 0, st, a.part, a.bpart, Tn, nt, splits, M, P,
-                           Phi, b, a.Y, nc, yy, accumulate);
-        HB_LAUNCH_CHECK();
-        continue;
+    for (long c = 0; c < C; ++c) {
+      const T* Yc = Y + c * ldw + c0 * P;                       // C > 1: P == 1
+      const T* wc = WGT ? w + c * ldw + c0 : nullptr;           // c0 is a multiple of 32: the chunk's weights stay 16-byte aligned
+      double* Phic = Phi + c * M * M;
+      double* bc = b + c * P * M;
+      if constexpr (sizeof(T) == 4) {
+        if (mfma) {
+          long Tn, nt, ks, splits;
+          st_split(M, nc, &Tn, &nt, &ks, &splits);   // splits <= st_max_splits(Tn): the workspace holds them
+          StatsArgs a;
+          a.A = Abuf; a.ld = nc; a.Y = Yc; a.P = P; a.M = M; a.nc = nc; a.ks = ks; a.T = Tn; a.nt = nt;
+          a.w = wc;
+          a.part = ws + st_round(M * nc_max);
+          a.bpart = a.part + st_round(st_max_splits(Tn) * Tn * ST_TILE);
+          const dim3 grid((unsigned)(Tn * splits), 1, 1);
+          if (nc % 4 == 0)
+            hipLaunchKernelGGL((sgp_stats_syrk_kernel<true, WGT>), grid, dim3(ST_THREADS), 0, st, a);
+          else
+            hipLaunchKernelGGL((sgp_stats_syrk_kernel<false, WGT>), grid, dim3(ST_THREADS), 0, st, a);
+          HB_LAUNCH_CHECK();
+          const long fb = 64 * Tn + (P * M + 255) / 256 + 1;
+          hipLaunchKernelGGL(sgp_stats_fold_kernel, dim3((unsigned)fb), dim3(256), 0, st, a.part, a.bpart, Tn, nt, splits, M, P,
+                             Phic, bc, a.Y, nc, yy, accumulate);
+          HB_LAUNCH_CHECK();
+          continue;
+        }
       }
+      const long nb = (M + ST_PLAIN_T - 1) / ST_PLAIN_T;
+      hipLaunchKernelGGL((sgp_stats_plain_phi_kernel<T, WGT>), dim3((unsigned)nb, (unsigned)nb, 1), dim3(ST_PLAIN_T, ST_PLAIN_T),
+                         0, st, Abuf, nc, M, nc, wc, Phic, accumulate);
+      HB_LAUNCH_CHECK();
+      hipLaunchKernelGGL((sgp_stats_plain_b_kernel<T>), dim3((unsigned)((P * M + 255) / 256 + 1)), dim3(256), 0, st, Abuf, nc, Yc,
+                         M, P, nc, bc, yy, accumulate);
+      HB_LAUNCH_CHECK();
     }
-    const long nb = (M + ST_PLAIN_T - 1) / ST_PLAIN_T;
-    hipLaunchKernelGGL((sgp_stats_plain_phi_kernel<T, WGT>), dim3((unsigned)nb, (unsigned)nb, 1), dim3(ST_PLAIN_T, ST_PLAIN_T), 0,
-                       st, Abuf, nc, M, nc, WGT ? w + c0 : nullptr, Phi, accumulate);
-    HB_LAUNCH_CHECK();
-    hipLaunchKernelGGL((sgp_stats_plain_b_kernel<T>), dim3((unsigned)((P * M + 255) / 256 + 1)), dim3(256), 0, st, Abuf, nc,
-                       Y + c0 * P, M, P, nc, b, yy, accumulate);
+  }
+  for (long c = 0; c < C; ++c) {
+    hipLaunchKernelGGL(sgp_stats_finish_kernel, dim3(hb_stream_grid(M * M, 256)), dim3(256), 0, st, Phi + c * M * M, M, a2sum + c);
     HB_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(sgp_stats_finish_kernel, dim3(hb_stream_grid(M * M, 256)), dim3(256), 0, st, Phi, M, a2sum);
-  HB_LAUNCH_CHECK();
   return 0;
 }
 
@@ -456,4 +472,24 @@ extern "C" int hb_sgp_wstats_f64(int kind, const double* X, const double* w, con
                                  long M, long d, double* ws, void* stream) {
   return sgp_stats<double, true>("hb_sgp_wstats", kind, X, r, w, z, ell, dl, W, Wfrag, Phi, b, nullptr, tr, N, M, d, 1, ws,
                                  (hipStream_t)stream);
+}
+
+// Weighted statistics for C weight sets from ONE A (hb_sgp_mwstats_*; the data pass of a natural-gradient step on C
+// independent q(u_c) that share z, the lengthscales and W: SparseGP.natgrad_q with a multi-latent likelihood).  The
+// partial tiles are reused set by set, so the workspace is that of hb_sgp_wstats_*, whatever C.
+extern "C" long hb_sgp_mwstats_ws_elems(long N, long M, long d, long C, int dtype_bytes) {
+  (void)C;
+  return hb_sgp_stats_ws_elems(N, M, d, 1, dtype_bytes);
+}
+extern "C" int hb_sgp_mwstats_f32(int kind, const float* X, const float* w, const float* r, long ldw, const float* z,
+                                  const float* ell, long dl, const float* W, const float* Wfrag, double* Phi, double* b, double* tr,
+                                  long N, long M, long d, long C, float* ws, void* stream) {
+  return sgp_stats<float, true>("hb_sgp_mwstats", kind, X, r, w, z, ell, dl, W, Wfrag, Phi, b, nullptr, tr, N, M, d, 1, ws,
+                                (hipStream_t)stream, C, ldw);
+}
+extern "C" int hb_sgp_mwstats_f64(int kind, const double* X, const double* w, const double* r, long ldw, const double* z,
+                                  const double* ell, long dl, const double* W, const double* Wfrag, double* Phi, double* b,
+                                  double* tr, long N, long M, long d, long C, double* ws, void* stream) {
+  return sgp_stats<double, true>("hb_sgp_mwstats", kind, X, r, w, z, ell, dl, W, Wfrag, Phi, b, nullptr, tr, N, M, d, 1, ws,
+                                 (hipStream_t)stream, C, ldw);
 }

@@ -220,7 +220,12 @@ class SparseInference:
         restrictions and exception types as statistics(); residual 'fullrank' and a mean-field q0 raise
         NotImplementedError; a Lambda that is not positive definite raises graph.CholeskyError.  A full step (rho = 1)
         is not guaranteed to raise the ELBO from a q far from the optimum (info['elbo'] shows an overshoot): start at
-        the prior or damp with rho < 1."""
+        the prior or damp with rho < 1.
+
+        A likelihood with num_latent = C > 1 (likelihoods.Softmax) fits C independent q(u_c) that share z, the
+        lengthscales and W: see _natgrad_q_multi for its Y, q0 and return shapes."""
+        if getattr(likelihood, "num_latent", 1) > 1:
+            return self._natgrad_q_multi(X, Y, likelihood, k_var, residual, q0, steps, rho, tol)
         sess, zvar, ls = self._stats_session("natgrad_q")
         torch, H = sess.torch, sess.H
         Xd, Yd = _host.device_data(sess, X, "X"), _host.device_data(sess, Y, "Y")
@@ -262,6 +267,101 @@ class SparseInference:
                         + 2.0 * float(np.log(np.diagonal(L.cpu().numpy())).sum()))
             elbo.append(float(lsum.cpu()[0]) - kl)
             resid.append(float(((Lam - Lt).abs().max() / Lt.abs().max()).cpu()))
+            if it == steps or (it > 0 and abs(elbo[-1] - elbo[-2]) <= tol * abs(elbo[-1])):
+                break
+            Lam, eta = (1.0 - rho) * Lam + rho * Lt, (1.0 - rho) * eta + rho * et
+        return (m.cpu().numpy(), np.tril(S.cpu().numpy()),
+                dict(elbo=np.asarray(elbo), residual=np.asarray(resid), steps=it))
+
+    def _natgrad_q_multi(self, X, Y, likelihood, k_var, residual, q0, steps, rho, tol):
+        """natgrad_q for a likelihood over C = likelihood.num_latent latent functions (likelihoods.Softmax): the whitened
+        model u_c ~ N(0, I_M) independent, f_c = sqrt(k_var) (u_c A + residual), y_j in {0 .. C-1}, with C independent
+        q(u_c) = N(m_c, S_c S_c^T) kept as Lambda_c, eta_c.  One step:
+            mu_jc, v_jc              C calls of hb_sgp_predict, one per (m_c, S_c)
+            lam_jc, beta_jc, l_j     ONE hb_lik_softmax_sites over the likelihood's nodes [S, C]
+            Phi_c, b_c               ONE hb_sgp_mwstats: A = W K(z, X) is formed once per chunk for all C weight sets
+            Lambda_c <- (1 - rho) Lambda_c + rho (I + k_var Phi_c),   eta_c <- (1 - rho) eta_c + rho sqrt(k_var) b_c
+        and C float64 tails.  ELBO = sum_j l_j - sum_c KL(q_c || N(0, I)); the residual is the largest over the classes.
+        Y [N, 1]: the labels (a numpy Y is checked on the host to hold integers in 0 .. C-1; labels already on the device
+        are the caller's duty).  q0 = (m [C, M], S [C, M, M]) or None (the prior).  Returns (m [C, M], S [C, M, M] lower,
+        info) as float64 numpy, info as for one latent function.  The ELBO is a fixed-node sum and lam is Price's form, not
+        the derivative of that sum: from step to step the ELBO can wiggle by about 1e-4 near the fixed point.  A full step
+        (rho = 1) does not settle (it cycles or diverges, see likelihoods.Softmax); the likelihood's natgrad_rho (0.5) is
+        what models.SVGPMulticlass passes.  residual 'fullrank' and a mean-field q0 raise NotImplementedError, other shapes ValueError."""
+        who = "natgrad_q"
+        _check_residual(residual)
+        if not isinstance(likelihood, Likelihood):
+            raise TypeError("%s: likelihood must be a henbun_amd.likelihoods.Likelihood, got %s" % (who, type(likelihood).__name__))
+        C = int(likelihood.num_latent)
+        if not float(k_var) > 0.0:
+            raise ValueError("%s: k_var must be positive (got %r)" % (who, k_var))
+        k_var, rho, steps = float(k_var), float(rho), int(steps)
+        if not (0.0 < rho <= 1.0 and steps >= 0):
+            raise ValueError("%s: 0 < rho <= 1 and steps >= 0 expected (got %r, %r)" % (who, rho, steps))
+        if q0 is not None:
+            m0, S0 = (np.asarray(a, dtype=np.float64) for a in q0)
+            if S0.ndim == 2 and S0.shape == m0.shape:
+                raise NotImplementedError("%s: q0 must be full-rank, (m [C, M], S [C, M, M]); a mean-field q is not covered" % who)
+            if m0.ndim != 2 or m0.shape[0] != C or S0.shape != (C, m0.shape[1], m0.shape[1]):
+                raise ValueError("%s: q0 = (m [%d, M], S [%d, M, M]) expected, got %s %s" % (who, C, C, m0.shape, S0.shape))
+        if isinstance(Y, np.ndarray):
+            if Y.ndim != 2 or Y.shape[1] != 1:
+                raise ValueError("%s: Y must hold the labels as [N, 1], got %s" % (who, Y.shape))
+            if not (np.all(Y == np.floor(Y)) and Y.size and Y.min() >= 0 and Y.max() <= C - 1):
+                raise ValueError("%s: the labels must be integers in 0 .. %d" % (who, C - 1))
+        sess, zvar, ls = self._stats_session(who)
+        torch, H = sess.torch, sess.H
+        Xd, Yd = _host.device_data(sess, X, "X"), _host.device_data(sess, Y, "Y")
+        M = int(zvar.shape[0])
+        if Yd.dim() != 2 or Yd.shape[1] != 1:
+            raise ValueError("%s: Y must hold the labels as [N, 1], got %s" % (who, tuple(Yd.shape)))
+        if q0 is not None and m0.shape[1] != M:
+            raise ValueError("%s: q0 = (m [%d, %d], S [%d, %d, %d]) expected, got %s %s" % (who, C, M, C, M, M, m0.shape, S0.shape))
+        z, ell, W, frag = self._whitening(sess, zvar, ls, Xd, Yd, who, as_plans=True)
+        N, d = Xd.shape
+        dt = sess.torch_dtype
+        f64 = dict(dtype=torch.float64, device=sess.device)
+        eye = torch.eye(M, **f64)
+        if q0 is None:
+            Lam, eta = eye.repeat(C, 1, 1), torch.zeros((C, M), **f64)
+        else:
+            Lam, eta = torch.empty((C, M, M), **f64), torch.empty((C, M), **f64)
+            for c in range(C):
+                Sinv = H.trinv(_host.upload(sess, np.tril(S0[c]), np.float64))
+                Lam[c] = H.matmul(Sinv, Sinv, transA=True)
+                eta[c:c + 1] = H.matmul(_host.upload(sess, m0[c].reshape(1, M), np.float64), Lam[c].contiguous())
+        nodes = _host.upload(sess, likelihood.nodes(), np.float64)
+        yv = Yd.reshape(-1).contiguous()
+        mode = H.SGP_DIAGONAL if residual == "diagonal" else H.SGP_NEGLECTED
+        fused = bool(getattr(settings.runtime, "fused_predict", True)) and H.sgp_predict_fused(
+            dt, 1, N, M, d, 1, H.SGP_S_TRIL, frag is not None)
+        ldw = -(-N // 4) * 4                        # rows padded to 16 bytes: what hb_sgp_mwstats asks of the weights
+        mean = torch.empty((C, N), dtype=dt, device=sess.device)
+        var = torch.empty_like(mean)
+        lam, beta = (torch.zeros((C, ldw), dtype=dt, device=sess.device) for _ in range(2))
+        lam_c, beta_c = (lam, beta) if ldw == N else (torch.empty_like(mean), torch.empty_like(mean))
+        m, S = torch.empty((C, M), **f64), torch.empty((C, M, M), **f64)
+        elbo, resid = [], []
+        for it in range(steps + 1):
+            kl = 0.0
+            for c in range(C):
+                whoc = "natgrad_q (step %d, class %d)" % (it, c)
+                L, V, t = _q_tail(H, Lam[c], eta[c:c + 1], whoc)
+                mc = H.matmul(t, V)
+                Sig, Sc = _q_cov(H, V, whoc)
+                m[c:c + 1], S[c] = mc, Sc
+                H.sgp_predict(Xd, z, ell, W, mc.to(dt), Sc.to(dt), s_kind=H.SGP_S_TRIL, mode=mode,
+                              out=(mean[c:c + 1], var[c:c + 1]), wfrag=frag if fused else None)
+                kl += 0.5 * (float(torch.diagonal(Sig).sum().cpu()) + float((mc * mc).sum().cpu()) - M
+                             + 2.0 * float(np.log(np.diagonal(L.cpu().numpy())).sum()))
+            _, _, lsum = H.lik_softmax_sites(yv, mean, var, nodes, mscale=np.sqrt(k_var), vscale=k_var, out=(lam_c, beta_c))
+            if lam_c is not lam:
+                lam[:, :N].copy_(lam_c)
+                beta[:, :N].copy_(beta_c)
+            Phi, b, _ = H.sgp_mwstats(Xd, lam[:, :N], beta[:, :N], z, ell, W, wfrag=frag)
+            Lt, et = Phi * k_var + eye, b * np.sqrt(k_var)
+            elbo.append(float(lsum.cpu()[0]) - kl)
+            resid.append(float(((Lam - Lt).abs().amax(dim=(1, 2)) / Lt.abs().amax(dim=(1, 2))).max().cpu()))
             if it == steps or (it > 0 and abs(elbo[-1] - elbo[-2]) <= tol * abs(elbo[-1])):
                 break
             Lam, eta = (1.0 - rho) * Lam + rho * Lt, (1.0 - rho) * eta + rho * et
@@ -392,7 +492,14 @@ class SparseInference:
         sum_j dl_j / dparam at the marginals of that q (hb_lik_param_grad_f64 on every chunk of the same walk, added in
         chunk order).  Like the other entries it is the partial derivative at fixed q, hence the total derivative at the
         fitted q.  A likelihood that is not `trainable` raises ValueError.  The other entries and the value are the bits
-        of lik_grad=False."""
+        of lik_grad=False.
+
+        A likelihood over several latent functions (likelihoods.Softmax) raises NotImplementedError: its value is a
+        fixed-node sum, and a gradient consistent with it is not settled ("Multi-class classification")."""
+        if getattr(likelihood, "num_latent", 1) > 1:
+            raise NotImplementedError("elbo_and_grad: one latent function only (%s has %d; the hyper-parameters of a "
+                                      "multi-latent model train through its sampled ELBO)"
+                                      % (type(likelihood).__name__, likelihood.num_latent))
         if lik_grad and not getattr(likelihood, "trainable", False):
             raise ValueError("elbo_and_grad: lik_grad=True needs a likelihood with a continuous parameter (got %s)"
                              % type(likelihood).__name__)

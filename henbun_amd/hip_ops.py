@@ -46,6 +46,7 @@ PWACQ = {k[len("HB_PWACQ_"):].lower(): v for k, v in _C.items() if k.startswith(
 PREC_NATIVE, PREC_BF16X3 = _hb("PREC_NATIVE", "PREC_BF16X3")
 LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON = _hb("LIK_GAUSSIAN", "LIK_BERNOULLI", "LIK_POISSON")
 LIK_LAPLACE, LIK_GAMMA, LIK_NEGBINOMIAL, LIK_BINOMIAL = _hb("LIK_LAPLACE", "LIK_GAMMA", "LIK_NEGBINOMIAL", "LIK_BINOMIAL")
+LIK_SOFTMAX = _C["HB_LIK_SOFTMAX"]
 MATUTIL_BAND, MATUTIL_ADD_EYE, MATUTIL_PHI, MATUTIL_SYM, MATUTIL_SYMLOW = _hb("MATUTIL_BAND", "MATUTIL_ADD_EYE", "MATUTIL_PHI",
                                                                               "MATUTIL_SYM", "MATUTIL_SYMLOW")
 
@@ -1339,6 +1340,49 @@ def sgp_wstats(X, w, r, z, ell, W, wfrag=None, ws=None):
     return Phi, b, tr
 
 
+def sgp_mwstats_ws_elems(dtype, N, M, d, C):
+    """Scratch elements hb_sgp_mwstats needs: those of hb_sgp_wstats, whatever C (the partial tiles are reused set by set)."""
+    return int(_lib.lib().raw("hb_sgp_mwstats_ws_elems")(int(N), int(M), int(d), int(C), _elem_bytes(dtype)))
+
+
+def sgp_mwstats(X, w, r, z, ell, W, wfrag=None, ws=None):
+    """Weighted statistics of C weight sets from ONE A = W K(z, X) (hb_sgp_mwstats): w [C, N], r [C, N] ->
+    (Phi [C, M, M], b [C, M], tr [C]) as FLOAT64 device tensors, Phi_c = A diag(w_c) A^T, b_c = (A r_c)^T.  A is formed once
+    per column chunk, the rank update runs set by set over it: set c has the BITS of sgp_wstats(X, w[c], r[c], ..).  The
+    rows of w and r may be padded (stride(0) >= N, stride(1) == 1); every row of w must start 16-byte aligned, which a
+    contiguous [C, N] float32 pair meets when N % 4 == 0 -- otherwise w and r are copied once into rows padded to a
+    multiple of 4."""
+    for t in (X, z, ell, W):
+        _chk(t)
+    if (X.dim() != 2 or z.dim() != 2 or X.shape[1] != z.shape[1] or w.dim() != 2 or w.shape != r.shape
+            or w.shape[1] != X.shape[0] or w.shape[0] < 1):
+        raise ValueError("sgp_mwstats: X [N, d], w [C, N], r [C, N], z [M, d] expected, got %s %s %s %s"
+                         % (tuple(X.shape), tuple(w.shape), tuple(r.shape), tuple(z.shape)))
+    dt, dev = X.dtype, X.device
+    if any(t.dtype != dt for t in (w, r, z, ell, W)) or not (w.is_cuda and r.is_cuda):
+        raise TypeError("sgp_mwstats: all operands must live on the GPU and share one dtype")
+    N, d = X.shape
+    M, C = z.shape[0], w.shape[0]
+    per16 = 16 // _elem_bytes(dt)
+    ldw = w.stride(0) if C > 1 else N
+    if (w.stride(1) != 1 or r.stride(1) != 1 or (C > 1 and (r.stride(0) != ldw or ldw < N or ldw % per16))
+            or w.data_ptr() % 16):
+        ldw = -(-N // per16) * per16
+        wp, rp = (_empty((C, ldw), dtype=dt, device=dev) for _ in range(2))
+        wp[:, :N].copy_(w)
+        rp[:, :N].copy_(r)
+        w, r = wp, rp
+    Phi = _empty((C, M, M), dtype=torch.float64, device=dev)
+    b = _empty((C, M), dtype=torch.float64, device=dev)
+    tr = _empty((C,), dtype=torch.float64, device=dev)
+    if ws is None:
+        ws = workspace(dt, dev, max(sgp_mwstats_ws_elems(dt, N, M, d, C), 1))
+    assert ws.numel() >= sgp_mwstats_ws_elems(dt, N, M, d, C), "hb_sgp_mwstats: workspace too small (sgp_mwstats_ws_elems)"
+    _lib.lib().call("hb_sgp_mwstats" + _suf(X), KERN_RBF, _p(X), _p(w), _p(r), ldw, _p(z), _p(ell), ell.numel(), _p(W),
+                    _p(wfrag), _p(Phi), _p(b), _p(tr), N, M, d, C, _p(ws), stream())
+    return Phi, b, tr
+
+
 def sgp_pathwise(x, omega, z, ell, coef, scale=1.0, out=None):
     """S pathwise function draws at the rows of x (hb_sgp_pathwise): out [S, n] = scale coef [S, 2L + M] B(x) with
     B = [cos / sin (omega_l . x / ell) interleaved | K(z_m, x)] synthesised inside the ONE launch.  x [n, d], omega [L, d],
@@ -1857,6 +1901,51 @@ def lik_predict(lik, mean, var, param=1.0):
     _lib.lib().call("hb_lik_predict" + _suf(mean), int(lik), _p(mean), _p(var), float(param), _p(ym), _p(yv), mean.numel(),
                     stream())
     return ym, yv
+
+
+def _softmax_inputs(who, y, mean, var, nodes):
+    """(N, C, S) of mean, var [C, N], nodes [S, C] float64 and, when given, y [N]."""
+    for t in (mean, var, nodes) + (() if y is None else (y,)):
+        _chk(t)
+    if mean.dim() != 2 or var.shape != mean.shape or var.dtype != mean.dtype:
+        raise ValueError("%s: mean and var must be [C, N] of one dtype, got %s %s" % (who, tuple(mean.shape), tuple(var.shape)))
+    C, N = mean.shape
+    if nodes.dim() != 2 or nodes.shape[1] != C or nodes.dtype != torch.float64:
+        raise ValueError("%s: nodes must be float64 [S, %d], got %s %s" % (who, C, nodes.dtype, tuple(nodes.shape)))
+    if y is not None and (y.numel() != N or y.dtype != mean.dtype):
+        raise ValueError("%s: y must hold N = %d labels in the dtype of mean" % (who, N))
+    return N, C, nodes.shape[0]
+
+
+def lik_softmax_sites(y, mean, var, nodes, mscale=1.0, vscale=1.0, out=None):
+    """Sites of the softmax likelihood under C independent marginals f_jc ~ N(mscale mean[c, j], vscale var[c, j])
+    (hb_lik_softmax_sites): (lam [C, N], beta [C, N]) in the dtype of the inputs and sum_j E[log softmax(f_j)_{y_j}] as a
+    float64 device tensor [1], the expectations taken over the S standard-normal nodes [S, C] (float64) shared by all
+    points.  y [N]: labels 0 .. C-1 stored in the dtype of mean.  lam = mean_s p (1 - p) >= 0.  Double arithmetic; two
+    calls return the same bits."""
+    N, C, S = _softmax_inputs("lik_softmax_sites", y, mean, var, nodes)
+    lam, beta = out if out is not None else (_empty_like(mean), _empty_like(mean))
+    lsum = _empty((1,), dtype=torch.float64, device=mean.device)
+    ws = workspace(torch.float64, mean.device, int(_lib.lib().raw("hb_lik_softmax_ws_elems")(N, C)))
+    _lib.lib().call("hb_lik_softmax_sites" + _suf(mean), _p(y), _p(mean), _p(var), float(mscale), float(vscale), _p(nodes), S,
+                    _p(lam), _p(beta), _p(lsum), N, C, _p(ws), stream())
+    return lam, beta, lsum
+
+
+def lik_softmax_predict(mean, var, nodes, y=None, mscale=1.0, vscale=1.0, prob=True, pointwise=True):
+    """Predictive of the softmax likelihood (hb_lik_softmax_predict): (prob [C, n] = mean_s softmax(f_s), or None with
+    prob=False; logdens [n] = log mean_s softmax(f_s)_{y_j}, or None without y or with pointwise=False; their sum as a
+    float64 device tensor [1], or None without y).  Inputs as for lik_softmax_sites."""
+    n, C, S = _softmax_inputs("lik_softmax_predict", y, mean, var, nodes)
+    if y is None and not prob:
+        raise ValueError("lik_softmax_predict: nothing asked for (no y and prob=False)")
+    pr = _empty_like(mean) if prob else None
+    ld = _empty((n,), dtype=mean.dtype, device=mean.device) if (y is not None and pointwise) else None
+    total = _empty((1,), dtype=torch.float64, device=mean.device) if y is not None else None
+    ws = workspace(torch.float64, mean.device, int(_lib.lib().raw("hb_lik_softmax_ws_elems")(n, C)))
+    _lib.lib().call("hb_lik_softmax_predict" + _suf(mean), _p(y), _p(mean), _p(var), float(mscale), float(vscale), _p(nodes), S,
+                    _p(pr), _p(ld), _p(total), n, C, _p(ws), stream())
+    return pr, ld, total
 
 
 def sgp_kgrad_ws_elems(N, M, d, P):

@@ -12,6 +12,8 @@ and its closed-form fit use one likelihood.
     Exponential()                Gamma(1)
     NegativeBinomial(dispersion) y in {0, 1, ..}, mean exp(f), variance mean + mean^2 / dispersion   trainable (dispersion)
     Binomial(total_count)        y successes out of total_count trials, logit link
+    Softmax(num_classes)         y in {0, .., C - 1}, p(y = c | f) = softmax(f)_c: C latent functions (num_latent = C),
+                                 its own native entries hb_lik_softmax_*, natgrad_rho = 0.5
 
 All are log-concave in f, which keeps the natural-gradient step positive definite.  `trainable` says that the parameter
 is continuous and has a gradient (hb_lik_param_grad_*): SparseGP.elbo_and_grad(lik_grad=True) returns it and
@@ -23,12 +25,15 @@ from __future__ import annotations
 import copy
 import math
 
+import numpy as np
+
 from . import densities, tf
 from . import graph as G
 
 
 class Likelihood:
     lik_id = None
+    num_latent = 1      # latent functions per data point (Softmax: the number of classes)
     param = 1.0
     trainable = False
     param_name = None
@@ -174,3 +179,58 @@ class Binomial(Likelihood):
         const = G.affine(G.add(G.unary("LGAMMA", G.affine(y, 1.0, 1.0)), G.unary("LGAMMA", G.affine(y, -1.0, n + 1.0))),
                          -1.0, math.lgamma(n + 1.0))
         return G.add(const, G.sub(G.mul(y, f), G.affine(tf.nn.softplus(f), n)))
+
+
+class Softmax(Likelihood):
+    """Multi-class classification: y in {0, .., C - 1}, p(y = c | f) = softmax(f)_c over num_classes = C latent functions
+    (the only likelihood here with num_latent > 1; SparseGP.natgrad_q fits C independent q(u_c), models.SVGPMulticlass is
+    the model).  E log softmax(f)_y under C independent Gaussian marginals is a C-dimensional expectation: it is taken over
+    num_nodes standard-normal draws eps [S, C] shared by all points and fixed for the life of the object (a fixed-node
+    sum, so a fit is deterministic).  `nodes()` returns them: drawn on the device from hip_ops.Rng(seed) on first use, or
+    the array handed in as `nodes` ([S, C], any S in 1 .. 1024).  128 nodes is a default, not a measurement.  The curvature
+    site is Price's form mean_s p (1 - p) >= 0, which keeps every Lambda_c positive definite.  A full natural-gradient step
+    does not settle with it (tests/softmax_ref.py on blobs on a ring, k_var = 4: three classes end in a period-2 cycle
+    between ELBO -51 and -140, ten classes diverge past -40000 within 10 steps); rho = 0.5 converges, hence natgrad_rho."""
+
+    lik_id = 32
+    natgrad_rho = 0.5
+    MAX_CLASSES, MAX_NODES = 64, 1024
+
+    def __init__(self, num_classes, num_nodes=128, seed=0, nodes=None):
+        C = int(num_classes)
+        if C != num_classes or not 2 <= C <= self.MAX_CLASSES:
+            raise ValueError("Softmax: num_classes must be an integer in 2 .. %d (got %r)" % (self.MAX_CLASSES, num_classes))
+        self.num_classes = self.num_latent = C
+        self.seed = int(seed)
+        self._nodes = None
+        if nodes is not None:
+            nodes = np.array(nodes, dtype=np.float64)
+            if nodes.ndim != 2 or nodes.shape[1] != C or not 1 <= nodes.shape[0] <= self.MAX_NODES or not np.all(np.isfinite(nodes)):
+                raise ValueError("Softmax: nodes must be a finite [S, %d] array with 1 <= S <= %d (got shape %s)"
+                                 % (C, self.MAX_NODES, nodes.shape))
+            self._nodes, num_nodes = nodes, nodes.shape[0]
+        S = int(num_nodes)
+        if S != num_nodes or not 1 <= S <= self.MAX_NODES:
+            raise ValueError("Softmax: num_nodes must be an integer in 1 .. %d (got %r)" % (self.MAX_NODES, num_nodes))
+        self.num_nodes = S
+
+    def _check(self, value):
+        raise ValueError("Softmax has no parameter")
+
+    def nodes(self):
+        """The [S, C] float64 standard-normal nodes (numpy): the injected array, or drawn once from hip_ops.Rng(seed)."""
+        if self._nodes is None:
+            import torch
+
+            from . import hip_ops
+
+            self._nodes = hip_ops.Rng(self.seed).normal((self.num_nodes, self.num_classes), dtype=torch.float64).cpu().numpy()
+        return self._nodes
+
+    def logp(self, f, y, param=None):
+        """log softmax(f)_y as a graph expression [1, n]: f [C, n], y the ONE-HOT labels [C, n];
+        sum_c y_c f_c - logsumexp_c f, the log-sum-exp shifted by the maximum over classes."""
+        f, y = G.as_tensor(f), G.as_tensor(y)
+        top = tf.reduce_max(f, 0, keep_dims=True)
+        lse = G.add(top, tf.log(tf.reduce_sum(tf.exp(G.sub(f, top)), 0, keep_dims=True)))
+        return G.sub(tf.reduce_sum(G.mul(y, f), 0, keep_dims=True), lse)

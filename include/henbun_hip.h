@@ -68,7 +68,9 @@ extern "C" {
  * predictive mean, cached upper bound of the predictive variance and closed-form acquisition from one kernel product);
  * hb_matmul_gram_vjp_tiles_ok / _tiles_f32 and hb_gram_tiles_fold_f32 (the Gram VJP's tile partials from the product that
  * computes Kbar, folded at the head of a serial chain); hb_gram_predict_grad_f32 / _f64 and hb_gram_predict_grad_ws_elems
- * (exact GP: input gradients of the cached predictive and of its closed-form acquisition). */
+ * (exact GP: input gradients of the cached predictive and of its closed-form acquisition); hb_lik_softmax_sites_f32 /
+ * _f64, hb_lik_softmax_predict_f32 / _f64, hb_lik_softmax_ws_elems, HB_LIK_SOFTMAX, hb_sgp_mwstats_f32 / _f64 and
+ * hb_sgp_mwstats_ws_elems (multi-class classification: softmax sites, weighted statistics of C weight sets from one A). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -710,6 +712,22 @@ int hb_sgp_wstats_f32(int kind, const float* X, const float* w, const float* r, 
 int hb_sgp_wstats_f64(int kind, const double* X, const double* w, const double* r, const double* z, const double* ell, long dl,
                       const double* W, const double* Wfrag, double* Phi, double* b, double* tr, long N, long M, long d,
                       double* ws, void* stream);
+/* hb_sgp_wstats_* for C weight sets from ONE A (csrc/sgp_stats.hip; not in the reference): the data pass of a
+ * natural-gradient step on C independent q(u_c) that share z, the lengthscales and W (SparseGP.natgrad_q with a
+ * multi-latent likelihood).  Row c of w and r starts at w + c ldw, r + c ldw (ldw >= N; C = 1: ldw is not read):
+ *   Phi [C, M, M]: Phi_c = A diag(w_c) A^T,   b [C, M]: b_c = (A r_c)^T,   tr [C]: tr Phi_c.
+ * Per column chunk hb_sgp_A_* runs once; the rank update and its fold then run set by set over that A_c through one set
+ * of partial tiles.  Chunk size, K-splits, fold order and mirror are those of hb_sgp_wstats_*: Phi_c, b_c, tr_c have the
+ * BITS of hb_sgp_wstats_*(w_c, r_c).  Every row of w must start 16-byte aligned (fp32: ldw % 4 == 0 when C > 1); refused
+ * before any launch otherwise.  ws >= hb_sgp_mwstats_ws_elems(N, M, d, C, sizeof(T)) elements of T -- those of
+ * hb_sgp_wstats_ws_elems, whatever C. */
+long hb_sgp_mwstats_ws_elems(long N, long M, long d, long C, int dtype_bytes);
+int hb_sgp_mwstats_f32(int kind, const float* X, const float* w, const float* r, long ldw, const float* z, const float* ell,
+                       long dl, const float* W, const float* Wfrag, double* Phi, double* b, double* tr, long N, long M, long d,
+                       long C, float* ws, void* stream);
+int hb_sgp_mwstats_f64(int kind, const double* X, const double* w, const double* r, long ldw, const double* z, const double* ell,
+                       long dl, const double* W, const double* Wfrag, double* Phi, double* b, double* tr, long N, long M, long d,
+                       long C, double* ws, void* stream);
 /* Sites of a factorising likelihood under Gaussian marginals (csrc/lik_sites.hip; not in the reference).  For
  * f_j ~ N(mu_j, v_j), mu_j = mscale mean[j], v_j = vscale var[j] (the scales take the unit-variance moments of
  * hb_sgp_predict_* to those of f = sqrt(k_var) (..): mscale = sqrt(k_var), vscale = k_var):
@@ -769,7 +787,8 @@ enum {
   HB_LIK_LAPLACE = 16,
   HB_LIK_GAMMA = 17,
   HB_LIK_NEGBINOMIAL = 18,
-  HB_LIK_BINOMIAL = 19
+  HB_LIK_BINOMIAL = 19,
+  HB_LIK_SOFTMAX = 32   /* C latent functions: served by hb_lik_softmax_*, refused by the entries above */
 };
 long hb_lik_sites_ws_elems(long N);
 int hb_lik_sites_f32(int lik, const float* y, const float* mean, const float* var, double mscale, double vscale, double param,
@@ -789,6 +808,35 @@ int hb_lik_logdens_f32(int lik, const float* y, const float* mean, const float* 
                        float* out, double* sum, long N, double* ws, void* stream);
 int hb_lik_logdens_f64(int lik, const double* y, const double* mean, const double* var, double mscale, double vscale,
                        double param, double* out, double* sum, long N, double* ws, void* stream);
+/* Softmax (multi-class) likelihood under C independent Gaussian marginals (csrc/lik_softmax.hip; not in the reference).
+ * y [N] holds the labels 0 .. C-1 as numbers of the storage type (labels outside that range ARE THE CALLER'S DUTY: such a
+ * point gets g = -mean_s p and contributes nothing to the sums); mean, var [C, N] row-major; mu = mscale mean, v = vscale
+ * var as for hb_lik_sites_*.  nodes [S, C]: standard-normal draws shared by all points (double).  With
+ * f_sc = mu_jc + sqrt(max(v_jc, 0)) nodes[s, c] and p_s = softmax_c(f_s) (shifted by the maximum):
+ *   l_j = mean_s log p_{s, y_j},  g_jc = mean_s ([c = y_j] - p_sc),  lam[c, j] = mean_s p_sc (1 - p_sc)  (Price's form of
+ *   -2 dE l / dv_c: never negative),  beta[c, j] = g_jc + lam[c, j] mu_jc,  lsum[0] = sum_j l_j.
+ * hb_lik_softmax_predict_*: prob[c, j] = mean_s p_sc (NULL: not written); with y given, logdens[j] = log mean_s p_{s, y_j},
+ * combined by log-sum-exp over the nodes -- as log1p(-mean_s (1 - p_{s, y_j})) where that mean of p is above 1/2, so a
+ * density near 1 keeps its digits too -- (NULL: not written), and total[0] = sum_j logdens[j] (NULL: not formed).  y NULL
+ * with logdens or total asked for is refused.
+ * Arithmetic is double in both entries; one rounding on output.  1 - p of the class that carries the maximum is formed
+ * from the sum of the OTHER classes' terms, so lam and g keep their relative digits where p is near 1.  lsum and total are
+ * per-workgroup partials (ws) folded by a second launch in block order, no atomics: two calls return the same bits.
+ * ws >= hb_lik_softmax_ws_elems(N, C) doubles (at most 1024).  Validated before any launch: 2 <= C <= 64, 1 <= S <= 1024,
+ * N >= 0 (N = 0 writes lsum = 0 / total = 0 and returns), vscale >= 0. */
+long hb_lik_softmax_ws_elems(long N, long C);
+int hb_lik_softmax_sites_f32(const float* y, const float* mean, const float* var, double mscale, double vscale,
+                             const double* nodes, long S, float* lam, float* beta, double* lsum, long N, long C, double* ws,
+                             void* stream);
+int hb_lik_softmax_sites_f64(const double* y, const double* mean, const double* var, double mscale, double vscale,
+                             const double* nodes, long S, double* lam, double* beta, double* lsum, long N, long C, double* ws,
+                             void* stream);
+int hb_lik_softmax_predict_f32(const float* y, const float* mean, const float* var, double mscale, double vscale,
+                               const double* nodes, long S, float* prob, float* logdens, double* total, long n, long C,
+                               double* ws, void* stream);
+int hb_lik_softmax_predict_f64(const double* y, const double* mean, const double* var, double mscale, double vscale,
+                               const double* nodes, long S, double* prob, double* logdens, double* total, long n, long C,
+                               double* ws, void* stream);
 /* Pathwise posterior function draws (csrc/sgp_pathwise.hip; not in the reference; Wilson et al. 2020).  S function draws,
  * each a coefficient row coef[s] = [ w_s / sqrt(L) | v_s ] over 2L random Fourier features of the unit RBF kernel and the M
  * canonical basis functions K(z_m, .), evaluated at n points:
