@@ -732,6 +732,13 @@ __device__ __forceinline__ float sgp_ag_load(const float* p) {   // agent-scope 
   return __hip_atomic_load(const_cast<float*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// the residual coefficient of the backward from one column's values (see sgp_resid_coef): cs = sum_p fbar_pj
+template <typename T>
+__device__ __forceinline__ T sgp_resid_coef_val(T eps_j, T vv, T cs) {
+  const T av = hb_abs(vv);
+  return av > T(0) ? -eps_j * hb_sign(vv) / hb_sqrt(av) * cs : T(0);
+}
+
 #define SGP_RED_LD 260   // floats per (quantity, column) in the end-of-kernel fold: 8 waves x 32 lanes + 4 (bank skew)
 // Epilogue of the third strip form (also the early-start form below): fold the per-lane statistics over the 256 (wave,
 // row-lane) contributions of every column, then -- a.fin -- the finishing pass and the likelihood head of the strip.
@@ -740,7 +747,8 @@ __device__ __forceinline__ float sgp_ag_load(const float* p) {   // agent-scope 
 // 16 jb + 4 (lane >> 4) + r in csq / cu [4 jb + r]; its upper eight waves leave after handing their statistics over.
 template <bool AG, bool L16 = false>
 __device__ __forceinline__ void sgp_2t_epilogue(const SgpArgs<float>& a, float* lds_raw, const float (&csq)[16], const float (&cu)[16],
-                                                const long e, const int bx, const int col0, const int n, const bool means) {
+                                                const long e, const int bx, const int col0, const int n, const bool means,
+                                                float* hand_c = nullptr, float* hand_fb = nullptr) {
   typedef float V4 __attribute__((ext_vector_type(4)));
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 31, h = lane >> 5;
   if (a.part) {
@@ -819,9 +827,18 @@ __device__ __forceinline__ void sgp_2t_epilogue(const SgpArgs<float>& a, float* 
             float gg;
             hb_gauss_point<float>(AG ? sgp_ag_load(a.hy + idx0 + i) : a.hy[idx0 + i], fj, hs, iv, lc, gg, h_ll, h_sc, h_vr);
             a.hdmu[idx0 + i] = gg;
-            if (a.hfbar) a.hfbar[idx0 + i] = hs * (a.hpost * gg);
+            const float fb = hs * (a.hpost * gg);
+            if (a.hfbar) a.hfbar[idx0 + i] = fb;
+            if (hand_c) {
+              // (sgp_fwd_kbar_strip_kernel) the backward's per-column operands, from the values in hand: LDS [32] each
+              hand_fb[2 * tid + i] = fb;
+              hand_c[2 * tid + i] = a.fin_diag ? sgp_resid_coef_val<float>(zi, vv, 0.f + fb) : 0.f;
+            }
           }
         }
+      } else if (hand_c) {
+        hand_fb[2 * tid] = 0.f, hand_fb[2 * tid + 1] = 0.f;   // columns past n: Abar is zero there
+        hand_c[2 * tid] = 0.f, hand_c[2 * tid + 1] = 0.f;
       }
     }
     if (a.head && tid < 64) {
@@ -1428,6 +1445,13 @@ static inline SgpWs sgp_ws(long E, long n, long M, long d, long P) {
 extern "C" long hb_sgp_ws_elems(long E, long n, long M, long d, long P) { return sgp_ws(E, n, M, d, P).total; }
 
 enum { SGP_CALL_FWD, SGP_CALL_A, SGP_CALL_BWD };
+#define SGP_FK_DMAX 2   // input dimensions the fused forward + Kbar strip kernel is built for
+// ... and the most strips (E * ceil(n / 32)) it is chosen for: two workgroups per CU of a 256-CU device, i.e. every strip
+// resident at once.  What the fusion saves is one launch's ramp and the second staging, per LAUNCH; where the strips
+// run in many rounds that is a thousandth of the time, nothing shows in the step (cfg 5, 16384 strips: either form
+// within the other's spread; cfg 2, 256 strips: 181.3 -> 174.3 us) and the plan would hold a second workspace of
+// 32 E M^2 elements for it.  Measured at those two counts only (profiles/strip_fused.txt).
+#define SGP_FK_MAX_STRIPS 512
 enum { SGP_K_TILED, SGP_K_STRIP, SGP_K_STRIP2, SGP_K_STRIP2T, SGP_K_STRIP16, SGP_K_STRIP3 };
 struct SgpForm {
   bool path;        // hb_sgp_strip_path: with Wfrag the call runs as column strips and may exchange A / Kbar fragment-major
@@ -1440,6 +1464,7 @@ struct SgpForm {
   bool rider;       // ... and a persistent factorisation of this shape takes it into its launch (hb_sgp_rider_supported)
   bool bwd_strip;   // the backward runs in column-strip form
   bool bwd_phi;     // hb_sgp_bwd_phi is served (hb_sgp_bwd_phi_supported)
+  bool fwd_kbar;    // forward and Kbar strips share one launch (hb_sgp_fwd_kbar_supported)
   SgpWs ws;
 };
 static SgpForm sgp_form(int call, int elem_bytes, long E, long n, long M, long d, long P, int prec, bool has_wfrag, bool w_aligned,
@@ -1454,6 +1479,7 @@ static SgpForm sgp_form(int call, int elem_bytes, long E, long n, long M, long d
   const bool form16 = hb_debug_get("sgp_form16", 0) != 0;
   const bool early = hb_debug_get("sgp_early", 1) != 0;                      // 0: no forward rides in the factorisation's launch
   const bool phi_direct = hb_debug_get("sgp_phi_direct", 1) != 0;            // 0: plans keep hb_sgp_bwd and the Cholesky VJP's first product
+  const bool fwd_kbar = hb_debug_get("sgp_fwd_kbar", 1) != 0;                // 0: forward and Kbar strips as two launches
   SgpForm f;
   f.ws = sgp_ws(E, n, M, d, P);
   const bool fp32 = elem_bytes == 4, bf16x3 = prec == HB_PREC_BF16X3;
@@ -1490,6 +1516,10 @@ static SgpForm sgp_form(int call, int elem_bytes, long E, long n, long M, long d
   // column-strip backward: fp32, fragment-major W^T available, small d and P, no xbar, the strip partials fit
   f.bwd_strip = fp32 && has_wfrag && !want_xbar && f.path && f.ws.strip_elems <= f.ws.mm_elems;
   f.bwd_phi = !bf16x3 && f.path && phi_direct;
+  // forward + Kbar strips in one launch: where the head rides in the forward and the backward is Phi-direct.  The fused
+  // kernel exists for d <= SGP_FK_DMAX: from d = 3 on the Kbar strip kernel itself runs at half the occupancy (its row
+  // gradients' registers), which the forward's two-workgroup form cannot take in.
+  f.fwd_kbar = f.head_units > 0 && f.bwd_phi && f.bwd_strip && d <= SGP_FK_DMAX && E * nS <= SGP_FK_MAX_STRIPS && fwd_kbar;
   return f;
 }
 // the exported queries speak of an fp32 call with a 16-byte aligned W and a workspace
@@ -1506,6 +1536,13 @@ struct SgpRider {
 };
 static thread_local SgpRider g_rider;
 static int sgp_A_strip_launch(SgpArgs<float> a, long E, int kernel, hipStream_t stream);
+// the tail of the fused forward + Kbar strip launch (sgp_fwd_kbar_strip_kernel): what the backward strip adds to the forward's operands
+struct SgpFwdKbar {
+  const float* WTf;   // fragment-major fp32 image of W^T
+  float* part;        // [E, nS, 2d + 1, M] strip partials of zbar, ell, ubar (sgp_ws: `shared` of the BACKWARD workspace)
+  float* Abf;         // fragment-major Abar
+};
+static int sgp_fwd_kbar_launch(SgpArgs<float> a, SgpFwdKbar k, long E, hipStream_t stream);
 
 extern "C" int hb_sgp_rider_supported(long E, long n, long M, long d, long P, int prec, int has_wfrag, int draw, long rng_lanes) {
   return sgp_form_query(E, n, M, d, P, prec, has_wfrag != 0, draw != 0, rng_lanes).rider ? 1 : 0;
@@ -1903,7 +1940,8 @@ static SgpArgs<T> sgp_args(const T* x, long sx, const T* z, const T* ell, long d
 template <typename T>
 static int sgp_fwd(int kind, int mode, const T* x, long sx, const T* z, const T* ell, long dl, const T* W, const T* Wf,
                    int prec, const T* u, const T* eps_in, uint64_t* rng, long rng_lanes, T* eps_out, T* A, T* A_frag, T* f,
-                   T* v, long E, long n, long M, long d, long P, T* ws, hipStream_t stream, const SgpHead<T>* head = nullptr) {
+                   T* v, long E, long n, long M, long d, long P, T* ws, hipStream_t stream, const SgpHead<T>* head = nullptr,
+                   const SgpFwdKbar* fk = nullptr) {
   const bool diag = mode == HB_SGP_DIAGONAL, draw = diag && !eps_in;
   const T* fin_eps_in = diag ? eps_in : nullptr;   // what the finishing pass, wherever it runs, reads and writes
   uint64_t* fin_rng = draw ? rng : nullptr;
@@ -1949,6 +1987,13 @@ static int sgp_fwd(int kind, int mode, const T* x, long sx, const T* z, const T*
       }
       HB_REQUIRE(!head || a.fin, "hb_sgp_fwd_gauss: this call cannot carry the head (hb_sgp_head_units(...) == 0)");
       if constexpr (std::is_same<T, float>::value) {
+        if (fk) {
+          // forward and Kbar strips in one launch (never recorded as a rider)
+          HB_REQUIRE(form.fwd_kbar && a.head && a.hfbar && A_frag, "hb_sgp_fwd_gauss_kbar: not served here (hb_sgp_fwd_kbar_supported), or fbar / A_frag missing");
+          HB_REQUIRE(!A, "hb_sgp_fwd_gauss_kbar: A is exchanged fragment-major only (pass A = NULL)");
+          HB_REQUIRE(!g_rider.armed, "hb_sgp_fwd_gauss_kbar after hb_sgp_rider_begin: the fused call does not ride");
+          return sgp_fwd_kbar_launch(a, *fk, E, stream);
+        }
         if (g_rider.armed) {
           // recorded, not launched: the factorisation that produces W / Wfrag launches it inside its own grid (early-start form)
           HB_REQUIRE(form.record, "hb_sgp_fwd after hb_sgp_rider_begin: this call cannot ride (hb_sgp_rider_supported)");
@@ -2085,9 +2130,7 @@ __device__ __forceinline__ T sgp_resid_coef(const T* __restrict__ eps, const T* 
   if (mode != HB_SGP_DIAGONAL) return T(0);
   T cs = T(0);
   for (long p = 0; p < P; ++p) cs += fbar[p * n + j];
-  const T vv = v[j];
-  const T av = hb_abs(vv);
-  return av > T(0) ? -eps[j] * hb_sign(vv) / hb_sqrt(av) * cs : T(0);
+  return sgp_resid_coef_val<T>(eps[j], v[j], cs);
 }
 
 template <typename T>
@@ -2261,6 +2304,9 @@ __device__ __forceinline__ float hb_half_wave_sum_dpp(float v) {
 // a lane sums its 16 columns in registers).  That replaces sgp_kbar_kernel + sgp_rowgrad_vec_kernel, i.e. the second
 // full read of Kbar and A (33.5 MB) disappears; the strips' partial sums are folded by sgp_strip_finish_kernel.
 // ---------------------------------------------------------------------------------------------------------------
+#ifndef HB_KSTAMP
+#define HB_KSTAMP(i)   // phase stamps of the diagnostic build (tools/strip_fused_stamps.hip)
+#endif
 template <int D, bool BF3>
 __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sgp_kbar_strip_kernel(SgpBwdArgs<float> a) {
   typedef float V4 __attribute__((ext_vector_type(4)));
@@ -2289,6 +2335,7 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 31, h = lane >> 5;
   const int nq = 2 * D + P;
   float* __restrict__ part = a.part + ((e * nS + bx) * (long)nq) * M;   // [2D + P][M] of this strip
+  HB_KSTAMP(0);
 
   // ---- stage z, the strip's x (both raw: differences are scaled, not coordinates), u, the per-column residual coefficient and fbar
   SgpStripColumn<D> col;   // (only the scale: the strip's x goes to LDS, a lane's row gradients visit 16 columns)
@@ -2357,7 +2404,7 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
         for (int s2 = 0; s2 < 4; ++s2) {
           const int c = 16 * h + 4 * v + s2;
           const float aval = avals[4 * v + s2];
-          float val = aval * cj4[s2];
+          float val = aval * cj4[s2];   // (the compiler contracts: product rounded, then fma(u, fbar, .): sgp_abar_group1 spells it out)
 #pragma unroll
           for (int p = 0; p < 4; ++p)
             if (p < P) {
@@ -2449,6 +2496,7 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
     }
   }
   __syncthreads();
+  HB_KSTAMP(1);
 
   // ---- tile-steps: W^T is upper triangular: row tile t contracts chunks Q = t .. nT-1
   const int nT = M / 32;
@@ -2612,6 +2660,7 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
       }
     }
   }
+  HB_KSTAMP(2);
   // ---- the strip's lengthscale partial: sum over all rows (lanes, waves) in a fixed order
   __syncthreads();
   float* red = lred;
@@ -2628,6 +2677,286 @@ __global__ void __launch_bounds__(SGP_STRIP_THREADS, (BF3 || D >= 3) ? 2 : 4) sg
       for (int ww = 0; ww < SGP_STRIP_THREADS / 64; ++ww) t += red[ww * D + dd];
       part[(long)(D + dd) * M] = t * col.sc[dd] * float(1.0 / (SGP_EXP2_SCALE * SGP_EXP2_SCALE * SGP_EXP2_SCALE));
     }
+  HB_KSTAMP(3);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Forward and Kbar column strips in ONE launch (hb_sgp_fwd_gauss_kbar_f32; fp32, fragment-major operands, P == 1).
+//
+// sgp_A_strip2t_kernel and sgp_kbar_strip_kernel<D, false> give the same workgroup the same 32 data columns, one launch
+// apart; with the finishing pass and the Gaussian head inside the forward, everything the backward strip reads -- A, v,
+// eps, fbar, u, z, x -- is in the forward workgroup when its epilogue ends.  The phases are those of the two kernels, in
+// order, with this hand-over between them (form (a): registers, not a second LDS buffer):
+//   - a wave keeps the row-per-lane values of its two finished tiles (2 x 16 registers; what the A image received,
+//     columns past n as zeros);
+//   - the epilogue leaves c_j and fbar_j of the strip in LDS from its own values (sgp_2t_epilogue, hand_c / hand_fb);
+//   - after the epilogue's last read of the fold buffer the waves write Abar = u^T fbar + A diag(c) over the K block
+//     (sgp_abar_group1: the arithmetic of the backward kernel for one latent function), its fragment-major image and the ubar partials;
+//   - the first W^T fragment set is requested before the epilogue, so the phase boundary costs no load latency.
+// Not needed any more: the second launch and its ramp, the read of the strip's A image (64 KB per workgroup), the
+// staging of z, u, x, fbar and c.  No operation of either parent changes, so every output keeps its bits.  LDS: the K
+// block (66 KB) + z + x + 1 KB: two workgroups per CU as in both parents.
+// ---------------------------------------------------------------------------------------------------------------
+#ifndef HB_FSTAMP
+#define HB_FSTAMP(i)
+#endif
+template <int D>
+__global__ void __launch_bounds__(SGP_STRIP_THREADS, 4) sgp_fwd_kbar_strip_kernel(SgpArgs<float> a, SgpFwdKbar k) {
+  typedef float V4 __attribute__((ext_vector_type(4)));
+  typedef Mma<float> MM;
+  constexpr int KS_FLOATS = SGP_SN * SGP_SLD, RED_FLOATS = 2 * SGP_SN * SGP_RED_LD;
+  __shared__ __attribute__((aligned(16))) float lds_raw[KS_FLOATS > RED_FLOATS ? KS_FLOATS : RED_FLOATS];
+  __shared__ __attribute__((aligned(16))) float zs[SGP_SM_MAX * D];
+  __shared__ __attribute__((aligned(16))) float xss[SGP_SN * D];
+  __shared__ __attribute__((aligned(16))) float cjs[SGP_SN];
+  __shared__ __attribute__((aligned(16))) float fbs[1][SGP_SN];
+  __shared__ float lred[(SGP_STRIP_THREADS / 64) * D];
+  float (*Ks)[SGP_SLD] = reinterpret_cast<float (*)[SGP_SLD]>(lds_raw);
+  long e;
+  int bx;
+  sgp_block(a.efast, e, bx);
+  const float* __restrict__ x = a.x + e * a.sx;
+  const float* __restrict__ z = a.z + e * a.M * D;
+  const float* __restrict__ ell = a.ell + e * a.dl;
+  const float* __restrict__ Wf = a.Wf + e * a.M * a.M;
+  const int M = (int)a.M, n = (int)a.n;
+  const int col0 = bx * SGP_SN;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 31, h = lane >> 5;
+  const int nT = M / 32;
+  const int t1 = nT - 1 - w, t0 = w;
+  const int d0 = w < t1 ? w + 1 : 0;      // the middle tile of an odd count is taken once, as t1
+  const int d1 = w <= t1 ? t1 + 1 : 0;
+  const int nts = d0 + d1;
+  const bool means = true;                // (the launcher requires the column partials and P == 1)
+  HB_FSTAMP(0);
+  // ================= forward: the phases of sgp_A_strip2t_kernel =================
+  float u0 = 0.f, u1 = 0.f;
+  {
+    const float* up = a.u + e * a.P * a.M;
+    if (d0) u0 = up[32 * t0 + li];
+    if (d1) u1 = up[32 * t1 + li];
+  }
+  SgpStripColumn<D> col;
+  SgpStageZ<D, SGP_STRIP_THREADS> zst;
+  col.load(x, ell, a.dl, col0, n, tid);
+  zst.request(z, M, tid);
+  zst.store(zs, M, tid);
+  if (tid < SGP_SN) {
+#pragma unroll
+    for (int dd = 0; dd < D; ++dd) xss[tid * D + dd] = col.xs[dd];   // the strip's x for the row gradients (column tid)
+  }
+  __syncthreads();
+  sgp_strip_fill<D, SGP_STRIP_THREADS>(Ks, zs, col, M, tid);
+  __syncthreads();
+  HB_FSTAMP(1);
+
+  float csq[16], cu[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) csq[r] = 0.f, cu[r] = 0.f;
+  typename MM::Acc acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  const int nS = (n + SGP_SN - 1) / SGP_SN;
+  float keep0[16], keep1[16];   // A[32 t0 + li][16h ..] and A[32 t1 + li][16h ..], as the A image received them
+#pragma unroll
+  for (int i = 0; i < 16; ++i) keep0[i] = 0.f, keep1[i] = 0.f;   // (a wave without tiles never reads them)
+
+  {
+    // a finished tile: statistics from the registers as they stand, the row-per-lane view, the A image -- and the rows
+    // stay with the wave.  (The LAST tile is retired behind the loop, not in it: the same operations on the same
+    // values, but its kept rows are then no loop-carried registers -- with them the loop spilled.)
+    auto retire_fwd = [&](int tile, float um, float (&keep)[16]) {
+      typedef float V2 __attribute__((ext_vector_type(2)));
+      const V2 um2 = {um, um};
+#pragma unroll
+      for (int r = 0; r < 16; r += 2) {
+        const V2 av = {acc[r], acc[r + 1]};
+        const V2 q2 = __builtin_elementwise_fma(av, av, V2{csq[r], csq[r + 1]});
+        const V2 m2 = __builtin_elementwise_fma(um2, av, V2{cu[r], cu[r + 1]});
+        csq[r] = q2[0], csq[r + 1] = q2[1];
+        cu[r] = m2[0], cu[r + 1] = m2[1];
+      }
+      sgp_acc_t_settle(acc);
+      sgp_acc_t_rows(acc, keep);
+      sgp_store_frag_rows(a.Af, keep, e, nT, nS, tile, bx, col0, n, lane);   // (masks the columns past n in `keep`)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    };
+    auto load = [&](V4 (&f)[4], int ts) {
+      const int tc = ts < nts ? ts : nts - 1;            // past the end: re-read the last step (never used)
+      const int tile = tc < d0 ? t0 : t1, Q = tc < d0 ? tc : tc - d0;
+      const float* p = Wf + ((long)(tile * nT + Q) << 10) + 4 * lane;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) f[v] = *reinterpret_cast<const V4*>(p + 256 * v);
+    };
+    auto compute = [&](const V4 (&f)[4], int ts) {
+      if (ts >= nts) return;                               // (uniform) the odd tail of the two-step loop
+      const int Q = ts < d0 ? ts : ts - d0;
+      V4 bv[4];
+#pragma unroll
+      for (int v = 0; v < 4; ++v) bv[v] = *reinterpret_cast<const V4*>(&Ks[li][32 * Q + 16 * h + 4 * v]);
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = MM::mma(bv[v][s], f[v][s], acc);   // transposed tile: rows on the lanes
+      if (ts == d0 - 1) retire_fwd(t0, u0, keep0);
+    };
+    if (nts > 0) {
+      V4 fa[4], fb[4];
+      load(fa, 0);
+#pragma nounroll
+      for (int ts = 0; ts < nts; ts += 2) {
+        load(fb, ts + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        compute(fa, ts);
+        __builtin_amdgcn_sched_barrier(0);
+        load(fa, ts + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        compute(fb, ts + 1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      retire_fwd(t1, u1, keep1);   // (nts > 0: the wave owns t1)
+    }
+  }
+  HB_FSTAMP(2);
+
+  // ================= backward walk (sgp_kbar_strip_kernel): W^T is upper triangular, row tile t contracts chunks t .. nT-1
+  const int ta = nT - 1 - w, tb = w;                 // shallow tile first (w + 1 chunks), then the deep one (nT - w)
+  const int kd0 = ta > tb ? w + 1 : 0;               // the middle tile of an odd count is taken once, as tb
+  const int kd1 = tb <= ta ? nT - w : 0;
+  const int knts = kd0 + kd1;
+  auto tile_of = [&](int ts) { return ts < kd0 ? ta : tb; };
+  auto chunk_of = [&](int ts) { return ts < kd0 ? ta + ts : tb + (ts - kd0); };
+  const float* __restrict__ WTf = k.WTf + e * a.M * a.M;
+  auto kload = [&](V4 (&f)[4], int ts) {
+    const int tc = ts < knts ? ts : knts - 1;
+    const float* p = WTf + ((long)(tile_of(tc) * nT + chunk_of(tc)) << 10) + 4 * lane;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) f[v] = *reinterpret_cast<const V4*>(p + 256 * v);
+  };
+  V4 fa[4], fb2[4];
+  if (knts > 0) kload(fa, 0);   // in flight under the epilogue's reductions
+  {
+    // the exp2 scales for the row gradients, computed again from ell (same operations, same bits) rather than carried
+    // in registers through the forward loop; the empty asm keeps the compiler from merging the two reads
+    const float* ell2 = ell;
+    asm volatile("" : "+s"(ell2));
+    col.scale(ell2, a.dl);
+  }
+
+  // ---- the forward's epilogue: column statistics, finishing pass, head; c_j and fbar_j of the strip stay in LDS
+  sgp_2t_epilogue<false>(a, lds_raw, csq, cu, e, bx, col0, n, means, cjs, &fbs[0][0]);
+  HB_FSTAMP(3);
+  __syncthreads();   // the fold buffer (the K block's LDS) is free; cjs / fbs are written
+
+  // ---- Abar[:, strip] -> LDS ([column][k]) from the kept rows, its image and the ubar partials
+  const int nq = 2 * D + 1;
+  float* __restrict__ part = k.part + ((e * nS + bx) * (long)nq) * M;   // [2D + 1][M] of this strip
+  auto abar_tile = [&](const float (&rows)[16], int t, float um) {
+    const int kk = 32 * t + li;
+    float usum = 0.f;
+    float* blk = k.Abf + ((((long)e * nT + t) * nS + bx) << 10) + 4 * lane;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const V4 ab4 = sgp_abar_group1(&rows[4 * v], um, cjs, fbs[0], h, v, usum);
+#pragma unroll
+      for (int s2 = 0; s2 < 4; ++s2) Ks[16 * h + 4 * v + s2][kk] = ab4[s2];
+      *reinterpret_cast<V4*>(blk + 256 * v) = ab4;
+    }
+    const float tsum = usum + __shfl_xor(usum, 32);
+    if (h == 0) part[(long)(2 * D) * M + kk] = tsum;
+  };
+  if (d0) abar_tile(keep0, t0, u0);
+  if (d1) abar_tile(keep1, t1, u1);
+  __syncthreads();
+  HB_FSTAMP(4);
+
+  // ---- tile-steps and retire of sgp_kbar_strip_kernel<D, false> (Abar image written above: no Kbar image)
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  float lwave[D];
+#pragma unroll
+  for (int dd = 0; dd < D; ++dd) lwave[dd] = 0.f;
+  auto retire = [&](int tile) {
+    sgp_acc_t_settle(acc);
+    float kb[16];
+    sgp_acc_t_rows(acc, kb);
+    if (col0 + SGP_SN > n) {   // (only the last strip has columns past n: the masks stay off the vector pipe elsewhere)
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (col0 + 16 * h + i >= n) kb[i] = 0.f;
+    }
+    const int row = 32 * tile + li;
+    float zr[D], zacc[D], lacc[D];
+#pragma unroll
+    for (int dd = 0; dd < D; ++dd) zr[dd] = zs[row * D + dd], zacc[dd] = 0.f, lacc[dd] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int c = 16 * h + i;
+      float tt[D], r2 = 0.f;
+#pragma unroll
+      for (int dd = 0; dd < D; ++dd) {
+        tt[dd] = (zr[dd] - xss[c * D + dd]) * col.sc[dd];   // difference first, then the exp2 scale (coordinates staged raw)
+        r2 += tt[dd] * tt[dd];
+      }
+      const float gk = kb[i] * hb_exp2_neg<float>(r2);   // (columns past n hold zeros)
+#pragma unroll
+      for (int dd = 0; dd < D; ++dd) {
+        zacc[dd] -= gk * tt[dd];
+        lacc[dd] += gk * tt[dd] * tt[dd];
+      }
+    }
+#pragma unroll
+    for (int dd = 0; dd < D; ++dd) {
+      zacc[dd] += __shfl_xor(zacc[dd], 32);
+      if (h == 0) part[(long)dd * M + row] = zacc[dd] * col.sc[dd] * float(1.0 / (SGP_EXP2_SCALE * SGP_EXP2_SCALE));
+      lwave[dd] += lacc[dd];
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  };
+  auto kcompute = [&](const V4 (&f)[4], int ts) {
+    if (ts >= knts) return;
+    const int Q = chunk_of(ts);
+    V4 bv[4];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) bv[v] = *reinterpret_cast<const V4*>(&Ks[li][32 * Q + 16 * h + 4 * v]);
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+#pragma unroll
+      for (int s2 = 0; s2 < 4; ++s2) acc = MM::mma(bv[v][s2], f[v][s2], acc);   // transposed tile
+    if (ts == kd0 - 1 || ts == knts - 1) retire(tile_of(ts));
+  };
+  if (knts > 0) {
+#pragma nounroll
+    for (int ts = 0; ts < knts; ts += 2) {
+      kload(fb2, ts + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      kcompute(fa, ts);
+      __builtin_amdgcn_sched_barrier(0);
+      kload(fa, ts + 2);
+      __builtin_amdgcn_sched_barrier(0);
+      kcompute(fb2, ts + 1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  HB_FSTAMP(5);
+  // ---- the strip's lengthscale partial: sum over all rows (lanes, waves) in a fixed order
+  __syncthreads();
+#pragma unroll
+  for (int dd = 0; dd < D; ++dd) {
+    const float t = wave_sum(lwave[dd]);
+    if (lane == 0) lred[w * D + dd] = t;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int dd = 0; dd < D; ++dd)
+    if (tid == dd) {
+      float t = 0.f;
+      for (int ww = 0; ww < SGP_STRIP_THREADS / 64; ++ww) t += lred[ww * D + dd];
+      part[(long)(D + dd) * M] = t * col.sc[dd] * float(1.0 / (SGP_EXP2_SCALE * SGP_EXP2_SCALE * SGP_EXP2_SCALE));
+    }
+  HB_FSTAMP(6);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -3479,6 +3808,27 @@ static SgpBwdArgs<T> sgp_bwd_args(const T* W, const T* u, const T* A, const T* f
   return a;
 }
 
+// The backward behind its strip kernel, fragment-major pipeline: the Lbar (hb_sgp_bwd_phi: Abar A^T) contraction over the
+// images, then ONE finish launch that folds the strip partials (at ws.shared) and the slabs (at ws.slabs) side by side.
+template <typename T>
+static int sgp_bwd_frag_rest(const SgpWs& wl, int prec, long dl, const T* A_frag, const T* Kbar_frag, const T* Abar_frag, T* Lbar,
+                             T* ubar, T* zbar, T* ellbar, long E, long n, long M, long d, long P, T* ws, hipStream_t stream) {
+  T* mmws = ws + wl.shared;
+  T* slabs = ws + wl.slabs;
+  const long slab_cap = wl.slab_cap, nS = hb_cdiv(n, SGP_SN);
+  HB_REQUIRE(slab_cap >= 1, "hb_sgp_bwd: workspace too small for the Lbar slabs");
+  int S = 0;
+  int rc = sgp_lbar_frag_launch(Abar_frag ? Abar_frag : Kbar_frag, A_frag, slabs, slab_cap > 32 ? 32 : slab_cap, E, M, nS, prec, &S, stream);
+  if (rc) return rc;
+  const int nbx = (int)hb_cdiv(M, 64), nb_strip = nbx * (int)(2 * d + P) * (int)E;
+  const long nTl = M / 32, phi_units = E * nTl * (nTl + 1);   // (16 rows of a 32 x 32 lower tile each)
+  const long nb_fold = Abar_frag ? (phi_units < 2048 ? phi_units : 2048) : (long)hb_stream_grid(E * M * M, 256);
+  hipLaunchKernelGGL(sgp_bwd_finish_kernel<T>, dim3((unsigned)(nb_strip + nb_fold)), dim3(256), 0, stream,
+                     mmws, (int)nS, M, d, dl, P, zbar, ellbar, ubar, nb_strip, nbx, slabs, S, E, Lbar, Abar_frag ? 1 : 0);
+  HB_LAUNCH_CHECK();
+  return 0;
+}
+
 template <typename T>
 static int sgp_bwd(int kind, int mode, const T* x, long sx, const T* z, const T* ell, long dl, const T* W,
                    const T* Wfrag, int prec, const T* u, const T* eps, const T* A, const T* A_frag, const T* v,
@@ -3523,22 +3873,7 @@ static int sgp_bwd(int kind, int mode, const T* x, long sx, const T* z, const T*
     if (A_frag) a.Kbar = nullptr;   // Kbar only feeds the Lbar contraction: the fragment-major copy is enough
     int rc = sgp_bwd_strip_launch(a, E, nS, stream);
     if (rc) return rc;
-    if (A_frag) {
-      // strip partials and Lbar slabs side by side in the workspace; ONE finish launch folds both
-      T* slabs = ws + form.ws.slabs;
-      const long slab_cap = form.ws.slab_cap;
-      HB_REQUIRE(slab_cap >= 1, "hb_sgp_bwd: workspace too small for the Lbar slabs");
-      int S = 0;
-      rc = sgp_lbar_frag_launch(Abar_frag ? Abar_frag : Kbar_frag, A_frag, slabs, slab_cap > 32 ? 32 : slab_cap, E, M, nS, prec, &S, stream);
-      if (rc) return rc;
-      const int nbx = (int)hb_cdiv(M, 64), nb_strip = nbx * (int)(2 * d + P) * (int)E;
-      const long nTl = M / 32, phi_units = E * nTl * (nTl + 1);   // (16 rows of a 32 x 32 lower tile each)
-      const long nb_fold = Abar_frag ? (phi_units < 2048 ? phi_units : 2048) : (long)hb_stream_grid(E * M * M, 256);
-      hipLaunchKernelGGL(sgp_bwd_finish_kernel<T>, dim3((unsigned)(nb_strip + nb_fold)), dim3(256), 0, stream,
-                         mmws, (int)nS, M, d, dl, P, zbar, ellbar, ubar, nb_strip, nbx, slabs, S, E, Lbar, Abar_frag ? 1 : 0);
-      HB_LAUNCH_CHECK();
-      return 0;
-    }
+    if (A_frag) return sgp_bwd_frag_rest<T>(form.ws, prec, dl, A_frag, Kbar_frag, Abar_frag, Lbar, ubar, zbar, ellbar, E, n, M, d, P, ws, stream);
     hipLaunchKernelGGL(sgp_strip_finish_kernel<T>, dim3((unsigned)hb_cdiv(M, 64), (unsigned)(2 * d + P), (unsigned)E), dim3(256), 0,
                        stream, mmws, (int)nS, M, d, dl, P, zbar, ellbar, ubar);
     HB_LAUNCH_CHECK();
@@ -3636,4 +3971,57 @@ extern "C" int hb_sgp_bwd_phi_f32(int kind, int mode, const float* x, long sx, c
   HB_REQUIRE(sgp_form_query(E, n, M, d, P, HB_PREC_NATIVE, true, false, 0).path, "hb_sgp_bwd_phi: shape outside the column-strip form (see hb_sgp_strip_path)");
   return sgp_bwd<float>(kind, mode, x, sx, z, ell, dl, W, Wfrag, HB_PREC_NATIVE, u, eps, nullptr, A_frag, v, fbar, nullptr,
                         Abar_frag, Phi, ubar, zbar, ellbar, nullptr, E, n, M, d, P, ws, (hipStream_t)stream, Abar_frag);
+}
+
+// ---- forward and Kbar column strips in one launch (sgp_fwd_kbar_strip_kernel) ----
+static int sgp_fwd_kbar_launch(SgpArgs<float> a, SgpFwdKbar k, long E, hipStream_t stream) {
+  dim3 grid = sgp_grid(hb_cdiv(a.n, SGP_SN), 1, E, a.efast);
+  if (a.d == 1)
+    hipLaunchKernelGGL((sgp_fwd_kbar_strip_kernel<1>), grid, dim3(SGP_STRIP_THREADS), 0, stream, a, k);
+  else
+    hipLaunchKernelGGL((sgp_fwd_kbar_strip_kernel<2>), grid, dim3(SGP_STRIP_THREADS), 0, stream, a, k);
+  HB_LAUNCH_CHECK();
+  return 0;
+}
+
+// 1 when hb_sgp_fwd_gauss_kbar_f32 serves this forward call: the head rides in it (hb_sgp_head_units > 0), its backward is
+// Phi-direct (hb_sgp_bwd_phi_supported), d <= 2, at most 512 strips, and hb_debug_set("sgp_fwd_kbar", 0) is not set.  Asked
+// when a plan is built.
+extern "C" int hb_sgp_fwd_kbar_supported(long E, long n, long M, long d, long P, int prec, int has_wfrag, int draw, long rng_lanes) {
+  return sgp_form_query(E, n, M, d, P, prec, has_wfrag != 0, draw != 0, rng_lanes).fwd_kbar ? 1 : 0;
+}
+
+// hb_sgp_fwd_gauss_f32 and the strip kernel of hb_sgp_bwd_phi_f32 for the same operands in ONE launch: besides everything
+// hb_sgp_fwd_gauss_f32 writes (same bits) it leaves the fragment-major Abar in Abar_frag and the strip partials of zbar,
+// ellbar and ubar in the backward workspace `bws` (hb_sgp_ws_elems; NOT a buffer another call writes before
+// hb_sgp_bwd_phi_rest_f32 has run).  The backward's fbar is the head's own (`fbar`, required).
+extern "C" int hb_sgp_fwd_gauss_kbar_f32(int kind, int mode, const float* x, long sx, const float* z, const float* ell, long dl,
+                                         const float* W, const float* Wfrag, int prec, const float* u, const float* eps_in,
+                                         uint64_t* rng, long rng_lanes, float* eps_out, float* A, float* A_frag, float* f, float* v,
+                                         long E, long n, long M, long d, long P, float* ws, const float* y, const float* scale,
+                                         const float* var, double post, float* dmu, float* fbar, float* head_part, long units,
+                                         float* Abar_frag, float* bws, void* stream) {
+  HB_REQUIRE(y && var && dmu && fbar && head_part && units > 0 && Wfrag && A_frag && Abar_frag && bws, "hb_sgp_fwd_gauss_kbar: NULL pointer");
+  HB_REQUIRE(prec == HB_PREC_NATIVE, "hb_sgp_fwd_gauss_kbar: native precision only");
+  SgpHead<float> h;
+  h.y = y, h.scale = scale, h.var = var, h.post = post, h.dmu = dmu, h.fbar = fbar, h.part = head_part, h.units = units;
+  SgpFwdKbar k;
+  k.WTf = Wfrag + hb_wfrag_layout(E, M, false).wt;
+  k.part = bws + sgp_ws(E, n, M, d, P).shared;
+  k.Abf = Abar_frag;
+  return sgp_fwd<float>(kind, mode, x, sx, z, ell, dl, W, Wfrag, prec, u, eps_in, rng, rng_lanes, eps_out, A, A_frag, f, v,
+                        E, n, M, d, P, ws, (hipStream_t)stream, &h, &k);
+}
+
+// What hb_sgp_bwd_phi_f32 does behind its strip kernel, for the images and partials hb_sgp_fwd_gauss_kbar_f32 left: the
+// Abar A^T contraction and the finish launch.  Writes Phi, ubar, zbar and ellbar (the bits of hb_sgp_bwd_phi_f32).
+extern "C" int hb_sgp_bwd_phi_rest_f32(const float* A_frag, const float* Abar_frag, float* Phi, float* ubar, float* zbar,
+                                       float* ellbar, long dl, long E, long n, long M, long d, long P, float* bws, void* stream) {
+  HB_REQUIRE(A_frag && Abar_frag && Phi && ubar && zbar && ellbar && bws, "hb_sgp_bwd_phi_rest: NULL pointer");
+  HB_REQUIRE(dl == 1 || dl == d, "hb_sgp_bwd_phi_rest: lengthscales must have 1 or d entries");
+  const SgpForm form = sgp_form(SGP_CALL_BWD, 4, E, n, M, d, P, HB_PREC_NATIVE, true, true, true, false, 0, false);
+  HB_REQUIRE(form.bwd_strip && form.path, "hb_sgp_bwd_phi_rest: shape outside the column-strip form (see hb_sgp_strip_path)");
+  if (E * M == 0) return 0;
+  return sgp_bwd_frag_rest<float>(form.ws, HB_PREC_NATIVE, dl, A_frag, Abar_frag, Abar_frag, Phi, ubar, zbar, ellbar, E, n, M, d, P, bws,
+                                  (hipStream_t)stream);
 }

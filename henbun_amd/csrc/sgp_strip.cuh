@@ -192,4 +192,28 @@ __device__ __forceinline__ void sgp_store_frag_rows(float* __restrict__ Xf, floa
   }
 }
 
+typedef float SgpV4 __attribute__((ext_vector_type(4)));
+// ---------------------------------------------------------------------------------------------------------------
+// The backward's operand for ONE latent function, one row of a 32 x 32 tile per lane, four columns at a time: with
+// a4[s] = A[k][16 h + 4 v + s] of the lane's row k and u = u_k,
+//     ab4[s] = Abar[k][16 h + 4 v + s] = a4[s] c_j + u f_j ,      usum += sum_s f_j a4[s]
+// (c_j in cjs[32], f_j = fbar_j in fbs[32]: LDS, zero for the columns past n).  This is the Abar statement of
+// sgp_kbar_strip_kernel at P == 1 with the contraction the compiler gives it there spelled out -- the product A c
+// rounded, then fma(u, f, .), and fma(f, a, usum): written plainly here, where P is a constant, the compiler fuses the
+// other pair and Abar differs in the last place (seen on the device).  The shared form was tried in the backward kernel
+// too and taken out again: either way of writing it cost that kernel ~100 selects per tile (cfg 5: 0.9 % of the step).
+__device__ __forceinline__ SgpV4 sgp_abar_group1(const float* a4, float u, const float* cjs, const float* fbs, int h, int v,
+                                                 float& usum) {
+  const SgpV4 cj4 = *reinterpret_cast<const SgpV4*>(&cjs[16 * h + 4 * v]);
+  const SgpV4 fb4 = *reinterpret_cast<const SgpV4*>(&fbs[16 * h + 4 * v]);
+  SgpV4 ab4;
+#pragma unroll
+  for (int s2 = 0; s2 < 4; ++s2) {
+    const float aval = a4[s2];
+    ab4[s2] = __builtin_fmaf(u, fb4[s2], aval * cj4[s2]);
+    usum = __builtin_fmaf(fb4[s2], aval, usum);
+  }
+  return ab4;
+}
+
 #endif  // HB_SGP_STRIP_CUH

@@ -1840,6 +1840,27 @@ def _sgp_emit(plan, node):
             # the head makes THIS step read y, var and scale, which are not inputs of the sgp node: a pending side job
             # that produces one of them (the hoisted minibatch gather of Y) must not ride on a launch behind this one
             plan.pin_side_reads([g.inputs[0], g.inputs[2]] + ([g.inputs[3]] if len(g.inputs) > 3 else []))
+    # Forward and Kbar strips in one launch: the head rides here, the backward behind this draw is Phi-direct and reads the
+    # head's own fbar -- the strip kernel of that backward then runs inside this launch and sgp_grad emits only the rest
+    gn, why = _fwd_kbar_match(plan, node, g, head, a_frag, skip_a, prec)
+    from ._settings import settings as _st0
+    if gn is not None and bool(getattr(_st0.runtime, "early_forward", False)) and plan._chol_rider.get(_through_stop_gradient(node.inputs[4])) is not None:
+        gn, why = None, "settings.runtime.early_forward is on: the forward is offered to the factorisation's launch, and the fused call never rides"
+    if gn is not None and not H.sgp_fwd_kbar_supported(x, z, u, prec, True, eps_in is None and mode == 1, rng):
+        gn, why = None, "d > 2, more than 512 strips, or switched off (hb_debug_set sgp_fwd_kbar 0)"
+    if g is not None:
+        plan.note(FWD_KBAR, node, gn is not None, why or "")
+    if gn is not None:
+        abar_frag = plan.scratch((a_frag.numel(),))
+        bws = plan.scratch((H.sgp_ws_elems(E, n, M, d, P),))   # the plan's own: the strip partials outlive the steps in between
+        plan._fwd_kbar[gn.id] = (abar_frag, bws)
+        fouts = (outs[0], outs[2], outs[3])
+        step = lambda: H.sgp_fwd_gauss_kbar(x, z, ell, W, u, wfrag, a_frag, abar_frag, bws, head, eps_in=eps_in, rng=rng,
+                                            mode=mode, out=fouts)
+        plan.steps.append(step)
+        plan.step_labels[id(step)], plan.step_nodes[id(step)] = "sgp+kbar", node
+        plan.chain_kind[id(step)] = "tail"
+        return
     step = lambda: H.sgp_fwd(x, z, ell, W, u, eps_in=eps_in, rng=rng, mode=mode, out=outs, wfrag=wfrag,
                              prec=prec, a_frag=a_frag, skip_a=skip_a, head=head)
     # Early-start form: the contraction starts inside the launch of the persistent factorisation that produces W, when
@@ -1889,6 +1910,38 @@ def _sgp_vjp(node, gs):
 
 
 PHI_DIRECT = "Cholesky VJP's first product folded into the sparse-GP backward (hb_sgp_bwd_phi)"
+FWD_KBAR = "forward and Kbar column strips in one launch (hb_sgp_fwd_gauss_kbar)"
+
+
+def _fwd_kbar_match(plan, node, g, head, a_frag, skip_a, prec):
+    """The sgp_grad node whose strip kernel can run inside the launch of sgp node `node` (head `g` riding), or (None, why
+    not): the backward must be the Phi-direct one of exactly this draw -- same operands, this draw's eps, A and v -- and
+    its fbar must be the buffer the head itself writes (views aside), so that nothing stands between the two strip phases."""
+    if g is None or head is None:
+        return None, "no likelihood head rides in the forward contraction"
+    if head.get("fbar") is None:
+        return None, "the head does not write dobjective/df itself (hb_gauss_ll_post)"
+    if a_frag is None or not skip_a:
+        return None, "A is exchanged row-major, or read elsewhere"
+    post = plan._gll_post.get(g.id)
+    grads = [c for c in plan._consumers.get(node.outputs[1], []) if c.op == "sgp_grad"]
+    if len(grads) != 1 or len(plan._consumers.get(node.outputs[1], [])) != 1:
+        return None, "A does not feed exactly one sgp_grad"
+    gn = grads[0]
+    gf = gn.inputs[8]
+    while gf.node.op == "reshape":
+        gf = gf.node.inputs[0]
+    if gf is not post[1]:
+        return None, "the backward's fbar is not the head's own dobjective/df"
+    same = all(gn.inputs[i] is node.inputs[j] for i, j in ((0, 0), (1, 1), (2, 2), (3, 4), (4, 5)))
+    if not (same and gn.inputs[5] is node.outputs[3] and gn.inputs[7] is node.outputs[2] and gn.attrs["mode"] == node.attrs["mode"]):
+        return None, "the backward does not read this draw's operands, eps and v"
+    if not plan.needed(gn.outputs[0]):
+        return None, "Lbar is not needed"
+    hit, why = _phi_direct_match(plan, gn, a_frag, prec, plan.needed(gn.outputs[4]))
+    if hit is None:
+        return None, "the backward is not Phi-direct: " + why
+    return gn, None
 
 
 def _phi_direct_match(plan, node, a_frag, prec, need_x):
@@ -1954,6 +2007,17 @@ def _sgp_grad_emit(plan, node):
             plan._phi_direct.update(skipped)
             wfrag = plan._wfrag[_through_stop_gradient(node.inputs[3])][0]
             outs = (plan.out(mu.outputs[0]),) + tuple(plan.out(t) for t in node.outputs[1:4])
+            fused = plan._fwd_kbar.get(node.id)
+            if fused is not None:
+                # the strip kernel ran inside the forward's launch (see _sgp_emit): the contraction and the finish are left
+                abar_frag, bws = fused
+                zsh, xsh = node.inputs[1].shape, node.inputs[0].shape
+                dims = (int(np.prod(zsh[:-2])) if len(zsh) > 2 else 1, xsh[-2], zsh[-2], xsh[-1], node.inputs[4].shape[-2])
+                dl = ell.numel() // dims[0]
+                rest = lambda: H.sgp_bwd_phi_rest(a_frag, abar_frag, bws, dims, dl, outs)
+                plan.steps.append(rest)
+                plan.step_labels[id(rest)], plan.step_nodes[id(rest)] = "sgp_grad_rest", node
+                return
             abar_frag = plan.scratch((a_frag.numel(),))
             plan.steps.append(lambda: H.sgp_bwd_phi(x, z, ell, W, u, eps, v, gf, wfrag, a_frag, mode=mode, out=outs,
                                                     abar_frag=abar_frag))
@@ -2534,6 +2598,7 @@ class Plan:
         self._afrag: Dict[Tensor, object] = {}   # A tensor of an sgp op -> its fragment-major copy (read by sgp_grad)
         self._fused_matutil = set()
         self._phi_direct = set()    # ids of the tril / product / Phisym nodes whose result the sparse-GP backward writes
+        self._fwd_kbar: Dict[int, tuple] = {}   # sgp_grad node id -> (Abar image, backward workspace) left by the fused forward launch
         self._fused_concat = set()
         self._lazy_cols: Dict[Tensor, object] = {}
         for t, b in (binds or []):

@@ -1110,6 +1110,58 @@ def sgp_fwd(x, z, ell, W, u, eps_in=None, rng=None, mode=SGP_DIAGONAL, out=None,
     return f, A, v, eps
 
 
+def sgp_ws_elems(E, n, M, d, P):
+    """Workspace elements of sgp_fwd / sgp_bwd for this shape (hb_sgp_ws_elems)."""
+    return int(_lib.lib().raw("hb_sgp_ws_elems")(int(E), int(n), int(M), int(d), int(P)))
+
+
+def sgp_fwd_kbar_supported(x, z, u, prec, has_wfrag, draw, rng):
+    """True when sgp_fwd_gauss_kbar serves this forward call (hb_sgp_fwd_kbar_supported: the head rides in it, its backward is
+    Phi-direct, d <= 2, at most 512 strips, and the diagnostic switch sgp_fwd_kbar is not 0).  The planner asks when it
+    builds a plan."""
+    return bool(_sgp_fwd_query("hb_sgp_fwd_kbar_supported", x, z, u, prec, has_wfrag, draw, rng))
+
+
+def sgp_fwd_gauss_kbar(x, z, ell, W, u, wfrag, a_frag, abar_frag, bws, head, eps_in=None, rng=None, mode=SGP_DIAGONAL, out=None):
+    """sgp_fwd with the Gaussian head (head['fbar'] required) and the backward's Kbar strips in ONE launch
+    (hb_sgp_fwd_gauss_kbar_f32): besides sgp_fwd's results it leaves Abar fragment-major in abar_frag and the backward's
+    strip partials in bws (hb_sgp_ws_elems elements, the caller's own until sgp_bwd_phi_rest has run).  A is exchanged
+    fragment-major only.  Returns (f, v, eps)."""
+    for t in (x, z, ell, W, u):
+        _chk(t)
+    E, n, M, d, P, sx = _sgp_dims(x, z, u)
+    lead = (E,) if z.dim() == 3 else ()
+    dev, dt = x.device, x.dtype
+    assert dt == torch.float32 and wfrag is not None and a_frag is not None and head.get("fbar") is not None
+    if out is None:
+        f = _empty(lead + (P, n), dtype=dt, device=dev)
+        v = _empty(lead + (n,), dtype=dt, device=dev)
+        eps = _empty(lead + (n,), dtype=dt, device=dev)
+    else:
+        f, v, eps = out
+    dl = ell.numel() // E
+    rp, rl = _rng_args(rng)
+    wse = int(_lib.lib().raw("hb_sgp_ws_elems")(E, n, M, d, P))
+    assert bws.numel() >= wse and abar_frag.numel() >= sgp_frag_elems(E, n, M)
+    ws = workspace(dt, dev, wse)
+    _lib.lib().call("hb_sgp_fwd_gauss_kbar_f32", KERN_RBF, mode, _p(x), sx, _p(z), _p(ell), dl, _p(W), _p(wfrag), int(PREC_NATIVE),
+                    _p(u), _p(eps_in), rp, rl, _p(eps), None, _p(a_frag), _p(f), _p(v), E, n, M, d, P, _p(ws), _p(head["y"]),
+                    _p(head.get("scale")), _p(head["var"]), float(head.get("post") or 0.0), _p(head["dmu"]), _p(head["fbar"]),
+                    _p(head["part"]), int(head["units"]), _p(abar_frag), _p(bws), stream())
+    return f, v, eps
+
+
+def sgp_bwd_phi_rest(a_frag, abar_frag, bws, dims, dl, out):
+    """The part of sgp_bwd_phi behind its strip kernel (hb_sgp_bwd_phi_rest_f32), on what sgp_fwd_gauss_kbar left: the
+    Abar A^T contraction and the finish launch.  dims = (E, n, M, d, P); out = (Phi, ubar, zbar, ellbar), returned."""
+    E, n, M, d, P = (int(t) for t in dims)
+    Phi, ubar, zbar, ellbar = out
+    assert Phi.dtype == torch.float32
+    _lib.lib().call("hb_sgp_bwd_phi_rest_f32", _p(a_frag), _p(abar_frag), _p(Phi), _p(ubar), _p(zbar), _p(ellbar), int(dl), E, n, M, d,
+                    P, _p(bws), stream())
+    return Phi, ubar, zbar, ellbar
+
+
 def sgp_A(x, z, ell, W, out=None, wfrag=None, prec=PREC_NATIVE):
     """A = W K(z,x): the M^2 n contraction alone (hb_sgp_A)."""
     E = z.shape[0] if z.dim() == 3 else 1

@@ -84,7 +84,8 @@ const char* hb_last_error_string(void);
  * only, the outputs are then meaningless), sgp_stats_target_wg (tiles x K-splits aimed at; hb_sgp_stats_ws_elems follows), sgp_select_block (64 / 256: the workgroup
  * size of hb_sgp_select_*; the results do not depend on it), sgp_kgrad_plain (hb_sgp_kgrad_* in its plain-loop form for
  * every shape), sgp_phi_direct (0: hb_sgp_bwd_phi_supported answers 0, so a plan built then keeps hb_sgp_bwd and the
- * Cholesky VJP's first product), gram_vjp_tiles (0: hb_matmul_gram_vjp_tiles_ok answers 0, so a plan built then runs the
+ * Cholesky VJP's first product), sgp_fwd_kbar (0: hb_sgp_fwd_kbar_supported answers 0, so a plan built then keeps the
+ * forward and the Kbar strips as two launches), gram_vjp_tiles (0: hb_matmul_gram_vjp_tiles_ok answers 0, so a plan built then runs the
  * Gram VJP of K(z, z) as launches of its own).  hb_debug_clear() drops every entry. */
 int hb_debug_set(const char* key, long value);
 int hb_debug_clear(void);
@@ -1182,6 +1183,27 @@ int hb_sgp_bwd_phi_f32(int kind, int mode, const float* x, long sx, const float*
                        const float* W, const float* Wfrag, const float* u, const float* eps, const float* A_frag,
                        const float* v, const float* fbar, float* Abar_frag, float* Phi, float* ubar, float* zbar,
                        float* ellbar, long E, long n, long M, long d, long P, float* ws, void* stream);
+/* Forward and Kbar column strips in ONE launch.  hb_sgp_fwd_gauss_f32 and the strip kernel of hb_sgp_bwd_phi_f32 give one
+ * workgroup the same 32 data columns, and with the head in the forward everything the backward strip reads is in that
+ * workgroup when the forward's epilogue ends.  Where hb_sgp_fwd_kbar_supported(...) == 1 -- hb_sgp_head_units(...) > 0,
+ * hb_sgp_bwd_phi_supported(...) == 1, d <= 2, E * ceil(n / 32) <= 512 strips (beyond that the two launches measured
+ * faster), and hb_debug_set("sgp_fwd_kbar", 0) not set (read by _supported alone) --
+ *   hb_sgp_fwd_gauss_kbar_f32: the arguments of hb_sgp_fwd_gauss_f32 (fbar and A_frag required, HB_PREC_NATIVE), then
+ *     Abar_frag (as hb_sgp_bwd_phi_f32's) and bws, a workspace of hb_sgp_ws_elems(E, n, M, d, P) elements that receives the
+ *     backward's strip partials and that nothing else may write until hb_sgp_bwd_phi_rest_f32 has run.  The backward's
+ *     fbar IS the head's fbar, its eps and v the forward's.  Never recorded as a rider (hb_sgp_rider_begin).
+ *   hb_sgp_bwd_phi_rest_f32: the rest of hb_sgp_bwd_phi_f32 -- the Abar A^T contraction over A_frag / Abar_frag and the
+ *     finish launch -- on the same bws: writes Phi, ubar, zbar, ellbar.
+ * Every output of the pair has the bits of hb_sgp_fwd_gauss_f32 followed by hb_sgp_bwd_phi_f32. */
+int hb_sgp_fwd_kbar_supported(long E, long n, long M, long d, long P, int prec, int has_wfrag, int draw, long rng_lanes);
+int hb_sgp_fwd_gauss_kbar_f32(int kind, int mode, const float* x, long sx, const float* z, const float* ell, long dl,
+                              const float* W, const float* Wfrag, int prec, const float* u, const float* eps_in,
+                              uint64_t* rng, long rng_lanes, float* eps_out, float* A, float* A_frag, float* f, float* v,
+                              long E, long n, long M, long d, long P, float* ws, const float* y, const float* scale,
+                              const float* var, double post, float* dmu, float* fbar, float* head_part, long units,
+                              float* Abar_frag, float* bws, void* stream);
+int hb_sgp_bwd_phi_rest_f32(const float* A_frag, const float* Abar_frag, float* Phi, float* ubar, float* zbar,
+                            float* ellbar, long dl, long E, long n, long M, long d, long P, float* bws, void* stream);
 int hb_sgp_bwd_f64(int kind, int mode, const double* x, long sx, const double* z, const double* ell,
                    long dl, const double* W, const double* Wfrag, int prec, const double* u,
                    const double* eps, const double* A, const double* A_frag, const double* v,

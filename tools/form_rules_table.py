@@ -29,7 +29,7 @@ PRECS = (H.PREC_NATIVE, H.PREC_BF16X3)
 DTYPES = (torch.float32, torch.float64)
 # (switch, flipped value): every switch the sparse-GP form rules read, each flipped alone
 SWITCHES = (None, ("sgp_no_strip", 1), ("sgp_force_strip", 1), ("sgp_tiled_crossover", 1), ("sgp_strip_form2", 1),
-            ("sgp_no_fused_finish", 1), ("sgp_form16", 1), ("sgp_early", 0), ("sgp_phi_direct", 0))
+            ("sgp_no_fused_finish", 1), ("sgp_form16", 1), ("sgp_early", 0), ("sgp_phi_direct", 0), ("sgp_fwd_kbar", 0))
 
 
 def _frag_image_elems(B, M, bf3):
@@ -55,6 +55,7 @@ def _gram_vjp_part(B, n, d):
 def rows():
     raw = _lib.lib().raw
     head_units, rider, ws_elems = raw("hb_sgp_head_units"), raw("hb_sgp_rider_supported"), raw("hb_sgp_ws_elems")
+    fwd_kbar = raw("hb_sgp_fwd_kbar_supported")   # (rows of this query and the sgp_fwd_kbar section are additions: without them the table is the one before)
     shapes = list(itertools.product(ES, NS, MS, DS, PS))
     for E, n, M, d, P in shapes:
         for prec in PRECS:
@@ -64,6 +65,7 @@ def rows():
                 a = (E, n, M, d, P, prec, wf, draw, lanes)
                 yield "sgp_head_units", a, int(head_units(*a))
                 yield "sgp_rider_supported", a, int(rider(*a))
+                yield "sgp_fwd_kbar_supported", a, int(fwd_kbar(*a))
         yield "sgp_bwd_phi_supported", (E, n, M, d, P), int(H.sgp_bwd_phi_supported(E, n, M, d, P))
         yield "sgp_ws_elems", (E, n, M, d, P), int(ws_elems(E, n, M, d, P))
         for dt, sk, wf in itertools.product(DTYPES, (H.SGP_S_DIAG, H.SGP_S_TRIL), (0, 1)):
