@@ -1,5 +1,6 @@
 // Sites and predictive of the softmax (multi-class) likelihood under C independent Gaussian marginals
-// (hb_lik_softmax_sites_*, hb_lik_softmax_predict_*, include/henbun_hip.h; SparseGP.natgrad_q, models.SVGPMulticlass).
+// (hb_lik_softmax_sites_*, hb_lik_softmax_grad_*, hb_lik_softmax_predict_*, include/henbun_hip.h; SparseGP.natgrad_q,
+// SparseGP.elbo_and_grad_multi, models.SVGPMulticlass).
 //
 // For point j with label y_j and f_c ~ N(mu_jc, v_jc), mu = mscale mean, v = vscale var, and S standard-normal nodes
 // eps [S, C] shared by all points:
@@ -151,6 +152,71 @@ __global__ void __launch_bounds__(SM_THREADS) lik_softmax_sites_kernel(const T* 
   if (threadIdx.x == 0) partial[blockIdx.x] = lsum;
 }
 
+// Weights of the hyper-parameter gradient at fixed q (hb_lik_softmax_grad_*): the sites kernel's walk, node tiles, softmax
+// and lsum (the same terms added in the same order on the same grid: the same bits), with the reparameterised weight in
+// place of Price's lam.  d_sc = [c = y] - p_sc is q on the label lane and -p elsewhere, as in g; with eps = nodes[s, c]
+//     r[c, j] = mean_s d_sc,   w[c, j] = -mean_s(d_sc eps_sc) / sqrt(v_jc)   (v_jc > 0: -2 d l_j / d v_jc of the node sum)
+//     w[c, j] = mean_s p_sc (1 - p_sc)                                        (v_jc <= 0: eps_sc does not reach f; Price's form)
+// w and r are double whatever T, rows `ldo` apart.
+template <typename T, int CP>
+__global__ void __launch_bounds__(SM_THREADS) lik_softmax_grad_kernel(const T* __restrict__ y, const T* __restrict__ mean,
+                                                                      const T* __restrict__ var, double mscale, double vscale,
+                                                                      const double* __restrict__ nodes, long S,
+                                                                      double* __restrict__ wout, double* __restrict__ rout,
+                                                                      long ldo, double* __restrict__ partial, long N, long C) {
+  __shared__ double tile[SM_TILE];
+  __shared__ double red[16];
+  constexpr int PPB = SM_THREADS / CP;
+  const int c = threadIdx.x % CP, g = threadIdx.x / CP;
+  const bool cls = c < C;
+  const long per = SM_TILE / C, ntiles = (S + per - 1) / per;
+  const double invS = 1.0 / (double)S;
+  long ns = 0;
+  if (ntiles == 1) {
+    ns = sm_stage(nodes, tile, 0, per, S, C);
+    __syncthreads();
+  }
+  double lsum = 0.0;
+  for (long base = (long)blockIdx.x * PPB; base < N; base += (long)gridDim.x * PPB) {
+    const long j = base + g, jj = j < N ? j : N - 1;
+    double mu = -INFINITY, sd = 0.0;
+    int yj = -1;
+    if (cls) {
+      const double v = vscale * (double)var[c * N + jj];
+      mu = mscale * (double)mean[c * N + jj];
+      sd = sqrt(v > 0.0 ? v : 0.0);
+      yj = (int)(double)y[jj];
+    }
+    const bool mine = c == yj;
+    double gacc = 0.0, lacc = 0.0, wacc = 0.0, ell = 0.0;
+    for (long t = 0; t < ntiles; ++t) {
+      if (ntiles > 1) {
+        __syncthreads();
+        ns = sm_stage(nodes, tile, t, per, S, C);
+        __syncthreads();
+      }
+      for (long s = 0; s < ns; ++s) {
+        const double eps = cls ? tile[s * C + c] : 0.0;
+        const double f = cls ? mu + sd * tile[s * C + c] : -INFINITY;   // the sites kernel's expression: the same bits
+        double p, q, lp;
+        sm_softmax<CP>(f, c, &p, &q, &lp);
+        const double dl = mine ? q : -p;
+        gacc += dl;
+        wacc = __builtin_fma(dl, eps, wacc);
+        lacc += p * q;
+        ell += mine ? lp : 0.0;
+      }
+    }
+    if (cls && j < N) {
+      rout[c * ldo + j] = gacc * invS;
+      wout[c * ldo + j] = sd > 0.0 ? -(wacc * invS) / sd : lacc * invS;
+      if (mine) lsum += ell * invS;
+    }
+  }
+  lsum = block_sum(lsum, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = lsum;
+}
+
 // HAS_Y: the label lane, and no other, also carries log sum_s p_{s, y} as a running (top, acc) pair,
 // acc = sum_s exp(lp_s - top), and sum_s (1 - p_{s, y})
 template <typename T, int CP, bool HAS_Y>
@@ -287,6 +353,27 @@ static int lik_softmax_sites(const T* y, const T* mean, const T* var, double msc
 }
 
 template <typename T>
+static int lik_softmax_grad(const T* y, const T* mean, const T* var, double mscale, double vscale, const double* nodes, long S,
+                            double* w, double* r, long ldo, double* lsum, long N, long C, double* ws, hipStream_t st) {
+  if (sm_check("hb_lik_softmax_grad", N, C, S, vscale)) return -1;
+  HB_REQUIRE(lsum && ws, "hb_lik_softmax_grad: NULL output / workspace pointer");
+  HB_REQUIRE(ldo >= N, "hb_lik_softmax_grad: the output rows must be at least N apart (ldo=%ld, N=%ld)", ldo, N);
+  HB_REQUIRE(N == 0 || (y && mean && var && nodes && w && r), "hb_lik_softmax_grad: NULL pointer");
+  const long nb = N > 0 ? sm_blocks(N, C) : 0;
+  if (nb > 0) {
+#define SM_LAUNCH_GRAD(CP)                                                                                              \
+  hipLaunchKernelGGL((lik_softmax_grad_kernel<T, CP>), dim3((unsigned)nb), dim3(SM_THREADS), 0, st, y, mean, var, mscale, \
+                     vscale, nodes, S, w, r, ldo, ws, N, C)
+    SM_DISPATCH(sm_group(C), SM_LAUNCH_GRAD)
+#undef SM_LAUNCH_GRAD
+    HB_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(lik_softmax_fold_kernel, dim3(1), dim3(SM_THREADS), 0, st, ws, nb, lsum);
+  HB_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T>
 static int lik_softmax_predict(const T* y, const T* mean, const T* var, double mscale, double vscale, const double* nodes,
                                long S, T* prob, T* logdens, double* total, long N, long C, double* ws, hipStream_t st) {
   if (sm_check("hb_lik_softmax_predict", N, C, S, vscale)) return -1;
@@ -324,6 +411,16 @@ extern "C" int hb_lik_softmax_sites_f64(const double* y, const double* mean, con
                                         const double* nodes, long S, double* lam, double* beta, double* lsum, long N, long C,
                                         double* ws, void* stream) {
   return lik_softmax_sites<double>(y, mean, var, mscale, vscale, nodes, S, lam, beta, lsum, N, C, ws, (hipStream_t)stream);
+}
+extern "C" int hb_lik_softmax_grad_f32(const float* y, const float* mean, const float* var, double mscale, double vscale,
+                                       const double* nodes, long S, double* w, double* r, long ldo, double* lsum, long N, long C,
+                                       double* ws, void* stream) {
+  return lik_softmax_grad<float>(y, mean, var, mscale, vscale, nodes, S, w, r, ldo, lsum, N, C, ws, (hipStream_t)stream);
+}
+extern "C" int hb_lik_softmax_grad_f64(const double* y, const double* mean, const double* var, double mscale, double vscale,
+                                       const double* nodes, long S, double* w, double* r, long ldo, double* lsum, long N, long C,
+                                       double* ws, void* stream) {
+  return lik_softmax_grad<double>(y, mean, var, mscale, vscale, nodes, S, w, r, ldo, lsum, N, C, ws, (hipStream_t)stream);
 }
 extern "C" int hb_lik_softmax_predict_f32(const float* y, const float* mean, const float* var, double mscale, double vscale,
                                           const double* nodes, long S, float* prob, float* logdens, double* total, long n, long C,

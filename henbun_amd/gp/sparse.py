@@ -42,6 +42,26 @@ def _check_lik_inputs(who, likelihood, k_var, residual, q, Yd, M):
     return m0, S0
 
 
+def _check_blocks_and_labels(who, name, C, q, Y):
+    """The host-side checks of a multi-latent route on q = (m [C, M], S [C, M, M]) (None: not given) and on a numpy Y of
+    labels [N, 1] in 0 .. C-1 (labels already on the device are the caller's duty).  Returns (m, S) as float64 numpy, or
+    (None, None)."""
+    m0 = S0 = None
+    if q is not None:
+        m0, S0 = (np.asarray(a, dtype=np.float64) for a in q)
+        if S0.ndim == 2 and S0.shape == m0.shape:
+            raise NotImplementedError("%s: %s must be full-rank, (m [C, M], S [C, M, M]); a mean-field q is not covered"
+                                      % (who, name))
+        if m0.ndim != 2 or m0.shape[0] != C or S0.shape != (C, m0.shape[1], m0.shape[1]):
+            raise ValueError("%s: %s = (m [%d, M], S [%d, M, M]) expected, got %s %s" % (who, name, C, C, m0.shape, S0.shape))
+    if isinstance(Y, np.ndarray):
+        if Y.ndim != 2 or Y.shape[1] != 1:
+            raise ValueError("%s: Y must hold the labels as [N, 1], got %s" % (who, Y.shape))
+        if not (np.all(Y == np.floor(Y)) and Y.size and Y.min() >= 0 and Y.max() <= C - 1):
+            raise ValueError("%s: the labels must be integers in 0 .. %d" % (who, C - 1))
+    return m0, S0
+
+
 def _q_tail(H, Lam, c, who, of="Lambda"):
     """(L, V, t), the float64 tail every route shares: Lambda = L L^T (one read-back), V = L^-1, t = c V^T [P, M]; the
     mean is m = t V.  (m and Sigma are separate steps: a route that needs neither launches neither.)"""
@@ -298,17 +318,7 @@ class SparseInference:
         k_var, rho, steps = float(k_var), float(rho), int(steps)
         if not (0.0 < rho <= 1.0 and steps >= 0):
             raise ValueError("%s: 0 < rho <= 1 and steps >= 0 expected (got %r, %r)" % (who, rho, steps))
-        if q0 is not None:
-            m0, S0 = (np.asarray(a, dtype=np.float64) for a in q0)
-            if S0.ndim == 2 and S0.shape == m0.shape:
-                raise NotImplementedError("%s: q0 must be full-rank, (m [C, M], S [C, M, M]); a mean-field q is not covered" % who)
-            if m0.ndim != 2 or m0.shape[0] != C or S0.shape != (C, m0.shape[1], m0.shape[1]):
-                raise ValueError("%s: q0 = (m [%d, M], S [%d, M, M]) expected, got %s %s" % (who, C, C, m0.shape, S0.shape))
-        if isinstance(Y, np.ndarray):
-            if Y.ndim != 2 or Y.shape[1] != 1:
-                raise ValueError("%s: Y must hold the labels as [N, 1], got %s" % (who, Y.shape))
-            if not (np.all(Y == np.floor(Y)) and Y.size and Y.min() >= 0 and Y.max() <= C - 1):
-                raise ValueError("%s: the labels must be integers in 0 .. %d" % (who, C - 1))
+        m0, S0 = _check_blocks_and_labels(who, "q0", C, q0, Y)
         sess, zvar, ls = self._stats_session(who)
         torch, H = sess.torch, sess.H
         Xd, Yd = _host.device_data(sess, X, "X"), _host.device_data(sess, Y, "Y")
@@ -449,19 +459,26 @@ class SparseInference:
         bound).  `streamed(Q, R)` returns the part through K(z, X) for Q = 2 W^T G W, R = W^T g^T (hb_sgp_kgrad /
         hb_sgp_wkgrad); the part through K(z, z) is L^T Lbar = T = -Abar A^T = -(2 G Phi + g^T b), the Cholesky VJP and
         the symmetric Gram VJP."""
-        torch, H = sess.torch, sess.H
-        M, d = z.shape
+        H = sess.H
         Q = H.matmul(W, H.matmul(Gm, W), transA=True, alpha=2.0)
         R = H.matmul(W, g, transA=True, transB=True)
         zbar, ellbar = streamed(Q, R)
         T = (H.matmul(Gm, Phi, alpha=-2.0) - H.matmul(g, b, transA=True)).contiguous()
+        zk, ek = self._kmm_grads(sess, z, ell, W, T)
+        return zbar + zk, ellbar + ek
+
+    def _kmm_grads(self, sess, z, ell, W, T):
+        """(zk [M, d], ek [dl]): the part of a bound's gradient through K(z, z) given L^T Lbar = T = -Abar A^T [M, M] -- the
+        Cholesky VJP and the symmetric Gram VJP of K(z, z) + jitter I."""
+        torch, H = sess.torch, sess.H
+        M, d = z.shape
         S = H.matmul(W, H.matmul(H.matutil(T, H.MATUTIL_PHI), W), transA=True)
         Kmmbar = H.matutil(S, H.MATUTIL_SYM)
         zk = torch.empty((M, d), dtype=torch.float64, device=sess.device)
         ek = torch.empty((ell.numel(),), dtype=torch.float64, device=sess.device)
         H.gram_bwd_raw(H.KERN_RBF | H.KERN_KBAR_SYMMETRIC, z, 0, z, 0, ell, 0, ell.numel(), Kmmbar, zk, zk, ek, 1, M, M, d,
                        H.workspace(torch.float64, sess.device, max(M * d, 1)))
-        return zbar + zk, ellbar + ek
+        return zk, ek
 
     def elbo_and_grad(self, X, Y, likelihood, q, k_var=1.0, residual="diagonal", lik_grad=False):
         """(value, grad): the ELBO sum_j E_q log p(y_j | f_j) - KL(q || N(0, I)) of a factorising likelihood at a FIXED
@@ -494,11 +511,10 @@ class SparseInference:
         fitted q.  A likelihood that is not `trainable` raises ValueError.  The other entries and the value are the bits
         of lik_grad=False.
 
-        A likelihood over several latent functions (likelihoods.Softmax) raises NotImplementedError: its value is a
-        fixed-node sum, and a gradient consistent with it is not settled ("Multi-class classification")."""
+        A likelihood over several latent functions (likelihoods.Softmax) raises NotImplementedError: that route has its
+        own weights, q and name, elbo_and_grad_multi."""
         if getattr(likelihood, "num_latent", 1) > 1:
-            raise NotImplementedError("elbo_and_grad: one latent function only (%s has %d; the hyper-parameters of a "
-                                      "multi-latent model train through its sampled ELBO)"
+            raise NotImplementedError("elbo_and_grad: one latent function only (%s has %d: use elbo_and_grad_multi)"
                                       % (type(likelihood).__name__, likelihood.num_latent))
         if lik_grad and not getattr(likelihood, "trainable", False):
             raise ValueError("elbo_and_grad: lik_grad=True needs a likelihood with a continuous parameter (got %s)"
@@ -542,6 +558,94 @@ class SparseInference:
         grad = dict(z=zg.cpu().numpy(), lengthscales=eg.cpu().numpy(), k_var=float(dks.cpu()) / (2.0 * k))
         if lik_grad:
             grad["lik_param"] = float(dps[0].cpu()[0])
+        return float(lsum.cpu()[0]) - kl, grad
+
+    def elbo_and_grad_multi(self, X, Y, likelihood, q, k_var=1.0, residual="diagonal"):
+        """(value, grad): elbo_and_grad for a likelihood over C = likelihood.num_latent latent functions
+        (likelihoods.Softmax) at FIXED q(u_c) = N(m_c, S_c S_c^T), q = (m [C, M], S [C, M, M] lower), labels Y [N, 1]:
+        value = sum_j l_j - sum_c KL(q_c || N(0, I)), l_j the mean of log softmax over the likelihood's fixed nodes -- the
+        ELBO natgrad_q reports -- and grad = dict(z=[M, d], lengthscales=[dl], k_var=float), float64 numpy.
+
+        What the number is: the EXACT partial gradient of that fixed-node value at fixed q.  The weights are the
+        derivatives of the node sum itself (hb_lik_softmax_grad), r_jc = dl_j/dmu_jc = g_jc and w_jc = -2 dl_j/dv_jc =
+        -mean_s(([c = y_j] - p_sc) eps_sc) / sqrt(v_jc), NOT Price's curvature lam = mean_s p (1 - p) of the
+        natural-gradient step, which is the derivative of the exact expectation and misses that of the node sum by up to
+        17 % in z at 128 nodes ("Multi-class classification").  w has either sign; that is harmless for a
+        gradient (only the conjugate update needs lam >= 0).  Where v_jc = 0 the node sum has no derivative in v and
+        w_jc is p (1 - p), the limit of the exact expectation's.  In m the fixed point of natgrad_q is stationary for this
+        value; in S only up to the node error, because the step uses Price's lam: at the fitted q the partial gradient
+        is the total derivative of the fitted ELBO up to that error.
+
+        Per class the gradient has elbo_and_grad's form, Abar_c = 2 G_c A diag(w_c) + g_c^T r_c^T with G_c = -(k_var / 2)
+        (S_c S_c^T - rho I), g_c = sqrt(k_var) m_c, and it is linear in the classes: the streamed part is C calls of
+        hb_sgp_wkgrad over all of X with Q_c = 2 W^T G_c W, R_c = W^T g_c^T, added in class order (a one-pass kernel over
+        all classes measured 1.6 x slower: at M = 512 one packed Q_c fills half an L2 and C of them do not fit, DESIGN.md
+        3), the K(z, z) part runs once with T = -sum_c (2 G_c Phi_c + g_c^T b_c), and dF/dk_var = sum_jc (r_jc mu_jc -
+        w_jc v_jc) / (2 k_var).
+        FLOAT64 ARITHMETIC end to end on the chunk walk of elbo_and_grad: per chunk C calls of hb_sgp_predict_f64, ONE
+        hb_lik_softmax_grad_f64 and ONE hb_sgp_mwstats_f64.  Refusals and exception types are natgrad_q's for such a
+        likelihood ('fullrank' and a mean-field q: NotImplementedError; other shapes and bad labels: ValueError), decided
+        before the session is touched; a likelihood over ONE latent function raises ValueError: use elbo_and_grad."""
+        who = "elbo_and_grad_multi"
+        _check_residual(residual)
+        if not isinstance(likelihood, Likelihood):
+            raise TypeError("%s: likelihood must be a henbun_amd.likelihoods.Likelihood, got %s" % (who, type(likelihood).__name__))
+        C = int(getattr(likelihood, "num_latent", 1))
+        if C < 2:
+            raise ValueError("%s: a likelihood over several latent functions expected (%s has one: use elbo_and_grad)"
+                             % (who, type(likelihood).__name__))
+        if not float(k_var) > 0.0:
+            raise ValueError("%s: k_var must be positive (got %r)" % (who, k_var))
+        if q is None:
+            raise ValueError("%s: q = (m [%d, M], S [%d, M, M]) expected, got None" % (who, C, C))
+        m0, S0 = _check_blocks_and_labels(who, "q", C, q, Y)
+        zshape = tuple(object.__getattribute__(self, "z").shape)
+        if len(zshape) == 2 and m0.shape[1] != zshape[0]:
+            raise ValueError("%s: q = (m [%d, %d], S [%d, %d, %d]) expected, got %s %s"
+                             % ((who, C, zshape[0], C) + zshape[:1] * 2 + (m0.shape, S0.shape)))
+        sess, Xd, Yd, z, ell, W = self._grad_inputs(X, Y, who)
+        if Yd.dim() != 2 or Yd.shape[1] != 1:
+            raise ValueError("%s: Y must hold the labels as [N, 1], got %s" % (who, tuple(Yd.shape)))
+        torch, H = sess.torch, sess.H
+        N, M = int(Xd.shape[0]), int(z.shape[0])
+        k = float(k_var)
+        rho = 1.0 if residual == "diagonal" else 0.0
+        f64 = dict(dtype=torch.float64, device=sess.device)
+        m, S = _host.upload(sess, m0, np.float64), _host.upload(sess, np.tril(S0), np.float64)
+        nodes = _host.upload(sess, likelihood.nodes(), np.float64)
+        mode = H.SGP_DIAGONAL if residual == "diagonal" else H.SGP_NEGLECTED
+        ldN = -(-N // 2) * 2                         # rows padded to 16 bytes: what hb_sgp_mwstats asks of the weights
+        w, r = (torch.zeros((C, ldN), **f64) for _ in range(2))
+
+        def per_chunk(c0, Xc, Yc):
+            nc = Xc.shape[0]
+            mean, var = (torch.empty((C, nc), **f64) for _ in range(2))      # unit-variance moments
+            for c in range(C):
+                H.sgp_predict(Xc, z, ell, W, m[c:c + 1], S[c], s_kind=H.SGP_S_TRIL, mode=mode,
+                              out=(mean[c:c + 1], var[c:c + 1]))
+            wc, rc = w[:, c0:c0 + nc], r[:, c0:c0 + nc]
+            _, _, ls = H.lik_softmax_grad(Yc.reshape(-1), mean, var, nodes, mscale=np.sqrt(k), vscale=k, out=(wc, rc))
+            Pc, bc, _ = H.sgp_mwstats(Xc, wc, rc, z, ell, W)
+            return Pc, bc, ls, (rc * mean * np.sqrt(k) - wc * var * k).sum()
+
+        # chunks of a multiple of 32 rows: every chunk of a row of w stays 16-byte aligned
+        Phi, b, lsum, dks = _walk_f64(torch, Xd, Yd, M, 32, per_chunk)
+        # tail: G_c = dF/dPhi_c, g_c = dF/db_c; T is linear in the classes, so one Cholesky VJP and one Gram VJP serve all
+        zbar = ellbar = T = None
+        for c in range(C):
+            Gm = H.matutil((H.matmul(S[c], S[c], transB=True) * (-0.5 * k)).contiguous(), H.MATUTIL_ADD_EYE, alpha=0.5 * rho * k)
+            g = (m[c:c + 1] * np.sqrt(k)).contiguous()
+            Q = H.matmul(W, H.matmul(Gm, W), transA=True, alpha=2.0)
+            R = H.matmul(W, g, transA=True, transB=True)
+            zc, ec = H.sgp_wkgrad(Xd, w[c, :N], r[c, :N], z, ell, Q, R)
+            Tc = H.matmul(Gm, Phi[c].contiguous(), alpha=-2.0) - H.matmul(g, b[c:c + 1].contiguous(), transA=True)
+            zbar, ellbar, T = (zc, ec, Tc) if T is None else (zbar + zc, ellbar + ec, T + Tc)
+        zk, ek = self._kmm_grads(sess, z, ell, W, T.contiguous())
+        # KL(q_c || N(0, I)) from S_c itself, as elbo_and_grad forms it
+        Sl = np.tril(S0)
+        kl = sum(0.5 * (float((Sl[c] * Sl[c]).sum()) + float((m0[c] * m0[c]).sum()) - M)
+                 - float(np.log(np.abs(np.diagonal(Sl[c]))).sum()) for c in range(C))
+        grad = dict(z=(zbar + zk).cpu().numpy(), lengthscales=(ellbar + ek).cpu().numpy(), k_var=float(dks.cpu()) / (2.0 * k))
         return float(lsum.cpu()[0]) - kl, grad
 
     # -- pathwise posterior function draws (Wilson et al. 2020) -----------------------------------------------------

@@ -1984,6 +1984,30 @@ def lik_softmax_sites(y, mean, var, nodes, mscale=1.0, vscale=1.0, out=None):
     return lam, beta, lsum
 
 
+def lik_softmax_grad(y, mean, var, nodes, mscale=1.0, vscale=1.0, out=None):
+    """Weights of the hyper-parameter gradient of the softmax ELBO at fixed q (hb_lik_softmax_grad): (w [C, N], r [C, N],
+    lsum [1]) as FLOAT64 device tensors whatever the dtype of the inputs, which are those of lik_softmax_sites.  r = g =
+    mean_s ([c = y] - p_s) = dl/dmu and w = -mean_s(([c = y] - p_s) nodes[s, c]) / sqrt(v) = -2 dl/dv are the exact partial
+    derivatives of the fixed-node value (w has either sign; where v <= 0 it is mean_s p (1 - p)).  lsum has the bits of
+    lik_softmax_sites's.  out=(w, r): float64 [C, N] views whose rows may be padded (one stride(0) >= N for both,
+    stride(1) == 1), written in place.  Two calls return the same bits."""
+    N, C, S = _softmax_inputs("lik_softmax_grad", y, mean, var, nodes)
+    if out is None:
+        w, r = (_empty((C, N), dtype=torch.float64, device=mean.device) for _ in range(2))
+    else:
+        w, r = out
+        for t in (w, r):
+            if (not t.is_cuda or t.dtype != torch.float64 or tuple(t.shape) != (C, N) or t.stride(1) != 1
+                    or t.stride(0) != w.stride(0) or t.stride(0) < N):
+                raise ValueError("lik_softmax_grad: out = (w, r) must be float64 [%d, %d] device tensors with unit column "
+                                 "stride and one row stride >= N" % (C, N))
+    lsum = _empty((1,), dtype=torch.float64, device=mean.device)
+    ws = workspace(torch.float64, mean.device, int(_lib.lib().raw("hb_lik_softmax_ws_elems")(N, C)))
+    _lib.lib().call("hb_lik_softmax_grad" + _suf(mean), _p(y), _p(mean), _p(var), float(mscale), float(vscale), _p(nodes), S,
+                    _p(w), _p(r), max(int(w.stride(0)), N), _p(lsum), N, C, _p(ws), stream())
+    return w, r, lsum
+
+
 def lik_softmax_predict(mean, var, nodes, y=None, mscale=1.0, vscale=1.0, prob=True, pointwise=True):
     """Predictive of the softmax likelihood (hb_lik_softmax_predict): (prob [C, n] = mean_s softmax(f_s), or None with
     prob=False; logdens [n] = log mean_s softmax(f_s)_{y_j}, or None without y or with pointwise=False; their sum as a

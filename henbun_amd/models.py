@@ -15,7 +15,7 @@ tf = hb.tf
 
 
 def _adam_ascent(model, evaluate, steps, lr, train_z):
-    """The host-side float64 Adam ASCENT loop SVGP.fit_hyper and SVGPLik.fit_hyper share: `steps` steps on the raw
+    """The host-side float64 Adam ASCENT loop SVGP.fit_hyper, SVGPLik.fit_hyper and SVGPMulticlass.fit_hyper share: `steps` steps on the raw
     parameters of model._hyper_variables() (z only with train_z) with the (value, raw gradient) `evaluate()` returns,
     written back after every step.  Returns the trace of values, steps + 1 entries.  A graph.CholeskyError out of
     `evaluate` is re-raised with the raw parameters of the last successful evaluation restored."""
@@ -412,7 +412,9 @@ class SVGPMulticlass(hb.model.Model):
     y: the labels 0 .. C-1, [N] or [N, 1].  The sampled ELBO trains z, the lengthscales, k_var and q by the minibatch route;
     fit_q() fits q(u) deterministically by natural-gradient steps over the full data (SparseGP.natgrad_q: per step C
     marginals passes, one softmax sites launch, ONE weighted statistics pass that forms A once for all classes, C tails).
-    Not built: the hyper-parameter gradient at fixed q (elbo_and_grad / fit_hyper) -- hyper-parameters train through ELBO.
+    elbo_and_grad() is the exact partial gradient of the fixed-node ELBO fit_q reports, at the current q, with respect to
+    z, the lengthscales and k_var (SparseGP.elbo_and_grad_multi); fit_hyper() alternates fit_q steps with Adam steps on it:
+    "select z, fit the hyper-parameters, fit q(u)" without a minibatch, as SVGPLik does for one latent function.
 
     The residual.  SparseGP.samples draws the 'diagonal' residual as ONE number per data point, shared by all latent
     functions of the SparseGP (the reference's semantics), and softmax does not see a shift common to all classes: in this
@@ -496,6 +498,44 @@ class SVGPMulticlass(hb.model.Model):
     def _likelihood_residual(self):
         """The residual mode whose moments the likelihood sees: 'neglected' for 'diagonal' too (the class docstring)."""
         return "neglected" if self.residual == "diagonal" else self.residual
+
+    def _hyper_variables(self):
+        """The Variables the ELBO at fixed q(u_c) depends on, by the names the gradient uses."""
+        gp = _part(self, "gp")
+        return dict(z=_part(gp, "z"), lengthscales=_part(_part(gp, "kern"), "lengthscales"), k_var=_part(self, "k_var"))
+
+    def elbo_and_grad(self):
+        """(value, grad): the fixed-node ELBO over the model's full X and labels at the model's CURRENT q(u) -- the value
+        fit_q reports -- and its exact partial gradient at that q with respect to the RAW (free) parameters, grad =
+        dict(z, lengthscales, k_var) in the shapes of the raw arrays, float64 numpy.  SparseGP.elbo_and_grad_multi
+        (float64 arithmetic whatever the session's dtype; the moments without the residual, as fit_q takes them), chained
+        through the transforms' dforward.  At the q fit_q converges to it is the total derivative of the fitted ELBO up to
+        the node error of the step's curvature (see elbo_and_grad_multi)."""
+        self.initialize()
+        value, cons = _part(self, "gp").elbo_and_grad_multi(_part(self, "X"), _part(self, "Y"), _part(self, "likelihood"),
+                                                            self._current_blocks(), k_var=_scalar(self, "k_var"),
+                                                            residual=self._likelihood_residual())
+        return value, _chain_to_raw(self, cons)
+
+    def fit_hyper(self, steps, lr=0.01, train_z=True, q_steps=5, rho=None):
+        """Deterministic full-batch fit of the hyper-parameters, the alternation of SVGPLik.fit_hyper: every outer step
+        runs fit_q(steps=q_steps, rho=rho) from the current q(u), then takes ONE Adam ASCENT step on elbo_and_grad() in the
+        raw parameters of the lengthscales, k_var and (train_z) z, on the host in float64.  No minibatch noise.  Ends with
+        a fit_q() at the final parameters.  Returns the trace of ELBO values, steps + 1 entries: after the first fit_q at
+        the starting parameters .. after the closing fit_q() at the final ones.  A step after which a factorisation fails
+        raises graph.CholeskyError with the last good parameters restored.  Call reset_q() first: the first fit_q starts
+        at the model's current q(u).  rho=None: the likelihood's natgrad_rho (0.5), as for fit_q."""
+        steps, done = int(steps), [0]
+
+        def evaluate():
+            if done[0] == steps:
+                self.fit_q()
+            else:
+                self.fit_q(steps=q_steps, rho=rho)
+            done[0] += 1
+            return self.elbo_and_grad()
+
+        return _adam_ascent(self, evaluate, steps, lr, train_z)
 
     def predict_f(self, Xnew, residual=None):
         """(mean [C, n], var [C, n]) of the latent functions at Xnew [n, d]: SparseGP.posterior((m_c, S_c)) per class.

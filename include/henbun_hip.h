@@ -70,7 +70,9 @@ extern "C" {
  * computes Kbar, folded at the head of a serial chain); hb_gram_predict_grad_f32 / _f64 and hb_gram_predict_grad_ws_elems
  * (exact GP: input gradients of the cached predictive and of its closed-form acquisition); hb_lik_softmax_sites_f32 /
  * _f64, hb_lik_softmax_predict_f32 / _f64, hb_lik_softmax_ws_elems, HB_LIK_SOFTMAX, hb_sgp_mwstats_f32 / _f64 and
- * hb_sgp_mwstats_ws_elems (multi-class classification: softmax sites, weighted statistics of C weight sets from one A). */
+ * hb_sgp_mwstats_ws_elems (multi-class classification: softmax sites, weighted statistics of C weight sets from one A);
+ * hb_lik_softmax_grad_f32 / _f64 (hyper-parameter gradient of the multi-class ELBO at fixed q(u_c): the exact weights of
+ * the fixed-node value). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -832,6 +834,25 @@ int hb_lik_softmax_sites_f32(const float* y, const float* mean, const float* var
 int hb_lik_softmax_sites_f64(const double* y, const double* mean, const double* var, double mscale, double vscale,
                              const double* nodes, long S, double* lam, double* beta, double* lsum, long N, long C, double* ws,
                              void* stream);
+/* Weights of the hyper-parameter gradient of the softmax ELBO at fixed q(u_c) (same file; not in the reference;
+ * SparseGP.elbo_and_grad_multi).  Inputs, layout, node tiles, softmax, grid, fold and validation are those of
+ * hb_lik_softmax_sites_*; the outputs are the EXACT partial derivatives of the fixed-node value l_j with respect to the
+ * marginals, ALWAYS double whatever the storage type, rows ldo >= N apart.  With d_sc = [c = y_j] - p_sc (1 - p on the
+ * label lane from the sum of the other classes' terms, never 1 - p with p near 1):
+ *   r[c ldo + j] = g_jc = mean_s d_sc                                   (= d l_j / d mu_jc)
+ *   w[c ldo + j] = -mean_s(d_sc nodes[s, c]) / sqrt(v_jc)   for v_jc > 0  (= -2 d l_j / d v_jc: signed, unlike lam)
+ *   w[c ldo + j] = mean_s p_sc (1 - p_sc)                   for v_jc <= 0 (the node sum has no derivative there; this is
+ *                                                           Price's form, the exact expectation's: p (1 - p) at mu where every
+ *                                                           class of the point has v = 0)
+ *   lsum[0] = sum_j l_j with the BITS of hb_lik_softmax_sites_*'s lsum on the same inputs (the same terms, accumulation
+ *   and fold order), so the gradient belongs to the value SparseGP.natgrad_q reports.
+ * Two calls return the same bits.  ws >= hb_lik_softmax_ws_elems(N, C) doubles. */
+int hb_lik_softmax_grad_f32(const float* y, const float* mean, const float* var, double mscale, double vscale,
+                            const double* nodes, long S, double* w, double* r, long ldo, double* lsum, long N, long C,
+                            double* ws, void* stream);
+int hb_lik_softmax_grad_f64(const double* y, const double* mean, const double* var, double mscale, double vscale,
+                            const double* nodes, long S, double* w, double* r, long ldo, double* lsum, long N, long C,
+                            double* ws, void* stream);
 int hb_lik_softmax_predict_f32(const float* y, const float* mean, const float* var, double mscale, double vscale,
                                const double* nodes, long S, float* prob, float* logdens, double* total, long n, long C,
                                double* ws, void* stream);
