@@ -579,7 +579,8 @@ extern "C" int hb_mlp2_sample_bwd_f32(const float* y, const float* w0, const flo
   hipStream_t stream = (hipStream_t)stream_;
   HB_REQUIRE(y && w0 && b0 && w1 && o && u && x && dw0 && db0 && dw1 && db1 && ws, "hb_mlp2_sample_bwd: NULL pointer");
   HB_REQUIRE(hb_mlp2_sample_supported(n, din, hid, MLP_O, 0, 1), "hb_mlp2_sample_bwd: unsupported shape n=%ld din=%ld hid=%ld", n, din, hid);
-  HB_REQUIRE(((uintptr_t)y | (uintptr_t)o | (uintptr_t)u | (uintptr_t)x | (uintptr_t)xbar) % 16 == 0, "hb_mlp2_sample_bwd: operands must be 16-byte aligned");
+  HB_REQUIRE(((uintptr_t)y | (uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)o | (uintptr_t)u | (uintptr_t)x | (uintptr_t)xbar) % 16 == 0,
+             "hb_mlp2_sample_bwd: operands must be 16-byte aligned");
   const long ntiles = n / 32;
   // ~440 registers with the operand prefetch buffers and the next tile's raw operands: one workgroup per CU (at two
   // waves per SIMD the allocation spills 20 .. 200 registers).  Row chunks so that the grid is about 256 workgroups, at

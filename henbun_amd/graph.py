@@ -1437,10 +1437,15 @@ def _mlp2_emit(plan, node):
 
     fused = (plan.dtype == plan.torch.float32 and bool(getattr(_st.runtime, "fused_encoder", True))
              and H.mlp2_sample_supported(n, din, hid, L2, rng.nlanes if rng is not None else 0, u_in is not None))
+    why = ("needs fp32, Din in {32, 64}, H in {128, 256}, 2 L = 32 outputs, n % 32 == 0, 2 n generator "
+           "lanes for in-kernel noise and settings.runtime.fused_encoder: lowered to the op-by-op launches")
+    # the fused kernels move y, W0, W1 (and injected noise) in 16-byte groups; the weights are views of the flat
+    # parameter buffer, which is packed without padding, so an odd-sized parameter laid out ahead of them shifts them
+    if fused and any(t.data_ptr() % 16 != 0 for t in (y, w0, w1) + ((u_in,) if u_in is not None else ())):
+        fused = False
+        why = "y, W0, W1 or the injected noise is not 16-byte aligned (its offset in the flat parameter buffer): lowered to the op-by-op launches"
     plan._mlp2[node.id] = {"fused": fused}
-    plan.note("fused encoder (hb_mlp2_sample_fwd / _bwd)", node, fused,
-              "" if fused else "needs fp32, Din in {32, 64}, H in {128, 256}, 2 L = 32 outputs, n % 32 == 0, 2 n generator "
-              "lanes for in-kernel noise and settings.runtime.fused_encoder: lowered to the op-by-op launches")
+    plan.note("fused encoder (hb_mlp2_sample_fwd / _bwd)", node, fused, "" if fused else why)
     if fused:
         ws = plan.torch.empty(H.mlp2_sample_ws_elems(n, din, hid), dtype=plan.dtype, device=plan.device)
         plan._mlp2[node.id]["ws"] = ws

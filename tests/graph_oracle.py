@@ -54,9 +54,20 @@ def _strided(x, shape, strides, offset):
     return torch.as_strided(x.contiguous().reshape(-1), tuple(shape), tuple(strides), offset).clone()
 
 
-def evaluate(outputs, leaf_values, noise=None):
+def evaluate(outputs, leaf_values, noise=None, dtype=torch.float64):
     """leaf_values: {leaf Tensor: array}; noise: {noise-leaf or fused-op node id: array}.
-    Returns {Tensor: torch tensor} for every tensor reachable from outputs."""
+    Returns {Tensor: torch tensor} for every tensor reachable from outputs.  dtype = torch.float32 evaluates the same
+    graph in single precision on the CPU: its distance from the float64 evaluation is the rounding a float32 device
+    run of that graph is entitled to (tests/graph_device.py)."""
+    global DT
+    saved, DT = DT, dtype
+    try:
+        return _evaluate(outputs, leaf_values, noise)
+    finally:
+        DT = saved
+
+
+def _evaluate(outputs, leaf_values, noise):
     vals = {}
     noise = noise or {}
     rng = np.random.RandomState(1234)
@@ -72,7 +83,7 @@ def evaluate(outputs, leaf_values, noise=None):
                 v = torch.as_tensor(np.asarray(noise[t]) if t in noise else rng.randn(*t.shape), dtype=DT)
             else:
                 lv = leaf_values[t]
-                v = lv if isinstance(lv, torch.Tensor) else torch.as_tensor(np.asarray(lv), dtype=DT)
+                v = lv.to(DT) if isinstance(lv, torch.Tensor) else torch.as_tensor(np.asarray(lv), dtype=DT)
             outs = [v.reshape(t.shape)]
         elif op == "ew":
             outs = _ew(at["f"], at["p"], ins)
@@ -230,10 +241,14 @@ def evaluate(outputs, leaf_values, noise=None):
                 f = _sgp_forward(xr, zr, lr, Lr, ur, eps, at["mode"])[0]
                 gL, gu, gz, gl, gx = torch.autograd.grad((f * gf).sum(), [Lr, ur, zr, lr, xr])
                 outs = [torch.tril(gL), gu, gz, gl, gx]
+        elif op == "vec_to_tri":
+            outs = [O.vec_to_tri(ins[0])]
+        elif op == "tri_to_vec":
+            outs = [O.tri_to_vec(ins[0])]
         else:
             raise NotImplementedError("graph_oracle: op " + op)
         for t, v in zip(n.outputs, outs):
-            vals[t] = v.reshape(t.shape)
+            vals[t] = v.to(DT).reshape(t.shape)
     return vals
 
 
