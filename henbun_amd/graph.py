@@ -22,6 +22,7 @@ import numpy as np
 
 from ._lib import HipBackendError as _HipBackendError
 from ._lib import constants as _constants
+from ._settings import settings as _settings
 
 # hb_matutil's modes (include/henbun_hip.h)
 MATUTIL_BAND, MATUTIL_ADD_EYE, MATUTIL_PHI, MATUTIL_SYM, MATUTIL_SYMLOW = (
@@ -294,6 +295,23 @@ def stop_gradient(x) -> Tensor:
     return make("stop_gradient", (x,), {}, [x.shape]).outputs[0]
 
 
+def _through(t, ops=("reshape",)):
+    """The tensor behind the views in front of `t`; `ops`: the aliasing ops to look through (reshape, stop_gradient)."""
+    while t.node.op in ops:
+        t = t.node.inputs[0]
+    return t
+
+
+# settings.runtime flags the planner reads, with the value each takes when the settings file does not name it
+_RUNTIME_DEFAULTS = dict(fuse_elementwise=True, column_programs=True, head_in_contraction=True, head_in_decoder=True,
+                         side_jobs=True, serial_chains=True, fused_encoder=True, fold_gram=True, fused_predict=True,
+                         early_forward=False, gram_vjp_in_product=False)
+
+
+def _runtime(name) -> bool:
+    return bool(getattr(_settings.runtime, name, _RUNTIME_DEFAULTS[name]))
+
+
 def sum_to_shape(g: Tensor, shape) -> Tensor:
     """Reduce a broadcast gradient back to `shape`."""
     shape = tuple(shape)
@@ -492,15 +510,122 @@ def _gauss_ll_post(node, consumers, outputs):
         return None
     m2 = c2[0]
     other = m2.inputs[0] if m2.inputs[1] is gmu else m2.inputs[1]
-
-    def root(t):
-        while t.node.op == "reshape":
-            t = t.node.inputs[0]
-        return t
-
-    if other.size != 1 or root(other) is not root(node.inputs[3]) or m2.outputs[0].size != dmu.size:
+    if other.size != 1 or _through(other) is not _through(node.inputs[3]) or m2.outputs[0].size != dmu.size:
         return None
     return (float(pp[0]), m2.outputs[0], [m1, m2])
+
+
+# The planner's graph-only matchers (_match_*) decide from the graph, the clusters, the output and bound sets and flags
+# alone -- no plan, no device -- and return their result and their ledger notes, (pass, node, fired, why) for Plan.note.
+def _match_gauss_ll_tails(order, consumers, outputs):
+    """The likelihood head writes d objective / d f itself when the two elementwise ops behind it feed nothing else:
+    ({gauss_ll node id: _gauss_ll_post's result}, ids of the absorbed elementwise nodes, notes)."""
+    hp = "likelihood head writes dobjective/df (hb_gauss_ll_post)"
+    posts, absorbed, notes = {}, set(), []
+    for n in [m for m in order if m.op == "gauss_ll"]:
+        post = _gauss_ll_post(n, consumers, outputs)
+        if post is not None and not any(m.id in absorbed for m in post[2]):
+            posts[n.id] = post
+            absorbed.update(m.id for m in post[2])
+            notes.append((hp, n, True, ""))
+        else:
+            notes.append((hp, n, False, "dmu is not followed by exactly scale * (post * dmu) feeding nothing else" if post is None
+                          else "its elementwise tail is already absorbed by another head"))
+    return posts, absorbed, notes
+
+
+def _emitted_before(order, clusters, colclusters, hoist_mb):
+    """before(t, node): tensor `t` exists when `node` is launched.  A view counts as its source, a fused program is
+    emitted at its last member's position, and hoisted minibatch gathers (`hoist_mb`, Plan._lower) come first."""
+    pos = {n.id: i for i, n in enumerate(order)}
+    def before(t, node):
+        nd = _through(t).node
+        if nd.op == "leaf:minibatch" and hoist_mb:
+            return True
+        cl = clusters.get(nd.id) or colclusters.get(nd.id)
+        last = cl.nodes[-1] if (cl is not None and len(cl.nodes) >= 2) else nd
+        return pos[last.id] < pos[node.id]
+    return before
+
+
+def _match_head_in_contraction(order, before):
+    """The likelihood head riding in the forward contraction (hb_sgp_fwd_gauss): a gauss_ll whose f is the single latent
+    function of an sgp draw, and whose other operands exist before that draw is launched (`before`: _emitted_before).
+    The head's per-point part then runs in the strip kernel's finishing pass; its three sums are folded by a small step
+    that is emitted right in front of their first reader (the step's last serial chain).  ({sgp node: head}, notes)."""
+    hp = "likelihood head inside the forward contraction (hb_sgp_fwd_gauss)"
+    heads, notes = {}, []
+    for n in order:
+        if n.op != "gauss_ll" or len(n.inputs[1].shape) == 0:
+            continue
+        ft = _through(n.inputs[1])
+        sg = ft.node
+        if sg.op != "sgp" or ft is not sg.outputs[0] or sg in heads or sg.inputs[5].shape[-2] != 1:
+            notes.append((hp, n, False, "f is not the single latent function of an sgp draw" if sg.op != "sgp" or ft is not sg.outputs[0]
+                          else ("the draw already carries a head" if sg in heads else "more than one latent function (P > 1)")))
+        elif n.inputs[0].size != ft.size:
+            notes.append((hp, n, False, "y and f differ in size (a broadcast)"))
+        elif all(before(t, sg) for t in [n.inputs[0], n.inputs[2]] + list(n.inputs[3:4])):
+            heads[sg] = n
+            notes.append((hp, n, True, ""))
+        else:
+            notes.append((hp, n, False, "y / var / scale are produced after the draw is launched"))
+    return heads, notes
+
+
+def _match_head_in_decoder(order, consumers, outputs, bound, before, riding, units):
+    """The same head riding in the MatBias product that produces its f (hb_matmul_gauss: a decoder layer feeding
+    densities.gaussian): f is then never written.  Conditions: a plain 2-D product (bias allowed, no activation,
+    nothing transposed) whose result feeds ONLY this head, and the head's other operands exist before it.  `riding`: ids
+    of the heads already riding in an sgp draw; `units(n, K, N)`: hb_matmul_gauss_units.  ({matmul node: head}, notes)."""
+    hp = "likelihood head inside the layer's product (hb_matmul_gauss)"
+    heads, notes = {}, []
+    for n in order:
+        if n.op != "gauss_ll" or n.id in riding or len(n.inputs[1].shape) != 2:
+            continue
+        ft, single = n.inputs[1], True
+        while ft.node.op == "reshape":
+            single = single and len(consumers.get(ft, [])) == 1
+            ft = ft.node.inputs[0]
+        mm = ft.node
+        if mm.op != "matmul" or ft is not mm.outputs[0]:
+            continue      # (not a layer's output: nothing to report)
+        at, why = mm.attrs, None
+        if at["ta"] or at["tb"] or at.get("actgrad") or at["act"] != "none" or len(mm.inputs[0].shape) != 2 or len(mm.inputs[1].shape) != 2:
+            why = "the product is transposed, batched or carries an activation"
+        elif not single or len(consumers.get(ft, [])) != 1 or ft in outputs or ft in bound:
+            why = "f is read by something else as well"
+        elif n.inputs[0].shape != n.inputs[1].shape or mm in heads:
+            why = "y and f differ in shape"
+        elif not all(before(t, mm) for t in [n.inputs[0], n.inputs[2]] + list(n.inputs[3:4])):
+            why = "y / var / scale are produced after the product is launched"
+        elif units(ft.shape[0], mm.inputs[0].shape[1], ft.shape[1]) == 0:
+            why = "shape outside the row-streaming form (fp32, n >= 2048, 32 < N <= 256, K = 16 / 32 / 64 / 128)"
+        if why is None:
+            heads[mm] = n
+        notes.append((hp, n, why is None, why or ""))
+    return heads, notes
+
+
+def _gauss_head(plan, g, units):
+    """The operands of likelihood head `g` for the launch it rides in (hb_sgp_fwd_gauss, hb_matmul_gauss): records the
+    head's partial sums for its fold (_gauss_ll_emit) and pins the side jobs that produce what the head reads."""
+    def early(t):
+        # (an operand may be a view whose reshape node sits later in the emission order: take it from its source)
+        shp = t.shape
+        while t.node.op == "reshape" and t not in plan._buf:
+            t = t.node.inputs[0]
+        return plan.buf(t).view(shp)
+
+    post = plan._gll_post.get(g.id)
+    head = dict(y=early(g.inputs[0]), var=early(g.inputs[2]), scale=early(g.inputs[3]) if len(g.inputs) > 3 else None,
+                dmu=plan.out(g.outputs[1]), post=post[0] if post else 0.0, fbar=plan.out(post[1]) if post else None,
+                part=plan.scratch((3 * units,)), units=units)
+    plan._gll_fused[g.id] = (head["part"], units)
+    # the head makes the step read y, var and scale, which are not inputs of the node that emits it: a pending side job
+    # that produces one of them (the hoisted minibatch gather of Y) must not ride on a launch behind this one
+    plan.pin_side_reads([g.inputs[0], g.inputs[2]] + list(g.inputs[3:4]))
+    return head
 
 
 def _gauss_ll_emit(plan, node):
@@ -858,6 +983,39 @@ def concat(values, axis) -> Tensor:
     return make("concat", tuple(vals), {"axis": axis}, [tuple(oshape)]).outputs[0]
 
 
+def _match_concat_placement(order, consumers, colclusters, outputs, bound):
+    """Concatenation in place: the parts of a concat along its leading non-unit axis are contiguous blocks of the
+    result, so a part that a fused program (or a single elementwise launch) produces is WRITTEN there -- the
+    gradient of a batched GP draw whose expert / gate halves come out of one column program needs no
+    scatter + add (three launches over [2E, n] arrays at cfg 5).  _concat_emit copies whatever did not land in place.
+    {tensor: (concat output, element offset of the tensor's block in it)}; the pass leaves no ledger notes."""
+    def place_target(t):
+        """The tensor whose buffer a concat part really is: looks through reshapes (views) down to a value that a fused
+        program or a single elementwise launch writes through Plan.out; None when the producer keeps its own buffer."""
+        n = t.node
+        if n.id in colclusters:
+            return t if n.op != "strided" else None
+        if n.op == "reshape":
+            return place_target(n.inputs[0])
+        return t if n.op == "ew" else None
+
+    placed = {}
+    for n in order:
+        if n.op != "concat":
+            continue
+        o, ax = n.outputs[0], n.attrs["axis"]
+        if any(d != 1 for d in o.shape[:ax]):
+            continue
+        off = 0
+        for t in n.inputs:
+            tgt = place_target(t)
+            if (tgt is not None and tgt not in bound and tgt not in placed and tgt not in outputs
+                    and len(consumers.get(tgt, [])) == 1):
+                placed[tgt] = (o, off)
+            off += t.size
+    return placed
+
+
 def _concat_emit(plan, node):
     H = plan.H
     if node.id in plan._fused_concat:
@@ -923,6 +1081,35 @@ def matmul(a, b, transpose_a=False, transpose_b=False, bias=None, act="none") ->
                 [tuple(lead) + (m, n)]).outputs[0]
 
 
+def _match_colsum(order, consumers, clusters):
+    """Weight gradient + bias gradient of a MatBias layer from one pass over the incoming gradient G: a 2-D product
+    X^T G whose right operand is also column-summed (reduce over axis 0) becomes hb_matmul_colsum -- the GEMM folds
+    the columns of G while it streams them, and the stand-alone reduction launches (two per layer) disappear.
+    ({matmul node id: the reduce node it absorbs}, ids of the absorbed reduce nodes, notes)."""
+    pos = {n.id: i for i, n in enumerate(order)}
+    pairs, absorbed, notes = {}, set(), []
+    for n in order:
+        if (n.op != "matmul" or not n.attrs["ta"] or n.attrs["tb"] or n.attrs.get("actgrad") or len(n.inputs) != 2
+                or n.attrs["act"] != "none" or len(n.inputs[0].shape) != 2 or len(n.inputs[1].shape) != 2):
+            continue
+        gmat = n.inputs[1]
+        for r in consumers.get(gmat, []):
+            ra = r.attrs if r.op == "reduce" else None
+            if (ra is None or r.id in absorbed or ra["kind"] != "sum" or ra["K1"] != 1
+                    or ra["R"] != gmat.shape[0] or ra["K2"] != gmat.shape[1]):
+                continue
+            cl = clusters.get(r.id)
+            if cl is not None and len(cl.nodes) > 1:
+                continue       # the reduction is part of a fused elementwise program
+            if any(pos[c.id] < pos[n.id] for c in consumers.get(r.outputs[0], [])):
+                continue       # somebody reads the sums before the GEMM has run
+            pairs[n.id] = r
+            absorbed.add(r.id)
+            notes.append(("weight + bias gradient from one pass (hb_matmul_colsum)", n, True, ""))
+            break
+    return pairs, absorbed, notes
+
+
 def _matmul_emit(plan, node):
     H = plan.H
     if node.id in plan._phi_direct:
@@ -931,25 +1118,14 @@ def _matmul_emit(plan, node):
     bias = plan.buf(node.inputs[2]) if len(node.inputs) > 2 else None
     at = node.attrs
     y = node.outputs[0]
-    g = getattr(plan, "_mm_head", {}).get(node.id)
+    g = plan._mm_head.get(node.id)
     if g is not None:
         # the Gaussian likelihood head of this layer runs in the product's epilogue (hb_matmul_gauss): f is never written
         units = H.matmul_gauss_units(y.shape[0], node.inputs[0].shape[1], y.shape[1], plan.dtype)
         ok = (units > 0 and a.stride(1) == 1 and a.stride(0) % 4 == 0 and a.data_ptr() % 16 == 0 and b.stride(1) == 1
               and (bias is None or bias.numel() == y.shape[1]))
         if ok:
-            def early(t):
-                shp = t.shape
-                while t.node.op == "reshape" and t not in plan._buf:
-                    t = t.node.inputs[0]
-                return plan.buf(t).view(shp)
-
-            post = plan._gll_post.get(g.id)
-            head = dict(y=early(g.inputs[0]), var=early(g.inputs[2]), scale=early(g.inputs[3]) if len(g.inputs) > 3 else None,
-                        dmu=plan.out(g.outputs[1]), post=post[0] if post else 0.0, fbar=plan.out(post[1]) if post else None,
-                        part=plan.scratch((3 * units,)), units=units)
-            plan._gll_fused[g.id] = (head["part"], units)
-            plan.pin_side_reads([g.inputs[0], g.inputs[2]] + list(g.inputs[3:4]))
+            head = _gauss_head(plan, g, units)
             plan.steps.append(lambda: H.matmul_gauss(a, b, bias, head))
             return
         # (the head was paired at plan time but this call cannot carry it: the plain product, and the head as a launch of its own)
@@ -994,13 +1170,12 @@ def _matmul_emit(plan, node):
     gg = cons[0] if (len(cons) == 1 and cons[0].op == "gram_grad") else None
     gp = "Gram VJP inside the product that computes Kbar (hb_matmul_gram_vjp)"
     if gg is not None and not epi and bias is None:
-        from ._settings import settings as _st
         tX, tX2, tell, tg = gg.inputs
         B, BX, BX2, n, n2, d, sX, sX2, sEll, dl = _gram_layout(tX, tX2, tell)
         pair = (wgk_like and gg.attrs.get("sym") and tg is y and node.attrs.get("sym_result") and gg.attrs["kind"] == "rbf"
                 and not (BX == 1 and B > 1) and y not in plan.outputs and y not in plan._bind and n == ysh[-1])
-        tiles = bool(pair and sEll == 0 and not getattr(_st.runtime, "gram_vjp_in_product", False)
-                     and H.matmul_gram_vjp_tiles_ok(n, kk, B, d, plan.dtype))
+        in_product = _runtime("gram_vjp_in_product")
+        tiles = bool(pair and sEll == 0 and not in_product and H.matmul_gram_vjp_tiles_ok(n, kk, B, d, plan.dtype))
         plan.note(GRAM_TILES, gg, tiles, "" if tiles else "needs the pairing of the in-product Gram VJP, lengthscales shared by the batch, at most "
                   "16384 tile partials (hb_matmul_gram_vjp_tiles_ok) and hb_debug_set gram_vjp_tiles 1")
         if tiles:
@@ -1011,9 +1186,7 @@ def _matmul_emit(plan, node):
             if host:
                 plan.steps.append(lambda: H.side_flush())
             return
-        ok = (bool(getattr(_st.runtime, "gram_vjp_in_product", False)) and wgk_like and gg.attrs.get("sym") and tg is y
-              and node.attrs.get("sym_result") and gg.attrs["kind"] == "rbf" and not (BX == 1 and B > 1) and y not in plan.outputs
-              and y not in plan._bind and n == ysh[-1] and H.matmul_gram_vjp_ok(n, kk, B, d, plan.dtype))
+        ok = bool(pair and in_product and H.matmul_gram_vjp_ok(n, kk, B, d, plan.dtype))
         plan.note(gp, gg, ok, "" if ok else "needs the in-workgroup split-K form, the symmetric one-pass VJP of a UnitRBF Gram and d <= 4")
         if ok:
             X, ell = plan.buf(tX), plan.buf(tell)
@@ -1192,12 +1365,10 @@ def _cholesky_emit(plan, node):
         if plan.dtype == plan.torch.float32 and M % 32 == 0 and M >= 32 and any(c.op in ("sgp", "sgp_grad", "sgp_predict",
                                                                                              "sgp_predict_cov")
                                                                                 for c in users):
-            from ._settings import settings as _st
-
             # settings.numerics.contraction = bf16x3: the M^2 n contractions take three-term bf16 operands
             # (fp32-level accuracy at the bf16 MFMA rate, include/henbun_hip.h HB_PREC_BF16X3); M <= 512 only.
             # Not requested by sgp_predict / sgp_predict_cov: prediction runs in native precision only.
-            bf3 = (str(getattr(_st.numerics, "contraction", "native")) == "bf16x3" and M <= 512
+            bf3 = (str(getattr(_settings.numerics, "contraction", "native")) == "bf16x3" and M <= 512
                    and any(c.op in ("sgp", "sgp_grad") for c in users))
             frag = plan.scratch((H.cholesky_frag_elems(B, M, bf3),))
             plan._wfrag[inv_node.outputs[0]] = (frag, bf3)
@@ -1236,12 +1407,17 @@ def _cholesky_emit(plan, node):
     plan.steps.append(lambda: H.cholesky(a, out=out, info=info))
 
 
+def _sgp_extents(node):
+    """(E, M, n, d, P) of an sgp, sgp_grad or sgp_predict node; P: the rows of u / m (input 4 of sgp_grad, else input 5)."""
+    zsh, xsh, u = node.inputs[1].shape, node.inputs[0].shape, node.inputs[4 if node.op == "sgp_grad" else 5]
+    return int(np.prod(zsh[:-2])) if len(zsh) > 2 else 1, zsh[-2], xsh[-2], xsh[-1], u.shape[-2]
+
+
 def _sgp_frag_exchange(plan, node, prec):
     """True when the A output of sparse-GP op `node` only feeds its own VJP in column-strip form (no x gradient): A is
     then exchanged fragment-major and its row-major copy is never written."""
     H = plan.H
-    zsh, xsh = node.inputs[1].shape, node.inputs[0].shape
-    E, M, n, d, P = int(np.prod(zsh[:-2])) if len(zsh) > 2 else 1, zsh[-2], xsh[-2], xsh[-1], node.inputs[5].shape[-2]
+    E, M, n, d, P = _sgp_extents(node)
     if plan.dtype != plan.torch.float32 or not H.sgp_strip_path(E, n, M, d, P, prec):
         return False
     users = list(plan._consumers.get(node.outputs[1], ()))
@@ -1433,9 +1609,7 @@ def _mlp2_emit(plan, node):
     act = node.attrs["act"]
     n, din, hid, L2 = _mlp2_dims(node)
     rng = None if u_in is not None else plan.rng(node.attrs["stream"])
-    from ._settings import settings as _st
-
-    fused = (plan.dtype == plan.torch.float32 and bool(getattr(_st.runtime, "fused_encoder", True))
+    fused = (plan.dtype == plan.torch.float32 and _runtime("fused_encoder")
              and H.mlp2_sample_supported(n, din, hid, L2, rng.nlanes if rng is not None else 0, u_in is not None))
     why = ("needs fp32, Din in {32, 64}, H in {128, 256}, 2 L = 32 outputs, n % 32 == 0, 2 n generator "
            "lanes for in-kernel noise and settings.runtime.fused_encoder: lowered to the op-by-op launches")
@@ -1680,9 +1854,7 @@ def _gram_emit(plan, node):
         cc = plan._consumers.get(kj, [])
         M = y.shape[-1]
         Bk = int(np.prod(y.shape[:-2])) if len(y.shape) > 2 else 1
-        from ._settings import settings as _st
-
-        if (bool(getattr(_st.runtime, "fold_gram", True)) and node.inputs[0] is node.inputs[1] and len(cc) == 1
+        if (_runtime("fold_gram") and node.inputs[0] is node.inputs[1] and len(cc) == 1
                 and cc[0].op == "cholesky" and kj not in plan.outputs
                 and kj not in plan._bind and plan.dtype == plan.torch.float32 and k in (H.KERN_RBF, H.KERN_CSYM_RBF)
                 and any(c.op == "trinv" for c in plan._consumers.get(cc[0].outputs[0], ()))
@@ -1796,12 +1968,6 @@ def sgp_samples(x, z, ell, L, u, mode="diagonal", eps=None) -> Tuple[Tensor, Ten
     return tuple(nd.outputs)
 
 
-def _through_stop_gradient(t):
-    while t.node.op == "stop_gradient":
-        t = t.node.inputs[0]
-    return t
-
-
 def _sgp_emit(plan, node):
     H = plan.H
     x, z, ell, L, W, u = (plan.buf(t) for t in node.inputs[:6])
@@ -1809,15 +1975,15 @@ def _sgp_emit(plan, node):
     outs = tuple(plan.out(t) for t in node.outputs)
     mode = SGP_MODES[node.attrs["mode"]]
     rng = plan.rng("local") if (eps_in is None and mode == 1) else None
-    wfrag, bf3 = plan._wfrag.get(_through_stop_gradient(node.inputs[4]), (None, False))
+    Wsrc = _through(node.inputs[4], ("stop_gradient",))
+    wfrag, bf3 = plan._wfrag.get(Wsrc, (None, False))
+    E, M, n, d, P = _sgp_extents(node)
     # bf16x3 operands (settings.numerics.contraction): column-strip kernel only (d <= 4, at most 4 latent functions)
-    bf3 = bf3 and node.inputs[0].shape[-1] <= 4 and node.inputs[5].shape[-2] <= 4
+    bf3 = bf3 and d <= 4 and P <= 4
     prec = H.PREC_BF16X3 if bf3 else H.PREC_NATIVE
     # A = L^-1 K(z,x) is only an intermediate between this op and its VJP: when both run in column-strip form it is
     # exchanged in fragment-major layout (every load and store of the three M^2 n contractions a contiguous KB),
     # and the row-major copy is not written at all
-    zsh, xsh = node.inputs[1].shape, node.inputs[0].shape
-    E, M, n, d, P = int(np.prod(zsh[:-2])) if len(zsh) > 2 else 1, zsh[-2], xsh[-2], xsh[-1], node.inputs[5].shape[-2]
     a_frag, skip_a = None, False
     if wfrag is not None and _sgp_frag_exchange(plan, node, prec):
         a_frag = plan.scratch((H.sgp_frag_elems(E, n, M, prec),))
@@ -1828,28 +1994,13 @@ def _sgp_emit(plan, node):
     if g is not None and wfrag is not None:
         units = H.sgp_head_units(x, z, u, prec, True, eps_in is None and mode == 1, rng)
         if units > 0:
-            post = plan._gll_post.get(g.id)
-            def early(t):
-                # (an operand may be a view whose reshape node sits later in the emission order: take it from its source)
-                shp = t.shape
-                while t.node.op == "reshape" and t not in plan._buf:
-                    t = t.node.inputs[0]
-                return plan.buf(t).view(shp)
-
-            head = dict(y=early(g.inputs[0]), var=early(g.inputs[2]),
-                        scale=early(g.inputs[3]) if len(g.inputs) > 3 else None,
-                        dmu=plan.out(g.outputs[1]), post=post[0] if post else 0.0,
-                        fbar=plan.out(post[1]) if post else None,
-                        part=plan.scratch((3 * units,)), units=units)
-            plan._gll_fused[g.id] = (head["part"], units)
-            # the head makes THIS step read y, var and scale, which are not inputs of the sgp node: a pending side job
-            # that produces one of them (the hoisted minibatch gather of Y) must not ride on a launch behind this one
-            plan.pin_side_reads([g.inputs[0], g.inputs[2]] + ([g.inputs[3]] if len(g.inputs) > 3 else []))
+            head = _gauss_head(plan, g, units)
     # Forward and Kbar strips in one launch: the head rides here, the backward behind this draw is Phi-direct and reads the
     # head's own fbar -- the strip kernel of that backward then runs inside this launch and sgp_grad emits only the rest
     gn, why = _fwd_kbar_match(plan, node, g, head, a_frag, skip_a, prec)
-    from ._settings import settings as _st0
-    if gn is not None and bool(getattr(_st0.runtime, "early_forward", False)) and plan._chol_rider.get(_through_stop_gradient(node.inputs[4])) is not None:
+    # Early-start form: the contraction starts inside the launch of the persistent factorisation that produces W
+    cell = plan._chol_rider.get(Wsrc) if _runtime("early_forward") else None
+    if gn is not None and cell is not None:
         gn, why = None, "settings.runtime.early_forward is on: the forward is offered to the factorisation's launch, and the fused call never rides"
     if gn is not None and not H.sgp_fwd_kbar_supported(x, z, u, prec, True, eps_in is None and mode == 1, rng):
         gn, why = None, "d > 2, more than 512 strips, or switched off (hb_debug_set sgp_fwd_kbar 0)"
@@ -1868,13 +2019,8 @@ def _sgp_emit(plan, node):
         return
     step = lambda: H.sgp_fwd(x, z, ell, W, u, eps_in=eps_in, rng=rng, mode=mode, out=outs, wfrag=wfrag,
                              prec=prec, a_frag=a_frag, skip_a=skip_a, head=head)
-    # Early-start form: the contraction starts inside the launch of the persistent factorisation that produces W, when
-    # everything else it reads exists before that launch (or is written by a side job riding on it)
+    # (taken when everything else the contraction reads exists before that launch, or is written by a side job riding on it)
     ep = "forward contraction starts inside the persistent Cholesky's launch (hb_sgp_rider_begin)"
-    cell = plan._chol_rider.get(_through_stop_gradient(node.inputs[4]))
-    from ._settings import settings as _st
-    if not bool(getattr(_st.runtime, "early_forward", False)):
-        cell = None
     if cell is not None and cell["rider"] is None:
         if not H.sgp_rider_supported(x, z, u, prec, wfrag is not None, eps_in is None and mode == 1, rng):
             plan.note(ep, node, False, "needs the fused finishing pass (fp32, one latent function, d <= 2, M % 64 == 0)")
@@ -1885,9 +2031,8 @@ def _sgp_emit(plan, node):
             early_nodes = {id(nd) for nd in plan._emitted[:cell["epos"]]}
 
             def ready(t):
-                while t.node.op in ("reshape", "stop_gradient") and t.node.inputs:
-                    t = t.node.inputs[0]
-                return t.node.op.startswith("leaf:") or id(t.node) in early_nodes
+                src = _through(t, ("reshape", "stop_gradient")).node
+                return src.op.startswith("leaf:") or id(src) in early_nodes
 
             if all(ready(t) for t in reads):
                 cell["rider"] = step
@@ -1933,10 +2078,7 @@ def _fwd_kbar_match(plan, node, g, head, a_frag, skip_a, prec):
     if len(grads) != 1 or len(plan._consumers.get(node.outputs[1], [])) != 1:
         return None, "A does not feed exactly one sgp_grad"
     gn = grads[0]
-    gf = gn.inputs[8]
-    while gf.node.op == "reshape":
-        gf = gf.node.inputs[0]
-    if gf is not post[1]:
+    if _through(gn.inputs[8]) is not post[1]:
         return None, "the backward's fbar is not the head's own dobjective/df"
     same = all(gn.inputs[i] is node.inputs[j] for i, j in ((0, 0), (1, 1), (2, 2), (3, 4), (4, 5)))
     if not (same and gn.inputs[5] is node.outputs[3] and gn.inputs[7] is node.outputs[2] and gn.attrs["mode"] == node.attrs["mode"]):
@@ -1981,17 +2123,16 @@ def _phi_direct_match(plan, node, a_frag, prec, need_x):
             and at["act"] == "none" and not at.get("actgrad")):
         return None, "Lbar does not feed the product L^T tril(Lbar)"
     L, Q = c.inputs[0], c.outputs[0]
-    Wsrc, fwd = _through_stop_gradient(node.inputs[3]), node.inputs[6].node
+    Wsrc, fwd = _through(node.inputs[3], ("stop_gradient",)), node.inputs[6].node
     if not (Wsrc.node.op == "trinv" and Wsrc.node.inputs[0] is L and fwd.op == "sgp" and fwd.inputs[3] is L
-            and _through_stop_gradient(fwd.inputs[4]) is Wsrc):
+            and _through(fwd.inputs[4], ("stop_gradient",)) is Wsrc):
         return None, "the product's left operand is not the factor L whose inverse whitened the draw"
-    if not private(Q) or c.id in plan._colsum_of or c.id in getattr(plan, "_mm_head", {}):
+    if not private(Q) or c.id in plan._colsum_of or c.id in plan._mm_head:
         return None, "L^T tril(Lbar) is a plan output, or has a reader besides Phisym"
     mu = plan._consumers[Q][0]
     if not (mu.op == "matutil" and mu.attrs["mode"] == MATUTIL_SYMLOW):
         return None, "L^T tril(Lbar) is not followed by Phisym (matutil mode 4)"
-    zsh, xsh = node.inputs[1].shape, node.inputs[0].shape
-    E, M, n, d, P = int(np.prod(zsh[:-2])) if len(zsh) > 2 else 1, zsh[-2], xsh[-2], xsh[-1], node.inputs[4].shape[-2]
+    E, M, n, d, P = _sgp_extents(node)
     if not H.sgp_bwd_phi_supported(E, n, M, d, P):
         return None, "shape outside the column-strip form, or switched off (hb_debug_set sgp_phi_direct 0)"
     return (mu, skipped + [c.id, mu.id]), None
@@ -2010,15 +2151,15 @@ def _sgp_grad_emit(plan, node):
             # Lbar itself is never formed
             mu, skipped = hit
             plan._phi_direct.update(skipped)
-            wfrag = plan._wfrag[_through_stop_gradient(node.inputs[3])][0]
+            wfrag = plan._wfrag[_through(node.inputs[3], ("stop_gradient",))][0]
             outs = (plan.out(mu.outputs[0]),) + tuple(plan.out(t) for t in node.outputs[1:4])
             fused = plan._fwd_kbar.get(node.id)
             if fused is not None:
                 # the strip kernel ran inside the forward's launch (see _sgp_emit): the contraction and the finish are left
                 abar_frag, bws = fused
-                zsh, xsh = node.inputs[1].shape, node.inputs[0].shape
-                dims = (int(np.prod(zsh[:-2])) if len(zsh) > 2 else 1, xsh[-2], zsh[-2], xsh[-1], node.inputs[4].shape[-2])
-                dl = ell.numel() // dims[0]
+                E, M, n, d, P = _sgp_extents(node)
+                dims = (E, n, M, d, P)
+                dl = ell.numel() // E
                 rest = lambda: H.sgp_bwd_phi_rest(a_frag, abar_frag, bws, dims, dl, outs)
                 plan.steps.append(rest)
                 plan.step_labels[id(rest)], plan.step_nodes[id(rest)] = "sgp_grad_rest", node
@@ -2032,7 +2173,7 @@ def _sgp_grad_emit(plan, node):
     if need_x and len(node.inputs[1].shape) > 2 and len(node.inputs[0].shape) == 2:
         raise NotImplementedError("gradient w.r.t. an x shared by several experts")
     xbuf = xb.reshape((-1,) + tuple(xb.shape[-2:])) if need_x else None
-    wfrag, bf3 = plan._wfrag.get(_through_stop_gradient(node.inputs[3]), (None, False))
+    wfrag, bf3 = plan._wfrag.get(_through(node.inputs[3], ("stop_gradient",)), (None, False))
     bf3 = bf3 and not need_x and node.inputs[0].shape[-1] <= 4 and node.inputs[4].shape[-2] <= 4
     prec = H.PREC_BF16X3 if bf3 else H.PREC_NATIVE
     a_frag, fprec = plan._afrag.get(node.inputs[6], (None, None))   # fragment-major A from the forward op (see _sgp_emit)
@@ -2074,13 +2215,10 @@ def _sgp_predict_emit(plan, node):
     H = plan.H
     x, z, ell, _, W, m, s = (plan.buf(t) for t in node.inputs)
     mean, var = (plan.out(t) for t in node.outputs)
-    zsh, xsh = node.inputs[1].shape, node.inputs[0].shape
-    E, M, n, d, P = int(np.prod(zsh[:-2])) if len(zsh) > 2 else 1, zsh[-2], xsh[-2], xsh[-1], node.inputs[5].shape[-2]
+    E, M, n, d, P = _sgp_extents(node)
     s_kind = SGP_PREDICT_S[node.attrs["s_kind"]]
-    wfrag, bf3 = plan._wfrag.get(_through_stop_gradient(node.inputs[4]), (None, False))
-    from ._settings import settings as _st
-
-    want = bool(getattr(_st.runtime, "fused_predict", True))
+    wfrag, bf3 = plan._wfrag.get(_through(node.inputs[4], ("stop_gradient",)), (None, False))
+    want = _runtime("fused_predict")
     fused = want and H.sgp_predict_fused(plan.dtype, E, n, M, d, P, s_kind, wfrag is not None)
     plan.note("fused streaming prediction (hb_sgp_predict, one strip kernel)", node, fused,
               "settings.runtime.fused_predict is off" if not want else
@@ -2129,7 +2267,7 @@ def _sgp_predict_cov_emit(plan, node):
     zsh, xsh = node.inputs[1].shape, node.inputs[0].shape
     E, M, n, P = int(np.prod(zsh[:-2])) if len(zsh) > 2 else 1, zsh[-2], xsh[-2], node.attrs["P"]
     s_kind = SGP_PREDICT_S[node.attrs["s_kind"]]
-    wfrag, _ = plan._wfrag.get(_through_stop_gradient(node.inputs[4]), (None, False))
+    wfrag, _ = plan._wfrag.get(_through(node.inputs[4], ("stop_gradient",)), (None, False))
     plan.note("fused predictive covariance (hb_sgp_predict_cov: A, then one symmetric MFMA product)", node, True)
     ws = plan.scratch((max(H.sgp_predict_cov_ws_elems(plan.dtype, E, n, M, P, s_kind), 1),))
     mode, jit = SGP_PREDICT_MODES[node.attrs["mode"]], node.attrs["jitter"]
@@ -2166,6 +2304,15 @@ def topo_order(outputs: Sequence[Tensor]) -> List[Node]:
             if t.node.id not in seen:
                 stack.append((t.node, False))
     return order
+
+
+def consumer_map(order):
+    """{tensor: the nodes that read it, in emission order} (a node that reads a tensor twice is listed twice)."""
+    consumers = {}
+    for n in order:
+        for t in n.inputs:
+            consumers.setdefault(t, []).append(n)
+    return consumers
 
 
 def _scatter_partition(ts):
@@ -2264,9 +2411,6 @@ def gradients(loss: Tensor, wrt: Sequence[Tensor]) -> List[Optional[Tensor]]:
     return res
 
 
-# ------------------------------------------------------------------------------
-# HIP executor
-# ------------------------------------------------------------------------------
 # ------------------------------------------------------------------------------
 # elementwise clustering: chains / groups of elementwise nodes -> one interpreted launch
 # ------------------------------------------------------------------------------
@@ -2439,10 +2583,7 @@ def cluster_columns(order, outputs=(), enabled=True, skip=()):
     member = {}
     if not enabled:
         return member
-    consumers = {}
-    for nd in order:
-        for t in nd.inputs:
-            consumers.setdefault(t, []).append(nd)
+    consumers = consumer_map(order)
     outputs = set(outputs)
     open_clusters = []
 
@@ -2556,11 +2697,9 @@ class Plan:
 
     def __init__(self, outputs, dtype, device, leaf_resolver, rngs, binds=None, prologue=None, stream=None):
         from . import hip_ops
-
         import torch
 
-        self.H = hip_ops
-        self.torch = torch
+        self.H, self.torch = hip_ops, torch
         self.dtype, self.device = dtype, device
         self.outputs = list(outputs)
         self.steps: List = []
@@ -2585,205 +2724,85 @@ class Plan:
         self._chains_fused = False
         self.step_labels = {}           # id(step closure) -> op label (profiling)
         self.step_nodes = {}            # id(step closure) -> graph Node that emitted it (work models in bench.py)
+        self.step_riders: Dict[int, Node] = {}       # id(step closure) -> node whose work rides in that step's launch
         self.noise_inputs: Dict[Tensor, object] = {}
         self._injected: Dict[Tensor, bool] = {}
         self._leaf_resolver = leaf_resolver
-        order = topo_order(self.outputs)
+        self._order = order = topo_order(self.outputs)
         self._order_pos = {n.id: i for i, n in enumerate(order)}
-        self._order = order
-        self._needed = set()
-        for n in order:
-            for t in n.inputs:
-                self._needed.add(t)
-        for t in self.outputs:
-            self._needed.add(t)
+        self._consumers = consumer_map(order)
+        self._needed = set(self._consumers) | set(self.outputs)
         self._extra_copies = []
-        self._fused_trinv = set()
+        # what the plan-time passes decide (below, before the first node is emitted)
+        self._gll_post: Dict[int, tuple] = {}     # gauss_ll node id -> (post, the tensor that is dobjective/df, absorbed nodes)
+        self._absorbed = set()                    # ids of the elementwise nodes a likelihood head writes for (hb_gauss_ll_post)
+        self._colclusters, self._clusters = {}, {}   # node id -> its column cluster / elementwise cluster
+        self._sgp_head: Dict[int, Node] = {}      # sgp node id -> gauss_ll node
+        self._mm_head: Dict[int, Node] = {}       # matmul node id -> gauss_ll node
+        self._gll_in_sgp: Dict[int, Node] = {}    # gauss_ll node id -> the sgp / matmul node it rides in
+        self._place: Dict[Tensor, object] = {}    # concat part -> its block of the concat's output
+        self._colsum_of: Dict[int, Node] = {}     # matmul node id -> the reduce node it absorbs
+        self._fused_colsum = set()                # ids of absorbed reduce nodes
+        # what the emit functions decide from live buffers, and leave for the nodes behind them
+        self._fused_trinv, self._fused_matutil, self._fused_concat = set(), set(), set()
         self._wfrag: Dict[Tensor, object] = {}   # W tensor -> fragment-major copies written by the fused factorisation
         self._afrag: Dict[Tensor, object] = {}   # A tensor of an sgp op -> its fragment-major copy (read by sgp_grad)
-        self._fused_matutil = set()
         self._phi_direct = set()    # ids of the tril / product / Phisym nodes whose result the sparse-GP backward writes
         self._fwd_kbar: Dict[int, tuple] = {}   # sgp_grad node id -> (Abar image, backward workspace) left by the fused forward launch
-        self._fused_concat = set()
         self._lazy_cols: Dict[Tensor, object] = {}
-        for t, b in (binds or []):
-            self._prebind(t, b)
-        if prologue:
-            prologue(self)
-        from ._settings import settings as _st
-
-        fuse = bool(getattr(_st.runtime, "fuse_elementwise", True))
-        consumers0 = {}
-        for n in order:
-            for t in n.inputs:
-                consumers0.setdefault(t, []).append(n)
-        # the likelihood head writes d objective / d f itself when the two elementwise ops behind it feed nothing else
-        self._gll_post: Dict[int, tuple] = {}
-        self._absorbed = set()
-        if fuse:
-            outs_set = set(self.outputs)
-            for n in order:
-                if n.op == "gauss_ll":
-                    post = _gauss_ll_post(n, consumers0, outs_set)
-                    if post is not None and not any(m.id in self._absorbed for m in post[2]):
-                        self._gll_post[n.id] = post
-                        self._absorbed.update(m.id for m in post[2])
-                        self.note("likelihood head writes dobjective/df (hb_gauss_ll_post)", n, True)
-                    else:
-                        self.note("likelihood head writes dobjective/df (hb_gauss_ll_post)", n, False,
-                                  "dmu is not followed by exactly scale * (post * dmu) feeding nothing else" if post is None
-                                  else "its elementwise tail is already absorbed by another head")
-        else:
-            self.note("elementwise fusion", None, False, "settings.runtime.fuse_elementwise is off")
-        # column programs first (short-and-wide spaces with row reductions inside: they need the compiled form), then
-        # the plain elementwise clusters over what is left
-        self._colclusters = cluster_columns(order, outputs=self.outputs, skip=self._absorbed,
-                                            enabled=fuse and hip_ops.ewise_jit_enabled() and bool(getattr(_st.runtime, "column_programs", True)))
-        self._clusters = cluster_elementwise(order, enabled=fuse, skip=set(self._colclusters) | self._absorbed,
-                                             max_elems=EW_CLUSTER_MAX_ELEMS_JIT if hip_ops.ewise_jit_enabled() else EW_CLUSTER_MAX_ELEMS)
-        consumers = {}
-        for n in order:
-            for t in n.inputs:
-                consumers.setdefault(t, []).append(n)
-        self._consumers = consumers
-        # The likelihood head riding in the forward contraction (hb_sgp_fwd_gauss): a gauss_ll whose f is the single latent
-        # function of an sgp draw, and whose other operands exist before that draw is launched.  The head's per-point part
-        # then runs in the strip kernel's finishing pass; its three sums are folded by a small step that is emitted right in
-        # front of their first reader (the step's last serial chain).
-        self._sgp_head: Dict[int, Node] = {}      # sgp node id -> gauss_ll node
-        self._gll_in_sgp: Dict[int, Node] = {}    # gauss_ll node id -> sgp node
-        self._gll_fused: Dict[int, tuple] = {}    # gauss_ll node id -> (partials buffer, units): set by _sgp_emit
+        self._gll_fused: Dict[int, tuple] = {}    # gauss_ll node id -> (partials buffer, units): set by _gauss_head
         self._pending: List[tuple] = []           # (step, label, node, tensors it writes): emitted before their first reader
-        if fuse and bool(getattr(_st.runtime, "head_in_contraction", True)):
-            hoist_mb = self.side_jobs_enabled()
-
-            def emitted_before(t, pos):
-                while t.node.op == "reshape":      # a view: what matters is where its source comes from
-                    t = t.node.inputs[0]
-                nd = t.node
-                if nd.op == "leaf:minibatch" and hoist_mb:
-                    return True                    # minibatch gathers are emitted first (see below)
-                cl = self._clusters.get(nd.id) or self._colclusters.get(nd.id)
-                last = cl.nodes[-1] if (cl is not None and len(cl.nodes) >= 2) else nd
-                return self._order_pos[last.id] < pos
-            for n in order:
-                if n.op != "gauss_ll" or len(n.inputs[1].shape) == 0:
-                    continue
-                ft = n.inputs[1]
-                while ft.node.op == "reshape":
-                    ft = ft.node.inputs[0]
-                sg = ft.node
-                hp = "likelihood head inside the forward contraction (hb_sgp_fwd_gauss)"
-                if sg.op != "sgp" or ft is not sg.outputs[0] or sg.id in self._sgp_head or sg.inputs[5].shape[-2] != 1:
-                    self.note(hp, n, False, "f is not the single latent function of an sgp draw" if sg.op != "sgp" or ft is not sg.outputs[0]
-                              else ("the draw already carries a head" if sg.id in self._sgp_head else "more than one latent function (P > 1)"))
-                    continue
-                if n.inputs[0].size != ft.size:
-                    self.note(hp, n, False, "y and f differ in size (a broadcast)")
-                    continue
-                pos = self._order_pos[sg.id]
-                others = [n.inputs[0], n.inputs[2]] + list(n.inputs[3:4])
-                if all(emitted_before(t, pos) for t in others):
-                    self._sgp_head[sg.id] = n
-                    self._gll_in_sgp[n.id] = sg
-                    self.note(hp, n, True)
-                else:
-                    self.note(hp, n, False, "y / var / scale are produced after the draw is launched")
-            # The same head riding in the MatBias product that produces its f (hb_matmul_gauss: a decoder layer feeding
-            # densities.gaussian): f is then never written.  Conditions: a plain 2-D product (bias allowed, no activation,
-            # nothing transposed) whose result feeds ONLY this head, and the head's other operands exist before it.
-            self._mm_head: Dict[int, Node] = {}       # matmul node id -> gauss_ll node
-            if bool(getattr(_st.runtime, "head_in_decoder", True)):
-                hp = "likelihood head inside the layer's product (hb_matmul_gauss)"
-                for n in order:
-                    if n.op != "gauss_ll" or n.id in self._gll_in_sgp or len(n.inputs[1].shape) != 2:
-                        continue
-                    ft, single = n.inputs[1], True
-                    while ft.node.op == "reshape":
-                        single = single and len(consumers.get(ft, [])) == 1
-                        ft = ft.node.inputs[0]
-                    mm = ft.node
-                    if mm.op != "matmul" or ft is not mm.outputs[0]:
-                        continue      # (not a layer's output: nothing to report)
-                    at = mm.attrs
-                    why = None
-                    if at["ta"] or at["tb"] or at.get("actgrad") or at["act"] != "none" or len(mm.inputs[0].shape) != 2 or len(mm.inputs[1].shape) != 2:
-                        why = "the product is transposed, batched or carries an activation"
-                    elif not single or len(consumers.get(ft, [])) != 1 or ft in self.outputs or ft in self._bind:
-                        why = "f is read by something else as well"
-                    elif n.inputs[0].shape != n.inputs[1].shape or mm.id in self._mm_head:
-                        why = "y and f differ in shape"
-                    elif not all(emitted_before(t, self._order_pos[mm.id]) for t in [n.inputs[0], n.inputs[2]] + list(n.inputs[3:4])):
-                        why = "y / var / scale are produced after the product is launched"
-                    elif hip_ops.matmul_gauss_units(ft.shape[0], mm.inputs[0].shape[1], ft.shape[1], dtype) == 0:
-                        why = "shape outside the row-streaming form (fp32, n >= 2048, 32 < N <= 256, K = 16 / 32 / 64 / 128)"
-                    if why is None:
-                        self._mm_head[mm.id] = n
-                        self._gll_in_sgp[n.id] = mm      # (same deferral of the fold as for a head riding in an sgp draw)
-                    self.note(hp, n, why is None, why or "")
-        # Concatenation in place: the parts of a concat along its leading non-unit axis are contiguous blocks of the
-        # result, so a part that a fused program (or a single elementwise launch) produces is WRITTEN there -- the
-        # gradient of a batched GP draw whose expert / gate halves come out of one column program needs no
-        # scatter + add (three launches over [2E, n] arrays at cfg 5).  _concat_emit copies whatever did not land in place.
-        self._place: Dict[Tensor, object] = {}
-        for n in order:
-            if n.op != "concat":
-                continue
-            o, ax = n.outputs[0], n.attrs["axis"]
-            if any(d != 1 for d in o.shape[:ax]):
-                continue
-            dst, off = None, 0
-            for t in n.inputs:
-                tgt = self._place_target(t)
-                if (tgt is not None and tgt not in self._bind and tgt not in self._place and tgt not in self.outputs
-                        and len(consumers.get(tgt, [])) == 1):
-                    if dst is None:
-                        dst = self.out(o).reshape(-1)
-                    self._place[tgt] = dst[off:off + t.size].view(tgt.shape)
-                off += t.size
-        # Weight gradient + bias gradient of a MatBias layer from one pass over the incoming gradient G: a 2-D product
-        # X^T G whose right operand is also column-summed (reduce over axis 0) becomes hb_matmul_colsum -- the GEMM folds
-        # the columns of G while it streams them, and the stand-alone reduction launches (two per layer) disappear.
         self._gram_for_chol: Dict[int, tuple] = {}   # cholesky node id -> (points, lengthscales, kind, jitter) of its folded Gram
         self._gram_in_mm: Dict[int, tuple] = {}      # gram_grad node id -> (lengthscale partials, rows, d, dl, groups): set by _matmul_emit
         self._gram_tiles: Dict[int, tuple] = {}      # gram_grad node id -> (tile partials, batch, M, d, dl): set by _matmul_emit
         self._chol_rider: Dict[Tensor, dict] = {}    # inverse tensor -> the persistent factorisation step's rider cell (_cholesky_emit)
-        self.step_riders: Dict[int, Node] = {}       # id(step closure) -> node whose work rides in that step's launch
         self._mlp2: Dict[int, dict] = {}             # mlp2_sample_kl node id -> {fused, ws | h}
-        self._colsum_of: Dict[int, Node] = {}    # matmul node id -> the reduce node it absorbs
-        self._fused_colsum = set()               # ids of absorbed reduce nodes
-        for n in order:
-            if (n.op != "matmul" or not n.attrs["ta"] or n.attrs["tb"] or n.attrs.get("actgrad") or len(n.inputs) != 2
-                    or n.attrs["act"] != "none" or len(n.inputs[0].shape) != 2 or len(n.inputs[1].shape) != 2):
-                continue
-            gmat = n.inputs[1]
-            for r in consumers.get(gmat, []):
-                ra = r.attrs if r.op == "reduce" else None
-                if (ra is None or r.id in self._fused_colsum or ra["kind"] != "sum" or ra["K1"] != 1
-                        or ra["R"] != gmat.shape[0] or ra["K2"] != gmat.shape[1]):
-                    continue
-                cl = self._clusters.get(r.id)
-                if cl is not None and len(cl.nodes) > 1:
-                    continue       # the reduction is part of a fused elementwise program
-                rout = r.outputs[0]
-                if any(self._order_pos[c.id] < self._order_pos[n.id] for c in consumers.get(rout, [])):
-                    continue       # somebody reads the sums before the GEMM has run
-                self._colsum_of[n.id] = r
-                self._fused_colsum.add(r.id)
-                self.note("weight + bias gradient from one pass (hb_matmul_colsum)", n, True)
-                break
         self._emitted: List[Node] = []      # nodes in emission order
         self._side_cands: List[dict] = []   # small independent steps that may ride on a later host launch (side jobs)
+        for t, b in (binds or []):
+            self._prebind(t, b)
+        if prologue:
+            prologue(self)
+        consumers, fuse, jit = self._consumers, _runtime("fuse_elementwise"), hip_ops.ewise_jit_enabled()
+        notes = [("elementwise fusion", None, False, "settings.runtime.fuse_elementwise is off")]   # the passes' ledger entries, in pass order
+        if fuse:
+            self._gll_post, self._absorbed, notes = _match_gauss_ll_tails(order, consumers, set(self.outputs))
+        # column programs first (short-and-wide spaces with row reductions inside: they need the compiled form), then
+        # the plain elementwise clusters over what is left
+        self._colclusters = cluster_columns(order, outputs=self.outputs, skip=self._absorbed,
+                                            enabled=fuse and jit and _runtime("column_programs"))
+        self._clusters = cluster_elementwise(order, enabled=fuse, skip=set(self._colclusters) | self._absorbed,
+                                             max_elems=EW_CLUSTER_MAX_ELEMS_JIT if jit else EW_CLUSTER_MAX_ELEMS)
+        if fuse and _runtime("head_in_contraction"):
+            before = _emitted_before(order, self._clusters, self._colclusters, self.side_jobs_enabled())
+            heads, nt = _match_head_in_contraction(order, before)
+            self._sgp_head = {sg.id: g for sg, g in heads.items()}
+            self._gll_in_sgp = {g.id: sg for sg, g in heads.items()}
+            notes += nt
+            if _runtime("head_in_decoder"):
+                heads, nt = _match_head_in_decoder(order, consumers, self.outputs, self._bind, before, set(self._gll_in_sgp),
+                                                   lambda n, k, m: hip_ops.matmul_gauss_units(n, k, m, dtype))
+                self._mm_head = {mm.id: g for mm, g in heads.items()}
+                self._gll_in_sgp.update((g.id, mm) for mm, g in heads.items())   # (the fold is deferred as for a head in an sgp draw)
+                notes += nt
+        # (allocated here: a concat's output, and so every buffer written in place, exists before the first node is emitted)
+        for tgt, (o, off) in _match_concat_placement(order, consumers, self._colclusters, self.outputs, self._bind).items():
+            self._place[tgt] = self.out(o).reshape(-1)[off:off + tgt.size].view(tgt.shape)
+        self._colsum_of, self._fused_colsum, nt = _match_colsum(order, consumers, self._clusters)
+        for entry in notes + nt:
+            self.note(*entry)
+        self._lower()
+
+    def _lower(self):
+        """Emit every node in order -- fused programs at their last member's position -- then the closing copies."""
         # minibatch gathers first: they depend on nothing, and emitted early they can ride on the first launch of the
         # Cholesky chain instead of being a launch of their own right before their first consumer
-        hoisted = set()
-        if self.side_jobs_enabled():
-            for n in order:
-                if n.op == "leaf:minibatch":
-                    self._emit(n)
-                    hoisted.add(n.id)
-        for n in order:
-            if n.id in hoisted:
+        hoist = self.side_jobs_enabled()
+        for n in self._order:
+            if hoist and n.op == "leaf:minibatch":
+                self._emit(n)
+        for n in self._order:
+            if hoist and n.op == "leaf:minibatch":
                 continue
             if n.id in self._absorbed:      # written by the likelihood head (hb_gauss_ll_post)
                 self._emitted.append(n)
@@ -2808,8 +2827,7 @@ class Plan:
         for t, b in list(self._bind.items()) + self._extra_copies:
             got = self._buf.get(t)
             if got is not None and got.data_ptr() != b.data_ptr():
-                src = got
-                self.steps.append(lambda src=src, b=b: hip_ops.ewise("COPY", [src.reshape(b.shape)], out=b))
+                self.steps.append(lambda src=got, b=b: self.H.ewise("COPY", [src.reshape(b.shape)], out=b))
 
     # -- buffer management
     def _prebind(self, t, b):
@@ -2836,18 +2854,6 @@ class Plan:
             else:
                 keep.append((step, label, node, writes))
         self._pending = keep
-
-    def _place_target(self, t):
-        """The tensor whose buffer a concat part really is: looks through reshapes (views) down to a value that a fused
-        program or a single elementwise launch writes through Plan.out; None when the producer keeps its own buffer."""
-        n = t.node
-        if n.id in self._colclusters:
-            return t if n.op != "strided" else None
-        if n.op == "reshape":
-            return self._place_target(n.inputs[0])
-        if n.op == "ew":
-            return t
-        return None
 
     def needed(self, t):
         return t in self._needed
@@ -2878,9 +2884,7 @@ class Plan:
 
     # -- side jobs (csrc/side_jobs.cuh): small independent steps recorded instead of launched, riding on a host launch
     def side_jobs_enabled(self):
-        from ._settings import settings as _st
-
-        return bool(getattr(_st.runtime, "side_jobs", True)) and self.dtype == self.torch.float32
+        return _runtime("side_jobs") and self.dtype == self.torch.float32
 
     def side_candidate(self, outs):
         """Register the step about to be appended as deferrable; returns the cell its closure must consult
@@ -2929,12 +2933,9 @@ class Plan:
     def pin_side_reads(self, tensors):
         """A step about to be emitted reads `tensors` although they are not inputs of its node (operands of a fused
         epilogue): pending side candidates that write one of them -- directly or behind reshape / stop_gradient views --
-        stop being adoptable, i.e. they run as a launch of their own at their original position."""
-        src = set()
-        for t in tensors:
-            while t is not None:
-                src.add(t)
-                t = t.node.inputs[0] if t.node.op in ("reshape", "stop_gradient") and t.node.inputs else None
+        stop being adoptable, i.e. they run as a launch of their own at their original position.  (A candidate writes
+        leaves or its own op's results, never a view: only the source behind the views can match.)"""
+        src = {_through(t, ("reshape", "stop_gradient")) for t in tensors}
         for c in self._side_cands:
             if not c["cell"]["defer"] and not c.get("dead") and any(o in src for o in c["outs"]):
                 c["dead"] = True
@@ -3199,9 +3200,7 @@ class Plan:
         if self._chains_fused:
             return
         self._chains_fused = True
-        from ._settings import settings as _st
-
-        if not bool(getattr(_st.runtime, "serial_chains", True)) or not self.H.ewise_jit_enabled():
+        if not _runtime("serial_chains") or not self.H.ewise_jit_enabled():
             return
         H = self.H
         out, i, steps = [], 0, self.steps

@@ -1,11 +1,14 @@
 """TEST INFRASTRUCTURE: one minimal graph per planner pass on which the pass fires, and neighbours on which it must
-decline (henbun_amd.graph.Plan.__init__, cluster_elementwise, cluster_columns and the lazy forms of the emit functions).
+decline (henbun_amd.graph: the graph-only matchers _match_gauss_ll_tails, _match_concat_placement and _match_colsum that
+Plan.__init__ runs, cluster_elementwise, cluster_columns and the lazy forms of the emit functions).
 
 PASSES[name] is a Spec: the builder, its leaf shapes, and `check(plan, tr)`, which asserts FROM THE PLAN (plan.explain,
 step labels, plan._place, plan._lazy_cols, plan._colsum_of, plan._gll_post, buffer sizes) that the pass did what the
 name says -- so that a planner change cannot leave the test passing while it tests something else.  PURE[name] asserts
-the part of the same expectation that cluster_elementwise / cluster_columns decide alone; the CPU suite runs those
-(tests/test_graph_lowering_cpu.py), the device suite runs both and then sends the values through tests/graph_device.py.
+the part of the same expectation that the graph-only functions decide alone, from (order, elementwise clusters, column
+clusters, y, Pure): `pure_decisions` computes those without a plan, `plan_decisions` reads them off a plan.  The CPU suite
+runs the PURE half (tests/test_graph_lowering_cpu.py), the device suite runs both and then sends the values through
+tests/graph_device.py.
 """
 from collections import namedtuple
 
@@ -17,6 +20,26 @@ from henbun_amd import graph as G
 Spec = namedtuple("Spec", "name build shapes positive kinds runtime weighted check")
 PASSES = {}
 PURE = {}
+
+
+Pure = namedtuple("Pure", "tails absorbed colsum fused_colsum place notes")
+
+
+def pure_decisions(order, outputs, column_programs=True):
+    """(elementwise clusters, column clusters, Pure): what the graph-only functions of henbun_amd.graph decide for this
+    graph, called in Plan.__init__'s order with its defaults (compiled programs, nothing bound); no plan, no device."""
+    consumers = G.consumer_map(order)
+    tails, absorbed, notes = G._match_gauss_ll_tails(order, consumers, set(outputs))
+    col = G.cluster_columns(order, outputs=outputs, skip=absorbed, enabled=column_programs)
+    ew = G.cluster_elementwise(order, max_elems=G.EW_CLUSTER_MAX_ELEMS_JIT, skip=set(col) | absorbed)
+    place = G._match_concat_placement(order, consumers, col, outputs, ())
+    colsum, fused_colsum, more = G._match_colsum(order, consumers, ew)
+    return ew, col, Pure(tails, absorbed, colsum, fused_colsum, place, notes + more)
+
+
+def plan_decisions(plan):
+    """The same record read off a plan (its ledger entries carry the node's label where the matchers' carry the node)."""
+    return Pure(plan._gll_post, plan._absorbed, plan._colsum_of, plan._fused_colsum, plan._place, plan.explain)
 
 
 def spec(name, build, shapes, check, positive=False, kinds=None, runtime=None, weighted=True, pure=None):
@@ -58,10 +81,6 @@ def fused_fwd(plan):
     return plan._clusters  # {node id: cluster}: clusters of >= 2 nodes become one program
 
 
-def decisions(plan, prefix):
-    return [(lab, fired, why) for p, lab, fired, why in plan.explain if p.startswith(prefix)]
-
-
 def launched_alone(plan, node):
     """The node got a launch of its own (it is not inside a fused program)."""
     c = plan._clusters.get(node.id)
@@ -73,7 +92,7 @@ def _chain(x):
     return G.unary("TANH", G.unary("EXP", x) * 0.5)
 
 
-def _pure_chain(order, ew, col, y):
+def _pure_chain(order, ew, col, y, m=None):
     c = ew.get(y.node.id)
     assert multi(c) and ew.get(one(fwd_nodes(y, "ew", "EXP")).id) is c
 
@@ -98,7 +117,7 @@ def _ext_inputs(c, ew):
     return {t for m in c.nodes for t in m.inputs if ew.get(t.node.id) is not c}
 
 
-def _pure_many_in(order, ew, col, y):
+def _pure_many_in(order, ew, col, y, m=None):
     assert G.EW_CLUSTER_MAX_IN == 12
     cl = {id(c): c for c in ew.values()}.values()
     assert all(len(_ext_inputs(c, ew)) <= G.EW_CLUSTER_MAX_IN for c in cl)
@@ -119,7 +138,7 @@ def _seven_outputs(x):
     return G.concat([G.unary(f, x) for f in _SEVEN], 0)
 
 
-def _pure_seven(order, ew, col, y):
+def _pure_seven(order, ew, col, y, m=None):
     assert G.EW_CLUSTER_MAX_OUT == 6
     parts = [t.node for t in y.node.inputs]
     c = ew[parts[0].id]
@@ -144,7 +163,7 @@ def _long_chain(x):
     return t
 
 
-def _pure_long(order, ew, col, y):
+def _pure_long(order, ew, col, y, m=None):
     # EW_CLUSTER_MAX_INSTR (44) is never the limit that binds: the margin on results, 4 * EW_CLUSTER_MAX_OUT = 24 nodes,
     # closes a cluster first.  A 50-op chain therefore splits at 24 nodes, and no cluster passes either limit.
     assert G.EW_CLUSTER_MAX_INSTR == 44 and 4 * G.EW_CLUSTER_MAX_OUT == 24
@@ -169,7 +188,7 @@ def _outer(x, y):
     return G.unary("TANH", x) + G.unary("SIGMOID", y)
 
 
-def _pure_outer(order, ew, col, y):
+def _pure_outer(order, ew, col, y, m=None):
     assert G._merge_space((3, 1), (1, 4)) is None and G._merge_space((3, 1), (3, 4)) == (3, 4)
     a, b = one(fwd_nodes(y, "ew", "TANH")), one(fwd_nodes(y, "ew", "SIGMOID"))
     assert ew[a.id] is not ew[b.id]
@@ -188,7 +207,7 @@ def _sealed(x):
     return G.unary("TANH", a * m) + 1.0       # (reads the maximum: it cannot be ordered before the reduction)
 
 
-def _pure_sealed(order, ew, col, y):
+def _pure_sealed(order, ew, col, y, m=None):
     a = one(fwd_nodes(y, "ew", "EXP"))
     b = one(fwd_nodes(y, "ew", "TANH"))
     ca, cb = ew[a.id], ew[b.id]
@@ -213,7 +232,7 @@ def _fullsum(x):
 
 
 def _pure_fullsum(fires):
-    def pure(order, ew, col, y):
+    def pure(order, ew, col, y, m=None):
         assert G.EW_REDUCE_MAX_ELEMS == 512
         r = one(fwd_nodes(y, "reduce"))
         c = ew.get(r.id)
@@ -240,7 +259,7 @@ def _four_sums(x):
     return G.concat([G.reduce_sum(G.unary(f, x), keepdims=True) for f in ("TANH", "SIGMOID", "EXP", "SOFTPLUS")], 1)
 
 
-def _pure_four(order, ew, col, y):
+def _pure_four(order, ew, col, y, m=None):
     rs = [t.node for t in y.node.inputs]
     assert [r.op for r in rs] == ["reduce"] * 4
     inside = [r for r in rs if r.id in ew]
@@ -263,7 +282,7 @@ def _sum_read_inside(x):
     return t / G.reduce_sum(G.unary("EXP", t), keepdims=True)
 
 
-def _pure_read_inside(order, ew, col, y):
+def _pure_read_inside(order, ew, col, y, m=None):
     r = one(fwd_nodes(y, "reduce"))
     c = ew[r.id]
     assert r.outputs[0] in c.reduced and ew[y.node.id] is not c       # the division reads the complete sum: next program
@@ -283,7 +302,7 @@ def _softmax0(x):
 
 
 def _pure_col(fires):
-    def pure(order, ew, col, y):
+    def pure(order, ew, col, y, m=None):
         assert (G.EW_COL_MAX_ROWS, G.EW_COL_MIN_COLS) == (8, 512)
         rs = fwd_nodes(y, "reduce")
         assert len(rs) == 2
@@ -326,7 +345,7 @@ def _softmax_of_rows_also_output(x):
 
 
 def _pure_slice(in_place):
-    def pure(order, ew, col, y):
+    def pure(order, ew, col, y, m=None):
         s = one(fwd_nodes(y, "strided"))
         assert G._col_strided_view(s, 2, 512) == ("full", 512, 512)
         assert col and (s.id in col) == in_place and y.node.id in col
@@ -390,9 +409,19 @@ def _placed(plan, t):
     return True
 
 
+def _pure_concat(expect, first=False):
+    """expect: for each part of the forward concat, whether it must be written in place."""
+    def pure(order, ew, col, y, m):
+        cat = _concat_first(y) if first else one(fwd_nodes(y, "concat"))
+        got = [G._through(t) in m.place for t in cat.inputs]
+        assert got == list(expect), got
+    return pure
+
+
 def _concat_check(expect):
     """expect: for each part of the forward concat, whether it must be written in place."""
     def check(plan, tr):
+        _pure_concat(expect)(None, None, None, tr.y, plan_decisions(plan))
         cat = one(fwd_nodes(tr.y, "concat"))
         got = []
         for t in cat.inputs:
@@ -420,6 +449,7 @@ def _concat_first(y):
 
 def _concat_check_first(expect):
     def check(plan, tr):
+        _pure_concat(expect, first=True)(None, None, None, tr.y, plan_decisions(plan))
         cat = _concat_first(tr.y)
         assert [_placed(plan, t) for t in cat.inputs] == list(expect)
     return check
@@ -445,14 +475,18 @@ def _concat_leaf(x):
     return G.concat([x, b], 1)
 
 
-spec("concat_parts_from_programs_are_written_in_place", _concat_plain, [(1, 6)], _concat_check([True, True]))
-spec("concat_part_with_two_consumers_is_copied", _concat_two_consumers, [(1, 6)], _concat_check_first([False, True]))
-spec("concat_part_that_is_an_output_is_copied", _concat_also_output, [(1, 6)], _concat_check([False, True]))
-spec("concat_of_the_same_tensor_twice_is_copied", _concat_twice, [(1, 6)], _concat_check([False, False]))
-# (Plan._place_target looks through reshapes -- they are views -- so a reshaped part IS written in place)
-spec("concat_part_behind_a_reshape_is_written_in_place", _concat_reshaped, [(1, 6)], _concat_check([True, True]))
-spec("concat_below_a_non_unit_leading_axis_is_copied", _concat_plain, [(4, 6)], _concat_check([False, False]))
-spec("concat_part_that_is_a_leaf_is_copied", _concat_leaf, [(1, 6)], _concat_check([False, True]))
+def concat_spec(name, build, shapes, expect, first=False):
+    spec(name, build, shapes, (_concat_check_first if first else _concat_check)(expect), pure=_pure_concat(expect, first))
+
+
+concat_spec("concat_parts_from_programs_are_written_in_place", _concat_plain, [(1, 6)], [True, True])
+concat_spec("concat_part_with_two_consumers_is_copied", _concat_two_consumers, [(1, 6)], [False, True], first=True)
+concat_spec("concat_part_that_is_an_output_is_copied", _concat_also_output, [(1, 6)], [False, True])
+concat_spec("concat_of_the_same_tensor_twice_is_copied", _concat_twice, [(1, 6)], [False, False])
+# (_match_concat_placement looks through reshapes -- they are views -- so a reshaped part IS written in place)
+concat_spec("concat_part_behind_a_reshape_is_written_in_place", _concat_reshaped, [(1, 6)], [True, True])
+concat_spec("concat_below_a_non_unit_leading_axis_is_copied", _concat_plain, [(4, 6)], [False, False])
+concat_spec("concat_part_that_is_a_leaf_is_copied", _concat_leaf, [(1, 6)], [False, True])
 
 
 # ---- weight + bias gradient from one pass (hb_matmul_colsum) ---------------------------------------------------------
@@ -476,26 +510,40 @@ def _colsum_in_cluster(g):
     return G.matmul(G.constant(_X84), gm, transpose_a=True) + G.reduce_sum(gm, 0, keepdims=True)
 
 
+def _pure_colsum(fires, why=None):
+    def pure(order, ew, col, y, m):
+        mm = one([n for n in fwd_nodes(y, "matmul") if n.attrs["ta"]])
+        r = one(fwd_nodes(y, "reduce"))
+        if fires:
+            assert m.colsum.get(mm.id) is r and r.id in m.fused_colsum
+            assert any(f for p, _, f, _ in m.notes if p.startswith("weight + bias gradient from one pass"))
+        else:
+            assert mm.id not in m.colsum and r.id not in m.fused_colsum
+        if why == "cluster":
+            assert multi(ew.get(r.id))
+        if why == "early":
+            pos = {n.id: i for i, n in enumerate(order)}
+            assert any(pos[c.id] < pos[mm.id] for c in G.consumer_map(order)[r.outputs[0]])
+    return pure
+
+
 def _colsum_check(fires, why=None):
     def check(plan, tr):
-        mm = one([n for n in fwd_nodes(tr.y, "matmul") if n.attrs["ta"]])
-        r = one(fwd_nodes(tr.y, "reduce"))
-        if fires:
-            assert plan._colsum_of.get(mm.id) is r and r.id in plan._fused_colsum
-            assert any(f for _, f, _ in decisions(plan, "weight + bias gradient from one pass"))
-        else:
-            assert mm.id not in plan._colsum_of and r.id not in plan._fused_colsum
-        if why == "cluster":
-            assert multi(plan._clusters.get(r.id))
+        _pure_colsum(fires, why)(plan._order, plan._clusters, None, tr.y, plan_decisions(plan))
         if why == "early":
+            mm = one([n for n in fwd_nodes(tr.y, "matmul") if n.attrs["ta"]])
             pos = plan._order_pos
-            assert any(pos[c.id] < pos[mm.id] for c in plan._consumers[r.outputs[0]])
+            assert any(pos[c.id] < pos[mm.id] for c in plan._consumers[one(fwd_nodes(tr.y, "reduce")).outputs[0]])
     return check
 
 
-spec("colsum_rides_in_the_product", _colsum_fires, [(8, 4), (8, 5)], _colsum_check(True))
-spec("colsum_read_before_the_product_is_a_launch", _colsum_read_early, [(8, 4), (8, 5)], _colsum_check(False, "early"))
-spec("colsum_inside_a_program_stays_there", _colsum_in_cluster, [(8, 1)], _colsum_check(False, "cluster"))
+def colsum_spec(name, build, shapes, fires, why=None):
+    spec(name, build, shapes, _colsum_check(fires, why), pure=_pure_colsum(fires, why))
+
+
+colsum_spec("colsum_rides_in_the_product", _colsum_fires, [(8, 4), (8, 5)], True)
+colsum_spec("colsum_read_before_the_product_is_a_launch", _colsum_read_early, [(8, 4), (8, 5)], False, "early")
+colsum_spec("colsum_inside_a_program_stays_there", _colsum_in_cluster, [(8, 1)], False, "cluster")
 
 
 # ---- the likelihood head's elementwise tail (hb_gauss_ll_post) -------------------------------------------------------
@@ -510,20 +558,26 @@ def _gll_tail_read_twice(yy, f, s, v):
     return G.reduce_sum(hb.densities.gaussian(yy, f * s, v))
 
 
+def _pure_gll(fires):
+    def pure(order, ew, col, y, m):
+        head = one([n for n in order if n.op == "gauss_ll"])
+        assert len(head.inputs) == 4                       # (the scale was recognised: the tail is scale * (post * dmu))
+        assert (head.id in m.tails) == fires
+        assert [f for p, _, f, _ in m.notes if p.startswith("likelihood head writes")] == [fires]
+        if fires:
+            assert len(m.tails[head.id][2]) == 2 and all(x.id in m.absorbed for x in m.tails[head.id][2])
+    return pure
+
+
 def _gll_check(fires):
     def check(plan, tr):
-        head = one([n for n in plan._order if n.op == "gauss_ll"])
-        assert len(head.inputs) == 4                       # (the scale was recognised: the tail is scale * (post * dmu))
-        assert (head.id in plan._gll_post) == fires
-        d = decisions(plan, "likelihood head writes")
-        assert [f for _, f, _ in d] == [fires]
-        if fires:
-            assert len(plan._gll_post[head.id][2]) == 2 and all(m.id in plan._absorbed for m in plan._gll_post[head.id][2])
+        _pure_gll(fires)(plan._order, None, None, tr.y, plan_decisions(plan))
     return check
 
 
-spec("gauss_ll_writes_its_elementwise_tail", _gll_tail, [(8,), (1,), (1,)], _gll_check(True), positive=True)
-spec("gauss_ll_tail_read_twice_stays_elementwise", _gll_tail_read_twice, [(8,), (8,), (1,), (1,)], _gll_check(False), positive=True)
+spec("gauss_ll_writes_its_elementwise_tail", _gll_tail, [(8,), (1,), (1,)], _gll_check(True), positive=True, pure=_pure_gll(True))
+spec("gauss_ll_tail_read_twice_stays_elementwise", _gll_tail_read_twice, [(8,), (8,), (1,), (1,)], _gll_check(False), positive=True,
+     pure=_pure_gll(False))
 
 
 # ---- lazy column block ---------------------------------------------------------------------------------------------------
@@ -572,7 +626,7 @@ def _check_partial_scatter(plan, tr):
 
 
 spec("transpose_of_a_column_is_a_reshape", lambda x: G.unary("TANH", G.transpose(x, [1, 0])), [(5, 1)], _check_transpose_column,
-     pure=lambda order, ew, col, y: _check_pure_no_strided(y))
+     pure=lambda order, ew, col, y, m=None: _check_pure_no_strided(y))
 spec("true_transpose_is_a_copy_and_its_gradient_a_full_scatter", lambda x: G.unary("TANH", G.transpose(x, [1, 0])), [(3, 4)],
      _check_transpose_true)
 spec("slice_gradient_is_a_fill_and_a_partial_scatter", lambda x: G.unary("TANH", x[:, 1:3]), [(4, 6)], _check_partial_scatter)

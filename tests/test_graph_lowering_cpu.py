@@ -2,12 +2,16 @@
 
 Every graph the device tests run is traced, differentiated and evaluated here first, with the CPU evaluator
 (tests/graph_oracle.py), in float64 and in float32; the generated graphs are shown to be 32 graphs with finite, moderate
-values that make the planner cluster and concatenate; and the fire / decline expectations that depend only on the pure
-clustering functions are asserted without a device."""
+values that make the planner cluster and concatenate; and the fire / decline expectations that depend only on the
+planner's graph-only functions (the clustering, the likelihood head's tail, concat placement, the colsum pairing) are
+asserted without a device."""
+import re
+
 import numpy as np
 import pytest
 import torch
 
+import henbun_amd as hb
 from henbun_amd import graph as G
 
 import graph_cases as GC
@@ -71,12 +75,35 @@ def test_generated_graphs_trace_evaluate_and_exercise_the_planner():
 
 @pytest.mark.parametrize("name", sorted(GP.PURE))
 def test_clustering_decisions_that_need_no_device(name):
-    """The fire / decline expectations of tests/test_graph_passes_gpu.py that cluster_elementwise / cluster_columns
-    decide alone."""
+    """The fire / decline expectations of tests/test_graph_passes_gpu.py that the planner's graph-only functions decide
+    alone (tests/graph_passes.pure_decisions)."""
     spec = GP.PASSES[name]
     leaves, arrs, y, grads, outs = _trace(spec.build, spec.shapes, spec.positive)
     order = G.topo_order(outs)
-    col = G.cluster_columns(order, outputs=outs)
-    ew = G.cluster_elementwise(order, max_elems=G.EW_CLUSTER_MAX_ELEMS_JIT, skip=set(col))
-    GP.PURE[name](order, ew, col, y)
+    ew, col, m = GP.pure_decisions(order, outs)
+    GP.PURE[name](order, ew, col, y, m)
     GO.evaluate(outs, dict(zip(leaves, arrs)))
+
+
+def test_runtime_flag_table():
+    """Every settings.runtime flag the planner reads goes through graph._runtime, whose table holds the defaults the
+    call sites carried before there was a table."""
+    with open(G.__file__) as f:
+        src = f.read()
+    used = re.findall(r'_runtime\("(\w+)"\)', src)
+    assert len(used) == src.count("_runtime(") - 1 == 11          # (every call names its flag literally; one is the def)
+    assert set(used) == set(G._RUNTIME_DEFAULTS)
+    assert src.count("_settings.runtime") == 1 and not re.search(r"^\s+from \._settings import", src, re.M)
+    assert G._RUNTIME_DEFAULTS == {
+        "fuse_elementwise": True, "column_programs": True, "head_in_contraction": True, "head_in_decoder": True,
+        "side_jobs": True, "serial_chains": True, "fused_encoder": True, "fold_gram": True, "fused_predict": True,
+        "early_forward": False, "gram_vjp_in_product": False}
+    cfg = hb.settings.get_settings()
+    for name, default in G._RUNTIME_DEFAULTS.items():
+        if hasattr(cfg.runtime, name):
+            delattr(cfg.runtime, name)
+    with hb.settings.temp_settings(cfg):
+        assert {k: G._runtime(k) for k in G._RUNTIME_DEFAULTS} == G._RUNTIME_DEFAULTS       # unnamed: the default
+        for name, default in G._RUNTIME_DEFAULTS.items():
+            setattr(cfg.runtime, name, not default)
+            assert G._runtime(name) is (not default)                                        # named: the setting

@@ -34,8 +34,8 @@ def test_pass(name):
     tr = GD.Traced(spec.build, spec.shapes, kinds=spec.kinds, positive=spec.positive, dtype="float64", weighted=spec.weighted)
     if name in GP.PURE:
         order = tr.order()
-        col = G.cluster_columns(order, outputs=tr.outputs, enabled=bool(spec.runtime.get("column_programs", True)))
-        GP.PURE[name](order, G.cluster_elementwise(order, max_elems=G.EW_CLUSTER_MAX_ELEMS_JIT, skip=set(col)), col, tr.y)
+        ew, col, m = GP.pure_decisions(order, tr.outputs, column_programs=bool(spec.runtime.get("column_programs", True)))
+        GP.PURE[name](order, ew, col, tr.y, m)
     GD.run_modes(tr, name, ("default", "plain", "captured"), inspect=_inspect(spec, tr), runtime=spec.runtime)
     tr32 = GD.Traced(spec.build, spec.shapes, kinds=spec.kinds, positive=spec.positive, dtype="float32", weighted=spec.weighted)
     GD.run_modes(tr32, name, ("default",), inspect=_inspect(spec, tr32), runtime=spec.runtime)
