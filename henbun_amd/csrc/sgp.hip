@@ -24,7 +24,7 @@
 #include <type_traits>
 #include "gemm_tile.cuh"
 #include "rng_pairs.cuh"
-#include "../../include/henbun_hip.h"
+#include "host_calls.cuh"   // hb_matmul
 
 #define SGP_BM 64
 #define SGP_BN 128
@@ -3709,19 +3709,6 @@ __global__ void __launch_bounds__(256) sgp_xbar_kernel(const T* __restrict__ x, 
   }
 }
 
-static inline int sgp_matmul(const float* A, const float* B, float* C, long batch, long M, long N, long K, long lda,
-                             long ldb, long ldc, long sA, long sB, long sC, int tA, int tB, double alpha, int flags,
-                             float* ws, long wse, void* stream) {
-  return hb_matmul_f32(A, B, C, batch, M, N, K, lda, ldb, ldc, sA, sB, sC, tA, tB, alpha, 0.0, nullptr, 0, HB_ACT_NONE,
-                       flags, ws, wse, stream);
-}
-static inline int sgp_matmul(const double* A, const double* B, double* C, long batch, long M, long N, long K, long lda,
-                             long ldb, long ldc, long sA, long sB, long sC, int tA, int tB, double alpha, int flags,
-                             double* ws, long wse, void* stream) {
-  return hb_matmul_f64(A, B, C, batch, M, N, K, lda, ldb, ldc, sA, sB, sC, tA, tB, alpha, 0.0, nullptr, 0, HB_ACT_NONE,
-                       flags, ws, wse, stream);
-}
-
 static int sgp_bwd_strip_launch(SgpBwdArgs<float> a, long E, long nS, hipStream_t stream) {
   dim3 grid = sgp_grid(nS, 1, E, a.efast);
 #define HB_KBS(D_)                                                                                               \
@@ -3877,7 +3864,7 @@ static int sgp_bwd(int kind, int mode, const T* x, long sx, const T* z, const T*
     hipLaunchKernelGGL(sgp_strip_finish_kernel<T>, dim3((unsigned)hb_cdiv(M, 64), (unsigned)(2 * d + P), (unsigned)E), dim3(256), 0,
                        stream, mmws, (int)nS, M, d, dl, P, zbar, ellbar, ubar);
     HB_LAUNCH_CHECK();
-    int rc2 = sgp_matmul(Kbar, A, Lbar, E, M, M, n, n, n, M, M * n, M * n, M * M, 0, 1, -1.0, HB_MM_TRIL_OUT, mmws, mmws_elems,
+    int rc2 = hb_matmul(Kbar, A, Lbar, E, M, M, n, n, n, M, M * n, M * n, M * M, 0, 1, -1.0, HB_MM_TRIL_OUT, mmws, mmws_elems,
                          (void*)stream);
     return rc2;
   }
@@ -3926,7 +3913,7 @@ static int sgp_bwd(int kind, int mode, const T* x, long sx, const T* z, const T*
   }
   // Lbar = -tril(Kbar A^T): contraction over the data axis, split-K, lower tiles only
   if (n > 0) {
-    int rc = sgp_matmul(Kbar, A, Lbar, E, M, M, n, n, n, M, M * n, M * n, M * M, 0, 1, -1.0, HB_MM_TRIL_OUT, mmws,
+    int rc = hb_matmul(Kbar, A, Lbar, E, M, M, n, n, n, M, M * n, M * n, M * M, 0, 1, -1.0, HB_MM_TRIL_OUT, mmws,
                         mmws_elems, (void*)stream);
     if (rc) return rc;
   } else {

@@ -31,9 +31,8 @@
 // K(z, X) at a fixed q(u) ("Hyper-parameter gradient at fixed q(u)").  r takes the place of Y[:, 0] in ys,
 // w is staged next to it and multiplies the accumulator before + R r; everything else is the code above, so w == 1,
 // r = Y[:, 0] returns the bits of hb_sgp_kgrad_* at P = 1 (x * 1.0 is exact).  Columns beyond N hold K = 0 as before.
-#include "common.cuh"
+#include "host_calls.cuh"   // hb_round64, HB_REQUIRE_RBF_MODEL
 #include "gram_value.cuh"
-#include "../../include/henbun_hip.h"
 
 #define KG_NB 32         // columns per step (two MFMA column tiles)
 #define KG_THREADS 512   // 8 waves
@@ -263,7 +262,6 @@ __global__ void __launch_bounds__(256) sgp_kgrad_fold_kernel(const double* __res
   zbar[q] = -s / (l * l);
 }
 
-static inline long kg_round(long v) { return (v + 63) & ~63L; }
 static inline bool kg_is_fast(long M, long d, long P) {
   return M % 16 == 0 && M <= KG_MMAX && d <= KG_DMAX && P <= KG_PMAX && hb_debug_get("sgp_kgrad_plain", 0) == 0;
 }
@@ -272,7 +270,7 @@ extern "C" long hb_sgp_kgrad_ws_elems(long N, long M, long d, long P) {
   (void)N;
   if (M <= 0 || d <= 0 || P <= 0) return 0;
   // the larger of the two forms, so that the diagnostic switch sgp_kgrad_plain needs no other workspace
-  const long fast = kg_round(M * M) + KG_MAXG * kg_round(M * d + d), plain = KG_MAXG * kg_round(2 * M * d);
+  const long fast = hb_round64(M * M) + KG_MAXG * hb_round64(M * d + d), plain = KG_MAXG * hb_round64(2 * M * d);
   return fast > plain ? fast : plain;
 }
 
@@ -297,9 +295,8 @@ static int sgp_kgrad(int kind, const T* X, const T* Y, const double* w, const do
                      long dl, const double* Q, const double* R, double* zbar, double* ellbar, long N, long M, long d, long P,
                      double* ws, hipStream_t st) {
   const char* who = WT ? "hb_sgp_wkgrad" : "hb_sgp_kgrad";
-  HB_REQUIRE(kind == HB_KERN_RBF, "%s: only the UnitRBF kernel is supported (kind=%d)", who, kind);
   HB_REQUIRE(N >= 1 && M >= 1 && d >= 1 && P >= 1, "%s: bad extents (N=%ld M=%ld d=%ld P=%ld)", who, N, M, d, P);
-  HB_REQUIRE(dl == 1 || dl == d, "%s: lengthscales must have 1 or d entries", who);
+  HB_REQUIRE_RBF_MODEL(who, "is supported", kind, dl, d, (const void*)nullptr, M);   // (no Wfrag: W is not an operand)
   HB_REQUIRE(X && (WT ? (w && r) : Y != nullptr) && z && ell && Q && R, "%s: NULL input pointer", who);
   HB_REQUIRE(zbar && ellbar, "%s: NULL output pointer", who);
   HB_REQUIRE(d <= 256 && P <= 256 && M + d + P <= 8000, "%s: M=%ld d=%ld P=%ld too large", who, M, d, P);
@@ -313,8 +310,8 @@ static int sgp_kgrad(int kind, const T* X, const T* Y, const double* w, const do
     hipLaunchKernelGGL(sgp_kgrad_pack_kernel, dim3(hb_stream_grid(M * M, 256)), dim3(256), 0, st, Q, Qf, M);
     HB_LAUNCH_CHECK();
     a.Q = Qf;
-    a.part = ws + kg_round(M * M);
-    a.stride = kg_round(M * d + d);
+    a.part = ws + hb_round64(M * M);
+    a.stride = hb_round64(M * d + d);
     a.steps = (N + KG_NB - 1) / KG_NB;
     a.per = (a.steps + KG_MAXG - 1) / KG_MAXG;
     G = (a.steps + a.per - 1) / a.per;   // <= KG_MAXG, every workgroup has at least one step
@@ -330,7 +327,7 @@ static int sgp_kgrad(int kind, const T* X, const T* Y, const double* w, const do
   } else {
     a.Q = Q;
     a.part = ws;
-    a.stride = kg_round(2 * M * d);
+    a.stride = hb_round64(2 * M * d);
     a.steps = N;
     a.per = (N + KG_MAXG - 1) / KG_MAXG;
     G = (N + a.per - 1) / a.per;

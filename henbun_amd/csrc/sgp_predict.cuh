@@ -5,9 +5,8 @@
 // every entry that reports a mean or a variance stores the same bits.
 #ifndef HB_SGP_PREDICT_CUH
 #define HB_SGP_PREDICT_CUH
-#include "common.cuh"
+#include "host_calls.cuh"   // hb_chunk_cols, hb_sgp_A, hb_matmul, HB_REQUIRE_RBF_MODEL
 #include "sgp_strip.cuh"
-#include "../../include/henbun_hip.h"
 
 #define PRED_THREADS 512          // 8 waves; wave w owns the row tiles w and nT - 1 - w (balanced triangular work)
 #define PRED_PMAX 4               // latent functions whose means / variances the fused form keeps per thread
@@ -287,26 +286,6 @@ static inline bool pred_fused_ok(long E, long n, long M, long d, long P, int s_k
 }
 static inline bool pred_is_fused(long E, long n, long M, long d, long P, int s_kind, bool has_wfrag, int dbytes) {
   return dbytes == 4 && has_wfrag && pred_fused_ok(E, n, M, d, P, s_kind);
-}
-
-static inline int pred_sgp_A(int kind, const float* x, long sx, const float* z, const float* ell, long dl, const float* W,
-                             const float* Wf, float* A, long E, long n, long M, long d, hipStream_t st) {
-  return hb_sgp_A_f32(kind, x, sx, z, ell, dl, W, Wf, HB_PREC_NATIVE, A, E, n, M, d, st);
-}
-static inline int pred_sgp_A(int kind, const double* x, long sx, const double* z, const double* ell, long dl, const double* W,
-                             const double* Wf, double* A, long E, long n, long M, long d, hipStream_t st) {
-  return hb_sgp_A_f64(kind, x, sx, z, ell, dl, W, Wf, HB_PREC_NATIVE, A, E, n, M, d, st);
-}
-// C = op(A) B, op = transpose when transA
-static inline int pred_matmul(const float* A, const float* B, float* C, long batch, long Mo, long N, long K, long lda, long ldb,
-                              long ldc, long sA, long sB, long sC, int transA, hipStream_t st) {
-  return hb_matmul_f32(A, B, C, batch, Mo, N, K, lda, ldb, ldc, sA, sB, sC, transA, 0, 1.0, 0.0, nullptr, 0, HB_ACT_NONE, 0,
-                       nullptr, 0, st);
-}
-static inline int pred_matmul(const double* A, const double* B, double* C, long batch, long Mo, long N, long K, long lda,
-                              long ldb, long ldc, long sA, long sB, long sC, int transA, hipStream_t st) {
-  return hb_matmul_f64(A, B, C, batch, Mo, N, K, lda, ldb, ldc, sA, sB, sC, transA, 0, 1.0, 0.0, nullptr, 0, HB_ACT_NONE, 0,
-                       nullptr, 0, st);
 }
 
 #endif  // HB_SGP_PREDICT_CUH

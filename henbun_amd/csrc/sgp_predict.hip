@@ -45,12 +45,7 @@ __global__ void __launch_bounds__(PRED_THREADS) sgp_predict_strip_kernel(PredArg
 
 static inline long pred_chunk_cols(long E, long n, long M, long P, int s_kind) {
   const long per_col = E * M + (s_kind == HB_SGP_S_TRIL ? E * P * (E * P * M) : 0);
-  long c = HB_PRED_CHUNK_ELEMS / (per_col > 0 ? per_col : 1);
-  c = c < HB_PRED_CHUNK ? c : HB_PRED_CHUNK;
-  c = c & ~31L;
-  if (c < 32) c = 32;
-  const long n32 = (n + 31) & ~31L;
-  return c < n32 ? c : (n32 > 0 ? n32 : 32);
+  return hb_chunk_cols(HB_PRED_CHUNK_ELEMS, per_col, HB_PRED_CHUNK, n);
 }
 
 extern "C" int hb_sgp_predict_fused(long E, long n, long M, long d, long P, int s_kind, int has_wfrag, int dtype_bytes) {
@@ -81,20 +76,18 @@ template <typename T>
 static int sgp_predict(int kind, const T* x, long sx, const T* z, const T* ell, long dl, const T* W, const T* Wf, const T* m,
                        const T* s, int s_kind, int mode, double jitter, T* mean, T* var, long E, long n, long M, long d, long P,
                        T* ws, hipStream_t st) {
-  HB_REQUIRE(kind == HB_KERN_RBF, "hb_sgp_predict: only the UnitRBF kernel has a closed-form predictive (kind=%d)", kind);
   HB_REQUIRE(mode == HB_SGP_NEGLECTED || mode == HB_SGP_DIAGONAL || mode == HB_SGP_FULLRANK,
              "hb_sgp_predict: unknown residual mode %d", mode);
   HB_REQUIRE(s_kind == HB_SGP_S_DIAG || s_kind == HB_SGP_S_TRIL, "hb_sgp_predict: unknown s_kind %d", s_kind);
   HB_REQUIRE(E >= 1 && n >= 0 && M >= 1 && d >= 1 && P >= 1, "hb_sgp_predict: bad extents (E=%ld n=%ld M=%ld d=%ld P=%ld)",
              E, n, M, d, P);
-  HB_REQUIRE(dl == 1 || dl == d, "hb_sgp_predict: lengthscales must have 1 or d entries");
   HB_REQUIRE(sx == 0 || sx == n * d, "hb_sgp_predict: x is shared (sx = 0) or [E, n, d] (sx = n d), got sx=%ld", sx);
   HB_REQUIRE(x && z && ell && W && m && s && mean && var, "hb_sgp_predict: NULL pointer");
   HB_REQUIRE(E <= 65535, "hb_sgp_predict: too many experts");
   const long R = E * P * M;
-  HB_REQUIRE(M * M < 2147483647L && n * d < 2147483647L && (s_kind == HB_SGP_S_DIAG || R * R < 2147483647L),
+  HB_REQUIRE(n * d < 2147483647L && (s_kind == HB_SGP_S_DIAG || R * R < 2147483647L),
              "hb_sgp_predict: matrix too large");
-  HB_REQUIRE(!Wf || ((uintptr_t)Wf % 16 == 0 && M % 32 == 0), "hb_sgp_predict: Wfrag needs 16-byte alignment and M %% 32 == 0");
+  HB_REQUIRE_RBF_MODEL("hb_sgp_predict", "has a closed-form predictive", kind, dl, d, Wf, M);
   if (n == 0) return 0;
   const bool fused = pred_is_fused(E, n, M, d, P, s_kind, Wf != nullptr, (int)sizeof(T));
   const long need = hb_sgp_predict_ws_elems(E, n, M, d, P, s_kind, Wf != nullptr, (int)sizeof(T));
@@ -120,12 +113,12 @@ static int sgp_predict(int kind, const T* x, long sx, const T* z, const T* ell, 
   T* Cbuf = s_kind == HB_SGP_S_TRIL ? ws + nc_max * E * M : nullptr;
   for (long j0 = 0; j0 < n; j0 += nc_max) {
     const long nc = n - j0 < nc_max ? n - j0 : nc_max;
-    int rc = pred_sgp_A(kind, x + j0 * d, sx, z, ell, dl, W, Wf, Abuf, E, nc, M, d, st);
+    int rc = hb_sgp_A(kind, x + j0 * d, sx, z, ell, dl, W, Wf, Abuf, E, nc, M, d, st);
     if (rc) return rc;
     if (Cbuf) {
       // C_ep = S_ep^T A_e: op(A) of the product is the [M, R] row block of S transposed
       for (long e = 0; e < E; ++e) {
-        rc = pred_matmul(s + e * P * M * R, Abuf + e * M * nc, Cbuf + e * P * R * nc, P, R, nc, M, R, nc, nc, M * R, 0, R * nc, 1, st);
+        rc = hb_matmul(s + e * P * M * R, Abuf + e * M * nc, Cbuf + e * P * R * nc, P, R, nc, M, R, nc, nc, M * R, 0, R * nc, 1, st);
         if (rc) return rc;
       }
     }

@@ -21,9 +21,8 @@
 // coalesced.  Only lower-triangle values are ever stored, so cov is bitwise symmetric.  Every tile is independent.
 //
 // fp64 runs a plain FMA loop in the same order (parity, not speed).
-#include "common.cuh"
+#include "host_calls.cuh"   // hb_round64, hb_sgp_A, hb_matmul, HB_REQUIRE_RBF_MODEL
 #include "gram_value.cuh"
-#include "../../include/henbun_hip.h"
 
 #define COV_BT 128               // output tile (rows = cols)
 #define COV_KB 16                // K rows per LDS stage
@@ -224,35 +223,17 @@ __global__ void __launch_bounds__(256) pred_cov_a2_kernel(const T* __restrict__ 
   }
 }
 
-static inline long cov_round(long v) { return (v + 63) & ~63L; }
-
 extern "C" long hb_sgp_predict_cov_ws_elems(long E, long n, long M, long P, int s_kind, int dtype_bytes) {
   (void)P;
   (void)dtype_bytes;
   if (E <= 0 || n <= 0 || M <= 0) return 0;
-  return cov_round(E * M * n) + (s_kind == HB_SGP_S_TRIL ? cov_round(M * n) : 0) + cov_round(E * n);
-}
-
-static inline int cov_sgp_A(int kind, const float* x, long sx, const float* z, const float* ell, long dl, const float* W,
-                            const float* Wf, float* A, long E, long n, long M, long d, hipStream_t st) {
-  return hb_sgp_A_f32(kind, x, sx, z, ell, dl, W, Wf, HB_PREC_NATIVE, A, E, n, M, d, st);
-}
-static inline int cov_sgp_A(int kind, const double* x, long sx, const double* z, const double* ell, long dl, const double* W,
-                            const double* Wf, double* A, long E, long n, long M, long d, hipStream_t st) {
-  return hb_sgp_A_f64(kind, x, sx, z, ell, dl, W, Wf, HB_PREC_NATIVE, A, E, n, M, d, st);
-}
-static inline int cov_matmul(const float* S, const float* A, float* C, long M, long n, hipStream_t st) {
-  return hb_matmul_f32(S, A, C, 1, M, n, M, M, n, n, 0, 0, 0, 1, 0, 1.0, 0.0, nullptr, 0, HB_ACT_NONE, 0, nullptr, 0, st);
-}
-static inline int cov_matmul(const double* S, const double* A, double* C, long M, long n, hipStream_t st) {
-  return hb_matmul_f64(S, A, C, 1, M, n, M, M, n, n, 0, 0, 0, 1, 0, 1.0, 0.0, nullptr, 0, HB_ACT_NONE, 0, nullptr, 0, st);
+  return hb_round64(E * M * n) + (s_kind == HB_SGP_S_TRIL ? hb_round64(M * n) : 0) + hb_round64(E * n);
 }
 
 template <typename T>
 static int sgp_predict_cov(int kind, const T* x, long sx, const T* z, const T* ell, long dl, const T* W, const T* Wf,
                            const T* s, int s_kind, int mode, double jitter, T* cov, long E, long n, long M, long d, long P,
                            T* ws, hipStream_t st) {
-  HB_REQUIRE(kind == HB_KERN_RBF, "hb_sgp_predict_cov: only the UnitRBF kernel has a closed-form covariance (kind=%d)", kind);
   HB_REQUIRE(mode == HB_SGP_NEGLECTED || mode == HB_SGP_DIAGONAL || mode == HB_SGP_FULLRANK,
              "hb_sgp_predict_cov: unknown residual mode %d", mode);
   HB_REQUIRE(s_kind == HB_SGP_S_DIAG || s_kind == HB_SGP_S_TRIL, "hb_sgp_predict_cov: unknown s_kind %d", s_kind);
@@ -260,13 +241,11 @@ static int sgp_predict_cov(int kind, const T* x, long sx, const T* z, const T* e
              "hb_sgp_predict_cov: bad extents (E=%ld n=%ld M=%ld d=%ld P=%ld)", E, n, M, d, P);
   HB_REQUIRE(s_kind == HB_SGP_S_DIAG || E * P == 1, "hb_sgp_predict_cov: a full-rank S (s_kind TRIL) needs E P == 1 (E=%ld P=%ld)",
              E, P);
-  HB_REQUIRE(dl == 1 || dl == d, "hb_sgp_predict_cov: lengthscales must have 1 or d entries");
   HB_REQUIRE(sx == 0 || sx == n * d, "hb_sgp_predict_cov: x is shared (sx = 0) or [E, n, d] (sx = n d), got sx=%ld", sx);
   HB_REQUIRE(x && z && ell && W && s && cov, "hb_sgp_predict_cov: NULL pointer");
   HB_REQUIRE(E * P <= 65535, "hb_sgp_predict_cov: too many experts x latent functions (E P = %ld)", E * P);
-  HB_REQUIRE(M * M < 2147483647L && n * d < 2147483647L, "hb_sgp_predict_cov: matrix too large");
-  HB_REQUIRE(!Wf || ((uintptr_t)Wf % 16 == 0 && M % 32 == 0),
-             "hb_sgp_predict_cov: Wfrag needs 16-byte alignment and M %% 32 == 0");
+  HB_REQUIRE(n * d < 2147483647L, "hb_sgp_predict_cov: matrix too large");
+  HB_REQUIRE_RBF_MODEL("hb_sgp_predict_cov", "has a closed-form covariance", kind, dl, d, Wf, M);
   const long need = hb_sgp_predict_cov_ws_elems(E, n, M, P, s_kind, (int)sizeof(T));
   HB_REQUIRE(need == 0 || (ws && (uintptr_t)ws % 16 == 0),
              "hb_sgp_predict_cov: needs a 16-byte aligned workspace of %ld elements", need);
@@ -276,13 +255,13 @@ static int sgp_predict_cov(int kind, const T* x, long sx, const T* z, const T* e
 
   // pass 1: A [E, M, n]; C = S^T A [M, n] (full-rank S); a2 [E, n] (DIAGONAL)
   T* A = ws;
-  T* C = s_kind == HB_SGP_S_TRIL ? ws + cov_round(E * M * n) : nullptr;   // (E = 1)
-  const long gap = cov_round(E * M * n) - E * M * n;
-  T* a2 = ws + cov_round(E * M * n) + (C ? cov_round(M * n) : 0);
-  int rc = cov_sgp_A(kind, x, sx, z, ell, dl, W, Wf, A, E, n, M, d, st);
+  T* C = s_kind == HB_SGP_S_TRIL ? ws + hb_round64(E * M * n) : nullptr;   // (E = 1)
+  const long gap = hb_round64(E * M * n) - E * M * n;
+  T* a2 = ws + hb_round64(E * M * n) + (C ? hb_round64(M * n) : 0);
+  int rc = hb_sgp_A(kind, x, sx, z, ell, dl, W, Wf, A, E, n, M, d, st);
   if (rc) return rc;
   if (C) {
-    rc = cov_matmul(s, A, C, M, n, st);
+    rc = hb_matmul(s, A, C, 1, M, n, M, M, n, n, 0, 0, 0, 1, st);   // C = S^T A
     if (rc) return rc;
   }
   if (mode == HB_SGP_DIAGONAL) {

@@ -370,14 +370,7 @@ __global__ void __launch_bounds__(ACQ_COL_THREADS) acq_col_kernel(AcqColArgs<T> 
 }
 
 // ------------------------------------------------------------------------------------------------ host
-static inline long acq_chunk_cols(long n, long M) {
-  long c = ACQ_CHUNK_ELEMS / (3 * M);
-  c = c < HB_PRED_CHUNK ? c : HB_PRED_CHUNK;
-  c = c & ~31L;
-  if (c < 32) c = 32;
-  const long n32 = (n + 31) & ~31L;
-  return c < n32 ? c : (n32 > 0 ? n32 : 32);
-}
+static inline long acq_chunk_cols(long n, long M) { return hb_chunk_cols(ACQ_CHUNK_ELEMS, 3 * M, HB_PRED_CHUNK, n); }   // M >= 1
 static inline long acq_ws_base(long M) { return ACQ_WS_HEAD + ((M + 3) & ~3L); }   // carry, alpha
 
 static long acq_ws_elems(long n, long M, long d, int s_kind, int has_wfrag, int dtype_bytes) {
@@ -427,15 +420,13 @@ template <typename T>
 static int sgp_acq_run(const char* who, int kind, const T* x, const T* z, const T* ell, long dl, const T* W, const T* Wf,
                        const T* m, const T* s, int s_kind, int mode, double jitter, const AcqTail& t, const AcqOut<T>& out,
                        long n, long M, long d, T* ws, hipStream_t st) {
-  HB_REQUIRE(kind == HB_KERN_RBF, "%s: only the UnitRBF kernel has a closed-form predictive (kind=%d)", who, kind);
   HB_REQUIRE(mode == HB_SGP_NEGLECTED || mode == HB_SGP_DIAGONAL || mode == HB_SGP_FULLRANK, "%s: unknown residual mode %d", who,
              mode);
   HB_REQUIRE(s_kind == HB_SGP_S_DIAG || s_kind == HB_SGP_S_TRIL, "%s: unknown s_kind %d", who, s_kind);
   HB_REQUIRE(n >= 0 && M >= 1 && d >= 1, "%s: bad extents (n=%ld M=%ld d=%ld)", who, n, M, d);
-  HB_REQUIRE(dl == 1 || dl == d, "%s: lengthscales must have 1 or d entries", who);
   HB_REQUIRE(x && z && ell && W && m && s, "%s: NULL pointer", who);
-  HB_REQUIRE(M * M < 2147483647L && n < 2147483647L && d < 2147483647L && n * d < 2147483647L, "%s: matrix too large", who);
-  HB_REQUIRE(!Wf || ((uintptr_t)Wf % 16 == 0 && M % 32 == 0), "%s: Wfrag needs 16-byte alignment and M %% 32 == 0", who);
+  HB_REQUIRE(n < 2147483647L && d < 2147483647L && n * d < 2147483647L, "%s: matrix too large", who);
+  HB_REQUIRE_RBF_MODEL(who, "has a closed-form predictive", kind, dl, d, Wf, M);
   const bool amax = out.best_val || out.best_idx;
   if (t.acq == ACQ_NONE) {
     HB_REQUIRE(out.dmean && out.dvar, "%s: dmean and dvar must be given", who);
@@ -506,10 +497,10 @@ static int sgp_acq_run(const char* who, int kind, const T* x, const T* z, const 
   T* part = amax ? sa2c + nc_max : nullptr;
   for (long j0 = 0; j0 < n; j0 += nc_max) {
     const long nc = n - j0 < nc_max ? n - j0 : nc_max;
-    int rc = pred_sgp_A(kind, x + j0 * d, 0, z, ell, dl, W, Wf, Abuf, 1, nc, M, d, st);
+    int rc = hb_sgp_A(kind, x + j0 * d, 0, z, ell, dl, W, Wf, Abuf, 1, nc, M, d, st);
     if (rc) return rc;
     if (tril) {   // C = S^T A
-      rc = pred_matmul(s, Abuf, Cbuf, 1, M, nc, M, M, nc, nc, 0, 0, 0, 1, st);
+      rc = hb_matmul(s, Abuf, Cbuf, 1, M, nc, M, M, nc, nc, 0, 0, 0, 1, st);
       if (rc) return rc;
     }
     hipLaunchKernelGGL((pred_colstat_kernel<T>), dim3(hb_stream_grid(nc, 256)), dim3(256), 0, st, (const T*)Abuf,
@@ -517,13 +508,13 @@ static int sgp_acq_run(const char* who, int kind, const T* x, const T* z, const 
     HB_LAUNCH_CHECK();
     if (want_grad) {
       if (tril) {   // S C
-        rc = pred_matmul(s, Cbuf, Vbuf, 1, M, nc, M, M, nc, nc, 0, 0, 0, 0, st);
+        rc = hb_matmul(s, Cbuf, Vbuf, 1, M, nc, M, M, nc, nc, 0, 0, 0, 0, st);
         if (rc) return rc;
       }
       hipLaunchKernelGGL((acq_v_kernel<T>), dim3(hb_stream_grid(M * nc, 256)), dim3(256), 0, st, (const T*)Abuf, Vbuf,
                          tril ? (const T*)nullptr : s, (const T*)sa2c, mode, M, nc);
       HB_LAUNCH_CHECK();
-      rc = pred_matmul(W, Vbuf, Cbuf, 1, M, nc, M, M, nc, nc, 0, 0, 0, 1, st);   // G = W^T V
+      rc = hb_matmul(W, Vbuf, Cbuf, 1, M, nc, M, M, nc, nc, 0, 0, 0, 1, st);   // G = W^T V
       if (rc) return rc;
     }
     AcqColArgs<T> a;

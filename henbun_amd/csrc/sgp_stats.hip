@@ -29,8 +29,7 @@
 //   element (parity, not speed).
 // After the last chunk: the strict upper triangle is copied from the lower one (Phi bitwise symmetric) and a2sum is the
 // fold of diag(Phi) -- not computed a second way.  yy is summed chunk by chunk by one block of the fold launch.
-#include "common.cuh"
-#include "../../include/henbun_hip.h"
+#include "host_calls.cuh"   // hb_round64, hb_chunk_cols, hb_sgp_A, HB_REQUIRE_RBF_MODEL
 
 #define ST_BT 128                // output tile (rows = cols)
 #define ST_KB 16                 // K columns per LDS stage
@@ -315,15 +314,7 @@ __global__ void __launch_bounds__(256) sgp_stats_finish_kernel(double* __restric
   }
 }
 
-static inline long st_round(long v) { return (v + 63) & ~63L; }
-static inline long st_chunk_cols(long N, long M) {
-  long c = ST_CHUNK_ELEMS / (M > 0 ? M : 1);
-  c = c < ST_CHUNK ? c : ST_CHUNK;
-  c &= ~31L;
-  if (c < 32) c = 32;
-  const long n32 = (N + 31) & ~31L;
-  return c < n32 ? c : n32;
-}
+static inline long st_chunk_cols(long N, long M) { return hb_chunk_cols(ST_CHUNK_ELEMS, M, ST_CHUNK, N); }   // N >= 1
 static inline bool st_is_mfma(long M, long P, int dbytes) { return dbytes == 4 && M % 32 == 0 && P <= ST_PMAX; }
 // K-splits of a chunk of nc columns: tiles x splits about ST_TARGET_WG, a split at least one stage long
 // (never more than st_max_splits, which sizes the workspace)
@@ -346,22 +337,13 @@ extern "C" long hb_sgp_stats_ws_elems(long N, long M, long d, long P, int dtype_
   (void)d;
   if (N <= 0 || M <= 0 || P <= 0) return 0;
   const long nc = st_chunk_cols(N, M);
-  long need = st_round(M * nc);
+  long need = hb_round64(M * nc);
   if (st_is_mfma(M, P, dtype_bytes)) {
     long T, nt, ks, splits;
     st_split(M, nc, &T, &nt, &ks, &splits);
-    need += st_round(st_max_splits(T) * T * ST_TILE) + st_round(st_max_splits(T) * nt * P * ST_BT);
+    need += hb_round64(st_max_splits(T) * T * ST_TILE) + hb_round64(st_max_splits(T) * nt * P * ST_BT);
   }
   return need;
-}
-
-static inline int st_sgp_A(int kind, const float* x, const float* z, const float* ell, long dl, const float* W, const float* Wf,
-                           float* A, long n, long M, long d, hipStream_t st) {
-  return hb_sgp_A_f32(kind, x, 0, z, ell, dl, W, Wf, HB_PREC_NATIVE, A, 1, n, M, d, st);
-}
-static inline int st_sgp_A(int kind, const double* x, const double* z, const double* ell, long dl, const double* W,
-                           const double* Wf, double* A, long n, long M, long d, hipStream_t st) {
-  return hb_sgp_A_f64(kind, x, 0, z, ell, dl, W, Wf, HB_PREC_NATIVE, A, 1, n, M, d, st);
 }
 
 // hb_sgp_stats_* (WGT false: w NULL) and hb_sgp_wstats_* (WGT true: Y is r [N], P = 1, yy NULL) share every launch.
@@ -374,13 +356,11 @@ template <typename T, bool WGT>
 static int sgp_stats(const char* who, int kind, const T* X, const T* Y, const T* w, const T* z, const T* ell, long dl, const T* W,
                      const T* Wf, double* Phi, double* b, double* yy, double* a2sum, long N, long M, long d, long P, T* ws,
                      hipStream_t st, long C = 1, long ldw = 0) {
-  HB_REQUIRE(kind == HB_KERN_RBF, "%s: only the UnitRBF kernel is supported (kind=%d)", who, kind);
   HB_REQUIRE(N >= 1 && M >= 1 && d >= 1 && P >= 1, "%s: bad extents (N=%ld M=%ld d=%ld P=%ld)", who, N, M, d, P);
-  HB_REQUIRE(dl == 1 || dl == d, "%s: lengthscales must have 1 or d entries", who);
   HB_REQUIRE(X && Y && z && ell && W && (!WGT || w), "%s: NULL input pointer", who);
   HB_REQUIRE(Phi && b && (WGT || yy) && a2sum, "%s: NULL output pointer", who);
-  HB_REQUIRE(M * M < 2147483647L && M <= 16384, "%s: M=%ld too large", who, M);
-  HB_REQUIRE(!Wf || ((uintptr_t)Wf % 16 == 0 && M % 32 == 0), "%s: Wfrag needs 16-byte alignment and M %% 32 == 0", who);
+  HB_REQUIRE(M <= 16384, "%s: M=%ld too large", who, M);
+  HB_REQUIRE_RBF_MODEL(who, "is supported", kind, dl, d, Wf, M);
   HB_REQUIRE(!WGT || (uintptr_t)w % 16 == 0, "%s: the weights need 16-byte alignment", who);
   HB_REQUIRE(C >= 1 && (C == 1 || (WGT && P == 1 && ldw >= N)), "%s: bad weight sets (C=%ld ldw=%ld N=%ld)", who, C, ldw, N);
   for (long c = 1; c < C; ++c)
@@ -398,7 +378,7 @@ static int sgp_stats(const char* who, int kind, const T* X, const T* Y, const T*
     // diagnostic switches (tools/bench_sgp_stats.py times the two passes apart): without the A pass the second pass runs
     // on whatever the workspace holds, without the second pass Phi and b are not written
     if (!no_A) {
-      const int rc = st_sgp_A(kind, X + c0 * d, z, ell, dl, W, Wf, Abuf, nc, M, d, st);
+      const int rc = hb_sgp_A(kind, X + c0 * d, 0, z, ell, dl, W, Wf, Abuf, 1, nc, M, d, st);
       if (rc) return rc;
     }
     if (no_syrk) continue;
@@ -414,8 +394,8 @@ static int sgp_stats(const char* who, int kind, const T* X, const T* Y, const T*
           StatsArgs a;
           a.A = Abuf; a.ld = nc; a.Y = Yc; a.P = P; a.M = M; a.nc = nc; a.ks = ks; a.T = Tn; a.nt = nt;
           a.w = wc;
-          a.part = ws + st_round(M * nc_max);
-          a.bpart = a.part + st_round(st_max_splits(Tn) * Tn * ST_TILE);
+          a.part = ws + hb_round64(M * nc_max);
+          a.bpart = a.part + hb_round64(st_max_splits(Tn) * Tn * ST_TILE);
           const dim3 grid((unsigned)(Tn * splits), 1, 1);
           if (nc % 4 == 0)
             hipLaunchKernelGGL((sgp_stats_syrk_kernel<true, WGT>), grid, dim3(ST_THREADS), 0, st, a);

@@ -131,6 +131,77 @@ def workspace(dtype, device, elems=WS_ELEMS) -> torch.Tensor:
     return w
 
 
+# ---- the wrapper contract: operands, outputs, workspaces -------------------------------------------------------------------
+# The C entries take every buffer as a bare pointer without a length, so these checks are the only ones a caller's
+# buffer gets before a kernel writes through it.  None of them allocates, synchronises or reads device memory when the
+# caller passed the buffer: plans emit the wrappers during capture with everything preallocated.
+def _require(cond, who, what):
+    """An extent or dtype the library takes on trust (a ValueError, not an assert: python -O must not drop it)."""
+    if not cond:
+        raise ValueError("%s: %s" % (who, what))
+
+
+def _operands(who, ref, *tensors, what="all operands must share one dtype"):
+    """Each tensor given (None entries are skipped) lives on the device, is contiguous and has the dtype of `ref` (a
+    tensor, checked like the others, or a torch.dtype)."""
+    dtype = ref if isinstance(ref, torch.dtype) else _chk(ref).dtype
+    for t in tensors:
+        if t is not None and _chk(t).dtype != dtype:
+            raise TypeError("%s: %s" % (who, what))
+
+
+def _out(who, t, shape, dtype, device, name="out", exact=True):
+    """A result buffer: the caller's `t`, which must be contiguous and exactly `shape` of `dtype`, or a fresh one.
+    exact=False: any contiguous shape of that many elements -- the wrappers a plan emits with the result in the shape of
+    its own graph node (leading dims split or merged, a [1] result as a scalar): gauss_ll, reduce_mid, gather_rows,
+    matutil, fullrank_sample_kl_fwd / _bwd, vec_to_tri, tri_to_vec, gram_fwd, cholesky, trinv, gram_cholesky_inverse;
+    gram_bilinear_grad and lik_sites take any shape of the right count as well.
+    Left to their wrappers, because the planner hands them views, strided blocks, column blocks or buffers larger than
+    the result on purpose: ewise, copy_nd, matmul, matmul_ld, matmul_colsum, diag_sample_kl_fwd / _bwd (rows=), sgp_fwd /
+    sgp_bwd and their relatives (sgp_A, sgp_fwd_gauss_kbar, sgp_bwd_phi, sgp_bwd_phi_rest), matmul_gram_vjp[_tiles],
+    gram_ell_fold, gram_tiles_fold, gauss_ll_fold, matmul_gauss's head (raw plan buffers, sized by the plan from the
+    library's own queries), lik_softmax_grad (padded rows, checked there), Rng.normal / randint (the result IS the shape
+    argument), and the status words `info` / `err` of every entry (int32 / int64 views of the plan's status block)."""
+    if t is None:
+        return _empty(tuple(shape), dtype=dtype, device=device)
+    shape = tuple(int(v) for v in shape)
+    if _chk(t, name).dtype != dtype or (tuple(t.shape) != shape if exact else t.numel() != int(np.prod(shape))):
+        raise ValueError("%s: %s must be %s%s of the operands' dtype" % (who, name, list(shape), "" if exact else
+                                                                         " (or any shape of as many elements)"))
+    return t
+
+
+def _outs(who, ts, shapes, dtype, device, names, exact=True):
+    """_out for a tuple of results (`ts` None: all fresh)."""
+    ts = (None,) * len(shapes) if ts is None else tuple(ts)
+    if len(ts) != len(shapes):
+        raise ValueError("%s: out must be (%s)" % (who, ", ".join(names)))
+    return tuple(_out(who, t, s, dtype, device, n, exact) for t, s, n in zip(ts, shapes, names))
+
+
+def _ws(who, ws, dtype, device, need, query, name="the workspace"):
+    """A workspace of `need` elements of `dtype`: the caller's, checked, or the shared scratch of the stream.  `query`
+    names the *_ws_elems function that answers `need`; `name`: the argument, for a scratch buffer that is not `ws`."""
+    if ws is None:
+        return workspace(dtype, device, max(need, 1))
+    if _chk(ws, name).dtype != dtype or ws.numel() < need:
+        raise ValueError("%s: %s must hold %d elements of %s (%s)" % (who, name, need, dtype, query))
+    return ws
+
+
+def _code(who, table, value, name="acq"):
+    """The code of a name-or-code argument in one of the enum tables (ACQ, PWACQ)."""
+    code = table.get(value) if isinstance(value, str) else value
+    if code not in table.values():
+        raise ValueError("%s: %s must be one of %s, got %r" % (who, name, sorted(table), value))
+    return code
+
+
+def _query(name, *ints):
+    """An integer answer of the library's host-side size and form rules (nothing runs on the device)."""
+    return int(_lib.lib().raw(name)(*[int(v) for v in ints]))
+
+
 def _bcast_strides(shape, out_shape):
     """element strides of a contiguous tensor of `shape` viewed as `out_shape` (0 on broadcast dims)."""
     nd = len(out_shape)
@@ -168,7 +239,7 @@ def ewise(op, inputs, nout=1, params=None, out=None):
     else:
         outs = list(out) if isinstance(out, (list, tuple)) else [out]
         for o in outs:
-            assert tuple(o.shape) == out_shape and o.is_contiguous()
+            _require(tuple(o.shape) == out_shape and o.is_contiguous(), "ewise", "out must be contiguous %s" % (out_shape,))
     in_arr = (c_void_p * nin)(*[t.data_ptr() for t in inputs])
     out_arr = (c_void_p * nout)(*[o.data_ptr() for o in outs])
     pr = (c_double * 4)(*(list(params or []) + [0.0] * 4)[:4])
@@ -187,7 +258,7 @@ def ewise_jit_enabled():
 
     if getattr(settings.runtime, "ewise", "jit") != "jit":
         return False
-    return bool(_lib.lib().raw("hb_ewise_jit_available")())
+    return bool(_query("hb_ewise_jit_available"))
 
 
 class EwiseProgram:
@@ -305,19 +376,15 @@ def gauss_ll(x, f, scale, var, out=None, post=None, fbar=None):
     """(ll[1], dmu[like x], dscale[1], dvar[1]) of sum_j log N(x_j | f_j*scale, var)  (hb_gauss_ll; scale may be None).
     `post`, `fbar`: also fbar = scale * (post * dmu), the gradient of post * ll w.r.t. f (hb_gauss_ll_post)."""
     _chk(x), _chk(f), _chk(var)
-    assert x.numel() == f.numel() and var.numel() == 1 and (scale is None or scale.numel() == 1)
+    _require(x.numel() == f.numel() and var.numel() == 1 and (scale is None or scale.numel() == 1), "gauss_ll",
+             "x and f of one size, one variance and at most one scale expected")
     n = x.numel()
-    if out is None:
-        ll = _empty(1, dtype=x.dtype, device=x.device)
-        dmu = _empty_like(x)
-        ds = _empty(1, dtype=x.dtype, device=x.device)
-        dv = _empty(1, dtype=x.dtype, device=x.device)
-    else:
-        ll, dmu, ds, dv = out
+    ll, dmu, ds, dv = _outs("gauss_ll", out, ((1,), tuple(x.shape), (1,), (1,)), x.dtype, x.device, ("ll", "dmu", "dscale", "dvar"),
+                            exact=False)
     ws = workspace(x.dtype, x.device, 3 * max((n + 1023) // 1024, 1))
     if fbar is not None:
         _chk(fbar)
-        assert fbar.numel() == n
+        _require(fbar.numel() == n, "gauss_ll", "fbar must hold the elements of x")
         _lib.lib().call("hb_gauss_ll_post" + _suf(x), _p(x), _p(f), _p(scale), _p(var), n, _p(ll), _p(dmu), _p(ds), _p(dv),
                         float(post), _p(fbar), _p(ws), ws.numel(), stream())
         return ll, dmu, ds, dv
@@ -329,9 +396,8 @@ def gauss_ll(x, f, scale, var, out=None, post=None, fbar=None):
 def reduce_mid(x, K1, R, K2, op=RED_SUM, out=None):
     """out[K1,K2] = reduce_R x[K1,R,K2] (x contiguous, any shape with K1*R*K2 elements)."""
     _chk(x)
-    assert x.numel() == K1 * R * K2
-    if out is None:
-        out = _empty(K1 * K2, dtype=x.dtype, device=x.device)
+    _require(x.numel() == K1 * R * K2, "reduce_mid", "x must hold K1 R K2 elements")
+    out = _out("reduce_mid", out, (K1 * K2,), x.dtype, x.device, exact=False)
     ws = workspace(x.dtype, x.device)
     _lib.lib().call("hb_reduce" + _suf(x), op, _p(x), _p(out), K1, R, K2, _p(ws), ws.numel(), stream())
     return out
@@ -359,9 +425,8 @@ def gather_rows(src, idx, perm=None, out=None, err=None):
     nsrc = src.shape[0]
     row = src.numel() // max(nsrc, 1)
     n = idx.numel()
-    if out is None:
-        out = _empty((n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
-    assert idx.dtype == torch.int64 and (perm is None or perm.dtype == torch.int64)
+    out = _out("gather_rows", out, (n,) + tuple(src.shape[1:]), src.dtype, src.device, exact=False)
+    _require(idx.dtype == torch.int64 and (perm is None or perm.dtype == torch.int64), "gather_rows", "int64 idx and perm expected")
     _lib.lib().call("hb_gather_rows" + _suf(src), _p(src), nsrc, row, _p(idx), _p(perm), n, _p(out), _p(err), stream())
     return out
 
@@ -370,11 +435,11 @@ class MultiGather:
     """out_a[i,:] = src_a[perm[idx[i]],:] for several arrays sharing idx, one launch (argument arrays built once)."""
 
     def __init__(self, srcs, outs, idx, perm, err):
-        assert 1 <= len(srcs) <= 8 and len(srcs) == len(outs)
+        _require(1 <= len(srcs) <= 8 and len(srcs) == len(outs), "MultiGather", "1 to 8 arrays and as many outputs expected")
         nsrc = srcs[0].shape[0]
         for s in srcs:
             _chk(s)
-            assert s.shape[0] == nsrc and s.dtype == srcs[0].dtype
+            _require(s.shape[0] == nsrc and s.dtype == srcs[0].dtype, "MultiGather", "arrays of one row count and dtype expected")
         self.suf = _suf(srcs[0])
         self.narr, self.nsrc, self.n = len(srcs), nsrc, idx.numel()
         self.srcs = (c_void_p * self.narr)(*[s.data_ptr() for s in srcs])
@@ -400,8 +465,7 @@ def matutil(x, mode, lower=-1, upper=-1, alpha=0.0, out=None):
     _chk(x)
     R, C = x.shape[-2], x.shape[-1]
     B = x.numel() // max(R * C, 1)
-    if out is None:
-        out = _empty_like(x)
+    out = _out("matutil", out, tuple(x.shape), x.dtype, x.device, exact=False)
     _lib.lib().call("hb_matutil" + _suf(x), _p(x), _p(out), B, R, C, mode, lower, upper, float(alpha), stream())
     return out
 
@@ -447,7 +511,7 @@ def side_flush():
 
 
 def side_pending():
-    return int(_lib.lib().raw("hb_side_pending")())
+    return _query("hb_side_pending")
 
 
 def chain_begin():
@@ -461,7 +525,7 @@ def chain_end():
 
 
 def chain_discard():
-    return int(_lib.lib().raw("hb_chain_discard")())
+    return _query("hb_chain_discard")
 
 
 def chain_source():
@@ -472,7 +536,7 @@ def chain_source():
 
 def side_discard():
     """Drop this thread's recorded side jobs without running them (hb_side_discard); returns how many there were."""
-    return int(_lib.lib().raw("hb_side_discard")())
+    return _query("hb_side_discard")
 
 
 def diag_sample_kl_fwd(mu, s, u_in=None, rng=None, out=None, rows=None, defer=False):
@@ -525,11 +589,10 @@ def fullrank_sample_kl_fwd(mu, S, u_in=None, rng=None, out=None, packed=False):
     _chk(mu), _chk(S)
     size = mu.shape[-1]
     rows = mu.numel() // max(size, 1)
-    assert S.numel() == rows * (size * (size + 1) // 2 if packed else size * size)
-    if out is None:
-        x, kl, u = _empty_like(mu), _empty(1, dtype=mu.dtype, device=mu.device), _empty_like(mu)
-    else:
-        x, kl, u = out
+    _require(S.numel() == rows * (size * (size + 1) // 2 if packed else size * size), "fullrank_sample_kl_fwd",
+             "S must hold one (packed) lower triangle per row of mu")
+    x, kl, u = _outs("fullrank_sample_kl_fwd", out, (tuple(mu.shape), (1,), tuple(mu.shape)), mu.dtype, mu.device,
+                     ("x", "kl", "u"), exact=False)
     ws = workspace(mu.dtype, mu.device)
     rp, rl = _rng_args(rng)
     # (one launch for a block of up to 1024 dimensions; the entry falls back to the three-launch form by itself)
@@ -552,12 +615,11 @@ def sync_word(device):
 
 
 def fullrank_sample_kl_bwd(S, u, x, xbar, klbar, out=None, packed=False):
+    _operands("fullrank_sample_kl_bwd", S, u, x, xbar, klbar)
     size = u.shape[-1]
     rows = u.numel() // max(size, 1)
-    if out is None:
-        mubar, Sbar = _empty_like(u), _empty_like(S)
-    else:
-        mubar, Sbar = out
+    mubar, Sbar = _outs("fullrank_sample_kl_bwd", out, (tuple(u.shape), tuple(S.shape)), S.dtype, S.device, ("mubar", "Sbar"),
+                        exact=False)
     _lib.lib().call("hb_fullrank_sample_kl_bwd" + _suf(S), _p(S), _p(u), _p(x), _p(xbar), _p(klbar), _p(mubar),
                     _p(Sbar), rows, size, int(bool(packed)), stream())
     return mubar, Sbar
@@ -576,8 +638,7 @@ def vec_to_tri(v, out=None):
     _chk(v)
     N = tri_size(v.shape[-1])
     B = v.numel() // max(v.shape[-1], 1)
-    if out is None:
-        out = _empty(tuple(v.shape[:-1]) + (N, N), dtype=v.dtype, device=v.device)
+    out = _out("vec_to_tri", out, tuple(v.shape[:-1]) + (N, N), v.dtype, v.device, exact=False)
     _lib.lib().call("hb_vec_to_tri" + _suf(v), _p(v), _p(out), B, N, stream())
     return out
 
@@ -587,8 +648,7 @@ def tri_to_vec(tri, out=None):
     _chk(tri)
     N = tri.shape[-1]
     B = tri.numel() // max(N * N, 1)
-    if out is None:
-        out = _empty(tuple(tri.shape[:-2]) + (N * (N + 1) // 2,), dtype=tri.dtype, device=tri.device)
+    out = _out("tri_to_vec", out, tuple(tri.shape[:-2]) + (N * (N + 1) // 2,), tri.dtype, tri.device, exact=False)
     _lib.lib().call("hb_tri_to_vec" + _suf(tri), _p(tri), _p(out), B, N, stream())
     return out
 
@@ -615,18 +675,17 @@ def gram_fwd(X, X2, ell, kind=KERN_RBF, out=None, diag_add=0.0):
     _chk(X), _chk(X2), _chk(ell)
     BX, n, d = _batch_view(X)
     BX2, n2, d2 = _batch_view(X2)
-    assert d == d2
+    _require(d == d2, "gram_fwd", "X and X2 must share their last extent")
     B = max(BX, BX2)
     if ell.dim() >= 2 and ell.shape[0] > 1:
         B = max(B, ell.shape[0])
-    assert BX in (1, B) and BX2 in (1, B)
+    _require(BX in (1, B) and BX2 in (1, B), "gram_fwd", "batch extents must match or be absent")
     sX = n * d if (BX == B and B > 1) else 0
     sX2 = n2 * d if (BX2 == B and B > 1) else 0
     sEll, dl = _ell_layout(ell, B, d)
     batched = X.dim() > 2 or X2.dim() > 2 or sEll != 0
     lead = tuple(X.shape[:-2]) if X.dim() > 2 else (tuple(X2.shape[:-2]) if X2.dim() > 2 else ((B,) if sEll else ()))
-    if out is None:
-        out = _empty((lead if batched else ()) + (n, n2), dtype=X.dtype, device=X.device)
+    out = _out("gram_fwd", out, (lead if batched else ()) + (n, n2), X.dtype, X.device, exact=False)
     _lib.lib().call("hb_gram_fwd" + _suf(X), kind, _p(X), sX, _p(X2), sX2, _p(ell), sEll, dl, _p(out), B, n, n2, d,
                     float(diag_add), stream())
     return out
@@ -733,12 +792,12 @@ def matmul_colsum(A, B, out=None, colsum=None):
     _chk(A), _chk(B)
     K, M = A.shape[-2], A.shape[-1]
     N = B.shape[-1]
-    assert A.dim() == 2 and B.dim() == 2 and B.shape[0] == K
+    _require(A.dim() == 2 and B.dim() == 2 and B.shape[0] == K, "matmul_colsum", "A [K, M] and B [K, N] expected")
     if out is None:
         out = _empty((M, N), dtype=A.dtype, device=A.device)
     if colsum is None:
         colsum = _empty((N,), dtype=A.dtype, device=A.device)
-    assert colsum.numel() == N and colsum.is_contiguous()
+    _require(colsum.numel() == N and colsum.is_contiguous(), "matmul_colsum", "colsum must be contiguous [N]")
     ws = workspace(A.dtype, A.device, 1 << 22)
     _lib.lib().call("hb_matmul_colsum" + _suf(A), _p(A), _p(B), _p(out), _p(colsum), M, N, K, M, N, N, _p(ws), ws.numel(),
                     stream())
@@ -748,28 +807,25 @@ def matmul_colsum(A, B, out=None, colsum=None):
 
 
 def mlp2_sample_supported(n, din, hid, nout, rng_lanes=0, has_u=True):
-    return bool(_lib.lib().raw("hb_mlp2_sample_supported")(n, din, hid, nout, int(rng_lanes), int(bool(has_u))))
+    return bool(_query("hb_mlp2_sample_supported", n, din, hid, nout, rng_lanes, bool(has_u)))
 
 
 def mlp2_sample_ws_elems(n, din, hid):
-    return int(_lib.lib().raw("hb_mlp2_sample_ws_elems")(n, din, hid))
+    return _query("hb_mlp2_sample_ws_elems", n, din, hid)
 
 
-def mlp2_sample_ws(n, din, hid, device):
+def mlp2_sample_ws(n, din, hid, device):   # (for callers that keep a workspace of their own; the wrappers' default is the shared scratch)
     return _empty(mlp2_sample_ws_elems(n, din, hid), dtype=torch.float32, device=device)
 
 
 def mlp2_sample_fwd(y, w0, b0, w1, b1, act, u_in=None, rng=None, out=None, ws=None):
     """(x, kl, u, o) of the fused two-layer encoder + LOCAL diagonal sample + MC-KL (hb_mlp2_sample_fwd_f32)."""
-    _chk(y), _chk(w0), _chk(w1)
+    who = "mlp2_sample_fwd"
+    _operands(who, y, w0, b0, w1, b1, u_in)
     n, din = y.shape
     hid = w0.shape[1]
-    if out is None:
-        out = (_empty((n, 16), dtype=y.dtype, device=y.device), _empty(1, dtype=y.dtype, device=y.device),
-               _empty((n, 16), dtype=y.dtype, device=y.device), _empty((n, 32), dtype=y.dtype, device=y.device))
-    x, kl, u, o = out
-    if ws is None:
-        ws = mlp2_sample_ws(n, din, hid, y.device)
+    x, kl, u, o = _outs(who, out, ((n, 16), (1,), (n, 16), (n, 32)), y.dtype, y.device, ("x", "kl", "u", "o"))
+    ws = _ws(who, ws, torch.float32, y.device, mlp2_sample_ws_elems(n, din, hid), "mlp2_sample_ws_elems")
     _lib.lib().call("hb_mlp2_sample_fwd_f32", _p(y), _p(w0), _p(b0), _p(w1), _p(b1), ACT[act], _p(u_in),
                     _p(rng.state) if (rng is not None and u_in is None) else None, rng.nlanes if rng is not None else 0,
                     _p(x), _p(kl), _p(u), _p(o), n, din, hid, _p(ws), stream())
@@ -778,13 +834,13 @@ def mlp2_sample_fwd(y, w0, b0, w1, b1, act, u_in=None, rng=None, out=None, ws=No
 
 def mlp2_sample_bwd(y, w0, b0, w1, act, o, u, x, xbar, klbar, out=None, ws=None):
     """(dw0, db0, dw1, db1) of the fused encoder + sampler (hb_mlp2_sample_bwd_f32): h recomputed from y."""
+    who = "mlp2_sample_bwd"
+    _operands(who, y, w0, b0, w1, o, u, x, xbar, klbar)
     n, din = y.shape
     hid = w0.shape[1]
-    if out is None:
-        out = (_empty_like(w0), _empty(hid, dtype=y.dtype, device=y.device), _empty_like(w1), _empty(32, dtype=y.dtype, device=y.device))
-    dw0, db0, dw1, db1 = out
-    if ws is None:
-        ws = mlp2_sample_ws(n, din, hid, y.device)
+    dw0, db0, dw1, db1 = _outs(who, out, (tuple(w0.shape), (hid,), tuple(w1.shape), (32,)), y.dtype, y.device,
+                               ("dw0", "db0", "dw1", "db1"))
+    ws = _ws(who, ws, torch.float32, y.device, mlp2_sample_ws_elems(n, din, hid), "mlp2_sample_ws_elems")
     _lib.lib().call("hb_mlp2_sample_bwd_f32", _p(y), _p(w0), _p(b0), _p(w1), ACT[act], _p(o), _p(u), _p(x), _p(xbar), _p(klbar),
                     _p(dw0), _p(db0), _p(dw1), _p(db1), n, din, hid, _p(ws), stream())
     return dw0, db0, dw1, db1
@@ -794,10 +850,9 @@ def cholesky(A, out=None, info=None):
     """L = chol(A) (lower), batched over leading dims.  Returns (L, info[B] int32 device tensor)."""
     _chk(A)
     M = A.shape[-1]
-    assert A.shape[-2] == M
+    _require(A.dim() >= 2 and A.shape[-2] == M, "cholesky", "square matrices [..., M, M] expected")
     B = A.numel() // max(M * M, 1)
-    if out is None:
-        out = _empty_like(A)
+    out = _out("cholesky", out, tuple(A.shape), A.dtype, A.device, exact=False)
     if info is None:
         info = _empty(max(B, 1), dtype=torch.int32, device=A.device)
     if out.data_ptr() == A.data_ptr() and A.numel():
@@ -824,7 +879,7 @@ def debug_clear():
 
 
 def cholesky_ws_elems(B, M, dtype):
-    return int(_lib.lib().raw("hb_cholesky_inverse_ws_elems")(B, M, _elem_bytes(dtype)))
+    return _query("hb_cholesky_inverse_ws_elems", B, M, _elem_bytes(dtype))
 
 
 def cholesky_workspace(dtype, device, B, M):
@@ -841,21 +896,15 @@ def cholesky_workspace(dtype, device, B, M):
 def cholesky_inverse(A, out=None, inv=None, info=None, ws=None, frag=None, frag_bf16x3=False):
     """(L, W, info): L = chol(A) and W = L^-1 from one fused launch sequence (batched over leading dims).
     `frag` (2*B*M*M elements, M % 32 == 0): receives the fragment-major copies of W and W^T (see the header)."""
+    who = "cholesky_inverse"
     _chk(A)
     M = A.shape[-1]
-    assert A.shape[-2] == M
+    _require(A.dim() >= 2 and A.shape[-2] == M, who, "square matrices [..., M, M] expected")
     B = A.numel() // max(M * M, 1)
-    if out is None:
-        out = _empty_like(A)
-    if inv is None:
-        inv = _empty_like(A)
+    out, inv = _outs(who, (out, inv), (tuple(A.shape),) * 2, A.dtype, A.device, ("out", "inv"))
     if info is None:
         info = _empty(max(B, 1), dtype=torch.int32, device=A.device)
-    if ws is None:
-        ws = cholesky_workspace(A.dtype, A.device, B, M)
-    assert ws.numel() >= cholesky_ws_elems(B, M, A.dtype), "hb_cholesky_inverse: workspace too small (cholesky_ws_elems)"
-    if frag is not None:
-        assert frag.numel() >= cholesky_frag_elems(B, M, frag_bf16x3) and M % 32 == 0 and frag.dtype == A.dtype
+    ws, frag = _cholesky_scratch(who, ws, frag, frag_bf16x3, A.dtype, A.device, B, M)
     _lib.lib().call("hb_cholesky_inverse" + _suf(A), _p(A), _p(out), _p(inv), B, M, _p(info), _p(ws), _p(frag),
                     int(bool(frag_bf16x3 and frag is not None)), stream())
     return out, inv, info
@@ -863,39 +912,43 @@ def cholesky_inverse(A, out=None, inv=None, info=None, ws=None, frag=None, frag_
 
 def cholesky_frag_elems(B, M, bf16x3=False):
     """Elements of cholesky_inverse's `frag` buffer: the images of W and W^T, and the bf16x3 planes behind them if asked for."""
-    return int(_lib.lib().raw("hb_cholesky_frag_elems")(int(B), int(M), int(bool(bf16x3))))
+    return _query("hb_cholesky_frag_elems", B, M, bool(bf16x3))
+
+
+def _cholesky_scratch(who, ws, frag, bf16x3, dtype, device, B, M):
+    """(ws, frag) of cholesky_inverse / gram_cholesky_inverse, checked.  The default workspace is cholesky_workspace's,
+    not the shared scratch: it must be zero-filled."""
+    ws = _ws(who, cholesky_workspace(dtype, device, B, M) if ws is None else ws, dtype, device,
+             cholesky_ws_elems(B, M, dtype), "cholesky_ws_elems")
+    if frag is not None:
+        _require(M % 32 == 0, who, "frag needs M %% 32 == 0, got M=%d" % M)
+        _ws(who, frag, dtype, device, cholesky_frag_elems(B, M, bf16x3), "cholesky_frag_elems", "frag")
+    return ws, frag
 
 
 def cholesky_persistent_shape(B, M, dtype):
     """hb_cholesky_inverse takes its one-launch persistent form for this (B, M, dtype)."""
-    return bool(_lib.lib().raw("hb_cholesky_persistent_shape")(B, M, _elem_bytes(dtype)))
+    return bool(_query("hb_cholesky_persistent_shape", B, M, _elem_bytes(dtype)))
 
 
 def gram_cholesky_inverse(X, ell, diag_add, kind=KERN_RBF, out=None, inv=None, info=None, ws=None, frag=None, frag_bf16x3=False):
     """(L, W, info) of K(X, X) + diag_add I without K being written: hb_gram_cholesky_inverse_f32 (the persistent
     Cholesky synthesises its tiles from the points).  X: [M, d] or [B, M, d]; ell as in gram_fwd."""
     _chk(X), _chk(ell)
-    assert X.dtype == torch.float32
+    _require(X.dtype == torch.float32, "gram_cholesky_inverse", "float32 operands expected")
     BX, M, d = _batch_view(X)
     B = BX
     if ell.dim() >= 2 and ell.shape[0] > 1:
         B = max(B, ell.shape[0])
-    assert BX in (1, B)
+    _require(BX in (1, B), "gram_cholesky_inverse", "batch extents must match or be absent")
     sX = M * d if (BX == B and B > 1) else 0
     sEll, dl = _ell_layout(ell, B, d)
     batched = X.dim() > 2 or sEll != 0
     shape = ((B,) if batched else ()) + (M, M)
-    if out is None:
-        out = _empty(shape, dtype=X.dtype, device=X.device)
-    if inv is None:
-        inv = _empty(shape, dtype=X.dtype, device=X.device)
+    out, inv = _outs("gram_cholesky_inverse", (out, inv), (shape,) * 2, X.dtype, X.device, ("out", "inv"), exact=False)
     if info is None:
         info = _empty(max(B, 1), dtype=torch.int32, device=X.device)
-    if ws is None:
-        ws = cholesky_workspace(X.dtype, X.device, B, M)
-    assert ws.numel() >= cholesky_ws_elems(B, M, X.dtype)
-    if frag is not None:
-        assert frag.numel() >= cholesky_frag_elems(B, M, frag_bf16x3) and frag.dtype == X.dtype
+    ws, frag = _cholesky_scratch("gram_cholesky_inverse", ws, frag, frag_bf16x3, X.dtype, X.device, B, M)
     _lib.lib().call("hb_gram_cholesky_inverse_f32", kind, _p(X), sX, _p(ell), sEll, dl, d, float(diag_add), _p(out), _p(inv), B, M,
                     _p(info), _p(ws), _p(frag), int(bool(frag_bf16x3 and frag is not None)), stream())
     return out, inv, info
@@ -906,8 +959,7 @@ def trinv(L, out=None):
     _chk(L)
     M = L.shape[-1]
     B = L.numel() // max(M * M, 1)
-    if out is None:
-        out = _empty_like(L)
+    out = _out("trinv", out, tuple(L.shape), L.dtype, L.device, exact=False)
     ws = workspace(L.dtype, L.device, max(B * M * M, 1))
     _lib.lib().call("hb_trinv" + _suf(L), _p(L), _p(out), B, M, _p(ws), stream())
     return out
@@ -925,13 +977,13 @@ def _sgp_dims(x, z, u):
 
 def sgp_strip_path(E, n, M, d, P, prec=PREC_NATIVE):
     """True when sgp_fwd / sgp_bwd (given wfrag) run in column-strip form and may exchange A / Kbar fragment-major."""
-    return bool(_lib.lib().raw("hb_sgp_strip_path")(E, n, M, d, P, int(prec)))
+    return bool(_query("hb_sgp_strip_path", E, n, M, d, P, prec))
 
 
 def sgp_frag_elems(E, n, M, prec=PREC_NATIVE):
     """fp32 elements of a fragment-major [E, M, n] operand buffer (columns padded to whole strips of 32); the bf16x3
     form holds three bf16 planes instead of one fp32 image: 1.5 times the bytes."""
-    return int(_lib.lib().raw("hb_sgp_frag_elems")(int(E), int(n), int(M), int(prec)))
+    return _query("hb_sgp_frag_elems", E, n, M, prec)
 
 
 def _sgp_fwd_query(name, x, z, u, prec, has_wfrag, draw, rng):
@@ -939,7 +991,7 @@ def _sgp_fwd_query(name, x, z, u, prec, has_wfrag, draw, rng):
     E, n, M, d, P, _ = _sgp_dims(x, z, u)
     if x.dtype != torch.float32:
         return 0
-    return int(_lib.lib().raw(name)(E, n, M, d, P, int(prec), int(bool(has_wfrag)), int(bool(draw)), rng.nlanes if rng is not None else 0))
+    return _query(name, E, n, M, d, P, prec, bool(has_wfrag), bool(draw), rng.nlanes if rng is not None else 0)
 
 
 def sgp_head_units(x, z, u, prec, has_wfrag, draw, rng):
@@ -951,18 +1003,18 @@ def matmul_gram_vjp_ok(M, K, batch, d, dtype):
     """The square product [batch, M, K] x [batch, K, M] can carry the Gram VJP of its result (hb_matmul_gram_vjp_ok)."""
     if dtype != torch.float32:
         return False
-    return bool(_lib.lib().raw("hb_matmul_gram_vjp_ok")(int(M), int(K), int(batch), int(d)))
+    return bool(_query("hb_matmul_gram_vjp_ok", M, K, batch, d))
 
 
 def matmul_gram_vjp_ws_elems(batch, M, d):
     """Scratch elements of matmul_gram_vjp's `part` (hb_matmul_gram_vjp_ws_elems)."""
-    return int(_lib.lib().raw("hb_matmul_gram_vjp_ws_elems")(int(batch), int(M), int(d)))
+    return _query("hb_matmul_gram_vjp_ws_elems", batch, M, d)
 
 
 def matmul_wgk_shape(M, N, K, batch):
     """The shape [batch, M, K] x [batch, K, N] lies inside hb_matmul_f32's in-workgroup split-K form (hb_matmul_wgk_shape:
     the shape part of the rule only -- alignment, flags and the mm_no_wgk switch are the call's own business)."""
-    return bool(_lib.lib().raw("hb_matmul_wgk_shape")(int(M), int(N), int(K), int(batch)))
+    return bool(_query("hb_matmul_wgk_shape", M, N, K, batch))
 
 
 MatmulForm = collections.namedtuple("MatmulForm", "form S vec finish bfast colsum_fused")
@@ -1011,7 +1063,7 @@ def matmul_gram_vjp_tiles_ok(M, K, batch, d, dtype):
     (hb_matmul_gram_vjp_tiles_ok; hb_debug_set("gram_vjp_tiles", 0) answers no)."""
     if dtype != torch.float32:
         return False
-    return bool(_lib.lib().raw("hb_matmul_gram_vjp_tiles_ok")(int(M), int(K), int(batch), int(d)))
+    return bool(_query("hb_matmul_gram_vjp_tiles_ok", M, K, batch, d))
 
 
 def matmul_gram_vjp_tiles(a, b, out, transA, transB, X, sX, ell, sEll, dl, d, part):
@@ -1036,7 +1088,7 @@ def matmul_gauss_units(n, K, N, dtype):
     """Partial-sum units of hb_matmul_gauss for an [n, K] x [K, N] MatBias layer feeding a Gaussian head (0: not this shape)."""
     if dtype != torch.float32:
         return 0
-    return int(_lib.lib().raw("hb_matmul_gauss_units")(int(n), int(K), int(N)))
+    return _query("hb_matmul_gauss_units", n, K, N)
 
 
 def matmul_gauss(x, w, bias, head):
@@ -1069,7 +1121,7 @@ def sgp_rider_flush():
 
 
 def sgp_rider_pending():
-    return int(_lib.lib().raw("hb_sgp_rider_pending")())
+    return _query("hb_sgp_rider_pending")
 
 
 def gauss_ll_fold(part, nb, ll, ds, dv):
@@ -1096,7 +1148,7 @@ def sgp_fwd(x, z, ell, W, u, eps_in=None, rng=None, mode=SGP_DIAGONAL, out=None,
         f, A, v, eps = out
     dl = ell.numel() // E
     rp, rl = _rng_args(rng)
-    ws = workspace(dt, dev, int(_lib.lib().raw("hb_sgp_ws_elems")(E, n, M, d, P)))
+    ws = workspace(dt, dev, sgp_ws_elems(E, n, M, d, P))
     # a_frag: also (skip_a: only) leave A fragment-major for sgp_bwd (column-strip form, see the header)
     if head is not None:
         _lib.lib().call("hb_sgp_fwd_gauss_f32", KERN_RBF, mode, _p(x), sx, _p(z), _p(ell), dl, _p(W), _p(wfrag), int(prec), _p(u),
@@ -1112,7 +1164,7 @@ def sgp_fwd(x, z, ell, W, u, eps_in=None, rng=None, mode=SGP_DIAGONAL, out=None,
 
 def sgp_ws_elems(E, n, M, d, P):
     """Workspace elements of sgp_fwd / sgp_bwd for this shape (hb_sgp_ws_elems)."""
-    return int(_lib.lib().raw("hb_sgp_ws_elems")(int(E), int(n), int(M), int(d), int(P)))
+    return _query("hb_sgp_ws_elems", E, n, M, d, P)
 
 
 def sgp_fwd_kbar_supported(x, z, u, prec, has_wfrag, draw, rng):
@@ -1132,7 +1184,9 @@ def sgp_fwd_gauss_kbar(x, z, ell, W, u, wfrag, a_frag, abar_frag, bws, head, eps
     E, n, M, d, P, sx = _sgp_dims(x, z, u)
     lead = (E,) if z.dim() == 3 else ()
     dev, dt = x.device, x.dtype
-    assert dt == torch.float32 and wfrag is not None and a_frag is not None and head.get("fbar") is not None
+    who = "sgp_fwd_gauss_kbar"
+    _require(dt == torch.float32 and all(t is not None for t in (wfrag, a_frag, abar_frag, bws, head.get("fbar"))), who,
+             "float32 operands, wfrag, a_frag, abar_frag, bws and head['fbar'] expected")
     if out is None:
         f = _empty(lead + (P, n), dtype=dt, device=dev)
         v = _empty(lead + (n,), dtype=dt, device=dev)
@@ -1141,8 +1195,9 @@ def sgp_fwd_gauss_kbar(x, z, ell, W, u, wfrag, a_frag, abar_frag, bws, head, eps
         f, v, eps = out
     dl = ell.numel() // E
     rp, rl = _rng_args(rng)
-    wse = int(_lib.lib().raw("hb_sgp_ws_elems")(E, n, M, d, P))
-    assert bws.numel() >= wse and abar_frag.numel() >= sgp_frag_elems(E, n, M)
+    wse = sgp_ws_elems(E, n, M, d, P)
+    _ws(who, bws, dt, dev, wse, "sgp_ws_elems", "bws")   # (the caller's own buffers, sized like workspaces)
+    _ws(who, abar_frag, dt, dev, sgp_frag_elems(E, n, M), "sgp_frag_elems", "abar_frag")
     ws = workspace(dt, dev, wse)
     _lib.lib().call("hb_sgp_fwd_gauss_kbar_f32", KERN_RBF, mode, _p(x), sx, _p(z), _p(ell), dl, _p(W), _p(wfrag), int(PREC_NATIVE),
                     _p(u), _p(eps_in), rp, rl, _p(eps), None, _p(a_frag), _p(f), _p(v), E, n, M, d, P, _p(ws), _p(head["y"]),
@@ -1156,7 +1211,7 @@ def sgp_bwd_phi_rest(a_frag, abar_frag, bws, dims, dl, out):
     Abar A^T contraction and the finish launch.  dims = (E, n, M, d, P); out = (Phi, ubar, zbar, ellbar), returned."""
     E, n, M, d, P = (int(t) for t in dims)
     Phi, ubar, zbar, ellbar = out
-    assert Phi.dtype == torch.float32
+    _require(Phi.dtype == torch.float32, "sgp_bwd_phi_rest", "float32 operands expected")
     _lib.lib().call("hb_sgp_bwd_phi_rest_f32", _p(a_frag), _p(abar_frag), _p(Phi), _p(ubar), _p(zbar), _p(ellbar), int(dl), E, n, M, d,
                     P, _p(bws), stream())
     return Phi, ubar, zbar, ellbar
@@ -1178,32 +1233,25 @@ def sgp_A(x, z, ell, W, out=None, wfrag=None, prec=PREC_NATIVE):
 def sgp_predict_fused(dtype, E, n, M, d, P, s_kind, has_wfrag):
     """True when hb_sgp_predict runs its fused streaming kernel for these extents (hb_sgp_predict_fused); everything else
     runs in column chunks."""
-    return bool(_lib.lib().raw("hb_sgp_predict_fused")(int(E), int(n), int(M), int(d), int(P), int(s_kind), int(bool(has_wfrag)),
-                                                       _elem_bytes(dtype)))
+    return bool(_query("hb_sgp_predict_fused", E, n, M, d, P, s_kind, bool(has_wfrag), _elem_bytes(dtype)))
 
 
 def sgp_predict_ws_elems(dtype, E, n, M, d, P, s_kind, has_wfrag):
     """Scratch elements hb_sgp_predict needs (bounded by one column chunk, not by n)."""
-    return int(_lib.lib().raw("hb_sgp_predict_ws_elems")(int(E), int(n), int(M), int(d), int(P), int(s_kind),
-                                                         int(bool(has_wfrag)), _elem_bytes(dtype)))
+    return _query("hb_sgp_predict_ws_elems", E, n, M, d, P, s_kind, bool(has_wfrag), _elem_bytes(dtype))
 
 
 def sgp_predict(x, z, ell, W, m, s, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, jitter=0.0, out=None, wfrag=None, ws=None):
     """Closed-form predictive moments (mean[E?,P,n], var[E?,P,n]) of sgp_fwd's draw for u ~ N(m, S S^T) (hb_sgp_predict).
     m [E?, P, M]; s: standard deviations [E?, P, M] (SGP_S_DIAG) or ONE lower-triangular [R, R], R = E P M (SGP_S_TRIL).
     `wfrag`: cholesky_inverse's fragment-major images of W (the fused form needs them; None: chunked form)."""
-    for t in (x, z, ell, W, m, s):
-        _chk(t)
+    who = "sgp_predict"
+    _operands(who, x, z, ell, W, m, s, wfrag)
     E, n, M, d, P, sx = _sgp_dims(x, z, m)
     lead = (E,) if z.dim() == 3 else ()
     dev, dt = x.device, x.dtype
-    if out is None:
-        mean = _empty(lead + (P, n), dtype=dt, device=dev)
-        var = _empty(lead + (P, n), dtype=dt, device=dev)
-    else:
-        mean, var = out
-    if ws is None:
-        ws = workspace(dt, dev, max(sgp_predict_ws_elems(dt, E, n, M, d, P, s_kind, wfrag is not None), 1))
+    mean, var = _outs(who, out, (lead + (P, n),) * 2, dt, dev, ("mean", "var"))
+    ws = _ws(who, ws, dt, dev, sgp_predict_ws_elems(dt, E, n, M, d, P, s_kind, wfrag is not None), "sgp_predict_ws_elems")
     _lib.lib().call("hb_sgp_predict" + _suf(x), KERN_RBF, _p(x), sx, _p(z), _p(ell), ell.numel() // E, _p(W), _p(wfrag), _p(m),
                     _p(s), int(s_kind), int(mode), float(jitter), _p(mean), _p(var), E, n, M, d, P, _p(ws), stream())
     return mean, var
@@ -1212,8 +1260,6 @@ def sgp_predict(x, z, ell, W, m, s, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, jitter
 def _predict_grad_shapes(who, x, z, ell, W, m, s, s_kind, wfrag):
     """(n, M, d) of the operands of sgp_predict_grad / sgp_acq, checked: on the device, contiguous, one expert and one
     latent function, shapes that fit, one dtype."""
-    for t in (x, z, ell, W, m, s) + (() if wfrag is None else (wfrag,)):
-        _chk(t)
     if x.dim() != 2 or z.dim() != 2 or z.shape[1] != x.shape[1] or tuple(W.shape) != (z.shape[0], z.shape[0]):
         raise ValueError("%s: x [n, d], z [M, d], W [M, M] expected, got %s %s %s"
                          % (who, tuple(x.shape), tuple(z.shape), tuple(W.shape)))
@@ -1222,35 +1268,20 @@ def _predict_grad_shapes(who, x, z, ell, W, m, s, s_kind, wfrag):
         raise ValueError("%s: m [M] and 1 or d lengthscales expected, got %s %s" % (who, tuple(m.shape), tuple(ell.shape)))
     if s_kind not in (SGP_S_DIAG, SGP_S_TRIL) or s.numel() != (M if s_kind == SGP_S_DIAG else M * M):
         raise ValueError("%s: s must be [M] (SGP_S_DIAG) or [M, M] (SGP_S_TRIL), got %s" % (who, tuple(s.shape)))
-    if any(t.dtype != x.dtype for t in (z, ell, W, m, s)) or (wfrag is not None and wfrag.dtype != x.dtype):
-        raise TypeError("%s: all operands must share one dtype" % who)
+    _operands(who, x, z, ell, W, m, s, wfrag)
     if wfrag is not None and wfrag.numel() < 2 * M * M:
         raise ValueError("%s: wfrag must hold the two fragment-major images of W (2 M^2 elements)" % who)
     return n, M, d
 
 
-def _predict_grad_ws(who, ws, x, need):
-    if ws is None:
-        return workspace(x.dtype, x.device, max(need, 1))
-    _chk(ws)
-    if ws.dtype != x.dtype or ws.numel() < need:
-        raise ValueError("%s: the workspace must hold %d elements of %s" % (who, need, x.dtype))
-    return ws
-
-
-def _predict_grad_out(who, t, shape, x, name):
-    if t is None:
-        return _empty(shape, dtype=x.dtype, device=x.device)
-    _chk(t)
-    if tuple(t.shape) != tuple(shape) or t.dtype != x.dtype:
-        raise ValueError("%s: %s must be %s of the operands' dtype" % (who, name, list(shape)))
-    return t
-
-
 def sgp_predict_grad_ws_elems(dtype, n, M, d, s_kind, has_wfrag):
     """Scratch elements hb_sgp_predict_grad / hb_sgp_acq need (bounded by one column chunk, not by n)."""
-    return int(_lib.lib().raw("hb_sgp_predict_grad_ws_elems")(int(n), int(M), int(d), int(s_kind), int(bool(has_wfrag)),
-                                                              _elem_bytes(dtype)))
+    return _query("hb_sgp_predict_grad_ws_elems", n, M, d, s_kind, bool(has_wfrag), _elem_bytes(dtype))
+
+
+def sgp_acq_ws_elems(dtype, n, M, d, s_kind, has_wfrag):
+    """Scratch elements hb_sgp_acq needs (those of hb_sgp_predict_grad)."""
+    return _query("hb_sgp_acq_ws_elems", n, M, d, s_kind, bool(has_wfrag), _elem_bytes(dtype))
 
 
 def sgp_predict_grad(x, z, ell, W, m, s, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, jitter=0.0, out=None, wfrag=None, ws=None,
@@ -1264,11 +1295,12 @@ def sgp_predict_grad(x, z, ell, W, m, s, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, j
     who = "sgp_predict_grad"
     n, M, d = _predict_grad_shapes(who, x, z, ell, W, m, s, s_kind, wfrag)
     o = (None,) * 4 if out is None else tuple(out)
-    mean = _predict_grad_out(who, o[0], (n,), x, "mean") if values else None
-    var = _predict_grad_out(who, o[1], (n,), x, "var") if values else None
-    dmean = _predict_grad_out(who, o[2], (n, d), x, "dmean")
-    dvar = _predict_grad_out(who, o[3], (n, d), x, "dvar")
-    ws = _predict_grad_ws(who, ws, x, sgp_predict_grad_ws_elems(x.dtype, n, M, d, s_kind, wfrag is not None))
+    dt, dev = x.dtype, x.device
+    mean = _out(who, o[0], (n,), dt, dev, "mean") if values else None
+    var = _out(who, o[1], (n,), dt, dev, "var") if values else None
+    dmean = _out(who, o[2], (n, d), dt, dev, "dmean")
+    dvar = _out(who, o[3], (n, d), dt, dev, "dvar")
+    ws = _ws(who, ws, dt, dev, sgp_predict_grad_ws_elems(dt, n, M, d, s_kind, wfrag is not None), "sgp_predict_grad_ws_elems")
     _lib.lib().call("hb_sgp_predict_grad" + _suf(x), KERN_RBF, _p(x), _p(z), _p(ell), ell.numel(), _p(W), _p(wfrag), _p(m), _p(s),
                     int(s_kind), int(mode), float(jitter), _p(mean), _p(var), _p(dmean), _p(dvar), n, M, d, _p(ws), stream())
     return mean, var, dmean, dvar
@@ -1284,9 +1316,7 @@ def sgp_acq(x, z, ell, W, m, s, acq, best=0.0, param=0.0, scale=1.0, largest=Tru
     Model operands as for sgp_predict_grad."""
     who = "sgp_acq"
     n, M, d = _predict_grad_shapes(who, x, z, ell, W, m, s, s_kind, wfrag)
-    code = ACQ.get(acq, None) if isinstance(acq, str) else acq
-    if code not in ACQ.values():
-        raise ValueError("%s: acq must be one of %s, got %r" % (who, sorted(ACQ), acq))
+    code = _code(who, ACQ, acq)
     if not (value or grad or argmax):
         raise ValueError("%s: at least one of value, grad, argmax expected" % who)
     if argmax and n < 1:
@@ -1295,9 +1325,7 @@ def sgp_acq(x, z, ell, W, m, s, acq, best=0.0, param=0.0, scale=1.0, largest=Tru
     g = _empty((n, d), dtype=x.dtype, device=x.device) if grad else None
     bv = _empty((1,), dtype=x.dtype, device=x.device) if argmax else None
     bi = _empty((1,), dtype=torch.int64, device=x.device) if argmax else None
-    need = int(_lib.lib().raw("hb_sgp_acq_ws_elems")(int(n), int(M), int(d), int(s_kind), int(wfrag is not None),
-                                                     _elem_bytes(x.dtype)))
-    ws = _predict_grad_ws(who, ws, x, need)
+    ws = _ws(who, ws, x.dtype, x.device, sgp_acq_ws_elems(x.dtype, n, M, d, s_kind, wfrag is not None), "sgp_acq_ws_elems")
     _lib.lib().call("hb_sgp_acq" + _suf(x), KERN_RBF, _p(x), _p(z), _p(ell), ell.numel(), _p(W), _p(wfrag), _p(m), _p(s),
                     int(s_kind), int(mode), float(jitter), int(code), float(best), float(param), float(scale),
                     1 if largest else 0, float(var_floor), _p(val), _p(g), _p(bv), _p(bi), n, M, d, _p(ws), stream())
@@ -1306,23 +1334,20 @@ def sgp_acq(x, z, ell, W, m, s, acq, best=0.0, param=0.0, scale=1.0, largest=Tru
 
 def sgp_predict_cov_ws_elems(dtype, E, n, M, P, s_kind):
     """Scratch elements hb_sgp_predict_cov needs: A [E, M, n], C = S^T A [M, n] (full-rank S), a2 [E, n] -- linear in n."""
-    return int(_lib.lib().raw("hb_sgp_predict_cov_ws_elems")(int(E), int(n), int(M), int(P), int(s_kind),
-                                                             _elem_bytes(dtype)))
+    return _query("hb_sgp_predict_cov_ws_elems", E, n, M, P, s_kind, _elem_bytes(dtype))
 
 
 def sgp_predict_cov(x, z, ell, W, s, P, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, jitter=0.0, out=None, wfrag=None, ws=None):
     """Full predictive covariance cov[E?, P, n, n] of sgp_fwd's draw for u ~ N(m, S S^T) (hb_sgp_predict_cov): bitwise
     symmetric, its diagonal the var of sgp_predict.  s: standard deviations [E?, P, M] (SGP_S_DIAG) or one lower-triangular
     [M, M] for E P == 1 (SGP_S_TRIL).  `wfrag`: cholesky_inverse's fragment-major images of W (optional)."""
-    for t in (x, z, ell, W, s):
-        _chk(t)
+    who = "sgp_predict_cov"
+    _operands(who, x, z, ell, W, s, wfrag)
     E, n, M, d, _, sx = _sgp_dims(x, z, s if s_kind == SGP_S_DIAG else z)
     lead = (E,) if z.dim() == 3 else ()
     dev, dt = x.device, x.dtype
-    if out is None:
-        out = _empty(lead + (int(P), n, n), dtype=dt, device=dev)
-    if ws is None:
-        ws = workspace(dt, dev, max(sgp_predict_cov_ws_elems(dt, E, n, M, P, s_kind), 1))
+    out = _out(who, out, lead + (int(P), n, n), dt, dev)
+    ws = _ws(who, ws, dt, dev, sgp_predict_cov_ws_elems(dt, E, n, M, P, s_kind), "sgp_predict_cov_ws_elems")
     _lib.lib().call("hb_sgp_predict_cov" + _suf(x), KERN_RBF, _p(x), sx, _p(z), _p(ell), ell.numel() // E, _p(W), _p(wfrag),
                     _p(s), int(s_kind), int(mode), float(jitter), _p(out), E, n, M, d, int(P), _p(ws), stream())
     return out
@@ -1331,7 +1356,7 @@ def sgp_predict_cov(x, z, ell, W, s, P, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, ji
 def sgp_stats_ws_elems(dtype, N, M, d, P):
     """Scratch elements hb_sgp_stats needs: one column chunk of A plus the K-split partial tiles -- the same for every
     N above one chunk."""
-    return int(_lib.lib().raw("hb_sgp_stats_ws_elems")(int(N), int(M), int(d), int(P), _elem_bytes(dtype)))
+    return _query("hb_sgp_stats_ws_elems", N, M, d, P, _elem_bytes(dtype))
 
 
 def sgp_stats(X, Y, z, ell, W, wfrag=None, ws=None):
@@ -1340,23 +1365,18 @@ def sgp_stats(X, Y, z, ell, W, wfrag=None, ws=None):
     device tensors whatever the input dtype.  X [N, d], Y [N, P], z [M, d], ell [dl], W [M, M]; one expert.  Phi is
     bitwise symmetric; two calls on the same inputs return the same bits.  `wfrag`: cholesky_inverse's fragment-major
     images of W (optional)."""
-    for t in (X, Y, z, ell, W):
-        _chk(t)
     if X.dim() != 2 or Y.dim() != 2 or z.dim() != 2 or X.shape[0] != Y.shape[0] or X.shape[1] != z.shape[1]:
         raise ValueError("sgp_stats: X [N, d], Y [N, P], z [M, d] expected, got %s %s %s"
                          % (tuple(X.shape), tuple(Y.shape), tuple(z.shape)))
     dt, dev = X.dtype, X.device
-    if any(t.dtype != dt for t in (Y, z, ell, W)):
-        raise TypeError("sgp_stats: all operands must share one dtype")
+    _operands("sgp_stats", X, Y, z, ell, W, wfrag)
     N, d = X.shape
     M, P = z.shape[0], Y.shape[1]
     Phi = _empty((M, M), dtype=torch.float64, device=dev)
     b = _empty((P, M), dtype=torch.float64, device=dev)
     yy = _empty((P,), dtype=torch.float64, device=dev)
     a2sum = _empty((1,), dtype=torch.float64, device=dev)
-    if ws is None:
-        ws = workspace(dt, dev, max(sgp_stats_ws_elems(dt, N, M, d, P), 1))
-    assert ws.numel() >= sgp_stats_ws_elems(dt, N, M, d, P), "hb_sgp_stats: workspace too small (sgp_stats_ws_elems)"
+    ws = _ws("sgp_stats", ws, dt, dev, sgp_stats_ws_elems(dt, N, M, d, P), "sgp_stats_ws_elems")
     _lib.lib().call("hb_sgp_stats" + _suf(X), KERN_RBF, _p(X), _p(Y), _p(z), _p(ell), ell.numel(), _p(W), _p(wfrag), _p(Phi),
                     _p(b), _p(yy), _p(a2sum), N, M, d, P, _p(ws), stream())
     return Phi, b, yy, a2sum
@@ -1364,29 +1384,24 @@ def sgp_stats(X, Y, z, ell, W, wfrag=None, ws=None):
 
 def sgp_wstats_ws_elems(dtype, N, M, d):
     """Scratch elements hb_sgp_wstats needs (those of hb_sgp_stats with P = 1; the same for every N above one chunk)."""
-    return int(_lib.lib().raw("hb_sgp_wstats_ws_elems")(int(N), int(M), int(d), _elem_bytes(dtype)))
+    return _query("hb_sgp_wstats_ws_elems", N, M, d, _elem_bytes(dtype))
 
 
 def sgp_wstats(X, w, r, z, ell, W, wfrag=None, ws=None):
     """Weighted statistics (hb_sgp_wstats): with A = W K(z, X) [M, N], (Phi = A diag(w) A^T [M, M], b = (A r)^T [1, M],
     tr Phi [1]) as FLOAT64 device tensors.  X [N, d], w [N] (any sign, zeros included), r [N], z [M, d], ell [dl],
     W [M, M]; one expert.  Phi is bitwise symmetric; two calls return the same bits; w == 1 gives the bits of sgp_stats."""
-    for t in (X, w, r, z, ell, W):
-        _chk(t)
     if X.dim() != 2 or z.dim() != 2 or X.shape[1] != z.shape[1] or w.numel() != X.shape[0] or r.numel() != X.shape[0]:
         raise ValueError("sgp_wstats: X [N, d], w [N], r [N], z [M, d] expected, got %s %s %s %s"
                          % (tuple(X.shape), tuple(w.shape), tuple(r.shape), tuple(z.shape)))
     dt, dev = X.dtype, X.device
-    if any(t.dtype != dt for t in (w, r, z, ell, W)):
-        raise TypeError("sgp_wstats: all operands must share one dtype")
+    _operands("sgp_wstats", X, w, r, z, ell, W, wfrag)
     N, d = X.shape
     M = z.shape[0]
     Phi = _empty((M, M), dtype=torch.float64, device=dev)
     b = _empty((1, M), dtype=torch.float64, device=dev)
     tr = _empty((1,), dtype=torch.float64, device=dev)
-    if ws is None:
-        ws = workspace(dt, dev, max(sgp_wstats_ws_elems(dt, N, M, d), 1))
-    assert ws.numel() >= sgp_wstats_ws_elems(dt, N, M, d), "hb_sgp_wstats: workspace too small (sgp_wstats_ws_elems)"
+    ws = _ws("sgp_wstats", ws, dt, dev, sgp_wstats_ws_elems(dt, N, M, d), "sgp_wstats_ws_elems")
     _lib.lib().call("hb_sgp_wstats" + _suf(X), KERN_RBF, _p(X), _p(w), _p(r), _p(z), _p(ell), ell.numel(), _p(W), _p(wfrag),
                     _p(Phi), _p(b), _p(tr), N, M, d, _p(ws), stream())
     return Phi, b, tr
@@ -1394,7 +1409,7 @@ def sgp_wstats(X, w, r, z, ell, W, wfrag=None, ws=None):
 
 def sgp_mwstats_ws_elems(dtype, N, M, d, C):
     """Scratch elements hb_sgp_mwstats needs: those of hb_sgp_wstats, whatever C (the partial tiles are reused set by set)."""
-    return int(_lib.lib().raw("hb_sgp_mwstats_ws_elems")(int(N), int(M), int(d), int(C), _elem_bytes(dtype)))
+    return _query("hb_sgp_mwstats_ws_elems", N, M, d, C, _elem_bytes(dtype))
 
 
 def sgp_mwstats(X, w, r, z, ell, W, wfrag=None, ws=None):
@@ -1404,14 +1419,13 @@ def sgp_mwstats(X, w, r, z, ell, W, wfrag=None, ws=None):
     rows of w and r may be padded (stride(0) >= N, stride(1) == 1); every row of w must start 16-byte aligned, which a
     contiguous [C, N] float32 pair meets when N % 4 == 0 -- otherwise w and r are copied once into rows padded to a
     multiple of 4."""
-    for t in (X, z, ell, W):
-        _chk(t)
     if (X.dim() != 2 or z.dim() != 2 or X.shape[1] != z.shape[1] or w.dim() != 2 or w.shape != r.shape
             or w.shape[1] != X.shape[0] or w.shape[0] < 1):
         raise ValueError("sgp_mwstats: X [N, d], w [C, N], r [C, N], z [M, d] expected, got %s %s %s %s"
                          % (tuple(X.shape), tuple(w.shape), tuple(r.shape), tuple(z.shape)))
     dt, dev = X.dtype, X.device
-    if any(t.dtype != dt for t in (w, r, z, ell, W)) or not (w.is_cuda and r.is_cuda):
+    _operands("sgp_mwstats", X, z, ell, W, wfrag)
+    if w.dtype != dt or r.dtype != dt or not (w.is_cuda and r.is_cuda):   # (their rows may be padded: not _operands)
         raise TypeError("sgp_mwstats: all operands must live on the GPU and share one dtype")
     N, d = X.shape
     M, C = z.shape[0], w.shape[0]
@@ -1427,9 +1441,7 @@ def sgp_mwstats(X, w, r, z, ell, W, wfrag=None, ws=None):
     Phi = _empty((C, M, M), dtype=torch.float64, device=dev)
     b = _empty((C, M), dtype=torch.float64, device=dev)
     tr = _empty((C,), dtype=torch.float64, device=dev)
-    if ws is None:
-        ws = workspace(dt, dev, max(sgp_mwstats_ws_elems(dt, N, M, d, C), 1))
-    assert ws.numel() >= sgp_mwstats_ws_elems(dt, N, M, d, C), "hb_sgp_mwstats: workspace too small (sgp_mwstats_ws_elems)"
+    ws = _ws("sgp_mwstats", ws, dt, dev, sgp_mwstats_ws_elems(dt, N, M, d, C), "sgp_mwstats_ws_elems")
     _lib.lib().call("hb_sgp_mwstats" + _suf(X), KERN_RBF, _p(X), _p(w), _p(r), ldw, _p(z), _p(ell), ell.numel(), _p(W),
                     _p(wfrag), _p(Phi), _p(b), _p(tr), N, M, d, C, _p(ws), stream())
     return Phi, b, tr
@@ -1441,12 +1453,7 @@ def sgp_pathwise(x, omega, z, ell, coef, scale=1.0, out=None):
     z [M, d] or None (M = 0: the prior path alone), ell [1] or [d], coef [S, 2L + M], all of one dtype.  The value of a
     column does not depend on the other columns: two calls, or x in pieces, return the same bits."""
     n, d, L, M, S = _pathwise_shapes("sgp_pathwise", x, omega, z, ell, coef)
-    if out is None:
-        out = _empty((S, n), dtype=x.dtype, device=x.device)
-    else:
-        _chk(out)
-        if tuple(out.shape) != (S, n) or out.dtype != x.dtype:
-            raise ValueError("sgp_pathwise: out must be [%d, %d] of the operands' dtype" % (S, n))
+    out = _out("sgp_pathwise", out, (S, n), x.dtype, x.device)
     _lib.lib().call("hb_sgp_pathwise" + _suf(x), KERN_RBF, _p(x), _p(omega), _p(z if M else None), _p(ell), ell.numel(), _p(coef),
                     float(scale), _p(out), n, L, M, d, S, stream())
     return out
@@ -1455,8 +1462,6 @@ def sgp_pathwise(x, omega, z, ell, coef, scale=1.0, out=None):
 def _pathwise_shapes(who, x, omega, z, ell, coef):
     """(n, d, L, M, S) of the operands of a pathwise entry (sgp_pathwise, _grad, _argmax, _acq), checked:
     on the device, contiguous, shapes that fit, one dtype."""
-    for t in (x, omega, ell, coef) + (() if z is None else (z,)):
-        _chk(t)
     if x.dim() != 2 or omega.dim() != 2 or coef.dim() != 2 or omega.shape[1] != x.shape[1] or (
             z is not None and (z.dim() != 2 or z.shape[1] != x.shape[1])):
         raise ValueError("%s: x [n, d], omega [L, d], z [M, d] or None, coef [S, 2L + M] expected, got %s %s %s %s"
@@ -1465,8 +1470,7 @@ def _pathwise_shapes(who, x, omega, z, ell, coef):
     L, M, S = omega.shape[0], 0 if z is None else z.shape[0], coef.shape[0]
     if coef.shape[1] != 2 * L + M:
         raise ValueError("%s: coef must hold 2L + M = %d columns, got %s" % (who, 2 * L + M, tuple(coef.shape)))
-    if any(t.dtype != x.dtype for t in (omega, ell, coef)) or (z is not None and z.dtype != x.dtype):
-        raise TypeError("%s: all operands must share one dtype" % who)
+    _operands(who, x, omega, z, ell, coef)
     return n, d, L, M, S
 
 
@@ -1476,20 +1480,11 @@ def sgp_pathwise_grad(x, omega, z, ell, coef, scale=1.0, out=None, grad=None, va
     stored, `out` (if given) is left untouched and None is returned in its place.  `out` carries the bits of sgp_pathwise;
     out[s, j] and grad[s, j, :] depend neither on the other columns nor on the other draws: two calls, x in pieces, or a
     subset of the draws return the same bits."""
-    n, d, L, M, S = _pathwise_shapes("sgp_pathwise_grad", x, omega, z, ell, coef)
+    who = "sgp_pathwise_grad"
+    n, d, L, M, S = _pathwise_shapes(who, x, omega, z, ell, coef)
     if values:
-        if out is None:
-            out = _empty((S, n), dtype=x.dtype, device=x.device)
-        else:
-            _chk(out)
-            if tuple(out.shape) != (S, n) or out.dtype != x.dtype:
-                raise ValueError("sgp_pathwise_grad: out must be [%d, %d] of the operands' dtype" % (S, n))
-    if grad is None:
-        grad = _empty((S, n, d), dtype=x.dtype, device=x.device)
-    else:
-        _chk(grad)
-        if tuple(grad.shape) != (S, n, d) or grad.dtype != x.dtype:
-            raise ValueError("sgp_pathwise_grad: grad must be [%d, %d, %d] of the operands' dtype" % (S, n, d))
+        out = _out(who, out, (S, n), x.dtype, x.device)
+    grad = _out(who, grad, (S, n, d), x.dtype, x.device, "grad")
     _lib.lib().call("hb_sgp_pathwise_grad" + _suf(x), KERN_RBF, _p(x), _p(omega), _p(z if M else None), _p(ell), ell.numel(),
                     _p(coef), float(scale), _p(out if values else None), _p(grad), n, L, M, d, S, stream())
     return (out if values else None), grad
@@ -1497,7 +1492,7 @@ def sgp_pathwise_grad(x, omega, z, ell, coef, scale=1.0, out=None, grad=None, va
 
 def sgp_pathwise_argmax_ws_elems(dtype, n, S):
     """Scratch elements (of the operands' dtype, whichever it is) hb_sgp_pathwise_argmax needs: 2 S ceil(n / 128)."""
-    return int(_lib.lib().raw("hb_sgp_pathwise_argmax_ws_elems")(int(n), int(S)))
+    return _query("hb_sgp_pathwise_argmax_ws_elems", n, S)
 
 
 def sgp_pathwise_argmax(x, omega, z, ell, coef, scale=1.0, largest=True, ws=None):
@@ -1511,13 +1506,8 @@ def sgp_pathwise_argmax(x, omega, z, ell, coef, scale=1.0, largest=True, ws=None
         raise ValueError("sgp_pathwise_argmax: at least one candidate expected, got x %s" % (tuple(x.shape),))
     best = _empty((S,), dtype=x.dtype, device=x.device)
     idx = _empty((S,), dtype=torch.int64, device=x.device)
-    need = sgp_pathwise_argmax_ws_elems(x.dtype, n, S)
-    if ws is None:
-        ws = workspace(x.dtype, x.device, max(need, 1))
-    _chk(ws)
-    if ws.dtype != x.dtype or ws.numel() < need:
-        raise ValueError("sgp_pathwise_argmax: the workspace must hold %d elements of %s (sgp_pathwise_argmax_ws_elems)"
-                         % (need, x.dtype))
+    ws = _ws("sgp_pathwise_argmax", ws, x.dtype, x.device, sgp_pathwise_argmax_ws_elems(x.dtype, n, S),
+             "sgp_pathwise_argmax_ws_elems")
     _lib.lib().call("hb_sgp_pathwise_argmax" + _suf(x), KERN_RBF, _p(x), _p(omega), _p(z if M else None), _p(ell), ell.numel(),
                     _p(coef), float(scale), 1 if largest else 0, _p(best), _p(idx), n, L, M, d, S, _p(ws), stream())
     return best, idx
@@ -1526,7 +1516,7 @@ def sgp_pathwise_argmax(x, omega, z, ell, coef, scale=1.0, largest=True, ws=None
 def sgp_pathwise_acq_ws_elems(n, S):
     """Scratch DOUBLES (whatever the operands' dtype) hb_sgp_pathwise_acq needs: 2 ceil(n / 128) for S <= 64, and
     ceil(S / 64) n more beyond."""
-    return int(_lib.lib().raw("hb_sgp_pathwise_acq_ws_elems")(int(n), int(S)))
+    return _query("hb_sgp_pathwise_acq_ws_elems", n, S)
 
 
 def sgp_pathwise_acq(x, omega, z, ell, coef, incumbent, scale=1.0, acq="ei", largest=True, values=True, ws=None, out=None):
@@ -1542,31 +1532,17 @@ def sgp_pathwise_acq(x, omega, z, ell, coef, incumbent, scale=1.0, acq="ei", lar
     n, d, L, M, S = _pathwise_shapes(who, x, omega, z, ell, coef)
     if n < 1:
         raise ValueError("%s: at least one candidate expected, got x %s" % (who, tuple(x.shape)))
-    code = PWACQ.get(acq, None) if isinstance(acq, str) else acq
-    if code not in PWACQ.values():
-        raise ValueError("%s: acq must be one of %s, got %r" % (who, sorted(PWACQ), acq))
+    code = _code(who, PWACQ, acq)
     if incumbent is None:
         raise ValueError("%s: incumbent [S] expected, got None" % who)
     _chk(incumbent, "incumbent")
     if tuple(incumbent.shape) != (S,) or incumbent.dtype != x.dtype:
         raise ValueError("%s: incumbent must be [%d] of the operands' dtype, got %s %s"
                          % (who, S, tuple(incumbent.shape), incumbent.dtype))
-    value = None
-    if values:
-        if out is None:
-            value = _empty((n,), dtype=x.dtype, device=x.device)
-        else:
-            value = _chk(out, "out")
-            if tuple(out.shape) != (n,) or out.dtype != x.dtype:
-                raise ValueError("%s: out must be [%d] of the operands' dtype" % (who, n))
+    value = _out(who, out, (n,), x.dtype, x.device) if values else None
     best = _empty((1,), dtype=x.dtype, device=x.device)
     idx = _empty((1,), dtype=torch.int64, device=x.device)
-    need = sgp_pathwise_acq_ws_elems(n, S)
-    if ws is None:
-        ws = workspace(torch.float64, x.device, max(need, 1))
-    _chk(ws)
-    if ws.dtype != torch.float64 or ws.numel() < need:
-        raise ValueError("%s: the workspace must hold %d elements of float64 (sgp_pathwise_acq_ws_elems)" % (who, need))
+    ws = _ws(who, ws, torch.float64, x.device, sgp_pathwise_acq_ws_elems(n, S), "sgp_pathwise_acq_ws_elems")
     _lib.lib().call("hb_sgp_pathwise_acq" + _suf(x), KERN_RBF, _p(x), _p(omega), _p(z if M else None), _p(ell), ell.numel(),
                     _p(coef), float(scale), int(code), 1 if largest else 0, _p(incumbent), _p(value), _p(best), _p(idx), n, L, M, d,
                     S, _p(ws), stream())
@@ -1575,13 +1551,13 @@ def sgp_pathwise_acq(x, omega, z, ell, coef, incumbent, scale=1.0, acq="ei", lar
 
 def gram_matvec_chunk():
     """Rows per workgroup of hb_gram_matvec: a compile-time constant of the library."""
-    return int(_lib.lib().raw("hb_gram_matvec_chunk")())
+    return _query("hb_gram_matvec_chunk")
 
 
 def gram_matvec_ws_elems(dtype, n, N, S):
     """Scratch elements hb_gram_matvec needs: 0 when N fits one chunk, chunks x S x n up to 16 chunks, beyond that 16 S n
     plus S n doubles -- O(S n) whatever N."""
-    return int(_lib.lib().raw("hb_gram_matvec_ws_elems")(int(n), int(N), int(S), _elem_bytes(dtype)))
+    return _query("hb_gram_matvec_ws_elems", n, N, S, _elem_bytes(dtype))
 
 
 def gram_matvec(x, x2, ell, V, scale=1.0, shift=0.0, out=None, ws=None, kind=KERN_RBF):
@@ -1590,8 +1566,6 @@ def gram_matvec(x, x2, ell, V, scale=1.0, shift=0.0, out=None, ws=None, kind=KER
     of one dtype.  The value of an output element depends neither on the other columns nor on the other rows of V: two
     calls, x in pieces, or a subset of the rows return the same bits.  `ws`: gram_matvec_ws_elems elements (default: the
     shared scratch of the stream)."""
-    for t in (x, ell, V) + (() if x2 is None else (x2,)):
-        _chk(t)
     if x.dim() != 2 or V.dim() != 2 or ell.dim() != 1 or (x2 is not None and (x2.dim() != 2 or x2.shape[1] != x.shape[1])):
         raise ValueError("gram_matvec: x [n, d], x2 [N, d] or None, ell [1] or [d], V [S, N] expected, got %s %s %s %s"
                          % (tuple(x.shape), None if x2 is None else tuple(x2.shape), tuple(ell.shape), tuple(V.shape)))
@@ -1600,19 +1574,9 @@ def gram_matvec(x, x2, ell, V, scale=1.0, shift=0.0, out=None, ws=None, kind=KER
     S = V.shape[0]
     if V.shape[1] != N:
         raise ValueError("gram_matvec: V must hold N = %d columns, got %s" % (N, tuple(V.shape)))
-    if any(t.dtype != x.dtype for t in (ell, V)) or (x2 is not None and x2.dtype != x.dtype):
-        raise TypeError("gram_matvec: all operands must share one dtype")
-    if out is None:
-        out = _empty((S, n), dtype=x.dtype, device=x.device)
-    else:
-        _chk(out)
-        if tuple(out.shape) != (S, n) or out.dtype != x.dtype:
-            raise ValueError("gram_matvec: out must be [%d, %d] of the operands' dtype" % (S, n))
-    need = gram_matvec_ws_elems(x.dtype, n, N, S)
-    if ws is None:
-        ws = workspace(x.dtype, x.device, max(need, 1))
-    if ws.dtype != x.dtype or ws.numel() < need:
-        raise ValueError("gram_matvec: the workspace must hold %d elements of %s (gram_matvec_ws_elems)" % (need, x.dtype))
+    _operands("gram_matvec", x, x2, ell, V)
+    out = _out("gram_matvec", out, (S, n), x.dtype, x.device)
+    ws = _ws("gram_matvec", ws, x.dtype, x.device, gram_matvec_ws_elems(x.dtype, n, N, S), "gram_matvec_ws_elems")
     _lib.lib().call("hb_gram_matvec" + _suf(x), int(kind), _p(x), _p(x2), _p(ell), ell.numel(), _p(V), float(scale),
                     float(shift), _p(out), n, N, d, S, _p(ws), stream())
     return out
@@ -1624,7 +1588,7 @@ GRAM_PREDICT_WS_BYTES = 1 << 30   # gram_predict cuts x into pieces so that hb_g
 def gram_predict_ws_elems(dtype, n, N, S):
     """Scratch elements hb_gram_predict needs: min(chunks, 16) x S x n partials (one chunk included), S n doubles beyond
     16 chunks, and a double and a long per 256 columns for the arg-max."""
-    return int(_lib.lib().raw("hb_gram_predict_ws_elems")(int(n), int(N), int(S), _elem_bytes(dtype)))
+    return _query("hb_gram_predict_ws_elems", n, N, S, _elem_bytes(dtype))
 
 
 def _gram_piece(ws_elems_of_n, dtype, n):
@@ -1644,8 +1608,6 @@ def _gram_predict_piece(n, N, S, dtype):
 def _gram_predict_operands(who, x, x2, ell, V, P, acq, var_floor):
     """(n, d, N, S, P, code) of the operands of gram_predict / gram_predict_grad, checked: on the device, contiguous,
     shapes that fit, one dtype, 1 <= P <= S; code: the acquisition's (-1 for None), which needs P == 1 and var_floor >= 0."""
-    for t in (x, x2, ell, V):
-        _chk(t)
     if x.dim() != 2 or V.dim() != 2 or ell.dim() != 1 or x2.dim() != 2 or x2.shape[1] != x.shape[1]:
         raise ValueError("%s: x [n, d], x2 [N, d], ell [1] or [d], V [S, N] expected, got %s %s %s %s"
                          % (who, tuple(x.shape), tuple(x2.shape), tuple(ell.shape), tuple(V.shape)))
@@ -1653,15 +1615,12 @@ def _gram_predict_operands(who, x, x2, ell, V, P, acq, var_floor):
     if V.shape[1] != N or N < 1 or ell.numel() not in (1, d):
         raise ValueError("%s: V must hold N = %d >= 1 columns and ell 1 or %d entries, got %s %s"
                          % (who, N, d, tuple(V.shape), tuple(ell.shape)))
-    if any(t.dtype != x.dtype for t in (x2, ell, V)):
-        raise TypeError("%s: all operands must share one dtype" % who)
+    _operands(who, x, x2, ell, V)
     if not 1 <= P <= S:
         raise ValueError("%s: 1 <= P <= S mean rows expected, got P=%d, S=%d" % (who, P, S))
     if acq is None:
         return n, d, N, S, P, -1
-    code = ACQ.get(acq, None) if isinstance(acq, str) else acq
-    if code not in ACQ.values():
-        raise ValueError("%s: acq must be one of %s, got %r" % (who, sorted(ACQ), acq))
+    code = _code(who, ACQ, acq)
     if P != 1:
         raise ValueError("%s: an acquisition is defined for one latent function only (P=%d)" % (who, P))
     if not float(var_floor) >= 0.0:
@@ -1731,7 +1690,7 @@ def gram_predict(x, x2, ell, V, P=1, scale=1.0, prior=1.0, acq=None, best=0.0, p
 def gram_predict_grad_ws_elems(dtype, n, N, d, S):
     """Scratch elements hb_gram_predict_grad needs: 1 + d times the min(chunks, 16) x S x n partials of gram_predict and,
     beyond 16 chunks, 1 + d times S n doubles; no arg-max partials."""
-    return int(_lib.lib().raw("hb_gram_predict_grad_ws_elems")(int(n), int(N), int(d), int(S), _elem_bytes(dtype)))
+    return _query("hb_gram_predict_grad_ws_elems", n, N, d, S, _elem_bytes(dtype))
 
 
 def _gram_predict_grad_piece(n, N, d, S, dtype):
@@ -1791,8 +1750,7 @@ def pcg_dot(a, b, out=None):
     _chk(a), _chk(b)
     if a.dim() != 2 or a.shape != b.shape or a.dtype != b.dtype:
         raise ValueError("pcg_dot: a, b [S, N] of one dtype expected, got %s %s" % (tuple(a.shape), tuple(b.shape)))
-    if out is None:
-        out = _empty((a.shape[0],), dtype=torch.float64, device=a.device)
+    out = _out("pcg_dot", out, (a.shape[0],), torch.float64, a.device, exact=False)
     _lib.lib().call("hb_pcg_dot" + _suf(a), _p(a), _p(b), _p(out), a.shape[0], a.shape[1], stream())
     return out
 
@@ -1848,7 +1806,7 @@ def pcg_direction(r, w, p, rz, rr, thr, wscale=1.0, zscale=1.0, first=False, coe
 
 def gram_bilinear_grad_ws_elems(N, dl):
     """Scratch DOUBLES hb_gram_bilinear_grad needs: min(chunks, 16) x strips x (1 + dl) -- O(N), whatever S."""
-    return int(_lib.lib().raw("hb_gram_bilinear_grad_ws_elems")(int(N), int(dl)))
+    return _query("hb_gram_bilinear_grad_ws_elems", N, dl)
 
 
 def gram_bilinear_grad(x, ell, A, B, w, out=None, ws=None, kind=KERN_RBF):
@@ -1856,13 +1814,11 @@ def gram_bilinear_grad(x, ell, A, B, w, out=None, ws=None, kind=KERN_RBF):
     B_sj K_ij (x_ik - x_jk)^2 / ell_k^3 (dl = 1: summed over k), with neither K nor sum_s w_s A_s (x) B_s written to memory.
     x [N, d], ell [1] or [d], A, B [S, N] of one dtype; w [S] float64 (a device tensor, or anything numpy converts).  Two
     calls return the same bits.  `ws`: gram_bilinear_grad_ws_elems doubles (default: the shared scratch of the stream)."""
-    for t in (x, ell, A, B):
-        _chk(t)
+    who = "gram_bilinear_grad"
     if x.dim() != 2 or ell.dim() != 1 or A.dim() != 2 or tuple(A.shape) != tuple(B.shape) or A.shape[1] != x.shape[0]:
         raise ValueError("gram_bilinear_grad: x [N, d], ell [1] or [d], A, B [S, N] expected, got %s %s %s %s"
                          % (tuple(x.shape), tuple(ell.shape), tuple(A.shape), tuple(B.shape)))
-    if any(t.dtype != x.dtype for t in (ell, A, B)):
-        raise TypeError("gram_bilinear_grad: x, ell, A and B must share one dtype")
+    _operands(who, x, ell, A, B, what="x, ell, A and B must share one dtype")
     N, d = x.shape
     S, dl = A.shape[0], ell.numel()
     if not torch.is_tensor(w):
@@ -1870,17 +1826,8 @@ def gram_bilinear_grad(x, ell, A, B, w, out=None, ws=None, kind=KERN_RBF):
     _chk(w)
     if w.dtype != torch.float64 or w.numel() != S:
         raise ValueError("gram_bilinear_grad: w must be float64 [%d]" % S)
-    if out is None:
-        out = _empty((1 + dl,), dtype=torch.float64, device=x.device)
-    else:
-        _chk(out)
-        if out.dtype != torch.float64 or out.numel() != 1 + dl:
-            raise ValueError("gram_bilinear_grad: out must be float64 [%d]" % (1 + dl))
-    need = gram_bilinear_grad_ws_elems(N, dl)
-    if ws is None:
-        ws = workspace(torch.float64, x.device, max(need, 1))
-    if ws.dtype != torch.float64 or ws.numel() < need:
-        raise ValueError("gram_bilinear_grad: the workspace must hold %d doubles (gram_bilinear_grad_ws_elems)" % need)
+    out = _out(who, out, (1 + dl,), torch.float64, x.device, exact=False)
+    ws = _ws(who, ws, torch.float64, x.device, gram_bilinear_grad_ws_elems(N, dl), "gram_bilinear_grad_ws_elems")
     _lib.lib().call("hb_gram_bilinear_grad" + _suf(x), int(kind), _p(x), _p(ell), dl, _p(A), _p(B), _p(w), _p(out), N, d, S,
                     _p(ws), stream())
     return out
@@ -1894,15 +1841,10 @@ def lik_sites(lik, y, mean, var, param=1.0, mscale=1.0, vscale=1.0, out=None):
     variance), LIK_BERNOULLI (logit link), LIK_POISSON (exp link), LIK_LAPLACE (param = the scale), LIK_GAMMA (exp link,
     param = the shape, y > 0), LIK_NEGBINOMIAL (exp link, param = the dispersion), LIK_BINOMIAL (logit link, param = the
     total count).  Double arithmetic; two calls return the same bits."""
-    for t in (y, mean, var):
-        _chk(t)
-    N = y.numel()
-    if mean.numel() != N or var.numel() != N or mean.dtype != y.dtype or var.dtype != y.dtype:
-        raise ValueError("lik_sites: y, mean, var must hold N elements of one dtype")
-    lam, beta = out if out is not None else (_empty((N,), dtype=y.dtype, device=y.device),
-                                             _empty((N,), dtype=y.dtype, device=y.device))
+    N = _lik_inputs("lik_sites", y, mean, var)
+    lam, beta = _outs("lik_sites", out, ((N,),) * 2, y.dtype, y.device, ("lam", "beta"), exact=False)
     ell = _empty((1,), dtype=torch.float64, device=y.device)
-    ws = workspace(torch.float64, y.device, int(_lib.lib().raw("hb_lik_sites_ws_elems")(N)))
+    ws = workspace(torch.float64, y.device, _query("hb_lik_sites_ws_elems", N))
     _lib.lib().call("hb_lik_sites" + _suf(y), int(lik), _p(y), _p(mean), _p(var), float(mscale), float(vscale), float(param),
                     _p(lam), _p(beta), _p(ell), N, _p(ws), stream())
     return lam, beta, ell
@@ -1924,7 +1866,7 @@ def lik_param_grad(lik, y, mean, var, param=1.0, mscale=1.0, vscale=1.0):
     parameter and are refused.  Double arithmetic; two calls return the same bits."""
     N = _lik_inputs("lik_param_grad", y, mean, var)
     out = _empty((2,), dtype=torch.float64, device=y.device)
-    ws = workspace(torch.float64, y.device, int(_lib.lib().raw("hb_lik_param_grad_ws_elems")(N)))
+    ws = workspace(torch.float64, y.device, _query("hb_lik_param_grad_ws_elems", N))
     _lib.lib().call("hb_lik_param_grad" + _suf(y), int(lik), _p(y), _p(mean), _p(var), float(mscale), float(vscale),
                     float(param), _p(out), N, _p(ws), stream())
     return out
@@ -1937,7 +1879,7 @@ def lik_logdens(lik, y, mean, var, param=1.0, mscale=1.0, vscale=1.0, pointwise=
     N = _lik_inputs("lik_logdens", y, mean, var)
     out = _empty((N,), dtype=y.dtype, device=y.device) if pointwise else None
     total = _empty((1,), dtype=torch.float64, device=y.device)
-    ws = workspace(torch.float64, y.device, int(_lib.lib().raw("hb_lik_sites_ws_elems")(N)))
+    ws = workspace(torch.float64, y.device, _query("hb_lik_sites_ws_elems", N))
     _lib.lib().call("hb_lik_logdens" + _suf(y), int(lik), _p(y), _p(mean), _p(var), float(mscale), float(vscale), float(param),
                     _p(out), _p(total), N, _p(ws), stream())
     return out, total
@@ -1976,9 +1918,9 @@ def lik_softmax_sites(y, mean, var, nodes, mscale=1.0, vscale=1.0, out=None):
     points.  y [N]: labels 0 .. C-1 stored in the dtype of mean.  lam = mean_s p (1 - p) >= 0.  Double arithmetic; two
     calls return the same bits."""
     N, C, S = _softmax_inputs("lik_softmax_sites", y, mean, var, nodes)
-    lam, beta = out if out is not None else (_empty_like(mean), _empty_like(mean))
+    lam, beta = _outs("lik_softmax_sites", out, ((C, N),) * 2, mean.dtype, mean.device, ("lam", "beta"))
     lsum = _empty((1,), dtype=torch.float64, device=mean.device)
-    ws = workspace(torch.float64, mean.device, int(_lib.lib().raw("hb_lik_softmax_ws_elems")(N, C)))
+    ws = workspace(torch.float64, mean.device, _query("hb_lik_softmax_ws_elems", N, C))
     _lib.lib().call("hb_lik_softmax_sites" + _suf(mean), _p(y), _p(mean), _p(var), float(mscale), float(vscale), _p(nodes), S,
                     _p(lam), _p(beta), _p(lsum), N, C, _p(ws), stream())
     return lam, beta, lsum
@@ -2002,7 +1944,7 @@ def lik_softmax_grad(y, mean, var, nodes, mscale=1.0, vscale=1.0, out=None):
                 raise ValueError("lik_softmax_grad: out = (w, r) must be float64 [%d, %d] device tensors with unit column "
                                  "stride and one row stride >= N" % (C, N))
     lsum = _empty((1,), dtype=torch.float64, device=mean.device)
-    ws = workspace(torch.float64, mean.device, int(_lib.lib().raw("hb_lik_softmax_ws_elems")(N, C)))
+    ws = workspace(torch.float64, mean.device, _query("hb_lik_softmax_ws_elems", N, C))
     _lib.lib().call("hb_lik_softmax_grad" + _suf(mean), _p(y), _p(mean), _p(var), float(mscale), float(vscale), _p(nodes), S,
                     _p(w), _p(r), max(int(w.stride(0)), N), _p(lsum), N, C, _p(ws), stream())
     return w, r, lsum
@@ -2018,7 +1960,7 @@ def lik_softmax_predict(mean, var, nodes, y=None, mscale=1.0, vscale=1.0, prob=T
     pr = _empty_like(mean) if prob else None
     ld = _empty((n,), dtype=mean.dtype, device=mean.device) if (y is not None and pointwise) else None
     total = _empty((1,), dtype=torch.float64, device=mean.device) if y is not None else None
-    ws = workspace(torch.float64, mean.device, int(_lib.lib().raw("hb_lik_softmax_ws_elems")(n, C)))
+    ws = workspace(torch.float64, mean.device, _query("hb_lik_softmax_ws_elems", n, C))
     _lib.lib().call("hb_lik_softmax_predict" + _suf(mean), _p(y), _p(mean), _p(var), float(mscale), float(vscale), _p(nodes), S,
                     _p(pr), _p(ld), _p(total), n, C, _p(ws), stream())
     return pr, ld, total
@@ -2026,7 +1968,7 @@ def lik_softmax_predict(mean, var, nodes, y=None, mscale=1.0, vscale=1.0, prob=T
 
 def sgp_kgrad_ws_elems(N, M, d, P):
     """Scratch DOUBLES hb_sgp_kgrad needs: the repacked Q and one partial per strip -- independent of N."""
-    return int(_lib.lib().raw("hb_sgp_kgrad_ws_elems")(int(N), int(M), int(d), int(P)))
+    return _query("hb_sgp_kgrad_ws_elems", N, M, d, P)
 
 
 def sgp_kgrad(X, Y, z, ell, Q, R, ws=None):
@@ -2034,8 +1976,6 @@ def sgp_kgrad(X, Y, z, ell, Q, R, ws=None):
     E = Kbar o K, returns (zbar [M, d], ellbar [dl]) = (-sum_j E_ij (z_i - x_j) / ell^2, sum_ij E_ij (z_i - x_j)^2 / ell^3)
     as float64 device tensors.  X [N, d] and Y [N, P] share one storage dtype (float32 or float64); z [M, d], ell [dl],
     Q [M, M], R [M, P] are float64 and all arithmetic is float64.  Two calls on the same inputs return the same bits."""
-    for t in (X, Y, z, ell, Q, R):
-        _chk(t)
     if X.dim() != 2 or Y.dim() != 2 or z.dim() != 2 or X.shape[0] != Y.shape[0] or X.shape[1] != z.shape[1]:
         raise ValueError("sgp_kgrad: X [N, d], Y [N, P], z [M, d] expected, got %s %s %s"
                          % (tuple(X.shape), tuple(Y.shape), tuple(z.shape)))
@@ -2044,16 +1984,13 @@ def sgp_kgrad(X, Y, z, ell, Q, R, ws=None):
     if ell.dim() != 1 or ell.numel() not in (1, d) or tuple(Q.shape) != (M, M) or tuple(R.shape) != (M, P):
         raise ValueError("sgp_kgrad: ell [1] or [d], Q [M, M], R [M, P] expected, got %s %s %s"
                          % (tuple(ell.shape), tuple(Q.shape), tuple(R.shape)))
-    if Y.dtype != X.dtype or any(t.dtype != torch.float64 for t in (z, ell, Q, R)):
-        raise TypeError("sgp_kgrad: X and Y share one storage dtype; z, ell, Q, R must be float64")
+    what = "X and Y share one storage dtype; z, ell, Q, R must be float64"
+    _operands("sgp_kgrad", X, Y, what=what)
+    _operands("sgp_kgrad", torch.float64, z, ell, Q, R, what=what)
     dev = X.device
     zbar = _empty((M, d), dtype=torch.float64, device=dev)
     ellbar = _empty((ell.numel(),), dtype=torch.float64, device=dev)
-    need = sgp_kgrad_ws_elems(N, M, d, P)
-    if ws is None:
-        ws = workspace(torch.float64, dev, max(need, 1))
-    if ws.dtype != torch.float64 or ws.numel() < need:
-        raise ValueError("sgp_kgrad: the workspace must hold %d float64 elements (sgp_kgrad_ws_elems)" % need)
+    ws = _ws("sgp_kgrad", ws, torch.float64, dev, sgp_kgrad_ws_elems(N, M, d, P), "sgp_kgrad_ws_elems")
     _lib.lib().call("hb_sgp_kgrad" + _suf(X), KERN_RBF, _p(X), _p(Y), _p(z), _p(ell), ell.numel(), _p(Q), _p(R), _p(zbar),
                     _p(ellbar), N, M, d, P, _p(ws), stream())
     return zbar, ellbar
@@ -2064,8 +2001,6 @@ def sgp_wkgrad(X, w, r, z, ell, Q, R, ws=None):
     in its storage dtype (float32 or float64); w [N], r [N], z [M, d], ell [dl], Q [M, M], R [M, 1] are float64 and all
     arithmetic is float64.  Returns (zbar [M, d], ellbar [dl]) as sgp_kgrad does; w == 1, r = Y[:, 0] returns its bits at
     P = 1; two calls on the same inputs return the same bits."""
-    for t in (X, w, r, z, ell, Q, R):
-        _chk(t)
     if X.dim() != 2 or z.dim() != 2 or X.shape[1] != z.shape[1] or tuple(w.shape) != (X.shape[0],) or tuple(r.shape) != w.shape:
         raise ValueError("sgp_wkgrad: X [N, d], w [N], r [N], z [M, d] expected, got %s %s %s %s"
                          % (tuple(X.shape), tuple(w.shape), tuple(r.shape), tuple(z.shape)))
@@ -2074,16 +2009,12 @@ def sgp_wkgrad(X, w, r, z, ell, Q, R, ws=None):
     if ell.dim() != 1 or ell.numel() not in (1, d) or tuple(Q.shape) != (M, M) or tuple(R.shape) != (M, 1):
         raise ValueError("sgp_wkgrad: ell [1] or [d], Q [M, M], R [M, 1] expected, got %s %s %s"
                          % (tuple(ell.shape), tuple(Q.shape), tuple(R.shape)))
-    if any(t.dtype != torch.float64 for t in (w, r, z, ell, Q, R)):
-        raise TypeError("sgp_wkgrad: X in its storage dtype; w, r, z, ell, Q, R must be float64")
+    _operands("sgp_wkgrad", X)
+    _operands("sgp_wkgrad", torch.float64, w, r, z, ell, Q, R, what="X in its storage dtype; w, r, z, ell, Q, R must be float64")
     dev = X.device
     zbar = _empty((M, d), dtype=torch.float64, device=dev)
     ellbar = _empty((ell.numel(),), dtype=torch.float64, device=dev)
-    need = sgp_kgrad_ws_elems(N, M, d, 1)
-    if ws is None:
-        ws = workspace(torch.float64, dev, max(need, 1))
-    if ws.dtype != torch.float64 or ws.numel() < need:
-        raise ValueError("sgp_wkgrad: the workspace must hold %d float64 elements (sgp_kgrad_ws_elems)" % need)
+    ws = _ws("sgp_wkgrad", ws, torch.float64, dev, sgp_kgrad_ws_elems(N, M, d, 1), "sgp_kgrad_ws_elems")
     _lib.lib().call("hb_sgp_wkgrad" + _suf(X), KERN_RBF, _p(X), _p(w), _p(r), _p(z), _p(ell), ell.numel(), _p(Q), _p(R),
                     _p(zbar), _p(ellbar), N, M, d, _p(ws), stream())
     return zbar, ellbar
@@ -2091,7 +2022,7 @@ def sgp_wkgrad(X, w, r, z, ell, Q, R, ws=None):
 
 def sgp_select_ws_elems(dtype, N, M, d):
     """Scratch elements hb_sgp_select needs: the history C [M, N], dvar [N] and the arg-max partials -- O(M N)."""
-    return int(_lib.lib().raw("hb_sgp_select_ws_elems")(int(N), int(M), int(d), _elem_bytes(dtype)))
+    return _query("hb_sgp_select_ws_elems", N, M, d, _elem_bytes(dtype))
 
 
 def sgp_select(X, ell, M, threshold=0.0, ws=None):
@@ -2103,13 +2034,10 @@ def sgp_select(X, ell, M, threshold=0.0, ws=None):
     -1 / 0), and the residual sum of conditional variances tr(K_XX - K_XZ K_ZZ^-1 K_ZX).  ell [1] or [d]; one expert.
     Two calls on the same inputs return the same bits.  The workspace is O(M N) elements (sgp_select_ws_elems): when
     `ws` is not given it is allocated for this call alone and released with it, not taken from the shared scratch."""
-    for t in (X, ell):
-        _chk(t)
     if X.dim() != 2 or ell.dim() != 1 or ell.numel() not in (1, X.shape[1]):
         raise ValueError("sgp_select: X [N, d] and ell [1] or [d] expected, got %s %s" % (tuple(X.shape), tuple(ell.shape)))
     dt, dev = X.dtype, X.device
-    if ell.dtype != dt:
-        raise TypeError("sgp_select: all operands must share one dtype")
+    _operands("sgp_select", X, ell)
     N, d = X.shape
     M = int(M)
     if not 1 <= M <= N:
@@ -2121,10 +2049,7 @@ def sgp_select(X, ell, M, threshold=0.0, ws=None):
     count = _empty((1,), dtype=torch.int64, device=dev)
     trace = _empty((1,), dtype=torch.float64, device=dev)
     need = sgp_select_ws_elems(dt, N, M, d)
-    if ws is None:
-        ws = _empty((need,), dtype=dt, device=dev)
-    if ws.dtype != dt or ws.numel() < need:
-        raise ValueError("sgp_select: the workspace must hold %d elements of %s (sgp_select_ws_elems)" % (need, dt))
+    ws = _ws("sgp_select", _empty((need,), dtype=dt, device=dev) if ws is None else ws, dt, dev, need, "sgp_select_ws_elems")
     _lib.lib().call("hb_sgp_select" + _suf(X), KERN_RBF, _p(X), _p(ell), ell.numel(), N, M, d, float(threshold), _p(idx),
                     _p(pivots), _p(count), _p(trace), _p(ws), stream())
     return idx, pivots, count, trace
@@ -2145,8 +2070,7 @@ def sgp_bwd(x, z, ell, W, u, eps, A, v, fbar, mode=SGP_DIAGONAL, need_xbar=False
         xbar = _empty((E, n, d), dtype=dt, device=dev) if need_xbar else None
     else:
         Kbar, Lbar, ubar, zbar, ellbar, xbar = out
-    wse = _lib.lib().raw("hb_sgp_ws_elems")(E, n, M, d, P)
-    ws = workspace(dt, dev, wse)
+    ws = workspace(dt, dev, sgp_ws_elems(E, n, M, d, P))
     if a_frag is not None and kbar_frag is None:
         kbar_frag = _empty(a_frag.numel(), dtype=dt, device=dev)
     _lib.lib().call("hb_sgp_bwd" + _suf(x), KERN_RBF, mode, _p(x), sx, _p(z), _p(ell), dl, _p(W), _p(wfrag), int(prec), _p(u), _p(eps),
@@ -2158,7 +2082,7 @@ def sgp_bwd(x, z, ell, W, u, eps, A, v, fbar, mode=SGP_DIAGONAL, need_xbar=False
 def sgp_bwd_phi_supported(E, n, M, d, P):
     """True when sgp_bwd_phi serves this shape (column-strip form in native precision) and the diagnostic switch
     sgp_phi_direct is not 0.  The planner asks when it builds a plan."""
-    return bool(_lib.lib().raw("hb_sgp_bwd_phi_supported")(E, n, M, d, P))
+    return bool(_query("hb_sgp_bwd_phi_supported", E, n, M, d, P))
 
 
 def sgp_bwd_phi(x, z, ell, W, u, eps, v, fbar, wfrag, a_frag, mode=SGP_DIAGONAL, out=None, abar_frag=None):
@@ -2166,16 +2090,16 @@ def sgp_bwd_phi(x, z, ell, W, u, eps, v, fbar, wfrag, a_frag, mode=SGP_DIAGONAL,
     triangles) instead of Lbar: hb_sgp_bwd_phi_f32.  fp32, fragment-major W and A.  Returns (Phi, ubar, zbar, ellbar)."""
     E, n, M, d, P, sx = _sgp_dims(x, z, u)
     dev, dt = x.device, x.dtype
-    assert dt == torch.float32 and wfrag is not None and a_frag is not None
+    _require(dt == torch.float32 and wfrag is not None and a_frag is not None, "sgp_bwd_phi", "float32 operands, wfrag and a_frag expected")
     dl = ell.numel() // E
     if out is None:
         Phi, ubar, zbar, ellbar = _empty_like(W), _empty_like(u), _empty_like(z), _empty_like(ell)
     else:
         Phi, ubar, zbar, ellbar = out
-    ws = workspace(dt, dev, _lib.lib().raw("hb_sgp_ws_elems")(E, n, M, d, P))
+    ws = workspace(dt, dev, sgp_ws_elems(E, n, M, d, P))
     if abar_frag is None:
         abar_frag = _empty(a_frag.numel(), dtype=dt, device=dev)
-    assert abar_frag.numel() >= sgp_frag_elems(E, n, M)
+    _ws("sgp_bwd_phi", abar_frag, dt, dev, sgp_frag_elems(E, n, M), "sgp_frag_elems", "abar_frag")
     _lib.lib().call("hb_sgp_bwd_phi_f32", KERN_RBF, mode, _p(x), sx, _p(z), _p(ell), dl, _p(W), _p(wfrag), _p(u), _p(eps), _p(a_frag),
                     _p(v), _p(fbar), _p(abar_frag), _p(Phi), _p(ubar), _p(zbar), _p(ellbar), E, n, M, d, P, _p(ws), stream())
     return Phi, ubar, zbar, ellbar
@@ -2187,15 +2111,15 @@ def adam_step(theta, g, m, v, t, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8, gscale=1.0
     """In-place TF-1 Adam on flat buffers; `t` is a 1-element int64 device tensor (advanced when `tick`).
     `info` (int32 status words of this step's factorisations), `dpflag` (one element of theta's dtype: the
     all-reduced failure flag) and `fail` (int64[2], sticky) make the update a no-op when a factorisation failed."""
-    assert t.dtype == torch.int64
+    _require(t.dtype == torch.int64, "adam_step", "t must be int64")
     n_info = 0
     if info is not None:
-        assert info.dtype == torch.int32 and info.is_contiguous()
+        _require(info.dtype == torch.int32 and info.is_contiguous(), "adam_step", "info must be contiguous int32")
         n_info = info.numel()
     if fail is not None:
-        assert fail.dtype == torch.int64 and fail.numel() == 2
+        _require(fail.dtype == torch.int64 and fail.numel() == 2, "adam_step", "fail must be int64 [2]")
     if dpflag is not None:
-        assert dpflag.dtype == theta.dtype and dpflag.numel() == 1
+        _require(dpflag.dtype == theta.dtype and dpflag.numel() == 1, "adam_step", "dpflag must be one element of theta's dtype")
     _lib.lib().call("hb_adam_step" + _suf(theta), _p(theta), _p(g), _p(m), _p(v), theta.numel(), float(lr), float(b1),
                     float(b2), float(eps), float(gscale), _p(t), int(bool(tick)), _p(info) if n_info else None, n_info,
                     _p(dpflag) if dpflag is not None else None, _p(fail) if fail is not None else None, stream())
@@ -2210,7 +2134,7 @@ def allreduce_sum(flat, comm_handle):
 
 def dp_pack(tail, objective, info):
     """tail[0] = objective, tail[1] = any(info != 0)  (hb_dp_pack)."""
-    assert tail.numel() == 2
+    _require(tail.numel() == 2, "dp_pack", "tail must hold 2 elements")
     n_info = 0 if info is None else info.numel()
     _lib.lib().call("hb_dp_pack" + _suf(tail), _p(tail), _p(objective), _p(info) if n_info else None, n_info, stream())
 

@@ -4,6 +4,7 @@ setting).  Host code only: no GPU is needed.  Two builds compute the same rules 
 byte-identical:
 
     python tools/form_rules_table.py | sha256sum
+    python tools/form_rules_table.py --ws | sha256sum      (the workspace size rules alone: the last section of the table)
 
 Rules a planner once restated in Python are compared against that restatement: where `hip_ops` has no query for one
 (an older build), the expression the planner used then stands in for it, verbatim.
@@ -85,8 +86,47 @@ def rows():
             yield "matmul_wgk_shape", (M, N, K, B), int(bool(_wgk_shape(M, N, K, B)))
 
 
+# the grid of the workspace size rules: every branch of the column-chunk rule (n = 0, below / at / above one strip of 32,
+# at / above the 32768-column cap, beyond the element budget), both element sizes, with and without Wfrag
+WS_NS = (0, 1, 31, 32, 33, 32768, 32769, 100000)
+WS_MS = (32, 48, 512, 1024)
+WS_PS = (1, 4, 5)
+WS_CS = (1, 3)
+WS_DS = (2, 5)
+WS_ES = (1, 2)
+WS_BYTES = (4, 8)
+
+
+def ws_rows():
+    """Every exported *_ws_elems rule of the chunked sparse-GP entries, asked through the C exports themselves (so that
+    any build answers, whatever its `hip_ops` wraps)."""
+    raw = _lib.lib().raw
+    q = lambda name, *a: (name, a, int(raw("hb_" + name)(*a)))
+    sks = (H.SGP_S_DIAG, H.SGP_S_TRIL)
+    for n, M, d in itertools.product(WS_NS, WS_MS, WS_DS):
+        for es in WS_BYTES:
+            for P in WS_PS:
+                yield q("sgp_stats_ws_elems", n, M, d, P, es)
+            yield q("sgp_wstats_ws_elems", n, M, d, es)
+            for C in WS_CS:
+                yield q("sgp_mwstats_ws_elems", n, M, d, C, es)
+            yield q("sgp_select_ws_elems", n, M, d, es)
+            for sk, wf in itertools.product(sks, (0, 1)):
+                yield q("sgp_predict_grad_ws_elems", n, M, d, sk, wf, es)
+                yield q("sgp_acq_ws_elems", n, M, d, sk, wf, es)
+                for E, P in itertools.product(WS_ES, WS_PS):
+                    yield q("sgp_predict_ws_elems", E, n, M, d, P, sk, wf, es)
+            for E, P, sk in itertools.product(WS_ES, WS_PS, sks):
+                yield q("sgp_predict_cov_ws_elems", E, n, M, P, sk, es)
+        for P in WS_PS:
+            yield q("sgp_kgrad_ws_elems", n, M, d, P)
+
+
 def main():
     out = sys.stdout
+    if "--ws" in sys.argv:   # the workspace size rules alone
+        out.write("".join("ws %s %s %d\n" % (name, ",".join(map(str, args)), val) for name, args, val in ws_rows()))
+        return
     for sw in SWITCHES:
         H.debug_clear()
         tag = "default"
@@ -103,6 +143,7 @@ def main():
             out.write("".join(buf))
         finally:
             H.debug_clear()
+    out.write("".join("ws %s %s %d\n" % (name, ",".join(map(str, args)), val) for name, args, val in ws_rows()))
 
 
 if __name__ == "__main__":
