@@ -16,6 +16,8 @@
 // and the predictive log density log E p(y_j | f) of all seven (hb_lik_logdens_*).
 // sum_j l_j: every block folds its threads' terms (a grid-stride loop, a fixed grid for a given N) into one partial, a
 // second launch of one block adds the partials in block order.  No atomics: two runs give the same bits.
+// HB_LIK_HETGAUSS (y ~ N(f, exp(g + c)), two latent functions) has entries of its own at the end of the file
+// (hb_lik_hetgauss_*); the one-latent entries refuse its id as they refuse HB_LIK_SOFTMAX.
 #include "common.cuh"
 #include "../../include/henbun_hip.h"
 
@@ -433,6 +435,7 @@ static inline long lk_blocks(long N) {
 static inline bool lk_has_own_param(int lik) { return lik >= HB_LIK_LAPLACE && lik <= HB_LIK_BINOMIAL; }
 
 static int lk_check(const char* who, int lik, long N, double param) {
+  HB_REQUIRE(lik != HB_LIK_HETGAUSS, "%s: HB_LIK_HETGAUSS has two latent functions: use hb_lik_hetgauss_*", who);
   HB_REQUIRE(lik == HB_LIK_GAUSSIAN || lik == HB_LIK_BERNOULLI || lik == HB_LIK_POISSON || lk_has_own_param(lik),
              "%s: unknown likelihood id %d", who, lik);
   HB_REQUIRE(N >= 0, "%s: negative N (%ld)", who, N);
@@ -525,6 +528,167 @@ static int lik_logdens(int lik, const T* y, const T* mean, const T* var, double 
   return 0;
 }
 
+// ------------------------------------------------------------------ heteroscedastic Gaussian: y ~ N(f, exp(g + c))
+// Closed forms throughout (the header has them).  e = exp(-mu_g - c + v_g / 2) overflows double only past an argument of
+// 709; the outputs then saturate (lk_out) or are inf in double, as the Poisson moments do.
+template <typename T>
+__global__ void __launch_bounds__(LK_THREADS) lik_hetgauss_sites_kernel(const T* __restrict__ y, const T* __restrict__ mean,
+                                                                        const T* __restrict__ var, long ld, double mscale,
+                                                                        double vscale, double c, T* __restrict__ lam,
+                                                                        T* __restrict__ beta, T* __restrict__ r,
+                                                                        double* __restrict__ partial, long N) {
+  __shared__ double red[16];
+  const long stride = (long)gridDim.x * LK_THREADS;
+  double s = 0.0;
+  for (long j = (long)blockIdx.x * LK_THREADS + threadIdx.x; j < N; j += stride) {
+    const double mf = mscale * (double)mean[j], vf = vscale * (double)var[j];
+    const double mg = mscale * (double)mean[ld + j], vg = vscale * (double)var[ld + j];
+    const double dy = (double)y[j] - mf, sq = dy * dy + vf, e = exp(-mg - c + 0.5 * vg), hse = 0.5 * (sq * e);
+    const double rf = dy * e, rg = -0.5 + hse;
+    lam[j] = lk_out<T>(e);
+    lam[ld + j] = lk_out<T>(hse);
+    beta[j] = lk_out<T>(rf + e * mf);
+    beta[ld + j] = lk_out<T>(rg + hse * mg);
+    if (r) {
+      r[j] = lk_out<T>(rf);
+      r[ld + j] = lk_out<T>(rg);
+    }
+    s += -0.91893853320467274178 - 0.5 * (mg + c) - hse;
+  }
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(LK_THREADS) lik_hetgauss_predict_kernel(const T* __restrict__ mean, const T* __restrict__ var,
+                                                                          long ld, double c, T* __restrict__ ymean,
+                                                                          T* __restrict__ yvar, long N) {
+  const long stride = (long)gridDim.x * LK_THREADS;
+  for (long j = (long)blockIdx.x * LK_THREADS + threadIdx.x; j < N; j += stride) {
+    ymean[j] = lk_out<T>((double)mean[j]);
+    yvar[j] = lk_out<T>((double)var[j] + exp((double)mean[ld + j] + c + 0.5 * (double)var[ld + j]));
+  }
+}
+
+// log sum_i w_i N(y; mu_f, v_f + exp(mu_g + c + sqrt(2 v_g) x_i)), by log-sum-exp over the nodes
+__device__ __forceinline__ double lk_hetgauss_logdens(double y, double mf, double vf, double mg, double vg, double c) {
+  const double dy = y - mf, sd = sqrt(2.0 * vg), m0 = mg + c;
+  double lp[LK_GH], top = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < LK_GH; ++i) {
+    const double tot = vf + exp(m0 + sd * LK_X[i]);
+    const double val = -0.5 * log(6.283185307179586477 * tot) - (dy * dy) / (2.0 * tot);
+    lp[i] = val;
+    top = val > top ? val : top;
+  }
+  if (!(top > -INFINITY)) return top + lp[0];   // every node at -inf, or a NaN input: NaN is passed on
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < LK_GH; ++i) s += LK_W[i] * exp(lp[i] - top);
+  return top + log(s);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(LK_THREADS) lik_hetgauss_logdens_kernel(const T* __restrict__ y, const T* __restrict__ mean,
+                                                                          const T* __restrict__ var, long ld, double mscale,
+                                                                          double vscale, double c, T* __restrict__ out,
+                                                                          double* __restrict__ partial, long N) {
+  __shared__ double red[16];
+  const long stride = (long)gridDim.x * LK_THREADS;
+  double s = 0.0;
+  for (long j = (long)blockIdx.x * LK_THREADS + threadIdx.x; j < N; j += stride) {
+    const double l = lk_hetgauss_logdens((double)y[j], mscale * (double)mean[j], vscale * (double)var[j],
+                                         mscale * (double)mean[ld + j], vscale * (double)var[ld + j], c);
+    if (out) out[j] = lk_out<T>(l);
+    s += l;
+  }
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+static int lk_hetgauss_check(const char* who, long N, long ld, double c, double vscale) {
+  HB_REQUIRE(N >= 0, "%s: negative N (%ld)", who, N);
+  HB_REQUIRE(ld >= N, "%s: the rows must be at least N apart (ld=%ld, N=%ld)", who, ld, N);
+  HB_REQUIRE(c == c && c - c == 0.0, "%s: the mean of the log variance must be finite (got %g)", who, c);
+  HB_REQUIRE(vscale >= 0.0, "%s: vscale must not be negative (got %g)", who, vscale);
+  return 0;
+}
+
+extern "C" long hb_lik_hetgauss_ws_elems(long N) { return N > 0 ? lk_blocks(N) : 1; }
+
+template <typename T>
+static int lik_hetgauss_sites(const T* y, const T* mean, const T* var, long ld, double mscale, double vscale, double c, T* lam,
+                              T* beta, T* r, double* ell_sum, long N, double* ws, hipStream_t st) {
+  if (lk_hetgauss_check("hb_lik_hetgauss_sites", N, ld, c, vscale)) return -1;
+  HB_REQUIRE(ell_sum && ws, "hb_lik_hetgauss_sites: NULL output / workspace pointer");
+  HB_REQUIRE(N == 0 || (y && mean && var && lam && beta), "hb_lik_hetgauss_sites: NULL pointer");
+  const long nb = N > 0 ? lk_blocks(N) : 0;
+  if (nb > 0) {
+    hipLaunchKernelGGL((lik_hetgauss_sites_kernel<T>), dim3((unsigned)nb), dim3(LK_THREADS), 0, st, y, mean, var, ld, mscale,
+                       vscale, c, lam, beta, r, ws, N);
+    HB_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(lik_sites_fold_kernel, dim3(1), dim3(LK_THREADS), 0, st, ws, nb, ell_sum);
+  HB_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T>
+static int lik_hetgauss_predict(const T* mean, const T* var, long ld, double c, T* ymean, T* yvar, long N, hipStream_t st) {
+  if (lk_hetgauss_check("hb_lik_hetgauss_predict", N, ld, c, 0.0)) return -1;
+  if (N == 0) return 0;
+  HB_REQUIRE(mean && var && ymean && yvar, "hb_lik_hetgauss_predict: NULL pointer");
+  hipLaunchKernelGGL((lik_hetgauss_predict_kernel<T>), dim3((unsigned)lk_blocks(N)), dim3(LK_THREADS), 0, st, mean, var, ld, c,
+                     ymean, yvar, N);
+  HB_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T>
+static int lik_hetgauss_logdens(const T* y, const T* mean, const T* var, long ld, double mscale, double vscale, double c, T* out,
+                                double* sum, long N, double* ws, hipStream_t st) {
+  if (lk_hetgauss_check("hb_lik_hetgauss_logdens", N, ld, c, vscale)) return -1;
+  HB_REQUIRE(sum && ws, "hb_lik_hetgauss_logdens: NULL output / workspace pointer");
+  HB_REQUIRE(N == 0 || (y && mean && var), "hb_lik_hetgauss_logdens: NULL pointer");
+  const long nb = N > 0 ? lk_blocks(N) : 0;
+  if (nb > 0) {
+    hipLaunchKernelGGL((lik_hetgauss_logdens_kernel<T>), dim3((unsigned)nb), dim3(LK_THREADS), 0, st, y, mean, var, ld, mscale,
+                       vscale, c, out, ws, N);
+    HB_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(lik_sites_fold_kernel, dim3(1), dim3(LK_THREADS), 0, st, ws, nb, sum);
+  HB_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int hb_lik_hetgauss_sites_f32(const float* y, const float* mean, const float* var, long ld, double mscale,
+                                         double vscale, double param, float* lam, float* beta, float* r, double* ell_sum,
+                                         long N, double* ws, void* stream) {
+  return lik_hetgauss_sites<float>(y, mean, var, ld, mscale, vscale, param, lam, beta, r, ell_sum, N, ws, (hipStream_t)stream);
+}
+extern "C" int hb_lik_hetgauss_sites_f64(const double* y, const double* mean, const double* var, long ld, double mscale,
+                                         double vscale, double param, double* lam, double* beta, double* r, double* ell_sum,
+                                         long N, double* ws, void* stream) {
+  return lik_hetgauss_sites<double>(y, mean, var, ld, mscale, vscale, param, lam, beta, r, ell_sum, N, ws, (hipStream_t)stream);
+}
+extern "C" int hb_lik_hetgauss_predict_f32(const float* mean, const float* var, long ld, double param, float* ymean,
+                                           float* yvar, long n, void* stream) {
+  return lik_hetgauss_predict<float>(mean, var, ld, param, ymean, yvar, n, (hipStream_t)stream);
+}
+extern "C" int hb_lik_hetgauss_predict_f64(const double* mean, const double* var, long ld, double param, double* ymean,
+                                           double* yvar, long n, void* stream) {
+  return lik_hetgauss_predict<double>(mean, var, ld, param, ymean, yvar, n, (hipStream_t)stream);
+}
+extern "C" int hb_lik_hetgauss_logdens_f32(const float* y, const float* mean, const float* var, long ld, double mscale,
+                                           double vscale, double param, float* out, double* sum, long N, double* ws,
+                                           void* stream) {
+  return lik_hetgauss_logdens<float>(y, mean, var, ld, mscale, vscale, param, out, sum, N, ws, (hipStream_t)stream);
+}
+extern "C" int hb_lik_hetgauss_logdens_f64(const double* y, const double* mean, const double* var, long ld, double mscale,
+                                           double vscale, double param, double* out, double* sum, long N, double* ws,
+                                           void* stream) {
+  return lik_hetgauss_logdens<double>(y, mean, var, ld, mscale, vscale, param, out, sum, N, ws, (hipStream_t)stream);
+}
 extern "C" int hb_lik_param_grad_f32(int lik, const float* y, const float* mean, const float* var, double mscale, double vscale,
                                      double param, double* out, long N, double* ws, void* stream) {
   return lik_param_grad<float>(lik, y, mean, var, mscale, vscale, param, out, N, ws, (hipStream_t)stream);

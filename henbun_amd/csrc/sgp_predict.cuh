@@ -10,6 +10,7 @@
 
 #define PRED_THREADS 512          // 8 waves; wave w owns the row tiles w and nT - 1 - w (balanced triangular work)
 #define PRED_PMAX 4               // latent functions whose means / variances the fused form keeps per thread
+#define HB_PRED_MULTI_CMAX 64     // latent functions of one hb_sgp_predict_multi_* call (at most)
 #define PRED_RED_LD 260           // floats per column in the fold of the S^T A statistics (8 waves x 32 lanes + 4)
 #define HB_PRED_CHUNK 32768L      // columns per chunk of the chunked form (at most)
 #define HB_PRED_CHUNK_ELEMS (1L << 24)  // scratch of one chunk (elements, at most): A chunk + S^T A chunk
@@ -117,24 +118,24 @@ struct PredMoments {
   }
 };
 
-// Phases 1-3 of a 32-column strip (blockIdx.x = strip, expert e) on the workgroup's buffers Ks, As [SGP_SN * SGP_SLD]
-// and zs [SGP_SM_MAX * D]:
-//   phase 1: K(z, x_strip) -> Ks[column][k];  A_strip = W K -> As[column][m]   (MFMA, W image)
-//   phase 2: per column: sum A^2, m_p^T A, sum s_p^2 A^2      (16 threads per column, fixed order)
-//   phase 3 (full rank): C = S^T A_strip (MFMA, S^T image), per-lane sums of C^2 folded through LDS; every finished
-//            tile of C is also handed to tileC(tile, acc)
-// On return As holds A_strip, zs holds z, and Ks (its first SGP_SN * PRED_RED_LD floats the fold buffer of phase 3) is
-// dead once every thread has passed a barrier.
-template <int D, typename TileC>
-__device__ __forceinline__ void pred_strip_moments(const PredArgs& a, float* Ks, float* As, float* zs, long e, PredMoments& o,
-                                                   TileC tileC) {
+// The phases of a 32-column strip (blockIdx.x = strip, expert e) on the workgroup's buffers Ks, As [SGP_SN * SGP_SLD] and
+// zs [SGP_SM_MAX * D], one function each so that every kernel that reports a mean or a variance runs the same code:
+//   pred_strip_A       phase 1: K(z, x_strip) -> Ks[column][k];  A_strip = W K -> As[column][m]   (MFMA, W image)
+//   pred_strip_colsums phase 2: per column: sum A^2, m_p^T A, sum s_p^2 A^2      (16 threads per column, fixed order)
+//   pred_strip_c2      phase 3 (full rank): C = S^T A_strip (MFMA, S^T image), per-lane sums of C^2 into the fold buffer
+//                      that overlays the dead K block; every finished tile of C is also handed to tileC(tile, acc)
+//   pred_strip_c2_fold the column's share of that fold;  pred_col_tree the fixed-order tree over a column's 16 threads
+// pred_strip_moments runs them for one set of at most PRED_PMAX latent functions (one S); csrc/sgp_predict.hip's
+// multi-latent kernel runs phase 1 once, phase 2 per group of PRED_PMAX means and phase 3 per latent function.
+template <int D>
+__device__ __forceinline__ void pred_strip_A(const PredArgs& a, float* Ks, float* As, float* zs, long e) {
   typedef float V4 __attribute__((ext_vector_type(4)));
   static_assert(SGP_SN * PRED_RED_LD <= SGP_SN * SGP_SLD, "the fold buffer overlays the K block");
   const int bx = blockIdx.x;
   const float* __restrict__ x = a.x + e * a.sx;
   const float* __restrict__ z = a.z + e * a.M * D;
   const float* __restrict__ ell = a.ell + e * a.dl;
-  const int M = (int)a.M, n = (int)a.n, P = (int)a.P;
+  const int M = (int)a.M, n = (int)a.n;
   const int col0 = bx * SGP_SN;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 31, h = lane >> 5;
   const int nT = M / 32;
@@ -161,27 +162,41 @@ __device__ __forceinline__ void pred_strip_moments(const PredArgs& a, float* Ks,
     for (int r = 0; r < 16; ++r) As[pred_acc_col(r, h) * SGP_SLD + 32 * tile + li] = acc[r];
   });
   __syncthreads();
+}
 
-  // ---- phase 3 (full rank, E P == 1): C = S^T A_strip; per-lane sums of C^2 in accumulator order
-  if (a.STf) {
-    float csq[16];
+// phase 3 for the S^T image STf: C = S^T A_strip; per-lane sums of C^2 in accumulator order, left in the fold buffer (the
+// first SGP_SN * PRED_RED_LD floats of Ks: 256 (wave, row-lane) partials per column).  The caller owns the barriers: none
+// of Ks may still be read when this starts, and a barrier stands between it and pred_strip_c2_fold.
+template <typename TileC>
+__device__ __forceinline__ void pred_strip_c2(const float* __restrict__ STf, const float* As, float* Ks, int nT, int w, int lane,
+                                              TileC tileC) {
+  const int li = lane & 31, h = lane >> 5;
+  float csq[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) csq[r] = 0.f;
-    pred_strip_product<true>(a.STf, As, nT, w, lane, [&](int tile, const Mma<float>::Acc& acc) {
+  for (int r = 0; r < 16; ++r) csq[r] = 0.f;
+  pred_strip_product<true>(STf, As, nT, w, lane, [&](int tile, const Mma<float>::Acc& acc) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) csq[r] = __builtin_fmaf(acc[r], acc[r], csq[r]);
-      tileC(tile, acc);
-    });
-    // the K block is dead since the barrier above: it takes the fold of the 256 (wave, row-lane) partials per column
+    for (int r = 0; r < 16; ++r) csq[r] = __builtin_fmaf(acc[r], acc[r], csq[r]);
+    tileC(tile, acc);
+  });
 #pragma unroll
-    for (int r = 0; r < 16; ++r) Ks[pred_acc_col(r, h) * PRED_RED_LD + 32 * w + li] = csq[r];
-  }
+  for (int r = 0; r < 16; ++r) Ks[pred_acc_col(r, h) * PRED_RED_LD + 32 * w + li] = csq[r];
+}
 
-  // ---- phase 2: column statistics from As; 16 threads per column, rows g, g + 16, ...
-  const int c = tid >> 4, g = tid & 15;
-  const float* mp = a.m + e * a.P * a.M;
-  const float* sp = a.s ? a.s + e * a.P * a.M : nullptr;
-  float sa2 = 0.f, mu[PRED_PMAX], ss[PRED_PMAX];
+// thread (c, g)'s share of column c's fold: 16 of its 256 partials, in order
+__device__ __forceinline__ float pred_strip_c2_fold(const float* Ks, int c, int g) {
+  float csum = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) csum += Ks[c * PRED_RED_LD + 16 * g + i];
+  return csum;
+}
+
+// phase 2: thread (c, g)'s share (rows g, g + 16, ...) of column c's statistics for P <= PRED_PMAX means mp [P, M] and,
+// with sp (diagonal S), standard deviations sp [P, M]
+__device__ __forceinline__ void pred_strip_colsums(const float* As, const float* __restrict__ mp, const float* __restrict__ sp,
+                                                   int M, int P, int c, int g, float& sa2, float (&mu)[PRED_PMAX],
+                                                   float (&ss)[PRED_PMAX]) {
+  sa2 = 0.f;
 #pragma unroll
   for (int p = 0; p < PRED_PMAX; ++p) mu[p] = 0.f, ss[p] = 0.f;
   for (int k = g; k < M; k += 16) {
@@ -191,43 +206,55 @@ __device__ __forceinline__ void pred_strip_moments(const PredArgs& a, float* Ks,
     for (int p = 0; p < PRED_PMAX; ++p) {
       if (p < P) {
         mu[p] = __builtin_fmaf(mp[(long)p * M + k], av, mu[p]);
-        if (!a.STf) {
+        if (sp) {
           const float t = sp[(long)p * M + k] * av;
           ss[p] = __builtin_fmaf(t, t, ss[p]);
         }
       }
     }
   }
+}
+
+// fixed-order tree over the 16 threads of a column (lanes 16 c' .. 16 c' + 15 of a wave): every one ends with the sum
+__device__ __forceinline__ float pred_col_tree(float v) {
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 16);
+  return v;
+}
+
+// On return As holds A_strip, zs holds z, and Ks (its first SGP_SN * PRED_RED_LD floats the fold buffer of phase 3) is
+// dead once every thread has passed a barrier.
+template <int D, typename TileC>
+__device__ __forceinline__ void pred_strip_moments(const PredArgs& a, float* Ks, float* As, float* zs, long e, PredMoments& o,
+                                                   TileC tileC) {
+  const int M = (int)a.M, P = (int)a.P;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  pred_strip_A<D>(a, Ks, As, zs, e);
+  // (the K block is dead since the barrier that ends phase 1: it takes the fold of phase 3)
+  if (a.STf) pred_strip_c2(a.STf, As, Ks, M / 32, w, lane, tileC);
+  const int c = tid >> 4, g = tid & 15;
+  float sa2, mu[PRED_PMAX], ss[PRED_PMAX];
+  pred_strip_colsums(As, a.m + e * a.P * a.M, a.STf ? nullptr : a.s + e * a.P * a.M, M, P, c, g, sa2, mu, ss);
   float csum = 0.f;
   if (a.STf) {
     __syncthreads();   // every wave's C^2 partials are in the fold buffer
-#pragma unroll
-    for (int i = 0; i < 16; ++i) csum += Ks[c * PRED_RED_LD + 16 * g + i];
+    csum = pred_strip_c2_fold(Ks, c, g);
   }
-  // fixed-order tree over the 16 threads of the column (lanes 16 c' .. 16 c' + 15 of a wave): every one ends with the sum
+  o.sa2 = pred_col_tree(sa2), o.csum = pred_col_tree(csum);
 #pragma unroll
-  for (int off = 8; off > 0; off >>= 1) {
-    sa2 += __shfl_xor(sa2, off, 16);
-    csum += __shfl_xor(csum, off, 16);
-#pragma unroll
-    for (int p = 0; p < PRED_PMAX; ++p) {
-      mu[p] += __shfl_xor(mu[p], off, 16);
-      ss[p] += __shfl_xor(ss[p], off, 16);
-    }
-  }
-  o.sa2 = sa2, o.csum = csum;
-#pragma unroll
-  for (int p = 0; p < PRED_PMAX; ++p) o.mu[p] = mu[p], o.ss[p] = ss[p];
+  for (int p = 0; p < PRED_PMAX; ++p) o.mu[p] = pred_col_tree(mu[p]), o.ss[p] = pred_col_tree(ss[p]);
 }
 
 // Fragment-major image of a triangular factor for the full-rank fused forms, in the layout of Wfrag (csrc/linalg.hip,
 // tril_inplace_kernel): element (t, Q, v, lane = (li, h), s) = X[32 t + li][32 Q + 16 h + 4 v + s], r = 32 t + li,
 // k = 32 Q + ..., with X = S^T (TRANS: S[k][r], zero where k < r) or X = S (S[r][k], zero where k > r); only the lower
-// triangle of S is read.
+// triangle of S is read.  blockIdx.y = which of gridDim.y matrices S [gridDim.y, M, M] (one image each, M^2 apart).
 template <bool TRANS>
 __global__ void __launch_bounds__(256) pred_s_image_kernel(const float* __restrict__ S, float* __restrict__ Xf, long M) {
   const int Mi = (int)M, nT = Mi / 32;
   const long total = M * M, stride = (long)gridDim.x * blockDim.x;
+  S += blockIdx.y * total;
+  Xf += blockIdx.y * total;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
     const int rem = (int)t;
     const int s = rem & 3, lane = (rem >> 2) & 63, v = (rem >> 8) & 3, blk = rem >> 10;

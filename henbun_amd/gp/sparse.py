@@ -42,10 +42,11 @@ def _check_lik_inputs(who, likelihood, k_var, residual, q, Yd, M):
     return m0, S0
 
 
-def _check_blocks_and_labels(who, name, C, q, Y):
-    """The host-side checks of a multi-latent route on q = (m [C, M], S [C, M, M]) (None: not given) and on a numpy Y of
-    labels [N, 1] in 0 .. C-1 (labels already on the device are the caller's duty).  Returns (m, S) as float64 numpy, or
-    (None, None)."""
+def _check_blocks_and_targets(who, name, likelihood, q, Y):
+    """The host-side checks of a multi-latent route on q = (m [C, M], S [C, M, M]) (None: not given) and on a numpy Y
+    [N, 1] of targets, by the likelihood's own rule (Softmax: labels in 0 .. C-1; HeteroscedasticGaussian: finite numbers;
+    targets already on the device are the caller's duty).  Returns (m, S) as float64 numpy, or (None, None)."""
+    C = int(likelihood.num_latent)
     m0 = S0 = None
     if q is not None:
         m0, S0 = (np.asarray(a, dtype=np.float64) for a in q)
@@ -55,10 +56,7 @@ def _check_blocks_and_labels(who, name, C, q, Y):
         if m0.ndim != 2 or m0.shape[0] != C or S0.shape != (C, m0.shape[1], m0.shape[1]):
             raise ValueError("%s: %s = (m [%d, M], S [%d, M, M]) expected, got %s %s" % (who, name, C, C, m0.shape, S0.shape))
     if isinstance(Y, np.ndarray):
-        if Y.ndim != 2 or Y.shape[1] != 1:
-            raise ValueError("%s: Y must hold the labels as [N, 1], got %s" % (who, Y.shape))
-        if not (np.all(Y == np.floor(Y)) and Y.size and Y.min() >= 0 and Y.max() <= C - 1):
-            raise ValueError("%s: the labels must be integers in 0 .. %d" % (who, C - 1))
+        likelihood.check_targets(who, Y)
     return m0, S0
 
 
@@ -242,8 +240,8 @@ class SparseInference:
         is not guaranteed to raise the ELBO from a q far from the optimum (info['elbo'] shows an overshoot): start at
         the prior or damp with rho < 1.
 
-        A likelihood with num_latent = C > 1 (likelihoods.Softmax) fits C independent q(u_c) that share z, the
-        lengthscales and W: see _natgrad_q_multi for its Y, q0 and return shapes."""
+        A likelihood with num_latent = C > 1 (likelihoods.Softmax, likelihoods.HeteroscedasticGaussian) fits C
+        independent q(u_c) that share z, the lengthscales and W: see _natgrad_q_multi for its Y, q0 and return shapes."""
         if getattr(likelihood, "num_latent", 1) > 1:
             return self._natgrad_q_multi(X, Y, likelihood, k_var, residual, q0, steps, rho, tol)
         sess, zvar, ls = self._stats_session("natgrad_q")
@@ -307,7 +305,12 @@ class SparseInference:
         info) as float64 numpy, info as for one latent function.  The ELBO is a fixed-node sum and lam is Price's form, not
         the derivative of that sum: from step to step the ELBO can wiggle by about 1e-4 near the fixed point.  A full step
         (rho = 1) does not settle (it cycles or diverges, see likelihoods.Softmax); the likelihood's natgrad_rho (0.5) is
-        what models.SVGPMulticlass passes.  residual 'fullrank' and a mean-field q0 raise NotImplementedError, other shapes ValueError."""
+        what models.SVGPMulticlass passes.  residual 'fullrank' and a mean-field q0 raise NotImplementedError, other shapes ValueError.
+
+        The target check, the sites launch and whether the marginals come from one pass are the likelihood's
+        (likelihoods.Likelihood.check_targets / multi_sites / fused_marginals).  likelihoods.HeteroscedasticGaussian
+        (C = 2, Y [N, 1] real): per step ONE hb_sgp_predict_multi (A formed once for both latent functions), ONE
+        hb_lik_hetgauss_sites and ONE hb_sgp_mwstats; its expectation is exact, so the ELBO has no node wiggle."""
         who = "natgrad_q"
         _check_residual(residual)
         if not isinstance(likelihood, Likelihood):
@@ -318,13 +321,13 @@ class SparseInference:
         k_var, rho, steps = float(k_var), float(rho), int(steps)
         if not (0.0 < rho <= 1.0 and steps >= 0):
             raise ValueError("%s: 0 < rho <= 1 and steps >= 0 expected (got %r, %r)" % (who, rho, steps))
-        m0, S0 = _check_blocks_and_labels(who, "q0", C, q0, Y)
+        m0, S0 = _check_blocks_and_targets(who, "q0", likelihood, q0, Y)
         sess, zvar, ls = self._stats_session(who)
         torch, H = sess.torch, sess.H
         Xd, Yd = _host.device_data(sess, X, "X"), _host.device_data(sess, Y, "Y")
         M = int(zvar.shape[0])
         if Yd.dim() != 2 or Yd.shape[1] != 1:
-            raise ValueError("%s: Y must hold the labels as [N, 1], got %s" % (who, tuple(Yd.shape)))
+            raise ValueError("%s: Y must hold the targets as [N, 1], got %s" % (who, tuple(Yd.shape)))
         if q0 is not None and m0.shape[1] != M:
             raise ValueError("%s: q0 = (m [%d, %d], S [%d, %d, %d]) expected, got %s %s" % (who, C, M, C, M, M, m0.shape, S0.shape))
         z, ell, W, frag = self._whitening(sess, zvar, ls, Xd, Yd, who, as_plans=True)
@@ -340,11 +343,13 @@ class SparseInference:
                 Sinv = H.trinv(_host.upload(sess, np.tril(S0[c]), np.float64))
                 Lam[c] = H.matmul(Sinv, Sinv, transA=True)
                 eta[c:c + 1] = H.matmul(_host.upload(sess, m0[c].reshape(1, M), np.float64), Lam[c].contiguous())
-        nodes = _host.upload(sess, likelihood.nodes(), np.float64)
+        state = likelihood.device_state(sess)
         yv = Yd.reshape(-1).contiguous()
         mode = H.SGP_DIAGONAL if residual == "diagonal" else H.SGP_NEGLECTED
-        fused = bool(getattr(settings.runtime, "fused_predict", True)) and H.sgp_predict_fused(
-            dt, 1, N, M, d, 1, H.SGP_S_TRIL, frag is not None)
+        one_pass = bool(likelihood.fused_marginals)
+        fused = bool(getattr(settings.runtime, "fused_predict", True)) and (
+            H.sgp_predict_multi_fused(dt, N, M, d, C, frag is not None) if one_pass else
+            H.sgp_predict_fused(dt, 1, N, M, d, 1, H.SGP_S_TRIL, frag is not None))
         ldw = -(-N // 4) * 4                        # rows padded to 16 bytes: what hb_sgp_mwstats asks of the weights
         mean = torch.empty((C, N), dtype=dt, device=sess.device)
         var = torch.empty_like(mean)
@@ -360,11 +365,14 @@ class SparseInference:
                 mc = H.matmul(t, V)
                 Sig, Sc = _q_cov(H, V, whoc)
                 m[c:c + 1], S[c] = mc, Sc
-                H.sgp_predict(Xd, z, ell, W, mc.to(dt), Sc.to(dt), s_kind=H.SGP_S_TRIL, mode=mode,
-                              out=(mean[c:c + 1], var[c:c + 1]), wfrag=frag if fused else None)
+                if not one_pass:
+                    H.sgp_predict(Xd, z, ell, W, mc.to(dt), Sc.to(dt), s_kind=H.SGP_S_TRIL, mode=mode,
+                                  out=(mean[c:c + 1], var[c:c + 1]), wfrag=frag if fused else None)
                 kl += 0.5 * (float(torch.diagonal(Sig).sum().cpu()) + float((mc * mc).sum().cpu()) - M
                              + 2.0 * float(np.log(np.diagonal(L.cpu().numpy())).sum()))
-            _, _, lsum = H.lik_softmax_sites(yv, mean, var, nodes, mscale=np.sqrt(k_var), vscale=k_var, out=(lam_c, beta_c))
+            if one_pass:
+                H.sgp_predict_multi(Xd, z, ell, W, m.to(dt), S.to(dt), mode=mode, out=(mean, var), wfrag=frag if fused else None)
+            lsum = likelihood.multi_sites(H, state, yv, mean, var, np.sqrt(k_var), k_var, (lam_c, beta_c))
             if lam_c is not lam:
                 lam[:, :N].copy_(lam_c)
                 beta[:, :N].copy_(beta_c)
@@ -560,7 +568,7 @@ class SparseInference:
             grad["lik_param"] = float(dps[0].cpu()[0])
         return float(lsum.cpu()[0]) - kl, grad
 
-    def elbo_and_grad_multi(self, X, Y, likelihood, q, k_var=1.0, residual="diagonal"):
+    def elbo_and_grad_multi(self, X, Y, likelihood, q, k_var=1.0, residual="diagonal", lik_grad=False):
         """(value, grad): elbo_and_grad for a likelihood over C = likelihood.num_latent latent functions
         (likelihoods.Softmax) at FIXED q(u_c) = N(m_c, S_c S_c^T), q = (m [C, M], S [C, M, M] lower), labels Y [N, 1]:
         value = sum_j l_j - sum_c KL(q_c || N(0, I)), l_j the mean of log softmax over the likelihood's fixed nodes -- the
@@ -585,7 +593,13 @@ class SparseInference:
         FLOAT64 ARITHMETIC end to end on the chunk walk of elbo_and_grad: per chunk C calls of hb_sgp_predict_f64, ONE
         hb_lik_softmax_grad_f64 and ONE hb_sgp_mwstats_f64.  Refusals and exception types are natgrad_q's for such a
         likelihood ('fullrank' and a mean-field q: NotImplementedError; other shapes and bad labels: ValueError), decided
-        before the session is touched; a likelihood over ONE latent function raises ValueError: use elbo_and_grad."""
+        before the session is touched; a likelihood over ONE latent function raises ValueError: use elbo_and_grad.
+
+        The weights call is the likelihood's (Likelihood.multi_weights).  likelihoods.HeteroscedasticGaussian: Y [N, 1]
+        real, w = lam and r = dl/dmu from ONE hb_lik_hetgauss_sites_f64 per chunk (its expectation is exact, so lam IS
+        -2 dl/dv) and the marginals from ONE hb_sgp_predict_multi_f64.  lik_grad=True (a `trainable` likelihood: ValueError
+        otherwise) adds grad['lik_param'] = sum_j dl_j / dparam at the marginals of that q, added in chunk order -- for
+        HeteroscedasticGaussian sum_j r_gj; the other entries and the value are the bits of lik_grad=False."""
         who = "elbo_and_grad_multi"
         _check_residual(residual)
         if not isinstance(likelihood, Likelihood):
@@ -594,25 +608,28 @@ class SparseInference:
         if C < 2:
             raise ValueError("%s: a likelihood over several latent functions expected (%s has one: use elbo_and_grad)"
                              % (who, type(likelihood).__name__))
+        if lik_grad and not getattr(likelihood, "trainable", False):
+            raise ValueError("%s: lik_grad=True needs a likelihood with a continuous parameter (got %s)"
+                             % (who, type(likelihood).__name__))
         if not float(k_var) > 0.0:
             raise ValueError("%s: k_var must be positive (got %r)" % (who, k_var))
         if q is None:
             raise ValueError("%s: q = (m [%d, M], S [%d, M, M]) expected, got None" % (who, C, C))
-        m0, S0 = _check_blocks_and_labels(who, "q", C, q, Y)
+        m0, S0 = _check_blocks_and_targets(who, "q", likelihood, q, Y)
         zshape = tuple(object.__getattribute__(self, "z").shape)
         if len(zshape) == 2 and m0.shape[1] != zshape[0]:
             raise ValueError("%s: q = (m [%d, %d], S [%d, %d, %d]) expected, got %s %s"
                              % ((who, C, zshape[0], C) + zshape[:1] * 2 + (m0.shape, S0.shape)))
         sess, Xd, Yd, z, ell, W = self._grad_inputs(X, Y, who)
         if Yd.dim() != 2 or Yd.shape[1] != 1:
-            raise ValueError("%s: Y must hold the labels as [N, 1], got %s" % (who, tuple(Yd.shape)))
+            raise ValueError("%s: Y must hold the targets as [N, 1], got %s" % (who, tuple(Yd.shape)))
         torch, H = sess.torch, sess.H
         N, M = int(Xd.shape[0]), int(z.shape[0])
         k = float(k_var)
         rho = 1.0 if residual == "diagonal" else 0.0
         f64 = dict(dtype=torch.float64, device=sess.device)
         m, S = _host.upload(sess, m0, np.float64), _host.upload(sess, np.tril(S0), np.float64)
-        nodes = _host.upload(sess, likelihood.nodes(), np.float64)
+        state = likelihood.device_state(sess)
         mode = H.SGP_DIAGONAL if residual == "diagonal" else H.SGP_NEGLECTED
         ldN = -(-N // 2) * 2                         # rows padded to 16 bytes: what hb_sgp_mwstats asks of the weights
         w, r = (torch.zeros((C, ldN), **f64) for _ in range(2))
@@ -620,16 +637,20 @@ class SparseInference:
         def per_chunk(c0, Xc, Yc):
             nc = Xc.shape[0]
             mean, var = (torch.empty((C, nc), **f64) for _ in range(2))      # unit-variance moments
-            for c in range(C):
-                H.sgp_predict(Xc, z, ell, W, m[c:c + 1], S[c], s_kind=H.SGP_S_TRIL, mode=mode,
-                              out=(mean[c:c + 1], var[c:c + 1]))
+            if likelihood.fused_marginals:
+                H.sgp_predict_multi(Xc, z, ell, W, m, S, mode=mode, out=(mean, var))
+            else:
+                for c in range(C):
+                    H.sgp_predict(Xc, z, ell, W, m[c:c + 1], S[c], s_kind=H.SGP_S_TRIL, mode=mode,
+                                  out=(mean[c:c + 1], var[c:c + 1]))
             wc, rc = w[:, c0:c0 + nc], r[:, c0:c0 + nc]
-            _, _, ls = H.lik_softmax_grad(Yc.reshape(-1), mean, var, nodes, mscale=np.sqrt(k), vscale=k, out=(wc, rc))
+            ls, dp = likelihood.multi_weights(H, state, Yc.reshape(-1), mean, var, np.sqrt(k), k, (wc, rc))
             Pc, bc, _ = H.sgp_mwstats(Xc, wc, rc, z, ell, W)
-            return Pc, bc, ls, (rc * mean * np.sqrt(k) - wc * var * k).sum()
+            parts = (Pc, bc, ls, (rc * mean * np.sqrt(k) - wc * var * k).sum())
+            return parts + (dp,) if lik_grad else parts
 
         # chunks of a multiple of 32 rows: every chunk of a row of w stays 16-byte aligned
-        Phi, b, lsum, dks = _walk_f64(torch, Xd, Yd, M, 32, per_chunk)
+        Phi, b, lsum, dks, *dps = _walk_f64(torch, Xd, Yd, M, 32, per_chunk)
         # tail: G_c = dF/dPhi_c, g_c = dF/db_c; T is linear in the classes, so one Cholesky VJP and one Gram VJP serve all
         zbar = ellbar = T = None
         for c in range(C):
@@ -646,6 +667,8 @@ class SparseInference:
         kl = sum(0.5 * (float((Sl[c] * Sl[c]).sum()) + float((m0[c] * m0[c]).sum()) - M)
                  - float(np.log(np.abs(np.diagonal(Sl[c]))).sum()) for c in range(C))
         grad = dict(z=(zbar + zk).cpu().numpy(), lengthscales=(ellbar + ek).cpu().numpy(), k_var=float(dks.cpu()) / (2.0 * k))
+        if lik_grad:
+            grad["lik_param"] = float(dps[0].cpu())
         return float(lsum.cpu()[0]) - kl, grad
 
     # -- pathwise posterior function draws (Wilson et al. 2020) -----------------------------------------------------
@@ -716,6 +739,29 @@ class SparseInference:
         dt = sess.torch_dtype
         return SparsePosterior(sess, z, ell, W, frag, m.reshape(M).to(dt).contiguous(), s.to(dt).contiguous(), residual,
                                float(settings.numerics.jitter_level), k_var)
+
+    def predict_multi(self, X, q, residual="diagonal"):
+        """Unit-variance marginals (mean [C, n], var [C, n]) as device tensors of C latent functions with independent
+        full-rank q(u_c), q = (m [C, M], S [C, M, M] lower), at the rows of X, from ONE pass (hb_sgp_predict_multi: A = W
+        K(z, X) is formed once for all C).  K(z, z) is factorised as the plans do it.  residual: 'diagonal' or
+        'neglected'.  Restrictions and exception types are those of natgrad_q for a multi-latent likelihood."""
+        _check_residual(residual)
+        m0, S0 = (np.asarray(a, dtype=np.float64) for a in q)
+        if m0.ndim != 2 or S0.shape != (m0.shape[0], m0.shape[1], m0.shape[1]):
+            raise ValueError("predict_multi: q = (m [C, M], S [C, M, M]) expected, got %s %s" % (m0.shape, S0.shape))
+        sess, zvar, ls = self._stats_session("predict_multi")
+        if m0.shape[1] != int(zvar.shape[0]):
+            raise ValueError("predict_multi: q is over %d inducing points, z holds %d" % (m0.shape[1], int(zvar.shape[0])))
+        H = sess.H
+        Xd = _host.device_data(sess, X, "X")
+        z, ell, W, frag = self._whitening(sess, zvar, ls, None, None, "predict_multi", as_plans=True)
+        if Xd.shape[1] != z.shape[1]:
+            raise ValueError("predict_multi: X %s does not match z %s" % (tuple(Xd.shape), tuple(z.shape)))
+        fused = bool(getattr(settings.runtime, "fused_predict", True)) and H.sgp_predict_multi_fused(
+            sess.torch_dtype, Xd.shape[0], m0.shape[1], Xd.shape[1], m0.shape[0], frag is not None)
+        return H.sgp_predict_multi(Xd, z, ell, W, _host.upload(sess, m0), _host.upload(sess, np.tril(S0)),
+                                   mode=H.SGP_DIAGONAL if residual == "diagonal" else H.SGP_NEGLECTED,
+                                   wfrag=frag if fused else None)
 
     def _q_moments(self, sess, q, M, who="pathwise_draws"):
         """(m [1, M], S [M, M] lower or s [M]) of q(u) as float64 device tensors, for pathwise_draws and posterior."""

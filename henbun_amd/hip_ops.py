@@ -47,6 +47,7 @@ PREC_NATIVE, PREC_BF16X3 = _hb("PREC_NATIVE", "PREC_BF16X3")
 LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON = _hb("LIK_GAUSSIAN", "LIK_BERNOULLI", "LIK_POISSON")
 LIK_LAPLACE, LIK_GAMMA, LIK_NEGBINOMIAL, LIK_BINOMIAL = _hb("LIK_LAPLACE", "LIK_GAMMA", "LIK_NEGBINOMIAL", "LIK_BINOMIAL")
 LIK_SOFTMAX = _C["HB_LIK_SOFTMAX"]
+LIK_HETGAUSS = _C["HB_LIK_HETGAUSS"]
 MATUTIL_BAND, MATUTIL_ADD_EYE, MATUTIL_PHI, MATUTIL_SYM, MATUTIL_SYMLOW = _hb("MATUTIL_BAND", "MATUTIL_ADD_EYE", "MATUTIL_PHI",
                                                                               "MATUTIL_SYM", "MATUTIL_SYMLOW")
 
@@ -160,8 +161,8 @@ def _out(who, t, shape, dtype, device, name="out", exact=True):
     the result on purpose: ewise, copy_nd, matmul, matmul_ld, matmul_colsum, diag_sample_kl_fwd / _bwd (rows=), sgp_fwd /
     sgp_bwd and their relatives (sgp_A, sgp_fwd_gauss_kbar, sgp_bwd_phi, sgp_bwd_phi_rest), matmul_gram_vjp[_tiles],
     gram_ell_fold, gram_tiles_fold, gauss_ll_fold, matmul_gauss's head (raw plan buffers, sized by the plan from the
-    library's own queries), lik_softmax_grad (padded rows, checked there), Rng.normal / randint (the result IS the shape
-    argument), and the status words `info` / `err` of every entry (int32 / int64 views of the plan's status block)."""
+    library's own queries), lik_softmax_grad and lik_hetgauss_sites (padded rows, checked there), Rng.normal / randint
+    (the result IS the shape argument), and the status words `info` / `err` of every entry (int32 / int64 views of the plan's status block)."""
     if t is None:
         return _empty(tuple(shape), dtype=dtype, device=device)
     shape = tuple(int(v) for v in shape)
@@ -1257,6 +1258,43 @@ def sgp_predict(x, z, ell, W, m, s, s_kind=SGP_S_DIAG, mode=SGP_DIAGONAL, jitter
     return mean, var
 
 
+def sgp_predict_multi_fused(dtype, n, M, d, C, has_wfrag):
+    """True when hb_sgp_predict_multi runs its fused strip kernel for these extents (hb_sgp_predict_multi_fused);
+    everything else runs the chunked form once per latent function."""
+    return bool(_query("hb_sgp_predict_multi_fused", n, M, d, C, bool(has_wfrag), _elem_bytes(dtype)))
+
+
+def sgp_predict_multi_ws_elems(dtype, n, M, d, C, has_wfrag):
+    """Scratch elements hb_sgp_predict_multi needs: C M^2 (the S^T images of the fused form), or one chunk."""
+    return _query("hb_sgp_predict_multi_ws_elems", n, M, d, C, bool(has_wfrag), _elem_bytes(dtype))
+
+
+def sgp_predict_multi(x, z, ell, W, m, S, mode=SGP_DIAGONAL, out=None, wfrag=None, ws=None):
+    """Closed-form predictive moments (mean [C, n], var [C, n]) of C latent functions of ONE expert with independent
+    full-rank q(u_c) = N(m_c, S_c S_c^T) that share x [n, d], z [M, d], ell and W (hb_sgp_predict_multi): m [C, M], S [C, M, M]
+    lower, 1 <= C <= 64; mode SGP_DIAGONAL or SGP_NEGLECTED.  The bits of C calls of sgp_predict(m[c:c+1], S[c],
+    s_kind=SGP_S_TRIL) with the same `wfrag`; with it (float32, M % 32 == 0, M <= 512, d <= 4) A = W K(z, x) is formed once
+    for all C in one strip kernel."""
+    who = "sgp_predict_multi"
+    _operands(who, x, z, ell, W, m, S, wfrag)
+    if x.dim() != 2 or z.dim() != 2 or z.shape[1] != x.shape[1] or tuple(W.shape) != (z.shape[0], z.shape[0]):
+        raise ValueError("%s: x [n, d], z [M, d], W [M, M] expected, got %s %s %s"
+                         % (who, tuple(x.shape), tuple(z.shape), tuple(W.shape)))
+    (n, d), M = x.shape, z.shape[0]
+    if m.dim() != 2 or m.shape[1] != M or tuple(S.shape) != (m.shape[0], M, M) or ell.numel() not in (1, d):
+        raise ValueError("%s: m [C, M], S [C, M, M] and 1 or d lengthscales expected, got %s %s %s"
+                         % (who, tuple(m.shape), tuple(S.shape), tuple(ell.shape)))
+    C = m.shape[0]
+    if wfrag is not None and wfrag.numel() < 2 * M * M:
+        raise ValueError("%s: wfrag must hold the two fragment-major images of W (2 M^2 elements)" % who)
+    dev, dt = x.device, x.dtype
+    mean, var = _outs(who, out, ((C, n),) * 2, dt, dev, ("mean", "var"))
+    ws = _ws(who, ws, dt, dev, sgp_predict_multi_ws_elems(dt, n, M, d, C, wfrag is not None), "sgp_predict_multi_ws_elems")
+    _lib.lib().call("hb_sgp_predict_multi" + _suf(x), KERN_RBF, _p(x), _p(z), _p(ell), ell.numel(), _p(W), _p(wfrag), _p(m),
+                    _p(S), int(mode), _p(mean), _p(var), n, M, d, C, _p(ws), stream())
+    return mean, var
+
+
 def _predict_grad_shapes(who, x, z, ell, W, m, s, s_kind, wfrag):
     """(n, M, d) of the operands of sgp_predict_grad / sgp_acq, checked: on the device, contiguous, one expert and one
     latent function, shapes that fit, one dtype."""
@@ -1964,6 +2002,77 @@ def lik_softmax_predict(mean, var, nodes, y=None, mscale=1.0, vscale=1.0, prob=T
     _lib.lib().call("hb_lik_softmax_predict" + _suf(mean), _p(y), _p(mean), _p(var), float(mscale), float(vscale), _p(nodes), S,
                     _p(pr), _p(ld), _p(total), n, C, _p(ws), stream())
     return pr, ld, total
+
+
+def _hetgauss_inputs(who, y, mean, var):
+    """(N, ld) of mean, var [2, N] views with one row stride ld >= N and unit column stride, and, when given, y [N]."""
+    for t in (mean, var):
+        if (not t.is_cuda or t.dim() != 2 or t.shape[0] != 2 or t.shape != mean.shape or t.dtype != mean.dtype
+                or t.stride(1) != 1 or t.stride(0) != mean.stride(0) or t.stride(0) < t.shape[1]):
+            raise ValueError("%s: mean and var must be [2, N] device tensors of one dtype with unit column stride and one "
+                             "row stride >= N" % who)
+    N = mean.shape[1]
+    if y is not None and (_chk(y).numel() != N or y.dtype != mean.dtype):
+        raise ValueError("%s: y must hold N = %d values in the dtype of mean" % (who, N))
+    return N, max(int(mean.stride(0)), N)
+
+
+def _hetgauss_rows(who, ts, names, N, ld, dtype, device):
+    """[2, N] result views whose rows are ld apart (given), or fresh ones of row stride ld (None)."""
+    res = []
+    for t, name in zip(ts, names):
+        if t is None:
+            t = _empty((2, ld), dtype=dtype, device=device)[:, :N]
+        elif (not t.is_cuda or t.dtype != dtype or tuple(t.shape) != (2, N) or t.stride(1) != 1
+              or max(int(t.stride(0)), N) != ld):
+            raise ValueError("%s: %s must be a [2, %d] device tensor of the inputs' dtype with unit column stride and the "
+                             "row stride of mean (%d)" % (who, name, N, ld))
+        res.append(t)
+    return res
+
+
+def lik_hetgauss_sites(y, mean, var, param=0.0, mscale=1.0, vscale=1.0, out=None, grad=False):
+    """Sites of the heteroscedastic Gaussian likelihood y ~ N(f, exp(g + param)) under independent marginals of f (row 0
+    of mean, var [2, N]) and g (row 1), scaled by mscale / vscale (hb_lik_hetgauss_sites): (lam [2, N], beta [2, N], r or
+    None, lsum float64 [1]).  Closed form, lam >= 0 and lam = -2 dl/dv exactly; grad=True also returns r = dl/dmu [2, N]
+    (sum_j r[1, j] is the derivative of lsum in param).  mean and var may be views of padded rows (one row stride >= N);
+    the results share that row stride: out = (lam, beta) or (lam, beta, r) such views, or None for fresh ones.  Double
+    arithmetic; two calls return the same bits."""
+    who = "lik_hetgauss_sites"
+    N, ld = _hetgauss_inputs(who, y, mean, var)
+    names = ("lam", "beta", "r") if grad else ("lam", "beta")
+    ts = (None,) * len(names) if out is None else tuple(out)
+    if len(ts) != len(names):
+        raise ValueError("%s: out must be (%s)" % (who, ", ".join(names)))
+    res = _hetgauss_rows(who, ts, names, N, ld, mean.dtype, mean.device)
+    lam, beta, r = res[0], res[1], (res[2] if grad else None)
+    lsum = _empty((1,), dtype=torch.float64, device=mean.device)
+    ws = workspace(torch.float64, mean.device, _query("hb_lik_hetgauss_ws_elems", N))
+    _lib.lib().call("hb_lik_hetgauss_sites" + _suf(mean), _p(y), _p(mean), _p(var), ld, float(mscale), float(vscale),
+                    float(param), _p(lam), _p(beta), _p(r), _p(lsum), N, _p(ws), stream())
+    return lam, beta, r, lsum
+
+
+def lik_hetgauss_predict(mean, var, param=0.0):
+    """(mean [n], variance [n]) of a new observation under the heteroscedastic Gaussian likelihood given the (already
+    scaled) marginals mean, var [2, n] of f and g (hb_lik_hetgauss_predict): (mu_f, v_f + exp(mu_g + param + v_g / 2))."""
+    n, ld = _hetgauss_inputs("lik_hetgauss_predict", None, mean, var)
+    ym, yv = (_empty((n,), dtype=mean.dtype, device=mean.device) for _ in range(2))
+    _lib.lib().call("hb_lik_hetgauss_predict" + _suf(mean), _p(mean), _p(var), ld, float(param), _p(ym), _p(yv), n, stream())
+    return ym, yv
+
+
+def lik_hetgauss_logdens(y, mean, var, param=0.0, mscale=1.0, vscale=1.0, pointwise=True):
+    """Predictive log density of the heteroscedastic Gaussian likelihood (hb_lik_hetgauss_logdens): (per point [N] in the
+    dtype of the inputs, or None with pointwise=False; their sum as a float64 device tensor [1]).  f is integrated in
+    closed form, g by the 20-node rule combined by log-sum-exp.  Inputs as for lik_hetgauss_sites."""
+    N, ld = _hetgauss_inputs("lik_hetgauss_logdens", y, mean, var)
+    out = _empty((N,), dtype=mean.dtype, device=mean.device) if pointwise else None
+    total = _empty((1,), dtype=torch.float64, device=mean.device)
+    ws = workspace(torch.float64, mean.device, _query("hb_lik_hetgauss_ws_elems", N))
+    _lib.lib().call("hb_lik_hetgauss_logdens" + _suf(mean), _p(y), _p(mean), _p(var), ld, float(mscale), float(vscale),
+                    float(param), _p(out), _p(total), N, _p(ws), stream())
+    return out, total
 
 
 def sgp_kgrad_ws_elems(N, M, d, P):

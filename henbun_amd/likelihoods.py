@@ -14,9 +14,12 @@ and its closed-form fit use one likelihood.
     Binomial(total_count)        y successes out of total_count trials, logit link
     Softmax(num_classes)         y in {0, .., C - 1}, p(y = c | f) = softmax(f)_c: C latent functions (num_latent = C),
                                  its own native entries hb_lik_softmax_*, natgrad_rho = 0.5
+    HeteroscedasticGaussian(log_var_mean)   y ~ N(f, exp(g + log_var_mean)): two latent functions (num_latent = 2), the
+                                 mean f and the log noise variance g; native entries hb_lik_hetgauss_*, natgrad_rho = 0.5;
+                                 trainable (log_var_mean, any real number)
 
 All are log-concave in f, which keeps the natural-gradient step positive definite.  `trainable` says that the parameter
-is continuous and has a gradient (hb_lik_param_grad_*): SparseGP.elbo_and_grad(lik_grad=True) returns it and
+is continuous and has a gradient (hb_lik_param_grad_*; HeteroscedasticGaussian: with its sites): SparseGP.elbo_and_grad(lik_grad=True) returns it and
 models.SVGPLik(learn_likelihood=True) learns it.  `logp(f, y, param=t)` takes the parameter from the graph tensor t
 instead of the stored float, which is how such a model's sampled ELBO sees its Variable.  `natgrad_rho` is the damping
 SVGPLik.fit_q and fit_hyper use unless told otherwise: 1 (full steps) except for Laplace."""
@@ -55,6 +58,27 @@ class Likelihood:
         return value
 
     def logp(self, f, y, param=None):
+        raise NotImplementedError
+
+    # -- what SparseGP.natgrad_q / elbo_and_grad_multi ask of a likelihood over several latent functions (num_latent > 1) --
+    fused_marginals = False   # True: the C marginals come from ONE hip_ops.sgp_predict_multi (else C calls of sgp_predict)
+
+    def check_targets(self, who, Y):
+        """Host-side check of a numpy Y [N, 1] (targets already on the device are the caller's duty)."""
+        raise NotImplementedError
+
+    def device_state(self, sess):
+        """What the sites and weights calls need on the device besides the marginals (Softmax: its nodes); built once
+        per route, before the first step."""
+        return None
+
+    def multi_sites(self, H, state, y, mean, var, mscale, vscale, out):
+        """lam, beta [C, N] into out = (lam, beta) at the marginals mean, var [C, N]; returns lsum (float64 [1])."""
+        raise NotImplementedError
+
+    def multi_weights(self, H, state, y, mean, var, mscale, vscale, out):
+        """The weights of the hyper-parameter gradient at fixed q into out = (w, r), float64 [C, N] views of padded rows;
+        returns (lsum, dparam): sum_j l_j and, for a trainable likelihood, sum_j dl_j / dparam (a device scalar) or None."""
         raise NotImplementedError
 
 
@@ -227,6 +251,24 @@ class Softmax(Likelihood):
             self._nodes = hip_ops.Rng(self.seed).normal((self.num_nodes, self.num_classes), dtype=torch.float64).cpu().numpy()
         return self._nodes
 
+    def check_targets(self, who, Y):
+        C = self.num_classes
+        if Y.ndim != 2 or Y.shape[1] != 1:
+            raise ValueError("%s: Y must hold the labels as [N, 1], got %s" % (who, Y.shape))
+        if not (np.all(Y == np.floor(Y)) and Y.size and Y.min() >= 0 and Y.max() <= C - 1):
+            raise ValueError("%s: the labels must be integers in 0 .. %d" % (who, C - 1))
+
+    def device_state(self, sess):
+        from .gp import _host
+
+        return _host.upload(sess, self.nodes(), np.float64)
+
+    def multi_sites(self, H, state, y, mean, var, mscale, vscale, out):
+        return H.lik_softmax_sites(y, mean, var, state, mscale=mscale, vscale=vscale, out=out)[2]
+
+    def multi_weights(self, H, state, y, mean, var, mscale, vscale, out):
+        return H.lik_softmax_grad(y, mean, var, state, mscale=mscale, vscale=vscale, out=out)[2], None
+
     def logp(self, f, y, param=None):
         """log softmax(f)_y as a graph expression [1, n]: f [C, n], y the ONE-HOT labels [C, n];
         sum_c y_c f_c - logsumexp_c f, the log-sum-exp shifted by the maximum over classes."""
@@ -234,3 +276,57 @@ class Softmax(Likelihood):
         top = tf.reduce_max(f, 0, keep_dims=True)
         lse = G.add(top, tf.log(tf.reduce_sum(tf.exp(G.sub(f, top)), 0, keep_dims=True)))
         return G.sub(tf.reduce_sum(G.mul(y, f), 0, keep_dims=True), lse)
+
+
+class HeteroscedasticGaussian(Likelihood):
+    """Regression with input-dependent noise: y ~ N(f, exp(g + c)) over TWO latent functions (num_latent = 2), the mean f
+    and the log noise variance g, with c = log_var_mean the prior mean of the log variance (any real number; trainable).
+    SparseGP.natgrad_q fits two independent q(u_f), q(u_g); models.SVGPHetero is the model.  Under independent Gaussian
+    marginals the expected log density, both sites and every derivative are closed forms (include/henbun_hip.h,
+    hb_lik_hetgauss_*), with s = (y - mu_f)^2 + v_f and e = exp(-mu_g - c + v_g / 2):
+        l = -1/2 log 2 pi - 1/2 (mu_g + c) - 1/2 s e,   lam_f = e,   lam_g = 1/2 s e   (both >= 0, and lam = -2 dl/dv exactly)
+    so the weights of the hyper-parameter gradient are the sites themselves, and dl/dc = dl/dmu_g.
+    Full natural-gradient steps overshoot (tests/hetgauss_ref.py on 300 .. 400 points with a sigmoid noise level, M = 24:
+    at rho = 1 the second step throws the ELBO from -281 to -18623, six times below the prior's value); at rho = 0.5 it
+    rose at every step and settled to 1e-6 relative in 14 .. 22 steps, hence natgrad_rho."""
+
+    lik_id = 33
+    num_latent = 2
+    natgrad_rho = 0.5
+    trainable = True
+    param_name = "log_var_mean"
+    fused_marginals = True
+
+    def __init__(self, log_var_mean=0.0):
+        self.param = self._check(log_var_mean)
+
+    def _check(self, value):
+        value = float(value)
+        if not math.isfinite(value):
+            raise ValueError("HeteroscedasticGaussian: log_var_mean must be finite (got %r)" % (value,))
+        return value
+
+    def check_targets(self, who, Y):
+        if Y.ndim != 2 or Y.shape[1] != 1:
+            raise ValueError("%s: Y must hold the observations as [N, 1], got %s" % (who, Y.shape))
+        if not (Y.size and np.all(np.isfinite(Y))):
+            raise ValueError("%s: the observations must be finite numbers" % who)
+
+    def multi_sites(self, H, state, y, mean, var, mscale, vscale, out):
+        return H.lik_hetgauss_sites(y, mean, var, param=self.param, mscale=mscale, vscale=vscale, out=out)[3]
+
+    def multi_weights(self, H, state, y, mean, var, mscale, vscale, out):
+        # w = lam and r = dl/dmu from the one launch; the entry keeps one row stride for inputs and outputs, so the
+        # (float64, per chunk) results are copied into the padded rows
+        lam, _, r, lsum = H.lik_hetgauss_sites(y, mean, var, param=self.param, mscale=mscale, vscale=vscale, grad=True)
+        out[0].copy_(lam)
+        out[1].copy_(r)
+        return lsum, r[1].sum()
+
+    def logp(self, f, y, param=None):
+        """log N(y; f_0, exp(f_1 + c)) as a graph expression [1, n]: f [2, n] (rows: the mean, the log variance), y [1, n]."""
+        f, y = G.as_tensor(f), G.as_tensor(y)
+        c = G.as_tensor(self.param if param is None else param)
+        lv = G.add(tf.slice(f, [1, 0], [1, -1]), c)
+        d = G.sub(y, tf.slice(f, [0, 0], [1, -1]))
+        return G.affine(G.add(lv, G.mul(G.mul(d, d), tf.exp(G.affine(lv, -1.0)))), -0.5, -0.5 * math.log(2.0 * math.pi))

@@ -577,6 +577,136 @@ class SVGPMulticlass(hb.model.Model):
         return ld.cpu().numpy(), float(total.cpu()[0])
 
 
+class SVGPHetero(hb.model.Model):
+    """Sparse variational GP regression with input-dependent noise: y ~ N(f(x), exp(g(x) + c)) with the likelihood
+    hb.likelihoods.HeteroscedasticGaussian -- two latent functions, the mean f and the log noise variance g, that share z,
+    the lengthscales and k_var (f_c = sqrt(k_var) u_c A), with two independent full-rank blocks q(u_f), q(u_g): one Normal
+    with n_layers = [2], as SVGPMulticlass holds its classes.  c = log_var_mean is the prior mean of the log variance:
+    a Variable `lik_param` (any real number) with learn_likelihood=True, which fit_hyper then learns.
+    The sampled ELBO trains everything by the minibatch route; fit_q() fits q(u) deterministically by natural-gradient
+    steps over the full data (SparseGP.natgrad_q: per step ONE marginals pass for both latent functions, one sites launch,
+    one weighted statistics pass, two tails); elbo_and_grad() is the exact partial gradient of the closed-form ELBO at the
+    current q (SparseGP.elbo_and_grad_multi); fit_hyper() alternates the two.
+
+    Limits.  Both latent functions share the lengthscales and k_var (per-latent hyper-parameters are not built).  The
+    residual: SparseGP.samples draws ONE residual per data point, shared by all latent functions of the SparseGP; a shared
+    draw would couple f and g, which the closed-form routes (independent marginals) cannot describe.  So the sampled ELBO
+    and the closed-form routes both use 'neglected', and 'diagonal' is refused."""
+
+    def setUp(self, X, Y, Z, log_var_mean=None, learn_likelihood=True, residual="neglected"):
+        """X [N, d]; Y [N, 1] real; Z [M, d].  log_var_mean=None: log(0.1 var Y), a tenth of the data's variance as
+        noise."""
+        if residual != "neglected":
+            raise NotImplementedError(
+                "SVGPHetero: residual %r is not covered: SparseGP.samples draws one residual per data point, shared by the "
+                "two latent functions, which would couple f and g, while the closed-form routes take independent marginals; "
+                "only 'neglected' describes one model on both routes" % (residual,))
+        Y = np.asarray(Y)
+        if Y.ndim != 2 or Y.shape != (X.shape[0], 1):
+            raise ValueError("SVGPHetero: Y must be [N, 1] with one row per row of X (got %s for %d rows)" % (Y.shape, X.shape[0]))
+        if log_var_mean is None:
+            log_var_mean = float(np.log(0.1 * max(float(np.var(Y)), 1e-12)))
+        self.likelihood = hb.likelihoods.HeteroscedasticGaussian(log_var_mean)
+        self.N = X.shape[0]
+        self.X = hb.param.MinibatchData(X)
+        self.Y = hb.param.MinibatchData(Y)
+        self.gp = hb.gp.SparseGP(kern=hb.gp.kernels.UnitRBF(np.ones(1)), z=Z)
+        self.u = hb.variationals.Normal(shape=[Z.shape[0]], n_layers=[2], q_shape="fullrank")
+        self.k_var = hb.param.Variable([1], transform=hb.transforms.positive)
+        self.learn_likelihood = bool(learn_likelihood)
+        if self.learn_likelihood:
+            self.lik_param = hb.param.Variable([1])
+            self.lik_param = np.ones(1) * self.likelihood.param
+        self.residual = residual
+        self.num_classes = 2      # the blocks of q(u): what the shared block helpers of SVGPMulticlass read
+
+    @hb.model.AutoOptimize()
+    def ELBO(self):
+        f = self.gp.samples(self.X, self.u, q_shape=self.residual) * tf.sqrt(self.k_var)      # [2, n]
+        n = tf.shape(self.X)[0]
+        if self.learn_likelihood:
+            ll = tf.reduce_sum(self.likelihood.logp(f, tf.transpose(self.Y), param=self.lik_param))
+        else:
+            ll = tf.reduce_sum(self.likelihood.logp(f, tf.transpose(self.Y)))
+        return (self.N / n) * ll - self.KL()
+
+    current_likelihood = SVGPLik.current_likelihood
+    select_inducing = SVGP.select_inducing
+    reset_q = SVGPMulticlass.reset_q
+    _write_blocks = SVGPMulticlass._write_blocks
+    _current_blocks = SVGPMulticlass._current_blocks
+    _hyper_variables = SVGPLik._hyper_variables
+
+    def fit_q(self, steps=50, rho=None, tol=1e-8):
+        """Fit the two blocks of q(u) at the current z, lengthscales, k_var and c by natural-gradient steps from the model's
+        CURRENT q, over the model's full device-resident X, Y, and write them back.  Returns (m [2, M], S [2, M, M], info) as
+        SparseGP.natgrad_q does.  rho=None: the likelihood's natgrad_rho, 0.5 -- a full step diverges.  Start from
+        reset_q(), not from the random initial q."""
+        self.initialize()
+        lik = self.current_likelihood()
+        rho = lik.natgrad_rho if rho is None else rho
+        m, S, info = _part(self, "gp").natgrad_q(_part(self, "X"), _part(self, "Y"), lik, k_var=_scalar(self, "k_var"),
+                                                 residual=self.residual, q0=self._current_blocks(), steps=steps, rho=rho,
+                                                 tol=tol)
+        self._write_blocks(m, S)
+        return m, S, info
+
+    def elbo_and_grad(self):
+        """(value, grad): the closed-form ELBO over the model's full X, Y at the model's CURRENT q(u) -- the value fit_q
+        reports -- and its exact partial gradient at that q with respect to the RAW (free) parameters, grad = dict(z,
+        lengthscales, k_var) and, with learn_likelihood=True, lik_param, in the shapes of the raw arrays, float64 numpy
+        (SparseGP.elbo_and_grad_multi, chained through the transforms' dforward).  At the q fit_q converges to it is the
+        total derivative of the fitted ELBO."""
+        self.initialize()
+        kw = dict(lik_grad=True) if _part(self, "learn_likelihood") else {}
+        value, cons = _part(self, "gp").elbo_and_grad_multi(_part(self, "X"), _part(self, "Y"), self.current_likelihood(),
+                                                            self._current_blocks(), k_var=_scalar(self, "k_var"),
+                                                            residual=self.residual, **kw)
+        return value, _chain_to_raw(self, cons)
+
+    fit_hyper = SVGPMulticlass.fit_hyper
+
+    def predict_f(self, Xnew):
+        """(mean [2, n], var [2, n]) of the two latent functions at Xnew [n, d] (rows: f, g), from ONE pass
+        (hb_sgp_predict_multi), scaled by sqrt(k_var) / k_var."""
+        m, S = self._current_blocks()
+        gp, k_var = _part(self, "gp"), _scalar(self, "k_var")
+        mean, var = gp.predict_multi(Xnew, (m, S), residual=self.residual)
+        mean, var = mean.cpu().numpy(), var.cpu().numpy()
+        return (mean * np.sqrt(k_var)).astype(mean.dtype), (var * k_var).astype(var.dtype)
+
+    def predict_y(self, Xnew):
+        """Mean and variance [n] of a new observation at Xnew: (mu_f, v_f + exp(mu_g + c + v_g / 2)) (hb_lik_hetgauss_predict)."""
+        mean, var = self.predict_f(Xnew)
+        sess = self._session
+        ym, yv = sess.H.lik_hetgauss_predict(upload(sess, mean), upload(sess, var), param=self.current_likelihood().param)
+        return ym.cpu().numpy(), yv.cpu().numpy()
+
+    def predict_noise_variance(self, Xnew):
+        """E exp(g + c) = exp(mu_g + c + v_g / 2) [n] at Xnew: the noise variance the model predicts there (predict_y's
+        variance without the part of f)."""
+        mean, var = self.predict_f(Xnew)
+        sess = self._session
+        zero = np.zeros_like(var[:1])
+        _, yv = sess.H.lik_hetgauss_predict(upload(sess, mean), upload(sess, np.concatenate([zero, var[1:]])),
+                                            param=self.current_likelihood().param)
+        return yv.cpu().numpy()
+
+    def predict_log_density(self, Xnew, Ynew):
+        """(per point [n], their sum as a float): the predictive log density of observations Ynew [n, 1] at Xnew, f
+        integrated in closed form and g by the 20-node rule (hb_lik_hetgauss_logdens); the sum is taken in double on the
+        device."""
+        mean, var = self.predict_f(Xnew)
+        Ynew = np.asarray(Ynew)
+        if Ynew.size != mean.shape[1]:
+            raise ValueError("predict_log_density: Ynew must hold one observation per row of Xnew (got %s for %d rows)"
+                             % (Ynew.shape, mean.shape[1]))
+        sess = self._session
+        out, total = sess.H.lik_hetgauss_logdens(upload(sess, Ynew.reshape(-1)), upload(sess, mean), upload(sess, var),
+                                                 param=self.current_likelihood().param)
+        return out.cpu().numpy(), float(total.cpu()[0])
+
+
 class Amortised(hb.model.Model):
     """cfg 4: NeuralNet encoder -> LOCAL Normal -> linear Gaussian decoder."""
 

@@ -72,7 +72,10 @@ extern "C" {
  * _f64, hb_lik_softmax_predict_f32 / _f64, hb_lik_softmax_ws_elems, HB_LIK_SOFTMAX, hb_sgp_mwstats_f32 / _f64 and
  * hb_sgp_mwstats_ws_elems (multi-class classification: softmax sites, weighted statistics of C weight sets from one A);
  * hb_lik_softmax_grad_f32 / _f64 (hyper-parameter gradient of the multi-class ELBO at fixed q(u_c): the exact weights of
- * the fixed-node value). */
+ * the fixed-node value); hb_sgp_predict_multi_f32 / _f64, hb_sgp_predict_multi_ws_elems, hb_sgp_predict_multi_fused,
+ * hb_lik_hetgauss_sites_f32 / _f64, hb_lik_hetgauss_predict_f32 / _f64, hb_lik_hetgauss_logdens_f32 / _f64,
+ * hb_lik_hetgauss_ws_elems and HB_LIK_HETGAUSS (heteroscedastic regression: the marginals of C full-rank latent functions
+ * from one pass, the two-latent Gaussian likelihood). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -660,6 +663,26 @@ int hb_sgp_predict_f32(int kind, const float* x, long sx, const float* z, const 
 int hb_sgp_predict_f64(int kind, const double* x, long sx, const double* z, const double* ell, long dl, const double* W,
                        const double* Wfrag, const double* m, const double* s, int s_kind, int mode, double jitter,
                        double* mean, double* var, long E, long n, long M, long d, long P, double* ws, void* stream);
+/* The same moments for C latent functions of ONE expert with independent full-rank q(u_c) = N(m_c, S_c S_c^T) that share
+ * x, z, ell, W and Wfrag (csrc/sgp_predict.hip; the marginals a multi-latent likelihood needs):
+ *   mean[c, j] = m_c^T A_j,   var[c, j] = || S_c^T A_j ||^2 + r_j,   r_j as above for HB_SGP_DIAGONAL / HB_SGP_NEGLECTED
+ * (any other mode is refused).  m [C, M], S [C, M, M] (the lower triangles are read), mean, var [C, n], 1 <= C <= 64.
+ * With Wfrag, fp32, M % 32 == 0, 32 <= M <= 512, d <= 4: ONE strip kernel behind one pack launch (the C fragment-major
+ * S_c^T images, C M^2 workspace elements).  A_strip = W K is formed once per strip; the means are taken in groups of 4 and
+ * C_c = S_c^T A_strip once per latent function: C + 1 strip products where C calls of hb_sgp_predict_* take 2 C.  Every
+ * other shape runs the one-latent chunked form once per latent function.  Either way mean and var hold the BITS of C calls
+ * of hb_sgp_predict_*(m_c, S_c, HB_SGP_S_TRIL, E = P = 1) with the same Wfrag.  ws >= hb_sgp_predict_multi_ws_elems(n, M, d,
+ * C, Wfrag != NULL, sizeof(T)) elements, 16-byte aligned.  Validated before any launch: the mode, C, the extents, NULL
+ * pointers, kind (HB_KERN_RBF only), dl, Wfrag's alignment, the workspace. */
+long hb_sgp_predict_multi_ws_elems(long n, long M, long d, long C, int has_wfrag, int dtype_bytes);
+/* 1 when hb_sgp_predict_multi_* runs its fused strip kernel for these extents (else: the chunked form per latent function) */
+int hb_sgp_predict_multi_fused(long n, long M, long d, long C, int has_wfrag, int dtype_bytes);
+int hb_sgp_predict_multi_f32(int kind, const float* x, const float* z, const float* ell, long dl, const float* W,
+                             const float* Wfrag, const float* m, const float* S, int mode, float* mean, float* var, long n,
+                             long M, long d, long C, float* ws, void* stream);
+int hb_sgp_predict_multi_f64(int kind, const double* x, const double* z, const double* ell, long dl, const double* W,
+                             const double* Wfrag, const double* m, const double* S, int mode, double* mean, double* var, long n,
+                             long M, long d, long C, double* ws, void* stream);
 /* Full predictive covariance of the same draw (csrc/sgp_predict_cov.hip; not in the reference).  Per expert e and latent
  * function p, with A_e = L_e^-1 K(z_e, x):
  *   cov[e,p] = A^T S_ep S_ep^T A + K(x, x) - A^T A + jitter I   (mode HB_SGP_FULLRANK: what samples() factorises, plus u)
@@ -791,7 +814,8 @@ enum {
   HB_LIK_GAMMA = 17,
   HB_LIK_NEGBINOMIAL = 18,
   HB_LIK_BINOMIAL = 19,
-  HB_LIK_SOFTMAX = 32   /* C latent functions: served by hb_lik_softmax_*, refused by the entries above */
+  HB_LIK_SOFTMAX = 32,  /* C latent functions: served by hb_lik_softmax_*, refused by the entries above */
+  HB_LIK_HETGAUSS = 33  /* two latent functions: served by hb_lik_hetgauss_*, refused by the entries above */
 };
 long hb_lik_sites_ws_elems(long N);
 int hb_lik_sites_f32(int lik, const float* y, const float* mean, const float* var, double mscale, double vscale, double param,
@@ -859,6 +883,40 @@ int hb_lik_softmax_predict_f32(const float* y, const float* mean, const float* v
 int hb_lik_softmax_predict_f64(const double* y, const double* mean, const double* var, double mscale, double vscale,
                                const double* nodes, long S, double* prob, double* logdens, double* total, long n, long C,
                                double* ws, void* stream);
+/* Heteroscedastic Gaussian likelihood over TWO latent functions (csrc/lik_sites.hip; not in the reference):
+ *   y ~ N(f, exp(g + c)),   param = c, the prior mean of the log noise variance (any finite number).
+ * mean, var [2, ld]: row 0 the unit-variance marginals of f, row 1 (ld elements on) those of g; mu = mscale mean, v =
+ * vscale var as for hb_lik_sites_*.  With s = (y - mu_f)^2 + v_f and e = exp(-mu_g - c + v_g / 2) the expected log density
+ * and its derivatives are closed forms (no quadrature):
+ *   l = -1/2 log 2 pi - 1/2 (mu_g + c) - 1/2 s e
+ *   dl/dmu_f = (y - mu_f) e,   lam_f = e            dl/dmu_g = -1/2 + 1/2 s e,   lam_g = 1/2 s e
+ *   beta = dl/dmu + lam mu;   both lam >= 0, and lam = -2 dl/dv exactly;   dl/dc = dl/dmu_g.
+ * hb_lik_hetgauss_sites_*: lam, beta [2, ld] and, when r is not NULL, r [2, ld] = dl/dmu (the weights of the hyper-parameter
+ * gradient at fixed q together with w = lam; sum_j r[1, j] = d sum_j l_j / dc), and ell_sum[0] = sum_j l_j.  y [N]; ld >= N
+ * (the padding hb_sgp_mwstats_* asks of its weights; elements N .. ld of a row are not touched).  Double arithmetic, rounded
+ * once on output and saturated to the largest finite value of the storage type; per-block partials (ws) folded in block
+ * order by a second launch, no atomics: two calls return the same bits.
+ * hb_lik_hetgauss_predict_*: mean and variance of a new y given f ~ N(mean[0, j], var[0, j]), g ~ N(mean[1, j], var[1, j])
+ * (already scaled): ymean = mu_f, yvar = v_f + exp(mu_g + c + v_g / 2); ymean, yvar [n].
+ * hb_lik_hetgauss_logdens_*: out[j] = log sum_i w_i N(y_j; mu_f, v_f + exp(mu_g + c + sqrt(2 v_g) x_i)) over the 20-node
+ * Gauss-Hermite rule in g (f is integrated in closed form), combined by log-sum-exp (out may be NULL), and sum[0] = sum_j
+ * out[j] by the same fold.  ws >= hb_lik_hetgauss_ws_elems(N) doubles (at most 1024) for the two entries that sum.
+ * Validated before any launch: N >= 0, ld >= N, a finite c, vscale >= 0, NULL pointers. */
+long hb_lik_hetgauss_ws_elems(long N);
+int hb_lik_hetgauss_sites_f32(const float* y, const float* mean, const float* var, long ld, double mscale, double vscale,
+                              double param, float* lam, float* beta, float* r, double* ell_sum, long N, double* ws,
+                              void* stream);
+int hb_lik_hetgauss_sites_f64(const double* y, const double* mean, const double* var, long ld, double mscale, double vscale,
+                              double param, double* lam, double* beta, double* r, double* ell_sum, long N, double* ws,
+                              void* stream);
+int hb_lik_hetgauss_predict_f32(const float* mean, const float* var, long ld, double param, float* ymean, float* yvar, long n,
+                                void* stream);
+int hb_lik_hetgauss_predict_f64(const double* mean, const double* var, long ld, double param, double* ymean, double* yvar,
+                                long n, void* stream);
+int hb_lik_hetgauss_logdens_f32(const float* y, const float* mean, const float* var, long ld, double mscale, double vscale,
+                                double param, float* out, double* sum, long N, double* ws, void* stream);
+int hb_lik_hetgauss_logdens_f64(const double* y, const double* mean, const double* var, long ld, double mscale, double vscale,
+                                double param, double* out, double* sum, long N, double* ws, void* stream);
 /* Pathwise posterior function draws (csrc/sgp_pathwise.hip; not in the reference; Wilson et al. 2020).  S function draws,
  * each a coefficient row coef[s] = [ w_s / sqrt(L) | v_s ] over 2L random Fourier features of the unit RBF kernel and the M
  * canonical basis functions K(z_m, .), evaluated at n points:
