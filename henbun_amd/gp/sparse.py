@@ -74,6 +74,23 @@ def _q_cov(H, V, who):
     return Sig, _host.factor(H, Sig, who, "Lambda^-1")
 
 
+def _input_variance(sess, X_var, Xd, who):
+    """The input variances as a contiguous [n, d] device tensor of the session's dtype, for points Xd [n, d]: X_var
+    [n, d], [d] or a scalar (broadcast).  Another shape, a negative or a non-finite entry raises ValueError -- the
+    entries are checked by ONE device reduction, before the broadcast."""
+    torch = sess.torch
+    if isinstance(X_var, torch.Tensor):
+        v = X_var.to(device=sess.device, dtype=sess.torch_dtype)
+    else:
+        v = _host.upload(sess, np.asarray(X_var, dtype=np.float64))
+    n, d = Xd.shape
+    if tuple(v.shape) not in ((), (d,), (n, d)):
+        raise ValueError("%s: X_var must be [%d, %d], [%d] or a scalar, got %s" % (who, n, d, d, tuple(v.shape)))
+    if not bool(((v >= 0) & torch.isfinite(v)).all().cpu()):
+        raise ValueError("%s: X_var must be finite and >= 0" % who)
+    return v.expand(n, d).contiguous()
+
+
 def _walk_f64(torch, Xd, Yd, M, align, per_chunk):
     """The float64 walk over the data: row chunks of Xd, Yd (f64_chunk_rows(M, align) rows) are up-converted to double
     and handed to per_chunk(c0, Xc, Yc), whose tuples are added entry by entry in chunk order."""
@@ -107,6 +124,31 @@ class SparseInference:
         Xd, Yd = _host.device_data(sess, X, "X"), _host.device_data(sess, Y, "Y")
         z, ell, W, frag = self._whitening(sess, zvar, ls, Xd, Yd, "statistics")
         return sess.H.sgp_stats(Xd, Yd, z, ell, W, wfrag=frag)
+
+    def psi_statistics(self, X_mean, X_var, Y):
+        """statistics() for UNCERTAIN inputs x_n ~ N(X_mean_n, diag(X_var_n)): (Phi [M, M], b [P, M], yy [P], a2sum [1])
+        as float64 device tensors, with the kernel expectations (psi statistics, Titsias & Lawrence 2010) in the place
+        of the kernel values,
+            Psi2 = sum_n E k(z, x_n) k(x_n, z),   C_p = sum_n E k(z, x_n) Y_np        (hb_sgp_psi_stats)
+            Phi = W Psi2 W^T,   b_p = W C_p,   a2sum = tr Phi,   W = chol(K(z, z) + jitter I)^-1,
+        so that optimal_q(.., stats=) returns the optimal q(u) and collapsed_bound(.., stats=) with residual 'diagonal'
+        the collapsed bound under input uncertainty: its trace term N - a2sum is psi0 - tr(Kmm^-1 Psi2).  (The
+        KL(q(X) || p(X)) of a latent-variable model is not part of it.)  X_var: [N, d], [d] or a scalar, the last two
+        shared by all points; X_var = 0 gives statistics(X_mean, Y).  A negative or non-finite entry raises ValueError.
+        The psi statistics are evaluated in DOUBLE whatever the session's dtype -- the sandwich amplifies an error of
+        Psi2 by |W|^2 ~ 1 / jitter -- from the inputs as the session stores them; W is _whitening's, up-converted, and
+        the sandwich is hb_matmul_f64.  Phi is bitwise symmetric.  Cost: N M (M + 1) / 2 double exponentials (Psi2 is no
+        rank update once the variances differ from point to point), against the MFMA rank update of statistics().
+        Restrictions and exception types are those of statistics()."""
+        sess, zvar, ls = self._stats_session("psi_statistics")
+        torch, H = sess.torch, sess.H
+        Xd, Yd = _host.device_data(sess, X_mean, "X_mean"), _host.device_data(sess, Y, "Y")
+        Vd = _input_variance(sess, X_var, Xd, "psi_statistics")
+        z, ell, W, _ = self._whitening(sess, zvar, ls, Xd, Yd, "psi_statistics")
+        Psi2, C, yy = H.sgp_psi_stats(Xd, Vd, Yd, z, ell)
+        W64 = W.to(torch.float64)
+        Phi = H.matutil(H.matmul(W64, H.matmul(Psi2, W64, transB=True)), H.MATUTIL_SYM)
+        return Phi, H.matmul(C, W64, transB=True), yy, torch.diagonal(Phi).sum().reshape(1)
 
     def _whitening(self, sess, zvar, ls, Xd, Yd, who, as_plans=False):
         """(z, ell, W, frag) on the device in the session's dtype: W = chol(K(z, z) + jitter I)^-1 from the fused factor
@@ -187,7 +229,8 @@ class SparseInference:
         'diagonal': s = diag(Lambda)^-1/2 [M], the optimum of the mean-field family (the mean is the same).
         Returns (m [P, M], S or s) as float64 numpy.  `residual` ('diagonal' / 'neglected') does not change q*: that
         term of the ELBO does not depend on q.  The M^3 tail runs on the device in float64 (hb_cholesky, hb_trinv,
-        hb_matmul).  `stats`: the tuple statistics(X, Y) returned, to share one pass between calls."""
+        hb_matmul).  `stats`: the tuple statistics(X, Y) returned, to share one pass between calls -- or the tuple of
+        psi_statistics(X_mean, X_var, Y), for the optimum under uncertain inputs (X is then not read)."""
         _check_residual(residual)
         if q_shape not in ("fullrank", "diagonal"):
             raise ValueError("q_shape must be 'fullrank' or 'diagonal', got %r" % (q_shape,))
@@ -205,7 +248,8 @@ class SparseInference:
             sum_p [ -N/2 log(2 pi noise_var) - yy_p / (2 noise_var) + 1/2 c_p^T Lambda^-1 c_p ] - P/2 log|Lambda|
             - P k_var (N - a2sum) / (2 noise_var)          ('diagonal'; 'neglected' drops the last term).
         N - a2sum is sum_j (kdiag_j - sum_m A_mj^2) for the unit-variance kernel.  samples() takes the absolute value of
-        that difference per point, so the two agree except where round-off makes a term negative."""
+        that difference per point, so the two agree except where round-off makes a term negative.  `stats` may come
+        from psi_statistics(X_mean, X_var, Y): the bound under uncertain inputs (only the row count of X is read)."""
         _check_residual(residual)
         if stats is None:
             stats = self.statistics(X, Y)
@@ -1017,6 +1061,33 @@ class SparsePosterior:
         z, ell, W, m, s = self._model()
         mean, var = H.sgp_predict(self._points(X), z, ell, W, m.reshape(1, -1), s, **self._kw())
         return np.sqrt(self.k_var) * mean.cpu().numpy().reshape(-1), self.k_var * var.cpu().numpy().reshape(-1)
+
+    def predict_uncertain(self, X_mean, X_var):
+        """(mean [n], var [n]) of f at GAUSSIAN inputs x*_j ~ N(X_mean_j, diag(X_var_j)), as numpy float64: the exact first
+        two moments of f(x*) over both the posterior and the input (Girard et al. 2003; Quinonero-Candela et al. 2003),
+            beta = W^T m,   Q = W^T (rho I - S S^T) W - beta beta^T        (rho = 1 for 'diagonal', 0 for 'neglected')
+            mean = sqrt(k_var) beta^T psi1,   var = k_var (rho - sum_mm' Q_mm' psi2(m, m') - (beta^T psi1)^2),
+        the law of total variance over the conditional k_var (rho (1 - sum A^2) + |S^T A|^2), with psi1 = E k(z, x*),
+        psi2 = E k(z, x*) k(x*, z) (hb_sgp_psi_predict).  X_var: [n, d], [d] or a scalar, finite and >= 0 (ValueError
+        otherwise).  predict() takes |1 - sum A^2|; an absolute value cannot pass through the expectation, so this
+        takes the difference itself: with X_var = 0 the two agree wherever 1 - sum A^2 >= 0, which the jitter guarantees
+        up to round-off.  beta and Q are built in float64 from the snapshot (a mean-field q: S S^T = diag(s^2)), and the
+        expectations are evaluated in double whatever the session's dtype."""
+        sess = self._sess
+        torch, H = sess.torch, sess.H
+        Xd = self._points(X_mean, "X_mean")
+        Vd = _input_variance(sess, X_var, Xd, "predict_uncertain")
+        z, ell, W, m, s = self._model()
+        M = int(z.shape[0])
+        rho = 1.0 if self.residual == "diagonal" else 0.0
+        W64, s64 = W.to(torch.float64), s.to(torch.float64)
+        beta = H.matmul(m.to(torch.float64).reshape(1, M).contiguous(), W64)              # beta^T = m^T W  [1, M]
+        SS = H.matmul(s64, s64, transB=True) if s.dim() == 2 else torch.diag(s64 * s64)
+        inner = H.matutil((SS * -1.0).contiguous(), H.MATUTIL_ADD_EYE, alpha=rho)         # rho I - S S^T
+        Q = H.matmul(W64, H.matmul(inner, W64), transA=True) - H.matmul(beta, beta, transA=True)
+        e1, e2 = H.sgp_psi_predict(Xd, Vd, z, ell, beta.reshape(M), H.matutil(Q.contiguous(), H.MATUTIL_SYM))
+        e1, e2 = e1.cpu().numpy(), e2.cpu().numpy()
+        return np.sqrt(self.k_var) * e1, self.k_var * (rho - e2 - e1 * e1)
 
     def predict_grad(self, X):
         """(mean [n], var [n], dmean [n, d], dvar [n, d]): predict's moments and their exact input gradients

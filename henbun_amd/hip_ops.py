@@ -1420,6 +1420,62 @@ def sgp_stats(X, Y, z, ell, W, wfrag=None, ws=None):
     return Phi, b, yy, a2sum
 
 
+def sgp_psi_stats_ws_elems(dtype, N, M, d, P):
+    """Scratch elements hb_sgp_psi_stats needs: the partial tiles of the splits of N -- the same for every N >= 1."""
+    return _query("hb_sgp_psi_stats_ws_elems", N, M, d, P, _elem_bytes(dtype))
+
+
+def sgp_psi_stats(Xmean, Xvar, Y, z, ell, ws=None):
+    """Psi statistics of a data set with Gaussian inputs x_n ~ N(Xmean_n, diag(Xvar_n)) for the unit RBF kernel
+    (hb_sgp_psi_stats): (Psi2 [M, M] = sum_n E k(z, x_n) k(x_n, z), C [P, M] = (E K(z, X) Y)^T, yy [P] = sum_n Y_np^2) as
+    FLOAT64 device tensors, evaluated in double whatever the input dtype.  Xmean, Xvar [N, d] (Xvar >= 0, zeros included:
+    the caller's duty), Y [N, P], z [M, d], ell [dl].  Psi2 is bitwise symmetric; two calls return the same bits.  Cost:
+    N M (M + 1) / 2 double exponentials."""
+    if (Xmean.dim() != 2 or Y.dim() != 2 or z.dim() != 2 or Xvar.shape != Xmean.shape or Xmean.shape[0] != Y.shape[0]
+            or Xmean.shape[1] != z.shape[1]):
+        raise ValueError("sgp_psi_stats: Xmean [N, d], Xvar [N, d], Y [N, P], z [M, d] expected, got %s %s %s %s"
+                         % (tuple(Xmean.shape), tuple(Xvar.shape), tuple(Y.shape), tuple(z.shape)))
+    dt, dev = Xmean.dtype, Xmean.device
+    _operands("sgp_psi_stats", Xmean, Xvar, Y, z, ell)
+    N, d = Xmean.shape
+    M, P = z.shape[0], Y.shape[1]
+    Psi2 = _empty((M, M), dtype=torch.float64, device=dev)
+    C = _empty((P, M), dtype=torch.float64, device=dev)
+    yy = _empty((P,), dtype=torch.float64, device=dev)
+    ws = _ws("sgp_psi_stats", ws, dt, dev, sgp_psi_stats_ws_elems(dt, N, M, d, P), "sgp_psi_stats_ws_elems")
+    _lib.lib().call("hb_sgp_psi_stats" + _suf(Xmean), KERN_RBF, _p(Xmean), _p(Xvar), _p(Y), _p(z), _p(ell), ell.numel(),
+                    _p(Psi2), _p(C), _p(yy), N, M, d, P, _p(ws), stream())
+    return Psi2, C, yy
+
+
+def sgp_psi_predict_ws_elems(dtype, n, M, d):
+    """Scratch elements hb_sgp_psi_predict needs: two partial sums per point and workgroup of the point."""
+    return _query("hb_sgp_psi_predict_ws_elems", n, M, d, _elem_bytes(dtype))
+
+
+def sgp_psi_predict(Xmean, Xvar, z, ell, beta, Q, ws=None):
+    """(e1 [n], e2 [n]) as FLOAT64 device tensors (hb_sgp_psi_predict): e1_j = sum_m beta_m psi1_j(m), e2_j = sum_mm'
+    Q_mm' psi2_j(m, m') at Gaussian inputs N(Xmean_j, diag(Xvar_j)).  Xmean, Xvar [n, d], z [M, d], ell [dl] in one dtype;
+    beta [M] and Q [M, M] float64, Q symmetric (its lower triangle is read).  A point's result does not depend on the
+    other points of the call, bit for bit."""
+    if Xmean.dim() != 2 or z.dim() != 2 or Xvar.shape != Xmean.shape or Xmean.shape[1] != z.shape[1]:
+        raise ValueError("sgp_psi_predict: Xmean [n, d], Xvar [n, d], z [M, d] expected, got %s %s %s"
+                         % (tuple(Xmean.shape), tuple(Xvar.shape), tuple(z.shape)))
+    dt, dev = Xmean.dtype, Xmean.device
+    _operands("sgp_psi_predict", Xmean, Xvar, z, ell)
+    _operands("sgp_psi_predict", torch.float64, beta, Q, what="beta and Q must be float64")
+    n, d = Xmean.shape
+    M = z.shape[0]
+    _require(beta.numel() == M and tuple(Q.shape) == (M, M), "sgp_psi_predict",
+             "beta [%d] and Q [%d, %d] expected, got %s %s" % (M, M, M, tuple(beta.shape), tuple(Q.shape)))
+    e1 = _empty((n,), dtype=torch.float64, device=dev)
+    e2 = _empty((n,), dtype=torch.float64, device=dev)
+    ws = _ws("sgp_psi_predict", ws, dt, dev, sgp_psi_predict_ws_elems(dt, n, M, d), "sgp_psi_predict_ws_elems")
+    _lib.lib().call("hb_sgp_psi_predict" + _suf(Xmean), KERN_RBF, _p(Xmean), _p(Xvar), _p(z), _p(ell), ell.numel(), _p(beta),
+                    _p(Q), _p(e1), _p(e2), n, M, d, _p(ws), stream())
+    return e1, e2
+
+
 def sgp_wstats_ws_elems(dtype, N, M, d):
     """Scratch elements hb_sgp_wstats needs (those of hb_sgp_stats with P = 1; the same for every N above one chunk)."""
     return _query("hb_sgp_wstats_ws_elems", N, M, d, _elem_bytes(dtype))

@@ -199,15 +199,37 @@ class SVGP(hb.model.Model):
         self.initialize()
         return _part(self, "X"), _part(self, "Y"), _scalar(self, "var"), _scalar(self, "k_var")
 
-    def fit_q(self):
+    def _psi_stats(self, X_var):
+        """None, or the statistics of the model's X read as input MEANS with variances X_var (SparseGP.psi_statistics)."""
+        if X_var is None:
+            return None
+        X, Y, _, _ = self._closed_form_inputs()
+        return _part(self, "gp").psi_statistics(X, X_var, Y)
+
+    def fit_q(self, X_var=None):
         """Set q(u) to its closed-form optimum at the current z, lengthscales, k_var and var, from ONE pass over the
         model's full device-resident X, Y (SparseGP.optimal_q; not a minibatch, no Adam step).  u.q_mu / u.q_sqrt are
         written in their own parametrisation -- log standard deviations for q_shape 'diagonal' (the mean-field optimum),
-        the lower-triangular factor (packed or dense) for 'fullrank'.  Returns (m [1, M], S or s) as optimal_q does."""
+        the lower-triangular factor (packed or dense) for 'fullrank'.  Returns (m [1, M], S or s) as optimal_q does.
+        X_var ([N, d], [d] or a scalar): the model's X are the MEANS of Gaussian inputs with these variances (known input
+        noise), and q(u) is the optimum under them (SparseGP.psi_statistics)."""
         X, Y, var, k_var = self._closed_form_inputs()
-        m, S = _part(self, "gp").optimal_q(X, Y, var, k_var, q_shape=_part(self, "u").q_shape, residual=self.residual)
+        m, S = _part(self, "gp").optimal_q(X, Y, var, k_var, q_shape=_part(self, "u").q_shape, residual=self.residual,
+                                           stats=self._psi_stats(X_var))
         _write_q(self, m, S)
         return m, S
+
+    def predict_f_uncertain(self, Xmean, Xvar):
+        """Mean and variance of the latent f at Gaussian inputs N(Xmean_j, diag(Xvar_j)) -- the exact first two moments
+        over posterior and input -- as arrays [1, n] in the units of predict_f (SparsePosterior.predict_uncertain at the
+        model's q(u), k_var and residual).  Xvar: [n, d], [d] or a scalar."""
+        mean, var = self.posterior().predict_uncertain(np.asarray(Xmean), Xvar)
+        return mean.reshape(1, -1), var.reshape(1, -1)
+
+    def predict_y_uncertain(self, Xmean, Xvar):
+        """predict_f_uncertain plus the Gaussian likelihood's variance, in the units of predict_y."""
+        mean, var = self.predict_f_uncertain(Xmean, Xvar)
+        return mean, var + _scalar(self, "var")
 
     def select_inducing(self, threshold=None):
         """Move z to the M rows of the model's own full X that greedy conditional-variance selection picks at the current
@@ -216,11 +238,12 @@ class SVGP(hb.model.Model):
         self.initialize()
         return _part(self, "gp").select_inducing(_part(self, "X"), threshold=threshold)
 
-    def collapsed_bound(self):
+    def collapsed_bound(self, X_var=None):
         """The ELBO at the optimal q(u) for the current hyper-parameters (SparseGP.collapsed_bound on the full X, Y):
-        what fit_q() followed by an exact evaluation of ELBO over all rows would give."""
+        what fit_q() followed by an exact evaluation of ELBO over all rows would give.  X_var: as for fit_q -- the bound
+        under Gaussian inputs with means X and these variances."""
         X, Y, var, k_var = self._closed_form_inputs()
-        return _part(self, "gp").collapsed_bound(X, Y, var, k_var, residual=self.residual)
+        return _part(self, "gp").collapsed_bound(X, Y, var, k_var, residual=self.residual, stats=self._psi_stats(X_var))
 
     def _hyper_variables(self):
         """The Variables collapsed_bound() depends on, by the names the gradient uses."""

@@ -75,7 +75,9 @@ extern "C" {
  * the fixed-node value); hb_sgp_predict_multi_f32 / _f64, hb_sgp_predict_multi_ws_elems, hb_sgp_predict_multi_fused,
  * hb_lik_hetgauss_sites_f32 / _f64, hb_lik_hetgauss_predict_f32 / _f64, hb_lik_hetgauss_logdens_f32 / _f64,
  * hb_lik_hetgauss_ws_elems and HB_LIK_HETGAUSS (heteroscedastic regression: the marginals of C full-rank latent functions
- * from one pass, the two-latent Gaussian likelihood). */
+ * from one pass, the two-latent Gaussian likelihood); hb_sgp_psi_stats_f32 / _f64, hb_sgp_psi_stats_ws_elems,
+ * hb_sgp_psi_predict_f32 / _f64 and hb_sgp_psi_predict_ws_elems (psi statistics: the closed-form routes under uncertain
+ * inputs). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -754,6 +756,40 @@ int hb_sgp_mwstats_f32(int kind, const float* X, const float* w, const float* r,
 int hb_sgp_mwstats_f64(int kind, const double* X, const double* w, const double* r, long ldw, const double* z, const double* ell,
                        long dl, const double* W, const double* Wfrag, double* Phi, double* b, double* tr, long N, long M, long d,
                        long C, double* ws, void* stream);
+/* Psi statistics: the data pass of the closed-form routes under UNCERTAIN inputs x_n ~ N(Xmean_n, diag(Xvar_n)), Xvar >= 0
+ * (csrc/sgp_psi.hip; not in the reference).  For the unit RBF kernel with lengthscales l_k, a_k = 1 / (l_k^2 + 2 s_k):
+ *   psi1_n(m)     = prod_k (1 + s_k / l_k^2)^-1/2 exp(-1/2 sum_k (mu_k - z_mk)^2 / (l_k^2 + s_k))                 = E k(x_n, z_m)
+ *   psi2_n(m, m') = prod_k (1 + 2 s_k / l_k^2)^-1/2 exp(-1/2 sum_k a_k [(mu_k - z_mk)^2 + (mu_k - z_m'k)^2]
+ *                                                      - 1/4 sum_k (z_mk - z_m'k)^2 (1 / l_k^2 - a_k))  = E k(x_n, z_m) k(x_n, z_m')
+ *   Psi2 [M, M] = sum_n psi2_n,   C [P, M]: C[p, m] = sum_n psi1_n(m) Y[n, p],   yy [P] = sum_n Y[n, p]^2
+ * ALWAYS double, and ALL ARITHMETIC is double whatever the storage type (Phi = W Psi2 W^T amplifies an error of Psi2 by
+ * |W|^2 ~ 1 / jitter); the two entries differ in the type they load.  Xvar = 0 in any or all dimensions gives k(x, z_m) and
+ * k(x, z_m) k(x, z_m'); a term whose exponent underflows is 0.  Xmean, Xvar [N, d], Y [N, P], z [M, d] row-major, ell [dl],
+ * dl 1 or d; kind must be HB_KERN_RBF; N, M, P >= 1, 1 <= d <= 1535.  Cost: N M (M + 1) / 2 double exponentials on the vector
+ * unit -- Psi2 is no rank update once the variances differ from point to point.  Workgroups own a 64 x 64 lower-triangle
+ * tile of pairs times a split of N (a function of (N, M) alone), the splits' partial tiles go to ws and a second launch
+ * folds them in split order: no atomics, two calls return the same bits; Psi2 is written in full and bitwise symmetric.
+ * ws >= hb_sgp_psi_stats_ws_elems(N, M, d, P, sizeof(T)) elements of T, 16-byte aligned; the same for every N >= 1.
+ * Refused before any launch: another kind, extents < 1, dl not 1 or d, a NULL pointer, M * M >= 2^31. */
+long hb_sgp_psi_stats_ws_elems(long N, long M, long d, long P, int dtype_bytes);
+int hb_sgp_psi_stats_f32(int kind, const float* Xmean, const float* Xvar, const float* Y, const float* z, const float* ell,
+                         long dl, double* Psi2, double* C, double* yy, long N, long M, long d, long P, float* ws, void* stream);
+int hb_sgp_psi_stats_f64(int kind, const double* Xmean, const double* Xvar, const double* Y, const double* z, const double* ell,
+                         long dl, double* Psi2, double* C, double* yy, long N, long M, long d, long P, double* ws, void* stream);
+/* The two contractions the predictive moments at Gaussian test inputs need (csrc/sgp_psi.hip), per point j of Xmean,
+ * Xvar [n, d]:   e1[j] = sum_m beta[m] psi1_j(m),   e2[j] = sum_{m, m'} Q[m, m'] psi2_j(m, m')
+ * with beta [M] and Q [M, M] in double; Q is taken as symmetric: its lower triangle is read and the off-diagonal terms
+ * doubled.  psi1, psi2 are the functions of hb_sgp_psi_stats_*, evaluated by the same device code.  The pairs of one point
+ * are spread over workgroups whose number depends on M alone and are summed in a fixed order: a point's result does not
+ * depend on the other points of the call, bit for bit.  n = 0 returns 0 without a launch.
+ * ws >= hb_sgp_psi_predict_ws_elems(n, M, d, sizeof(T)) elements of T, 16-byte aligned.  Refusals as above. */
+long hb_sgp_psi_predict_ws_elems(long n, long M, long d, int dtype_bytes);
+int hb_sgp_psi_predict_f32(int kind, const float* Xmean, const float* Xvar, const float* z, const float* ell, long dl,
+                           const double* beta, const double* Q, double* e1, double* e2, long n, long M, long d, float* ws,
+                           void* stream);
+int hb_sgp_psi_predict_f64(int kind, const double* Xmean, const double* Xvar, const double* z, const double* ell, long dl,
+                           const double* beta, const double* Q, double* e1, double* e2, long n, long M, long d, double* ws,
+                           void* stream);
 /* Sites of a factorising likelihood under Gaussian marginals (csrc/lik_sites.hip; not in the reference).  For
  * f_j ~ N(mu_j, v_j), mu_j = mscale mean[j], v_j = vscale var[j] (the scales take the unit-variance moments of
  * hb_sgp_predict_* to those of f = sqrt(k_var) (..): mscale = sqrt(k_var), vscale = k_var):
