@@ -450,7 +450,50 @@ class SparseInference:
             raise ValueError("noise_var and k_var must be positive (got %r, %r)" % (noise_var, k_var))
         sess, Xd, Yd, z, ell, W = self._grad_inputs(X, Y)
         stats = self._statistics_f64(sess, Xd, Yd, z, ell, W)
-        return self._grad_from_statistics(sess, Xd, Yd, z, ell, W, stats, noise_var, k_var, residual)
+        H = sess.H
+        return self._grad_from_statistics(sess, z, ell, W, stats, noise_var, k_var, residual,
+                                          lambda Q, R: H.sgp_kgrad(Xd, Yd, z, ell, Q, R), int(Xd.shape[0]), int(Yd.shape[1]))
+
+    def psi_bound_and_grad(self, X_mean, X_var, Y, noise_var, k_var=1.0, residual="diagonal"):
+        """collapsed_bound_and_grad() for UNCERTAIN inputs x_n ~ N(X_mean_n, diag(X_var_n)): (value, grad) with the
+        collapsed bound from the psi statistics (collapsed_bound(stats=psi_statistics(..)), evaluated in float64) and its
+        exact gradient with respect to the CONSTRAINED values, grad = dict(X_mean=[N, d], X_var, z=[M, d],
+        lengthscales=[dl], noise_var=float, k_var=float), float64 numpy.  X_var: [N, d], [d] or a scalar, as
+        psi_statistics takes it; grad["X_var"] has the shape given (the shared forms: summed over the points).  The
+        KL(q(X) || p(X)) of a latent-variable model is NOT part of it (models.BayesianGPLVM adds it on the host).
+
+        FLOAT64 ARITHMETIC end to end whatever the session's dtype, as collapsed_bound_and_grad: X_mean, X_var and Y are
+        up-converted (N (2 d + P) numbers), Psi2 and C come from hb_sgp_psi_stats_f64, the sandwich W Psi2 W^T from
+        hb_matmul_f64; the tail, the weights Q = 2 W^T G W, R = W^T g^T and the Cholesky / Gram VJP of K(z, z) are those of
+        collapsed_bound_and_grad, and the pass that turns (Q, R) into gradients is hb_sgp_psi_grad_f64: two passes of one
+        double exponential per point and pair of inducing points ("Bayesian GP-LVM").  X_var = 0 gives the z,
+        lengthscale and scalar gradients of collapsed_bound_and_grad(X_mean, Y, ..).  Restrictions and exception types are
+        those of psi_statistics and collapsed_bound_and_grad."""
+        _check_residual(residual)
+        if not (float(noise_var) > 0.0 and float(k_var) > 0.0):
+            raise ValueError("noise_var and k_var must be positive (got %r, %r)" % (noise_var, k_var))
+        who = "psi_bound_and_grad"
+        sess, Xd, Yd, z, ell, W = self._grad_inputs(X_mean, Y, who)
+        torch, H = sess.torch, sess.H
+        Vd = _input_variance(sess, X_var, Xd, who)
+        var_shape = tuple(X_var.shape) if isinstance(X_var, torch.Tensor) else np.shape(X_var)
+        mu, sv, Y64 = (t.to(torch.float64).contiguous() for t in (Xd, Vd, Yd))
+        Psi2, C, yy = H.sgp_psi_stats(mu, sv, Y64, z, ell)
+        Phi = H.matutil(H.matmul(W, H.matmul(Psi2, W, transB=True)), H.MATUTIL_SYM)
+        b = H.matmul(C, W, transB=True)
+        point = {}
+
+        def streamed(Q, R):
+            point["mu"], point["s"], zbar, ellbar = H.sgp_psi_grad(mu, sv, Y64, z, ell, Q, R)
+            return zbar, ellbar
+
+        val, grad = self._grad_from_statistics(sess, z, ell, W, (Phi, b, yy), noise_var, k_var, residual, streamed,
+                                               int(Xd.shape[0]), int(Yd.shape[1]))
+        sbar = point["s"]
+        if len(var_shape) < 2:                                               # a shared variance: summed over the points
+            sbar = sbar.sum(0) if len(var_shape) == 1 else sbar.sum()
+        grad["X_mean"], grad["X_var"] = point["mu"].cpu().numpy(), sbar.cpu().numpy()
+        return val, grad
 
     def _grad_inputs(self, X, Y, who="collapsed_bound_and_grad"):
         """(sess, Xd, Yd, z, ell, W): the data as the session stores it, z and the lengthscales as the session stores
@@ -479,20 +522,21 @@ class SparseInference:
         Phi, b, yy = _walk_f64(torch, Xd, Yd, z.shape[0], 1, per_chunk)
         return H.matutil(Phi.contiguous(), H.MATUTIL_SYM), b.contiguous(), torch.diagonal(yy).contiguous()
 
-    def _grad_from_statistics(self, sess, Xd, Yd, z, ell, W, stats, noise_var, k_var, residual):
-        """The tail and the two gradient passes of collapsed_bound_and_grad for given float64 (Phi, b, yy)."""
+    def _grad_from_statistics(self, sess, z, ell, W, stats, noise_var, k_var, residual, streamed, N, P):
+        """The tail and the two gradient passes of collapsed_bound_and_grad / psi_bound_and_grad for given float64
+        (Phi, b, yy) of N points and P outputs; `streamed(Q, R)` returns the part of (zbar, ellbar) through K(z, X) or
+        through the psi statistics (hb_sgp_kgrad / hb_sgp_psi_grad)."""
         torch, H = sess.torch, sess.H
         Phi, b, yy = stats
         s2, k = float(noise_var), float(k_var)
         rho = 1.0 if residual == "diagonal" else 0.0
-        N, P = int(Xd.shape[0]), int(Yd.shape[1])
         # tail: D = dF/dLambda, G = dF/dPhi, g = dF/db
         _, LL, V, t, c = self._lambda_solve((Phi, b), s2, k)                  # t [P, M], |t_p|^2 = c_p^T Lambda^-1 c_p
         m = H.matmul(t, V)                                                   # [P, M] = c Lambda^-1
         D = (H.matmul(m, m, transA=True, alpha=-0.5) - (0.5 * P) * H.matmul(V, V, transA=True)).contiguous()
         Gm = H.matutil((D * (k / s2)).contiguous(), H.MATUTIL_ADD_EYE, alpha=rho * P * k / (2.0 * s2))
         g = (m * (np.sqrt(k) / s2)).contiguous()
-        zg, eg = self._kernel_grads(sess, z, ell, W, Gm, g, Phi, b, lambda Q, R: H.sgp_kgrad(Xd, Yd, z, ell, Q, R))
+        zg, eg = self._kernel_grads(sess, z, ell, W, Gm, g, Phi, b, streamed)
         # scalars and the value, on the host
         tau, mb, mc = float((D * Phi).sum().cpu()), float((m * b).sum().cpu()), float((m * c).sum().cpu())
         a2sum, yys = float(torch.diagonal(Phi).sum().cpu()), float(yy.sum().cpu())

@@ -1476,6 +1476,39 @@ def sgp_psi_predict(Xmean, Xvar, z, ell, beta, Q, ws=None):
     return e1, e2
 
 
+def sgp_psi_grad_ws_elems(dtype, N, M, d, P):
+    """Scratch elements hb_sgp_psi_grad needs: the partials of its two passes -- the same for every N >= 1."""
+    return _query("hb_sgp_psi_grad_ws_elems", N, M, d, P, _elem_bytes(dtype))
+
+
+def sgp_psi_grad(Xmean, Xvar, Y, z, ell, Q, R, ws=None):
+    """Gradients of the psi statistics (hb_sgp_psi_grad): for F = 1/2 sum_n sum_mm' Q_mm' psi2_n(m, m') + sum_n sum_m
+    (R Y_n)_m psi1_n(m), returns (mubar [N, d], sbar [N, d], zbar [M, d], ellbar [dl]) = dF / d(Xmean, Xvar, z, ell) as
+    FLOAT64 device tensors, evaluated in double whatever the input dtype.  Xmean, Xvar [N, d] (Xvar >= 0: the caller's
+    duty), Y [N, P], z [M, d], ell [dl] in one dtype; Q [M, M] (symmetric: its lower triangle is read) and R [M, P]
+    float64.  Two calls return the same bits, and a point's rows of mubar, sbar do not depend on the other points."""
+    if (Xmean.dim() != 2 or Y.dim() != 2 or z.dim() != 2 or Xvar.shape != Xmean.shape or Xmean.shape[0] != Y.shape[0]
+            or Xmean.shape[1] != z.shape[1]):
+        raise ValueError("sgp_psi_grad: Xmean [N, d], Xvar [N, d], Y [N, P], z [M, d] expected, got %s %s %s %s"
+                         % (tuple(Xmean.shape), tuple(Xvar.shape), tuple(Y.shape), tuple(z.shape)))
+    dt, dev = Xmean.dtype, Xmean.device
+    _operands("sgp_psi_grad", Xmean, Xvar, Y, z, ell)
+    _operands("sgp_psi_grad", torch.float64, Q, R, what="Q and R must be float64")
+    N, d = Xmean.shape
+    M, P = z.shape[0], Y.shape[1]
+    _require(ell.dim() == 1 and ell.numel() in (1, d) and tuple(Q.shape) == (M, M) and tuple(R.shape) == (M, P), "sgp_psi_grad",
+             "ell [1] or [%d], Q [%d, %d], R [%d, %d] expected, got %s %s %s"
+             % (d, M, M, M, P, tuple(ell.shape), tuple(Q.shape), tuple(R.shape)))
+    mubar = _empty((N, d), dtype=torch.float64, device=dev)
+    sbar = _empty((N, d), dtype=torch.float64, device=dev)
+    zbar = _empty((M, d), dtype=torch.float64, device=dev)
+    ellbar = _empty((ell.numel(),), dtype=torch.float64, device=dev)
+    ws = _ws("sgp_psi_grad", ws, dt, dev, sgp_psi_grad_ws_elems(dt, N, M, d, P), "sgp_psi_grad_ws_elems")
+    _lib.lib().call("hb_sgp_psi_grad" + _suf(Xmean), KERN_RBF, _p(Xmean), _p(Xvar), _p(Y), _p(z), _p(ell), ell.numel(), _p(Q),
+                    _p(R), _p(mubar), _p(sbar), _p(zbar), _p(ellbar), N, M, d, P, _p(ws), stream())
+    return mubar, sbar, zbar, ellbar
+
+
 def sgp_wstats_ws_elems(dtype, N, M, d):
     """Scratch elements hb_sgp_wstats needs (those of hb_sgp_stats with P = 1; the same for every N above one chunk)."""
     return _query("hb_sgp_wstats_ws_elems", N, M, d, _elem_bytes(dtype))

@@ -251,26 +251,152 @@ class SVGP(hb.model.Model):
         return dict(z=_part(gp, "z"), lengthscales=_part(_part(gp, "kern"), "lengthscales"), k_var=_part(self, "k_var"),
                     var=_part(self, "var"))
 
-    def collapsed_bound_and_grad(self):
+    def collapsed_bound_and_grad(self, X_var=None):
         """(value, grad): the collapsed bound and its exact gradient with respect to the RAW (free) parameters,
         grad = dict(z, lengthscales, k_var, var) in the shapes of the raw arrays, float64 numpy.
         SparseGP.collapsed_bound_and_grad on the full X, Y (float64 arithmetic whatever the session's dtype), chained
-        through the transforms' dforward."""
+        through the transforms' dforward.  X_var ([N, d], [d] or a scalar; as for fit_q): the bound of
+        collapsed_bound(X_var=X_var) and its gradient under Gaussian inputs with means X and these variances
+        (SparseGP.psi_bound_and_grad; the gradients with respect to the inputs themselves are not returned)."""
         X, Y, var, k_var = self._closed_form_inputs()
-        value, gr = _part(self, "gp").collapsed_bound_and_grad(X, Y, var, k_var, residual=self.residual)
+        if X_var is None:
+            value, gr = _part(self, "gp").collapsed_bound_and_grad(X, Y, var, k_var, residual=self.residual)
+        else:
+            value, gr = _part(self, "gp").psi_bound_and_grad(X, X_var, Y, var, k_var, residual=self.residual)
         return value, _chain_to_raw(self, dict(z=gr["z"], lengthscales=gr["lengthscales"], k_var=gr["k_var"], var=gr["noise_var"]))
 
-    def fit_hyper(self, steps, lr=0.01, train_z=True):
+    def fit_hyper(self, steps, lr=0.01, train_z=True, X_var=None):
         """Full-batch fit of the hyper-parameters: `steps` Adam ASCENT steps on the collapsed bound in the raw
         parameters of lengthscales, k_var, var and (train_z) z, on the host in float64 with the exact gradient of
         collapsed_bound_and_grad -- M d + dl + 2 numbers, two passes over the data per step, no minibatch noise.  The
         parameters are written back after every step and q(u) is set to its optimum (fit_q) at the end.  Returns the
         trace of bound values, steps + 1 entries: before the first step .. at the final parameters.  A step after
         which K(z, z) + jitter I or Lambda is no longer positive definite raises graph.CholeskyError with the last good
-        parameters restored."""
-        trace = _adam_ascent(self, self.collapsed_bound_and_grad, steps, lr, train_z)
-        self.fit_q()
+        parameters restored.  X_var: known input noise, as for fit_q -- the fit climbs collapsed_bound(X_var=X_var) and
+        ends with fit_q(X_var=X_var)."""
+        if X_var is None:
+            trace = _adam_ascent(self, self.collapsed_bound_and_grad, steps, lr, train_z)
+        else:
+            trace = _adam_ascent(self, lambda: self.collapsed_bound_and_grad(X_var=X_var), steps, lr, train_z)
+        self.fit_q(X_var=X_var)
         return trace
+
+
+class BayesianGPLVM(hb.model.Model):
+    """Bayesian GP latent-variable model (Titsias & Lawrence 2010): Y [N, P] = f(X) + noise with UNOBSERVED inputs, a
+    variational q(X) = prod_n N(X_mean_n, diag(X_var_n)) over a latent space of `latent_dim` dimensions, the prior
+    p(X) = N(0, I), a sparse GP with ARD lengthscales (one per latent dimension: a dimension the data do not need is
+    switched off by a long lengthscale) and full-batch training on the collapsed bound from psi statistics minus
+    KL(q(X) || p(X)):
+        m = BayesianGPLVM(Y=Y, latent_dim=2, M=16);  trace = m.fit(200, lr=0.05);  mean, var = m.latent()
+    X_mean: initial means [N, Q] (None: the first Q principal components of Y, scaled to unit variance); X_var: initial
+    variances (a scalar or [N, Q]); Z: inducing points [M, Q] (None: hb.gp.greedy_inducing on the initial means).  Not in
+    scope: a sampled ELBO, minibatches, back-constraints, the latent of a new observation, other priors."""
+
+    def setUp(self, Y, latent_dim, M, X_mean=None, X_var=0.1, Z=None):
+        Y = np.asarray(Y)
+        N, Q = Y.shape[0], int(latent_dim)
+        if X_mean is None:
+            Yc = np.asarray(Y, np.float64) - np.mean(Y, 0)
+            _, _, Vt = np.linalg.svd(Yc, full_matrices=False)
+            X_mean = np.zeros((N, Q))
+            r = min(Q, Vt.shape[0])
+            X_mean[:, :r] = Yc @ Vt[:r].T
+            sd = X_mean.std(0)
+            X_mean = X_mean / np.where(sd > 0, sd, 1.0)
+        X_mean = np.asarray(X_mean, np.float64)
+        X_var = np.array(np.broadcast_to(np.asarray(X_var, np.float64), (N, Q)))
+        if X_mean.shape != (N, Q) or not (np.all(np.isfinite(X_var)) and np.all(X_var > 0)):
+            raise ValueError("BayesianGPLVM: X_mean must be [%d, %d] and X_var positive, a scalar or [%d, %d]" % (N, Q, N, Q))
+        if Z is None:
+            Z = hb.gp.greedy_inducing(X_mean, M, np.ones(Q), dtype=self._session.np_dtype)
+        Z = np.asarray(Z, np.float64)
+        if Z.shape != (int(M), Q):
+            raise ValueError("BayesianGPLVM: Z must be [%d, %d], got %s" % (int(M), Q, Z.shape))
+        self.Y = hb.param.Data(Y)
+        self.X_mean = hb.param.Variable([N, Q])
+        self.X_mean = X_mean
+        self.X_var = hb.param.Variable([N, Q], transform=hb.transforms.positive)
+        self.X_var = X_var
+        self.gp = hb.gp.SparseGP(kern=hb.gp.kernels.UnitRBF(np.ones(Q)), z=Z)
+        self.k_var = hb.param.Variable([1], transform=hb.transforms.positive)
+        self.var = hb.param.Variable([1], transform=hb.transforms.positive)
+        scale = float(np.mean(np.var(np.asarray(Y, np.float64), 0)))      # initial k_var: the mean column variance of Y
+        self.k_var = np.ones(1) * (scale if scale > 0 else 1.0)
+        self.var = np.ones(1) * (0.1 * scale if scale > 0 else 0.1)        # initial noise variance: a tenth of it
+        self.residual = "diagonal"
+
+    def _hyper_variables(self):
+        """The Variables bound() depends on, by the names the gradient uses."""
+        gp = _part(self, "gp")
+        return dict(X_mean=_part(self, "X_mean"), X_var=_part(self, "X_var"), z=_part(gp, "z"),
+                    lengthscales=_part(_part(gp, "kern"), "lengthscales"), k_var=_part(self, "k_var"), var=_part(self, "var"))
+
+    def _inputs(self):
+        """(X_mean [N, Q], X_var [N, Q] as the session stores them, float64 numpy; Y; noise variance; k_var)."""
+        self.initialize()
+        sess = self._session
+        mu, s = (np.asarray(sess.read_value(_part(self, n)), np.float64) for n in ("X_mean", "X_var"))
+        return mu, s, _part(self, "Y"), _scalar(self, "var"), _scalar(self, "k_var")
+
+    def latent(self):
+        """(mean [N, Q], var [N, Q]) of q(X), float64 numpy."""
+        mu, s, _, _, _ = self._inputs()
+        return mu, s
+
+    @staticmethod
+    def _kl(mu, s):
+        """KL(q(X) || N(0, I)) and its gradients with respect to the means and the variances, on the host in double."""
+        return 0.5 * float(np.sum(s + mu * mu - 1.0 - np.log(s))), mu, 0.5 * (1.0 - 1.0 / s)
+
+    def bound(self):
+        """The collapsed bound from psi statistics (SparseGP.collapsed_bound(stats=psi_statistics(..))) minus
+        KL(q(X) || p(X)): a lower bound of log p(Y)."""
+        mu, s, Y, var, k_var = self._inputs()
+        gp = _part(self, "gp")
+        return (gp.collapsed_bound(mu, Y, var, k_var, residual=self.residual, stats=gp.psi_statistics(mu, s, Y))
+                - self._kl(mu, s)[0])
+
+    def bound_and_grad(self):
+        """(value, grad): the bound of bound(), evaluated in float64 (SparseGP.psi_bound_and_grad), and its exact gradient
+        with respect to the RAW (free) parameters, grad = dict(X_mean, X_var, z, lengthscales, k_var, var) in the shapes of
+        the raw arrays, float64 numpy.  The KL term and its gradient are added on the host in double."""
+        mu, s, Y, var, k_var = self._inputs()
+        value, gr = _part(self, "gp").psi_bound_and_grad(mu, s, Y, var, k_var, residual=self.residual)
+        kl, kl_mu, kl_s = self._kl(mu, s)
+        cons = dict(X_mean=gr["X_mean"] - kl_mu, X_var=gr["X_var"] - kl_s, z=gr["z"], lengthscales=gr["lengthscales"],
+                    k_var=gr["k_var"], var=gr["noise_var"])
+        return value - kl, _chain_to_raw(self, cons)
+
+    def fit(self, steps, lr=0.01, train_z=True):
+        """Full-batch fit: `steps` Adam ASCENT steps on bound_and_grad in the raw parameters of q(X), the lengthscales,
+        k_var, var and (train_z) z, on the host in float64 (the loop of SVGP.fit_hyper).  Returns the trace of bound
+        values, steps + 1 entries: before the first step .. at the final parameters."""
+        return _adam_ascent(self, self.bound_and_grad, steps, lr, train_z)
+
+    def fit_q(self):
+        """(m [P, M], S [M, M]): the optimal q(u) at the current parameters under q(X) (SparseGP.optimal_q with the psi
+        statistics), float64 numpy; S is shared by the P outputs."""
+        mu, s, Y, var, k_var = self._inputs()
+        gp = _part(self, "gp")
+        return gp.optimal_q(mu, Y, var, k_var, residual=self.residual, stats=gp.psi_statistics(mu, s, Y))
+
+    def predict_y(self, Xnew):
+        """(mean [n, P], var [n]) of a new observation at the latent points Xnew [n, Q] under the optimal q(u) of
+        fit_q(); S is shared by the outputs, so the variance is too.  Float64 on the device (hb_sgp_A_f64, hb_matmul_f64)."""
+        m, S = self.fit_q()
+        mu, _, Y, var, k_var = self._inputs()
+        sess, _, _, z, ell, W = _part(self, "gp")._grad_inputs(mu, Y, "predict_y")
+        torch, H = sess.torch, sess.H
+        Xnew = np.asarray(Xnew, np.float64)
+        if Xnew.ndim != 2 or Xnew.shape[1] != mu.shape[1]:
+            raise ValueError("predict_y: Xnew must be [n, %d], got %s" % (mu.shape[1], Xnew.shape))
+        A = H.sgp_A(upload(sess, Xnew, carry=np.float64), z, ell, W)                          # [M, n]
+        md, Sd = (upload(sess, a, dtype=np.float64) for a in (m, S))
+        mean = H.matmul(A, md, transA=True, transB=True) * np.sqrt(k_var)                   # [n, P]
+        SA = H.matmul(Sd, A, transA=True)
+        v = k_var * ((1.0 - (A * A).sum(0)) + (SA * SA).sum(0)) + var
+        return mean.cpu().numpy(), v.cpu().numpy()
 
 
 class SVGPLik(hb.model.Model):

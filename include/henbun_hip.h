@@ -77,7 +77,7 @@ extern "C" {
  * hb_lik_hetgauss_ws_elems and HB_LIK_HETGAUSS (heteroscedastic regression: the marginals of C full-rank latent functions
  * from one pass, the two-latent Gaussian likelihood); hb_sgp_psi_stats_f32 / _f64, hb_sgp_psi_stats_ws_elems,
  * hb_sgp_psi_predict_f32 / _f64 and hb_sgp_psi_predict_ws_elems (psi statistics: the closed-form routes under uncertain
- * inputs). */
+ * inputs); hb_sgp_psi_grad_f32 / _f64 and hb_sgp_psi_grad_ws_elems (their gradients: the Bayesian GP-LVM). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -790,6 +790,27 @@ int hb_sgp_psi_predict_f32(int kind, const float* Xmean, const float* Xvar, cons
 int hb_sgp_psi_predict_f64(int kind, const double* Xmean, const double* Xvar, const double* z, const double* ell, long dl,
                            const double* beta, const double* Q, double* e1, double* e2, long n, long M, long d, double* ws,
                            void* stream);
+/* Gradients of the psi statistics (csrc/sgp_psi_grad.hip; not in the reference).  For a bound that depends on the per-point
+ * statistics of hb_sgp_psi_stats_* as
+ *   F = 1/2 sum_n sum_{m, m'} Q[m, m'] psi2_n(m, m') + sum_n sum_m rho_nm psi1_n(m),   rho_nm = sum_p R[m, p] Y[n, p]
+ * (Q [M, M] symmetric -- its lower triangle is read -- and R [M, P] in double: Q = 2 W^T G W, R = W^T g^T of the collapsed
+ * bound), the four gradients, all double and overwritten:
+ *   mubar [N, d] = dF/dXmean,  sbar [N, d] = dF/dXvar,  zbar [M, d] = dF/dz,  ellbar [dl] = dF/dell (dl = 1: summed over d)
+ * through psi1 and psi2 only (the part through K(z, z) is the caller's).  ALL ARITHMETIC is double whatever the storage
+ * type.  Xvar = 0 is exact (no log s is taken); a point whose exponents underflow contributes exact zeros.  Two passes of
+ * one exponential per (point, pair of the lower triangle) each: a point-major one for mubar, sbar (one thread per point,
+ * the rows of the triangle split over workgroups by a rule of M alone: a point's result does not depend on the other points
+ * of the call, bit for bit) and a pair-major one for zbar, ellbar (the tiles and register blocks of hb_sgp_psi_stats_*).
+ * Partials go to ws and are folded in a fixed order by further launches: no atomics, two calls return the same bits.
+ * ws >= hb_sgp_psi_grad_ws_elems(N, M, d, P, sizeof(T)) elements of T, 16-byte aligned; the same for every N >= 1 (N is
+ * walked in chunks).  Refusals, before any launch, as hb_sgp_psi_stats_*. */
+long hb_sgp_psi_grad_ws_elems(long N, long M, long d, long P, int dtype_bytes);
+int hb_sgp_psi_grad_f32(int kind, const float* Xmean, const float* Xvar, const float* Y, const float* z, const float* ell,
+                        long dl, const double* Q, const double* R, double* mubar, double* sbar, double* zbar, double* ellbar,
+                        long N, long M, long d, long P, float* ws, void* stream);
+int hb_sgp_psi_grad_f64(int kind, const double* Xmean, const double* Xvar, const double* Y, const double* z, const double* ell,
+                        long dl, const double* Q, const double* R, double* mubar, double* sbar, double* zbar, double* ellbar,
+                        long N, long M, long d, long P, double* ws, void* stream);
 /* Sites of a factorising likelihood under Gaussian marginals (csrc/lik_sites.hip; not in the reference).  For
  * f_j ~ N(mu_j, v_j), mu_j = mscale mean[j], v_j = vscale var[j] (the scales take the unit-variance moments of
  * hb_sgp_predict_* to those of f = sqrt(k_var) (..): mscale = sqrt(k_var), vscale = k_var):

@@ -166,7 +166,9 @@ def precision(lines):
             try:
                 st = gp.statistics(g(m, "X"), g(m, "Y"))
                 inp = gp._grad_inputs(g(m, "X"), g(m, "Y"))
-                _, gb = gp._grad_from_statistics(*inp, (st[0], st[1], st[2]), 0.09, 1.0, "diagonal")
+                ss, Xd_, Yd_, z_, l_, W_ = inp
+                _, gb = gp._grad_from_statistics(ss, z_, l_, W_, (st[0], st[1], st[2]), 0.09, 1.0, "diagonal",
+                                                 lambda Q, R: ss.H.sgp_kgrad(Xd_, Yd_, z_, l_, Q, R), Xd_.shape[0], Yd_.shape[1])
                 eb = "%.2g" % (np.abs(gb["z"] - a["z"]).max() / zmax)
             except hb.graph.CholeskyError as e:
                 eb = "fp32 factorisation failed"
