@@ -22,41 +22,34 @@ def _check_residual(residual):
         raise ValueError("residual must be 'diagonal' or 'neglected', got %r" % (residual,))
 
 
-def _check_lik_inputs(who, likelihood, k_var, residual, q, Yd, M):
-    """The argument checks natgrad_q and elbo_and_grad share: residual, a henbun_amd.likelihoods.Likelihood (TypeError),
-    k_var > 0, Y [N, 1] and q = (m [1, M], S [M, M]) or None.  Returns (m, S) as float64 numpy, or None."""
+def _check_lik_inputs(who, name, likelihood, k_var, residual, q, Y, M=None):
+    """The argument checks natgrad_q, elbo_and_grad and elbo_and_grad_multi share, all decided on the host before the
+    session is touched: residual, a henbun_amd.likelihoods.Likelihood (TypeError), k_var > 0, the targets by the
+    likelihood's own rule (Likelihood.check_targets: Y [N, 1]; a numpy Y also by value) and q (`name`: what the route calls
+    it) as the blocks of C = likelihood.num_latent latent functions, (m [C, M], S [C, M, M]) -- for C = 1 the public form
+    (m [1, M], S [M, M]) is lifted to its one block.  M: the number of inducing points, where it is known.  Returns (m, S)
+    as float64 numpy, or None for q = None."""
     _check_residual(residual)
     if not isinstance(likelihood, Likelihood):
         raise TypeError("%s: likelihood must be a henbun_amd.likelihoods.Likelihood, got %s" % (who, type(likelihood).__name__))
     if not float(k_var) > 0.0:
         raise ValueError("%s: k_var must be positive (got %r)" % (who, k_var))
-    if Yd.shape[1] != 1:
-        raise NotImplementedError("%s: one latent function only (Y must be [N, 1], got %s)" % (who, tuple(Yd.shape)))
-    if q is None:
-        return None
-    m0, S0 = (np.asarray(a, dtype=np.float64) for a in q)
-    if S0.ndim != 2:
-        raise NotImplementedError("%s: q must be a full-rank q, (m [1, M], S [M, M]); a mean-field q is not covered" % who)
-    if m0.size != M or S0.shape != (M, M):
-        raise ValueError("%s: q = (m [1, %d], S [%d, %d]) expected, got %s %s" % (who, M, M, M, m0.shape, S0.shape))
-    return m0, S0
-
-
-def _check_blocks_and_targets(who, name, likelihood, q, Y):
-    """The host-side checks of a multi-latent route on q = (m [C, M], S [C, M, M]) (None: not given) and on a numpy Y
-    [N, 1] of targets, by the likelihood's own rule (Softmax: labels in 0 .. C-1; HeteroscedasticGaussian: finite numbers;
-    targets already on the device are the caller's duty).  Returns (m, S) as float64 numpy, or (None, None)."""
-    C = int(likelihood.num_latent)
-    m0 = S0 = None
-    if q is not None:
-        m0, S0 = (np.asarray(a, dtype=np.float64) for a in q)
-        if S0.ndim == 2 and S0.shape == m0.shape:
-            raise NotImplementedError("%s: %s must be full-rank, (m [C, M], S [C, M, M]); a mean-field q is not covered"
-                                      % (who, name))
-        if m0.ndim != 2 or m0.shape[0] != C or S0.shape != (C, m0.shape[1], m0.shape[1]):
-            raise ValueError("%s: %s = (m [%d, M], S [%d, M, M]) expected, got %s %s" % (who, name, C, C, m0.shape, S0.shape))
     if isinstance(Y, np.ndarray):
         likelihood.check_targets(who, Y)
+    if q is None:
+        return None
+    C = int(likelihood.num_latent)
+    form = "%s = (m [%d, %%s], S [%s%%s, %%s])" % (name, C, "%d, " % C if C > 1 else "")
+    m0, S0 = (np.asarray(a, dtype=np.float64) for a in q)
+    got = "got %s %s" % (m0.shape, S0.shape)
+    if C == 1 and S0.ndim < 3:
+        m0, S0 = m0.reshape(1, -1), S0[None]
+    if S0.ndim == 2 and S0.shape == m0.shape:
+        raise NotImplementedError("%s: %s must be full-rank; a mean-field q is not covered" % (who, form % ("M", "M", "M")))
+    if m0.ndim != 2 or m0.shape[0] != C or S0.shape != (C, m0.shape[1], m0.shape[1]):
+        raise ValueError("%s: %s expected, %s" % (who, form % ("M", "M", "M"), got))
+    if M is not None and m0.shape[1] != M:
+        raise ValueError("%s: %s expected, %s" % (who, form % (M, M, M), got))
     return m0, S0
 
 
@@ -72,6 +65,28 @@ def _q_cov(H, V, who):
     """(Sigma, S) on top of _q_tail: Sigma = Lambda^-1 = V^T V and its lower factor S (one more read-back)."""
     Sig = H.matmul(V, V, transA=True)
     return Sig, _host.factor(H, Sig, who, "Lambda^-1")
+
+
+def _marginals(H, likelihood, X, z, ell, W, m, S, mode, out, wfrag=None):
+    """The unit-variance marginals of the C latent functions at X under the blocks m [C, M], S [C, M, M], into out =
+    (mean, var) [C, n]: ONE hb_sgp_predict_multi (A = W K(z, X) formed once for all C) where the likelihood asks for it
+    (Likelihood.fused_marginals), else C calls of hb_sgp_predict -- the same bits (hip_ops.sgp_predict_multi)."""
+    if likelihood.fused_marginals:
+        H.sgp_predict_multi(X, z, ell, W, m, S, mode=mode, out=out, wfrag=wfrag)
+    else:
+        for c in range(m.shape[0]):
+            H.sgp_predict(X, z, ell, W, m[c:c + 1], S[c], s_kind=H.SGP_S_TRIL, mode=mode,
+                          out=(out[0][c:c + 1], out[1][c:c + 1]), wfrag=wfrag)
+
+
+def _weighted_stats(H, X, w, r, z, ell, W, wfrag=None):
+    """(Phi [C, M, M], b [C, M]) float64 of the weight sets w, r [C, n]: Phi_c = A diag(w_c) A^T, b_c = (A r_c)^T.  One set
+    is hb_sgp_wstats, several are ONE hb_sgp_mwstats (A formed once per chunk for all of them).  Set by set the two return
+    the same bits (hip_ops.sgp_mwstats), but hb_sgp_mwstats has not been timed at C = 1, so one set keeps its own entry."""
+    if w.shape[0] == 1:
+        Phi, b, _ = H.sgp_wstats(X, w, r, z, ell, W, wfrag=wfrag)
+        return Phi[None], b
+    return H.sgp_mwstats(X, w, r, z, ell, W, wfrag=wfrag)[:2]
 
 
 def _input_variance(sess, X_var, Xd, who):
@@ -261,119 +276,57 @@ class SparseInference:
         logdet = 2.0 * float(np.log(np.diagonal(L.cpu().numpy())).sum())
         return _host.collapsed_value(N, yy.shape[0], noise_var, k_var, yy, quad, logdet, a2sum, residual)
 
+    def _inducing_count(self):
+        """M of a z [M, d], read without touching the session (None for another shape: _stats_session refuses it)."""
+        zshape = tuple(object.__getattribute__(self, "z").shape)
+        return zshape[0] if len(zshape) == 2 else None
+
     def natgrad_q(self, X, Y, likelihood, k_var=1.0, residual="diagonal", q0=None, steps=20, rho=1.0, tol=1e-8):
-        """Natural-gradient fit of q(u) = N(m, S S^T) for a factorising likelihood (henbun_amd.likelihoods: Gaussian,
-        Bernoulli, Poisson, Laplace, Gamma, Exponential, NegativeBinomial, Binomial -- all log-concave in f, so lam_j >= 0
-        and Lambda stays positive definite) at fixed hyper-parameters, for the whitened model u ~ N(0, I), f = sqrt(k_var) (u A +
-        residual), y_j ~ p(y_j | f_j).  q is kept as Lambda = (S S^T)^-1, eta = Lambda m; one step is the conjugate
-        update with per-point pseudo-observations (conjugate-computation VI, Khan & Lin 2017):
-            mu_j, v_j            the marginals of f_j under q                         (hb_sgp_predict, one pass over X)
-            lam_j, beta_j, l_j   E[-d2 log p], E[d log p] + lam_j mu_j, E[log p]      (hb_lik_sites)
-            Phi = A diag(lam) A^T,  b = A beta                                        (hb_sgp_wstats, one pass over X)
-            Lambda <- (1 - rho) Lambda + rho (I + k_var Phi),   eta <- (1 - rho) eta + rho sqrt(k_var) b
-        and m = Lambda^-1 eta, S = chol(Lambda^-1) from the float64 tail of optimal_q.  With the Gaussian likelihood one
-        step at rho = 1 is optimal_q.  K(z, z) is factorised once per call, from z and the lengthscales as the session's
-        plans transform them on the device, so the q(u) returned lives in the whitening predict_f and the ELBO use.
-        Returns (m [1, M], S [M, M] lower with a positive diagonal, info) as float64 numpy; info = dict(elbo, residual,
-        steps): the ELBO sum_j l_j - KL(q || N(0, I)) and the fixed-point residual max|Lambda - (I + k_var Phi)| /
-        max|I + k_var Phi| at every iterate, the starting one included (steps + 1 entries), and the steps taken.  m, S
-        are the last iterate evaluated.  q0=None starts at the prior; q0 = (m, S) at a given full-rank q.  Stops when
-        the relative change of the ELBO is <= tol, or after `steps`.  X, Y as for statistics(), Y [N, 1].  Same
-        restrictions and exception types as statistics(); residual 'fullrank' and a mean-field q0 raise
-        NotImplementedError; a Lambda that is not positive definite raises graph.CholeskyError.  A full step (rho = 1)
-        is not guaranteed to raise the ELBO from a q far from the optimum (info['elbo'] shows an overshoot): start at
-        the prior or damp with rho < 1.
-
-        A likelihood with num_latent = C > 1 (likelihoods.Softmax, likelihoods.HeteroscedasticGaussian) fits C
-        independent q(u_c) that share z, the lengthscales and W: see _natgrad_q_multi for its Y, q0 and return shapes."""
-        if getattr(likelihood, "num_latent", 1) > 1:
-            return self._natgrad_q_multi(X, Y, likelihood, k_var, residual, q0, steps, rho, tol)
-        sess, zvar, ls = self._stats_session("natgrad_q")
-        torch, H = sess.torch, sess.H
-        Xd, Yd = _host.device_data(sess, X, "X"), _host.device_data(sess, Y, "Y")
-        M = int(zvar.shape[0])
-        q0 = _check_lik_inputs("natgrad_q", likelihood, k_var, residual, q0, Yd, M)
-        k_var, rho, steps = float(k_var), float(rho), int(steps)
-        if not (0.0 < rho <= 1.0 and steps >= 0):
-            raise ValueError("natgrad_q: 0 < rho <= 1 and steps >= 0 expected (got %r, %r)" % (rho, steps))
-        z, ell, W, frag = self._whitening(sess, zvar, ls, Xd, Yd, "natgrad_q", as_plans=True)
-        N, d = Xd.shape
-        f64 = dict(dtype=torch.float64, device=sess.device)
-        if q0 is None:
-            Lam, eta = torch.eye(M, **f64), torch.zeros((1, M), **f64)
-        else:
-            Sinv = H.trinv(_host.upload(sess, np.tril(q0[1]), np.float64))
-            Lam = H.matmul(Sinv, Sinv, transA=True)
-            eta = H.matmul(_host.upload(sess, q0[0].reshape(1, M), np.float64), Lam)
-        mode = H.SGP_DIAGONAL if residual == "diagonal" else H.SGP_NEGLECTED
-        fused = bool(getattr(settings.runtime, "fused_predict", True)) and H.sgp_predict_fused(
-            sess.torch_dtype, 1, N, M, d, 1, H.SGP_S_TRIL, frag is not None)
-        mean = torch.empty((1, N), dtype=sess.torch_dtype, device=sess.device)
-        var, lam, beta = (torch.empty_like(mean) for _ in range(3))
-        eye = torch.eye(M, **f64)
-        elbo, resid = [], []
-        for it in range(steps + 1):
-            who = "natgrad_q (step %d)" % it
-            L, V, t = _q_tail(H, Lam, eta, who)
-            m = H.matmul(t, V)
-            Sig, S = _q_cov(H, V, who)
-            H.sgp_predict(Xd, z, ell, W, m.to(sess.torch_dtype), S.to(sess.torch_dtype), s_kind=H.SGP_S_TRIL, mode=mode,
-                          out=(mean, var), wfrag=frag if fused else None)
-            _, _, lsum = H.lik_sites(likelihood.lik_id, Yd, mean, var, param=likelihood.param, mscale=np.sqrt(k_var),
-                                     vscale=k_var, out=(lam, beta))
-            Phi, b, _ = H.sgp_wstats(Xd, lam, beta, z, ell, W, wfrag=frag)
-            Lt, et = Phi * k_var + eye, b * np.sqrt(k_var)
-            # KL(q || N(0, I)) from Sigma and the factor of Lambda.  elbo_and_grad forms it from S instead: equal in
-            # exact arithmetic, not in the last bits, so neither borrows the other's
-            kl = 0.5 * (float(torch.diagonal(Sig).sum().cpu()) + float((m * m).sum().cpu()) - M
-                        + 2.0 * float(np.log(np.diagonal(L.cpu().numpy())).sum()))
-            elbo.append(float(lsum.cpu()[0]) - kl)
-            resid.append(float(((Lam - Lt).abs().max() / Lt.abs().max()).cpu()))
-            if it == steps or (it > 0 and abs(elbo[-1] - elbo[-2]) <= tol * abs(elbo[-1])):
-                break
-            Lam, eta = (1.0 - rho) * Lam + rho * Lt, (1.0 - rho) * eta + rho * et
-        return (m.cpu().numpy(), np.tril(S.cpu().numpy()),
-                dict(elbo=np.asarray(elbo), residual=np.asarray(resid), steps=it))
-
-    def _natgrad_q_multi(self, X, Y, likelihood, k_var, residual, q0, steps, rho, tol):
-        """natgrad_q for a likelihood over C = likelihood.num_latent latent functions (likelihoods.Softmax): the whitened
-        model u_c ~ N(0, I_M) independent, f_c = sqrt(k_var) (u_c A + residual), y_j in {0 .. C-1}, with C independent
-        q(u_c) = N(m_c, S_c S_c^T) kept as Lambda_c, eta_c.  One step:
-            mu_jc, v_jc              C calls of hb_sgp_predict, one per (m_c, S_c)
-            lam_jc, beta_jc, l_j     ONE hb_lik_softmax_sites over the likelihood's nodes [S, C]
-            Phi_c, b_c               ONE hb_sgp_mwstats: A = W K(z, X) is formed once per chunk for all C weight sets
+        """Natural-gradient fit of q(u) for a factorising likelihood (henbun_amd.likelihoods) over C = likelihood.num_latent
+        latent functions at fixed hyper-parameters, for the whitened model u_c ~ N(0, I_M) independent, f_c = sqrt(k_var)
+        (u_c A + residual), y_j ~ p(y_j | f_j1 .. f_jC), with C independent q(u_c) = N(m_c, S_c S_c^T) that share z, the
+        lengthscales and W.  C = 1: Gaussian, Bernoulli, Poisson, Laplace, Gamma, Exponential, NegativeBinomial, Binomial --
+        all log-concave in f, so lam_j >= 0 and Lambda stays positive definite; C > 1: Softmax (C classes),
+        HeteroscedasticGaussian (C = 2).  q_c is kept as Lambda_c = (S_c S_c^T)^-1, eta_c = Lambda_c m_c; one step is the
+        conjugate update with per-point pseudo-observations (conjugate-computation VI, Khan & Lin 2017):
+            mu_jc, v_jc              the marginals of f_jc under q_c: C calls of hb_sgp_predict, or ONE hb_sgp_predict_multi
+                                     (A formed once for all C) where the likelihood has fused_marginals
+            lam_jc, beta_jc, l_j     E[-d2 log p], E[d log p] + lam mu, E[log p]: ONE sites launch, the likelihood's
+                                     (Likelihood.sites: hb_lik_sites, hb_lik_softmax_sites over the likelihood's nodes
+                                     [S, C], hb_lik_hetgauss_sites)
+            Phi_c = A diag(lam_c) A^T,  b_c = A beta_c      one pass over X: hb_sgp_wstats (C = 1) or ONE hb_sgp_mwstats,
+                                     A = W K(z, X) formed once per chunk for all C weight sets
             Lambda_c <- (1 - rho) Lambda_c + rho (I + k_var Phi_c),   eta_c <- (1 - rho) eta_c + rho sqrt(k_var) b_c
-        and C float64 tails.  ELBO = sum_j l_j - sum_c KL(q_c || N(0, I)); the residual is the largest over the classes.
-        Y [N, 1]: the labels (a numpy Y is checked on the host to hold integers in 0 .. C-1; labels already on the device
-        are the caller's duty).  q0 = (m [C, M], S [C, M, M]) or None (the prior).  Returns (m [C, M], S [C, M, M] lower,
-        info) as float64 numpy, info as for one latent function.  The ELBO is a fixed-node sum and lam is Price's form, not
-        the derivative of that sum: from step to step the ELBO can wiggle by about 1e-4 near the fixed point.  A full step
-        (rho = 1) does not settle (it cycles or diverges, see likelihoods.Softmax); the likelihood's natgrad_rho (0.5) is
-        what models.SVGPMulticlass passes.  residual 'fullrank' and a mean-field q0 raise NotImplementedError, other shapes ValueError.
-
-        The target check, the sites launch and whether the marginals come from one pass are the likelihood's
-        (likelihoods.Likelihood.check_targets / multi_sites / fused_marginals).  likelihoods.HeteroscedasticGaussian
-        (C = 2, Y [N, 1] real): per step ONE hb_sgp_predict_multi (A formed once for both latent functions), ONE
-        hb_lik_hetgauss_sites and ONE hb_sgp_mwstats; its expectation is exact, so the ELBO has no node wiggle."""
+        and m_c = Lambda_c^-1 eta_c, S_c = chol(Lambda_c^-1) from C float64 tails of optimal_q.  With the Gaussian
+        likelihood one step at rho = 1 is optimal_q.  K(z, z) is factorised once per call, from z and the lengthscales as
+        the session's plans transform them on the device, so the q(u) returned lives in the whitening predict_f and the
+        ELBO use.
+        X, Y as for statistics(), Y [N, 1]: the targets, checked by the likelihood's own rule (Likelihood.check_targets: a
+        numpy Y of Softmax must hold integers in 0 .. C-1, of HeteroscedasticGaussian finite numbers; targets already on
+        the device are the caller's duty).  q0=None starts at the prior; q0 at a given full-rank q: (m [1, M], S [M, M])
+        for one latent function, (m [C, M], S [C, M, M]) for C > 1.  Returns (m [1, M], S [M, M], info) resp. (m [C, M],
+        S [C, M, M], info) as float64 numpy, S lower with a positive diagonal; info = dict(elbo, residual, steps): the ELBO
+        sum_j l_j - sum_c KL(q_c || N(0, I)) and the fixed-point residual max|Lambda_c - (I + k_var Phi_c)| / max|I + k_var
+        Phi_c| (the largest over c) at every iterate, the starting one included (steps + 1 entries), and the steps taken.
+        m, S are the last iterate evaluated.  Stops when the relative change of the ELBO is <= tol, or after `steps`.
+        Same restrictions and exception types as statistics(); residual 'fullrank' and a mean-field q0 raise
+        NotImplementedError, other shapes and bad targets ValueError, all before the session is touched; a Lambda that is
+        not positive definite raises graph.CholeskyError.  A full step (rho = 1) is not guaranteed to raise the ELBO from a
+        q far from the optimum (info['elbo'] shows an overshoot): start at the prior or damp with rho < 1.
+        Softmax: the ELBO is a fixed-node sum and lam is Price's form, not the derivative of that sum: from step to step
+        the ELBO can wiggle by about 1e-4 near the fixed point.  A full step does not settle (it cycles or diverges, see
+        likelihoods.Softmax); the likelihood's natgrad_rho (0.5) is what models.SVGPMulticlass passes.
+        HeteroscedasticGaussian: its expectation is exact, so the ELBO has no node wiggle; natgrad_rho 0.5 as well."""
         who = "natgrad_q"
-        _check_residual(residual)
-        if not isinstance(likelihood, Likelihood):
-            raise TypeError("%s: likelihood must be a henbun_amd.likelihoods.Likelihood, got %s" % (who, type(likelihood).__name__))
-        C = int(likelihood.num_latent)
-        if not float(k_var) > 0.0:
-            raise ValueError("%s: k_var must be positive (got %r)" % (who, k_var))
+        q0 = _check_lik_inputs(who, "q0", likelihood, k_var, residual, q0, Y, self._inducing_count())
         k_var, rho, steps = float(k_var), float(rho), int(steps)
         if not (0.0 < rho <= 1.0 and steps >= 0):
             raise ValueError("%s: 0 < rho <= 1 and steps >= 0 expected (got %r, %r)" % (who, rho, steps))
-        m0, S0 = _check_blocks_and_targets(who, "q0", likelihood, q0, Y)
         sess, zvar, ls = self._stats_session(who)
         torch, H = sess.torch, sess.H
         Xd, Yd = _host.device_data(sess, X, "X"), _host.device_data(sess, Y, "Y")
-        M = int(zvar.shape[0])
-        if Yd.dim() != 2 or Yd.shape[1] != 1:
-            raise ValueError("%s: Y must hold the targets as [N, 1], got %s" % (who, tuple(Yd.shape)))
-        if q0 is not None and m0.shape[1] != M:
-            raise ValueError("%s: q0 = (m [%d, %d], S [%d, %d, %d]) expected, got %s %s" % (who, C, M, C, M, M, m0.shape, S0.shape))
+        likelihood.check_targets(who, Yd)
+        C, M = int(likelihood.num_latent), int(zvar.shape[0])
         z, ell, W, frag = self._whitening(sess, zvar, ls, Xd, Yd, who, as_plans=True)
         N, d = Xd.shape
         dt = sess.torch_dtype
@@ -384,51 +337,41 @@ class SparseInference:
         else:
             Lam, eta = torch.empty((C, M, M), **f64), torch.empty((C, M), **f64)
             for c in range(C):
-                Sinv = H.trinv(_host.upload(sess, np.tril(S0[c]), np.float64))
+                Sinv = H.trinv(_host.upload(sess, np.tril(q0[1][c]), np.float64))
                 Lam[c] = H.matmul(Sinv, Sinv, transA=True)
-                eta[c:c + 1] = H.matmul(_host.upload(sess, m0[c].reshape(1, M), np.float64), Lam[c].contiguous())
+                eta[c:c + 1] = H.matmul(_host.upload(sess, q0[0][c].reshape(1, M), np.float64), Lam[c].contiguous())
         state = likelihood.device_state(sess)
         yv = Yd.reshape(-1).contiguous()
         mode = H.SGP_DIAGONAL if residual == "diagonal" else H.SGP_NEGLECTED
-        one_pass = bool(likelihood.fused_marginals)
         fused = bool(getattr(settings.runtime, "fused_predict", True)) and (
-            H.sgp_predict_multi_fused(dt, N, M, d, C, frag is not None) if one_pass else
+            H.sgp_predict_multi_fused(dt, N, M, d, C, frag is not None) if likelihood.fused_marginals else
             H.sgp_predict_fused(dt, 1, N, M, d, 1, H.SGP_S_TRIL, frag is not None))
-        ldw = -(-N // 4) * 4                        # rows padded to 16 bytes: what hb_sgp_mwstats asks of the weights
-        mean = torch.empty((C, N), dtype=dt, device=sess.device)
-        var = torch.empty_like(mean)
-        lam, beta = (torch.zeros((C, ldw), dtype=dt, device=sess.device) for _ in range(2))
-        lam_c, beta_c = (lam, beta) if ldw == N else (torch.empty_like(mean), torch.empty_like(mean))
+        mean, var, lam, beta = (torch.empty((C, N), dtype=dt, device=sess.device) for _ in range(4))
         m, S = torch.empty((C, M), **f64), torch.empty((C, M, M), **f64)
         elbo, resid = [], []
         for it in range(steps + 1):
             kl = 0.0
             for c in range(C):
-                whoc = "natgrad_q (step %d, class %d)" % (it, c)
+                whoc = "natgrad_q (step %d, latent function %d)" % (it, c)
                 L, V, t = _q_tail(H, Lam[c], eta[c:c + 1], whoc)
                 mc = H.matmul(t, V)
                 Sig, Sc = _q_cov(H, V, whoc)
                 m[c:c + 1], S[c] = mc, Sc
-                if not one_pass:
-                    H.sgp_predict(Xd, z, ell, W, mc.to(dt), Sc.to(dt), s_kind=H.SGP_S_TRIL, mode=mode,
-                                  out=(mean[c:c + 1], var[c:c + 1]), wfrag=frag if fused else None)
+                # KL(q_c || N(0, I)) from Sigma and the factor of Lambda.  elbo_and_grad forms it from S instead: equal in
+                # exact arithmetic, not in the last bits, so neither borrows the other's
                 kl += 0.5 * (float(torch.diagonal(Sig).sum().cpu()) + float((mc * mc).sum().cpu()) - M
                              + 2.0 * float(np.log(np.diagonal(L.cpu().numpy())).sum()))
-            if one_pass:
-                H.sgp_predict_multi(Xd, z, ell, W, m.to(dt), S.to(dt), mode=mode, out=(mean, var), wfrag=frag if fused else None)
-            lsum = likelihood.multi_sites(H, state, yv, mean, var, np.sqrt(k_var), k_var, (lam_c, beta_c))
-            if lam_c is not lam:
-                lam[:, :N].copy_(lam_c)
-                beta[:, :N].copy_(beta_c)
-            Phi, b, _ = H.sgp_mwstats(Xd, lam[:, :N], beta[:, :N], z, ell, W, wfrag=frag)
+            _marginals(H, likelihood, Xd, z, ell, W, m.to(dt), S.to(dt), mode, (mean, var), frag if fused else None)
+            lsum = likelihood.sites(H, state, yv, mean, var, np.sqrt(k_var), k_var, (lam, beta))
+            Phi, b = _weighted_stats(H, Xd, lam, beta, z, ell, W, frag)
             Lt, et = Phi * k_var + eye, b * np.sqrt(k_var)
             elbo.append(float(lsum.cpu()[0]) - kl)
             resid.append(float(((Lam - Lt).abs().amax(dim=(1, 2)) / Lt.abs().amax(dim=(1, 2))).max().cpu()))
             if it == steps or (it > 0 and abs(elbo[-1] - elbo[-2]) <= tol * abs(elbo[-1])):
                 break
             Lam, eta = (1.0 - rho) * Lam + rho * Lt, (1.0 - rho) * eta + rho * et
-        return (m.cpu().numpy(), np.tril(S.cpu().numpy()),
-                dict(elbo=np.asarray(elbo), residual=np.asarray(resid), steps=it))
+        m, S = m.cpu().numpy(), np.tril(S.cpu().numpy())
+        return m, S[0] if C == 1 else S, dict(elbo=np.asarray(elbo), residual=np.asarray(resid), steps=it)
 
     def collapsed_bound_and_grad(self, X, Y, noise_var, k_var=1.0, residual="diagonal"):
         """(value, grad): the collapsed bound of collapsed_bound() and its exact gradient with respect to the CONSTRAINED
@@ -608,53 +551,11 @@ class SparseInference:
         of lik_grad=False.
 
         A likelihood over several latent functions (likelihoods.Softmax) raises NotImplementedError: that route has its
-        own weights, q and name, elbo_and_grad_multi."""
+        own weights, q and name, elbo_and_grad_multi (both run _elbo_and_grad)."""
         if getattr(likelihood, "num_latent", 1) > 1:
             raise NotImplementedError("elbo_and_grad: one latent function only (%s has %d: use elbo_and_grad_multi)"
                                       % (type(likelihood).__name__, likelihood.num_latent))
-        if lik_grad and not getattr(likelihood, "trainable", False):
-            raise ValueError("elbo_and_grad: lik_grad=True needs a likelihood with a continuous parameter (got %s)"
-                             % type(likelihood).__name__)
-        sess, Xd, Yd, z, ell, W = self._grad_inputs(X, Y, "elbo_and_grad")
-        torch, H = sess.torch, sess.H
-        N, M = int(Xd.shape[0]), int(z.shape[0])
-        m0, S0 = _check_lik_inputs("elbo_and_grad", likelihood, k_var, residual, q, Yd, M)
-        k = float(k_var)
-        rho = 1.0 if residual == "diagonal" else 0.0
-        m, S = _host.upload(sess, m0.reshape(1, M), np.float64), _host.upload(sess, np.tril(S0), np.float64)
-        mode = H.SGP_DIAGONAL if residual == "diagonal" else H.SGP_NEGLECTED
-        lam = torch.empty((N,), dtype=torch.float64, device=sess.device)
-        gam = torch.empty_like(lam)
-
-        def per_chunk(c0, Xc, Yc):
-            mean, var = H.sgp_predict(Xc, z, ell, W, m, S, s_kind=H.SGP_S_TRIL, mode=mode)       # unit-variance moments [1, nc]
-            lc, bc = lam[c0:c0 + Xc.shape[0]], gam[c0:c0 + Xc.shape[0]]
-            _, _, ls = H.lik_sites(likelihood.lik_id, Yc.reshape(-1), mean, var, param=likelihood.param, mscale=np.sqrt(k),
-                                   vscale=k, out=(lc, bc))
-            mu = mean.reshape(-1) * np.sqrt(k)
-            bc -= lc * mu                                                   # gamma = beta - lam mu
-            Pc, rc, _ = H.sgp_wstats(Xc, lc, bc, z, ell, W)
-            parts = (Pc, rc, ls, (bc * mu - lc * var.reshape(-1) * k).sum())
-            if lik_grad:
-                parts += (H.lik_param_grad(likelihood.lik_id, Yc.reshape(-1), mean, var, param=likelihood.param,
-                                           mscale=np.sqrt(k), vscale=k)[1:],)
-            return parts
-
-        # chunks of a multiple of 32 rows: every chunk of lam stays 16-byte aligned
-        Phi, b, lsum, dks, *dps = _walk_f64(torch, Xd, Yd, M, 32, per_chunk)
-        # tail: G = dF/dPhi_w, g = dF/db_w
-        Gm = H.matutil((H.matmul(S, S, transB=True) * (-0.5 * k)).contiguous(), H.MATUTIL_ADD_EYE, alpha=0.5 * rho * k)
-        g = (m * np.sqrt(k)).contiguous()
-        zg, eg = self._kernel_grads(sess, z, ell, W, Gm, g, Phi.contiguous(), b.contiguous(),
-                                    lambda Q, R: H.sgp_wkgrad(Xd, lam, gam, z, ell, Q, R))
-        # KL(q || N(0, I)) from S itself (natgrad_q forms it from Sigma and the factor of Lambda; see there), and
-        # dF/dk_var: scalars on the host
-        Sl = np.tril(S0)
-        kl = 0.5 * (float((Sl * Sl).sum()) + float((m0 * m0).sum()) - M) - float(np.log(np.abs(np.diagonal(Sl))).sum())
-        grad = dict(z=zg.cpu().numpy(), lengthscales=eg.cpu().numpy(), k_var=float(dks.cpu()) / (2.0 * k))
-        if lik_grad:
-            grad["lik_param"] = float(dps[0].cpu()[0])
-        return float(lsum.cpu()[0]) - kl, grad
+        return self._elbo_and_grad("elbo_and_grad", X, Y, likelihood, q, k_var, residual, lik_grad)
 
     def elbo_and_grad_multi(self, X, Y, likelihood, q, k_var=1.0, residual="diagonal", lik_grad=False):
         """(value, grad): elbo_and_grad for a likelihood over C = likelihood.num_latent latent functions
@@ -683,40 +584,38 @@ class SparseInference:
         likelihood ('fullrank' and a mean-field q: NotImplementedError; other shapes and bad labels: ValueError), decided
         before the session is touched; a likelihood over ONE latent function raises ValueError: use elbo_and_grad.
 
-        The weights call is the likelihood's (Likelihood.multi_weights).  likelihoods.HeteroscedasticGaussian: Y [N, 1]
+        The weights call is the likelihood's (Likelihood.weights).  likelihoods.HeteroscedasticGaussian: Y [N, 1]
         real, w = lam and r = dl/dmu from ONE hb_lik_hetgauss_sites_f64 per chunk (its expectation is exact, so lam IS
         -2 dl/dv) and the marginals from ONE hb_sgp_predict_multi_f64.  lik_grad=True (a `trainable` likelihood: ValueError
         otherwise) adds grad['lik_param'] = sum_j dl_j / dparam at the marginals of that q, added in chunk order -- for
         HeteroscedasticGaussian sum_j r_gj; the other entries and the value are the bits of lik_grad=False."""
         who = "elbo_and_grad_multi"
-        _check_residual(residual)
-        if not isinstance(likelihood, Likelihood):
-            raise TypeError("%s: likelihood must be a henbun_amd.likelihoods.Likelihood, got %s" % (who, type(likelihood).__name__))
-        C = int(getattr(likelihood, "num_latent", 1))
-        if C < 2:
+        if isinstance(likelihood, Likelihood) and likelihood.num_latent < 2:
             raise ValueError("%s: a likelihood over several latent functions expected (%s has one: use elbo_and_grad)"
                              % (who, type(likelihood).__name__))
+        return self._elbo_and_grad(who, X, Y, likelihood, q, k_var, residual, lik_grad)
+
+    def _elbo_and_grad(self, who, X, Y, likelihood, q, k_var, residual, lik_grad):
+        """The one route behind elbo_and_grad and elbo_and_grad_multi (which document it), on the blocks q = (m [C, M],
+        S [C, M, M]) of C = likelihood.num_latent latent functions: the float64 chunk walk -- marginals (_marginals), the
+        likelihood's weights w, r (Likelihood.weights), weighted statistics (_weighted_stats) -- then per latent function the
+        tail G_c, g_c, Q_c, R_c with hb_sgp_wkgrad over all of X, ONE Cholesky and Gram VJP of K(z, z) for T = -sum_c (2 G_c
+        Phi_c + g_c^T b_c), and the KL from S."""
         if lik_grad and not getattr(likelihood, "trainable", False):
             raise ValueError("%s: lik_grad=True needs a likelihood with a continuous parameter (got %s)"
                              % (who, type(likelihood).__name__))
-        if not float(k_var) > 0.0:
-            raise ValueError("%s: k_var must be positive (got %r)" % (who, k_var))
+        q = _check_lik_inputs(who, "q", likelihood, k_var, residual, q, Y, self._inducing_count())
         if q is None:
-            raise ValueError("%s: q = (m [%d, M], S [%d, M, M]) expected, got None" % (who, C, C))
-        m0, S0 = _check_blocks_and_targets(who, "q", likelihood, q, Y)
-        zshape = tuple(object.__getattribute__(self, "z").shape)
-        if len(zshape) == 2 and m0.shape[1] != zshape[0]:
-            raise ValueError("%s: q = (m [%d, %d], S [%d, %d, %d]) expected, got %s %s"
-                             % ((who, C, zshape[0], C) + zshape[:1] * 2 + (m0.shape, S0.shape)))
+            raise ValueError("%s: q = (m, S) expected, got None" % who)
+        m0, S0 = q[0], np.tril(q[1])
         sess, Xd, Yd, z, ell, W = self._grad_inputs(X, Y, who)
-        if Yd.dim() != 2 or Yd.shape[1] != 1:
-            raise ValueError("%s: Y must hold the targets as [N, 1], got %s" % (who, tuple(Yd.shape)))
+        likelihood.check_targets(who, Yd)
         torch, H = sess.torch, sess.H
-        N, M = int(Xd.shape[0]), int(z.shape[0])
+        N, (C, M) = int(Xd.shape[0]), m0.shape
         k = float(k_var)
         rho = 1.0 if residual == "diagonal" else 0.0
         f64 = dict(dtype=torch.float64, device=sess.device)
-        m, S = _host.upload(sess, m0, np.float64), _host.upload(sess, np.tril(S0), np.float64)
+        m, S = _host.upload(sess, m0, np.float64), _host.upload(sess, S0, np.float64)
         state = likelihood.device_state(sess)
         mode = H.SGP_DIAGONAL if residual == "diagonal" else H.SGP_NEGLECTED
         ldN = -(-N // 2) * 2                         # rows padded to 16 bytes: what hb_sgp_mwstats asks of the weights
@@ -725,21 +624,18 @@ class SparseInference:
         def per_chunk(c0, Xc, Yc):
             nc = Xc.shape[0]
             mean, var = (torch.empty((C, nc), **f64) for _ in range(2))      # unit-variance moments
-            if likelihood.fused_marginals:
-                H.sgp_predict_multi(Xc, z, ell, W, m, S, mode=mode, out=(mean, var))
-            else:
-                for c in range(C):
-                    H.sgp_predict(Xc, z, ell, W, m[c:c + 1], S[c], s_kind=H.SGP_S_TRIL, mode=mode,
-                                  out=(mean[c:c + 1], var[c:c + 1]))
+            _marginals(H, likelihood, Xc, z, ell, W, m, S, mode, (mean, var))
             wc, rc = w[:, c0:c0 + nc], r[:, c0:c0 + nc]
-            ls, dp = likelihood.multi_weights(H, state, Yc.reshape(-1), mean, var, np.sqrt(k), k, (wc, rc))
-            Pc, bc, _ = H.sgp_mwstats(Xc, wc, rc, z, ell, W)
-            parts = (Pc, bc, ls, (rc * mean * np.sqrt(k) - wc * var * k).sum())
+            mu = mean * np.sqrt(k)
+            ls, dp = likelihood.weights(H, state, Yc.reshape(-1), mean, var, np.sqrt(k), k, (wc, rc), mu, lik_grad=lik_grad)
+            Pc, bc = _weighted_stats(H, Xc, wc, rc, z, ell, W)
+            parts = (Pc, bc, ls, (rc * mu - wc * var * k).sum())
             return parts + (dp,) if lik_grad else parts
 
         # chunks of a multiple of 32 rows: every chunk of a row of w stays 16-byte aligned
         Phi, b, lsum, dks, *dps = _walk_f64(torch, Xd, Yd, M, 32, per_chunk)
-        # tail: G_c = dF/dPhi_c, g_c = dF/db_c; T is linear in the classes, so one Cholesky VJP and one Gram VJP serve all
+        # tail: G_c = dF/dPhi_c, g_c = dF/db_c; T is linear in the latent functions, so one Cholesky VJP and one Gram VJP
+        # serve all
         zbar = ellbar = T = None
         for c in range(C):
             Gm = H.matutil((H.matmul(S[c], S[c], transB=True) * (-0.5 * k)).contiguous(), H.MATUTIL_ADD_EYE, alpha=0.5 * rho * k)
@@ -750,13 +646,13 @@ class SparseInference:
             Tc = H.matmul(Gm, Phi[c].contiguous(), alpha=-2.0) - H.matmul(g, b[c:c + 1].contiguous(), transA=True)
             zbar, ellbar, T = (zc, ec, Tc) if T is None else (zbar + zc, ellbar + ec, T + Tc)
         zk, ek = self._kmm_grads(sess, z, ell, W, T.contiguous())
-        # KL(q_c || N(0, I)) from S_c itself, as elbo_and_grad forms it
-        Sl = np.tril(S0)
-        kl = sum(0.5 * (float((Sl[c] * Sl[c]).sum()) + float((m0[c] * m0[c]).sum()) - M)
-                 - float(np.log(np.abs(np.diagonal(Sl[c]))).sum()) for c in range(C))
+        # KL(q_c || N(0, I)) from S_c itself (natgrad_q forms it from Sigma and the factor of Lambda; see there), and
+        # dF/dk_var: scalars on the host
+        kl = sum(0.5 * (float((S0[c] * S0[c]).sum()) + float((m0[c] * m0[c]).sum()) - M)
+                 - float(np.log(np.abs(np.diagonal(S0[c]))).sum()) for c in range(C))
         grad = dict(z=(zbar + zk).cpu().numpy(), lengthscales=(ellbar + ek).cpu().numpy(), k_var=float(dks.cpu()) / (2.0 * k))
         if lik_grad:
-            grad["lik_param"] = float(dps[0].cpu())
+            grad["lik_param"] = float(dps[0].cpu()[0])
         return float(lsum.cpu()[0]) - kl, grad
 
     # -- pathwise posterior function draws (Wilson et al. 2020) -----------------------------------------------------

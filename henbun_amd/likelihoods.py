@@ -60,26 +60,39 @@ class Likelihood:
     def logp(self, f, y, param=None):
         raise NotImplementedError
 
-    # -- what SparseGP.natgrad_q / elbo_and_grad_multi ask of a likelihood over several latent functions (num_latent > 1) --
+    # -- what SparseGP.natgrad_q / elbo_and_grad / elbo_and_grad_multi ask of a likelihood over C = num_latent latent
+    # functions.  The defaults below serve every likelihood over ONE (the entries hb_lik_sites / hb_lik_param_grad by
+    # lik_id); Softmax and HeteroscedasticGaussian bring their own.
     fused_marginals = False   # True: the C marginals come from ONE hip_ops.sgp_predict_multi (else C calls of sgp_predict)
 
     def check_targets(self, who, Y):
-        """Host-side check of a numpy Y [N, 1] (targets already on the device are the caller's duty)."""
-        raise NotImplementedError
+        """The targets Y must be [N, 1]: the shape of a numpy array or a device tensor, and for a numpy array (the host
+        side) the values too, where a likelihood restricts them -- targets already on the device are the caller's duty."""
+        if Y.ndim != 2 or Y.shape[1] != 1:
+            raise NotImplementedError("%s: one latent function only (Y must be [N, 1], got %s)" % (who, tuple(Y.shape)))
 
     def device_state(self, sess):
         """What the sites and weights calls need on the device besides the marginals (Softmax: its nodes); built once
         per route, before the first step."""
         return None
 
-    def multi_sites(self, H, state, y, mean, var, mscale, vscale, out):
+    def sites(self, H, state, y, mean, var, mscale, vscale, out):
         """lam, beta [C, N] into out = (lam, beta) at the marginals mean, var [C, N]; returns lsum (float64 [1])."""
-        raise NotImplementedError
+        return H.lik_sites(self.lik_id, y, mean, var, param=self.param, mscale=mscale, vscale=vscale, out=out)[2]
 
-    def multi_weights(self, H, state, y, mean, var, mscale, vscale, out):
+    def weights(self, H, state, y, mean, var, mscale, vscale, out, mu, lik_grad=False):
         """The weights of the hyper-parameter gradient at fixed q into out = (w, r), float64 [C, N] views of padded rows;
-        returns (lsum, dparam): sum_j l_j and, for a trainable likelihood, sum_j dl_j / dparam (a device scalar) or None."""
-        raise NotImplementedError
+        returns (lsum, dparam): sum_j l_j and, with lik_grad=True (a trainable likelihood), sum_j dl_j / dparam as a float64
+        device tensor [1], else None.  mu = mscale mean, which the caller holds already.  Here w = lam and r = gamma = beta
+        - lam mu (Stein's identity), and the parameter gradient is one more launch (hb_lik_param_grad), issued only when
+        asked for."""
+        lam, r = out
+        lsum = self.sites(H, state, y, mean, var, mscale, vscale, out)
+        r -= lam * mu
+        dparam = None
+        if lik_grad:
+            dparam = H.lik_param_grad(self.lik_id, y, mean, var, param=self.param, mscale=mscale, vscale=vscale)[1:]
+        return lsum, dparam
 
 
 class Gaussian(Likelihood):
@@ -254,8 +267,8 @@ class Softmax(Likelihood):
     def check_targets(self, who, Y):
         C = self.num_classes
         if Y.ndim != 2 or Y.shape[1] != 1:
-            raise ValueError("%s: Y must hold the labels as [N, 1], got %s" % (who, Y.shape))
-        if not (np.all(Y == np.floor(Y)) and Y.size and Y.min() >= 0 and Y.max() <= C - 1):
+            raise ValueError("%s: Y must hold the labels as [N, 1], got %s" % (who, tuple(Y.shape)))
+        if isinstance(Y, np.ndarray) and not (np.all(Y == np.floor(Y)) and Y.size and Y.min() >= 0 and Y.max() <= C - 1):
             raise ValueError("%s: the labels must be integers in 0 .. %d" % (who, C - 1))
 
     def device_state(self, sess):
@@ -263,10 +276,10 @@ class Softmax(Likelihood):
 
         return _host.upload(sess, self.nodes(), np.float64)
 
-    def multi_sites(self, H, state, y, mean, var, mscale, vscale, out):
+    def sites(self, H, state, y, mean, var, mscale, vscale, out):
         return H.lik_softmax_sites(y, mean, var, state, mscale=mscale, vscale=vscale, out=out)[2]
 
-    def multi_weights(self, H, state, y, mean, var, mscale, vscale, out):
+    def weights(self, H, state, y, mean, var, mscale, vscale, out, mu, lik_grad=False):
         return H.lik_softmax_grad(y, mean, var, state, mscale=mscale, vscale=vscale, out=out)[2], None
 
     def logp(self, f, y, param=None):
@@ -308,20 +321,20 @@ class HeteroscedasticGaussian(Likelihood):
 
     def check_targets(self, who, Y):
         if Y.ndim != 2 or Y.shape[1] != 1:
-            raise ValueError("%s: Y must hold the observations as [N, 1], got %s" % (who, Y.shape))
-        if not (Y.size and np.all(np.isfinite(Y))):
+            raise ValueError("%s: Y must hold the observations as [N, 1], got %s" % (who, tuple(Y.shape)))
+        if isinstance(Y, np.ndarray) and not (Y.size and np.all(np.isfinite(Y))):
             raise ValueError("%s: the observations must be finite numbers" % who)
 
-    def multi_sites(self, H, state, y, mean, var, mscale, vscale, out):
+    def sites(self, H, state, y, mean, var, mscale, vscale, out):
         return H.lik_hetgauss_sites(y, mean, var, param=self.param, mscale=mscale, vscale=vscale, out=out)[3]
 
-    def multi_weights(self, H, state, y, mean, var, mscale, vscale, out):
-        # w = lam and r = dl/dmu from the one launch; the entry keeps one row stride for inputs and outputs, so the
-        # (float64, per chunk) results are copied into the padded rows
+    def weights(self, H, state, y, mean, var, mscale, vscale, out, mu, lik_grad=False):
+        # w = lam and r = dl/dmu from the one launch (dparam = sum_j r_gj comes with it, asked for or not); the entry keeps
+        # one row stride for inputs and outputs, so the (float64, per chunk) results are copied into the padded rows
         lam, _, r, lsum = H.lik_hetgauss_sites(y, mean, var, param=self.param, mscale=mscale, vscale=vscale, grad=True)
         out[0].copy_(lam)
         out[1].copy_(r)
-        return lsum, r[1].sum()
+        return lsum, r[1].sum().reshape(1)
 
     def logp(self, f, y, param=None):
         """log N(y; f_0, exp(f_1 + c)) as a graph expression [1, n]: f [2, n] (rows: the mean, the log variance), y [1, n]."""

@@ -399,7 +399,116 @@ class BayesianGPLVM(hb.model.Model):
         return mean.cpu().numpy(), v.cpu().numpy()
 
 
-class SVGPLik(hb.model.Model):
+class _SVGPNonConjugate(hb.model.Model):
+    """What SVGPLik, SVGPMulticlass and SVGPHetero share: a likelihood (hb.likelihoods) over C = likelihood.num_latent
+    latent functions of one SparseGP `gp`, a full-rank q(u) `u` of C blocks -- Normal(shape=[1, M]) or Normal(shape=[M],
+    n_layers=[C]), packed or dense -- the Variable `k_var`, `residual`, the data X, Y, and optionally the likelihood's
+    parameter as the Variable `lik_param` (learn_likelihood).  The deterministic full-batch routes live here once; a
+    model adds setUp, the sampled ELBO, its predictions and its fit_q defaults."""
+
+    learn_likelihood = False                  # True: `lik_param` holds the likelihood's parameter and fit_hyper learns it
+    _gp_elbo_and_grad = "elbo_and_grad_multi"   # the SparseGP method elbo_and_grad() calls
+
+    def current_likelihood(self):
+        """The likelihood in use: the one handed in, or with learn_likelihood=True a copy that carries the current value
+        of lik_param."""
+        lik = _part(self, "likelihood")
+        if not _part(self, "learn_likelihood"):
+            return lik
+        self.initialize()
+        return lik.with_param(_scalar(self, "lik_param"))
+
+    select_inducing = SVGP.select_inducing
+
+    def _likelihood_residual(self):
+        """The residual mode of the moments the closed-form routes hand to the likelihood: the model's own."""
+        return self.residual
+
+    def reset_q(self):
+        """Set every block of q(u) to the prior N(0, I), where natgrad_q's own default starts.  A freshly built model holds
+        a RANDOM q(u), from which a full natural-gradient step (rho = 1) overshoots: call this before the first fit_q() /
+        fit_hyper()."""
+        self.initialize()
+        C, M = _part(self, "likelihood").num_latent, _part(self, "u").size
+        self._write_blocks(np.zeros((C, M)), np.broadcast_to(np.eye(M), (C, M, M)))
+
+    def _write_blocks(self, m, S):
+        """Write q(u_c) = N(m_c, S_c S_c^T) into u in its own parametrisation: m [C, M]; S [C, M, M] (or [M, M] for one
+        block) lower-triangular, stored packed or dense."""
+        q, sess = _part(self, "u"), self._session
+        mu, sq = _part(q, "q_mu"), _part(q, "q_sqrt")
+        sess.write_raw(mu, np.reshape(m, mu._full_shape))
+        sess.write_raw(sq, np.reshape(tri_pack(S) if q.packed else S, sq._full_shape))
+
+    def _current_blocks(self):
+        """(m [C, M], S [C, M, M] lower) of the model's q(u) as the session stores it, float64 numpy."""
+        self.initialize()
+        q, sess = _part(self, "u"), self._session
+        M = q.size
+        S = np.asarray(sess.read_raw(_part(q, "q_sqrt")), dtype=np.float64)
+        S = tri_unpack(S.reshape(-1, M * (M + 1) // 2)) if q.packed else np.tril(S.reshape(-1, M, M))
+        return np.asarray(sess.read_raw(_part(q, "q_mu")), dtype=np.float64).reshape(-1, M), S
+
+    def _hyper_variables(self):
+        """The Variables the ELBO at a fixed q(u) depends on, by the names the gradient uses."""
+        gp = _part(self, "gp")
+        hv = dict(z=_part(gp, "z"), lengthscales=_part(_part(gp, "kern"), "lengthscales"), k_var=_part(self, "k_var"))
+        if _part(self, "learn_likelihood"):
+            hv["lik_param"] = _part(self, "lik_param")
+        return hv
+
+    def _fit_q(self, steps, rho, tol):
+        """fit_q of every model: SparseGP.natgrad_q from the model's CURRENT q(u) over the model's full device-resident X,
+        Y at the current z, lengthscales, k_var and likelihood parameter; the blocks are written back.  rho=None: the
+        likelihood's natgrad_rho."""
+        self.initialize()
+        lik = self.current_likelihood()
+        m, S, info = _part(self, "gp").natgrad_q(_part(self, "X"), _part(self, "Y"), lik, k_var=_scalar(self, "k_var"),
+                                                 residual=self._likelihood_residual(), q0=self._current_blocks(),
+                                                 steps=steps, rho=lik.natgrad_rho if rho is None else rho, tol=tol)
+        self._write_blocks(m, S)
+        return m, S, info
+
+    def elbo_and_grad(self):
+        """(value, grad): the ELBO over the model's full X, Y at the model's CURRENT q(u) -- the value fit_q reports -- and
+        its partial gradient at that q with respect to the RAW (free) parameters, grad = dict(z, lengthscales, k_var) and,
+        with learn_likelihood=True, lik_param, in the shapes of the raw arrays, float64 numpy.  SparseGP.elbo_and_grad for
+        one latent function, SparseGP.elbo_and_grad_multi for several (float64 arithmetic whatever the session's dtype;
+        the moments fit_q takes, for SVGPMulticlass those without the residual), chained through the transforms'
+        dforward.  After fit_q() has converged this is the total derivative of the fitted ELBO -- for SVGPMulticlass up to
+        the node error of the step's curvature (see elbo_and_grad_multi)."""
+        self.initialize()
+        kw = dict(lik_grad=True) if _part(self, "learn_likelihood") else {}
+        route = getattr(_part(self, "gp"), self._gp_elbo_and_grad)
+        value, cons = route(_part(self, "X"), _part(self, "Y"), self.current_likelihood(), self._current_blocks(),
+                            k_var=_scalar(self, "k_var"), residual=self._likelihood_residual(), **kw)
+        return value, _chain_to_raw(self, cons)
+
+    def fit_hyper(self, steps, lr=0.01, train_z=True, q_steps=5, rho=None):
+        """Deterministic full-batch fit of the hyper-parameters, alternating as GPflow's natural-gradient recipe does:
+        every outer step runs fit_q(steps=q_steps, rho=rho) from the current q(u), then takes ONE Adam ASCENT step on
+        elbo_and_grad() in the raw parameters of lengthscales, k_var, (train_z) z and, with learn_likelihood=True, the
+        likelihood's parameter -- on the host in float64, the loop of SVGP.fit_hyper.  No minibatch noise.  Ends with a
+        fit_q() at the final parameters (at the likelihood's natgrad_rho, whatever `rho`).  Returns the trace of ELBO
+        values, steps + 1 entries: after the first fit_q at the starting parameters .. after the closing fit_q()
+        at the final ones.  A step after which a factorisation fails raises graph.CholeskyError with the last good
+        parameters restored.  The first fit_q starts at the model's current q(u): from a freshly initialised (random)
+        q a full step overshoots (see fit_q), so call reset_q() first (or fit q(u) some other way, or pass rho < 1).
+        rho=None: the likelihood's natgrad_rho, as for fit_q."""
+        steps, done = int(steps), [0]
+
+        def evaluate():
+            if done[0] == steps:
+                self.fit_q()
+            else:
+                self.fit_q(steps=q_steps, rho=rho)
+            done[0] += 1
+            return self.elbo_and_grad()
+
+        return _adam_ascent(self, evaluate, steps, lr, train_z)
+
+
+class SVGPLik(_SVGPNonConjugate):
     """Sparse variational GP with a non-conjugate factorising likelihood (hb.likelihoods: Bernoulli, Poisson, Gaussian,
     Laplace, Gamma, Exponential, NegativeBinomial, Binomial) and a full-rank q(u): SVGP's latent model, the sampled ELBO
     with likelihood.logp, and a deterministic fit of q(u) by natural-gradient steps (SparseGP.natgrad_q).
@@ -437,20 +546,11 @@ class SVGPLik(hb.model.Model):
             ll = tf.reduce_sum(self.likelihood.logp(f, tf.transpose(self.Y)))
         return (self.N / n) * ll - self.KL()
 
-    def current_likelihood(self):
-        """The likelihood in use: the one handed in, or with learn_likelihood=True a copy that carries the current value
-        of lik_param."""
-        lik = _part(self, "likelihood")
-        if not _part(self, "learn_likelihood"):
-            return lik
-        self.initialize()
-        return lik.with_param(_scalar(self, "lik_param"))
-
+    _gp_elbo_and_grad = "elbo_and_grad"
     _predict = SVGP._predict                      # reads gp, u, k_var and residual only when no noise is asked for
     predict_f = SVGP.predict_f
     predict_f_samples = SVGP.predict_f_samples
     sample_functions = SVGP.sample_functions
-    select_inducing = SVGP.select_inducing
     posterior = SVGP.posterior
     suggest_batch = SVGP.suggest_batch
 
@@ -485,76 +585,10 @@ class SVGPLik(hb.model.Model):
         writes them for 'fullrank'.  Returns (m [1, M], S [M, M], info) as natgrad_q does.  A full step (rho = 1) from a q
         far from the optimum, such as a freshly initialised one, can overshoot before it settles: info['elbo'] shows it,
         and rho < 1 damps it.  rho=None takes the likelihood's natgrad_rho: 1, except Laplace's 0.25."""
-        self.initialize()
-        rho = _part(self, "likelihood").natgrad_rho if rho is None else rho
-        m, S, info = _part(self, "gp").natgrad_q(_part(self, "X"), _part(self, "Y"), self.current_likelihood(),
-                                                 k_var=_scalar(self, "k_var"), residual=self.residual,
-                                                 q0=self._current_q(), steps=steps, rho=rho, tol=tol)
-        _write_q(self, m, S)
-        return m, S, info
-
-    def reset_q(self):
-        """Set q(u) to the prior N(0, I), where natgrad_q's own default starts.  A freshly built model holds a RANDOM q(u),
-        from which a full natural-gradient step (rho = 1) overshoots: call this before the first fit_q() / fit_hyper()."""
-        self.initialize()
-        M = _part(self, "u").size
-        _write_q(self, np.zeros(M), np.eye(M))
-
-    def _current_q(self):
-        """(m [1, M], S [M, M] lower) of the model's q(u) as the session stores it, float64 numpy."""
-        self.initialize()
-        q, sess = _part(self, "u"), self._session
-        M = q.size
-        S = np.asarray(sess.read_raw(_part(q, "q_sqrt")), dtype=np.float64)
-        S = tri_unpack(S.reshape(-1)) if q.packed else np.tril(S.reshape(M, M))
-        return np.asarray(sess.read_raw(_part(q, "q_mu")), dtype=np.float64).reshape(1, M), S
-
-    def _hyper_variables(self):
-        """The Variables the ELBO at a fixed q(u) depends on, by the names the gradient uses."""
-        gp = _part(self, "gp")
-        hv = dict(z=_part(gp, "z"), lengthscales=_part(_part(gp, "kern"), "lengthscales"), k_var=_part(self, "k_var"))
-        if _part(self, "learn_likelihood"):
-            hv["lik_param"] = _part(self, "lik_param")
-        return hv
-
-    def elbo_and_grad(self):
-        """(value, grad): the ELBO over the model's full X, Y at the model's CURRENT q(u) and its partial gradient at
-        that q with respect to the RAW (free) parameters, grad = dict(z, lengthscales, k_var) in the shapes of the raw
-        arrays, float64 numpy.  SparseGP.elbo_and_grad (float64 arithmetic whatever the session's dtype), chained
-        through the transforms' dforward.  After fit_q() has converged this is the total derivative of the fitted ELBO.
-        With learn_likelihood=True grad also holds lik_param."""
-        learn = _part(self, "learn_likelihood")
-        kw = dict(lik_grad=True) if learn else {}
-        value, cons = _part(self, "gp").elbo_and_grad(_part(self, "X"), _part(self, "Y"), self.current_likelihood(),
-                                                      self._current_q(), k_var=_scalar(self, "k_var"), residual=self.residual,
-                                                      **kw)
-        return value, _chain_to_raw(self, cons)
-
-    def fit_hyper(self, steps, lr=0.01, train_z=True, q_steps=5, rho=None):
-        """Deterministic full-batch fit of the hyper-parameters, alternating as GPflow's natural-gradient recipe does:
-        every outer step runs fit_q(steps=q_steps, rho=rho) from the current q(u), then takes ONE Adam ASCENT step on
-        elbo_and_grad() in the raw parameters of lengthscales, k_var, (train_z) z and, with learn_likelihood=True, the
-        likelihood's parameter -- on the host in float64, the loop of SVGP.fit_hyper.  No minibatch noise.  Ends with a
-        fit_q() at the final parameters (at the likelihood's natgrad_rho, whatever `rho`).  Returns the trace of ELBO
-        values, steps + 1 entries: after the first fit_q at the starting parameters .. after the closing fit_q()
-        at the final ones.  A step after which a factorisation fails raises graph.CholeskyError with the last good
-        parameters restored.  The first fit_q starts at the model's current q(u): from a freshly initialised (random)
-        q a full step overshoots (see fit_q), so call reset_q() first (or fit q(u) some other way, or pass rho < 1).
-        rho=None: the likelihood's natgrad_rho, as for fit_q."""
-        steps, done = int(steps), [0]
-
-        def evaluate():
-            if done[0] == steps:
-                self.fit_q()
-            else:
-                self.fit_q(steps=q_steps, rho=rho)
-            done[0] += 1
-            return self.elbo_and_grad()
-
-        return _adam_ascent(self, evaluate, steps, lr, train_z)
+        return self._fit_q(steps, rho, tol)
 
 
-class SVGPMulticlass(hb.model.Model):
+class SVGPMulticlass(_SVGPNonConjugate):
     """Sparse variational GP classification of C = num_classes classes with the softmax likelihood (hb.likelihoods.Softmax;
     GPflow's Softmax / MultiClass): C latent functions that share z, the lengthscales and k_var, f_c = sqrt(k_var) (u_c A +
     residual), with C independent full-rank blocks q(u_c) = N(m_c, S_c S_c^T) -- one Normal with n_layers = [C].
@@ -606,85 +640,17 @@ class SVGPMulticlass(hb.model.Model):
         ll = tf.reduce_sum(self.likelihood.logp(f, tf.transpose(self.Yhot)))
         return (self.N / n) * ll - self.KL()
 
-    select_inducing = SVGP.select_inducing
-
-    def reset_q(self):
-        """Set every q(u_c) to the prior N(0, I), where natgrad_q's own default starts: a freshly built model holds a
-        RANDOM q(u).  Call this before the first fit_q()."""
-        self.initialize()
-        C, M = self.num_classes, _part(self, "u").size
-        self._write_blocks(np.zeros((C, M)), np.broadcast_to(np.eye(M), (C, M, M)))
-
-    def _write_blocks(self, m, S):
-        q, sess = _part(self, "u"), self._session
-        sess.write_raw(_part(q, "q_mu"), m)
-        sess.write_raw(_part(q, "q_sqrt"), tri_pack(S) if q.packed else S)
-
-    def _current_blocks(self):
-        """(m [C, M], S [C, M, M] lower) of the model's q(u) as the session stores it, float64 numpy."""
-        self.initialize()
-        q, sess = _part(self, "u"), self._session
-        C, M = self.num_classes, q.size
-        S = np.asarray(sess.read_raw(_part(q, "q_sqrt")), dtype=np.float64)
-        S = tri_unpack(S.reshape(C, -1)) if q.packed else np.tril(S.reshape(C, M, M))
-        return np.asarray(sess.read_raw(_part(q, "q_mu")), dtype=np.float64).reshape(C, M), S
-
     def fit_q(self, steps=50, rho=None, tol=1e-8):
         """Fit the C blocks of q(u) at the current z, lengthscales and k_var by natural-gradient steps from the model's
         CURRENT q, over the model's full device-resident X and labels, and write them back.  Returns (m [C, M],
         S [C, M, M], info) as SparseGP.natgrad_q does.  rho=None: the likelihood's natgrad_rho, 0.5 -- a full step
         diverges.  Start from reset_q(), not from the random initial q.  The fit takes the moments without the residual
         (natgrad_q(residual='neglected')) whatever the model's `residual`: see setUp."""
-        self.initialize()
-        lik = _part(self, "likelihood")
-        rho = lik.natgrad_rho if rho is None else rho
-        m, S, info = _part(self, "gp").natgrad_q(_part(self, "X"), _part(self, "Y"), lik, k_var=_scalar(self, "k_var"),
-                                                 residual=self._likelihood_residual(), q0=self._current_blocks(), steps=steps,
-                                                 rho=rho, tol=tol)
-        self._write_blocks(m, S)
-        return m, S, info
+        return self._fit_q(steps, rho, tol)
 
     def _likelihood_residual(self):
         """The residual mode whose moments the likelihood sees: 'neglected' for 'diagonal' too (the class docstring)."""
         return "neglected" if self.residual == "diagonal" else self.residual
-
-    def _hyper_variables(self):
-        """The Variables the ELBO at fixed q(u_c) depends on, by the names the gradient uses."""
-        gp = _part(self, "gp")
-        return dict(z=_part(gp, "z"), lengthscales=_part(_part(gp, "kern"), "lengthscales"), k_var=_part(self, "k_var"))
-
-    def elbo_and_grad(self):
-        """(value, grad): the fixed-node ELBO over the model's full X and labels at the model's CURRENT q(u) -- the value
-        fit_q reports -- and its exact partial gradient at that q with respect to the RAW (free) parameters, grad =
-        dict(z, lengthscales, k_var) in the shapes of the raw arrays, float64 numpy.  SparseGP.elbo_and_grad_multi
-        (float64 arithmetic whatever the session's dtype; the moments without the residual, as fit_q takes them), chained
-        through the transforms' dforward.  At the q fit_q converges to it is the total derivative of the fitted ELBO up to
-        the node error of the step's curvature (see elbo_and_grad_multi)."""
-        self.initialize()
-        value, cons = _part(self, "gp").elbo_and_grad_multi(_part(self, "X"), _part(self, "Y"), _part(self, "likelihood"),
-                                                            self._current_blocks(), k_var=_scalar(self, "k_var"),
-                                                            residual=self._likelihood_residual())
-        return value, _chain_to_raw(self, cons)
-
-    def fit_hyper(self, steps, lr=0.01, train_z=True, q_steps=5, rho=None):
-        """Deterministic full-batch fit of the hyper-parameters, the alternation of SVGPLik.fit_hyper: every outer step
-        runs fit_q(steps=q_steps, rho=rho) from the current q(u), then takes ONE Adam ASCENT step on elbo_and_grad() in the
-        raw parameters of the lengthscales, k_var and (train_z) z, on the host in float64.  No minibatch noise.  Ends with
-        a fit_q() at the final parameters.  Returns the trace of ELBO values, steps + 1 entries: after the first fit_q at
-        the starting parameters .. after the closing fit_q() at the final ones.  A step after which a factorisation fails
-        raises graph.CholeskyError with the last good parameters restored.  Call reset_q() first: the first fit_q starts
-        at the model's current q(u).  rho=None: the likelihood's natgrad_rho (0.5), as for fit_q."""
-        steps, done = int(steps), [0]
-
-        def evaluate():
-            if done[0] == steps:
-                self.fit_q()
-            else:
-                self.fit_q(steps=q_steps, rho=rho)
-            done[0] += 1
-            return self.elbo_and_grad()
-
-        return _adam_ascent(self, evaluate, steps, lr, train_z)
 
     def predict_f(self, Xnew, residual=None):
         """(mean [C, n], var [C, n]) of the latent functions at Xnew [n, d]: SparseGP.posterior((m_c, S_c)) per class.
@@ -726,7 +692,7 @@ class SVGPMulticlass(hb.model.Model):
         return ld.cpu().numpy(), float(total.cpu()[0])
 
 
-class SVGPHetero(hb.model.Model):
+class SVGPHetero(_SVGPNonConjugate):
     """Sparse variational GP regression with input-dependent noise: y ~ N(f(x), exp(g(x) + c)) with the likelihood
     hb.likelihoods.HeteroscedasticGaussian -- two latent functions, the mean f and the log noise variance g, that share z,
     the lengthscales and k_var (f_c = sqrt(k_var) u_c A), with two independent full-rank blocks q(u_f), q(u_g): one Normal
@@ -767,7 +733,6 @@ class SVGPHetero(hb.model.Model):
             self.lik_param = hb.param.Variable([1])
             self.lik_param = np.ones(1) * self.likelihood.param
         self.residual = residual
-        self.num_classes = 2      # the blocks of q(u): what the shared block helpers of SVGPMulticlass read
 
     @hb.model.AutoOptimize()
     def ELBO(self):
@@ -779,41 +744,12 @@ class SVGPHetero(hb.model.Model):
             ll = tf.reduce_sum(self.likelihood.logp(f, tf.transpose(self.Y)))
         return (self.N / n) * ll - self.KL()
 
-    current_likelihood = SVGPLik.current_likelihood
-    select_inducing = SVGP.select_inducing
-    reset_q = SVGPMulticlass.reset_q
-    _write_blocks = SVGPMulticlass._write_blocks
-    _current_blocks = SVGPMulticlass._current_blocks
-    _hyper_variables = SVGPLik._hyper_variables
-
     def fit_q(self, steps=50, rho=None, tol=1e-8):
         """Fit the two blocks of q(u) at the current z, lengthscales, k_var and c by natural-gradient steps from the model's
         CURRENT q, over the model's full device-resident X, Y, and write them back.  Returns (m [2, M], S [2, M, M], info) as
         SparseGP.natgrad_q does.  rho=None: the likelihood's natgrad_rho, 0.5 -- a full step diverges.  Start from
         reset_q(), not from the random initial q."""
-        self.initialize()
-        lik = self.current_likelihood()
-        rho = lik.natgrad_rho if rho is None else rho
-        m, S, info = _part(self, "gp").natgrad_q(_part(self, "X"), _part(self, "Y"), lik, k_var=_scalar(self, "k_var"),
-                                                 residual=self.residual, q0=self._current_blocks(), steps=steps, rho=rho,
-                                                 tol=tol)
-        self._write_blocks(m, S)
-        return m, S, info
-
-    def elbo_and_grad(self):
-        """(value, grad): the closed-form ELBO over the model's full X, Y at the model's CURRENT q(u) -- the value fit_q
-        reports -- and its exact partial gradient at that q with respect to the RAW (free) parameters, grad = dict(z,
-        lengthscales, k_var) and, with learn_likelihood=True, lik_param, in the shapes of the raw arrays, float64 numpy
-        (SparseGP.elbo_and_grad_multi, chained through the transforms' dforward).  At the q fit_q converges to it is the
-        total derivative of the fitted ELBO."""
-        self.initialize()
-        kw = dict(lik_grad=True) if _part(self, "learn_likelihood") else {}
-        value, cons = _part(self, "gp").elbo_and_grad_multi(_part(self, "X"), _part(self, "Y"), self.current_likelihood(),
-                                                            self._current_blocks(), k_var=_scalar(self, "k_var"),
-                                                            residual=self.residual, **kw)
-        return value, _chain_to_raw(self, cons)
-
-    fit_hyper = SVGPMulticlass.fit_hyper
+        return self._fit_q(steps, rho, tol)
 
     def predict_f(self, Xnew):
         """(mean [2, n], var [2, n]) of the two latent functions at Xnew [n, d] (rows: f, g), from ONE pass

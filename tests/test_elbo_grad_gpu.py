@@ -284,7 +284,7 @@ def test_svgplik_gradient_against_central_differences_of_its_own_value():
     val, g = m.elbo_and_grad()
     raw0 = _raw_of(m)
     assert set(g) == {"z", "lengthscales", "k_var"} and all(g[n].shape == raw0[n].shape for n in g)
-    qm, qS = m._current_q()
+    qm, (qS,) = m._current_blocks()
     hv = m._hyper_variables()
 
     def f_dev(name, x):

@@ -97,11 +97,25 @@ def test_rbf_model_inputs_refuses_before_the_session_is_touched():
 def test_check_lik_inputs_refusals():
     lik, M = hb.likelihoods.Bernoulli(), 4
     Y1, Y2, q = np.zeros((5, 1)), np.zeros((5, 2)), (np.zeros((1, 4)), np.eye(4))
-    check = lambda **kw: sparse._check_lik_inputs(*[{**dict(who="who", likelihood=lik, k_var=1.0, residual="diagonal", q=q, Yd=Y1,
-                                                           M=M), **kw}[k]
-                                                    for k in ("who", "likelihood", "k_var", "residual", "q", "Yd", "M")])
+    check = lambda **kw: sparse._check_lik_inputs(*[{**dict(who="who", name="q", likelihood=lik, k_var=1.0, residual="diagonal",
+                                                           q=q, Yd=Y1, M=M), **kw}[k]
+                                                    for k in ("who", "name", "likelihood", "k_var", "residual", "q", "Yd", "M")])
     m0, S0 = check(q=([[0, 1, 2, 3]], np.eye(4, dtype=np.float32)))
     assert m0.dtype == S0.dtype == np.float64 and m0.shape == (1, 4) and check(q=None) is None
+    assert S0.shape == (1, 4, 4)                                            # the one block of a one-latent q
+    # the block-shaped q of a likelihood over C = 3 latent functions
+    lik3, Y3 = hb.likelihoods.Softmax(3, nodes=np.zeros((2, 3))), np.zeros((5, 1))
+    m3, S3 = check(likelihood=lik3, Yd=Y3, q=(np.zeros((3, 4), dtype=np.float32), [np.eye(4)] * 3))
+    assert m3.dtype == S3.dtype == np.float64 and m3.shape == (3, 4) and S3.shape == (3, 4, 4)
+    assert check(likelihood=lik3, Yd=Y3, q=None) is None
+    with pytest.raises(NotImplementedError, match="mean-field"):
+        check(likelihood=lik3, Yd=Y3, q=(np.zeros((3, 4)), np.ones((3, 4))))
+    with pytest.raises(ValueError, match=r"q = \(m \[3, 4\], S \[3, 4, 4\]\) expected"):
+        check(likelihood=lik3, Yd=Y3, q=(np.zeros((3, 5)), np.stack([np.eye(5)] * 3)))     # M of another z
+    with pytest.raises(ValueError, match=r"q = \(m \[3, M\], S \[3, M, M\]\) expected"):
+        check(likelihood=lik3, Yd=Y3, q=q)                                  # the one-latent shape
+    with pytest.raises(ValueError, match="labels"):
+        check(likelihood=lik3, Yd=Y3 + 3.0)
     with pytest.raises(NotImplementedError, match="fullrank"):
         check(residual="fullrank")
     with pytest.raises(ValueError, match="residual"):

@@ -124,7 +124,8 @@ def _q_of(m):
     """(mean [1, M], S [M, M] lower or s [M]) as the session stores them, float64."""
     q, sess = object.__getattribute__(m, "u"), m._session
     if q.q_shape == "fullrank":
-        return m._current_q()
+        qm, (qS,) = m._current_blocks()
+        return qm, qS
     raw = lambda k: np.asarray(sess.read_raw(object.__getattribute__(q, k)), dtype=np.float64).reshape(-1)
     return raw("q_mu").reshape(1, -1), np.exp(raw("q_sqrt"))
 

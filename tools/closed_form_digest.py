@@ -6,7 +6,9 @@ Fixed-seed problems, the PUBLIC API only (so the script runs unchanged on an old
 returned array or float, taken over its float64 bytes; a call that raises prints `name raised <ExceptionType>`.  Two runs
 of one tree must agree first (the kernels fold in fixed order); then two trees whose host code differs only in where it
 lives must agree line by line.  Sessions float32 and float64; (N, M, d, P) = (97, 32, 1, 1): one chunk, fragment images
-in float32; (40001, 96, 3, 2): two chunks; (4096, 50, 1, 1): M no multiple of 32, the plain forms."""
+in float32; (40001, 96, 3, 2): two chunks; (4096, 50, 1, 1): M no multiple of 32, the plain forms.  The likelihoods over
+several latent functions (Softmax with 3 classes over 16 fixed nodes, HeteroscedasticGaussian) run natgrad_q,
+elbo_and_grad_multi and the fit_hyper of their models on the same problems."""
 import hashlib
 import os
 import sys
@@ -17,10 +19,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import henbun_amd as hb  # noqa: E402
-from henbun_amd.models import SVGP, ExactGPR, SVGPLik  # noqa: E402
+from henbun_amd.models import SVGP, ExactGPR, SVGPHetero, SVGPLik, SVGPMulticlass  # noqa: E402
 
 CASES = [(97, 32, 1, 1), (40001, 96, 3, 2), (4096, 50, 1, 1)]
 NOISE, K_VAR = 0.4, 1.3
+NODES = np.random.RandomState(7).randn(16, 3)          # the softmax likelihood's fixed nodes [S, C]
 
 
 def digest(name, v):
@@ -46,7 +49,8 @@ def call(name, fn):
 
 
 def problem(N, M, d, P):
-    """The data of tests/test_optimal_q_gpu.py::_stats_case, plus labels and counts for the two other likelihoods."""
+    """The data of tests/test_optimal_q_gpu.py::_stats_case, plus labels and counts for the other likelihoods (the
+    three-class labels from a stream of their own: the draws above are those of the earlier digests)."""
     rng = np.random.RandomState(N + M + d + P)
     dom = 0.5 * M if d == 1 else 4.0
     X = rng.uniform(0, dom, (N, d))
@@ -56,7 +60,8 @@ def problem(N, M, d, P):
     ell = np.ones(1) * 0.9 if d == 1 else np.array([0.9, 1.1, 1.3])
     ybin = (rng.uniform(size=(N, 1)) < 1.0 / (1.0 + np.exp(-2.0 * F[:, :1]))).astype(np.float64)
     ycnt = rng.poisson(np.exp(F[:, :1])).astype(np.float64)
-    return X, Y, Z, ell, ybin, ycnt
+    score = np.stack([F[:, 0], -F[:, 0], np.zeros(N)], 1) + 0.5 * np.random.RandomState(N + M + d + P + 1).randn(N, 3)
+    return X, Y, Z, ell, ybin, ycnt, np.argmax(score, 1).astype(np.float64)[:, None]
 
 
 class Host(hb.model.Model):
@@ -65,7 +70,7 @@ class Host(hb.model.Model):
         self.gp = hb.gp.SparseGP(kern=hb.gp.kernels.UnitRBF(ell), z=Z)
 
 
-def sparse_routes(tag, dtype, X, Y, Z, ell, ybin, ycnt):
+def sparse_routes(tag, dtype, X, Y, Z, ell, ybin, ycnt, ycls):
     m = Host(X=X, Y=Y, Z=Z, ell=ell, dtype=dtype)
     m.gp.kern.lengthscales = ell.copy()
     m.initialize()
@@ -86,6 +91,19 @@ def sparse_routes(tag, dtype, X, Y, Z, ell, ybin, ycnt):
                 call(tag + "natgrad_q.%s.rho%g.%s" % (lname, rho, start),
                      lambda: gp.natgrad_q(X, y, lik, k_var=K_VAR, q0=qs, steps=3, rho=rho))
         call(tag + "elbo_and_grad.%s" % lname, lambda: gp.elbo_and_grad(X, y, lik, q0, k_var=K_VAR))
+    for lname, lik in (("gaussian", hb.likelihoods.Gaussian(NOISE)), ("laplace", hb.likelihoods.Laplace(0.5))):
+        call(tag + "elbo_and_grad.%s.lik_grad" % lname, lambda: gp.elbo_and_grad(X, Y[:, :1], lik, q0, k_var=K_VAR, lik_grad=True))
+    for lname, lik, y in (("softmax", hb.likelihoods.Softmax(3, nodes=NODES), ycls),
+                          ("hetgauss", hb.likelihoods.HeteroscedasticGaussian(-1.0), Y[:, :1])):
+        scale = 1.0 + 0.1 * np.arange(lik.num_latent)
+        qC = (scale[:, None] * q0[0], scale[:, None, None] * q0[1])          # blocks (m [C, M], S [C, M, M]) that differ
+        for start, qs in (("prior", None), ("q0", qC)):
+            call(tag + "natgrad_q.%s.rho0.5.%s" % (lname, start),
+                 lambda: gp.natgrad_q(X, y, lik, k_var=K_VAR, q0=qs, steps=3, rho=0.5))
+        call(tag + "elbo_and_grad_multi.%s" % lname, lambda: gp.elbo_and_grad_multi(X, y, lik, qC, k_var=K_VAR))
+        if lik.trainable:
+            call(tag + "elbo_and_grad_multi.%s.lik_grad" % lname,
+                 lambda: gp.elbo_and_grad_multi(X, y, lik, qC, k_var=K_VAR, lik_grad=True))
     if q is not None:
         xs = np.linspace(X.min(), X.max(), 33 * X.shape[1]).reshape(33, X.shape[1])
         call(tag + "pathwise_draws", lambda: gp.pathwise_draws((q[0][:1], q[1]), 4, num_features=256, k_var=K_VAR, seed=1)(xs))
@@ -105,10 +123,10 @@ def exact_routes(tag, dtype, X, Y, ell):
     call(tag + "ExactGPR.fit_hyper", lambda: (m.fit_hyper(2), m.gp.kern.lengthscales.value, m.k_var.value, m.var.value))
 
 
-def model_routes(tag, dtype, X, Y, Z, ell, ybin):
+def model_routes(tag, dtype, X, Y, Z, ell, ybin, ycls):
     def fresh(cls, y, **kw):
         np.random.seed(0)                # the models draw their initial q(u) from numpy's global stream
-        m = cls(X=X, Y=y, Z=Z, dtype=dtype, **kw)
+        m = cls(X=X, Z=Z, dtype=dtype, **{"y" if cls is SVGPMulticlass else "Y": y}, **kw)
         m.gp.kern.lengthscales = ell[:1].copy()
         m.k_var = np.ones(1) * K_VAR
         return m
@@ -121,6 +139,13 @@ def model_routes(tag, dtype, X, Y, Z, ell, ybin):
     call(tag + "SVGP.fit_hyper", lambda: (m.fit_hyper(3), hyper(m), m.var.value))
     ml = fresh(SVGPLik, ybin, likelihood=hb.likelihoods.Bernoulli())
     call(tag + "SVGPLik.reset_q.fit_hyper", lambda: (ml.reset_q(), ml.fit_hyper(2, q_steps=2), hyper(ml)))
+    ml = fresh(SVGPLik, Y[:, :1], likelihood=hb.likelihoods.Gaussian(NOISE), learn_likelihood=True)
+    call(tag + "SVGPLik.learn_likelihood.reset_q.fit_hyper",
+         lambda: (ml.reset_q(), ml.fit_hyper(2, q_steps=2), hyper(ml), ml.lik_param.value))
+    mc = fresh(SVGPMulticlass, ycls, num_classes=3, nodes=NODES)
+    call(tag + "SVGPMulticlass.reset_q.fit_hyper", lambda: (mc.reset_q(), mc.fit_hyper(2, q_steps=2), hyper(mc)))
+    mh = fresh(SVGPHetero, Y[:, :1])
+    call(tag + "SVGPHetero.reset_q.fit_hyper", lambda: (mh.reset_q(), mh.fit_hyper(2, q_steps=2), hyper(mh), mh.lik_param.value))
     call(tag + "greedy_inducing", lambda: hb.gp.greedy_inducing(X, Z.shape[0], ell, return_info=True, dtype=dtype))
 
 
@@ -128,13 +153,13 @@ def main():
     for dtype in ("float32", "float64"):
         for N, M, d, P in CASES:
             tag = "%s.N%d.M%d.d%d.P%d." % (dtype, N, M, d, P)
-            X, Y, Z, ell, ybin, ycnt = problem(N, M, d, P)
+            X, Y, Z, ell, ybin, ycnt, ycls = problem(N, M, d, P)
             cfg = hb.settings.get_settings()
             cfg.numerics.jitter_level = 1e-5 if d == 1 else 1e-3
             with hb.settings.temp_settings(cfg):
-                sparse_routes(tag, dtype, X, Y, Z, ell, ybin, ycnt)
+                sparse_routes(tag, dtype, X, Y, Z, ell, ybin, ycnt, ycls)
                 exact_routes(tag, dtype, X, Y, ell)
-                model_routes(tag, dtype, X, Y, Z, ell, ybin)
+                model_routes(tag, dtype, X, Y, Z, ell, ybin, ycls)
 
 
 if __name__ == "__main__":
