@@ -31,6 +31,18 @@
 // K(z, X) at a fixed q(u) ("Hyper-parameter gradient at fixed q(u)").  r takes the place of Y[:, 0] in ys,
 // w is staged next to it and multiplies the accumulator before + R r; everything else is the code above, so w == 1,
 // r = Y[:, 0] returns the bits of hb_sgp_kgrad_* at P = 1 (x * 1.0 is exact).  Columns beyond N hold K = 0 as before.
+//
+// Input gradient (hb_sgp_kgrad_x_*, hb_sgp_wkgrad_x_*, the template flag XG of both kernels): the products e (z - x) whose
+// ROW sums are zbar have the input gradient as their COLUMN sums,
+//     xbar_jd = + sum_i E_ij (z_id - x_jd) / ell_d^2          [N, d], double
+// (every dependence of the bound on X goes through K(z, X): Kdiag == 1).  Strip form: a lane keeps one accumulator per
+// (column tile, dimension) over its rows of a step; at the end of the step the four lane groups l / 16 are folded with two
+// shuffles (xor 16, then 32), the 8 waves through an LDS array [KG_NW][KG_NB][D] in wave order (a wave without a row tile
+// adds zeros), and thread (c, dd) writes the column.  A column belongs to one step of one workgroup and its sum runs over
+// the rows in an order that depends on M alone: no atomics, no workspace, no fold launch, and the bits of a column do
+// not depend on N or on the other columns of the call.  Plain form: the column's e_i go to LDS, every dimension is summed
+// per thread over its strided rows, per wave by shuffles and over the 4 waves in wave order.  XG = false is the code
+// without any of it (if constexpr): zbar and ellbar of the two entries are the same bits.
 #include "host_calls.cuh"   // hb_round64, HB_REQUIRE_RBF_MODEL
 #include "gram_value.cuh"
 
@@ -43,8 +55,15 @@
 #define KG_MAXG 256      // strips (workgroups) at most: one per CU
 #define KG_PLAIN_T 256
 
-template <typename T>
-struct KgArgs {
+template <bool XG>
+struct KgXbar {};
+template <>
+struct KgXbar<true> {
+  double* xbar;        // [N, d] (the _x entries only: the other instantiations keep their argument block)
+};
+
+template <typename T, bool XG>
+struct KgArgs : KgXbar<XG> {
   const T* X;          // [N, d]
   const T* Y;          // [N, P] (unweighted form)
   const double* w;     // [N], [N]: the column weights and r of the weighted form (P = 1), else unused
@@ -69,13 +88,16 @@ __global__ void __launch_bounds__(256) sgp_kgrad_pack_kernel(const double* __res
   }
 }
 
-// doubles of LDS the strip kernel takes: K, xs, ys, (weighted: wv), red, zs
-static inline size_t kg_strip_lds_elems(long M, int D, bool weighted) {
-  return (size_t)(M * KG_NB + KG_NB * D + KG_NB * KG_PMAX + (weighted ? KG_NB : 0) + KG_NW * D + M * D);
+// doubles of LDS the strip kernel takes: K, xs, ys, (weighted: wv), red, zs, (input gradient: the waves' column sums)
+static constexpr size_t kg_strip_lds_elems(long M, int D, bool weighted, bool xg) {
+  return (size_t)(M * KG_NB + KG_NB * D + KG_NB * KG_PMAX + (weighted ? KG_NB : 0) + KG_NW * D + M * D +
+                  (xg ? KG_NW * KG_NB * D : 0));
 }
+static_assert(kg_strip_lds_elems(KG_MMAX, KG_DMAX, true, true) * sizeof(double) <= 160 * 1024,
+              "the largest strip form must fit the 160 KB of LDS a CU has");
 
-template <typename T, int D, bool WT>
-__global__ void __launch_bounds__(KG_THREADS) sgp_kgrad_strip_kernel(KgArgs<T> a) {
+template <typename T, int D, bool WT, bool XG>
+__global__ void __launch_bounds__(KG_THREADS) sgp_kgrad_strip_kernel(KgArgs<T, XG> a) {
   typedef Mma<double> MM;
   extern __shared__ __attribute__((aligned(16))) double kg_smem[];
   const long M = a.M, N = a.N, P = a.P, nrt = M / 16, nks = M / 4;
@@ -85,6 +107,7 @@ __global__ void __launch_bounds__(KG_THREADS) sgp_kgrad_strip_kernel(KgArgs<T> a
   double* wv = ys + KG_NB * KG_PMAX;   // [KG_NB] (weighted form only)
   double* red = wv + (WT ? KG_NB : 0); // [KG_NW][D]
   double* zs = red + KG_NW * D;        // [M][D]: zbar of the strip, every row's slots owned by one lane
+  // (input gradient only: xr = zs + M * D, [KG_NW][KG_NB][D], the waves' column sums of a step)
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
 
@@ -116,6 +139,13 @@ __global__ void __launch_bounds__(KG_THREADS) sgp_kgrad_strip_kernel(KgArgs<T> a
       Ks[e] = j0 + c < N ? gram_value<double>(HB_KERN_RBF, a.z + k * D, xs + c * D, a.ell, a.dl, D) : 0.0;
     }
     __syncthreads();
+    double xacc[XG ? 2 : 1][XG ? D : 1];   // column sums of e (z - x) over this lane's rows of the step
+    if constexpr (XG) {
+#pragma unroll
+      for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+        for (int dd = 0; dd < D; ++dd) xacc[jt][dd] = 0.0;
+    }
     for (long it = w; it < nrt; it += KG_NW) {
       MM::Acc acc[2];
 #pragma unroll
@@ -153,6 +183,7 @@ __global__ void __launch_bounds__(KG_THREADS) sgp_kgrad_strip_kernel(KgArgs<T> a
             const double ed = e * diff;
             zb[dd] += ed;
             eacc[dd] = __builtin_fma(ed, diff, eacc[dd]);
+            if constexpr (XG) xacc[jt][dd] += ed;
           }
         }
         // the 16 column lanes of row i folded in a fixed order; lane l % 16 == 0 owns row i's slots of zs
@@ -163,6 +194,29 @@ __global__ void __launch_bounds__(KG_THREADS) sgp_kgrad_strip_kernel(KgArgs<T> a
           for (int off = 1; off < 16; off <<= 1) v += __shfl_xor(v, off, 64);
           if ((lane & 15) == 0) zs[i * D + dd] += v;
         }
+      }
+    }
+    if constexpr (XG) {
+      // the four lane groups l / 16 hold the rows l / 16 + 4 r of every row tile: fold them (16, then 32), then the 8
+      // waves in wave order; xr is read again only behind the barrier at the top of the next step
+      double* xr = zs + M * D;
+#pragma unroll
+      for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+        for (int dd = 0; dd < D; ++dd) {
+          double v = xacc[jt][dd];
+          v += __shfl_xor(v, 16, 64);
+          v += __shfl_xor(v, 32, 64);
+          if (lane < 16) xr[(w * KG_NB + 16 * jt + lane) * D + dd] = v;
+        }
+      __syncthreads();
+      if (tid < KG_NB * D) {
+        const int c = tid / D, dd = tid % D;
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < KG_NW; ++k) s += xr[(k * KG_NB + c) * D + dd];
+        const double l = a.ell[a.dl == 1 ? 0 : dd];
+        if (j0 + c < N) a.xbar[(j0 + c) * D + dd] = s / (l * l);
       }
     }
   }
@@ -185,13 +239,20 @@ __global__ void __launch_bounds__(KG_THREADS) sgp_kgrad_strip_kernel(KgArgs<T> a
 
 // plain form: a workgroup walks its columns one at a time; thread i (strided) owns row i and its slots of the partials
 // ([M, d] for zbar, then [M, d] row partials of ellbar)
-template <typename T, bool WT>
-__global__ void __launch_bounds__(KG_PLAIN_T) sgp_kgrad_plain_kernel(KgArgs<T> a) {
+// doubles of LDS the plain kernel takes: Kc, xc, yc, (weighted: the weight), (input gradient: the column's e and the
+// waves' sums)
+static inline size_t kg_plain_lds_elems(long M, long d, long P, bool weighted, bool xg) {
+  return (size_t)(M + d + P + (weighted ? 1 : 0) + (xg ? M + (KG_PLAIN_T / 64) * d : 0));
+}
+
+template <typename T, bool WT, bool XG>
+__global__ void __launch_bounds__(KG_PLAIN_T) sgp_kgrad_plain_kernel(KgArgs<T, XG> a) {
   extern __shared__ __attribute__((aligned(16))) double kg_smem[];
   const long M = a.M, N = a.N, d = a.d, P = a.P;
   double* Kc = kg_smem;   // [M]
   double* xc = Kc + M;    // [d]
   double* yc = xc + d;    // [P], then the column's weight (weighted form)
+  // (input gradient only: Ec = yc + P (+ 1 weighted), [M], the column of E; xr = Ec + M, [4][d], the waves' sums)
   const int tid = threadIdx.x;
   double* zp = a.part + (long)blockIdx.x * a.stride;
   double* ep = zp + M * d;
@@ -216,11 +277,35 @@ __global__ void __launch_bounds__(KG_PLAIN_T) sgp_kgrad_plain_kernel(KgArgs<T> a
       if (WT) kb *= yc[P];
       for (long p = 0; p < P; ++p) kb = __builtin_fma(a.R[i * P + p], yc[p], kb);
       const double e = kb * Kc[i];
+      if constexpr (XG) yc[P + (WT ? 1 : 0) + i] = e;
       for (long dd = 0; dd < d; ++dd) {
         const double diff = a.z[i * d + dd] - xc[dd];
         const double ed = e * diff;
         zp[i * d + dd] += ed;
         ep[i * d + dd] = __builtin_fma(ed, diff, ep[i * d + dd]);
+      }
+    }
+    if constexpr (XG) {
+      // per dimension: this thread's strided rows, the wave by shuffles, the 4 waves in wave order (thread dd); Ec, xr
+      // and xc are written again only behind the barriers at the top of the next column
+      const double* Ec = yc + P + (WT ? 1 : 0);
+      double* xr = yc + P + (WT ? 1 : 0) + M;
+      __syncthreads();
+      for (long dd = 0; dd < d; ++dd) {
+        double s = 0.0;
+        for (long i = tid; i < M; i += KG_PLAIN_T) {
+          const double ed = Ec[i] * (a.z[i * d + dd] - xc[dd]);
+          s += ed;
+        }
+        s = wave_sum(s);
+        if ((tid & 63) == 0) xr[(tid >> 6) * d + dd] = s;
+      }
+      __syncthreads();
+      if (tid < d) {
+        double s = 0.0;
+        for (int k = 0; k < KG_PLAIN_T / 64; ++k) s += xr[k * d + tid];
+        const double l = a.ell[a.dl == 1 ? 0 : tid];
+        a.xbar[j * d + tid] = s / (l * l);
       }
     }
   }
@@ -274,35 +359,38 @@ extern "C" long hb_sgp_kgrad_ws_elems(long N, long M, long d, long P) {
   return fast > plain ? fast : plain;
 }
 
-template <typename T, int D, bool WT>
-static int kg_launch_strip(const KgArgs<T>& a, long G, hipStream_t st) {
-  const size_t lds = kg_strip_lds_elems(a.M, D, WT) * sizeof(double);
-  static bool attr_set = false;   // once per instantiation: the largest M needs up to 150 KB of the CU's 160 KB
+template <typename T, int D, bool WT, bool XG>
+static int kg_launch_strip(const KgArgs<T, XG>& a, long G, hipStream_t st) {
+  const size_t lds = kg_strip_lds_elems(a.M, D, WT, XG) * sizeof(double);
+  // once per instantiation: the largest M needs up to 150 KB (158 KB with the input gradient) of the CU's 160 KB
+  static bool attr_set = false;
   if (!attr_set) {
-    const size_t lds_max = kg_strip_lds_elems(KG_MMAX, D, WT) * sizeof(double);
-    HB_HIP(hipFuncSetAttribute((const void*)sgp_kgrad_strip_kernel<T, D, WT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    const size_t lds_max = kg_strip_lds_elems(KG_MMAX, D, WT, XG) * sizeof(double);
+    HB_HIP(hipFuncSetAttribute((const void*)sgp_kgrad_strip_kernel<T, D, WT, XG>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lds_max));
     attr_set = true;
   }
-  hipLaunchKernelGGL((sgp_kgrad_strip_kernel<T, D, WT>), dim3((unsigned)G), dim3(KG_THREADS), lds, st, a);
+  hipLaunchKernelGGL((sgp_kgrad_strip_kernel<T, D, WT, XG>), dim3((unsigned)G), dim3(KG_THREADS), lds, st, a);
   HB_LAUNCH_CHECK();
   return 0;
 }
 
-// WT: Y is NULL, P is 1 and w, r [N] are given (hb_sgp_wkgrad_*); else w, r are NULL (hb_sgp_kgrad_*)
-template <typename T, bool WT>
+// WT: Y is NULL, P is 1 and w, r [N] are given (hb_sgp_wkgrad_*); else w, r are NULL (hb_sgp_kgrad_*).  XG: xbar [N, d]
+// is written as well (the _x entries); else xbar is NULL and unused
+template <typename T, bool WT, bool XG>
 static int sgp_kgrad(int kind, const T* X, const T* Y, const double* w, const double* r, const double* z, const double* ell,
-                     long dl, const double* Q, const double* R, double* zbar, double* ellbar, long N, long M, long d, long P,
-                     double* ws, hipStream_t st) {
-  const char* who = WT ? "hb_sgp_wkgrad" : "hb_sgp_kgrad";
+                     long dl, const double* Q, const double* R, double* zbar, double* ellbar, double* xbar, long N, long M,
+                     long d, long P, double* ws, hipStream_t st) {
+  const char* who = XG ? (WT ? "hb_sgp_wkgrad_x" : "hb_sgp_kgrad_x") : (WT ? "hb_sgp_wkgrad" : "hb_sgp_kgrad");
   HB_REQUIRE(N >= 1 && M >= 1 && d >= 1 && P >= 1, "%s: bad extents (N=%ld M=%ld d=%ld P=%ld)", who, N, M, d, P);
   HB_REQUIRE_RBF_MODEL(who, "is supported", kind, dl, d, (const void*)nullptr, M);   // (no Wfrag: W is not an operand)
   HB_REQUIRE(X && (WT ? (w && r) : Y != nullptr) && z && ell && Q && R, "%s: NULL input pointer", who);
-  HB_REQUIRE(zbar && ellbar, "%s: NULL output pointer", who);
+  HB_REQUIRE(zbar && ellbar && (!XG || xbar), "%s: NULL output pointer", who);
   HB_REQUIRE(d <= 256 && P <= 256 && M + d + P <= 8000, "%s: M=%ld d=%ld P=%ld too large", who, M, d, P);
   HB_REQUIRE(ws && (uintptr_t)ws % 16 == 0, "%s: needs a 16-byte aligned workspace of %ld doubles", who,
              hb_sgp_kgrad_ws_elems(N, M, d, P));
-  KgArgs<T> a;
+  KgArgs<T, XG> a;
+  if constexpr (XG) a.xbar = xbar;
   a.X = X; a.Y = Y; a.w = w; a.r = r; a.z = z; a.ell = ell; a.R = R; a.dl = dl; a.N = N; a.M = M; a.d = d; a.P = P;
   long G, ne;
   if (kg_is_fast(M, d, P)) {
@@ -318,10 +406,10 @@ static int sgp_kgrad(int kind, const T* X, const T* Y, const double* w, const do
     ne = 1;
     int rc;
     switch (d) {
-      case 1: rc = kg_launch_strip<T, 1, WT>(a, G, st); break;
-      case 2: rc = kg_launch_strip<T, 2, WT>(a, G, st); break;
-      case 3: rc = kg_launch_strip<T, 3, WT>(a, G, st); break;
-      default: rc = kg_launch_strip<T, 4, WT>(a, G, st); break;
+      case 1: rc = kg_launch_strip<T, 1, WT, XG>(a, G, st); break;
+      case 2: rc = kg_launch_strip<T, 2, WT, XG>(a, G, st); break;
+      case 3: rc = kg_launch_strip<T, 3, WT, XG>(a, G, st); break;
+      default: rc = kg_launch_strip<T, 4, WT, XG>(a, G, st); break;
     }
     if (rc) return rc;
   } else {
@@ -332,8 +420,17 @@ static int sgp_kgrad(int kind, const T* X, const T* Y, const double* w, const do
     a.per = (N + KG_MAXG - 1) / KG_MAXG;
     G = (N + a.per - 1) / a.per;
     ne = M;
-    const size_t lds = (size_t)(M + d + P + (WT ? 1 : 0)) * sizeof(double);
-    hipLaunchKernelGGL((sgp_kgrad_plain_kernel<T, WT>), dim3((unsigned)G), dim3(KG_PLAIN_T), lds, st, a);
+    const size_t lds = kg_plain_lds_elems(M, d, P, WT, XG) * sizeof(double);
+    if constexpr (XG) {
+      // the column of E doubles the footprint: up to 136 KB at the largest M + d + P the entry accepts
+      static bool attr_set = false;
+      if (!attr_set) {
+        HB_HIP(hipFuncSetAttribute((const void*)sgp_kgrad_plain_kernel<T, WT, XG>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)(kg_plain_lds_elems(8000, 256, 0, WT, XG) * sizeof(double))));
+        attr_set = true;
+      }
+    }
+    hipLaunchKernelGGL((sgp_kgrad_plain_kernel<T, WT, XG>), dim3((unsigned)G), dim3(KG_PLAIN_T), lds, st, a);
     HB_LAUNCH_CHECK();
   }
   const long fb = (M * d + 255) / 256 + 1;
@@ -346,20 +443,48 @@ static int sgp_kgrad(int kind, const T* X, const T* Y, const double* w, const do
 extern "C" int hb_sgp_kgrad_f32(int kind, const float* X, const float* Y, const double* z, const double* ell, long dl,
                                 const double* Q, const double* R, double* zbar, double* ellbar, long N, long M, long d, long P,
                                 double* ws, void* stream) {
-  return sgp_kgrad<float, false>(kind, X, Y, nullptr, nullptr, z, ell, dl, Q, R, zbar, ellbar, N, M, d, P, ws, (hipStream_t)stream);
+  return sgp_kgrad<float, false, false>(kind, X, Y, nullptr, nullptr, z, ell, dl, Q, R, zbar, ellbar, nullptr, N, M, d, P, ws,
+                                        (hipStream_t)stream);
 }
 extern "C" int hb_sgp_kgrad_f64(int kind, const double* X, const double* Y, const double* z, const double* ell, long dl,
                                 const double* Q, const double* R, double* zbar, double* ellbar, long N, long M, long d, long P,
                                 double* ws, void* stream) {
-  return sgp_kgrad<double, false>(kind, X, Y, nullptr, nullptr, z, ell, dl, Q, R, zbar, ellbar, N, M, d, P, ws, (hipStream_t)stream);
+  return sgp_kgrad<double, false, false>(kind, X, Y, nullptr, nullptr, z, ell, dl, Q, R, zbar, ellbar, nullptr, N, M, d, P, ws,
+                                         (hipStream_t)stream);
 }
 extern "C" int hb_sgp_wkgrad_f32(int kind, const float* X, const double* w, const double* r, const double* z, const double* ell,
                                  long dl, const double* Q, const double* R, double* zbar, double* ellbar, long N, long M, long d,
                                  double* ws, void* stream) {
-  return sgp_kgrad<float, true>(kind, X, nullptr, w, r, z, ell, dl, Q, R, zbar, ellbar, N, M, d, 1, ws, (hipStream_t)stream);
+  return sgp_kgrad<float, true, false>(kind, X, nullptr, w, r, z, ell, dl, Q, R, zbar, ellbar, nullptr, N, M, d, 1, ws,
+                                       (hipStream_t)stream);
 }
 extern "C" int hb_sgp_wkgrad_f64(int kind, const double* X, const double* w, const double* r, const double* z, const double* ell,
                                  long dl, const double* Q, const double* R, double* zbar, double* ellbar, long N, long M, long d,
                                  double* ws, void* stream) {
-  return sgp_kgrad<double, true>(kind, X, nullptr, w, r, z, ell, dl, Q, R, zbar, ellbar, N, M, d, 1, ws, (hipStream_t)stream);
+  return sgp_kgrad<double, true, false>(kind, X, nullptr, w, r, z, ell, dl, Q, R, zbar, ellbar, nullptr, N, M, d, 1, ws,
+                                        (hipStream_t)stream);
+}
+extern "C" int hb_sgp_kgrad_x_f32(int kind, const float* X, const float* Y, const double* z, const double* ell, long dl,
+                                  const double* Q, const double* R, double* zbar, double* ellbar, double* xbar, long N, long M,
+                                  long d, long P, double* ws, void* stream) {
+  return sgp_kgrad<float, false, true>(kind, X, Y, nullptr, nullptr, z, ell, dl, Q, R, zbar, ellbar, xbar, N, M, d, P, ws,
+                                       (hipStream_t)stream);
+}
+extern "C" int hb_sgp_kgrad_x_f64(int kind, const double* X, const double* Y, const double* z, const double* ell, long dl,
+                                  const double* Q, const double* R, double* zbar, double* ellbar, double* xbar, long N, long M,
+                                  long d, long P, double* ws, void* stream) {
+  return sgp_kgrad<double, false, true>(kind, X, Y, nullptr, nullptr, z, ell, dl, Q, R, zbar, ellbar, xbar, N, M, d, P, ws,
+                                        (hipStream_t)stream);
+}
+extern "C" int hb_sgp_wkgrad_x_f32(int kind, const float* X, const double* w, const double* r, const double* z,
+                                   const double* ell, long dl, const double* Q, const double* R, double* zbar, double* ellbar,
+                                   double* xbar, long N, long M, long d, double* ws, void* stream) {
+  return sgp_kgrad<float, true, true>(kind, X, nullptr, w, r, z, ell, dl, Q, R, zbar, ellbar, xbar, N, M, d, 1, ws,
+                                      (hipStream_t)stream);
+}
+extern "C" int hb_sgp_wkgrad_x_f64(int kind, const double* X, const double* w, const double* r, const double* z,
+                                   const double* ell, long dl, const double* Q, const double* R, double* zbar, double* ellbar,
+                                   double* xbar, long N, long M, long d, double* ws, void* stream) {
+  return sgp_kgrad<double, true, true>(kind, X, nullptr, w, r, z, ell, dl, Q, R, zbar, ellbar, xbar, N, M, d, 1, ws,
+                                       (hipStream_t)stream);
 }

@@ -98,6 +98,8 @@ def _input_variance(sess, X_var, Xd, who):
         v = X_var.to(device=sess.device, dtype=sess.torch_dtype)
     else:
         v = _host.upload(sess, np.asarray(X_var, dtype=np.float64))
+        if np.ndim(X_var) == 0:
+            v = v.reshape(())                                  # (upload hands a scalar back as [1]: a [d] only for d = 1)
     n, d = Xd.shape
     if tuple(v.shape) not in ((), (d,), (n, d)):
         raise ValueError("%s: X_var must be [%d, %d], [%d] or a scalar, got %s" % (who, n, d, d, tuple(v.shape)))
@@ -373,7 +375,7 @@ class SparseInference:
         m, S = m.cpu().numpy(), np.tril(S.cpu().numpy())
         return m, S[0] if C == 1 else S, dict(elbo=np.asarray(elbo), residual=np.asarray(resid), steps=it)
 
-    def collapsed_bound_and_grad(self, X, Y, noise_var, k_var=1.0, residual="diagonal"):
+    def collapsed_bound_and_grad(self, X, Y, noise_var, k_var=1.0, residual="diagonal", x_grad=False):
         """(value, grad): the collapsed bound of collapsed_bound() and its exact gradient with respect to the CONSTRAINED
         values, grad = dict(z=[M, d], lengthscales=[dl], noise_var=float, k_var=float), float64 numpy.  One pass over
         the data for the statistics, the M^3 tail, one more pass for the part of the gradient that goes through
@@ -387,15 +389,38 @@ class SparseInference:
         float32 session it can differ from collapsed_bound() by the float32 error of statistics().  Same restrictions
         and exception types as statistics(): UnitRBF, one expert, the lengthscales one Variable; residual 'fullrank'
         raises NotImplementedError; a K(z, z) + jitter I or Lambda that is not positive definite raises
-        graph.CholeskyError."""
+        graph.CholeskyError.
+
+        x_grad=True: grad also holds X [N, d], the gradient with respect to the INPUTS as the session stores them
+        (float64 numpy; a float32 session's X is exact in double, so it is the exact gradient at the stored values).
+        The bound depends on X through K(z, X) alone (k(x, x) = 1), so it is the column sums of the products whose row
+        sums are the streamed part of the z gradient, from the same pass (hb_sgp_kgrad_x; DESIGN.md 3, "Input gradient
+        and deep kernels").  The other entries and the value are the bits of x_grad=False."""
+        val, grad, xbar = self._collapsed_bound_and_grad(X, Y, noise_var, k_var, residual, x_grad)
+        if x_grad:
+            grad["X"] = xbar.cpu().numpy()
+        return val, grad
+
+    def _collapsed_bound_and_grad(self, X, Y, noise_var, k_var, residual, x_grad):
+        """(value, grad, xbar): collapsed_bound_and_grad with the input gradient left ON THE DEVICE (float64 [N, d]; None
+        without x_grad) -- models.DeepKernelSVGP chains it through its network there."""
         _check_residual(residual)
         if not (float(noise_var) > 0.0 and float(k_var) > 0.0):
             raise ValueError("noise_var and k_var must be positive (got %r, %r)" % (noise_var, k_var))
         sess, Xd, Yd, z, ell, W = self._grad_inputs(X, Y)
         stats = self._statistics_f64(sess, Xd, Yd, z, ell, W)
         H = sess.H
-        return self._grad_from_statistics(sess, z, ell, W, stats, noise_var, k_var, residual,
-                                          lambda Q, R: H.sgp_kgrad(Xd, Yd, z, ell, Q, R), int(Xd.shape[0]), int(Yd.shape[1]))
+        point = {"X": None}
+
+        def streamed(Q, R):
+            if not x_grad:
+                return H.sgp_kgrad(Xd, Yd, z, ell, Q, R)
+            zbar, ellbar, point["X"] = H.sgp_kgrad(Xd, Yd, z, ell, Q, R, x_grad=True)
+            return zbar, ellbar
+
+        val, grad = self._grad_from_statistics(sess, z, ell, W, stats, noise_var, k_var, residual, streamed,
+                                               int(Xd.shape[0]), int(Yd.shape[1]))
+        return val, grad, point["X"]
 
     def psi_bound_and_grad(self, X_mean, X_var, Y, noise_var, k_var=1.0, residual="diagonal"):
         """collapsed_bound_and_grad() for UNCERTAIN inputs x_n ~ N(X_mean_n, diag(X_var_n)): (value, grad) with the
@@ -519,7 +544,7 @@ class SparseInference:
                        H.workspace(torch.float64, sess.device, max(M * d, 1)))
         return zk, ek
 
-    def elbo_and_grad(self, X, Y, likelihood, q, k_var=1.0, residual="diagonal", lik_grad=False):
+    def elbo_and_grad(self, X, Y, likelihood, q, k_var=1.0, residual="diagonal", lik_grad=False, x_grad=False):
         """(value, grad): the ELBO sum_j E_q log p(y_j | f_j) - KL(q || N(0, I)) of a factorising likelihood at a FIXED
         q(u) = N(m, S S^T), q = (m [1, M], S [M, M] lower), and its partial gradient with respect to the CONSTRAINED
         z, lengthscales and k_var at that q: grad = dict(z=[M, d], lengthscales=[dl], k_var=float), float64 numpy.  At
@@ -550,12 +575,17 @@ class SparseInference:
         fitted q.  A likelihood that is not `trainable` raises ValueError.  The other entries and the value are the bits
         of lik_grad=False.
 
+        x_grad=True: grad also holds X [N, d], the partial gradient at that q with respect to the INPUTS as the session
+        stores them, float64 numpy: the marginals depend on X through K(z, X) alone, so it is the column sums of the
+        products of the hb_sgp_wkgrad pass, whose E carries lam_j and gamma_j (hb_sgp_wkgrad_x, one call over all of X).
+        The other entries and the value are the bits of x_grad=False.
+
         A likelihood over several latent functions (likelihoods.Softmax) raises NotImplementedError: that route has its
         own weights, q and name, elbo_and_grad_multi (both run _elbo_and_grad)."""
         if getattr(likelihood, "num_latent", 1) > 1:
             raise NotImplementedError("elbo_and_grad: one latent function only (%s has %d: use elbo_and_grad_multi)"
                                       % (type(likelihood).__name__, likelihood.num_latent))
-        return self._elbo_and_grad("elbo_and_grad", X, Y, likelihood, q, k_var, residual, lik_grad)
+        return self._elbo_and_grad("elbo_and_grad", X, Y, likelihood, q, k_var, residual, lik_grad, x_grad=x_grad)
 
     def elbo_and_grad_multi(self, X, Y, likelihood, q, k_var=1.0, residual="diagonal", lik_grad=False):
         """(value, grad): elbo_and_grad for a likelihood over C = likelihood.num_latent latent functions
@@ -595,12 +625,12 @@ class SparseInference:
                              % (who, type(likelihood).__name__))
         return self._elbo_and_grad(who, X, Y, likelihood, q, k_var, residual, lik_grad)
 
-    def _elbo_and_grad(self, who, X, Y, likelihood, q, k_var, residual, lik_grad):
+    def _elbo_and_grad(self, who, X, Y, likelihood, q, k_var, residual, lik_grad, x_grad=False):
         """The one route behind elbo_and_grad and elbo_and_grad_multi (which document it), on the blocks q = (m [C, M],
         S [C, M, M]) of C = likelihood.num_latent latent functions: the float64 chunk walk -- marginals (_marginals), the
         likelihood's weights w, r (Likelihood.weights), weighted statistics (_weighted_stats) -- then per latent function the
         tail G_c, g_c, Q_c, R_c with hb_sgp_wkgrad over all of X, ONE Cholesky and Gram VJP of K(z, z) for T = -sum_c (2 G_c
-        Phi_c + g_c^T b_c), and the KL from S."""
+        Phi_c + g_c^T b_c), and the KL from S.  x_grad (one latent function only): the input gradient of that call too."""
         if lik_grad and not getattr(likelihood, "trainable", False):
             raise ValueError("%s: lik_grad=True needs a likelihood with a continuous parameter (got %s)"
                              % (who, type(likelihood).__name__))
@@ -642,7 +672,10 @@ class SparseInference:
             g = (m[c:c + 1] * np.sqrt(k)).contiguous()
             Q = H.matmul(W, H.matmul(Gm, W), transA=True, alpha=2.0)
             R = H.matmul(W, g, transA=True, transB=True)
-            zc, ec = H.sgp_wkgrad(Xd, w[c, :N], r[c, :N], z, ell, Q, R)
+            if x_grad:
+                zc, ec, xbar = H.sgp_wkgrad(Xd, w[c, :N], r[c, :N], z, ell, Q, R, x_grad=True)
+            else:
+                zc, ec = H.sgp_wkgrad(Xd, w[c, :N], r[c, :N], z, ell, Q, R)
             Tc = H.matmul(Gm, Phi[c].contiguous(), alpha=-2.0) - H.matmul(g, b[c:c + 1].contiguous(), transA=True)
             zbar, ellbar, T = (zc, ec, Tc) if T is None else (zbar + zc, ellbar + ec, T + Tc)
         zk, ek = self._kmm_grads(sess, z, ell, W, T.contiguous())
@@ -653,6 +686,8 @@ class SparseInference:
         grad = dict(z=(zbar + zk).cpu().numpy(), lengthscales=(ellbar + ek).cpu().numpy(), k_var=float(dks.cpu()) / (2.0 * k))
         if lik_grad:
             grad["lik_param"] = float(dps[0].cpu()[0])
+        if x_grad:
+            grad["X"] = xbar.cpu().numpy()
         return float(lsum.cpu()[0]) - kl, grad
 
     # -- pathwise posterior function draws (Wilson et al. 2020) -----------------------------------------------------

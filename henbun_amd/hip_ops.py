@@ -2169,11 +2169,13 @@ def sgp_kgrad_ws_elems(N, M, d, P):
     return _query("hb_sgp_kgrad_ws_elems", N, M, d, P)
 
 
-def sgp_kgrad(X, Y, z, ell, Q, R, ws=None):
+def sgp_kgrad(X, Y, z, ell, Q, R, ws=None, x_grad=False):
     """Streamed part of the gradient of the collapsed bound (hb_sgp_kgrad): with K = K(z, X), Kbar = Q K + R Y^T and
     E = Kbar o K, returns (zbar [M, d], ellbar [dl]) = (-sum_j E_ij (z_i - x_j) / ell^2, sum_ij E_ij (z_i - x_j)^2 / ell^3)
     as float64 device tensors.  X [N, d] and Y [N, P] share one storage dtype (float32 or float64); z [M, d], ell [dl],
-    Q [M, M], R [M, P] are float64 and all arithmetic is float64.  Two calls on the same inputs return the same bits."""
+    Q [M, M], R [M, P] are float64 and all arithmetic is float64.  Two calls on the same inputs return the same bits.
+    x_grad=True (hb_sgp_kgrad_x): returns (zbar, ellbar, xbar) with the input gradient xbar [N, d] = +sum_i E_ij
+    (z_i - x_j) / ell^2, float64, from the same pass; zbar and ellbar are the bits of x_grad=False."""
     if X.dim() != 2 or Y.dim() != 2 or z.dim() != 2 or X.shape[0] != Y.shape[0] or X.shape[1] != z.shape[1]:
         raise ValueError("sgp_kgrad: X [N, d], Y [N, P], z [M, d] expected, got %s %s %s"
                          % (tuple(X.shape), tuple(Y.shape), tuple(z.shape)))
@@ -2189,16 +2191,22 @@ def sgp_kgrad(X, Y, z, ell, Q, R, ws=None):
     zbar = _empty((M, d), dtype=torch.float64, device=dev)
     ellbar = _empty((ell.numel(),), dtype=torch.float64, device=dev)
     ws = _ws("sgp_kgrad", ws, torch.float64, dev, sgp_kgrad_ws_elems(N, M, d, P), "sgp_kgrad_ws_elems")
+    if x_grad:
+        xbar = _empty((N, d), dtype=torch.float64, device=dev)
+        _lib.lib().call("hb_sgp_kgrad_x" + _suf(X), KERN_RBF, _p(X), _p(Y), _p(z), _p(ell), ell.numel(), _p(Q), _p(R),
+                        _p(zbar), _p(ellbar), _p(xbar), N, M, d, P, _p(ws), stream())
+        return zbar, ellbar, xbar
     _lib.lib().call("hb_sgp_kgrad" + _suf(X), KERN_RBF, _p(X), _p(Y), _p(z), _p(ell), ell.numel(), _p(Q), _p(R), _p(zbar),
                     _p(ellbar), N, M, d, P, _p(ws), stream())
     return zbar, ellbar
 
 
-def sgp_wkgrad(X, w, r, z, ell, Q, R, ws=None):
+def sgp_wkgrad(X, w, r, z, ell, Q, R, ws=None, x_grad=False):
     """Column-weighted form of sgp_kgrad (hb_sgp_wkgrad): Kbar_ij = w_j (Q K)_ij + R_i r_j, one latent function.  X [N, d]
     in its storage dtype (float32 or float64); w [N], r [N], z [M, d], ell [dl], Q [M, M], R [M, 1] are float64 and all
     arithmetic is float64.  Returns (zbar [M, d], ellbar [dl]) as sgp_kgrad does; w == 1, r = Y[:, 0] returns its bits at
-    P = 1; two calls on the same inputs return the same bits."""
+    P = 1; two calls on the same inputs return the same bits.  x_grad=True (hb_sgp_wkgrad_x): (zbar, ellbar, xbar) with the
+    input gradient xbar [N, d] as sgp_kgrad returns it (E carries w and r)."""
     if X.dim() != 2 or z.dim() != 2 or X.shape[1] != z.shape[1] or tuple(w.shape) != (X.shape[0],) or tuple(r.shape) != w.shape:
         raise ValueError("sgp_wkgrad: X [N, d], w [N], r [N], z [M, d] expected, got %s %s %s %s"
                          % (tuple(X.shape), tuple(w.shape), tuple(r.shape), tuple(z.shape)))
@@ -2213,6 +2221,11 @@ def sgp_wkgrad(X, w, r, z, ell, Q, R, ws=None):
     zbar = _empty((M, d), dtype=torch.float64, device=dev)
     ellbar = _empty((ell.numel(),), dtype=torch.float64, device=dev)
     ws = _ws("sgp_wkgrad", ws, torch.float64, dev, sgp_kgrad_ws_elems(N, M, d, 1), "sgp_kgrad_ws_elems")
+    if x_grad:
+        xbar = _empty((N, d), dtype=torch.float64, device=dev)
+        _lib.lib().call("hb_sgp_wkgrad_x" + _suf(X), KERN_RBF, _p(X), _p(w), _p(r), _p(z), _p(ell), ell.numel(), _p(Q), _p(R),
+                        _p(zbar), _p(ellbar), _p(xbar), N, M, d, _p(ws), stream())
+        return zbar, ellbar, xbar
     _lib.lib().call("hb_sgp_wkgrad" + _suf(X), KERN_RBF, _p(X), _p(w), _p(r), _p(z), _p(ell), ell.numel(), _p(Q), _p(R),
                     _p(zbar), _p(ellbar), N, M, d, _p(ws), stream())
     return zbar, ellbar

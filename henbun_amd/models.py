@@ -399,6 +399,183 @@ class BayesianGPLVM(hb.model.Model):
         return mean.cpu().numpy(), v.cpu().numpy()
 
 
+class DeepKernelSVGP(hb.model.Model):
+    """Deep kernel learning (Wilson et al. 2016): GP regression with a Gaussian likelihood on the FEATURES h = net(x) of a
+    hb.nn.NeuralNet [D_in, *hidden, feature_dim], an RBF sparse GP with ARD lengthscales and M inducing points z in
+    feature space, trained full-batch on the collapsed bound:
+        m = DeepKernelSVGP(X=X, Y=Y, M=64, hidden=[32, 32], feature_dim=2);  trace = m.fit(200, lr=0.02)
+        mean, var = m.predict_y(Xnew)
+    X [N, D_in] and Y [N, P] are full-batch Data; activation: 'tanh', 'relu' or 'sigmoid' (after every layer but the
+    last); Z: initial inducing points [M, feature_dim] (None: the features of the rows i N / M of X under the initial
+    network, taken the first time they are needed; select_inducing() moves them to a greedy selection).  The weights start at N(0, 1 / fan-in) draws of numpy's global generator, the
+    biases at 0.  feature_dim <= 4 takes the column-strip form of the gradient pass (M % 16 == 0, M <= 512), larger
+    feature spaces its plain form.
+
+    The gradient of the bound with respect to the features comes from the gradient pass itself (hb_sgp_kgrad_x,
+    SparseGP.collapsed_bound_and_grad(x_grad=True)) and is chained through the network by the graph autodiff.  In a
+    float32 session the features are float32: the bound and its gradient are taken at those stored values, exact in
+    double like every float32 X, and the chain through the network is float32.
+    Not in scope: a classification variant (on elbo_and_grad(x_grad=True)), minibatches, a MAP GP-LVM."""
+
+    _ACTIVATIONS = dict(tanh=hb.nn.tanh, relu=hb.nn.relu, sigmoid=hb.nn.sigmoid)
+
+    def setUp(self, X, Y, M, hidden=(32,), feature_dim=2, activation="tanh", Z=None):
+        X, Y = np.asarray(X), np.asarray(Y)
+        if activation not in self._ACTIVATIONS:
+            raise ValueError("DeepKernelSVGP: activation must be one of %s, got %r" % (sorted(self._ACTIVATIONS), activation))
+        if X.ndim != 2 or Y.ndim != 2 or X.shape[0] != Y.shape[0]:
+            raise ValueError("DeepKernelSVGP: X [N, D_in] and Y [N, P] expected, got %s %s" % (X.shape, Y.shape))
+        N, F = X.shape[0], int(feature_dim)
+        nodes = [int(X.shape[1])] + [int(h) for h in hidden] + [F]
+        self.X = hb.param.Data(X)
+        self.Y = hb.param.Data(Y)
+        self.Hbar = hb.param.Data(np.zeros((N, F)))               # the cotangent dF/dfeatures, written on the device
+        self.net = hb.nn.NeuralNet(nodes, neuron_types=self._ACTIVATIONS[activation])
+        for i in range(len(nodes) - 1):
+            self.net[i].w = np.random.randn(nodes[i], nodes[i + 1]) / np.sqrt(nodes[i])
+            self.net[i].b = np.zeros((1, nodes[i + 1]))
+        self._z_given = Z is not None
+        Z = np.zeros((int(M), F)) if Z is None else np.asarray(Z, np.float64)
+        if Z.shape != (int(M), F):
+            raise ValueError("DeepKernelSVGP: Z must be [%d, %d], got %s" % (int(M), F, Z.shape))
+        self.gp = hb.gp.SparseGP(kern=hb.gp.kernels.UnitRBF(np.ones(F)), z=Z)
+        self.u = hb.variationals.Normal(shape=[Y.shape[1], int(M)], q_shape="fullrank")
+        self.k_var = hb.param.Variable([1], transform=hb.transforms.positive)
+        self.var = hb.param.Variable([1], transform=hb.transforms.positive)
+        self.residual = "diagonal"
+        self._plans = {}
+
+    def _net_variables(self):
+        """The network's Variables by the names the gradient uses: net0.w, net0.b, net1.w, .."""
+        net = _part(self, "net")
+        return {"net%d.%s" % (i, n): _part(net[i], n) for i in range(len(net.nodes) - 1) for n in ("w", "b")}
+
+    def _hyper_variables(self):
+        """The Variables collapsed_bound() depends on, by the names the gradient uses."""
+        gp = _part(self, "gp")
+        hv = dict(z=_part(gp, "z"), lengthscales=_part(_part(gp, "kern"), "lengthscales"), k_var=_part(self, "k_var"),
+                  var=_part(self, "var"))
+        hv.update(self._net_variables())
+        return hv
+
+    def _plan(self, what):
+        """The two plans over all rows, built once per parameter layout: 'forward' leaves H = net(X) [N, feature_dim] on
+        the device; 'backward' returns J^T Hbar for every network variable, the gradients of sum(net(X) * Hbar) taken by
+        the graph autodiff with Hbar a Data buffer."""
+        sess = self._session
+        key = (what, sess.layout_version)
+        if key not in self._plans:
+            Ht = _part(self, "net")(_part(self, "X").tensor())
+            if what == "forward":
+                outs = [Ht]
+            else:
+                leaves = [v._leaf for v in self._net_variables().values()]
+                outs = hb.graph.gradients(hb.graph.reduce_sum(Ht * _part(self, "Hbar").tensor()), leaves)
+            self._plans[key] = (sess.make_plan(outs), outs)
+        return self._plans[key]
+
+    def _features(self):
+        """H = net(X) at the current weights as a device tensor [N, feature_dim] of the session's dtype (the forward
+        plan's own buffer: valid until the plan runs again).  The first call without a given Z moves z to the features
+        of the rows i N / M."""
+        self.initialize()
+        plan, outs = self._plan("forward")
+        plan.run()
+        plan.check()
+        H = plan.buf(outs[0])
+        if not self._z_given:
+            self._z_given = True
+            zvar = _part(_part(self, "gp"), "z")
+            rows = (np.arange(zvar.shape[0]) * H.shape[0]) // zvar.shape[0]
+            self._session.write_raw(zvar, zvar.transform.backward(H[rows.tolist()].cpu().numpy().astype(np.float64)))
+        return H
+
+    def features(self, Xnew=None):
+        """net(X) (Xnew=None: the model's own inputs) or net(Xnew) as numpy [n, feature_dim], from one plan over all
+        rows."""
+        if Xnew is None:
+            return self._features().cpu().numpy()
+        self.initialize()
+        return self.run(_part(self, "net")(hb.graph.as_tensor(np.asarray(Xnew))))
+
+    def _closed_form_inputs(self):
+        """(features on the device, Y, noise variance, k_var) at the current parameters."""
+        H = self._features()
+        return H, _part(self, "Y"), _scalar(self, "var"), _scalar(self, "k_var")
+
+    def collapsed_bound(self):
+        """The ELBO at the optimal q(u) for the current parameters (SparseGP.collapsed_bound on the features)."""
+        H, Y, var, k_var = self._closed_form_inputs()
+        return _part(self, "gp").collapsed_bound(H, Y, var, k_var, residual=self.residual)
+
+    def bound_and_grad(self):
+        """(value, grad): the collapsed bound and its exact gradient with respect to the RAW parameters, grad = dict(z,
+        lengthscales, k_var, var, net0.w, net0.b, ..) in the shapes of the raw arrays, float64 numpy.  Four steps: the
+        forward plan leaves H = net(X) on the device; SparseGP.collapsed_bound_and_grad(H, Y, .., x_grad=True) (float64
+        arithmetic whatever the session's dtype) returns the value, the gradients of z, the lengthscales and the two
+        variances and Hbar = dF/dH [N, feature_dim]; Hbar goes into the model's Data buffer on the device (rounded to
+        the session's dtype); the backward plan returns J^T Hbar for the network's variables."""
+        H, Y, var, k_var = self._closed_form_inputs()
+        value, gr, xbar = _part(self, "gp")._collapsed_bound_and_grad(H, Y, var, k_var, self.residual, True)
+        sess = self._session
+        sess.data_buffer(_part(self, "Hbar")).copy_(xbar)
+        sess.torch.cuda.synchronize()
+        plan, outs = self._plan("backward")
+        plan.run()
+        plan.check()
+        cons = dict(z=gr["z"], lengthscales=gr["lengthscales"], k_var=gr["k_var"], var=gr["noise_var"])
+        for name, g in zip(self._net_variables(), outs):
+            cons[name] = plan.value(g)
+        return value, _chain_to_raw(self, cons)
+
+    def fit(self, steps, lr=0.01, train_z=True):
+        """Full-batch fit: `steps` Adam ASCENT steps on bound_and_grad in the raw parameters of the network, the
+        lengthscales, k_var, var and (train_z) z, on the host in float64 (the loop of SVGP.fit_hyper: a step after which
+        a factorisation fails raises graph.CholeskyError with the last good parameters restored), then fit_q().  Returns
+        the trace of bound values, steps + 1 entries: before the first step .. at the final parameters."""
+        self._features()                     # (a pending initial z is written before the loop reads it)
+        trace = _adam_ascent(self, self.bound_and_grad, steps, lr, train_z)
+        self.fit_q()
+        return trace
+
+    def fit_q(self):
+        """Set q(u) to its closed-form optimum at the current parameters (SparseGP.optimal_q on the features); returns
+        (m [P, M], S [M, M])."""
+        H, Y, var, k_var = self._closed_form_inputs()
+        m, S = _part(self, "gp").optimal_q(H, Y, var, k_var, q_shape="fullrank", residual=self.residual)
+        _write_q(self, m, S)
+        return m, S
+
+    def select_inducing(self, threshold=None):
+        """Move z to the features of the M rows greedy conditional-variance selection picks on the CURRENT features
+        (SparseGP.select_inducing); returns their row indices.  q(u) is not touched: call fit_q() afterwards."""
+        self._z_given = True
+        return _part(self, "gp").select_inducing(self._features(), threshold=threshold)
+
+    def _predict(self, Xnew, noise):
+        Xnew = np.asarray(Xnew)
+        q = _part(self, "u")
+        self._features()
+        with self.tf_mode():
+            mean, var = self.gp.predict_f(self.net(hb.graph.as_tensor(Xnew)), q, q_shape=self.residual)
+            mean, var = mean * tf.sqrt(self.k_var), var * self.k_var
+            if noise:
+                var = var + self.var
+        plan = self._session.make_plan([mean, var])
+        plan.run()
+        plan.check()
+        return tuple(plan.value(o) for o in plan.outputs)
+
+    def predict_f(self, Xnew):
+        """Closed-form posterior mean and variance of the latent f at Xnew [n, D_in], arrays [P, n]: the features of
+        Xnew, then SparseGP.predict_f at the model's q(u), in one plan (units as SVGP.predict_f)."""
+        return self._predict(Xnew, False)
+
+    def predict_y(self, Xnew):
+        """predict_f plus the Gaussian likelihood's variance."""
+        return self._predict(Xnew, True)
+
+
 class _SVGPNonConjugate(hb.model.Model):
     """What SVGPLik, SVGPMulticlass and SVGPHetero share: a likelihood (hb.likelihoods) over C = likelihood.num_latent
     latent functions of one SparseGP `gp`, a full-rank q(u) `u` of C blocks -- Normal(shape=[1, M]) or Normal(shape=[M],

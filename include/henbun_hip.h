@@ -77,7 +77,9 @@ extern "C" {
  * hb_lik_hetgauss_ws_elems and HB_LIK_HETGAUSS (heteroscedastic regression: the marginals of C full-rank latent functions
  * from one pass, the two-latent Gaussian likelihood); hb_sgp_psi_stats_f32 / _f64, hb_sgp_psi_stats_ws_elems,
  * hb_sgp_psi_predict_f32 / _f64 and hb_sgp_psi_predict_ws_elems (psi statistics: the closed-form routes under uncertain
- * inputs); hb_sgp_psi_grad_f32 / _f64 and hb_sgp_psi_grad_ws_elems (their gradients: the Bayesian GP-LVM). */
+ * inputs); hb_sgp_psi_grad_f32 / _f64 and hb_sgp_psi_grad_ws_elems (their gradients: the Bayesian GP-LVM);
+ * hb_sgp_kgrad_x_f32 / _f64 and hb_sgp_wkgrad_x_f32 / _f64 (hb_sgp_kgrad_* / hb_sgp_wkgrad_* with the input gradient
+ * xbar [N, d] as a third output: deep kernel learning). */
 #define HB_ABI_VERSION 2
 
 /* ---- runtime ----------------------------------------------------------- */
@@ -1290,6 +1292,32 @@ int hb_sgp_wkgrad_f32(int kind, const float* X, const double* w, const double* r
 int hb_sgp_wkgrad_f64(int kind, const double* X, const double* w, const double* r, const double* z, const double* ell, long dl,
                       const double* Q, const double* R, double* zbar, double* ellbar, long N, long M, long d, double* ws,
                       void* stream);
+/* hb_sgp_kgrad_* / hb_sgp_wkgrad_* with the INPUT gradient as a third output (same file, the template flag XG of the same
+ * kernels; not in the reference): the products E_ij (z_ik - x_jk) whose row sums are zbar have as their column sums
+ *   xbar[j, k] = +sum_i E_ij (z_ik - x_jk) / ell_k^2          [N, d], double, row-major, overwritten
+ * -- the complete derivative of the collapsed bound (of the ELBO at a fixed q(u) for the weighted form, where E already
+ * carries w_j and r_j) with respect to X at fixed weights Q, R, because k(x, x) == 1 and every dependence on X goes
+ * through K(z, X).  The arguments are those of the entry without _x with xbar after ellbar; the same checks, shapes,
+ * forms, diagnostic switch and workspace (hb_sgp_kgrad_ws_elems: xbar needs none).  zbar and ellbar are the bits of the
+ * entry without _x.  Strip form: per step of 32 columns the lanes' sums over their rows are folded over the four lane
+ * groups by two shuffles and over the 8 waves through LDS in wave order, and every column is written by the one
+ * workgroup that owns its step -- no atomics, no fold launch; the order depends on M alone, so two calls return the same
+ * bits and the bits of a column do not depend on N or on the other columns.  LDS: 8 x 32 x d doubles more, 158 208 B of
+ * the CU's 160 KB at M = 512, d = 4, weighted.  Plain form: per column and dimension a sum per thread over its strided
+ * rows, per wave by shuffles, over the 4 waves in wave order.  sum_j xbar_j = -zbar_streamed summed over i (translation
+ * invariance). */
+int hb_sgp_kgrad_x_f32(int kind, const float* X, const float* Y, const double* z, const double* ell, long dl, const double* Q,
+                       const double* R, double* zbar, double* ellbar, double* xbar, long N, long M, long d, long P, double* ws,
+                       void* stream);
+int hb_sgp_kgrad_x_f64(int kind, const double* X, const double* Y, const double* z, const double* ell, long dl, const double* Q,
+                       const double* R, double* zbar, double* ellbar, double* xbar, long N, long M, long d, long P, double* ws,
+                       void* stream);
+int hb_sgp_wkgrad_x_f32(int kind, const float* X, const double* w, const double* r, const double* z, const double* ell, long dl,
+                        const double* Q, const double* R, double* zbar, double* ellbar, double* xbar, long N, long M, long d,
+                        double* ws, void* stream);
+int hb_sgp_wkgrad_x_f64(int kind, const double* X, const double* w, const double* r, const double* z, const double* ell, long dl,
+                        const double* Q, const double* R, double* zbar, double* ellbar, double* xbar, long N, long M, long d,
+                        double* ws, void* stream);
 /* VJP given fbar [E,P,n]:
  *   Abar = u^T fbar + A diag(c),  c = -eps sign(v)/sqrt|v| * sum_p fbar_p
  *   Kbar = W^T Abar            [E,M,n]  (scratch output, kept for Lbar)
